@@ -25,10 +25,19 @@ torch.distributed.run BEFORE anything touches a GPU; under the driver's own torc
 workers are already there.  One process per GPU, independent proofs sharded across ranks, no data-path
 collective: "scaling": "weak".
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (the MSM bucket accumulation), timed
-live with HIP events on the stream the kernel runs on; `cpu_baseline` times ONE full proof of the same
-workload by the CPU oracle (oracle/fastplonk.py + oracle/coracle.cpp: a port, OpenMP over the host cores)
-and checks that its bytes equal the GPU proof's.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times `--steps` proofs and reports the headline
+(`value`, `ms_per_step`, `config`, `witness`) and nothing else.  `--full` adds everything that takes work of its own
+after the timed region, as the line carried it before the option existed: HIP events on the dominant kernel inside the
+timed region and a further profiling pass (`roofline`, `int_alu`, `commitments`, `kernels`, `rounds_ms`, `gpu_active`),
+the `latency` legs (unless --no-latency), the host verifier (`verify`), the single-proof sharded leg of `--shard both`
+on N > 1 GPUs, and `cpu_baseline` (unless --no-cpu-baseline).  `roofline` is for the dominant kernel (the MSM bucket
+accumulation), timed live with HIP events on the stream the kernel runs on; `cpu_baseline` times ONE full proof of the
+same workload by the CPU oracle (oracle/fastplonk.py + oracle/coracle.cpp: a port, OpenMP over the host cores) and
+checks that its bytes equal the GPU proof's.
+
+`--dump-outputs DIR` writes what the caller of the timed path receives from its last step, the serialised proof, as
+DIR/proof.npy (float32, one element per byte).  The inputs (SRS trapdoor, circuit, witnesses, blinders) are fixed
+seeds, so two builds run with the same arguments can be compared byte for byte.
 """
 import argparse
 import json
@@ -281,7 +290,12 @@ def main():
     ap.add_argument("--shard", default="both", choices=["proofs", "proof", "both"],
                     help="N > 1: 'proofs' = independent proofs sharded across the GPUs (weak scaling, the headline); "
                          "'proof' = ONE proof's MSMs and 4n-coset work sharded across the GPUs (strong scaling, value = "
-                         "1 / latency); 'both' (default) = the headline plus the single-proof leg in the same line")
+                         "1 / latency); 'both' (default) = the headline plus, with --full, the single-proof leg in the same line")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the per-kernel figures (roofline, int_alu, kernels, rounds_ms, "
+                         "gpu_active), the latency legs, the verifier, the sharded single-proof leg and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's proof to DIR/proof.npy (float32, one element per byte)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_workers(args, sys.argv[1:]))
@@ -316,7 +330,8 @@ def main():
     tau = 0x5EED5EED1234567890ABCDEF % fld["r"]
     ctx.srs_generate(tau, n + 8)
 
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
+    shard_leg = world > 1 and (args.shard == "proof" or (args.shard == "both" and args.full))
     if args.workload == "withdraw" and log_n not in WITHDRAW_SHAPES:
         sys.stderr.write("bench.py: no withdraw shape fills n = 2^%d (have %s); using --workload synthetic\n"
                          % (log_n, sorted(WITHDRAW_SHAPES)))
@@ -325,7 +340,7 @@ def main():
     wl = build(z, torch, ctx, dev, fld, args, log_n)
     evals, gates, table, host_w, preps, pis, pi_map0 = (wl[k] for k in ("evals", "gates", "table", "host_w", "preps", "pis", "pi_map0"))
     commits = wl["commits"]
-    evals_keep = evals if (world > 1 and args.shard != "proofs") else None
+    evals_keep = evals if shard_leg else None
     if not want_cpu:
         wl["evals"] = None
         del evals
@@ -367,30 +382,32 @@ def main():
     for _ in range(args.warmup):
         proof = one_proof()
     barrier()
-    # The dominant kernel is timed live over the timed region with HIP events on the stream it runs on (profile level 2:
-    # one event pair per MSM).  Every other scope (~80 more event records per proof, each a few microseconds of stream
-    # time) is measured in a separate, untimed pass of the same chained workload right after.
-    ctx.profile_enable(2 if os.environ.get("ZKT_BENCH_NO_EVENTS") is None else 0)
+    # --full: the dominant kernel is timed live over the timed region with HIP events on the stream it runs on (profile
+    # level 2: one event pair per MSM).  Every other scope (~80 more event records per proof, each a few microseconds of
+    # stream time) is measured in a separate, untimed pass of the same chained workload right after.
+    ctx.profile_enable(2 if args.full and os.environ.get("ZKT_BENCH_NO_EVENTS") is None else 0)
     t_start = time.perf_counter()
     for _ in range(args.steps):
         proof = one_proof()
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t_start
     barrier()
-    prof_acc = ctx.profile_get("msm_accumulate")
-    prof_acc_launches = ctx.profile_get("msm_accumulate#launches")[0]
-    prof_idle = ctx.profile_get("host_wait")
-    scope_names = ("msm_accumulate", "msm_main", "msm_lag_accumulate", "msm_lag_main", "msm_fold", "msm_tail", "ntt_%d" % log_n, "ntt_%d" % (log_n + 2), "quotient",
-                   "round1", "round2", "round3", "round4", "round5")
-    prof_steps = max(2, min(args.steps, 6))
-    ctx.profile_enable(1)
-    for _ in range(prof_steps):
-        one_proof()
-    torch.cuda.synchronize(dev)
-    prof = {k: ctx.profile_get(k) for k in scope_names}
-    ctx.profile_enable(0)
-    if prof_acc[0]:
-        prof["msm_accumulate"] = prof_acc          # the roofline's kernel time is the timed region's own
+    last_proof = proof
+    if args.full:
+        prof_acc = ctx.profile_get("msm_accumulate")
+        prof_acc_launches = ctx.profile_get("msm_accumulate#launches")[0]
+        prof_idle = ctx.profile_get("host_wait")
+        scope_names = ("msm_accumulate", "msm_main", "msm_lag_accumulate", "msm_lag_main", "msm_fold", "msm_tail", "ntt_%d" % log_n, "ntt_%d" % (log_n + 2), "quotient",
+                       "round1", "round2", "round3", "round4", "round5")
+        prof_steps = max(2, min(args.steps, 6))
+        ctx.profile_enable(1)
+        for _ in range(prof_steps):
+            one_proof()
+        torch.cuda.synchronize(dev)
+        prof = {k: ctx.profile_get(k) for k in scope_names}
+        ctx.profile_enable(0)
+        if prof_acc[0]:
+            prof["msm_accumulate"] = prof_acc          # the roofline's kernel time is the timed region's own
     red_dev = dev if (dist is None or dist.get_backend() == "nccl") else None
     elapsed = par.max_over_ranks(dist, elapsed, red_dev)   # whole-job time = slowest rank
     assert proof is not None and len(proof) == (802 if args.curve == "bn254" else 1010)
@@ -401,7 +418,7 @@ def main():
 
     # ---- the other end of the range, same line: single proofs nobody announced -------------------------------------
     latency = None
-    if rank == 0 and not args.no_latency:
+    if args.full and rank == 0 and not args.no_latency:
         ctx.prove_prepared(preps[0], transcript())      # drains the last announcement
 
         def timed(fn, reps=3):
@@ -478,7 +495,7 @@ def main():
     # ---- the verifier the reference's caller runs after every proof (bin/src/main.rs:298; proof.rs:285-503): host C++,
     # ---- pairings included (zkt_verify), on the proof just made -----------------------------------------------------
     verify = None
-    if rank == 0:
+    if args.full and rank == 0:
         from zkt_plonk_amd import _lib as zl
         pi_pos, pi_vals, _bl = pis[0]
         vproof = ctx.prove_prepared(preps[0], transcript())
@@ -514,6 +531,77 @@ def main():
                         "multi-scalar multiplications, one folded product of two optimal-ate pairings; one host core, "
                         "median of 7"}
 
+    lag_info = ctx.lagrange_info()
+    out = {
+        "metric": "proofs/sec (withdraw, n=2^%d)" % log_n, "value": round(value, 4), "unit": "proofs/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32 limbs (256-bit Montgomery)",
+        "data": "synthetic",
+        "config": {"workload": wl["describe"], "parallelism": "proofs sharded across %d GPU(s)" % world,
+                   "chained": bool(chain), "distinct_witnesses": 2, "witness_on_device": True, "table_cached": True,
+                   "lagrange_commits": lag_info["log_n"] == log_n,
+                   "proof_bytes": len(proof), "setup_s": round(setup_s, 1)},
+    }
+    if args.full:
+        out.update(kernel_figures(ctx, args, fld, prof, prof_steps, prof_acc_launches, prof_idle, ms_per_step,
+                                  lag_info))
+    if wl.get("witness") is not None:
+        out["witness"] = wl["witness"]
+        out["poseidon_witness_ms"] = wl["witness"]["device_ms"]
+    if latency is not None:
+        out["latency"] = latency
+        # the stricter regimes as first-class figures beside `value` (proofs/s of back-to-back single proofs)
+        out["value_unchained"] = round(1e3 / latency["unchained_single_proof_ms"], 4)
+        out["value_cold"] = round(1e3 / latency["cold_single_proof_ms"], 4)
+    if inflight is not None:
+        out["inflight"] = inflight
+    if verify is not None:
+        out["verify_ms"] = verify["ms"]
+        out["verify"] = verify
+
+    # ---- ONE proof across all the GPUs (SURVEY.md 8e / BASELINE.json configs[4]) -------------------------------------
+    if shard_leg:
+        refs = [ctx.prove_prepared(preps[k], transcript()) for k in range(2)]        # this GPU alone, for the bytes
+        progress = {"phase": "start"}
+        guard = leg_watchdog(rank, out, float(os.environ.get("ZKT_SHARD_LEG_TIMEOUT", "180")), progress)
+        try:
+            sh = sharded_leg(z, par, dist, dev, args, fld, tau, evals_keep, vk, host_w, table, pis, gates, refs, barrier,
+                             progress)
+        except Exception as e:      # reported, never fatal for the headline
+            sh = {"error": "%s: %s" % (type(e).__name__, e)}
+        guard.cancel()
+        leg_proof = sh.pop("last_proof", None)
+        out["single_proof_sharded"] = sh
+        if args.shard == "proof" and "ms_per_proof" in sh:
+            last_proof = leg_proof                      # the timed path is the sharded one
+            out.update(value=round(1e3 / sh["ms_per_proof"], 4), ms_per_step=sh["ms_per_proof"], scaling="strong")
+            out["config"]["parallelism"] = "one proof sharded across %d GPU(s)" % world
+
+    if want_cpu:
+        pi_pos, pi_vals, blinders = pis[0]
+        gpu_proof = ctx.prove_prepared(preps[0], transcript())
+        out["cpu_baseline"] = cpu_baseline(ctx, args.curve, log_n, evals, host_w[0], table, pi_map0, blinders, vk, gpu_proof,
+                                           wl.get("oracle_twin"))
+    if rank == 0:
+        if args.dump_outputs:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "proof.npy"), np.frombuffer(last_proof, dtype=np.uint8).astype(np.float32))
+        print(json.dumps(out), flush=True)
+    ctx.close()
+    if dist is not None:
+        dist.destroy_process_group()
+    # a sharded proof whose bytes differ from the single-GPU proof's is a correctness failure of the multi-GPU transport
+    # (the RCCL device path cannot be rehearsed on one-GPU boxes): the line above is printed, the run fails
+    sh = out.get("single_proof_sharded")
+    if isinstance(sh, dict) and sh.get("proof_bytes_equal_single_gpu") is False:
+        sys.stderr.write("bench.py rank %d: sharded proof bytes differ from the single-GPU proof\n" % rank)
+        sys.exit(4)
+
+
+def kernel_figures(ctx, args, fld, prof, prof_steps, prof_acc_launches, prof_idle, ms_per_step, lag_info):
+    """--full: the roofline of the dominant kernel, the integer-ALU figures, the commitments, the transforms and rounds
+    of the profiling pass, and the main stream's idle time inside the timed region (entries of the result line)."""
+    log_n, n, L = args.log_n, 1 << args.log_n, fld["fq_limbs"]
     # ---- roofline of the dominant kernel (MSM bucket accumulation), live HIP-event timing ----
     acc_calls, acc_ms = prof["msm_accumulate"]
     msm_points = n + 3                                              # typical MSM length of the prover
@@ -570,7 +658,6 @@ def main():
     }
     lag_calls, lag_ms = prof["msm_lag_main"]
     lag_acc_calls, lag_acc_ms = prof["msm_lag_accumulate"]
-    lag_info = ctx.lagrange_info()
     per_proof = lambda calls: round(calls / float(prof_steps), 2)
     commitments = {
         "dense_msms_per_proof": per_proof(msm_calls), "lagrange_msms_per_proof": per_proof(lag_calls),
@@ -603,16 +690,7 @@ def main():
         qavg = qms / qc * 1e-3
         ntt["quotient"] = {"avg_ms": round(qavg * 1e3, 4), "GB/s": round(23 * 32 * 4 * n / qavg / 1e9, 2),
                            "frac_hbm": round(23 * 32 * 4 * n / qavg / 1e9 / HBM_PEAK_GBS, 5)}
-
     out = {
-        "metric": "proofs/sec (withdraw, n=2^%d)" % log_n, "value": round(value, 4), "unit": "proofs/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32 limbs (256-bit Montgomery)",
-        "data": "synthetic",
-        "config": {"workload": wl["describe"], "parallelism": "proofs sharded across %d GPU(s)" % world,
-                   "chained": bool(chain), "distinct_witnesses": 2, "witness_on_device": True, "table_cached": True,
-                   "lagrange_commits": lag_info["log_n"] == log_n,
-                   "proof_bytes": len(proof), "setup_s": round(setup_s, 1)},
         "roofline": roofline, "int_alu": int_alu, "commitments": commitments, "kernels": ntt,
         "rounds_ms": {k: round(prof[k][1] / prof[k][0], 3) for k in ("round1", "round2", "round3", "round4", "round5") if prof[k][0]},
         "kernels_measured": "msm_accumulate: HIP events inside the timed region; the other scopes and rounds_ms: %d further "
@@ -629,52 +707,7 @@ def main():
                   "busy = wall clock per proof minus that.  The bucket-reduction tails run on a side stream during part of "
                   "the idle time",
         }
-    if wl.get("witness") is not None:
-        out["witness"] = wl["witness"]
-        out["poseidon_witness_ms"] = wl["witness"]["device_ms"]
-    if latency is not None:
-        out["latency"] = latency
-        # the stricter regimes as first-class figures beside `value` (proofs/s of back-to-back single proofs)
-        out["value_unchained"] = round(1e3 / latency["unchained_single_proof_ms"], 4)
-        out["value_cold"] = round(1e3 / latency["cold_single_proof_ms"], 4)
-    if inflight is not None:
-        out["inflight"] = inflight
-    if verify is not None:
-        out["verify_ms"] = verify["ms"]
-        out["verify"] = verify
-
-    # ---- ONE proof across all the GPUs (SURVEY.md 8e / BASELINE.json configs[4]) -------------------------------------
-    if world > 1 and args.shard != "proofs":
-        refs = [ctx.prove_prepared(preps[k], transcript()) for k in range(2)]        # this GPU alone, for the bytes
-        progress = {"phase": "start"}
-        guard = leg_watchdog(rank, out, float(os.environ.get("ZKT_SHARD_LEG_TIMEOUT", "180")), progress)
-        try:
-            sh = sharded_leg(z, par, dist, dev, args, fld, tau, evals_keep, vk, host_w, table, pis, gates, refs, barrier,
-                             progress)
-        except Exception as e:      # reported, never fatal for the headline
-            sh = {"error": "%s: %s" % (type(e).__name__, e)}
-        guard.cancel()
-        out["single_proof_sharded"] = sh
-        if args.shard == "proof" and "ms_per_proof" in sh:
-            out.update(value=round(1e3 / sh["ms_per_proof"], 4), ms_per_step=sh["ms_per_proof"], scaling="strong")
-            out["config"]["parallelism"] = "one proof sharded across %d GPU(s)" % world
-
-    if want_cpu:
-        pi_pos, pi_vals, blinders = pis[0]
-        gpu_proof = ctx.prove_prepared(preps[0], transcript())
-        out["cpu_baseline"] = cpu_baseline(ctx, args.curve, log_n, evals, host_w[0], table, pi_map0, blinders, vk, gpu_proof,
-                                           wl.get("oracle_twin"))
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    ctx.close()
-    if dist is not None:
-        dist.destroy_process_group()
-    # a sharded proof whose bytes differ from the single-GPU proof's is a correctness failure of the multi-GPU transport
-    # (the RCCL device path cannot be rehearsed on one-GPU boxes): the line above is printed, the run fails
-    sh = out.get("single_proof_sharded")
-    if isinstance(sh, dict) and sh.get("proof_bytes_equal_single_gpu") is False:
-        sys.stderr.write("bench.py rank %d: sharded proof bytes differ from the single-GPU proof\n" % rank)
-        sys.exit(4)
+    return out
 
 
 def leg_watchdog(rank, out, seconds, progress):
@@ -769,7 +802,7 @@ def sharded_leg(z, par, dist, dev, args, fld, tau, evals, vk, host_w, table, pis
             "proof_bytes_equal_single_gpu": bool(all_ok), "srs_points_per_gpu": hi - lo,
             "msm_window_bits": info["window_bits"], "coset_points_per_gpu": 4 * n // world,
             "collectives_per_proof": (calls1 - calls0) / args.steps,
-            "bytes_sent_per_gpu_per_proof": (bytes1 - bytes0) // args.steps, "backend": dist.get_backend()}
+            "bytes_sent_per_gpu_per_proof": (bytes1 - bytes0) // args.steps, "backend": dist.get_backend(), "last_proof": pr}
 
 
 def csrc_digest():

@@ -1,7 +1,7 @@
 # usage: [BENCH_ARGS="--curve bls12_381 --log-n 22"] bash tools/ab_env.sh <tag> "VAR=val" "VAR2=val2 VAR3=val3" ...
 # each argument = one bench run with that environment ("X=1" = default); knobs are honoured by _ab/libzkt_exp.so only
 TAG=$1; shift
-B="${BENCH_ARGS:-} --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline --no-latency"
+B="${BENCH_ARGS:-} --steps ${STEPS:-20} --warmup 3 --full --no-cpu-baseline --no-latency"
 i=0
 for e in "$@"; do
   i=$((i+1))

@@ -1,7 +1,7 @@
 # A/B of one source change on ONE box: _ab/libzkt_exp.so (built from the previous commit: "old") against the main library ("new"),
 # alternating.  usage (GPU box): bash tools/ab_ow.sh ["<bench args>" ...]
 set -e
-B="--steps ${STEPS:-30} --warmup 3 --no-cpu-baseline --no-latency"
+B="--steps ${STEPS:-30} --warmup 3 --full --no-cpu-baseline --no-latency"
 [ $# -eq 0 ] && set -- "--log-n 20"
 for a in "$@"; do
   for i in 1 2 3; do

@@ -13,8 +13,8 @@ d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print(sys.argv[2], d["value"], d["ms_per_step"], d["roofline"]["avg_launch_ms"], d["rounds_ms"], (d.get("witness") or {}).get("device_ms"), d.get("latency"), d.get("verify_ms"))
 PY
 }
-run bn254_2_14 --log-n 14 --steps 60 --warmup 3 --inflight 2 &&
-run bn254_2_18 --log-n 18 --steps 40 --warmup 3 --inflight 3 &&
-run bn254_2_19 --log-n 19 --steps 20 --warmup 3 &&
-run bls12_381_2_20 --curve bls12_381 --log-n 20 --steps 5 --warmup 1 --no-cpu-baseline &&
-run bls12_381_2_22 --curve bls12_381 --log-n 22 --steps 3 --warmup 1 --no-cpu-baseline
+run bn254_2_14 --log-n 14 --full --steps 60 --warmup 3 --inflight 2 &&
+run bn254_2_18 --log-n 18 --full --steps 40 --warmup 3 --inflight 3 &&
+run bn254_2_19 --log-n 19 --full --steps 20 --warmup 3 &&
+run bls12_381_2_20 --curve bls12_381 --log-n 20 --full --steps 5 --warmup 1 --no-cpu-baseline &&
+run bls12_381_2_22 --curve bls12_381 --log-n 22 --full --steps 3 --warmup 1 --no-cpu-baseline

@@ -6,7 +6,7 @@ OUT=gpurun_out/final_$TAG
 mkdir -p $OUT
 step() { echo "[$(date +%T)] $*" | tee -a $OUT/steps.log; }
 step "bench (default: BN254 2^20 withdraw, with the CPU baseline)"
-python bench.py --steps 20 --warmup 3 > $OUT/bench_${TAG}.json 2> $OUT/bench_${TAG}.err || { tail -5 $OUT/bench_${TAG}.err; exit 1; }
+python bench.py --full --steps 20 --warmup 3 > $OUT/bench_${TAG}.json 2> $OUT/bench_${TAG}.err || { tail -5 $OUT/bench_${TAG}.err; exit 1; }
 step "rocprof kernel stats, BN254 2^20"
 bash tools/prof_stats.sh ${TAG}_bn254_2_20 && mv gpurun_out/${TAG}_bn254_2_20_* $OUT/ || exit 1
 step "PMC traffic, BN254 2^20"

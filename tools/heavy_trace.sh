@@ -2,6 +2,7 @@
 # which MSMs of a proof meet crowded buckets: durations of k_msm_heavy in launch order.  usage: BENCH_ARGS=... bash tools/heavy_trace.sh
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
+BENCH_ARGS="$BENCH_ARGS --full"   # the profiling pass and the verifier's proof as well
 rm -rf $R/gpurun_out/prof_heavy
 rocprofv3 --kernel-trace --output-format csv -d $R/gpurun_out/prof_heavy -- python3 $R/bench.py $BENCH_ARGS --steps 2 --warmup 1 --no-cpu-baseline --no-latency > /dev/null 2>&1
 cd $R

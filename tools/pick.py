@@ -1,4 +1,4 @@
-"""Prints selected (dotted) keys of the last JSON line on stdin.  usage: python bench.py ... | python tools/pick.py value roofline.avg_launch_ms"""
+"""Prints selected (dotted) keys of the last JSON line on stdin.  usage: python bench.py --full ... | python tools/pick.py value roofline.avg_launch_ms"""
 import json
 import sys
 

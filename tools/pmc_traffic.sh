@@ -5,6 +5,7 @@
 set -e
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
+BENCH_ARGS="$BENCH_ARGS --full"   # the same proofs per run as the committed passes: profiling pass and verifier included
 for ctr in FETCH_SIZE WRITE_SIZE; do
   rm -rf $R/gpurun_out/pmc_$ctr
   rocprofv3 --pmc $ctr --output-format csv -d $R/gpurun_out/pmc_$ctr -- python3 $R/bench.py $BENCH_ARGS --steps 1 --warmup 0 --no-cpu-baseline --no-latency > /dev/null 2>&1

@@ -4,6 +4,7 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 TAG=$1; shift
+BENCH_ARGS="$BENCH_ARGS --full"   # the profiling pass (timeline.py's count) and roofline.avg_launch_ms (prof_reconcile.py)
 for kv in "$@"; do export "$kv"; done
 rm -rf $R/gpurun_out/prof_$TAG
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_$TAG -- python3 $R/bench.py $BENCH_ARGS --steps 5 --warmup 1 --no-cpu-baseline --no-latency > $R/gpurun_out/${TAG}_profiled_run.json 2> $R/gpurun_out/${TAG}_profiled_run.err
