@@ -198,6 +198,30 @@ int zkt_msm_enqueue_dev(zkt_ctx* ctx, const void* d_scalars, size_t len, size_t 
 /* Window size c, number of windows and loaded powers of the current SRS (0s when none). */
 int zkt_msm_info(zkt_ctx* ctx, int* window_bits, int* windows, size_t* srs_count);
 
+/* VariableBaseMSM::multi_scalar_mul (ark-ec 0.3) on the device for ARBITRARY affine bases, the seam of
+ * HomomorphicCommitment::multi_scalar_mul (commitment.rs:31-45): sum_i scalars[i] * bases[i].
+ * bases: n x (x, y) Montgomery limbs in arkworks' layout (8 / 12 u64 per point), (0,0) = identity.
+ * scalars: n x 4 u64, Montgomery (scalars_montgomery = 1) or canonical 256-bit integers (0).  Canonical scalars are used
+ * as full integers: every bit counts, values >= r included (for a point of the prime-order subgroup the result is then
+ * sum (s_i mod r) P_i).  Bases may repeat, appear negated, be the identity or carry a zero scalar.  Bases are NOT checked
+ * for being on the curve or in the subgroup (as arkworks does not); an invalid point gives an unspecified point, never a
+ * fault.  Result: affine, host memory, (0,0) and *out_is_infinity = 1 for the identity (out_is_infinity may be NULL).
+ * n = 0 -> the identity; 1 <= n <= ZKT_MSM_BASES_MAX on either curve; a larger n -> ZKT_ERR_INVALID_ARGUMENT, a failed
+ * allocation -> ZKT_ERR_HIP.  Needs no SRS: the call works on any context (with or without a key, forked, between proofs)
+ * and leaves the loaded SRS, Lagrange-basis table, circuit and the prover's MSM buffers untouched; its scratch memory is
+ * its own, allocated on first use, grown as needed and freed by zkt_ctx_destroy.  A proof announced with
+ * zkt_prove_set_next keeps its early work: the call only adds its own launches behind it on the context's stream, and that
+ * proof's bytes do not change.  Local even on a context with a communicator (no collective).  Synchronises the stream.
+ * _dev: bases and scalars already in HBM, same layouts; the result still goes to host memory. */
+#define ZKT_MSM_BASES_MAX ((size_t)1 << 22)
+int zkt_msm_g1_bases(zkt_ctx* ctx, const uint64_t* bases_xy_mont, const uint64_t* scalars, size_t n,
+                     int scalars_montgomery, uint64_t* out_xy_mont, int* out_is_infinity);
+int zkt_msm_g1_bases_dev(zkt_ctx* ctx, const void* d_bases_xy_mont, const void* d_scalars, size_t n,
+                         int scalars_montgomery, uint64_t* out_xy_mont_host, int* out_is_infinity);
+/* Digit width c and number of windows zkt_msm_g1_bases uses for n points (0s for n = 0); n > ZKT_MSM_BASES_MAX ->
+ * ZKT_ERR_INVALID_ARGUMENT. */
+int zkt_msm_bases_info(zkt_ctx* ctx, size_t n, int scalars_montgomery, int* window_bits, int* windows);
+
 /* ---- Commitments of evaluation vectors (Lagrange-basis key) ------------------------------------------
  * The reference commits to t, h1, h2 and z2 through their coefficients (prove.rs:145-180,225-251: poly_from_evals,
  * add_blinders_to_poly, PC::commit -- one dense MSM each).  As EVALUATION vectors they are piecewise constant (table

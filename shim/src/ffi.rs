@@ -82,6 +82,10 @@ extern "C" {
     pub fn zkt_prove_set_next(ctx: *mut ZktCtx, next: *const ZktProveInputs) -> c_int;
     pub fn zkt_g1_msm_host(curve_id: c_int, points_xy_mont: *const u64, scalars: *const u64, n: usize, scalars_montgomery: c_int,
                            out_xy_mont: *mut u64, out_is_infinity: *mut c_int) -> c_int;
+    pub fn zkt_msm_g1_bases(ctx: *mut ZktCtx, bases_xy_mont: *const u64, scalars: *const u64, n: usize,
+                            scalars_montgomery: c_int, out_xy_mont: *mut u64, out_is_infinity: *mut c_int) -> c_int;
+    pub fn zkt_msm_g1_bases_dev(ctx: *mut ZktCtx, d_bases_xy_mont: *const c_void, d_scalars: *const c_void, n: usize,
+                                scalars_montgomery: c_int, out_xy_mont_host: *mut u64, out_is_infinity: *mut c_int) -> c_int;
     pub fn zkt_verify(curve_id: c_int, inputs: *const ZktVerifyInputs, transcript: *mut c_void, h_g2_mont: *const u64,
                       beta_h_g2_mont: *const u64, accepted: *mut c_int) -> c_int;
     pub fn zkt_verify_batch(curve_id: c_int, inputs: *const ZktVerifyInputs, transcripts: *const *mut c_void, count: usize,

@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.environ.get("ZKT_LIB_PATH") or os.path.join(_HERE, "libzkt_plonk_hip.so")
 _HEADER = os.path.join(_HERE, "..", "include", "zkt_plonk.h")
 
+MSM_BASES_MAX = 1 << 22   # ZKT_MSM_BASES_MAX: most points zkt_msm_g1_bases takes
 CURVE_BN254 = 0
 CURVE_BLS12_381 = 1
 _CURVES = {"bn254": 0, "bls12_381": 1, "bls12-381": 1, 0: 0, 1: 1}
@@ -112,6 +113,10 @@ def _bind_optional(L):
         L.zkt_msm_g1_dev.argtypes = [vp, vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, vp]
         L.zkt_msm_enqueue_dev.argtypes = [vp, vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int]
         L.zkt_msm_info.argtypes = [vp, ip, ip, ctypes.POINTER(ctypes.c_size_t)]
+    if hasattr(L, "zkt_msm_g1_bases"):
+        L.zkt_msm_g1_bases.argtypes = [vp, u64p, u64p, ctypes.c_size_t, ctypes.c_int, u64p, ip]
+        L.zkt_msm_g1_bases_dev.argtypes = [vp, vp, vp, ctypes.c_size_t, ctypes.c_int, u64p, ip]
+        L.zkt_msm_bases_info.argtypes = [vp, ctypes.c_size_t, ctypes.c_int, ip, ip]
 
 
 ALL_GATHER_CB = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
@@ -768,6 +773,35 @@ class Context:
 
     def msm_enqueue_dev(self, d_scalars: int, n: int, base_offset: int = 0, montgomery: bool = True):
         self.check(self._L.zkt_msm_enqueue_dev(self._h, ctypes.c_void_p(d_scalars), n, base_offset, int(montgomery)))
+
+    def msm_bases(self, bases: np.ndarray, scalars: np.ndarray, montgomery: bool = True):
+        """zkt_msm_g1_bases: sum scalars[i] * bases[i] over the caller's points (no SRS needed) ->
+        (xy Montgomery limbs (2*fq_limbs,), is_infinity)"""
+        bases = np.ascontiguousarray(bases, dtype=np.uint64).reshape(-1, 2 * self.fq_limbs)
+        scalars = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+        if bases.shape[0] != scalars.shape[0]:
+            raise ValueError("msm_bases: %d bases, %d scalars" % (bases.shape[0], scalars.shape[0]))
+        n = bases.shape[0]
+        out = np.zeros(2 * self.fq_limbs, dtype=np.uint64)
+        inf = ctypes.c_int(0)
+        self.check(self._L.zkt_msm_g1_bases(self._h, u64p(bases) if n else None, u64p(scalars) if n else None, n,
+                                            int(montgomery), u64p(out), ctypes.byref(inf)))
+        return out, bool(inf.value)
+
+    def msm_bases_dev(self, d_bases: int, d_scalars: int, n: int, montgomery: bool = True):
+        """zkt_msm_g1_bases_dev: bases (n x 2*fq_limbs words) and scalars (n x 4 words) already in HBM ->
+        (xy Montgomery limbs, is_infinity)"""
+        out = np.zeros(2 * self.fq_limbs, dtype=np.uint64)
+        inf = ctypes.c_int(0)
+        self.check(self._L.zkt_msm_g1_bases_dev(self._h, ctypes.c_void_p(d_bases), ctypes.c_void_p(d_scalars), n,
+                                                int(montgomery), u64p(out), ctypes.byref(inf)))
+        return out, bool(inf.value)
+
+    def msm_bases_info(self, n: int, montgomery: bool = True):
+        """-> dict(window_bits, windows) that zkt_msm_g1_bases uses for n points"""
+        c, w = ctypes.c_int(0), ctypes.c_int(0)
+        self.check(self._L.zkt_msm_bases_info(self._h, n, int(montgomery), ctypes.byref(c), ctypes.byref(w)))
+        return dict(window_bits=c.value, windows=w.value)
 
     def msm_info(self):
         c, w, n = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_size_t(0)

@@ -18,6 +18,7 @@
 namespace zkt {
 
 struct MsmState;      // msm.hip
+struct MsmBasesState; // msm.hip (zkt_msm_g1_bases)
 struct CircuitState;  // prover.hip
 
 }  // namespace zkt
@@ -60,6 +61,7 @@ struct zkt_ctx {
     bool sharded() const { return comm.vt.world > 1; }
 
     std::shared_ptr<zkt::MsmState> msm;
+    std::shared_ptr<zkt::MsmBasesState> msmb;   // zkt_msm_g1_bases scratch (separate from the prover's MSM state)
     uint64_t msm_epoch = 0;   // bumped by every MSM enqueue and SRS (re)load: work issued ahead of time is tied to it
     uint64_t srs_generation = 0;   // bumped by every SRS (re)load: cached commitments are tied to the key they were made under
     // zkt_ctx_fork: forks share this context's read-only tables.  A parent with live forks refuses to reload them; when it

@@ -286,7 +286,9 @@ ZKT_D uint32_t block_excl_scan_256(uint32_t mine, uint32_t* wsum) {
     return before + incl - (in ? mine : 0u);
 }
 
-template <class C, int DIG>
+// VB (variable bases, zkt_msm_g1_bases): every window has buckets of its own, key = w * bt.vb_stride + d, and Montgomery
+// scalars leave Montgomery form here (the bases carry no R^-1).
+template <class C, int DIG, bool VB = false>
 __global__ __launch_bounds__(1024) void k_msm_bin_count(MsmBatch bt, int mont,
                                                         MsmWindows win, uint32_t per_block, uint32_t nb1, uint32_t lb,
                                                         uint32_t* counts) {
@@ -314,9 +316,13 @@ __global__ __launch_bounds__(1024) void k_msm_bin_count(MsmBatch bt, int mont,
     for (int t = 0; t < 2; ++t) {
         if (!have[t]) continue;
         Fe<R> s = sc[t];
-        if (!mont) s = fe_to_mont<R>(s);   // the table holds R^-1 P_i: digits are those of s R
-        msm_for_each_digit_sel<R, DIG>(s, win, [&](int, uint32_t d, uint32_t) {
-            if (d) atomicAdd(&hist[d >> lb], 1u);
+        if (VB) {
+            if (mont) s = fe_from_mont<R>(s);
+        } else if (!mont) {
+            s = fe_to_mont<R>(s);   // the table holds R^-1 P_i: digits are those of s R
+        }
+        msm_for_each_digit_sel<R, DIG>(s, win, [&](int w, uint32_t d, uint32_t) {
+            if (d) atomicAdd(&hist[(VB ? (uint32_t)w * bt.vb_stride + d : d) >> lb], 1u);
         });
     }
     __syncthreads();
@@ -413,7 +419,7 @@ __global__ __launch_bounds__(1024) void k_msm_scan_aux(const uint32_t* offs, uin
 // LDS: cursor[nb1] | delta[nb1] | first[nb1] | stage PF::type[...]
 // Every workgroup orders its pairs by bin in LDS (positions from LDS atomics on the bin cursors), then one wavefront
 // per bin copies the bin's run to its place in `pairs`: 64 consecutive entries per instruction.
-template <class C, class PF, int DIG>
+template <class C, class PF, int DIG, bool VB = false>
 __global__ __launch_bounds__(1024) void k_msm_bin_scatter(MsmBatch bt, int mont,
                                                           MsmWindows win, uint32_t per_block,
                                                           uint32_t nb1, uint32_t lb, const uint32_t* offs,
@@ -461,11 +467,17 @@ __global__ __launch_bounds__(1024) void k_msm_bin_scatter(MsmBatch bt, int mont,
         if (!have[t]) continue;
         const size_t i = (size_t)blockIdx.x * per_block + threadIdx.x + 1024u * t;
         Fe<R> s = sc[t];
-        if (!mont) s = fe_to_mont<R>(s);
+        if (VB) {
+            if (mont) s = fe_from_mont<R>(s);
+        } else if (!mont) {
+            s = fe_to_mont<R>(s);
+        }
         msm_for_each_digit_sel<R, DIG>(s, win, [&](int w, uint32_t d, uint32_t neg) {
             if (d) {
-                const uint32_t at = atomicAdd(&cursor[d >> lb], 1u);
-                stage[at] = PF::make(d, (uint32_t)((size_t)w * count + base_off + i), neg, lb);
+                // VB: the key names the window, the index the base; otherwise the index names the window's table row
+                const uint32_t key = VB ? (uint32_t)w * bt.vb_stride + d : d;
+                const uint32_t at = atomicAdd(&cursor[key >> lb], 1u);
+                stage[at] = PF::make(key, VB ? (uint32_t)(base_off + i) : (uint32_t)((size_t)w * count + base_off + i), neg, lb);
             }
         });
     }
@@ -867,9 +879,20 @@ ZKT_D XyzzX<Q> wave_sum(XyzzX<Q> acc) {   // valid in lane 0
     return acc;
 }
 
+// The W windows of one variable-base MSM (zkt_msm_g1_bases) as the slots of the two kernels below, slot y = window y, all in
+// one launch: the members they read, each an equally spaced array instead of MsmTailBatch's list of pointers.
+struct MsmTailWindows {
+    struct Strided {
+        char* base;
+        size_t stride;   // bytes
+        __device__ void* operator[](uint32_t y) const { return base + (size_t)y * stride; }
+    };
+    Strided buckets, rowcol, partials;
+};
+
 // wavefront w < NI: R_w = sum_j bucket[w NJ + j];  NI <= w < NI + NJ: C_(w - NI) = sum_i bucket[i NJ + (w - NI)]
-template <class C, bool MSM_TAIL_INL>
-__global__ __launch_bounds__(256) void k_msm_rowcol(uint32_t q1, uint32_t q2, MsmTailBatch tb) {
+template <class C, bool MSM_TAIL_INL, class TB = MsmTailBatch>
+__global__ __launch_bounds__(256) void k_msm_rowcol(uint32_t q1, uint32_t q2, TB tb) {
     using Q = typename C::Fq;
     const Xyzz<Q>* buckets = (const Xyzz<Q>*)tb.buckets[blockIdx.y];
     Xyzz<Q>* rc = (Xyzz<Q>*)tb.rowcol[blockIdx.y];
@@ -892,8 +915,8 @@ __global__ __launch_bounds__(256) void k_msm_rowcol(uint32_t q1, uint32_t q2, Ms
 // y = k < q2: sum of C_j over j with bit k; y = q2 + k, k < q1: sum of R_i over i with bit k; y = q1 + q2: the top bucket
 // alone.  Written in arkworks' R form straight into pinned host memory: the host applies the weights 2^y
 // (hostec.hpp weighted_row_sum) -- the remaining ~35 dependent curve operations cost a wavefront 0.6 ms and the host 15 us.
-template <class C, bool MSM_TAIL_INL>
-__global__ __launch_bounds__(64) void k_msm_weighted_rows(uint32_t q1, uint32_t q2, uint32_t B, MsmTailBatch tb) {
+template <class C, bool MSM_TAIL_INL, class TB = MsmTailBatch>
+__global__ __launch_bounds__(64) void k_msm_weighted_rows(uint32_t q1, uint32_t q2, uint32_t B, TB tb) {
     using Q = typename C::Fq;
     const Xyzz<Q>* rc = (const Xyzz<Q>*)tb.rowcol[blockIdx.y];
     const Xyzz<Q>* top_bucket = (const Xyzz<Q>*)tb.buckets[blockIdx.y] + B;
@@ -1652,6 +1675,273 @@ int srs_download(zkt_ctx* c, size_t offset, size_t count, uint64_t* out) {
     if (c->curve == ZKT_CURVE_BN254) return srs_download_t<Bn254Curve>(c, offset, count, out);
     return srs_download_t<Bls381Curve>(c, offset, count, out);
 }
+// ---------------------------------------------------------------------------------------------
+// zkt_msm_g1_bases: the same MSM over the CALLER's points (HomomorphicCommitment::multi_scalar_mul, commitment.rs:31-45,
+// on arbitrary bases; ark-ec's VariableBaseMSM).  There is no window table, so every window reads the same base and owns
+// 2^(c-1) buckets of its own: key = w 2^(c-1) + |d|, table index i (k_msm_bin_count / k_msm_bin_scatter with VB).  The
+// grouping, the accumulation and the bucket fold above then run unchanged over the W 2^(c-1) keys; each window's
+// sum_b b S_b goes through the row / column reduction with the windows as tail slots, and the host weights row y of
+// window w by 2^(start_w + y) -- the Horner pass over the windows is folded into the one it already does.
+// ---------------------------------------------------------------------------------------------
+struct MsmBasesPlan {
+    MsmWindows win{};
+    int c = 0;                     // widest digit
+    uint32_t Bw = 0, Btot = 0;     // buckets per window; keys 1 .. Btot in all
+    uint32_t lb = 0, nb1 = 0;
+    int lcols = 8;
+    bool packed = false;
+    uint32_t l1_scalars = 0;
+    size_t m = 0, l2_items = 0;
+};
+
+// Digit width by the number of points, from an A/B sweep on MI355X (profiles/msm_bases_cbits.txt): W 2^(c-1) buckets make
+// the tail W times the SRS path's, so c stays below that path's log2(n) - 2 while the reductions dominate (lg - 4 up to
+// 2^15 points), then jumps to the widths whose bucket keys take the wide, 1024-column sort: BN254 c = 15 (seventeen
+// windows) from 2^16, 16 at 2^22; BLS12-381 c = 13 from 2^17 (its fifteen-bit layout has eighteen mostly 14-bit windows
+// and loses), 16 from 2^20.  c = 14 (nineteen windows, 4-byte pairs over 609 level-1 bins) lost at every size.  16 is the
+// sort's limit (W 2^15 keys in 1024 bins of 1024 columns).
+static int msm_bases_cbits(size_t n, int curve) {
+    const int lg = floor_log2(n ? n : 1);
+    int cb = lg - 4 < 8 ? 8 : lg - 4;
+    if (curve == ZKT_CURVE_BN254) {
+        if (lg >= 22) cb = 16;
+        else if (lg >= 16) cb = 15;
+    } else {
+        if (lg >= 20) cb = 16;
+        else if (cb > 13) cb = 13;
+    }
+    if (const char* e = exp_env("ZKT_MSMB_CBITS")) {   // experiment: another digit width
+        const int f = atoi(e);
+        if (f >= 7 && f <= 16) cb = f;
+    }
+    return cb;
+}
+
+template <class C>
+static int msm_bases_plan(zkt_ctx* c, size_t n, int mont, MsmBasesPlan& P) {
+    using R = typename C::Fr;
+    // Canonical scalars are full 256-bit integers (ark-ec reads every bit of into_repr()); Montgomery ones leave their
+    // form below r.  One bit more for the last carry of the signed digits.
+    const int total = mont ? R::BITS + 1 : 257;
+    const int cb = msm_bases_cbits(n, c->curve);
+    const int W = (total + cb - 1) / cb;
+    if (W > (int)sizeof(P.win.width)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "msm_g1_bases: too many windows");
+    const int lo = total / W, rem = total % W;
+    P.win.W = W;
+    int pos = 0;
+    for (int w = 0; w < W; ++w) {
+        P.win.width[w] = (uint8_t)(lo + (w < rem ? 1 : 0));
+        P.win.start[w] = (uint16_t)pos;
+        pos += P.win.width[w];
+    }
+    P.c = lo + (rem ? 1 : 0);
+    P.Bw = 1u << (P.c - 1);
+    P.Btot = (uint32_t)W * P.Bw;
+    P.m = (size_t)W * n;
+    int idx_bits = 1;
+    while ((n - 1) >> idx_bits) ++idx_bits;
+    int lb = 31 - idx_bits;
+    if (lb > MSM_BIN_LB_MAX) lb = MSM_BIN_LB_MAX;
+    P.packed = lb >= 4 && ((P.Btot >> lb) + 1) < (uint32_t)MSM_MAX_NB1;
+    P.lb = P.packed ? (uint32_t)lb : (uint32_t)MSM_BIN_LB_MAX;
+    if (!P.packed && ((P.Btot >> P.lb) + 1) >= (uint32_t)MSM_MAX_NB1) {
+        P.lb = MSM_BIN_LB_WIDE;
+        P.lcols = MSM_BIN_LB_WIDE;
+    }
+    P.nb1 = (P.Btot >> P.lb) + 1;
+    if (P.nb1 >= (uint32_t)MSM_MAX_NB1 || P.m >= ((size_t)1 << 31))
+        return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "msm_g1_bases: digit layout outside the sort's range");
+    P.l1_scalars = ((uint32_t)MSM_L1_CAP / (uint32_t)W) & ~63u;
+    if (P.l1_scalars > 1024u) P.l1_scalars = 1024u;
+    P.l2_items = P.m / MSM_L2_TILE + P.nb1;
+    return ZKT_OK;
+}
+
+template <class C>
+static int msm_bases_state(zkt_ctx* c, MsmBasesState** out) {
+    using Q = typename C::Fq;
+    if (!c->msmb) {
+        auto st = std::make_shared<MsmBasesState>();
+        for (int pk = 0; pk < 2; ++pk) {   // LDS cap of the level-1 scatter, for the worst case (as msm_setup)
+            const int lds = (int)(((3 * (uint32_t)MSM_MAX_NB1 + 3) & ~3u) * 4 + MSM_L1_CAP * (pk ? 4 : 8));
+            const void* f = pk ? (const void*)k_msm_bin_scatter<C, PairPacked, 0, true>
+                               : (const void*)k_msm_bin_scatter<C, PairWide, 0, true>;
+            ZKT_HIP(c, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        }
+        int blocks_per_cu = 0, cus = 0;
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, c->device) == hipSuccess) cus = prop.multiProcessorCount;
+        st->acc_threads = 196608;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, k_msm_accumulate<C>, 256, 0) == hipSuccess &&
+            blocks_per_cu > 0 && cus > 0)
+            st->acc_threads = (size_t)blocks_per_cu * cus * 256;
+        st->acc_threads *= 2;
+        const size_t rows = sizeof(MsmWindows::width) * (size_t)(MSM_MAX_Y + 1);
+        ZKT_HIP(c, hipHostMalloc(&st->partials, rows * sizeof(Xyzz<Q>), hipHostMallocMapped));
+        ZKT_HIP(c, hipHostGetDevicePointer(&st->partials_dev, st->partials, 0));
+        c->msmb = st;
+    }
+    *out = c->msmb.get();
+    return ZKT_OK;
+}
+
+template <class C>
+static int msm_bases_t(zkt_ctx* c, const void* bases, bool bases_on_device, const void* scalars, bool scalars_on_device,
+                       size_t n, int mont, uint64_t* out_xy, int* out_inf) {
+    using Q = typename C::Fq;
+    Affine<Q> res;
+    res.x = fe_zero<Q>();
+    res.y = fe_zero<Q>();
+    if (n > 0) {
+        MsmBasesPlan P;
+        int rc = msm_bases_plan<C>(c, n, mont, P);
+        if (rc) return rc;
+        MsmBasesState* st = nullptr;
+        if ((rc = msm_bases_state<C>(c, &st))) return rc;
+        const int W = P.win.W;
+        const uint32_t q = (uint32_t)(P.c - 1), q2 = q / 2, q1 = q - q2;   // 2^q buckets below Bw = 2^q1 rows x 2^q2 columns
+        const uint32_t sums = (1u << q1) + (1u << q2);
+        const uint32_t S = P.l1_scalars;
+        const unsigned nblk = (unsigned)((n + S - 1) / S);
+        const uint32_t total = P.nb1 * nblk, ntiles = (total + MSM_SCAN_TILE - 1) / MSM_SCAN_TILE;
+        const size_t max_chunks = std::min(P.m, st->acc_threads) + 1;
+        auto grow = [&](MsmBasesState::Buf& b, size_t bytes) { return ensure_buffer(c, &b.p, &b.bytes, bytes); };
+        if ((rc = grow(st->bases, n * sizeof(Affine<Q>))) || (rc = grow(st->vals, P.m * 4)) ||
+            (rc = grow(st->pairs, P.m * (P.packed ? 4 : 8))) || (rc = grow(st->bin_offs, ((size_t)total + 1) * 4)) ||
+            (rc = grow(st->bin_aux, ((size_t)ntiles + 4) * 4)) || (rc = grow(st->bin_start, ((size_t)P.nb1 + 1) * 4)) ||
+            (rc = grow(st->tile_start, ((size_t)P.nb1 + 1) * 4)) || (rc = grow(st->tile_desc, P.l2_items * 8)) ||
+            (rc = grow(st->cnt2, (P.l2_items << P.lcols) * 4)) || (rc = grow(st->pos2, (P.l2_items << P.lcols) * 4)) ||
+            (rc = grow(st->chunk_bucket, (max_chunks + 2) * 4)) || (rc = grow(st->offsets, (((size_t)P.nb1 << P.lb) + 2) * 4)) ||
+            (rc = grow(st->heavy, ((size_t)P.Btot + 2) * 4)) || (rc = grow(st->params, 16)) ||
+            (rc = grow(st->pieces, (max_chunks + P.Btot + 2) * sizeof(XyzzRaw<Q>))) ||
+            (rc = grow(st->buckets, ((size_t)P.Btot + 1) * sizeof(Xyzz<Q>))) ||
+            (rc = grow(st->rowcol, (size_t)W * sums * sizeof(Xyzz<Q>))))
+            return rc;
+        if (!scalars_on_device) {
+            if ((rc = grow(st->scalars, n * 32))) return rc;
+            ZKT_HIP(c, hipMemcpyAsync(st->scalars.p, scalars, n * 32, hipMemcpyHostToDevice, c->stream));
+            scalars = st->scalars.p;
+        }
+        // the bases once into the accumulation's packed R' form ((0,0) stays zero and is skipped there)
+        ZKT_HIP(c, hipMemcpyAsync(st->bases.p, bases, n * sizeof(Affine<Q>),
+                                  bases_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_srs_to_fx<C>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (Affine<Q>*)st->bases.p, n);
+        ZKT_HIP(c, hipGetLastError());
+
+        // one MSM: every launch has blockIdx.y = 0, so the batch strides stay zero
+        MsmBatch bt{};
+        for (int j = 0; j < MSM_BATCH; ++j) {
+            bt.scalars[j] = scalars;
+            bt.n[j] = n;
+            bt.base_off[j] = 0;
+            bt.table[j] = st->bases.p;
+            bt.tcount[j] = n;
+            bt.heavy[j] = (uint32_t*)st->heavy.p;
+            bt.params[j] = (uint32_t*)st->params.p;
+            bt.offsets[j] = (uint32_t*)st->offsets.p;
+            bt.pieces[j] = st->pieces.p;
+        }
+        bt.vb_stride = P.Bw;
+        uint32_t* bin_offs = (uint32_t*)st->bin_offs.p;
+        uint32_t* bin_aux = (uint32_t*)st->bin_aux.p;
+        uint32_t* bin_start = (uint32_t*)st->bin_start.p;
+        uint32_t* tile_start = (uint32_t*)st->tile_start.p;
+        const uint2* tile_desc = (const uint2*)st->tile_desc.p;
+        uint32_t* cnt2 = (uint32_t*)st->cnt2.p;
+        uint32_t* pos2 = (uint32_t*)st->pos2.p;
+        uint32_t* vals = (uint32_t*)st->vals.p;
+        uint32_t* chunk_bucket = (uint32_t*)st->chunk_bucket.p;
+        const uint32_t items = (uint32_t)P.l2_items;
+        {
+            ProfScope prof(c, "msm_bases_main");
+            hipLaunchKernelGGL((k_msm_bin_count<C, 0, true>), dim3(nblk, 1), dim3(1024), (size_t)P.nb1 * 4, c->stream, bt, mont, P.win,
+                               S, P.nb1, P.lb, bin_offs);
+            hipLaunchKernelGGL(k_msm_scan_tiles, dim3(ntiles, 1), dim3(1024), 0, c->stream, bin_offs, total, bin_aux, bt);
+            hipLaunchKernelGGL(k_msm_scan_aux, dim3(1, 1), dim3(1024), 0, c->stream, bin_offs, bin_aux, ntiles, nblk, P.nb1,
+                               bin_start, tile_start, (uint2*)st->tile_desc.p, (uint32_t)st->acc_threads, P.Btot, 0u, bt);
+            ZKT_HIP(c, hipGetLastError());
+            const size_t lds_scatter = (size_t)((3 * P.nb1 + 3) & ~3u) * 4 + (size_t)MSM_L1_CAP * (P.packed ? 4 : 8);
+            if (P.packed) {
+                hipLaunchKernelGGL((k_msm_bin_scatter<C, PairPacked, 0, true>), dim3(nblk, 1), dim3(1024), lds_scatter, c->stream, bt,
+                                   mont, P.win, S, P.nb1, P.lb, bin_offs, bin_aux, (uint32_t*)st->pairs.p);
+                ZKT_HIP(c, hipGetLastError());
+                hipLaunchKernelGGL((k_msm_l2_count<PairPacked, 8>), dim3(items, 1), dim3(256), 0, c->stream,
+                                   (const uint32_t*)st->pairs.p, P.nb1, P.lb, tile_start, tile_desc, cnt2, bt);
+            } else {
+                hipLaunchKernelGGL((k_msm_bin_scatter<C, PairWide, 0, true>), dim3(nblk, 1), dim3(1024), lds_scatter, c->stream, bt,
+                                   mont, P.win, S, P.nb1, P.lb, bin_offs, bin_aux, (uint2*)st->pairs.p);
+                ZKT_HIP(c, hipGetLastError());
+                auto kc2 = P.lcols == 8 ? k_msm_l2_count<PairWide, 8> : k_msm_l2_count<PairWide, 10>;
+                hipLaunchKernelGGL(kc2, dim3(items, 1), dim3(256), 0, c->stream, (const uint2*)st->pairs.p, P.nb1, P.lb, tile_start,
+                                   tile_desc, cnt2, bt);
+            }
+            {
+                auto ksc = P.lcols == 8 ? k_msm_l2_scan<8> : k_msm_l2_scan<10>;
+                hipLaunchKernelGGL(ksc, dim3(P.nb1, 1), dim3(256), 0, c->stream, cnt2, pos2, bin_start, tile_start, P.Btot, P.lb,
+                                   chunk_bucket, bt);
+            }
+            if (P.packed) {
+                hipLaunchKernelGGL((k_msm_l2_scatter<PairPacked, 8>), dim3(items, 1), dim3(MSM_L2S_THREADS), 0, c->stream,
+                                   (const uint32_t*)st->pairs.p, P.nb1, P.lb, tile_start, tile_desc, cnt2, pos2, vals, bt);
+            } else {
+                auto kss = P.lcols == 8 ? k_msm_l2_scatter<PairWide, 8> : k_msm_l2_scatter<PairWide, 10>;
+                hipLaunchKernelGGL(kss, dim3(items, 1), dim3(MSM_L2S_THREADS), 0, c->stream, (const uint2*)st->pairs.p, P.nb1,
+                                   P.lb, tile_start, tile_desc, cnt2, pos2, vals, bt);
+            }
+            ZKT_HIP(c, hipGetLastError());
+            const uint32_t chunks = (uint32_t)std::min(P.m, st->acc_threads);
+            hipLaunchKernelGGL(k_msm_accumulate<C>, dim3((chunks + 255) / 256, 1), dim3(256), 0, c->stream, vals, P.Btot,
+                               chunk_bucket, bt);
+            ZKT_HIP(c, hipGetLastError());
+        }
+        {
+            ProfScope prof(c, "msm_bases_tail");
+            MsmTailBatch tb{};
+            for (int j = 0; j < MSM_TAIL_BATCH; ++j) {
+                tb.offsets[j] = (const uint32_t*)st->offsets.p;
+                tb.params[j] = (const uint32_t*)st->params.p;
+                tb.pieces[j] = st->pieces.p;
+                tb.buckets[j] = st->buckets.p;
+                tb.heavy[j] = (uint32_t*)st->heavy.p;
+            }
+            // the fold of all W 2^(c-1) buckets as one MSM's (slot 0) ...
+            hipLaunchKernelGGL((k_msm_bucket_sum<C, true>), dim3((P.Btot + 1 + 255) / 256, 1), dim3(256), 0, c->stream, P.Btot, tb);
+            hipLaunchKernelGGL((k_msm_heavy<C, true>), dim3(MSM_HEAVY_BLOCKS, 1), dim3(256), 0, c->stream, tb);
+            ZKT_HIP(c, hipGetLastError());
+            // ... then window w reduces buckets w Bw .. w Bw + Bw as a slot of its own, all windows in one launch.  Its bucket 0
+            // is the previous window's top bucket; it only enters row 0 and column 0, which no bit-weighted row reads.
+            MsmTailWindows tw;
+            tw.buckets = {(char*)st->buckets.p, (size_t)P.Bw * sizeof(Xyzz<Q>)};
+            tw.rowcol = {(char*)st->rowcol.p, (size_t)sums * sizeof(Xyzz<Q>)};
+            tw.partials = {(char*)st->partials_dev, (size_t)(q + 1) * sizeof(Xyzz<Q>)};
+            hipLaunchKernelGGL((k_msm_rowcol<C, true, MsmTailWindows>), dim3((sums + 3) / 4, (unsigned)W), dim3(256), 0, c->stream,
+                               q1, q2, tw);
+            hipLaunchKernelGGL((k_msm_weighted_rows<C, true, MsmTailWindows>), dim3(q + 1, (unsigned)W), dim3(64), 0, c->stream,
+                               q1, q2, P.Bw, tw);
+            ZKT_HIP(c, hipGetLastError());
+        }
+        ZKT_HIP(c, hipStreamSynchronize(c->stream));
+        // sum_w 2^(start_w) sum_y 2^y V_(w,y): rows in window order have non-decreasing exponents
+        std::vector<int> exps((size_t)W * (q + 1));
+        for (int w = 0; w < W; ++w)
+            for (uint32_t y = 0; y <= q; ++y) exps[(size_t)w * (q + 1) + y] = (int)P.win.start[w] + (int)y;
+        res = xyzz_to_affine_host<Q>(hostec::weighted_row_sum<Q>((const Xyzz<Q>*)st->partials, (int)exps.size(), 1, exps.data()));
+    }
+    memcpy(out_xy, res.x.v, Q::N * 4);
+    memcpy(out_xy + Q::N / 2, res.y.v, Q::N * 4);
+    if (out_inf) *out_inf = aff_is_inf<Q>(res) ? 1 : 0;
+    return ZKT_OK;
+}
+
+int msm_bases(zkt_ctx* c, const void* bases, bool bases_on_device, const void* scalars, bool scalars_on_device, size_t n, int mont,
+              uint64_t* out_xy, int* out_inf) {
+    if (n > ZKT_MSM_BASES_MAX)
+        return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "msm_g1_bases: more points than ZKT_MSM_BASES_MAX (2^22)");
+    if (c->curve == ZKT_CURVE_BN254)
+        return msm_bases_t<Bn254Curve>(c, bases, bases_on_device, scalars, scalars_on_device, n, mont, out_xy, out_inf);
+    return msm_bases_t<Bls381Curve>(c, bases, bases_on_device, scalars, scalars_on_device, n, mont, out_xy, out_inf);
+}
+
 void msm_info(zkt_ctx* c, int* cbits, int* windows, size_t* count) {
     if (!c->msm) {
         *cbits = 0; *windows = 0; *count = 0;
@@ -1724,6 +2014,31 @@ int zkt_msm_enqueue_dev(zkt_ctx* c, const void* d_scalars, size_t len, size_t ba
     if (!c || !d_scalars) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
     (void)hipSetDevice(c->device);
     return msm_enqueue_only(c, d_scalars, len, base_offset, scalars_montgomery);
+}
+
+int zkt_msm_g1_bases(zkt_ctx* c, const uint64_t* bases_xy_mont, const uint64_t* scalars, size_t n, int scalars_montgomery,
+                     uint64_t* out_xy_mont, int* out_is_infinity) {
+    if (!c || (n && (!bases_xy_mont || !scalars)) || !out_xy_mont) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
+    (void)hipSetDevice(c->device);
+    return msm_bases(c, bases_xy_mont, false, scalars, false, n, scalars_montgomery, out_xy_mont, out_is_infinity);
+}
+
+int zkt_msm_g1_bases_dev(zkt_ctx* c, const void* d_bases_xy_mont, const void* d_scalars, size_t n, int scalars_montgomery,
+                         uint64_t* out_xy_mont_host, int* out_is_infinity) {
+    if (!c || (n && (!d_bases_xy_mont || !d_scalars)) || !out_xy_mont_host)
+        return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
+    (void)hipSetDevice(c->device);
+    return msm_bases(c, d_bases_xy_mont, true, d_scalars, true, n, scalars_montgomery, out_xy_mont_host, out_is_infinity);
+}
+
+int zkt_msm_bases_info(zkt_ctx* c, size_t n, int scalars_montgomery, int* window_bits, int* windows) {
+    if (!c || !window_bits || !windows) return ZKT_ERR_INVALID_ARGUMENT;
+    if (n > ZKT_MSM_BASES_MAX) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "msm_g1_bases: more points than ZKT_MSM_BASES_MAX (2^22)");
+    const int total = scalars_montgomery ? (c->curve == ZKT_CURVE_BN254 ? 255 : 256) : 257;
+    const int cb = msm_bases_cbits(n, c->curve);
+    *windows = n ? (total + cb - 1) / cb : 0;
+    *window_bits = n ? (total + *windows - 1) / *windows : 0;
+    return ZKT_OK;
 }
 
 int zkt_msm_info(zkt_ctx* c, int* window_bits, int* windows, size_t* srs_count) {

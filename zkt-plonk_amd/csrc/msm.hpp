@@ -35,6 +35,7 @@ struct MsmBatch {
     uint32_t* offsets[MSM_BATCH];
     void* pieces[MSM_BATCH];
     uint64_t s_bin_offs, s_bin_aux, s_bin, s_tile_desc, s_cnt, s_pairs_bytes, s_vals, s_chunk;   // strides, in elements (pairs: bytes)
+    uint32_t vb_stride;              // variable-base MSM (zkt_msm_g1_bases): buckets per window; unused by the SRS path
 };
 
 constexpr int MSM_TAIL_BATCH = 6;    // bucket folds / reductions that go out as ONE launch per kernel (blockIdx.y = slot)
@@ -119,6 +120,25 @@ struct MsmState {
     }
 };
 
+// Scratch of zkt_msm_g1_bases (variable-base MSM over the caller's points, msm.hip): buffers of its own, allocated on the
+// first call and grown when a call needs more, so that the call never touches the prover's slots, work set or tables.
+// Device buffers are the context's (dev_alloc); only the pinned partial sums are freed here.
+struct MsmBasesState {
+    struct Buf {
+        void* p = nullptr;
+        size_t bytes = 0;
+    };
+    Buf bases;        // the call's points in the accumulation's packed R' form
+    Buf scalars;      // zkt_msm_g1_bases: the uploaded scalars
+    Buf vals, pairs, bin_offs, bin_aux, bin_start, tile_start, tile_desc, cnt2, pos2, chunk_bucket;   // grouping
+    Buf offsets, heavy, params, pieces, buckets, rowcol;                                              // accumulation, tail
+    void* partials = nullptr;       // pinned: W x (c) rows of partial sums the host combines (Horner over the windows)
+    void* partials_dev = nullptr;
+    size_t acc_threads = 0;         // chunks an accumulation is cut into (occupancy query x 2, as MsmState)
+    ~MsmBasesState() {
+        if (partials) (void)hipHostFree(partials);
+    }
+};
 
 // msm.hip: window multiples + R' conversion of an affine base table whose first `count` entries are filled (arkworks R form)
 int msm_table_finish(zkt_ctx* c, void* table, size_t count);
