@@ -548,6 +548,33 @@ int zkt_debug_open_witness(zkt_ctx* ctx, const uint64_t* coeffs, size_t len, con
 int zkt_debug_eval_lincomb(zkt_ctx* ctx, const uint64_t* const* polys, const size_t* lens, int k, const uint64_t* points,
                            const uint64_t* scalars, uint64_t* out_evals, uint64_t* out_lincomb, size_t out_len);
 
+/* Raw-limb field and curve routines (csrc/fx.hpp, csrc/ecx.hpp) for tests at their stated bounds.  One dispatcher runs
+ * either on the host (zkt_host_*: the C++ loops of the products, no GPU needed) or in a plain kernel, one record per
+ * thread, on the context's stream (zkt_debug_*: the device's multiply-add chains).  Limbs are passed as given, never
+ * normalised on the way in.  fx records: in = a, b, c, d of L words each (a packed operand in the first N words of its
+ * slot), out = 4 L words (a packed result in the first N words, a predicate in word 0, the rest zero).  xyzz records (the
+ * curve's base field): in = two points of 4 L + 1 words (x, y, zz, zzz, identity flag; an affine operand in the x, y
+ * slots), out = one point.  which: 0 = Fr, 1 = Fq.  An op the field does not support returns ZKT_ERR_INVALID_ARGUMENT. */
+enum zkt_fx_op {
+    ZKT_FX_UNPACK = 0, ZKT_FX_UNPACK_SHIFT = 1, ZKT_FX_PACK = 2, ZKT_FX_FROM_ARK = 3, ZKT_FX_TO_ARK = 4,
+    ZKT_FX_NORMALIZE = 5, ZKT_FX_ADD = 6, ZKT_FX_DBL = 7, ZKT_FX_SUB_1 = 8, ZKT_FX_SUB_2 = 9, ZKT_FX_SUB_4 = 10,
+    ZKT_FX_SUB_8 = 11, ZKT_FX_SUB2_6 = 12, ZKT_FX_ADD_LAZY = 13, ZKT_FX_SUB_LAZY_3 = 14, ZKT_FX_SUB_LAZY_4 = 15,
+    ZKT_FX_SUB_LAZY_5 = 16, ZKT_FX_SUB_LAZY_9 = 17, ZKT_FX_SUB_LAZY_WIDE_8_30 = 18, ZKT_FX_MUL = 19, ZKT_FX_MUL_INL = 20,
+    ZKT_FX_SQR = 21, ZKT_FX_SQR_INL = 22, ZKT_FX_MUL2_INL = 23, ZKT_FX_MUL_SHOUP = 24 /* a x, b w, c wq */,
+    ZKT_FX_MUL_LOW = 25, ZKT_FX_REDUCE_SMALL = 26, ZKT_FX_REDUCE_LAZY = 27 /* not on the 381-bit field */,
+    ZKT_FX_COND_SUB_P = 28, ZKT_FX_CANON = 29, ZKT_FX_IS_ZERO_CANON = 30, ZKT_FX_IS_ZERO_LT2P = 31, ZKT_FX_OP_COUNT = 32
+};
+enum zkt_xyzz_op {
+    ZKT_XYZZ_ADD_MIXED = 0, ZKT_XYZZ_ADD_MIXED_INL = 1, ZKT_XYZZ_ADD = 2, ZKT_XYZZ_ADD_INL = 3, ZKT_XYZZ_DOUBLE = 4,
+    ZKT_XYZZ_DOUBLE_AFFINE = 5, ZKT_XYZZ_OP_COUNT = 6
+};
+/* limb count L, limb width and SH (R' = 2^(limb_bits L) = 2^(32 N + SH)) of a field's limb form; no context needed */
+int zkt_debug_fx_layout(int curve_id, int which, int* limbs, int* limb_bits, int* sh);
+int zkt_host_fx_op(int curve_id, int which, int op, const uint32_t* in, size_t n, uint32_t* out);
+int zkt_debug_fx_op(zkt_ctx* ctx, int which, int op, const uint32_t* in, size_t n, uint32_t* out);
+int zkt_host_xyzz_op(int curve_id, int op, const uint32_t* in, size_t n, uint32_t* out);
+int zkt_debug_xyzz_op(zkt_ctx* ctx, int op, const uint32_t* in, size_t n, uint32_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -95,6 +95,12 @@ def lib():
         L.zkt_debug_params.argtypes = [vp, ctypes.c_int, u32p, ctypes.c_size_t]
         L.zkt_debug_fr_mul.argtypes = [vp, u64p, u64p, ctypes.c_size_t, u64p]
         L.zkt_debug_quotient.argtypes = [vp, u64p, ctypes.POINTER(ctypes.c_void_p), u64p, u64p, ctypes.c_size_t, u64p]
+        ip = ctypes.POINTER(ctypes.c_int)
+        L.zkt_debug_fx_layout.argtypes = [ctypes.c_int, ctypes.c_int, ip, ip, ip]
+        L.zkt_host_fx_op.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, u32p, ctypes.c_size_t, u32p]
+        L.zkt_debug_fx_op.argtypes = [vp, ctypes.c_int, ctypes.c_int, u32p, ctypes.c_size_t, u32p]
+        L.zkt_host_xyzz_op.argtypes = [ctypes.c_int, ctypes.c_int, u32p, ctypes.c_size_t, u32p]
+        L.zkt_debug_xyzz_op.argtypes = [vp, ctypes.c_int, u32p, ctypes.c_size_t, u32p]
         _bind_optional(L)
         _bind_prover(L)
         _lib = L
@@ -404,6 +410,60 @@ def g1_sum_host(curve, points) -> tuple:
     if rc:
         raise ZktError(rc, "zkt_g1_sum_host")
     return out, bool(inf.value)
+
+
+# ---- raw-limb field / curve routines (test hooks; the record layout is described in include/zkt_plonk.h) ----------
+def _header_enum(prefix: str) -> dict:
+    text = re.sub(r"/\*.*?\*/", "", open(_HEADER).read(), flags=re.S)
+    return {m.group(1)[len(prefix):]: int(m.group(2)) for m in re.finditer(r"\b(%s[A-Z0-9_]+)\s*=\s*(\d+)" % prefix, text)}
+
+
+def fx_ops() -> dict:
+    """zkt_fx_op as {name: value}, e.g. "MUL_INL" -> 20 (read from the public header)."""
+    return {k: v for k, v in _header_enum("ZKT_FX_").items() if k != "OP_COUNT"}
+
+
+def xyzz_ops() -> dict:
+    return {k: v for k, v in _header_enum("ZKT_XYZZ_").items() if k != "OP_COUNT"}
+
+
+def fx_layout(curve, which: int) -> tuple:
+    """(L, limb_bits, SH) of the field's limb form (zkt_debug_fx_layout)."""
+    vals = [ctypes.c_int(0) for _ in range(3)]
+    rc = lib().zkt_debug_fx_layout(curve_id(curve), which, *[ctypes.byref(v) for v in vals])
+    if rc:
+        raise ZktError(rc, "zkt_debug_fx_layout")
+    return tuple(v.value for v in vals)
+
+
+def _u32p(a: np.ndarray):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
+
+
+def _records(records, width: int) -> np.ndarray:
+    return np.ascontiguousarray(records, dtype=np.uint32).reshape(-1, width)
+
+
+def host_fx_op(curve, which: int, op: int, records) -> np.ndarray:
+    """zkt_host_fx_op on (n, 4 L) u32 records -> (n, 4 L) results, on the host."""
+    L_ = fx_layout(curve, which)[0]
+    rec = _records(records, 4 * L_)
+    out = np.zeros_like(rec)
+    rc = lib().zkt_host_fx_op(curve_id(curve), which, op, _u32p(rec), rec.shape[0], _u32p(out))
+    if rc:
+        raise ZktError(rc, "zkt_host_fx_op")
+    return out
+
+
+def host_xyzz_op(curve, op: int, records) -> np.ndarray:
+    """zkt_host_xyzz_op on (n, 2 (4 L + 1)) u32 records -> (n, 4 L + 1) points, on the host."""
+    w = 4 * fx_layout(curve, 1)[0] + 1
+    rec = _records(records, 2 * w)
+    out = np.zeros((rec.shape[0], w), dtype=np.uint32)
+    rc = lib().zkt_host_xyzz_op(curve_id(curve), op, _u32p(rec), rec.shape[0], _u32p(out))
+    if rc:
+        raise ZktError(rc, "zkt_host_xyzz_op")
+    return out
 
 
 def srs_generate_g2(curve, tau: int):
@@ -936,6 +996,22 @@ class Context:
         b = np.ascontiguousarray(b, dtype=np.uint64).reshape(-1, 4)
         out = np.empty_like(a)
         self.check(self._L.zkt_debug_fr_mul(self._h, u64p(a), u64p(b), a.shape[0], u64p(out)))
+        return out
+
+    def debug_fx_op(self, which: int, op: int, records) -> np.ndarray:
+        """zkt_debug_fx_op: the field routine `op` on the device, one (4 L,) u32 record per thread."""
+        L_ = fx_layout(self.curve, which)[0]
+        rec = _records(records, 4 * L_)
+        out = np.zeros_like(rec)
+        self.check(self._L.zkt_debug_fx_op(self._h, which, op, _u32p(rec), rec.shape[0], _u32p(out)))
+        return out
+
+    def debug_xyzz_op(self, op: int, records) -> np.ndarray:
+        """zkt_debug_xyzz_op: the curve routine `op` on the device, one (2 (4 L + 1),) u32 record per thread."""
+        w = 4 * fx_layout(self.curve, 1)[0] + 1
+        rec = _records(records, 2 * w)
+        out = np.zeros((rec.shape[0], w), dtype=np.uint32)
+        self.check(self._L.zkt_debug_xyzz_op(self._h, op, _u32p(rec), rec.shape[0], _u32p(out)))
         return out
 
     def debug_grand_products(self, n: int, challenges, vectors):

@@ -5,6 +5,7 @@
 #include "hostinv.hpp"
 #include "ec.hpp"
 #include "hostec.hpp"
+#include "fx_test.hpp"
 
 #include <cstring>
 
@@ -167,6 +168,20 @@ template <class P>
 __global__ void k_fr_mul(const Fe<P>* a, const Fe<P>* b, Fe<P>* o, size_t n) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) fe_store<P>(o + i, fe_mul<P>(fe_load<P>(a + i), fe_load<P>(b + i)));
+}
+
+// the raw-limb test hooks (fx_test.hpp): one record per thread, the same dispatcher the host loop runs
+template <class P>
+__global__ void k_fx_test(int op, const uint32_t* in, size_t n, uint32_t* out) {
+    constexpr int W = 4 * FxP<P>::L;
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) fx_test_op<P>(op, in + i * W, out + i * W);
+}
+template <class Q>
+__global__ void k_xyzz_test(int op, const uint32_t* in, size_t n, uint32_t* out) {
+    constexpr int W = 4 * FxP<Q>::L + 1;
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) xyzz_test_op<Q>(op, in + i * 2 * W, out + i * W);
 }
 
 template <class P>
@@ -430,8 +445,10 @@ int zkt_debug_params(zkt_ctx* c, int which, uint32_t* out, size_t out_words) {
 
 }  // extern "C"
 
-// Host-side execution of the field routines (same __host__ __device__ code the kernels run): lets the
-// CPU test-suite pin the 29-bit-limb arithmetic against big integers without a GPU.
+// Host-side execution of the field routines: the same __host__ __device__ source the kernels compile, but the products
+// (fx_mul_inl, fx_sqr_inl, fx_mul2_inl, fx_mul_shoup) take their #else branches, plain C++ loops, not the device's
+// multiply-add chains (zkt_debug_fx_op runs those).  Lets the CPU test-suite pin the 29-bit-limb arithmetic against big
+// integers without a GPU.
 //   op 0: packed Montgomery product (fe_mul)          op 1: 32-bit-limb CIOS reference (fe_mul_sat)
 //   op 2: ark -> R'-limbs -> ark round trip           op 3: lazy chain  (a + b) * (a + 8p - b) reduced
 //   op 4: a^-1 by the host's binary GCD (hostinv.hpp)  op 5: a^-1 by the kernels' Fermat ladder
@@ -508,6 +525,59 @@ static void g1_sum_host(const uint64_t* pts, size_t count, uint64_t* out, int* o
     if (out_inf) *out_inf = aff_is_inf<Q>(r) ? 1 : 0;
 }
 
+// raw-limb test hooks (fx_test.hpp): the host loop and the kernel run the same dispatcher on the same records
+constexpr size_t FX_TEST_MAX_RECORDS = (size_t)1 << 24;
+
+template <class P>
+static int host_fx_run(int op, const uint32_t* in, size_t n, uint32_t* out) {
+    if (!fx_test_op_valid<P>(op)) return ZKT_ERR_INVALID_ARGUMENT;
+    constexpr int W = 4 * FxP<P>::L;
+    for (size_t i = 0; i < n; ++i) fx_test_op<P>(op, in + i * W, out + i * W);
+    return ZKT_OK;
+}
+template <class Q>
+static int host_xyzz_run(int op, const uint32_t* in, size_t n, uint32_t* out) {
+    if (op < 0 || op >= ZKT_XYZZ_OP_COUNT) return ZKT_ERR_INVALID_ARGUMENT;
+    constexpr int W = 4 * FxP<Q>::L + 1;
+    for (size_t i = 0; i < n; ++i) xyzz_test_op<Q>(op, in + i * 2 * W, out + i * W);
+    return ZKT_OK;
+}
+// in_words / out_words per record; K: the kernel for the field
+static int debug_test_launch(zkt_ctx* c, void (*k)(int, const uint32_t*, size_t, uint32_t*), int op, const uint32_t* in,
+                             size_t n, uint32_t* out, size_t in_words, size_t out_words) {
+    if (n == 0) return ZKT_OK;
+    if (n > FX_TEST_MAX_RECORDS) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "too many records");
+    (void)hipSetDevice(c->device);
+    int rc = ensure_buffer(c, &c->io_a, &c->io_a_bytes, n * in_words * 4);
+    if (rc) return rc;
+    if ((rc = ensure_buffer(c, &c->io_b, &c->io_b_bytes, n * out_words * 4))) return rc;
+    ZKT_HIP(c, hipMemcpyAsync(c->io_a, in, n * in_words * 4, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, op, (const uint32_t*)c->io_a, n,
+                       (uint32_t*)c->io_b);
+    ZKT_HIP(c, hipGetLastError());
+    ZKT_HIP(c, hipMemcpyAsync(out, c->io_b, n * out_words * 4, hipMemcpyDeviceToHost, c->stream));
+    ZKT_HIP(c, hipStreamSynchronize(c->stream));
+    return ZKT_OK;
+}
+template <class P>
+static int debug_fx_run(zkt_ctx* c, int op, const uint32_t* in, size_t n, uint32_t* out) {
+    if (!fx_test_op_valid<P>(op)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "field op not supported on this field");
+    constexpr size_t W = 4 * FxP<P>::L;
+    return debug_test_launch(c, k_fx_test<P>, op, in, n, out, W, W);
+}
+template <class Q>
+static int debug_xyzz_run(zkt_ctx* c, int op, const uint32_t* in, size_t n, uint32_t* out) {
+    if (op < 0 || op >= ZKT_XYZZ_OP_COUNT) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "unknown curve op");
+    constexpr size_t W = 4 * FxP<Q>::L + 1;
+    return debug_test_launch(c, k_xyzz_test<Q>, op, in, n, out, 2 * W, W);
+}
+template <class P>
+static void fx_layout(int* limbs, int* limb_bits, int* sh) {
+    *limbs = FxP<P>::L;
+    *limb_bits = 29;
+    *sh = FxP<P>::SH;
+}
+
 extern "C" {
 
 int zkt_g1_sum_host(int curve_id, const uint64_t* pts, size_t count, uint64_t* out, int* out_inf) {
@@ -548,6 +618,50 @@ int zkt_debug_fr_mul(zkt_ctx* c, const uint64_t* a, const uint64_t* b, size_t n,
     ZKT_HIP(c, hipMemcpyAsync(out, c->io_a, n * 32, hipMemcpyDeviceToHost, c->stream));
     ZKT_HIP(c, hipStreamSynchronize(c->stream));
     return ZKT_OK;
+}
+
+int zkt_debug_fx_layout(int curve_id, int which, int* limbs, int* limb_bits, int* sh) {
+    if (!limbs || !limb_bits || !sh || (which != 0 && which != 1)) return ZKT_ERR_INVALID_ARGUMENT;
+    if (curve_id == ZKT_CURVE_BN254) {
+        if (which == 0) fx_layout<Bn254Fr>(limbs, limb_bits, sh); else fx_layout<Bn254Fq>(limbs, limb_bits, sh);
+    } else if (curve_id == ZKT_CURVE_BLS12_381) {
+        if (which == 0) fx_layout<Bls381Fr>(limbs, limb_bits, sh); else fx_layout<Bls381Fq>(limbs, limb_bits, sh);
+    } else {
+        return ZKT_ERR_INVALID_ARGUMENT;
+    }
+    return ZKT_OK;
+}
+
+int zkt_host_fx_op(int curve_id, int which, int op, const uint32_t* in, size_t n, uint32_t* out) {
+    if ((!in || !out) && n) return ZKT_ERR_INVALID_ARGUMENT;
+    if (which != 0 && which != 1) return ZKT_ERR_INVALID_ARGUMENT;
+    if (curve_id == ZKT_CURVE_BN254)
+        return which == 0 ? host_fx_run<Bn254Fr>(op, in, n, out) : host_fx_run<Bn254Fq>(op, in, n, out);
+    if (curve_id == ZKT_CURVE_BLS12_381)
+        return which == 0 ? host_fx_run<Bls381Fr>(op, in, n, out) : host_fx_run<Bls381Fq>(op, in, n, out);
+    return ZKT_ERR_INVALID_ARGUMENT;
+}
+
+int zkt_debug_fx_op(zkt_ctx* c, int which, int op, const uint32_t* in, size_t n, uint32_t* out) {
+    if (!c) return ZKT_ERR_INVALID_ARGUMENT;
+    if (((!in || !out) && n) || (which != 0 && which != 1)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "bad arguments");
+    if (c->curve == ZKT_CURVE_BN254)
+        return which == 0 ? debug_fx_run<Bn254Fr>(c, op, in, n, out) : debug_fx_run<Bn254Fq>(c, op, in, n, out);
+    return which == 0 ? debug_fx_run<Bls381Fr>(c, op, in, n, out) : debug_fx_run<Bls381Fq>(c, op, in, n, out);
+}
+
+int zkt_host_xyzz_op(int curve_id, int op, const uint32_t* in, size_t n, uint32_t* out) {
+    if ((!in || !out) && n) return ZKT_ERR_INVALID_ARGUMENT;
+    if (curve_id == ZKT_CURVE_BN254) return host_xyzz_run<Bn254Fq>(op, in, n, out);
+    if (curve_id == ZKT_CURVE_BLS12_381) return host_xyzz_run<Bls381Fq>(op, in, n, out);
+    return ZKT_ERR_INVALID_ARGUMENT;
+}
+
+int zkt_debug_xyzz_op(zkt_ctx* c, int op, const uint32_t* in, size_t n, uint32_t* out) {
+    if (!c) return ZKT_ERR_INVALID_ARGUMENT;
+    if ((!in || !out) && n) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "bad arguments");
+    if (c->curve == ZKT_CURVE_BN254) return debug_xyzz_run<Bn254Fq>(c, op, in, n, out);
+    return debug_xyzz_run<Bls381Fq>(c, op, in, n, out);
 }
 
 }  // extern "C"

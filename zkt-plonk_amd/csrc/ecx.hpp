@@ -4,7 +4,7 @@
 //
 // Value bounds carried by an XyzzX between operations (p = base-field modulus):
 //     X < 8p,  Y < 4p,  ZZ < 2p,  ZZZ < 2p,   all limbs normalised.
-// Every product below satisfies a*b < 128 p^2 <= R' * p (BN254 Fq: R'/p ~ 168; BLS12-381 Fq: 2^25).
+// Every product below satisfies a*b < 128 p^2 <= R' * p (BN254 Fq: R'/p ~ 169; BLS12-381 Fq: 2^25).
 #pragma once
 #include "ec.hpp"
 #include "fx.hpp"

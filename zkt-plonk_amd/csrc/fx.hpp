@@ -685,7 +685,9 @@ ZKT_HD bool fx_is_zero_canon(const Fx<P>& a) {  // a canonical
 // one more), 53 multiply-adds for L = 9; r = x w - q p needs only the low L limbs of x w + q (2^(29 L) - p): 90.  143
 // multiply-adds and no m-chain (v_mul_lo + mask per limb) against the Montgomery product's 171: the NTT's butterfly
 // twiddles (tables in LDS, both words per entry) use it; one-off products and memory-resident tables stay Montgomery.
-// Input: limbs <= 2^31.3 (a lazy sum or difference), value < 2^(29 L); w, wq normalised.  Output normalised, < 3p.
+// Input: limbs <= 2^31.33 (a lazy sum or difference: the NTT's fx_sub_lazy_wide reaches 2^30 + 2^30 + 2^29 = 2^31.32),
+// value < 2^(29 L); w, wq normalised.  Output normalised, < 3p.  Nine limbs only: a column of L such products must stay
+// below 2^64 (9 * 2^60.33 does, 14 * 2^60.33 does not).
 // No Montgomery factor is involved: x w mod p in whatever form x is in, w a plain canonical integer.
 template <class P>
 ZKT_HD Fx<P> fx_mul_shoup(const Fx<P>& x, const Fx<P>& w, const Fx<P>& wq) {
