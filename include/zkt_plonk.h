@@ -303,7 +303,8 @@ typedef struct {
     const uint64_t* b_evals;
     const uint64_t* c_evals;
     size_t n_rows;
-    /* the lookup table as a LookupTable IndexSet (lookup/table.rs:19): distinct values, insertion order */
+    /* the lookup table as a LookupTable IndexSet (lookup/table.rs:19): distinct values, insertion order.  A value
+     * that appears twice -> ZKT_ERR_INVALID_ARGUMENT ("lookup table holds a repeated value"). */
     const uint64_t* table;
     size_t table_len;
     /* PublicInputs BTreeMap (constraint_system/pi.rs:52-105): ascending positions and their values */
@@ -540,6 +541,16 @@ int zkt_debug_quotient(zkt_ctx* ctx, const uint64_t* challenges, const uint64_t*
  * out_z1 / out_z2: n elements each.  Montgomery words. */
 int zkt_debug_grand_products(zkt_ctx* ctx, const uint64_t* challenges, const uint64_t* const* vectors, uint64_t* out_z1,
                              uint64_t* out_z2);
+/* Plookup's h1 / h2 alone (lookup/multiset.rs:103-146 combine_split with t = table padded by zeros to n), through
+ * the prover's own round-2 code: the loaded circuit fixes n; f: n elements (what round 2 forms as q_lookup . c);
+ * table: table_len < n distinct values in insertion order (zkt_prove_inputs.table); h1_out / h2_out: n elements each.
+ * fresh = 0 reuses the sorted keys the previous call or proof left on the device, as a proof over an unchanged table
+ * does (table is then ignored unless none are resident).  Errors as zkt_prove gives them: a value of f outside the
+ * table -> ZKT_ERR_NOT_IN_TABLE, a repeated table value, table_len >= n or halves whose length is not n ->
+ * ZKT_ERR_INVALID_ARGUMENT; no circuit -> ZKT_ERR_NOT_LOADED.  Refused while a next proof is announced
+ * (zkt_prove_set_next); the next zkt_prove rebuilds its table polynomial and keys.  Host pointers, Montgomery words. */
+int zkt_debug_combine_split(zkt_ctx* ctx, const uint64_t* table, size_t table_len, const uint64_t* f, int fresh,
+                            uint64_t* h1_out, uint64_t* h2_out);
 /* kzg10's witness polynomial alone (row a12): out[0 .. len - 1) = (p(X) - p(z)) / (X - z) for the len <= n + 8 coefficients
  * p, as the prover computes it (scaled suffix sums).  Host pointers, Montgomery words. */
 int zkt_debug_open_witness(zkt_ctx* ctx, const uint64_t* coeffs, size_t len, const uint64_t* z4, uint64_t* out);

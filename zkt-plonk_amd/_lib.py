@@ -581,6 +581,7 @@ class Context:
         if rc:
             raise ZktError(rc, "zkt_ctx_create failed (no GPU? there is no CPU fallback)")
         self._h = h
+        self.circuit_log_n = None   # log2 n of the circuit loaded through this wrapper (host buffers of the debug hooks)
 
     def fork(self) -> "Context":
         """zkt_ctx_fork: a context sharing this one's key / circuit / twiddle tables, with its own stream and work buffers."""
@@ -806,6 +807,7 @@ class Context:
         L = self._L
         L.zkt_circuit_load_file.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int]
         self.check(L.zkt_circuit_load_file(self._h, pk_path.encode(), log_n))
+        self.circuit_log_n = log_n
 
     def srs_generate(self, tau: int, count: int):
         t = np.array([(tau >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)], dtype=np.uint64)
@@ -900,6 +902,7 @@ class Context:
         ptrs = (ctypes.POINTER(ctypes.c_uint64) * 10)(*[u64p(a) if a.size else ctypes.POINTER(ctypes.c_uint64)() for a in arrs])
         lens = (ctypes.c_size_t * 10)(*[a.shape[0] for a in arrs])
         self.check(self._L.zkt_circuit_load(self._h, log_n, ptrs, lens))
+        self.circuit_log_n = log_n
 
     def circuit_setup(self, log_n: int, evals):
         """proof_system::setup (setup.rs:42-166) on the device.  evals: the 10 evaluation vectors (len_k <= n, 4) in
@@ -912,6 +915,7 @@ class Context:
         out = np.zeros((10, 2 * self.fq_limbs), dtype=np.uint64)
         inf = (ctypes.c_int * 10)()
         self.check(self._L.zkt_circuit_setup(self._h, log_n, ptrs, lens, 0, u64p(out), inf))
+        self.circuit_log_n = log_n
         return out, np.array([bool(x) for x in inf])
 
     def _prepare(self, wires, n_rows, table, pi_pos, pi_vals, blinders, on_device, variables=None, idx=None, keep=()):
@@ -1026,6 +1030,22 @@ class Context:
                                                      ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
         self.check(self._L.zkt_debug_grand_products(self._h, u64p(ch), ptrs, u64p(z1), u64p(z2)))
         return z1, z2
+
+    def debug_combine_split(self, table, f, fresh: bool = True):
+        """h1, h2 (n, 4) each through the prover's round-2 code (zkt_debug_combine_split): table (table_len, 4) distinct
+        values in insertion order, f (n, 4) for the loaded circuit's n; fresh=False reuses the keys the previous call or
+        proof left on the device.  Montgomery words throughout."""
+        t = np.ascontiguousarray(table, dtype=np.uint64).reshape(-1, 4)
+        ff = np.ascontiguousarray(f, dtype=np.uint64).reshape(-1, 4)
+        if self.circuit_log_n is None or ff.shape[0] != 1 << self.circuit_log_n:
+            raise ValueError("f must hold the n elements of a circuit loaded through this Context")
+        n = ff.shape[0]
+        h1, h2 = np.empty((n, 4), dtype=np.uint64), np.empty((n, 4), dtype=np.uint64)
+        P64 = ctypes.POINTER(ctypes.c_uint64)
+        self._L.zkt_debug_combine_split.argtypes = [ctypes.c_void_p, P64, ctypes.c_size_t, P64, ctypes.c_int, P64, P64]
+        self.check(self._L.zkt_debug_combine_split(self._h, u64p(t) if t.shape[0] else None, t.shape[0], u64p(ff),
+                                                   1 if fresh else 0, u64p(h1), u64p(h2)))
+        return h1, h2
 
     def check_epk_file(self, path: str):
         """zkt_circuit_check_epk_file: None when every vector of the reference CLI's --epk file equals the loaded circuit's

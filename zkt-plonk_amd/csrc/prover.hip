@@ -384,6 +384,7 @@ struct Prover {
         uint32_t* d_odd = S.lk_u32 + 3 * S.lk_cap;
         uint32_t* d_hits = S.lk_u32 + 4 * S.lk_cap;   // zero between proofs (k_lookup_starts clears what it reads)
         if (fresh || S.lk_nkeys == 0) {
+            S.lk_nkeys = 0;   // no resident keys until the new ones are checked and uploaded
             // host staging lives in the circuit state (the copies below are asynchronous and nothing here waits)
             static_assert(sizeof(F) == 32, "scalar field element = 8 words");
             S.lk_host_keys.resize((table_len + 1) * 8);
@@ -428,6 +429,11 @@ struct Prover {
                 return false;
             };
             std::sort(order.begin(), order.end(), less);
+            // a LookupTable is an IndexSet (lookup/table.rs:19): equal values, now adjacent, would each get their own
+            // count and split the hits between them, a multiset the reference cannot build
+            for (uint32_t i = 1; i < nk; ++i)
+                if (!less(order[i - 1], order[i]))
+                    return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "lookup table holds a repeated value");
             sorted.resize(nk);
             for (uint32_t i = 0; i < nk; ++i) sorted[i] = keys[order[i]];
             ZKT_HIP(c, hipMemcpyAsync(d_keys, keys.data(), nk * 32, hipMemcpyHostToDevice, c->stream));
@@ -1397,6 +1403,28 @@ static int debug_grand_products_t(zkt_ctx* c, const uint64_t* ch, const uint64_t
     return ZKT_OK;
 }
 
+// Round 2's h1 / h2 alone: f goes where round 2 puts q_lookup . c, then the prover's own combine_split runs
+template <class C>
+static int debug_combine_split_t(zkt_ctx* c, const uint64_t* table, size_t table_len, const uint64_t* f, bool fresh,
+                                 uint64_t* h1_out, uint64_t* h2_out) {
+    CircuitState& S = *c->circuit;
+    const size_t n = S.n;
+    MerlinHostTranscript tr("zkt_debug_combine_split");   // combine_split draws no challenge
+    Prover<C> p(c, S, tr);
+    ZKT_HIP(c, hipMemsetAsync(S.status, 0, 4, c->stream));
+    ZKT_HIP(c, hipMemcpyAsync(S.ev[4], f, n * 32, hipMemcpyHostToDevice, c->stream));
+    int rc = p.combine_split(table, table_len, fresh);
+    if (!rc) rc = p.check_status();   // synchronises; bit 4 -> ZKT_ERR_NOT_IN_TABLE, bit 8 -> ZKT_ERR_INVALID_ARGUMENT
+    if (rc) {
+        (void)hipStreamSynchronize(c->stream);   // the uploads may still read the caller's f
+        return rc;
+    }
+    ZKT_HIP(c, hipMemcpyAsync(h1_out, S.ev[5], n * 32, hipMemcpyDeviceToHost, c->stream));
+    ZKT_HIP(c, hipMemcpyAsync(h2_out, S.ev[6], n * 32, hipMemcpyDeviceToHost, c->stream));
+    ZKT_HIP(c, hipStreamSynchronize(c->stream));
+    return ZKT_OK;
+}
+
 // A file the reference CLI wrote with --epk (bin/src/main.rs:108-109: ExtendedProverKey<F>, keys/mod.rs:148-174) against the
 // extended key this circuit's ProverKey gives on the device (keys/mod.rs:78-146 as zkt_circuit_load runs it): every vector is
 // recomputed in arkworks' own form (the resident cosets partly live in the quotient kernel's radix), turned canonical,
@@ -1756,6 +1784,21 @@ int zkt_debug_grand_products(zkt_ctx* c, const uint64_t* challenges, const uint6
     c->circuit->prefetch_stage = 0;   // the work buffers are shared with an announced proof's early rounds
     if (c->curve == ZKT_CURVE_BN254) return debug_grand_products_t<Bn254Curve>(c, challenges, vectors, out_z1, out_z2);
     return debug_grand_products_t<Bls381Curve>(c, challenges, vectors, out_z1, out_z2);
+}
+
+int zkt_debug_combine_split(zkt_ctx* c, const uint64_t* table, size_t table_len, const uint64_t* f, int fresh,
+                            uint64_t* h1_out, uint64_t* h2_out) {
+    if (!c || !f || !h1_out || !h2_out || (table_len && !table)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
+    if (!c->circuit) return set_err(c, ZKT_ERR_NOT_LOADED, "no circuit loaded (zkt_circuit_load)");
+    CircuitState& S = *c->circuit;
+    if (S.has_next) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "zkt_debug_combine_split: a next proof is announced");
+    if (table_len >= S.n) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "max table size is equal or larger than n");
+    (void)hipSetDevice(c->device);
+    S.prefetch_stage = 0;   // the work buffers are shared with an announced proof's early rounds
+    // the keys this call leaves resident need not be those of the cached table polynomial: the next proof rebuilds both
+    S.t_cached = false;
+    if (c->curve == ZKT_CURVE_BN254) return debug_combine_split_t<Bn254Curve>(c, table, table_len, f, fresh != 0, h1_out, h2_out);
+    return debug_combine_split_t<Bls381Curve>(c, table, table_len, f, fresh != 0, h1_out, h2_out);
 }
 
 int zkt_circuit_check_epk_file(zkt_ctx* c, const char* epk_path, int* first_mismatch_vector, size_t* mismatch_at) {
