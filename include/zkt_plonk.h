@@ -81,6 +81,9 @@ int zkt_ctx_synchronize(zkt_ctx* ctx);
  * commitments taken in the Lagrange basis (their pairs are few, they would dilute the dense kernel's average);
  * "host_wait": idle time of the context's stream across the prover's host round trips (from the moment the stream
  * drains while the host waits for a round's commitments or evaluations to the next launch; six per proof).
+ * The KZG seam (zkt_kzg_commit_batch / zkt_kzg_open): "kzg_commit_batch" (the whole batch of MSMs on the stream),
+ * "kzg_open_upload" (the coefficients' copy to HBM), "kzg_open_combine" (power tables and the fused combination /
+ * evaluation pass), "kzg_open_divide" (division by X - z) and "kzg_open_msm" (the witness commitment).
  * A scope that covers a batch counts its units in `calls` (the three commitments of a round grouped and accumulated as one
  * batch of launches: 3); "<name>#launches" returns the number of recorded scopes instead.
  * on = 0: off; 1: every scope; 2: only "msm_accumulate" and "host_wait" -- the level for timing the dominant kernel
@@ -221,6 +224,38 @@ int zkt_msm_g1_bases_dev(zkt_ctx* ctx, const void* d_bases_xy_mont, const void* 
 /* Digit width c and number of windows zkt_msm_g1_bases uses for n points (0s for n = 0); n > ZKT_MSM_BASES_MAX ->
  * ZKT_ERR_INVALID_ARGUMENT. */
 int zkt_msm_bases_info(zkt_ctx* ctx, size_t n, int scalars_montgomery, int* window_bits, int* windows);
+
+/* ---- KZG commitment seam (PC::commit / PC::open of a KZG10 wrapper that keeps the host prover) ----------
+ * zkt_kzg_commit_batch: PC::commit(ck, [p_0 .. p_(k-1)], None) in ONE call, entry j = sum_i p_j[i] * powers_of_g[i].
+ * The k MSMs go out on the prover's schedule (grouped launches where the key size gains from them, the bucket reductions
+ * overlapping the next MSM) instead of one blocking zkt_msm_g1 each; the host form uploads polynomial j + 1 on a copy
+ * stream while polynomial j's MSM runs.  scalars_montgomery as in zkt_msm_g1.
+ * zkt_kzg_open: open_individual_opening_challenges with challenges c_j (opening_challenges(j), j < k):
+ * w = commit(floor((sum_j c_j p_j) / (X - z))), and out_evals[j] = p_j(z) when out_evals_mont is not NULL (k x 4 u64).
+ * Coefficients, challenges and the point are Montgomery limbs, as they sit in arkworks memory.
+ * Output: entry j at out_xy_mont + j * 2L (L = 4 on BN254, 6 on BLS12-381), x limbs then y limbs as zkt_msm_g1; the
+ * identity is written as (0,0) with its flag set to 1; out_is_infinity may be NULL.
+ * Lengths: lens[j] = 0 is the zero polynomial; k = 0 -> ZKT_OK, nothing written; k > ZKT_KZG_BATCH_MAX ->
+ * ZKT_ERR_INVALID_ARGUMENT; any lens[j] above the loaded powers -> ZKT_ERR_TOO_MANY_COEFFICIENTS, checked before any work
+ * is enqueued (no output is written then).  Any point z is valid, z = 0 (the witness is the combination shifted down by one
+ * coefficient) and roots of unity included; a combination of degree < 1 gives the identity.
+ * Needs a loaded SRS (ZKT_ERR_NOT_LOADED otherwise) and no circuit; a key loaded as a slice (zkt_srs_load_slice /
+ * _generate_slice) -> ZKT_ERR_INVALID_ARGUMENT.  Local: no collective, even with a communicator set.  The scratch memory
+ * is the call's own (allocated on first use, grown as needed, freed by zkt_ctx_destroy; a forked context gets its own); the
+ * circuit's buffers are never touched, and a proof announced with zkt_prove_set_next yields the same bytes (its early work
+ * is redone when the call took the MSM slots it used).  Synchronises the stream.
+ * _dev: the coefficient vectors already in HBM (d_coeffs[j] may be NULL when lens[j] = 0); results still go to host memory. */
+#define ZKT_KZG_BATCH_MAX 32
+int zkt_kzg_commit_batch(zkt_ctx* ctx, const uint64_t* const* coeffs, const size_t* lens, int k,
+                         int scalars_montgomery, uint64_t* out_xy_mont, int* out_is_infinity);
+int zkt_kzg_commit_batch_dev(zkt_ctx* ctx, const void* const* d_coeffs, const size_t* lens, int k,
+                             int scalars_montgomery, uint64_t* out_xy_mont, int* out_is_infinity);
+int zkt_kzg_open(zkt_ctx* ctx, const uint64_t* const* coeffs, const size_t* lens, int k,
+                 const uint64_t* challenges_mont, const uint64_t* point_mont,
+                 uint64_t* out_w_xy_mont, int* out_w_is_infinity, uint64_t* out_evals_mont);
+int zkt_kzg_open_dev(zkt_ctx* ctx, const void* const* d_coeffs, const size_t* lens, int k,
+                     const uint64_t* challenges_mont, const uint64_t* point_mont,
+                     uint64_t* out_w_xy_mont, int* out_w_is_infinity, uint64_t* out_evals_mont);
 
 /* ---- Commitments of evaluation vectors (Lagrange-basis key) ------------------------------------------
  * The reference commits to t, h1, h2 and z2 through their coefficients (prove.rs:145-180,225-251: poly_from_evals,

@@ -50,6 +50,7 @@ pub struct ZktProveInputs {
 pub const ZKT_VARIABLE_ZERO: u32 = 0xFFFF_FFFF;
 pub const ZKT_CURVE_BN254: c_int = 0;
 pub const ZKT_CURVE_BLS12_381: c_int = 1;
+pub const ZKT_KZG_BATCH_MAX: usize = 32;   // include/zkt_plonk.h: most polynomials per zkt_kzg_commit_batch / zkt_kzg_open
 
 extern "C" {
     pub fn zkt_ctx_create(curve_id: c_int, device_id: c_int, out: *mut *mut ZktCtx) -> c_int;
@@ -65,6 +66,16 @@ extern "C" {
     pub fn zkt_msm_g1(ctx: *mut ZktCtx, scalars: *const u64, len: usize, base_offset: usize, scalars_montgomery: c_int,
                       out_xy_mont: *mut u64, out_is_infinity: *mut c_int) -> c_int;
     pub fn zkt_ctx_fork(ctx: *mut ZktCtx, out: *mut *mut ZktCtx) -> c_int;
+    pub fn zkt_kzg_commit_batch(ctx: *mut ZktCtx, coeffs: *const *const u64, lens: *const usize, k: c_int,
+                                scalars_montgomery: c_int, out_xy_mont: *mut u64, out_is_infinity: *mut c_int) -> c_int;
+    pub fn zkt_kzg_commit_batch_dev(ctx: *mut ZktCtx, d_coeffs: *const *const c_void, lens: *const usize, k: c_int,
+                                    scalars_montgomery: c_int, out_xy_mont: *mut u64, out_is_infinity: *mut c_int) -> c_int;
+    pub fn zkt_kzg_open(ctx: *mut ZktCtx, coeffs: *const *const u64, lens: *const usize, k: c_int, challenges_mont: *const u64,
+                        point_mont: *const u64, out_w_xy_mont: *mut u64, out_w_is_infinity: *mut c_int,
+                        out_evals_mont: *mut u64) -> c_int;
+    pub fn zkt_kzg_open_dev(ctx: *mut ZktCtx, d_coeffs: *const *const c_void, lens: *const usize, k: c_int,
+                            challenges_mont: *const u64, point_mont: *const u64, out_w_xy_mont: *mut u64,
+                            out_w_is_infinity: *mut c_int, out_evals_mont: *mut u64) -> c_int;
     pub fn zkt_commit_evals_dev(ctx: *mut ZktCtx, d_evals: *const c_void, blinders: *const u64, k: c_int, path: c_int,
                                 out_xy_mont: *mut u64, out_is_infinity: *mut c_int) -> c_int;
     pub fn zkt_ctx_set_lagrange(ctx: *mut ZktCtx, on: c_int) -> c_int;

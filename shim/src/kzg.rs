@@ -1,6 +1,6 @@
 //! `PC: HomomorphicCommitment<F>` (plonk-core/src/commitment.rs:10-46) on the GPU: `GpuKZG10<E>` has every associated type
 //! of `SonicKZG10<E, DensePolynomial<E::Fr>>` (keys, commitments and proofs serialise identically; `setup`, `trim` and the
-//! checks are arkworks'), `commit` and `open` run their multi-scalar multiplications through `zkt_msm_g1`.
+//! checks are arkworks'), `commit` and `open` run on the device through `zkt_kzg_commit_batch` / `zkt_kzg_open` (one call per commit / opening).
 //!
 //! UNCOMPILED (no Rust toolchain in the authoring image, see lib.rs): written against ark-ec / ark-poly-commit 0.3.0 as
 //! recalled -- in particular the trait's required items (`open_individual_opening_challenges`,
@@ -91,16 +91,32 @@ where
     E::G1Affine: G1FromXY,
     <E::G1Affine as AffineCurve>::BaseField: PrimeField,
 {
-    /// kzg10::commit without hiding = MSM(powers_of_g[..len], coeffs); the scalars go over as they lie in memory
-    /// (Montgomery form, `montgomery = 1`): `into_repr()` is the device's business.
-    fn commit_one(coeffs: &[E::Fr]) -> Result<kzg10::Commitment<E>, ark_poly_commit::Error> {
-        let mut xy = [0u64; 12];   // 2 x 6 limbs covers Fq381
-        let mut inf: c_int = 0;
-        with_ctx::<E::Fr, _>(|ctx| {
-            check(ctx, unsafe { ffi::zkt_msm_g1(ctx, coeffs.as_ptr() as *const u64, coeffs.len(), 0, 1, xy.as_mut_ptr(), &mut inf) })
-        })
-        .map_err(|_| ark_poly_commit::Error::TooManyCoefficients { num_coefficients: coeffs.len(), num_powers: 0 })?;
-        Ok(kzg10::Commitment(g1_from_limbs::<E::G1Affine>(&xy, inf != 0)))
+    /// kzg10::commit without hiding of every polynomial in ONE `zkt_kzg_commit_batch` = MSM(powers_of_g[..len], coeffs)
+    /// each, on the prover's schedule; the scalars go over as they lie in memory (Montgomery form, `montgomery = 1`):
+    /// `into_repr()` is the device's business.  At most ZKT_KZG_BATCH_MAX (32) per call: longer lists go in pieces.
+    fn commit_batch(polys: &[&[E::Fr]]) -> Result<Vec<kzg10::Commitment<E>>, ark_poly_commit::Error> {
+        let mut out = Vec::with_capacity(polys.len());
+        for part in polys.chunks(ffi::ZKT_KZG_BATCH_MAX) {
+            let ptrs: Vec<*const u64> = part.iter().map(|p| p.as_ptr() as *const u64).collect();
+            let lens: Vec<usize> = part.iter().map(|p| p.len()).collect();
+            let mut xy = vec![0u64; 12 * part.len()];
+            let mut inf: Vec<c_int> = vec![0; part.len()];
+            with_ctx::<E::Fr, _>(|ctx| {
+                check(ctx, unsafe {
+                    ffi::zkt_kzg_commit_batch(ctx, ptrs.as_ptr(), lens.as_ptr(), part.len() as c_int, 1, xy.as_mut_ptr(),
+                                              inf.as_mut_ptr())
+                })
+            })
+            .map_err(|_| ark_poly_commit::Error::TooManyCoefficients {
+                num_coefficients: lens.iter().copied().max().unwrap_or(0),
+                num_powers: 0,
+            })?;
+            let w = 2 * <<E::G1Affine as AffineCurve>::BaseField as PrimeField>::BigInt::NUM_LIMBS;
+            for j in 0..part.len() {
+                out.push(kzg10::Commitment(g1_from_limbs::<E::G1Affine>(&xy[w * j..w * (j + 1)], inf[j] != 0)));
+            }
+        }
+        Ok(out)
     }
 }
 
@@ -139,15 +155,19 @@ where
         Poly<E>: 'a,
     {
         let _ = ck;   // on the device since load_committer_key
-        let mut commits = Vec::new();
-        let mut rands = Vec::new();
-        for p in polynomials {
+        let polys: Vec<&LabeledPolynomial<E::Fr, Poly<E>>> = polynomials.into_iter().collect();
+        for p in &polys {
             // plonk-core commits without degree bounds or hiding (prove.rs:133-135,178-180,249-251,306-308,373-375);
             // anything else is not this path's business
             assert!(p.degree_bound().is_none() && p.hiding_bound().is_none(), "GpuKZG10: plain commitments only");
-            commits.push(LabeledCommitment::new(p.label().clone(), Self::commit_one(p.polynomial().coeffs())?, None));
-            rands.push(Self::Randomness::empty());
         }
+        let coeffs: Vec<&[E::Fr]> = polys.iter().map(|p| p.polynomial().coeffs()).collect();
+        let commits = Self::commit_batch(&coeffs)?
+            .into_iter()
+            .zip(polys.iter())
+            .map(|(c, p)| LabeledCommitment::new(p.label().clone(), c, None))
+            .collect();
+        let rands = polys.iter().map(|_| Self::Randomness::empty()).collect();
         Ok((commits, rands))
     }
 
@@ -169,13 +189,25 @@ where
         Poly<E>: 'a,
     {
         let _ = ck;
-        let mut combined = Poly::<E>::zero();
-        for (k, p) in labeled_polynomials.into_iter().enumerate() {
-            combined += (opening_challenges(k as u64), p.polynomial());
-        }
-        let divisor = Poly::<E>::from_coefficients_vec(vec![-*point, E::Fr::from(1u64)]);
-        let witness = &combined / &divisor;
-        Ok(kzg10::Proof { w: Self::commit_one(&witness.coeffs)?.0, random_v: None })
+        // ONE zkt_kzg_open: the combination sum_k c_k p_k, its division by X - z and the witness commitment, on the device
+        let polys: Vec<&[E::Fr]> = labeled_polynomials.into_iter().map(|p| p.polynomial().coeffs()).collect();
+        assert!(polys.len() <= ffi::ZKT_KZG_BATCH_MAX, "GpuKZG10: at most 32 polynomials per opening");
+        let challenges: Vec<E::Fr> = (0..polys.len()).map(|k| opening_challenges(k as u64)).collect();
+        let ptrs: Vec<*const u64> = polys.iter().map(|p| p.as_ptr() as *const u64).collect();
+        let lens: Vec<usize> = polys.iter().map(|p| p.len()).collect();
+        let mut xy = [0u64; 12];   // 2 x 6 limbs covers Fq381
+        let mut inf: c_int = 0;
+        with_ctx::<E::Fr, _>(|ctx| {
+            check(ctx, unsafe {
+                ffi::zkt_kzg_open(ctx, ptrs.as_ptr(), lens.as_ptr(), polys.len() as c_int, challenges.as_ptr() as *const u64,
+                                  point as *const E::Fr as *const u64, xy.as_mut_ptr(), &mut inf, core::ptr::null_mut())
+            })
+        })
+        .map_err(|_| ark_poly_commit::Error::TooManyCoefficients {
+            num_coefficients: lens.iter().copied().max().unwrap_or(0),
+            num_powers: 0,
+        })?;
+        Ok(kzg10::Proof { w: g1_from_limbs::<E::G1Affine>(&xy, inf != 0), random_v: None })
     }
 
     fn check_individual_opening_challenges<'a>(

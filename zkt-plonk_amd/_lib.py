@@ -14,6 +14,7 @@ _LIB = os.environ.get("ZKT_LIB_PATH") or os.path.join(_HERE, "libzkt_plonk_hip.s
 _HEADER = os.path.join(_HERE, "..", "include", "zkt_plonk.h")
 
 MSM_BASES_MAX = 1 << 22   # ZKT_MSM_BASES_MAX: most points zkt_msm_g1_bases takes
+KZG_BATCH_MAX = 32        # ZKT_KZG_BATCH_MAX: most polynomials one zkt_kzg_commit_batch / zkt_kzg_open takes
 CURVE_BN254 = 0
 CURVE_BLS12_381 = 1
 _CURVES = {"bn254": 0, "bls12_381": 1, "bls12-381": 1, 0: 0, 1: 1}
@@ -123,6 +124,12 @@ def _bind_optional(L):
         L.zkt_msm_g1_bases.argtypes = [vp, u64p, u64p, ctypes.c_size_t, ctypes.c_int, u64p, ip]
         L.zkt_msm_g1_bases_dev.argtypes = [vp, vp, vp, ctypes.c_size_t, ctypes.c_int, u64p, ip]
         L.zkt_msm_bases_info.argtypes = [vp, ctypes.c_size_t, ctypes.c_int, ip, ip]
+    if hasattr(L, "zkt_kzg_commit_batch"):
+        pp, szp = ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)
+        L.zkt_kzg_commit_batch.argtypes = [vp, pp, szp, ctypes.c_int, ctypes.c_int, u64p, ip]
+        L.zkt_kzg_commit_batch_dev.argtypes = [vp, pp, szp, ctypes.c_int, ctypes.c_int, u64p, ip]
+        L.zkt_kzg_open.argtypes = [vp, pp, szp, ctypes.c_int, u64p, u64p, u64p, ip, u64p]
+        L.zkt_kzg_open_dev.argtypes = [vp, pp, szp, ctypes.c_int, u64p, u64p, u64p, ip, u64p]
 
 
 ALL_GATHER_CB = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
@@ -864,6 +871,63 @@ class Context:
         c, w = ctypes.c_int(0), ctypes.c_int(0)
         self.check(self._L.zkt_msm_bases_info(self._h, n, int(montgomery), ctypes.byref(c), ctypes.byref(w)))
         return dict(window_bits=c.value, windows=w.value)
+
+    # ---- KZG commitment seam (zkt_kzg_commit_batch / zkt_kzg_open) ----
+    def _kzg_polys(self, polys):
+        arrs = [np.ascontiguousarray(p, dtype=np.uint64).reshape(-1, 4) for p in polys]
+        ptrs = (ctypes.c_void_p * max(len(arrs), 1))(*[a.ctypes.data if a.shape[0] else None for a in arrs])
+        return arrs, ptrs, self._kzg_lens([a.shape[0] for a in arrs])
+
+    @staticmethod
+    def _kzg_lens(lens):
+        return (ctypes.c_size_t * max(len(lens), 1))(*[int(n) for n in lens])
+
+    def _kzg_points(self, out, inf, k):
+        W = 2 * self.fq_limbs
+        return [(out[j * W:(j + 1) * W].copy(), bool(inf[j])) for j in range(k)]
+
+    def kzg_commit_batch(self, polys, montgomery: bool = True):
+        """zkt_kzg_commit_batch: PC::commit of every coefficient vector in `polys` (arrays of (len, 4) u64) in one call ->
+        [(xy Montgomery limbs (2*fq_limbs,), is_infinity)] in order"""
+        arrs, ptrs, lens = self._kzg_polys(polys)
+        k = len(arrs)
+        out = np.zeros(max(k, 1) * 2 * self.fq_limbs, dtype=np.uint64)
+        inf = (ctypes.c_int * max(k, 1))()
+        self.check(self._L.zkt_kzg_commit_batch(self._h, ptrs, lens, k, int(montgomery), u64p(out), inf))
+        return self._kzg_points(out, inf, k)
+
+    def kzg_commit_batch_dev(self, d_ptrs, lens, montgomery: bool = True):
+        """zkt_kzg_commit_batch_dev: the coefficient vectors already in HBM (device pointers, lengths in elements)"""
+        k = len(lens)
+        ptrs = (ctypes.c_void_p * max(k, 1))(*[int(d) if d else None for d in d_ptrs])
+        out = np.zeros(max(k, 1) * 2 * self.fq_limbs, dtype=np.uint64)
+        inf = (ctypes.c_int * max(k, 1))()
+        self.check(self._L.zkt_kzg_commit_batch_dev(self._h, ptrs, self._kzg_lens(lens), k, int(montgomery), u64p(out), inf))
+        return self._kzg_points(out, inf, k)
+
+    def _kzg_open_call(self, fn, ptrs, lens, k, challenges, z, evals):
+        ch = np.ascontiguousarray(challenges, dtype=np.uint64).reshape(-1, 4)
+        if ch.shape[0] != k:
+            raise ValueError("kzg_open: %d polynomials, %d challenges" % (k, ch.shape[0]))
+        zz = np.ascontiguousarray(z, dtype=np.uint64).reshape(4)
+        w = np.zeros(2 * self.fq_limbs, dtype=np.uint64)
+        inf = ctypes.c_int(0)
+        ev = np.zeros((max(k, 1), 4), dtype=np.uint64)
+        self.check(fn(self._h, ptrs, lens, k, u64p(ch) if k else None, u64p(zz), u64p(w), ctypes.byref(inf),
+                      u64p(ev) if evals else None))
+        return (w, bool(inf.value)), (ev[:k].copy() if evals else None)
+
+    def kzg_open(self, polys, challenges, z, evals: bool = True):
+        """zkt_kzg_open: w = commit(floor((sum_j challenges[j] polys[j]) / (X - z))), all Montgomery ->
+        ((xy, is_infinity), evaluations p_j(z) as a (k, 4) array, or None when evals is False)"""
+        arrs, ptrs, lens = self._kzg_polys(polys)
+        return self._kzg_open_call(self._L.zkt_kzg_open, ptrs, lens, len(arrs), challenges, z, evals)
+
+    def kzg_open_dev(self, d_ptrs, lens, challenges, z, evals: bool = True):
+        """zkt_kzg_open_dev: kzg_open over coefficient vectors already in HBM"""
+        k = len(lens)
+        ptrs = (ctypes.c_void_p * max(k, 1))(*[int(d) if d else None for d in d_ptrs])
+        return self._kzg_open_call(self._L.zkt_kzg_open_dev, ptrs, self._kzg_lens(lens), k, challenges, z, evals)
 
     def msm_info(self):
         c, w, n = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_size_t(0)

@@ -267,6 +267,7 @@ void zkt_ctx_destroy(zkt_ctx* c) {
     c->ntt_plans.clear();
     c->msm.reset();
     c->msmb.reset();   // zkt_msm_g1_bases scratch: its device buffers are freed with c->owned below, its pinned rows here
+    c->kzg.reset();    // the KZG seam's copy stream and events; its device buffers go with c->owned
     c->circuit.reset();
     if (c->comm.pinned) (void)hipHostFree(c->comm.pinned);
     for (void* p : c->owned) (void)hipFree(p);

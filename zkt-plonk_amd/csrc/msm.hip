@@ -27,6 +27,7 @@
 #include "msm.hpp"
 
 #include <algorithm>
+#include <functional>
 #include <type_traits>
 #include <cstdlib>
 #include <cstring>
@@ -1586,6 +1587,23 @@ int msm_flush_tails(zkt_ctx* c) {
     if (!c->msm) return ZKT_OK;
     if (c->curve == ZKT_CURVE_BN254) return msm_launch_tails<Bn254Curve>(c);
     return msm_launch_tails<Bls381Curve>(c);
+}
+// Commitments begun together on the prover's schedule (a round of zkt_prove, zkt_kzg_commit_batch): batches of up to
+// MSM_BATCH launches-as-one when `grouped` (msm_batches_grouping), one launch sequence per MSM otherwise -- either way the
+// bucket reduction of one overlaps the accumulation of the next -- then the deferred tails (small keys) as one batch.
+// ready(j), when given, runs before the MSM of entry j is enqueued (kzg.hip: the upload of its scalars).
+int msm_begin_many(zkt_ctx* c, int k, const void* const* d_scalars, const size_t* ns, int mont, const int* slots, const int* tbls,
+                   bool grouped, const std::function<int(int)>& ready) {
+    for (int at = 0; at < k;) {
+        const int kk = grouped ? std::min(MSM_BATCH, k - at) : 1;
+        for (int j = at; j < at + kk && ready; ++j)
+            if (int rc = ready(j)) return rc;
+        const int rc = grouped ? msm_begin_batch(c, kk, d_scalars + at, ns + at, mont, slots + at, tbls + at)
+                               : msm_begin(c, d_scalars[at], ns[at], 0, mont, slots[at], tbls[at]);
+        if (rc) return rc;
+        at += kk;
+    }
+    return msm_flush_tails(c);
 }
 int msm_end(zkt_ctx* c, int slot, uint64_t* out_xy) {
     if (c->curve == ZKT_CURVE_BN254) {

@@ -91,6 +91,7 @@ __global__ void k_lincomb(LinCombDev a, Fe<P>* out, size_t n) {
 constexpr int EV_E = 8;
 constexpr int EV_SEG = 256 * EV_E;
 constexpr int EV_PW = 257;   // x^0 .. x^255 and x^256 per polynomial
+static_assert(EV_PW == OPEN_PW_ROW, "poly.hpp publishes the row length of the opening power tables");
 
 // pw[k][t] = point[k]^t for t = 0..256, followed by pw[k][257 + b] = point[k]^(2048 b) for b < nblk
 template <class P>
@@ -972,28 +973,58 @@ int quotient_split_blind(zkt_ctx* c, const void* q, size_t n, const void* d_b0b1
     ZKT_DISPATCH(c, quot_split_t, q, n, d_b0b1, q_lo, q_mid, q_hi, d_status);
 }
 
-template <class P> static int open_witness_t(zkt_ctx* c, const void* p, size_t len, const uint32_t* z, const uint32_t* zinv, void* ta, void* tb, void* scan_tmp, void* out, void* d_powers) {
-    if (len == 0) return ZKT_OK;
-    // w_j = z^-(j+1) * sum_{i > j} p_i z^i: scale by z^i, suffix sums, scale by z^-(j+1)
-    const Fe<P> zz = host_fe<P>(z), zi = host_fe<P>(zinv);
-    Fe<P>* pw = (Fe<P>*)d_powers;
-    const int E = ow_elems(len);
-    const unsigned blocks = (unsigned)ow_blocks(len);
-    const Fe<P>* blk = pw + 2 * EV_PW;
-    hipLaunchKernelGGL(k_pow_tables<P>, dim3(1), dim3(OW_THREADS), 0, c->stream, zz, zi, pw, (int)blocks, E);
-    hipLaunchKernelGGL(k_mul_pow<P>, dim3(blocks), dim3(256), 0, c->stream, (const Fe<P>*)p, (Fe<P>*)ta, len, len,
-                       (const Fe<P>*)pw, blk, E, 0);
-    ZKT_HIP(c, hipGetLastError());
-    int rc = scan_t<P, OpAdd>(c, (const Fe<P>*)ta, (Fe<P>*)tb, len, true, (Fe<P>*)scan_tmp);
-    if (rc) return rc;
-    // out[j] = S[j + 1] * zinv^(j + 1) for j + 1 < len, zero at j = len - 1
-    hipLaunchKernelGGL(k_mul_pow<P>, dim3(blocks), dim3(256), 0, c->stream, (const Fe<P>*)tb + 1, (Fe<P>*)out, len - 1, len,
-                       (const Fe<P>*)pw + EV_PW, blk + blocks, E, 1);
+int open_elems(size_t len) { return ow_elems(len); }
+size_t open_blocks(size_t len) { return ow_blocks(len); }
+template <class P> static int open_pow_tables_t(zkt_ctx* c, const uint32_t* z, const uint32_t* zinv, void* d_powers, size_t len) {
+    hipLaunchKernelGGL(k_pow_tables<P>, dim3(1), dim3(OW_THREADS), 0, c->stream, host_fe<P>(z), host_fe<P>(zinv), (Fe<P>*)d_powers,
+                       (int)ow_blocks(len), ow_elems(len));
     ZKT_HIP(c, hipGetLastError());
     return ZKT_OK;
 }
+int open_pow_tables(zkt_ctx* c, const uint32_t z[8], const uint32_t z_inv[8], void* d_powers, size_t len) {
+    ZKT_DISPATCH(c, open_pow_tables_t, z, z_inv, d_powers, len);
+}
+// out[j] = S[j + 1] * zinv^(j + 1) for j + 1 < len, zero at j = len - 1, where S is the suffix sum of t (t_i = p_i z^i)
+template <class P> static int open_divide_t(zkt_ctx* c, const void* t, size_t len, void* tb, void* scan_tmp, void* out, const void* d_powers) {
+    if (len == 0) return ZKT_OK;
+    const Fe<P>* pw = (const Fe<P>*)d_powers;
+    const int E = ow_elems(len);
+    const unsigned blocks = (unsigned)ow_blocks(len);
+    int rc = scan_t<P, OpAdd>(c, (const Fe<P>*)t, (Fe<P>*)tb, len, true, (Fe<P>*)scan_tmp);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_mul_pow<P>, dim3(blocks), dim3(256), 0, c->stream, (const Fe<P>*)tb + 1, (Fe<P>*)out, len - 1, len,
+                       pw + EV_PW, pw + 2 * EV_PW + blocks, E, 1);
+    ZKT_HIP(c, hipGetLastError());
+    return ZKT_OK;
+}
+int open_divide(zkt_ctx* c, const void* t, size_t len, void* d_tmp, void* d_scan_tmp, void* out, const void* d_powers) {
+    ZKT_DISPATCH(c, open_divide_t, t, len, d_tmp, d_scan_tmp, out, d_powers);
+}
+
+template <class P> static int open_witness_t(zkt_ctx* c, const void* p, size_t len, const uint32_t* z, const uint32_t* zinv, void* ta, void* tb, void* scan_tmp, void* out, void* d_powers) {
+    if (len == 0) return ZKT_OK;
+    // w_j = z^-(j+1) * sum_{i > j} p_i z^i: scale by z^i, suffix sums, scale by z^-(j+1)
+    Fe<P>* pw = (Fe<P>*)d_powers;
+    const int E = ow_elems(len);
+    const unsigned blocks = (unsigned)ow_blocks(len);
+    int rc = open_pow_tables_t<P>(c, z, zinv, d_powers, len);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_mul_pow<P>, dim3(blocks), dim3(256), 0, c->stream, (const Fe<P>*)p, (Fe<P>*)ta, len, len,
+                       (const Fe<P>*)pw, (const Fe<P>*)pw + 2 * EV_PW, E, 0);
+    ZKT_HIP(c, hipGetLastError());
+    return open_divide_t<P>(c, ta, len, tb, scan_tmp, out, d_powers);
+}
 int open_witness(zkt_ctx* c, const void* p, size_t len, const uint32_t z[8], const uint32_t z_inv[8], void* d_tmp_a, void* d_tmp_b, void* d_scan_tmp, void* out, void* d_powers) {
     ZKT_DISPATCH(c, open_witness_t, p, len, z, z_inv, d_tmp_a, d_tmp_b, d_scan_tmp, out, d_powers);
+}
+
+template <class P> static int sum_rows_t(zkt_ctx* c, const void* partials, int nblk, int rows, void* out) {
+    hipLaunchKernelGGL(k_eval_final<P>, dim3(rows), dim3(256), 0, c->stream, (const Fe<P>*)partials, nblk, (Fe<P>*)out);
+    ZKT_HIP(c, hipGetLastError());
+    return ZKT_OK;
+}
+int poly_sum_rows(zkt_ctx* c, const void* d_partials, int nblk, int rows, void* d_out) {
+    ZKT_DISPATCH(c, sum_rows_t, d_partials, nblk, rows, d_out);
 }
 
 template <class P> static int gen_powers_t(zkt_ctx* c, void* out, size_t n, const uint32_t* base, const uint32_t* scale) {

@@ -92,6 +92,16 @@ int quotient_split_blind(zkt_ctx* c, const void* q, size_t n, const void* d_b0b1
 int open_witness(zkt_ctx* c, const void* p, size_t len, const uint32_t z[8], const uint32_t z_inv[8], void* d_tmp_a, void* d_tmp_b,
                  void* d_scan_tmp, void* out, void* d_powers /* open_witness_powers(len) elements of scratch */);
 size_t open_witness_powers(size_t maxlen);   // elements: the powers of z and 1/z the two scalings read
+// open_witness in stages (kzg.hip runs a first stage of its own).  d_powers (open_witness_powers(len) elements) after
+// open_pow_tables: z^0 .. z^256 | zinv^0 .. zinv^256 (OPEN_PW_ROW each), then z^(256 E b) and zinv^(256 E b) for
+// b < open_blocks(len), E = open_elems(len).  open_divide: out[j] = zinv^(j+1) sum_{i > j} t_i (j < len - 1), zero at len - 1.
+constexpr int OPEN_PW_ROW = 257;
+int open_elems(size_t len);
+size_t open_blocks(size_t len);
+int open_pow_tables(zkt_ctx* c, const uint32_t z[8], const uint32_t z_inv[8], void* d_powers, size_t len);
+int open_divide(zkt_ctx* c, const void* t, size_t len, void* d_tmp, void* d_scan_tmp, void* out, const void* d_powers);
+// out[r] = sum_b partials[r * nblk + b], r < rows (per-workgroup partial sums of rows evaluations)
+int poly_sum_rows(zkt_ctx* c, const void* d_partials, int nblk, int rows, void* d_out);
 // table generation
 int gen_powers(zkt_ctx* c, void* out, size_t n, const uint32_t base[8], const uint32_t scale[8]);
 // Plookup sorted halves h1/h2 (lookup/multiset.rs:103-146)

@@ -13,6 +13,7 @@
 #include "transcript.hpp"
 
 #include <algorithm>
+#include <functional>
 #include <cstring>
 #include <memory>
 #include <optional>
@@ -25,6 +26,9 @@ int msm_g1_dev(zkt_ctx* c, const void* d_scalars, size_t n, size_t base_off, int
 int msm_begin(zkt_ctx* c, const void* d_scalars, size_t n, size_t base_off, int mont, int slot, int tbl = 0);
 int msm_begin_batch(zkt_ctx* c, int k, const void* const* d_scalars, const size_t* ns, int mont, const int* slots, const int* tbls);
 int msm_flush_tails(zkt_ctx* c);           // issues the deferred bucket reductions of the commitments begun so far (small keys)
+// a round's queued commitments: batches of MSM_BATCH launches-as-one, then the deferred tails (shared with kzg.hip)
+int msm_begin_many(zkt_ctx* c, int k, const void* const* d_scalars, const size_t* ns, int mont, const int* slots, const int* tbls,
+                   bool grouped, const std::function<int(int)>& ready = {});
 bool msm_defers_tails(const zkt_ctx* c);
 bool msm_batches_grouping(const zkt_ctx* c);
 // lagrange.hip
@@ -247,21 +251,16 @@ struct Prover {
     int n_queue = 0, n_lag_queued = 0;
     bool queueing() const { return !c->sharded() && !c->batch_off && msm_batches_grouping(c); }
     int commit_flush() {
-        int rc = ZKT_OK;
-        for (int at = 0; at < n_queue && !rc; at += 3) {
-            const int k = std::min(3, n_queue - at);
-            const void* sc[3];
-            size_t lens[3];
-            int slots[3], tbls[3];
-            for (int j = 0; j < k; ++j) {
-                sc[j] = queue[at + j].scalars; lens[j] = queue[at + j].len; slots[j] = queue[at + j].slot; tbls[j] = queue[at + j].tbl;
-            }
-            rc = msm_begin_batch(c, k, sc, lens, 1, slots, tbls);
+        const int k = n_queue;
+        const void* sc[6];
+        size_t lens[6];
+        int slots[6], tbls[6];
+        for (int j = 0; j < k; ++j) {
+            sc[j] = queue[j].scalars; lens[j] = queue[j].len; slots[j] = queue[j].slot; tbls[j] = queue[j].tbl;
         }
         n_queue = 0;
         n_lag_queued = 0;
-        if (rc) return rc;
-        return msm_flush_tails(c);
+        return msm_begin_many(c, k, sc, lens, 1, slots, tbls, true);
     }
     int commit_push(const void* scalars, size_t len, int slot, int tbl) {
         if (n_queue == 6)
