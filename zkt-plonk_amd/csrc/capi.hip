@@ -6,16 +6,11 @@
 #include "ec.hpp"
 #include "hostec.hpp"
 #include "fx_test.hpp"
+#include "msm.hpp"
 
 #include <cstring>
 
 namespace zkt {
-
-void circuit_release(zkt_ctx* c);   // prover.hip
-void msm_release(zkt_ctx* c);       // msm.hip
-// msm.hip / prover.hip: a state of its own over the parent's read-only tables (zkt_ctx_fork)
-int msm_fork(zkt_ctx* child, const zkt_ctx* parent);
-int circuit_fork(zkt_ctx* child, const zkt_ctx* parent);
 
 const char* exp_env(const char* name) {
 #ifdef ZKT_EXPERIMENTS

@@ -118,6 +118,12 @@ int comm_all_gather_async(zkt_ctx* c, const void* d_send, void* d_recv, size_t b
 
 // grows *p to at least `bytes`
 int ensure_buffer(zkt_ctx* c, void** p, size_t* cur, size_t bytes);
+// scratch that is allocated on first use and grown when a call needs more (the context's allocation, freed with it)
+struct DevBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+};
+inline int grow(zkt_ctx* c, DevBuf& b, size_t bytes) { return ensure_buffer(c, &b.p, &b.bytes, bytes); }
 int dev_alloc(zkt_ctx* c, void** p, size_t bytes);
 void dev_free(zkt_ctx* c, void* p);
 
@@ -131,5 +137,10 @@ int ntt_run_batch(zkt_ctx* c, int log_n, int inverse, int coset, int nb, const v
                   void* const* d_out);
 int ntt_class_code(int log_big, int cls);
 int ntt_run_class(zkt_ctx* c, int log_n, int log_big, int cls, const void* d_in, size_t in_len, void* d_out, void* d_fold);
+
+// prover.hip
+void circuit_release(zkt_ctx* c);
+// a circuit state of its own over the parent's read-only tables (zkt_ctx_fork)
+int circuit_fork(zkt_ctx* child, const zkt_ctx* parent);
 
 }  // namespace zkt

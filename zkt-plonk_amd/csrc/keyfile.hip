@@ -19,6 +19,7 @@
 #include "ctx.hpp"
 #include "ec.hpp"
 #include "keyfile.hpp"
+#include "msm.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -27,8 +28,6 @@
 #include <vector>
 
 namespace zkt {
-
-int srs_load(zkt_ctx* c, const void* src, size_t count, bool on_device, size_t slice_off, size_t total);   // msm.hip
 
 struct Cursor {
     const uint8_t* p;

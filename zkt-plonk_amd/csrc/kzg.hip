@@ -21,12 +21,6 @@
 
 namespace zkt {
 
-// msm.hip
-int msm_g1_dev(zkt_ctx* c, const void* d_scalars, size_t n, size_t base_off, int mont, uint64_t* out_xy, int* out_inf);
-int msm_end(zkt_ctx* c, int slot, uint64_t* out_xy);
-int msm_begin_many(zkt_ctx* c, int k, const void* const* d_scalars, const size_t* ns, int mont, const int* slots, const int* tbls,
-                   bool grouped, const std::function<int(int)>& ready);
-
 // Host uploads: hipMemcpyAsync straight from the caller's pageable memory on a copy stream of the context's own.  The
 // call returns once the runtime has staged the copy, so the host stages polynomial j + 1 while the GPU runs polynomial
 // j's MSM.  A pinned ring of two 4 MiB buffers filled by a host memcpy was measured against it and lost: BN254 2^20 k = 3
@@ -39,15 +33,11 @@ int msm_begin_many(zkt_ctx* c, int k, const void* const* d_scalars, const size_t
 constexpr int KZG_OPEN_E = 4;
 
 struct KzgState {
-    struct Buf {
-        void* p = nullptr;
-        size_t bytes = 0;
-    };
     hipStream_t copy = nullptr;
     hipEvent_t ev_up = nullptr, ev_main = nullptr;
     // device scratch (the context's allocations, freed with it)
-    Buf up;                          // host forms: the uploaded coefficients
-    Buf t, tb, w, scan, pw, part, evals;   // zkt_kzg_open
+    DevBuf up;                         // host forms: the uploaded coefficients
+    DevBuf t, tb, w, scan, pw, part, evals;   // zkt_kzg_open
     ~KzgState() {
         if (ev_up) (void)hipEventDestroy(ev_up);
         if (ev_main) (void)hipEventDestroy(ev_main);
@@ -66,7 +56,6 @@ static int kzg_state(zkt_ctx* c, KzgState** out) {
     *out = c->kzg.get();
     return ZKT_OK;
 }
-static int kzg_buf(zkt_ctx* c, KzgState::Buf& b, size_t bytes) { return ensure_buffer(c, &b.p, &b.bytes, bytes); }
 
 // the copy stream starts behind everything on the context's stream (the upload buffer may still be read there)
 static int kzg_copy_after_main(zkt_ctx* c, KzgState& K) {
@@ -125,7 +114,7 @@ static int kzg_commit(zkt_ctx* c, const void* const* src, bool host, const size_
             for (size_t i = w0; i < std::min(live.size(), w0 + S); ++i) b += lens[live[i]] * 32;
             most = std::max(most, b);
         }
-        if ((rc = kzg_buf(c, K->up, most))) return rc;
+        if ((rc = grow(c, K->up, most))) return rc;
     }
     std::vector<uint64_t> res((size_t)k * W, 0);
     // the prover's rule: grouped launches where the key size gains from them (and not in the A/B builds that turn them off)
@@ -281,11 +270,11 @@ static int kzg_open(zkt_ctx* c, const void* const* src, bool host, const size_t*
     KzgState* K = nullptr;
     if ((rc = kzg_state(c, &K))) return rc;
     const uint32_t nblk = (uint32_t)((L + 256 * KZG_OPEN_E - 1) / (256 * KZG_OPEN_E));
-    if ((rc = kzg_buf(c, K->t, L * 32)) || (rc = kzg_buf(c, K->tb, L * 32)) || (rc = kzg_buf(c, K->w, L * 32)) ||
-        (rc = kzg_buf(c, K->scan, (2 * (L / 1024 + 2048)) * 32)) || (rc = kzg_buf(c, K->pw, open_witness_powers(L) * 32)) ||
-        (rc = kzg_buf(c, K->part, (size_t)k * nblk * 32)) || (rc = kzg_buf(c, K->evals, (size_t)k * 32)))
+    if ((rc = grow(c, K->t, L * 32)) || (rc = grow(c, K->tb, L * 32)) || (rc = grow(c, K->w, L * 32)) ||
+        (rc = grow(c, K->scan, (2 * (L / 1024 + 2048)) * 32)) || (rc = grow(c, K->pw, open_witness_powers(L) * 32)) ||
+        (rc = grow(c, K->part, (size_t)k * nblk * 32)) || (rc = grow(c, K->evals, (size_t)k * 32)))
         return rc;
-    if (host && (rc = kzg_buf(c, K->up, total * 32))) return rc;
+    if (host && (rc = grow(c, K->up, total * 32))) return rc;
     KzgOpenArgs a{};
     a.nterms = k;
     size_t off = 0;

@@ -168,7 +168,7 @@ static int lagrange_build_t(zkt_ctx* c, int log_n) {
     const size_t count2 = n + extra;
     int rc;
     void *A = nullptr, *tw = nullptr, *seg = nullptr, *table2 = nullptr;
-    if ((rc = dev_alloc(c, &table2, (size_t)st.W * count2 * sizeof(Affine<Q>)))) return rc;
+    if ((rc = dev_alloc(c, &table2, (size_t)st.plan.W * count2 * sizeof(Affine<Q>)))) return rc;
     auto release = [&](int code) {
         dev_free(c, A);
         dev_free(c, tw);
@@ -231,7 +231,7 @@ int lagrange_ensure(zkt_ctx* c, int log_n) {
     if (st.lag_failed && st.lag_log_n == log_n) return ZKT_OK;
     const size_t n = (size_t)1 << log_n;
     const bool whole_key = !c->sharded() && st.slice_off == 0 && st.total == st.count;
-    if (!whole_key || st.count <= n || log_n > 30 || (uint64_t)st.W * (n + LAG_MAX_EXTRA) >= ((uint64_t)1 << 31)) {
+    if (!whole_key || st.count <= n || log_n > 30 || (uint64_t)st.plan.W * (n + LAG_MAX_EXTRA) >= ((uint64_t)1 << 31)) {
         if (!st.table2_borrowed) dev_free(c, st.table2);
         st.table2_borrowed = false;
         st.table2 = nullptr;

@@ -961,27 +961,35 @@ __global__ void k_srs_to_fx(Affine<typename C::Fq>* table, size_t total) {
 // rows of partial sums an MSM leaves for the host besides the top bucket's: one per bit of the bucket index below B
 static int msm_rows(int c) { return c - 1; }
 
-// level-1 kernels by digit layout (0 = generic loop)
-template <class C>
-static auto msm_pick_bin_count(int dig) -> decltype(&k_msm_bin_count<C, 0>) {
-    switch (dig) {
-        case 1: return k_msm_bin_count<C, 1>;
-        case 2: return k_msm_bin_count<C, 2>;
-        case 3: return k_msm_bin_count<C, 3>;
-        case 4: return k_msm_bin_count<C, 4>;
-        case 5: return k_msm_bin_count<C, 5>;
-        default: return k_msm_bin_count<C, 0>;
+// level-1 kernels by digit layout (0 = generic loop); VB (caller-supplied bases) has the generic layout only
+template <class C, bool VB = false>
+static auto msm_pick_bin_count(int dig) -> decltype(&k_msm_bin_count<C, 0, VB>) {
+    if constexpr (VB) {
+        return k_msm_bin_count<C, 0, true>;
+    } else {
+        switch (dig) {
+            case 1: return k_msm_bin_count<C, 1>;
+            case 2: return k_msm_bin_count<C, 2>;
+            case 3: return k_msm_bin_count<C, 3>;
+            case 4: return k_msm_bin_count<C, 4>;
+            case 5: return k_msm_bin_count<C, 5>;
+            default: return k_msm_bin_count<C, 0>;
+        }
     }
 }
-template <class C, class PF>
-static auto msm_pick_bin_scatter(int dig) -> decltype(&k_msm_bin_scatter<C, PF, 0>) {
-    switch (dig) {
-        case 1: return k_msm_bin_scatter<C, PF, 1>;
-        case 2: return k_msm_bin_scatter<C, PF, 2>;
-        case 3: return k_msm_bin_scatter<C, PF, 3>;
-        case 4: return k_msm_bin_scatter<C, PF, 4>;
-        case 5: return k_msm_bin_scatter<C, PF, 5>;
-        default: return k_msm_bin_scatter<C, PF, 0>;
+template <class C, class PF, bool VB = false>
+static auto msm_pick_bin_scatter(int dig) -> decltype(&k_msm_bin_scatter<C, PF, 0, VB>) {
+    if constexpr (VB) {
+        return k_msm_bin_scatter<C, PF, 0, true>;
+    } else {
+        switch (dig) {
+            case 1: return k_msm_bin_scatter<C, PF, 1>;
+            case 2: return k_msm_bin_scatter<C, PF, 2>;
+            case 3: return k_msm_bin_scatter<C, PF, 3>;
+            case 4: return k_msm_bin_scatter<C, PF, 4>;
+            case 5: return k_msm_bin_scatter<C, PF, 5>;
+            default: return k_msm_bin_scatter<C, PF, 0>;
+        }
     }
 }
 
@@ -989,6 +997,98 @@ static int floor_log2(size_t x) {
     int l = 0;
     while ((x >> (l + 1)) != 0) ++l;
     return l;
+}
+
+// The plan of an MSM over `points` bases: scalars of `total` bits (the last carry of the signed digits included) cut into
+// digits of at most `cb` bits.  own_buckets: every window owns 2^(c-1) buckets and a pair's index addresses the points
+// themselves (caller-supplied bases); otherwise the windows share one set and the index addresses the W x points window
+// table (the key).
+static int msm_plan(zkt_ctx* c, int total, int cb, size_t points, bool own_buckets, MsmPlan& P) {
+    P = MsmPlan{};
+    // W windows of width cmax or cmax-1 covering exactly `total` bits
+    const int W = (total + cb - 1) / cb;
+    if (W > (int)sizeof(P.win.width)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "msm_g1_bases: too many windows");
+    const int lo = total / W, rem = total % W;
+    P.W = P.win.W = W;
+    int pos = 0;
+    for (int w = 0; w < W; ++w) {
+        P.win.width[w] = (uint8_t)(lo + (w < rem ? 1 : 0));
+        P.win.start[w] = (uint16_t)pos;
+        pos += P.win.width[w];
+    }
+    P.c = lo + (rem ? 1 : 0);
+    P.dig = own_buckets ? 0 : msm_digit_layout(P.win, total);
+    P.Bw = 1u << (P.c - 1);
+    P.keys = own_buckets ? (uint32_t)W * P.Bw : P.Bw;
+    const size_t m = (size_t)W * points;   // pairs at most
+    if (!own_buckets && m >= ((size_t)1 << 31))
+        return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "SRS too large for 31-bit table indices");
+    {   // pair format: one 32-bit word when low key bits + table index + sign fit (see PairPacked)
+        const size_t idx_max = (own_buckets ? points : m) - 1;
+        int idx_bits = 1;
+        while (idx_max >> idx_bits) ++idx_bits;
+        int lb = 31 - idx_bits;
+        if (lb > MSM_BIN_LB_MAX) lb = MSM_BIN_LB_MAX;
+        P.packed = lb >= 4 && ((P.keys >> lb) + 1) < (uint32_t)MSM_MAX_NB1;
+        P.lb = P.packed ? (uint32_t)lb : (uint32_t)MSM_BIN_LB_MAX;
+        if (!P.packed && ((P.keys >> P.lb) + 1) >= (uint32_t)MSM_MAX_NB1) {   // more than 2^17 keys
+            P.lb = MSM_BIN_LB_WIDE;
+            P.lcols = MSM_BIN_LB_WIDE;
+        }
+    }
+    P.nb1 = (P.keys >> P.lb) + 1;
+    if (P.nb1 >= (uint32_t)MSM_MAX_NB1 || m >= ((size_t)1 << 31))
+        return set_err(c, ZKT_ERR_INVALID_ARGUMENT,
+                       own_buckets ? "msm_g1_bases: digit layout outside the sort's range" : "msm: too many level-1 bins");
+    // staged pairs per level-1 workgroup: MSM_L1_CAP of either format; the 4-byte format then needs 60 KB of LDS and two
+    // workgroups (32 waves) share a CU, which these latency-bound kernels need more than longer runs
+    P.l1_scalars = ((uint32_t)MSM_L1_CAP / (uint32_t)W) & ~63u;
+    if (P.l1_scalars > 1024u) P.l1_scalars = 1024u;
+    P.l2_items = (uint32_t)(m / MSM_L2_TILE + P.nb1);
+    return ZKT_OK;
+}
+
+// LDS cap of the level-1 scatter.  The attribute belongs to the kernel, not to a state: size it for the worst case of the
+// instantiation (any number of level-1 bins), so that several states -- contexts in flight, thread-ranks with unequal SRS
+// slices -- cannot shrink each other's cap.
+template <class C, bool VB>
+static int msm_scatter_lds_cap(zkt_ctx* c, bool packed, int dig) {
+    const int lds = (int)(((3 * (uint32_t)MSM_MAX_NB1 + 3) & ~3u) * 4 + MSM_L1_CAP * (packed ? 4 : 8));
+    const void* f = packed ? (const void*)msm_pick_bin_scatter<C, PairPacked, VB>(dig)
+                           : (const void*)msm_pick_bin_scatter<C, PairWide, VB>(dig);
+    ZKT_HIP(c, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    return ZKT_OK;
+}
+
+// Chunks an accumulation is cut into (acc_threads) and the dynamic LDS of its launch (acc_lds: 0 outside experiments).
+template <class C>
+static int msm_acc_setup(zkt_ctx* c, size_t* acc_threads, size_t* acc_lds) {
+    int blocks_per_cu = 0, cus = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, c->device) == hipSuccess) cus = prop.multiProcessorCount;
+    *acc_lds = 0;
+    if (const char* e = exp_env("ZKT_MSM_ACC_LDS")) {   // experiment: cap the resident workgroups through dynamic LDS
+        const int kb = atoi(e);
+        if (kb < 0 || kb > 160) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "ZKT_MSM_ACC_LDS: 0 .. 160 (KiB)");
+        *acc_lds = (size_t)kb * 1024;
+        ZKT_HIP(c, hipFuncSetAttribute((const void*)k_msm_accumulate<C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)*acc_lds));
+    }
+    *acc_threads = 196608;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, k_msm_accumulate<C>, 256, *acc_lds) == hipSuccess &&
+        blocks_per_cu > 0 && cus > 0)
+        *acc_threads = (size_t)blocks_per_cu * cus * 256;
+    // Twice as many chunks as the chip keeps resident: the bucket reduction of the previous MSM runs on the side stream
+    // while this accumulation starts, and every one of its workgroups holds the registers of an accumulation
+    // workgroup for 100-200 us.  With exactly one wave-front of chunks the workgroups that could not start on time
+    // ended a whole accumulation late (+8 % on the kernel); with two, the dispatcher gives the delayed CUs fewer of
+    // the second half.  (ZKT_MSM_OVER = 1 .. 8 overrides the factor for experiments.)
+    int over = 2;
+    if (const char* e = exp_env("ZKT_MSM_OVER")) {
+        const int f = atoi(e);
+        if (f >= 1 && f <= 8) over = f;
+    }
+    *acc_threads *= (size_t)over;
+    return ZKT_OK;
 }
 
 template <class C>
@@ -1022,26 +1122,9 @@ static int msm_setup(zkt_ctx* c, size_t count, const MsmState* share = nullptr) 
         const int f = atoi(e);
         if (f >= 8 && f <= MSM_MAX_Y) cb = f;
     }
-    {   // W windows of width cmax or cmax-1 covering exactly lambda+1 bits
-        const int total = R::BITS + 1;
-        const int W = (total + cb - 1) / cb;
-        const int lo = total / W, rem = total % W;
-        st->win.W = W;
-        int pos = 0;
-        for (int w = 0; w < W; ++w) {
-            st->win.width[w] = (uint8_t)(lo + (w < rem ? 1 : 0));
-            st->win.start[w] = (uint16_t)pos;
-            pos += st->win.width[w];
-        }
-        st->W = W;
-        st->c = lo + (rem ? 1 : 0);
-        cb = st->c;
-        st->dig = msm_digit_layout(st->win, total);
-    }
-    st->B = 1u << (cb - 1);
-    if ((uint64_t)st->W * count >= ((uint64_t)1 << 31))
-        return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "SRS too large for 31-bit table indices");
-    int rc;
+    int rc = msm_plan(c, R::BITS + 1, cb, count, false, st->plan);
+    if (rc) return rc;
+    const MsmPlan& P = st->plan;
     if (share) {   // zkt_ctx_fork: the parent's tables (same count, hence the same layout), everything below this context's own
         st->table = share->table;
         st->table_borrowed = true;
@@ -1052,10 +1135,10 @@ static int msm_setup(zkt_ctx* c, size_t count, const MsmState* share = nullptr) 
         st->lag_failed = share->lag_failed;
         st->slice_off = share->slice_off;
         st->total = share->total;
-    } else if ((rc = dev_alloc(c, &st->table, (size_t)st->W * count * sizeof(Affine<Q>)))) {
+    } else if ((rc = dev_alloc(c, &st->table, (size_t)P.W * count * sizeof(Affine<Q>)))) {
         return rc;
     }
-    size_t m = (size_t)st->W * count;
+    size_t m = (size_t)P.W * count;
     // the main-stream work buffers exist MSM_BATCH times (a round's commitments are grouped and accumulated as one batch:
     // msm_enqueue_batch); strides between the copies in st->strides
     constexpr size_t NB = MSM_BATCH;
@@ -1064,32 +1147,12 @@ static int msm_setup(zkt_ctx* c, size_t count, const MsmState* share = nullptr) 
     st->strides.s_pairs_bytes = up(m) * 8;
     if ((rc = dev_alloc(c, (void**)&st->vals2, NB * st->strides.s_vals * 4))) return rc;
     if ((rc = dev_alloc(c, &st->pairs, NB * st->strides.s_pairs_bytes))) return rc;
-    {   // pair format: one 32-bit word when low key bits + table index + sign fit (see PairPacked)
-        int idx_bits = 1;
-        while ((m - 1) >> idx_bits) ++idx_bits;
-        int lb = 31 - idx_bits;
-        if (lb > MSM_BIN_LB_MAX) lb = MSM_BIN_LB_MAX;
-        st->packed = lb >= 4 && ((st->B >> lb) + 1) < (uint32_t)MSM_MAX_NB1;
-        st->lb = st->packed ? (uint32_t)lb : (uint32_t)MSM_BIN_LB_MAX;
-        if (!st->packed && ((st->B >> st->lb) + 1) >= (uint32_t)MSM_MAX_NB1) {   // more than 2^17 buckets
-            st->lb = MSM_BIN_LB_WIDE;
-            st->lcols = MSM_BIN_LB_WIDE;
-        }
-    }
-    st->nb1 = (st->B >> st->lb) + 1;
-    if (st->nb1 >= (uint32_t)MSM_MAX_NB1) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "msm: too many level-1 bins");
-    // staged pairs per level-1 workgroup: MSM_L1_CAP of either format; the 4-byte format then needs 60 KB of LDS and two
-    // workgroups (32 waves) share a CU, which these latency-bound kernels need more than longer runs
-    const uint32_t l1_cap = (uint32_t)MSM_L1_CAP;
-    st->l1_scalars = (l1_cap / (uint32_t)st->W) & ~63u;
-    if (st->l1_scalars > 1024u) st->l1_scalars = 1024u;
-    const size_t max_blk = (count + st->l1_scalars - 1) / st->l1_scalars;
-    st->strides.s_bin_offs = up((size_t)st->nb1 * max_blk + 1);
-    st->strides.s_bin_aux = up((size_t)st->nb1 * max_blk / MSM_SCAN_TILE + 4);
-    st->strides.s_bin = up((size_t)st->nb1 + 1);
-    st->l2_items = (uint32_t)(m / MSM_L2_TILE + st->nb1);
-    st->strides.s_tile_desc = up(st->l2_items);
-    st->strides.s_cnt = up((size_t)st->l2_items << st->lcols);
+    const size_t max_blk = (count + P.l1_scalars - 1) / P.l1_scalars;
+    st->strides.s_bin_offs = up((size_t)P.nb1 * max_blk + 1);
+    st->strides.s_bin_aux = up((size_t)P.nb1 * max_blk / MSM_SCAN_TILE + 4);
+    st->strides.s_bin = up((size_t)P.nb1 + 1);
+    st->strides.s_tile_desc = up(P.l2_items);
+    st->strides.s_cnt = up((size_t)P.l2_items << P.lcols);
     if ((rc = dev_alloc(c, (void**)&st->bin_offs, NB * st->strides.s_bin_offs * 4))) return rc;
     if ((rc = dev_alloc(c, (void**)&st->bin_aux, NB * st->strides.s_bin_aux * 4))) return rc;
     if ((rc = dev_alloc(c, (void**)&st->bin_start, NB * st->strides.s_bin * 4))) return rc;
@@ -1097,58 +1160,26 @@ static int msm_setup(zkt_ctx* c, size_t count, const MsmState* share = nullptr) 
     if ((rc = dev_alloc(c, &st->tile_desc, NB * st->strides.s_tile_desc * 8))) return rc;
     if ((rc = dev_alloc(c, (void**)&st->cnt2, NB * st->strides.s_cnt * 4))) return rc;
     if ((rc = dev_alloc(c, (void**)&st->pos2, NB * st->strides.s_cnt * 4))) return rc;
-    {
-        // the attribute belongs to the kernel, not to this state: size it for the worst case of the instantiation (any
-        // number of level-1 bins), so that several states -- contexts in flight, thread-ranks with unequal SRS slices --
-        // cannot shrink each other's cap
-        const int lds = (int)(((3 * (uint32_t)MSM_MAX_NB1 + 3) & ~3u) * 4 + MSM_L1_CAP * (st->packed ? 4 : 8));
-        const void* f = st->packed ? (const void*)msm_pick_bin_scatter<C, PairPacked>(st->dig)
-                                   : (const void*)msm_pick_bin_scatter<C, PairWide>(st->dig);
-        ZKT_HIP(c, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    }
+    if ((rc = msm_scatter_lds_cap<C, false>(c, P.packed, P.dig))) return rc;
     static_assert(MsmState::SLOTS == 11, "per-slot arrays are sized for 11 slots");
     for (int i = 0; i < MsmState::SLOTS; ++i) {
-        if ((rc = dev_alloc(c, (void**)&st->offsets[i], (((size_t)st->nb1 << st->lb) + 2) * 4))) return rc;
-        if ((rc = dev_alloc(c, (void**)&st->heavy[i], ((size_t)st->B + 2) * 4))) return rc;
+        if ((rc = dev_alloc(c, (void**)&st->offsets[i], (((size_t)P.nb1 << P.lb) + 2) * 4))) return rc;
+        if ((rc = dev_alloc(c, (void**)&st->heavy[i], ((size_t)P.keys + 2) * 4))) return rc;
         if ((rc = dev_alloc(c, (void**)&st->params[i], 16))) return rc;
     }
-    {
-        int blocks_per_cu = 0, cus = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, c->device) == hipSuccess) cus = prop.multiProcessorCount;
-        if (const char* e = exp_env("ZKT_MSM_ACC_LDS")) {   // experiment: cap the resident workgroups through dynamic LDS
-            const int kb = atoi(e);
-            if (kb < 0 || kb > 160) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "ZKT_MSM_ACC_LDS: 0 .. 160 (KiB)");
-            st->acc_lds = (size_t)kb * 1024;
-            ZKT_HIP(c, hipFuncSetAttribute((const void*)k_msm_accumulate<C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)st->acc_lds));
-        }
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, k_msm_accumulate<C>, 256, st->acc_lds) == hipSuccess &&
-            blocks_per_cu > 0 && cus > 0)
-            st->acc_threads = (size_t)blocks_per_cu * cus * 256;
-        // Twice as many chunks as the chip keeps resident: the bucket reduction of the previous MSM runs on the side stream
-        // while this accumulation starts, and every one of its workgroups holds the registers of an accumulation
-        // workgroup for 100-200 us.  With exactly one wave-front of chunks the workgroups that could not start on time
-        // ended a whole accumulation late (+8 % on the kernel); with two, the dispatcher gives the delayed CUs fewer of
-        // the second half.  (ZKT_MSM_OVER = 1 .. 8 overrides the factor for experiments.)
-        int over = 2;
-        if (const char* e = exp_env("ZKT_MSM_OVER")) {
-            const int f = atoi(e);
-            if (f >= 1 && f <= 8) over = f;
-        }
-        st->acc_threads *= (size_t)over;
-    }
+    if ((rc = msm_acc_setup<C>(c, &st->acc_threads, &st->acc_lds))) return rc;
     // chunk >= ceil(pairs / acc_threads) pairs per thread (k_msm_scan_aux), so an MSM never cuts its pairs into more than
     // acc_threads chunks (nor more than it has pairs): that bounds the piece array of every slot
     size_t max_chunks = std::min(m, st->acc_threads) + 1;
     for (int i = 0; i < MsmState::SLOTS; ++i)
-        if ((rc = dev_alloc(c, &st->pieces[i], (max_chunks + st->B + 2) * sizeof(XyzzRaw<Q>)))) return rc;
+        if ((rc = dev_alloc(c, &st->pieces[i], (max_chunks + P.keys + 2) * sizeof(XyzzRaw<Q>)))) return rc;
     st->strides.s_chunk = up(max_chunks + 2);
     if ((rc = dev_alloc(c, (void**)&st->chunk_bucket, NB * st->strides.s_chunk * 4))) return rc;
     ZKT_HIP(c, hipStreamCreateWithFlags(&st->side, hipStreamNonBlocking));
     for (int i = 0; i < MsmState::SLOTS; ++i) {
-        if ((rc = dev_alloc(c, &st->buckets[i], ((size_t)st->B + 1) * sizeof(Xyzz<Q>)))) return rc;
+        if ((rc = dev_alloc(c, &st->buckets[i], ((size_t)P.keys + 1) * sizeof(Xyzz<Q>)))) return rc;
         {   // 2^q1 row sums + 2^q2 column sums of the bucket matrix (q1 + q2 = c - 1)
-            const int q = cb - 1, q2 = q / 2, q1 = q - q2;
+            const int q = P.c - 1, q2 = q / 2, q1 = q - q2;
             if ((rc = dev_alloc(c, &st->rowcol[i], (((size_t)1 << q1) + ((size_t)1 << q2)) * sizeof(Xyzz<Q>)))) return rc;
         }
         ZKT_HIP(c, hipHostMalloc(&st->host_result[i], (size_t)(MSM_MAX_Y + 1) * MSM_R2_BLOCKS * sizeof(Xyzz<Q>), hipHostMallocMapped));
@@ -1169,9 +1200,9 @@ static int table_finish(zkt_ctx* c, void* table, size_t count) {
     using Q = typename C::Fq;
     MsmState& st = *c->msm;
     unsigned blocks = (unsigned)((count + 127) / 128);
-    hipLaunchKernelGGL(k_srs_windows<C>, dim3(blocks), dim3(128), 0, c->stream, (Affine<Q>*)table, count, st.win);
+    hipLaunchKernelGGL(k_srs_windows<C>, dim3(blocks), dim3(128), 0, c->stream, (Affine<Q>*)table, count, st.plan.win);
     ZKT_HIP(c, hipGetLastError());
-    const size_t total = (size_t)st.W * count;
+    const size_t total = (size_t)st.plan.W * count;
     hipLaunchKernelGGL(k_srs_to_fx<C>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream,
                        (Affine<Q>*)table, total);
     ZKT_HIP(c, hipGetLastError());
@@ -1182,7 +1213,6 @@ template <class C>
 static int srs_finish(zkt_ctx* c) {
     return table_finish<C>(c, c->msm->table, c->msm->count);
 }
-void msm_release(zkt_ctx* c);
 int msm_fork(zkt_ctx* child, const zkt_ctx* parent) {
     msm_release(child);
     if (!parent->msm) return ZKT_OK;
@@ -1307,10 +1337,10 @@ static int msm_launch_tails_t(zkt_ctx* c) {
     {
     ProfScope prof_fold(c, "msm_fold", st.side, (uint64_t)k);
     if (st.defer_tails) {   // small key: sixteen lanes per bucket, no crowded-bucket pass
-        hipLaunchKernelGGL((k_msm_bucket_sum_lanes<C, TI>), dim3((16 * (st.B + 1) + 255) / 256, ky), dim3(256), 0, st.side, st.B, tb);
+        hipLaunchKernelGGL((k_msm_bucket_sum_lanes<C, TI>), dim3((16 * (st.plan.keys + 1) + 255) / 256, ky), dim3(256), 0, st.side, st.plan.keys, tb);
         ZKT_HIP(c, hipGetLastError());
     } else {
-        hipLaunchKernelGGL((k_msm_bucket_sum<C, TI>), dim3((st.B + 1 + 255) / 256, ky), dim3(256), 0, st.side, st.B, tb);
+        hipLaunchKernelGGL((k_msm_bucket_sum<C, TI>), dim3((st.plan.keys + 1 + 255) / 256, ky), dim3(256), 0, st.side, st.plan.keys, tb);
         ZKT_HIP(c, hipGetLastError());
         hipLaunchKernelGGL((k_msm_heavy<C, TI>), dim3(MSM_HEAVY_BLOCKS, ky), dim3(256), 0, st.side, tb);
         ZKT_HIP(c, hipGetLastError());
@@ -1318,11 +1348,11 @@ static int msm_launch_tails_t(zkt_ctx* c) {
     }
     {
     ProfScope prof_tail(c, "msm_tail", st.side, (uint64_t)k);
-    const uint32_t q = (uint32_t)(st.c - 1), q2 = q / 2, q1 = q - q2;   // 2^q buckets below B = 2^q1 rows x 2^q2 columns
+    const uint32_t q = (uint32_t)(st.plan.c - 1), q2 = q / 2, q1 = q - q2;   // 2^q buckets below B = 2^q1 rows x 2^q2 columns
     const uint32_t sums = (1u << q1) + (1u << q2);
     hipLaunchKernelGGL((k_msm_rowcol<C, TI>), dim3((sums + 3) / 4, ky), dim3(256), 0, st.side, q1, q2, tb);
     ZKT_HIP(c, hipGetLastError());
-    hipLaunchKernelGGL((k_msm_weighted_rows<C, TI>), dim3(q + 1, ky), dim3(64), 0, st.side, q1, q2, st.B, tb);
+    hipLaunchKernelGGL((k_msm_weighted_rows<C, TI>), dim3(q + 1, ky), dim3(64), 0, st.side, q1, q2, st.plan.Bw, tb);
     ZKT_HIP(c, hipGetLastError());
     }
     // the ny + 1 row sums are written straight into pinned host memory (16 posted writes of 128 B; a copy engine took
@@ -1340,6 +1370,81 @@ static int msm_launch_tails(zkt_ctx* c) {
     bool inl = c->msm->defer_tails || c->msm->count <= MSM_TAIL_INL_MAX;
     if (const char* e = exp_env("ZKT_MSM_TAIL_INL")) inl = atoi(e) != 0;
     return inl ? msm_launch_tails_t<C, true>(c) : msm_launch_tails_t<C, false>(c);
+}
+
+// The main-stream work buffers of a grouping (MsmState's, which hold MSM_BATCH copies `s_*` apart, or MsmBasesState's).
+struct MsmWork {
+    uint32_t *bin_offs, *bin_aux, *bin_start, *tile_start;
+    void* tile_desc;
+    uint32_t *cnt2, *pos2;
+    void* pairs;
+    uint32_t *vals, *chunk_bucket;
+};
+
+// The grouping of the ky <= MSM_BATCH MSMs of `bt` (blockIdx.y = MSM; n = the longest of them) by plan P: level-1 count,
+// scans, level-1 scatter, then the level-2 count, scan and scatter, which leave the table indices grouped by key in
+// wk.vals and the first key of every accumulation chunk in wk.chunk_bucket.  VB: caller-supplied bases.
+// (the chunk itself is computed on the device from the pairs that really exist: k_msm_scan_aux -> bt.params)
+template <class C, bool VB>
+static int msm_launch_grouping(zkt_ctx* c, const MsmPlan& P, const MsmWork& wk, const MsmBatch& bt, int mont, size_t n, unsigned ky,
+                               size_t acc_threads, bool defer_tails) {
+    const uint32_t S = P.l1_scalars;
+    const unsigned nblk = (unsigned)((n + S - 1) / S);
+    const uint32_t total = P.nb1 * nblk, ntiles = (total + MSM_SCAN_TILE - 1) / MSM_SCAN_TILE;
+    const uint2* tile_desc = (const uint2*)wk.tile_desc;
+    {
+        auto kc = msm_pick_bin_count<C, VB>(P.dig);
+        hipLaunchKernelGGL(kc, dim3(nblk, ky), dim3(1024), (size_t)P.nb1 * 4, c->stream, bt, mont, P.win, S, P.nb1, P.lb, wk.bin_offs);
+    }
+    hipLaunchKernelGGL(k_msm_scan_tiles, dim3(ntiles, ky), dim3(1024), 0, c->stream, wk.bin_offs, total, wk.bin_aux, bt);
+    hipLaunchKernelGGL(k_msm_scan_aux, dim3(1, ky), dim3(1024), 0, c->stream, wk.bin_offs, wk.bin_aux, ntiles, nblk, P.nb1,
+                       wk.bin_start, wk.tile_start, (uint2*)wk.tile_desc, (uint32_t)acc_threads, P.keys, defer_tails ? 1u : 0u, bt);
+    ZKT_HIP(c, hipGetLastError());
+    const size_t lds_scatter = (size_t)((3 * P.nb1 + 3) & ~3u) * 4 + (size_t)MSM_L1_CAP * (P.packed ? 4 : 8);
+    const uint32_t items = (uint32_t)((size_t)P.W * n / MSM_L2_TILE + P.nb1);
+    if (P.packed) {
+        auto ks = msm_pick_bin_scatter<C, PairPacked, VB>(P.dig);
+        hipLaunchKernelGGL(ks, dim3(nblk, ky), dim3(1024), lds_scatter, c->stream, bt, mont, P.win, S, P.nb1, P.lb, wk.bin_offs,
+                           wk.bin_aux, (uint32_t*)wk.pairs);
+        ZKT_HIP(c, hipGetLastError());
+        hipLaunchKernelGGL((k_msm_l2_count<PairPacked, 8>), dim3(items, ky), dim3(256), 0, c->stream, (const uint32_t*)wk.pairs,
+                           P.nb1, P.lb, wk.tile_start, tile_desc, wk.cnt2, bt);
+    } else {
+        auto ks = msm_pick_bin_scatter<C, PairWide, VB>(P.dig);
+        hipLaunchKernelGGL(ks, dim3(nblk, ky), dim3(1024), lds_scatter, c->stream, bt, mont, P.win, S, P.nb1, P.lb, wk.bin_offs,
+                           wk.bin_aux, (uint2*)wk.pairs);
+        ZKT_HIP(c, hipGetLastError());
+        auto kc2 = P.lcols == 8 ? k_msm_l2_count<PairWide, 8> : k_msm_l2_count<PairWide, 10>;
+        hipLaunchKernelGGL(kc2, dim3(items, ky), dim3(256), 0, c->stream, (const uint2*)wk.pairs, P.nb1, P.lb, wk.tile_start,
+                           tile_desc, wk.cnt2, bt);
+    }
+    {
+        auto ksc = P.lcols == 8 ? k_msm_l2_scan<8> : k_msm_l2_scan<10>;
+        hipLaunchKernelGGL(ksc, dim3(P.nb1, ky), dim3(256), 0, c->stream, wk.cnt2, wk.pos2, wk.bin_start, wk.tile_start, P.keys,
+                           P.lb, wk.chunk_bucket, bt);
+    }
+    if (P.packed) {
+        hipLaunchKernelGGL((k_msm_l2_scatter<PairPacked, 8>), dim3(items, ky), dim3(MSM_L2S_THREADS), 0, c->stream,
+                           (const uint32_t*)wk.pairs, P.nb1, P.lb, wk.tile_start, tile_desc, wk.cnt2, wk.pos2, wk.vals, bt);
+    } else {
+        auto kss = P.lcols == 8 ? k_msm_l2_scatter<PairWide, 8> : k_msm_l2_scatter<PairWide, 10>;
+        hipLaunchKernelGGL(kss, dim3(items, ky), dim3(MSM_L2S_THREADS), 0, c->stream, (const uint2*)wk.pairs, P.nb1, P.lb,
+                           wk.tile_start, tile_desc, wk.cnt2, wk.pos2, wk.vals, bt);
+    }
+    ZKT_HIP(c, hipGetLastError());
+    return ZKT_OK;
+}
+
+// The accumulation of ONE MSM of n scalars (bt's entry 0) over its grouped indices: as many threads as the MSM can have
+// chunks (threads past the last chunk leave at once).
+template <class C>
+static int msm_launch_accumulate(zkt_ctx* c, const MsmPlan& P, const uint32_t* vals, const uint32_t* chunk_bucket, const MsmBatch& bt,
+                                 size_t n, size_t acc_threads, size_t acc_lds) {
+    const uint32_t max_chunks = (uint32_t)std::min((size_t)P.W * n, acc_threads);
+    hipLaunchKernelGGL(k_msm_accumulate<C>, dim3((max_chunks + 255) / 256, 1), dim3(256), acc_lds, c->stream, vals, P.keys,
+                       chunk_bucket, bt);
+    ZKT_HIP(c, hipGetLastError());
+    return ZKT_OK;
 }
 
 // Enqueues k <= MSM_BATCH MSMs over the same table as ONE batch: every grouping kernel and the accumulation go out once,
@@ -1379,60 +1484,13 @@ static int msm_enqueue_batch(zkt_ctx* c, int k, const void* const* d_scalars, co
         bt.pieces[j] = st.pieces[slot];
         if (j < k) n_max = std::max(n_max, ns[jj]);
     }
-    const size_t n = n_max;
-    const uint32_t m = (uint32_t)((size_t)st.W * n);
-    const unsigned ky = (unsigned)k;
-    // (the chunk itself is computed on the device from the pairs that really exist: k_msm_scan_aux -> params[slot])
     {
     // (Lagrange-basis commitments are timed apart: a batch that mixes both counts as dense)
     ProfScope prof_all(c, all_lag ? "msm_lag_main" : "msm_main", nullptr, (uint64_t)k);
-    {
-        const uint32_t S = st.l1_scalars;
-        const unsigned nblk = (unsigned)((n + S - 1) / S);
-        const uint32_t total = st.nb1 * nblk, ntiles = (total + MSM_SCAN_TILE - 1) / MSM_SCAN_TILE;
-        {
-            auto kc = msm_pick_bin_count<C>(st.dig);
-            hipLaunchKernelGGL(kc, dim3(nblk, ky), dim3(1024), (size_t)st.nb1 * 4, c->stream, bt, mont, st.win, S, st.nb1, st.lb,
-                               st.bin_offs);
-        }
-        hipLaunchKernelGGL(k_msm_scan_tiles, dim3(ntiles, ky), dim3(1024), 0, c->stream, st.bin_offs, total, st.bin_aux, bt);
-        hipLaunchKernelGGL(k_msm_scan_aux, dim3(1, ky), dim3(1024), 0, c->stream, st.bin_offs, st.bin_aux, ntiles, nblk, st.nb1,
-                           st.bin_start, st.tile_start, (uint2*)st.tile_desc, (uint32_t)st.acc_threads, st.B,
-                           st.defer_tails ? 1u : 0u, bt);
-        ZKT_HIP(c, hipGetLastError());
-        const size_t lds_scatter = (size_t)((3 * st.nb1 + 3) & ~3u) * 4 + (size_t)MSM_L1_CAP * (st.packed ? 4 : 8);
-        const uint32_t items = (uint32_t)(m / MSM_L2_TILE + st.nb1);
-        if (st.packed) {
-            auto ks = msm_pick_bin_scatter<C, PairPacked>(st.dig);
-            hipLaunchKernelGGL(ks, dim3(nblk, ky), dim3(1024), lds_scatter, c->stream, bt, mont, st.win, S,
-                               st.nb1, st.lb, st.bin_offs, st.bin_aux, (uint32_t*)st.pairs);
-            ZKT_HIP(c, hipGetLastError());
-            hipLaunchKernelGGL((k_msm_l2_count<PairPacked, 8>), dim3(items, ky), dim3(256), 0, c->stream, (const uint32_t*)st.pairs,
-                               st.nb1, st.lb, st.tile_start, (const uint2*)st.tile_desc, st.cnt2, bt);
-        } else {
-            auto ks = msm_pick_bin_scatter<C, PairWide>(st.dig);
-            hipLaunchKernelGGL(ks, dim3(nblk, ky), dim3(1024), lds_scatter, c->stream, bt, mont, st.win, S,
-                               st.nb1, st.lb, st.bin_offs, st.bin_aux, (uint2*)st.pairs);
-            ZKT_HIP(c, hipGetLastError());
-            auto kc2 = st.lcols == 8 ? k_msm_l2_count<PairWide, 8> : k_msm_l2_count<PairWide, 10>;
-            hipLaunchKernelGGL(kc2, dim3(items, ky), dim3(256), 0, c->stream, (const uint2*)st.pairs, st.nb1,
-                               st.lb, st.tile_start, (const uint2*)st.tile_desc, st.cnt2, bt);
-        }
-        {
-            auto ksc = st.lcols == 8 ? k_msm_l2_scan<8> : k_msm_l2_scan<10>;
-            hipLaunchKernelGGL(ksc, dim3(st.nb1, ky), dim3(256), 0, c->stream, st.cnt2, st.pos2, st.bin_start,
-                               st.tile_start, st.B, st.lb, st.chunk_bucket, bt);
-        }
-        if (st.packed) {
-            hipLaunchKernelGGL((k_msm_l2_scatter<PairPacked, 8>), dim3(items, ky), dim3(MSM_L2S_THREADS), 0, c->stream, (const uint32_t*)st.pairs,
-                               st.nb1, st.lb, st.tile_start, (const uint2*)st.tile_desc, st.cnt2, st.pos2, st.vals2, bt);
-        } else {
-            auto kss = st.lcols == 8 ? k_msm_l2_scatter<PairWide, 8> : k_msm_l2_scatter<PairWide, 10>;
-            hipLaunchKernelGGL(kss, dim3(items, ky), dim3(MSM_L2S_THREADS), 0, c->stream, (const uint2*)st.pairs, st.nb1,
-                               st.lb, st.tile_start, (const uint2*)st.tile_desc, st.cnt2, st.pos2, st.vals2, bt);
-        }
-        ZKT_HIP(c, hipGetLastError());
-    }
+    const MsmWork wk{st.bin_offs, st.bin_aux, st.bin_start, st.tile_start, st.tile_desc, st.cnt2, st.pos2, st.pairs, st.vals2,
+                     st.chunk_bucket};
+    if (int rc = msm_launch_grouping<C, false>(c, st.plan, wk, bt, mont, n_max, (unsigned)k, st.acc_threads, st.defer_tails))
+        return rc;
     // Accumulation and tail, one MSM after the other even when the grouping was batched: the bucket reduction of MSM j
     // (side stream) then runs beside the accumulation of MSM j + 1, which absorbs it (two wave-fronts of chunks); issued
     // together behind the batch the three tails ran beside the transforms that follow a round and slowed them by 8-10 %.
@@ -1444,11 +1502,9 @@ static int msm_enqueue_batch(zkt_ctx* c, int k, const void* const* d_scalars, co
         one.table[0] = bt.table[j];
         {
             ProfScope prof_acc(c, tbls[j] ? "msm_lag_accumulate" : "msm_accumulate");
-            // as many threads as an MSM can have chunks (threads past the last chunk leave at once)
-            const uint32_t max_chunks = (uint32_t)std::min((size_t)st.W * ns[j], st.acc_threads);
-            hipLaunchKernelGGL(k_msm_accumulate<C>, dim3((max_chunks + 255) / 256, 1), dim3(256), st.acc_lds, c->stream,
-                               st.vals2 + (size_t)j * st.strides.s_vals, st.B, st.chunk_bucket + (size_t)j * st.strides.s_chunk, one);
-            ZKT_HIP(c, hipGetLastError());
+            if (int rc = msm_launch_accumulate<C>(c, st.plan, st.vals2 + (size_t)j * st.strides.s_vals,
+                                                  st.chunk_bucket + (size_t)j * st.strides.s_chunk, one, ns[j], st.acc_threads, st.acc_lds))
+                return rc;
         }
         // ---- tail on the side stream: the bucket fold (latency bound: one wave per SIMD, a few dependent additions) and
         // the bucket reduction overlap whatever the main stream does next; everything they read is the slot's own ----
@@ -1471,7 +1527,7 @@ static int msm_enqueue(zkt_ctx* c, const void* d_scalars, size_t n, size_t base_
 // ~50 curve operations on 64-bit limbs.
 template <class Q>
 static Xyzz<Q> msm_host_finish(const MsmState& st, int slot) {
-    const int ny = msm_rows(st.c);
+    const int ny = msm_rows(st.plan.c);
     int exps[MSM_MAX_Y + 1];
     for (int y = 0; y <= ny; ++y) exps[y] = y;
     return hostec::weighted_row_sum<Q>((const Xyzz<Q>*)st.host_result[slot], ny + 1, MSM_R2_BLOCKS, exps);
@@ -1659,11 +1715,11 @@ int msm_enqueue_only(zkt_ctx* c, const void* d_scalars, size_t n, size_t base_of
     if (c->curve == ZKT_CURVE_BN254) return msm_enqueue<Bn254Curve>(c, d_scalars, n, base_off, mont);
     return msm_enqueue<Bls381Curve>(c, d_scalars, n, base_off, mont);
 }
-int srs_load(zkt_ctx* c, const void* src, size_t count, bool on_device, size_t slice_off = 0, size_t total = 0) {
+int srs_load(zkt_ctx* c, const void* src, size_t count, bool on_device, size_t slice_off, size_t total) {
     if (c->curve == ZKT_CURVE_BN254) return srs_load_t<Bn254Curve>(c, src, count, on_device, slice_off, total);
     return srs_load_t<Bls381Curve>(c, src, count, on_device, slice_off, total);
 }
-int srs_generate(zkt_ctx* c, const uint64_t* tau4, size_t count, size_t slice_off = 0, size_t total = 0) {
+int srs_generate(zkt_ctx* c, const uint64_t* tau4, size_t count, size_t slice_off, size_t total) {
     if (c->curve == ZKT_CURVE_BN254) return srs_generate_t<Bn254Curve>(c, tau4, count, slice_off, total);
     return srs_generate_t<Bls381Curve>(c, tau4, count, slice_off, total);
 }
@@ -1701,17 +1757,6 @@ int srs_download(zkt_ctx* c, size_t offset, size_t count, uint64_t* out) {
 // sum_b b S_b goes through the row / column reduction with the windows as tail slots, and the host weights row y of
 // window w by 2^(start_w + y) -- the Horner pass over the windows is folded into the one it already does.
 // ---------------------------------------------------------------------------------------------
-struct MsmBasesPlan {
-    MsmWindows win{};
-    int c = 0;                     // widest digit
-    uint32_t Bw = 0, Btot = 0;     // buckets per window; keys 1 .. Btot in all
-    uint32_t lb = 0, nb1 = 0;
-    int lcols = 8;
-    bool packed = false;
-    uint32_t l1_scalars = 0;
-    size_t m = 0, l2_items = 0;
-};
-
 // Digit width by the number of points, from an A/B sweep on MI355X (profiles/msm_bases_cbits.txt): W 2^(c-1) buckets make
 // the tail W times the SRS path's, so c stays below that path's log2(n) - 2 while the reductions dominate (lg - 4 up to
 // 2^15 points), then jumps to the widths whose bucket keys take the wide, 1024-column sort: BN254 c = 15 (seventeen
@@ -1735,44 +1780,11 @@ static int msm_bases_cbits(size_t n, int curve) {
     return cb;
 }
 
-template <class C>
-static int msm_bases_plan(zkt_ctx* c, size_t n, int mont, MsmBasesPlan& P) {
-    using R = typename C::Fr;
+static int msm_bases_plan(zkt_ctx* c, size_t n, int mont, MsmPlan& P) {
     // Canonical scalars are full 256-bit integers (ark-ec reads every bit of into_repr()); Montgomery ones leave their
     // form below r.  One bit more for the last carry of the signed digits.
-    const int total = mont ? R::BITS + 1 : 257;
-    const int cb = msm_bases_cbits(n, c->curve);
-    const int W = (total + cb - 1) / cb;
-    if (W > (int)sizeof(P.win.width)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "msm_g1_bases: too many windows");
-    const int lo = total / W, rem = total % W;
-    P.win.W = W;
-    int pos = 0;
-    for (int w = 0; w < W; ++w) {
-        P.win.width[w] = (uint8_t)(lo + (w < rem ? 1 : 0));
-        P.win.start[w] = (uint16_t)pos;
-        pos += P.win.width[w];
-    }
-    P.c = lo + (rem ? 1 : 0);
-    P.Bw = 1u << (P.c - 1);
-    P.Btot = (uint32_t)W * P.Bw;
-    P.m = (size_t)W * n;
-    int idx_bits = 1;
-    while ((n - 1) >> idx_bits) ++idx_bits;
-    int lb = 31 - idx_bits;
-    if (lb > MSM_BIN_LB_MAX) lb = MSM_BIN_LB_MAX;
-    P.packed = lb >= 4 && ((P.Btot >> lb) + 1) < (uint32_t)MSM_MAX_NB1;
-    P.lb = P.packed ? (uint32_t)lb : (uint32_t)MSM_BIN_LB_MAX;
-    if (!P.packed && ((P.Btot >> P.lb) + 1) >= (uint32_t)MSM_MAX_NB1) {
-        P.lb = MSM_BIN_LB_WIDE;
-        P.lcols = MSM_BIN_LB_WIDE;
-    }
-    P.nb1 = (P.Btot >> P.lb) + 1;
-    if (P.nb1 >= (uint32_t)MSM_MAX_NB1 || P.m >= ((size_t)1 << 31))
-        return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "msm_g1_bases: digit layout outside the sort's range");
-    P.l1_scalars = ((uint32_t)MSM_L1_CAP / (uint32_t)W) & ~63u;
-    if (P.l1_scalars > 1024u) P.l1_scalars = 1024u;
-    P.l2_items = P.m / MSM_L2_TILE + P.nb1;
-    return ZKT_OK;
+    const int total = mont ? (c->curve == ZKT_CURVE_BN254 ? Bn254Fr::BITS : Bls381Fr::BITS) + 1 : 257;
+    return msm_plan(c, total, msm_bases_cbits(n, c->curve), n, true, P);
 }
 
 template <class C>
@@ -1780,20 +1792,10 @@ static int msm_bases_state(zkt_ctx* c, MsmBasesState** out) {
     using Q = typename C::Fq;
     if (!c->msmb) {
         auto st = std::make_shared<MsmBasesState>();
-        for (int pk = 0; pk < 2; ++pk) {   // LDS cap of the level-1 scatter, for the worst case (as msm_setup)
-            const int lds = (int)(((3 * (uint32_t)MSM_MAX_NB1 + 3) & ~3u) * 4 + MSM_L1_CAP * (pk ? 4 : 8));
-            const void* f = pk ? (const void*)k_msm_bin_scatter<C, PairPacked, 0, true>
-                               : (const void*)k_msm_bin_scatter<C, PairWide, 0, true>;
-            ZKT_HIP(c, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        }
-        int blocks_per_cu = 0, cus = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, c->device) == hipSuccess) cus = prop.multiProcessorCount;
-        st->acc_threads = 196608;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, k_msm_accumulate<C>, 256, 0) == hipSuccess &&
-            blocks_per_cu > 0 && cus > 0)
-            st->acc_threads = (size_t)blocks_per_cu * cus * 256;
-        st->acc_threads *= 2;
+        int rc;
+        if ((rc = msm_scatter_lds_cap<C, true>(c, true, 0)) || (rc = msm_scatter_lds_cap<C, true>(c, false, 0)) ||
+            (rc = msm_acc_setup<C>(c, &st->acc_threads, &st->acc_lds)))
+            return rc;
         const size_t rows = sizeof(MsmWindows::width) * (size_t)(MSM_MAX_Y + 1);
         ZKT_HIP(c, hipHostMalloc(&st->partials, rows * sizeof(Xyzz<Q>), hipHostMallocMapped));
         ZKT_HIP(c, hipHostGetDevicePointer(&st->partials_dev, st->partials, 0));
@@ -1811,32 +1813,31 @@ static int msm_bases_t(zkt_ctx* c, const void* bases, bool bases_on_device, cons
     res.x = fe_zero<Q>();
     res.y = fe_zero<Q>();
     if (n > 0) {
-        MsmBasesPlan P;
-        int rc = msm_bases_plan<C>(c, n, mont, P);
+        MsmPlan P;
+        int rc = msm_bases_plan(c, n, mont, P);
         if (rc) return rc;
         MsmBasesState* st = nullptr;
         if ((rc = msm_bases_state<C>(c, &st))) return rc;
-        const int W = P.win.W;
+        const int W = P.W;
         const uint32_t q = (uint32_t)(P.c - 1), q2 = q / 2, q1 = q - q2;   // 2^q buckets below Bw = 2^q1 rows x 2^q2 columns
         const uint32_t sums = (1u << q1) + (1u << q2);
-        const uint32_t S = P.l1_scalars;
-        const unsigned nblk = (unsigned)((n + S - 1) / S);
-        const uint32_t total = P.nb1 * nblk, ntiles = (total + MSM_SCAN_TILE - 1) / MSM_SCAN_TILE;
-        const size_t max_chunks = std::min(P.m, st->acc_threads) + 1;
-        auto grow = [&](MsmBasesState::Buf& b, size_t bytes) { return ensure_buffer(c, &b.p, &b.bytes, bytes); };
-        if ((rc = grow(st->bases, n * sizeof(Affine<Q>))) || (rc = grow(st->vals, P.m * 4)) ||
-            (rc = grow(st->pairs, P.m * (P.packed ? 4 : 8))) || (rc = grow(st->bin_offs, ((size_t)total + 1) * 4)) ||
-            (rc = grow(st->bin_aux, ((size_t)ntiles + 4) * 4)) || (rc = grow(st->bin_start, ((size_t)P.nb1 + 1) * 4)) ||
-            (rc = grow(st->tile_start, ((size_t)P.nb1 + 1) * 4)) || (rc = grow(st->tile_desc, P.l2_items * 8)) ||
-            (rc = grow(st->cnt2, (P.l2_items << P.lcols) * 4)) || (rc = grow(st->pos2, (P.l2_items << P.lcols) * 4)) ||
-            (rc = grow(st->chunk_bucket, (max_chunks + 2) * 4)) || (rc = grow(st->offsets, (((size_t)P.nb1 << P.lb) + 2) * 4)) ||
-            (rc = grow(st->heavy, ((size_t)P.Btot + 2) * 4)) || (rc = grow(st->params, 16)) ||
-            (rc = grow(st->pieces, (max_chunks + P.Btot + 2) * sizeof(XyzzRaw<Q>))) ||
-            (rc = grow(st->buckets, ((size_t)P.Btot + 1) * sizeof(Xyzz<Q>))) ||
-            (rc = grow(st->rowcol, (size_t)W * sums * sizeof(Xyzz<Q>))))
+        const size_t m = (size_t)W * n;
+        const size_t nblk = (n + P.l1_scalars - 1) / P.l1_scalars;
+        const size_t total = P.nb1 * nblk, ntiles = (total + MSM_SCAN_TILE - 1) / MSM_SCAN_TILE;
+        const size_t max_chunks = std::min(m, st->acc_threads) + 1, l2 = P.l2_items;
+        if ((rc = grow(c, st->bases, n * sizeof(Affine<Q>))) || (rc = grow(c, st->vals, m * 4)) ||
+            (rc = grow(c, st->pairs, m * (P.packed ? 4 : 8))) || (rc = grow(c, st->bin_offs, (total + 1) * 4)) ||
+            (rc = grow(c, st->bin_aux, (ntiles + 4) * 4)) || (rc = grow(c, st->bin_start, ((size_t)P.nb1 + 1) * 4)) ||
+            (rc = grow(c, st->tile_start, ((size_t)P.nb1 + 1) * 4)) || (rc = grow(c, st->tile_desc, l2 * 8)) ||
+            (rc = grow(c, st->cnt2, (l2 << P.lcols) * 4)) || (rc = grow(c, st->pos2, (l2 << P.lcols) * 4)) ||
+            (rc = grow(c, st->chunk_bucket, (max_chunks + 2) * 4)) || (rc = grow(c, st->offsets, (((size_t)P.nb1 << P.lb) + 2) * 4)) ||
+            (rc = grow(c, st->heavy, ((size_t)P.keys + 2) * 4)) || (rc = grow(c, st->params, 16)) ||
+            (rc = grow(c, st->pieces, (max_chunks + P.keys + 2) * sizeof(XyzzRaw<Q>))) ||
+            (rc = grow(c, st->buckets, ((size_t)P.keys + 1) * sizeof(Xyzz<Q>))) ||
+            (rc = grow(c, st->rowcol, (size_t)W * sums * sizeof(Xyzz<Q>))))
             return rc;
         if (!scalars_on_device) {
-            if ((rc = grow(st->scalars, n * 32))) return rc;
+            if ((rc = grow(c, st->scalars, n * 32))) return rc;
             ZKT_HIP(c, hipMemcpyAsync(st->scalars.p, scalars, n * 32, hipMemcpyHostToDevice, c->stream));
             scalars = st->scalars.p;
         }
@@ -1860,57 +1861,14 @@ static int msm_bases_t(zkt_ctx* c, const void* bases, bool bases_on_device, cons
             bt.pieces[j] = st->pieces.p;
         }
         bt.vb_stride = P.Bw;
-        uint32_t* bin_offs = (uint32_t*)st->bin_offs.p;
-        uint32_t* bin_aux = (uint32_t*)st->bin_aux.p;
-        uint32_t* bin_start = (uint32_t*)st->bin_start.p;
-        uint32_t* tile_start = (uint32_t*)st->tile_start.p;
-        const uint2* tile_desc = (const uint2*)st->tile_desc.p;
-        uint32_t* cnt2 = (uint32_t*)st->cnt2.p;
-        uint32_t* pos2 = (uint32_t*)st->pos2.p;
-        uint32_t* vals = (uint32_t*)st->vals.p;
-        uint32_t* chunk_bucket = (uint32_t*)st->chunk_bucket.p;
-        const uint32_t items = (uint32_t)P.l2_items;
+        const MsmWork wk{(uint32_t*)st->bin_offs.p, (uint32_t*)st->bin_aux.p, (uint32_t*)st->bin_start.p, (uint32_t*)st->tile_start.p,
+                         st->tile_desc.p, (uint32_t*)st->cnt2.p, (uint32_t*)st->pos2.p, st->pairs.p, (uint32_t*)st->vals.p,
+                         (uint32_t*)st->chunk_bucket.p};
         {
             ProfScope prof(c, "msm_bases_main");
-            hipLaunchKernelGGL((k_msm_bin_count<C, 0, true>), dim3(nblk, 1), dim3(1024), (size_t)P.nb1 * 4, c->stream, bt, mont, P.win,
-                               S, P.nb1, P.lb, bin_offs);
-            hipLaunchKernelGGL(k_msm_scan_tiles, dim3(ntiles, 1), dim3(1024), 0, c->stream, bin_offs, total, bin_aux, bt);
-            hipLaunchKernelGGL(k_msm_scan_aux, dim3(1, 1), dim3(1024), 0, c->stream, bin_offs, bin_aux, ntiles, nblk, P.nb1,
-                               bin_start, tile_start, (uint2*)st->tile_desc.p, (uint32_t)st->acc_threads, P.Btot, 0u, bt);
-            ZKT_HIP(c, hipGetLastError());
-            const size_t lds_scatter = (size_t)((3 * P.nb1 + 3) & ~3u) * 4 + (size_t)MSM_L1_CAP * (P.packed ? 4 : 8);
-            if (P.packed) {
-                hipLaunchKernelGGL((k_msm_bin_scatter<C, PairPacked, 0, true>), dim3(nblk, 1), dim3(1024), lds_scatter, c->stream, bt,
-                                   mont, P.win, S, P.nb1, P.lb, bin_offs, bin_aux, (uint32_t*)st->pairs.p);
-                ZKT_HIP(c, hipGetLastError());
-                hipLaunchKernelGGL((k_msm_l2_count<PairPacked, 8>), dim3(items, 1), dim3(256), 0, c->stream,
-                                   (const uint32_t*)st->pairs.p, P.nb1, P.lb, tile_start, tile_desc, cnt2, bt);
-            } else {
-                hipLaunchKernelGGL((k_msm_bin_scatter<C, PairWide, 0, true>), dim3(nblk, 1), dim3(1024), lds_scatter, c->stream, bt,
-                                   mont, P.win, S, P.nb1, P.lb, bin_offs, bin_aux, (uint2*)st->pairs.p);
-                ZKT_HIP(c, hipGetLastError());
-                auto kc2 = P.lcols == 8 ? k_msm_l2_count<PairWide, 8> : k_msm_l2_count<PairWide, 10>;
-                hipLaunchKernelGGL(kc2, dim3(items, 1), dim3(256), 0, c->stream, (const uint2*)st->pairs.p, P.nb1, P.lb, tile_start,
-                                   tile_desc, cnt2, bt);
-            }
-            {
-                auto ksc = P.lcols == 8 ? k_msm_l2_scan<8> : k_msm_l2_scan<10>;
-                hipLaunchKernelGGL(ksc, dim3(P.nb1, 1), dim3(256), 0, c->stream, cnt2, pos2, bin_start, tile_start, P.Btot, P.lb,
-                                   chunk_bucket, bt);
-            }
-            if (P.packed) {
-                hipLaunchKernelGGL((k_msm_l2_scatter<PairPacked, 8>), dim3(items, 1), dim3(MSM_L2S_THREADS), 0, c->stream,
-                                   (const uint32_t*)st->pairs.p, P.nb1, P.lb, tile_start, tile_desc, cnt2, pos2, vals, bt);
-            } else {
-                auto kss = P.lcols == 8 ? k_msm_l2_scatter<PairWide, 8> : k_msm_l2_scatter<PairWide, 10>;
-                hipLaunchKernelGGL(kss, dim3(items, 1), dim3(MSM_L2S_THREADS), 0, c->stream, (const uint2*)st->pairs.p, P.nb1,
-                                   P.lb, tile_start, tile_desc, cnt2, pos2, vals, bt);
-            }
-            ZKT_HIP(c, hipGetLastError());
-            const uint32_t chunks = (uint32_t)std::min(P.m, st->acc_threads);
-            hipLaunchKernelGGL(k_msm_accumulate<C>, dim3((chunks + 255) / 256, 1), dim3(256), 0, c->stream, vals, P.Btot,
-                               chunk_bucket, bt);
-            ZKT_HIP(c, hipGetLastError());
+            if ((rc = msm_launch_grouping<C, true>(c, P, wk, bt, mont, n, 1, st->acc_threads, false)) ||
+                (rc = msm_launch_accumulate<C>(c, P, wk.vals, wk.chunk_bucket, bt, n, st->acc_threads, st->acc_lds)))
+                return rc;
         }
         {
             ProfScope prof(c, "msm_bases_tail");
@@ -1923,7 +1881,7 @@ static int msm_bases_t(zkt_ctx* c, const void* bases, bool bases_on_device, cons
                 tb.heavy[j] = (uint32_t*)st->heavy.p;
             }
             // the fold of all W 2^(c-1) buckets as one MSM's (slot 0) ...
-            hipLaunchKernelGGL((k_msm_bucket_sum<C, true>), dim3((P.Btot + 1 + 255) / 256, 1), dim3(256), 0, c->stream, P.Btot, tb);
+            hipLaunchKernelGGL((k_msm_bucket_sum<C, true>), dim3((P.keys + 1 + 255) / 256, 1), dim3(256), 0, c->stream, P.keys, tb);
             hipLaunchKernelGGL((k_msm_heavy<C, true>), dim3(MSM_HEAVY_BLOCKS, 1), dim3(256), 0, c->stream, tb);
             ZKT_HIP(c, hipGetLastError());
             // ... then window w reduces buckets w Bw .. w Bw + Bw as a slot of its own, all windows in one launch.  Its bucket 0
@@ -1965,8 +1923,8 @@ void msm_info(zkt_ctx* c, int* cbits, int* windows, size_t* count) {
         *cbits = 0; *windows = 0; *count = 0;
         return;
     }
-    *cbits = c->msm->c;
-    *windows = c->msm->W;
+    *cbits = c->msm->plan.c;
+    *windows = c->msm->plan.W;
     *count = c->msm->count;
 }
 
@@ -2052,10 +2010,11 @@ int zkt_msm_g1_bases_dev(zkt_ctx* c, const void* d_bases_xy_mont, const void* d_
 int zkt_msm_bases_info(zkt_ctx* c, size_t n, int scalars_montgomery, int* window_bits, int* windows) {
     if (!c || !window_bits || !windows) return ZKT_ERR_INVALID_ARGUMENT;
     if (n > ZKT_MSM_BASES_MAX) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "msm_g1_bases: more points than ZKT_MSM_BASES_MAX (2^22)");
-    const int total = scalars_montgomery ? (c->curve == ZKT_CURVE_BN254 ? 255 : 256) : 257;
-    const int cb = msm_bases_cbits(n, c->curve);
-    *windows = n ? (total + cb - 1) / cb : 0;
-    *window_bits = n ? (total + *windows - 1) / *windows : 0;
+    MsmPlan P;   // n = 0: no windows
+    if (n)
+        if (int rc = msm_bases_plan(c, n, scalars_montgomery, P)) return rc;
+    *windows = P.W;
+    *window_bits = P.c;
     return ZKT_OK;
 }
 

@@ -1,6 +1,9 @@
-// State of the fixed-base MSM (msm.hip) shared with the Lagrange-basis table builder (lagrange.hip).
+// The G1 MSM (msm.hip) and the Lagrange-basis table builder (lagrange.hip): the plan and state of both MSM paths (over the
+// key's window table, over caller-supplied bases) and every entry point the other translation units call.
 #pragma once
 #include "ctx.hpp"
+
+#include <functional>
 
 namespace zkt {
 
@@ -19,6 +22,24 @@ struct MsmWindows {
     int W;
     uint8_t width[40];
     uint16_t start[40];
+};
+
+// What the grouping (two-level counting sort of (key, table index) pairs) and everything behind it is sized by, for
+// either MSM path (msm_plan, msm.hip).  Over the key's window table all windows share ONE set of B = 2^(c-1) buckets and a
+// pair's index addresses table[W][count]; over caller-supplied bases every window owns Bw = 2^(c-1) buckets of its own
+// (keys 1 .. W Bw) and the index addresses the n bases.
+struct MsmPlan {
+    MsmWindows win{};
+    int W = 0, c = 0;        // windows, widest digit
+    int dig = 0;             // compile-time window layout of the level-1 kernels (0: generic; always 0 over supplied bases)
+    uint32_t Bw = 0;         // buckets per window = 2^(c-1), ids 1..Bw
+    uint32_t keys = 0;       // key range of the sort: Bw (shared buckets) or W Bw
+    uint32_t lb = 8;         // level-2 key bits: key = (bin << lb) | low
+    int lcols = 8;           // log2 columns of the level-2 tables (8, or 10 for more than 2^17 keys)
+    bool packed = false;     // (low key, table index, sign) fit ONE 32-bit word: 4-byte pairs
+    uint32_t nb1 = 0;        // level-1 bins
+    uint32_t l1_scalars = 0; // scalars per level-1 workgroup
+    uint32_t l2_items = 0;   // upper bound of level-2 tiles
 };
 
 constexpr int MSM_BATCH = 3;         // MSMs whose grouping and accumulation go out as ONE launch per kernel (blockIdx.y = MSM)
@@ -56,10 +77,8 @@ struct MsmState {
     size_t count = 0;      // bases loaded
     // index-range sharding: this GPU holds powers [slice_off, slice_off + count) of a key of `total`
     size_t slice_off = 0, total = 0;
-    int c = 0, W = 0;      // max window bits, windows
-    MsmWindows win{};
+    MsmPlan plan;          // window and sort layout for `count` bases (shared buckets)
     uint32_t* heavy[11] = {};   // per slot: [0] = count, [1..] = heavy bucket ids
-    uint32_t B = 0;        // buckets = 2^(c-1), ids 1..B
     void* table = nullptr; // Affine[W][count]
     // Second base table (lagrange.hip): prefix sums of the Lagrange-basis key of the domain of size 2^lag_log_n followed by
     // the blinder points, same window layout, count2 <= count bases.  Commitments of polynomials given by their
@@ -80,13 +99,6 @@ struct MsmState {
     void* tile_desc = nullptr;                     // uint2[l2_items]: pair range of every level-2 tile
     uint32_t *cnt2 = nullptr, *pos2 = nullptr;     // [level-2 tiles][256]
     uint32_t* chunk_bucket = nullptr;              // bucket of the first pair of every accumulation chunk
-    uint32_t nb1 = 0;                              // level-1 bins
-    uint32_t lb = 8;                               // level-2 key bits: bucket = (bin << lb) | low
-    int lcols = 8;                                 // log2 columns of the level-2 tables (8, or 10 for more than 2^17 buckets)
-    bool packed = false;                           // (low key, table index, sign) fit ONE 32-bit word: 4-byte pairs
-    int dig = 0;                                   // compile-time window layout of the level-1 kernels (0: generic)
-    uint32_t l1_scalars = 0;                       // scalars per level-1 workgroup
-    uint32_t l2_items = 0;                         // upper bound of level-2 tiles
     MsmBatch strides{};                            // the s_* members: distance between the work buffers of a batch's MSMs
     // per slot, because the bucket fold that reads them runs on the side stream while the next MSM is already grouping
     uint32_t* offsets[11] = {};   // B + 2
@@ -124,31 +136,52 @@ struct MsmState {
 // first call and grown when a call needs more, so that the call never touches the prover's slots, work set or tables.
 // Device buffers are the context's (dev_alloc); only the pinned partial sums are freed here.
 struct MsmBasesState {
-    struct Buf {
-        void* p = nullptr;
-        size_t bytes = 0;
-    };
-    Buf bases;        // the call's points in the accumulation's packed R' form
-    Buf scalars;      // zkt_msm_g1_bases: the uploaded scalars
-    Buf vals, pairs, bin_offs, bin_aux, bin_start, tile_start, tile_desc, cnt2, pos2, chunk_bucket;   // grouping
-    Buf offsets, heavy, params, pieces, buckets, rowcol;                                              // accumulation, tail
+    DevBuf bases;     // the call's points in the accumulation's packed R' form
+    DevBuf scalars;   // zkt_msm_g1_bases: the uploaded scalars
+    DevBuf vals, pairs, bin_offs, bin_aux, bin_start, tile_start, tile_desc, cnt2, pos2, chunk_bucket;   // grouping
+    DevBuf offsets, heavy, params, pieces, buckets, rowcol;                                              // accumulation, tail
     void* partials = nullptr;       // pinned: W x (c) rows of partial sums the host combines (Horner over the windows)
     void* partials_dev = nullptr;
-    size_t acc_threads = 0;         // chunks an accumulation is cut into (occupancy query x 2, as MsmState)
+    size_t acc_lds = 0, acc_threads = 0;   // as MsmState's
     ~MsmBasesState() {
         if (partials) (void)hipHostFree(partials);
     }
 };
 
-// msm.hip: window multiples + R' conversion of an affine base table whose first `count` entries are filled (arkworks R form)
+constexpr size_t MSM_DEFER_MAX = ((size_t)1 << 16) + 64;      // small key: latency regime (tails deferred and batched)
+constexpr size_t MSM_TAIL_INL_MAX = ((size_t)1 << 18) + 64;   // up to here the bucket reduction's additions inline their products
+
+// ---- msm.hip ----
+// the key: `count` powers from the host or the device / generated from a trapdoor (test, bench); slice_off, total: this
+// GPU's index range of a sharded key (total = 0: the whole key)
+int srs_load(zkt_ctx* c, const void* src, size_t count, bool on_device, size_t slice_off = 0, size_t total = 0);
+int srs_generate(zkt_ctx* c, const uint64_t* tau4, size_t count, size_t slice_off = 0, size_t total = 0);
+void msm_release(zkt_ctx* c);
+// window multiples + R' conversion of an affine base table whose first `count` entries are filled (arkworks R form)
 int msm_table_finish(zkt_ctx* c, void* table, size_t count);
-// msm.hip: `child` gets an MSM state of its own (work buffers, slots, side stream) over `parent`'s base tables
+// `child` gets an MSM state of its own (work buffers, slots, side stream) over `parent`'s base tables (zkt_ctx_fork)
 int msm_fork(zkt_ctx* child, const zkt_ctx* parent);
+void msm_slice(zkt_ctx* c, size_t* off, size_t* count, size_t* total);
+// one MSM, begun and collected
+int msm_g1_dev(zkt_ctx* c, const void* d_scalars, size_t n, size_t base_off, int mont, uint64_t* out_xy, int* out_inf);
+// prover-facing batch form: begin up to MsmState::SLOTS commitments, then collect them (tbl = 1: the Lagrange-prefix
+// table of lagrange.hip)
+int msm_begin(zkt_ctx* c, const void* d_scalars, size_t n, size_t base_off, int mont, int slot, int tbl = 0);
+int msm_begin_batch(zkt_ctx* c, int k, const void* const* d_scalars, const size_t* ns, int mont, const int* slots, const int* tbls);
+// a round's queued commitments: batches of MSM_BATCH launches-as-one when `grouped`, then the deferred tails; ready(j),
+// when given, runs before the MSM of entry j is enqueued
+int msm_begin_many(zkt_ctx* c, int k, const void* const* d_scalars, const size_t* ns, int mont, const int* slots, const int* tbls,
+                   bool grouped, const std::function<int(int)>& ready = {});
+int msm_end(zkt_ctx* c, int slot, uint64_t* out_xy);
+int msm_end_sharded(zkt_ctx* c, const int* slots, const bool* have, int k, uint64_t* out_xy /* k x 12 words */);
 // issues the deferred tails (no-op when none are waiting); the prover calls it behind the last commitment of a round
 int msm_flush_tails(zkt_ctx* c);
 bool msm_defers_tails(const zkt_ctx* c);
 bool msm_batches_grouping(const zkt_ctx* c);   // a round's commitments are grouped as one batch of launches (small keys, and 2^18)
-constexpr size_t MSM_DEFER_MAX = ((size_t)1 << 16) + 64;      // small key: latency regime (tails deferred and batched)
-constexpr size_t MSM_TAIL_INL_MAX = ((size_t)1 << 18) + 64;   // up to here the bucket reduction's additions inline their products
+
+// ---- lagrange.hip ----
+int lagrange_ensure(zkt_ctx* c, int log_n);
+bool lagrange_ready(const zkt_ctx* c, int log_n);
+size_t lagrange_bases(const zkt_ctx* c);
 
 }  // namespace zkt

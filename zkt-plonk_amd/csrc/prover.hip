@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include "ec.hpp"
 #include "keyfile.hpp"
+#include "msm.hpp"
 #include "poly.hpp"
 #include "transcript.hpp"
 
@@ -20,24 +21,6 @@
 #include <vector>
 
 namespace zkt {
-
-// msm.hip (tbl = 1: the Lagrange-prefix table of lagrange.hip)
-int msm_g1_dev(zkt_ctx* c, const void* d_scalars, size_t n, size_t base_off, int mont, uint64_t* out_xy, int* out_inf);
-int msm_begin(zkt_ctx* c, const void* d_scalars, size_t n, size_t base_off, int mont, int slot, int tbl = 0);
-int msm_begin_batch(zkt_ctx* c, int k, const void* const* d_scalars, const size_t* ns, int mont, const int* slots, const int* tbls);
-int msm_flush_tails(zkt_ctx* c);           // issues the deferred bucket reductions of the commitments begun so far (small keys)
-// a round's queued commitments: batches of MSM_BATCH launches-as-one, then the deferred tails (shared with kzg.hip)
-int msm_begin_many(zkt_ctx* c, int k, const void* const* d_scalars, const size_t* ns, int mont, const int* slots, const int* tbls,
-                   bool grouped, const std::function<int(int)>& ready = {});
-bool msm_defers_tails(const zkt_ctx* c);
-bool msm_batches_grouping(const zkt_ctx* c);
-// lagrange.hip
-int lagrange_ensure(zkt_ctx* c, int log_n);
-bool lagrange_ready(const zkt_ctx* c, int log_n);
-size_t lagrange_bases(const zkt_ctx* c);
-int msm_end(zkt_ctx* c, int slot, uint64_t* out_xy);
-int msm_end_sharded(zkt_ctx* c, const int* slots, const bool* have, int k, uint64_t* out_xy);
-void msm_slice(zkt_ctx* c, size_t* off, size_t* count, size_t* total);
 
 enum { PK_QM = 0, PK_QL, PK_QR, PK_QO, PK_QC, PK_S1, PK_S2, PK_S3, PK_QLOOKUP, PK_QTABLE, PK_COUNT };
 // coset vectors kept on the device (keys/mod.rs:153-174; x and l_1 are stored, zh is 4 scalars)
