@@ -559,6 +559,21 @@ int zkt_g1_sum_host(int curve_id, const uint64_t* points_xy_mont, size_t count, 
 /* Elementwise Fr product on the device (out[i] = a[i]*b[i], Montgomery); test hook for the field
  * kernels. Host pointers. */
 int zkt_debug_fr_mul(zkt_ctx* ctx, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out);
+/* Up to four transforms of one plan in one launch per pass, the way the prover's rounds issue them, and nothing else:
+ * polynomial y reads in_len[y] <= 2^log_n elements of d_in[y] (the rest is zero) and writes 2^log_n to d_out[y]; the outputs
+ * are distinct, d_out[y] == d_in[y] is allowed.  Device pointers, Montgomery words; enqueued on the context's stream.
+ * nb outside 1 .. 4 -> ZKT_ERR_INVALID_ARGUMENT. */
+int zkt_debug_ntt_batch(zkt_ctx* ctx, int log_n, int inverse, int coset, int nb, const void* const* d_in, const size_t* in_len,
+                        void* const* d_out);
+/* Overrides the pass radices of every transform above 2^10 that this context runs afterwards: npass = 2 or 3 passes of
+ * 2^log_r[i] points, 5 <= log_r[i] <= 9, first pass first.  Tests use it to run every radix in every position at small
+ * sizes; the policy alone reaches radix 2^9 only from 2^25.  npass = 0 restores the policy (log_r is ignored).  Plans built
+ * under a split are kept apart from the policy's.  The prover's own transforms on this context obey the override too, at
+ * sizes it does not fit they fail: do not run a proof under one, restore the policy first.  ZKT_ERR_INVALID_ARGUMENT:
+ * another npass, a radix outside 5 .. 9, a forked context (it shares its root's plans); and, from the transform, a domain
+ * size that is not the product of the radices.  (A tile that would not fit its pass is refused as well, but no two or
+ * three radices of 2^5 and more have one: that check is a guard, not a reachable refusal.) */
+int zkt_debug_ntt_split(zkt_ctx* ctx, int npass, const int* log_r);
 /* Self-check of the host pairing's shortcuts against their plain definitions (Frobenius maps = powers by p, sparse
  * and cyclotomic products = dense ones, the final exponentiation leaves an element of order r).  0 = all good. */
 int zkt_debug_pairing_selftest(int curve_id);

@@ -92,6 +92,9 @@ def lib():
         L.zkt_dev_download.argtypes = [vp, vp, vp, ctypes.c_size_t]
         L.zkt_ntt.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, u64p, ctypes.c_size_t, u64p]
         L.zkt_ntt_dev.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t, vp]
+        L.zkt_debug_ntt_batch.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp),
+                                          ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(vp)]
+        L.zkt_debug_ntt_split.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
         L.zkt_domain_group_gen.argtypes = [vp, ctypes.c_int, u64p]
         L.zkt_debug_params.argtypes = [vp, ctypes.c_int, u32p, ctypes.c_size_t]
         L.zkt_debug_fr_mul.argtypes = [vp, u64p, u64p, ctypes.c_size_t, u64p]
@@ -1058,6 +1061,18 @@ class Context:
         w = list(buf)
         to_int = lambda l: sum(int(x) << (32 * i) for i, x in enumerate(l))
         return dict(p=to_int(w[0:n]), inv32=int(w[n]), r=to_int(w[n + 1:2 * n + 1]), r2=to_int(w[2 * n + 1:3 * n + 1]))
+
+    def debug_ntt_batch(self, log_n: int, d_in, in_len, d_out, inverse=False, coset=False, nb=None):
+        """zkt_debug_ntt_batch: nb transforms of one plan in one launch per pass; device pointers, lengths in elements."""
+        nb = len(d_in) if nb is None else nb
+        ins, outs = (ctypes.c_void_p * len(d_in))(*d_in), (ctypes.c_void_p * len(d_out))(*d_out)
+        lens = (ctypes.c_size_t * len(in_len))(*in_len)
+        self.check(self._L.zkt_debug_ntt_batch(self._h, log_n, int(inverse), int(coset), nb, ins, lens, outs))
+
+    def debug_ntt_split(self, log_r=()):
+        """zkt_debug_ntt_split: force the pass radices of the transforms above 2^10 run afterwards; () restores the policy."""
+        lr = (ctypes.c_int * max(len(log_r), 3))(*log_r)
+        self.check(self._L.zkt_debug_ntt_split(self._h, len(log_r), lr))
 
     def debug_fr_mul(self, a: np.ndarray, b: np.ndarray) -> np.ndarray:
         a = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 4)

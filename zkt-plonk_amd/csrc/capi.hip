@@ -388,6 +388,19 @@ int zkt_ntt_dev(zkt_ctx* c, int log_n, int inverse, int coset, const void* d_in,
     return ntt_run(c, log_n, inverse, coset ? 1 : 0, d_in, in_len, d_out);
 }
 
+int zkt_debug_ntt_batch(zkt_ctx* c, int log_n, int inverse, int coset, int nb, const void* const* d_in, const size_t* in_len,
+                        void* const* d_out) {
+    if (!c) return ZKT_ERR_INVALID_ARGUMENT;
+    if (!d_in || !in_len || !d_out) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
+    (void)hipSetDevice(c->device);
+    return ntt_run_batch(c, log_n, inverse, coset ? 1 : 0, nb, d_in, in_len, d_out);
+}
+
+int zkt_debug_ntt_split(zkt_ctx* c, int npass, const int* log_r) {
+    if (!c) return ZKT_ERR_INVALID_ARGUMENT;
+    return ntt_force_split(c, npass, log_r);
+}
+
 int zkt_ntt(zkt_ctx* c, int log_n, int inverse, int coset, const uint64_t* in, size_t in_len, uint64_t* out) {
     if (!c || !out || (!in && in_len)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
     if (log_n < 0 || log_n > 27) return set_err(c, ZKT_ERR_INVALID_DOMAIN_SIZE, "InvalidEvalDomainSize");

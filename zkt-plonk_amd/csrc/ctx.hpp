@@ -31,8 +31,12 @@ struct zkt_ctx {
     bool own_stream = false;
     std::string err;
 
-    // NTT plans keyed by (log_n, inverse, coset); tables live in HBM for the ctx lifetime.
-    std::map<std::tuple<int, int, int>, std::shared_ptr<void>> ntt_plans;
+    // NTT plans keyed by (log_n, inverse, coset, split); tables live in HBM for the ctx lifetime.  split: 0 = the policy's
+    // radices, otherwise the forced ones of zkt_debug_ntt_split (ntt_split_code), so the two never serve each other.
+    // (A fork copies the map, forced plans included; its own split stays 0, so it never looks one of those up.)
+    std::map<std::tuple<int, int, int, int>, std::shared_ptr<void>> ntt_plans;
+    int ntt_split_npass = 0;                 // zkt_debug_ntt_split: 0 = policy, else 2 or 3 passes of ntt_split_log_r
+    int ntt_split_log_r[3] = {0, 0, 0};
     // scratch (grown on demand, never shrunk)
     void* ntt_scratch = nullptr;
     size_t ntt_scratch_bytes = 0;
@@ -136,6 +140,8 @@ int ntt_run(zkt_ctx* c, int log_n, int inverse, int coset, const void* d_in, siz
 int ntt_run_batch(zkt_ctx* c, int log_n, int inverse, int coset, int nb, const void* const* d_in, const size_t* in_len,
                   void* const* d_out);
 int ntt_class_code(int log_big, int cls);
+// zkt_debug_ntt_split: npass = 0 restores the policy; transforms above 2^10 built afterwards use the given radices
+int ntt_force_split(zkt_ctx* c, int npass, const int* log_r);
 int ntt_run_class(zkt_ctx* c, int log_n, int log_big, int cls, const void* d_in, size_t in_len, void* d_out, void* d_fold);
 
 // prover.hip

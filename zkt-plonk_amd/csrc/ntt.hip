@@ -404,6 +404,42 @@ static void split_log_n(int log_n, int* npass, int* lr) {
     for (int i = 0; i < p; ++i) lr[i] = base + (i < rem ? 1 : 0);
 }
 
+// A forced split (zkt_debug_ntt_split) is usable when every radix has a pass kernel and every tile fits its pass: T = 2^(10 -
+// LOG_R) consecutive columns need log_s >= 10 - LOG_R on a non-last pass and log_r1 >= 10 - LOG_R on the last.  (With
+// radices of 2^5 and more both hold for any two or three of them; the check keeps that from being an accident.)
+static bool split_fits(int npass, const int* lr) {
+    if (npass != 2 && npass != 3) return false;
+    int log_n = 0;
+    for (int i = 0; i < npass; ++i) {
+        if (lr[i] < 5 || lr[i] > 9) return false;
+        log_n += lr[i];
+    }
+    int acc = 0;
+    for (int i = 0; i + 1 < npass; ++i) {
+        acc += lr[i];
+        if (log_n - acc < TILE_LOG - lr[i]) return false;
+    }
+    return lr[0] >= TILE_LOG - lr[npass - 1];
+}
+
+static int ntt_split_code(const zkt_ctx* c) {
+    if (!c->ntt_split_npass) return 0;
+    return c->ntt_split_npass | c->ntt_split_log_r[0] << 4 | c->ntt_split_log_r[1] << 8 | c->ntt_split_log_r[2] << 12;
+}
+
+int ntt_force_split(zkt_ctx* c, int npass, const int* log_r) {
+    if (c->parent) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "zkt_debug_ntt_split: a forked context shares its root's plans");
+    if (npass == 0) {
+        c->ntt_split_npass = 0;
+        return ZKT_OK;
+    }
+    if (!log_r || !split_fits(npass, log_r))
+        return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "zkt_debug_ntt_split: two or three radices of 2^5 .. 2^9 whose tiles fit");
+    c->ntt_split_npass = npass;
+    for (int i = 0; i < 3; ++i) c->ntt_split_log_r[i] = i < npass ? log_r[i] : 0;
+    return ZKT_OK;
+}
+
 template <class P>
 struct PlanHolder {
     NttPlan<P> plan;
@@ -461,11 +497,16 @@ static Fe<P> coset_shift(int code) {
 }
 
 template <class P>
-static int build_plan(zkt_ctx* c, int log_n, int inverse, int coset, NttPlan<P>& pl) {
+static int build_plan(zkt_ctx* c, int log_n, int inverse, int coset, bool forced, NttPlan<P>& pl) {
     pl.log_n = log_n;
     pl.inverse = inverse;
     pl.coset = coset;
-    split_log_n(log_n, &pl.npass, pl.log_r);
+    if (forced) {
+        pl.npass = c->ntt_split_npass;
+        for (int i = 0; i < 3; ++i) pl.log_r[i] = c->ntt_split_log_r[i];
+    } else {
+        split_log_n(log_n, &pl.npass, pl.log_r);
+    }
     const uint64_t N = (uint64_t)1 << log_n;
     Fe<P> w = root_of_unity<P>(log_n);
     if (inverse) w = fe_inv_host<P>(w);
@@ -629,11 +670,14 @@ static int ntt_run_batch_t(zkt_ctx* c, int log_n, int inverse, int coset, int nb
     const uint64_t N = (uint64_t)1 << log_n;
     for (int y = 0; y < nb; ++y)
         if (in_len[y] > N) return set_err(c, ZKT_ERR_INVALID_DOMAIN_SIZE, "more coefficients than the domain size");
-    auto key = std::make_tuple(log_n, inverse ? 1 : 0, coset);
+    const bool forced = c->ntt_split_npass && log_n > TILE_LOG;   // the single-workgroup kernel has no passes to split
+    if (forced && c->ntt_split_log_r[0] + c->ntt_split_log_r[1] + c->ntt_split_log_r[2] != log_n)
+        return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "the forced split (zkt_debug_ntt_split) does not multiply to this domain size");
+    auto key = std::make_tuple(log_n, inverse ? 1 : 0, coset, forced ? ntt_split_code(c) : 0);
     auto it = c->ntt_plans.find(key);
     if (it == c->ntt_plans.end()) {
         auto holder = std::make_shared<NttPlan<P>>();
-        int rc = build_plan<P>(c, log_n, inverse ? 1 : 0, coset, *holder);
+        int rc = build_plan<P>(c, log_n, inverse ? 1 : 0, coset, forced, *holder);
         if (rc) return rc;
         it = c->ntt_plans.emplace(key, std::static_pointer_cast<void>(holder)).first;
     }
