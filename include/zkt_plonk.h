@@ -78,7 +78,9 @@ int zkt_ctx_synchronize(zkt_ctx* ctx);
  * reduction, on the side stream), "quotient", and the prover's rounds as stream time between their first and last
  * launch: "round1", "round2" (prove.rs:116-185; issued early when announced by zkt_prove_set_next), "round3"
  * (:190-255), "round4" (:258-313), "round5" (:318-451); "msm_lag_main" / "msm_lag_accumulate": the same two scopes for
- * commitments taken in the Lagrange basis (their pairs are few, they would dilute the dense kernel's average);
+ * commitments taken in the Lagrange basis -- t, h1, h2, z2 over the prefix table and the wires committed over their
+ * base tables (see "Commitments of evaluation vectors"): they have fewer pairs than the n + 3 points "msm_accumulate" is
+ * priced at and would dilute the dense kernel's average;
  * "host_wait": idle time of the context's stream across the prover's host round trips (from the moment the stream
  * drains while the host waits for a round's commitments or evaluations to the next launch; six per proof).
  * The KZG seam (zkt_kzg_commit_batch / zkt_kzg_open): "kzg_commit_batch" (the whole batch of MSMs on the stream),
@@ -267,7 +269,29 @@ int zkt_kzg_open_dev(zkt_ctx* ctx, const void* const* d_coeffs, const size_t* le
  * what its coefficients would.  The second base table (prefix sums of the inverse DFT of the powers over G1, plus the
  * blinder points; as large as the first) is built on the first proof after a key or circuit change -- about 0.55 s at
  * n = 2^20 on BN254 -- when the key is whole (not a slice of a sharded key) and holds more than n powers; otherwise,
- * or after zkt_ctx_set_lagrange(ctx, 0), the coefficients are committed as the reference does. */
+ * or after zkt_ctx_set_lagrange(ctx, 0), the coefficients are committed as the reference does.
+ *
+ * Wire polynomials over per-variable bases.  A wire's evaluation vector is a gather of the variable map (prove.rs:49-55:
+ * a[i] = variables[w_l[i]]), so  commit(a) = sum_v variables[v] T_v + blinder terms,  T_v = sum_{i : w_l[i] = v} [L_i(tau)] G:
+ * one scalar per DISTINCT variable of the wire, not one per row.  The route is taken for a proof that passes the witness
+ * as `variables` + w_l / w_r / w_o with wires_on_device != 0, when the Lagrange-basis table above exists and commitments
+ * of evaluations are not switched off; per wire, when its distinct variables are fewer than 0.9 n_rows (the withdraw
+ * circuit at n = 2^20: the right wire has 0.27 n_rows, the left 0.83, the output wire 1.00 and stays dense).
+ * Cached: per wire the sorted distinct variables and the table of their T_v with the two blinder points (window
+ * multiples as for the other tables: 64 bytes x windows per base on BN254, 265 MB + 810 MB for the circuit above), built
+ * inside the first proof that brings a wiring (one-off; not yet timed on hardware, see docs/EXPERIMENTS.md), keyed on the three vectors'
+ * addresses, n_rows, n_vars, the key and the domain.  Forks made afterwards read the same tables; a fork made before
+ * builds its own.  A key or circuit reload drops them.
+ * Staleness: the build keeps a 128-bit digest of the vectors' contents (sums of position-keyed 64-bit mixes; it guards
+ * against reuse of the addresses, not against an adversary).  Every proof on the route computes the digest of the vectors it
+ * was given ahead of round 1; the host compares when it collects round 1 (also of a proof announced with
+ * zkt_prove_set_next), before a_commit is absorbed.  On a mismatch the affected commitments are taken again from the
+ * blinded coefficients, which exist anyway, and the tables are rebuilt by the next proof (a context whose forks read its
+ * tables keeps them and commits densely instead).
+ * Fallbacks, per wire, to the coefficient route: too many distinct variables; a T_v that is the identity (a degenerate
+ * tau); a table that cannot be allocated; a blinded polynomial trimmed below n coefficients (a constant or all-Zero
+ * wire: its blinders then sit below X^n; found with the digest, committed again).  Sharded keys and host-resident
+ * witnesses keep dense wire commitments.  The proof bytes are the same on either route. */
 int zkt_ctx_set_lagrange(zkt_ctx* ctx, int on);
 /* *log_n = domain the table serves (-1: none, evaluations go through their coefficients), *bases = its points */
 int zkt_lagrange_info(zkt_ctx* ctx, int* log_n, size_t* bases);
@@ -601,6 +625,15 @@ int zkt_debug_grand_products(zkt_ctx* ctx, const uint64_t* challenges, const uin
  * (zkt_prove_set_next); the next zkt_prove rebuilds its table polynomial and keys.  Host pointers, Montgomery words. */
 int zkt_debug_combine_split(zkt_ctx* ctx, const uint64_t* table, size_t table_len, const uint64_t* f, int fresh,
                             uint64_t* h1_out, uint64_t* h2_out);
+/* The prover's round-1 code alone (gather, transforms, the three wire commitments and their collection) on a variable
+ * map and index vectors in HBM that need satisfy no circuit; the loaded circuit fixes n.  blinders: 6 x 4 words (two per
+ * wire, a b c), host.  route 0 = through the coefficients, 1 = over the wire base tables where the rules of "Commitments
+ * of evaluation vectors" allow them; out_route[k] = 1 when wire k's commitment is the one taken over its table.
+ * out_xy: 3 x (x || y) Montgomery limbs, (0,0) and out_is_infinity[k] = 1 for the identity.  An index >= n_vars ->
+ * ZKT_ERR_INVALID_ARGUMENT.  Synchronises the stream; refused while a next proof is announced (zkt_prove_set_next). */
+int zkt_debug_commit_wires_dev(zkt_ctx* ctx, const void* d_variables, size_t n_vars, const uint32_t* d_w_l, const uint32_t* d_w_r,
+                               const uint32_t* d_w_o, size_t n_rows, const uint64_t* blinders, int route, uint64_t* out_xy_mont,
+                               int* out_is_infinity, int* out_route);
 /* kzg10's witness polynomial alone (row a12): out[0 .. len - 1) = (p(X) - p(z)) / (X - z) for the len <= n + 8 coefficients
  * p, as the prover computes it (scaled suffix sums).  Host pointers, Montgomery words. */
 int zkt_debug_open_witness(zkt_ctx* ctx, const uint64_t* coeffs, size_t len, const uint64_t* z4, uint64_t* out);

@@ -1126,6 +1126,25 @@ class Context:
                                                    1 if fresh else 0, u64p(h1), u64p(h2)))
         return h1, h2
 
+    def debug_commit_wires_dev(self, d_variables: int, n_vars: int, d_w_l: int, d_w_r: int, d_w_o: int, n_rows: int, blinders,
+                               route: int = 1):
+        """zkt_debug_commit_wires_dev: the prover's round-1 commitments of the three wires for a variable map and index
+        vectors in HBM (device addresses).  blinders (6, 4).  -> (xy (3, 2*fq_limbs) Montgomery limbs, is_infinity (3,),
+        route taken (3,): 1 = over the wire's base table)."""
+        bl = np.ascontiguousarray(blinders, dtype=np.uint64).reshape(6, 4)
+        out = np.zeros((3, 2 * self.fq_limbs), dtype=np.uint64)
+        inf = (ctypes.c_int * 3)()
+        took = (ctypes.c_int * 3)()
+        self._L.zkt_debug_commit_wires_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                                       ctypes.POINTER(ctypes.c_uint64), ctypes.c_int,
+                                                       ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int),
+                                                       ctypes.POINTER(ctypes.c_int)]
+        self.check(self._L.zkt_debug_commit_wires_dev(self._h, ctypes.c_void_p(d_variables), n_vars, ctypes.c_void_p(d_w_l),
+                                                      ctypes.c_void_p(d_w_r), ctypes.c_void_p(d_w_o), n_rows, u64p(bl), int(route),
+                                                      u64p(out), inf, took))
+        return out, [bool(x) for x in inf], [int(x) for x in took]
+
     def check_epk_file(self, path: str):
         """zkt_circuit_check_epk_file: None when every vector of the reference CLI's --epk file equals the loaded circuit's
         extended key as the device derives it, else (vector 0..16, first differing element or -1 for a wrong length)."""

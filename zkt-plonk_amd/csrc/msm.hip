@@ -1133,6 +1133,10 @@ static int msm_setup(zkt_ctx* c, size_t count, const MsmState* share = nullptr) 
         st->count2 = share->count2;
         st->lag_log_n = share->lag_log_n;
         st->lag_failed = share->lag_failed;
+        if (share->wb.built && !share->wb.stale) {   // the wire base tables that exist now; later ones this context builds itself
+            st->wb = share->wb;
+            st->wb.borrowed = true;
+        }
         st->slice_off = share->slice_off;
         st->total = share->total;
     } else if ((rc = dev_alloc(c, &st->table, (size_t)P.W * count * sizeof(Affine<Q>)))) {
@@ -1232,6 +1236,9 @@ void msm_release(zkt_ctx* c) {
     MsmState& st = *c->msm;
     (void)hipStreamSynchronize(c->stream);
     if (st.side) (void)hipStreamSynchronize(st.side);
+    wire_bases_drop(c);
+    for (DevBuf& b : st.wb_scalars) dev_free(c, b.p);
+    dev_free(c, st.wb_dig);
     void* ptrs[] = {st.table_borrowed ? nullptr : st.table, st.table2_borrowed ? nullptr : st.table2, st.vals2, st.pairs,
                     st.bin_offs, st.bin_aux, st.bin_start, st.tile_start, st.cnt2, st.pos2, st.chunk_bucket, st.tile_desc};
     for (void* p : ptrs) dev_free(c, p);
@@ -1463,7 +1470,8 @@ static int msm_enqueue_batch(zkt_ctx* c, int k, const void* const* d_scalars, co
                 if (int rc0 = msm_launch_tails<C>(c)) return rc0;
     if (st.n_tail_wait + k > MSM_TAIL_BATCH)
         if (int rc0 = msm_launch_tails<C>(c)) return rc0;
-    // tbls[j] = 1: the Lagrange-prefix table of lagrange.hip (count2 bases) instead of the key's powers
+    // tbls[j] = 1: the Lagrange-prefix table of lagrange.hip (count2 bases) instead of the key's powers; MSM_TBL_WIRE + k: the
+    // base table of wire k (lagrange.hip: one base per distinct variable)
     MsmBatch bt = st.strides;
     bool all_lag = true;
     for (int j = 0; j < k; ++j) all_lag = all_lag && tbls[j] != 0;
@@ -1476,8 +1484,8 @@ static int msm_enqueue_batch(zkt_ctx* c, int k, const void* const* d_scalars, co
         bt.scalars[j] = d_scalars[jj];
         bt.n[j] = ns[jj];
         bt.base_off[j] = base_offs[jj];
-        bt.table[j] = tbls[jj] ? st.table2 : st.table;
-        bt.tcount[j] = tbls[jj] ? st.count2 : st.count;
+        bt.table[j] = st.tbl_table(tbls[jj]);
+        bt.tcount[j] = st.tbl_count(tbls[jj]);
         bt.heavy[j] = st.heavy[slot];
         bt.params[j] = st.params[slot];
         bt.offsets[j] = st.offsets[slot];
@@ -1604,8 +1612,9 @@ static int msm_run_t(zkt_ctx* c, const void* d_scalars, size_t n, size_t base_of
 int msm_begin(zkt_ctx* c, const void* d_scalars, size_t n, size_t base_off, int mont, int slot, int tbl) {
     if (!c->msm) return set_err(c, ZKT_ERR_NOT_LOADED, "no SRS loaded (zkt_srs_load)");
     if (slot < 0 || slot >= MsmState::SLOTS) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "bad MSM slot");
-    if (tbl && !c->msm->table2) return set_err(c, ZKT_ERR_NOT_LOADED, "no Lagrange-basis table built");
-    const size_t cnt = tbl ? c->msm->count2 : c->msm->count;
+    if (tbl < 0 || tbl > MSM_TBL_WIRE + 2) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "bad MSM base table");
+    if (tbl && !c->msm->tbl_table(tbl)) return set_err(c, ZKT_ERR_NOT_LOADED, "no Lagrange-basis table built");
+    const size_t cnt = c->msm->tbl_count(tbl);
     if (n == 0 || base_off > cnt || n > cnt - base_off)
         return set_err(c, ZKT_ERR_TOO_MANY_COEFFICIENTS, "TooManyCoefficients: polynomial longer than the committer key");
     if (c->curve == ZKT_CURVE_BN254) return msm_enqueue<Bn254Curve>(c, d_scalars, n, base_off, mont, slot, tbl);
@@ -1620,8 +1629,9 @@ int msm_begin_batch(zkt_ctx* c, int k, const void* const* d_scalars, const size_
         if (slots[j] < 0 || slots[j] >= MsmState::SLOTS) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "bad MSM slot");
         for (int i = 0; i < j; ++i)
             if (slots[i] == slots[j]) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "msm batch: slots must differ");
-        if (tbls[j] && !c->msm->table2) return set_err(c, ZKT_ERR_NOT_LOADED, "no Lagrange-basis table built");
-        if (ns[j] == 0 || ns[j] > (tbls[j] ? c->msm->count2 : c->msm->count))
+        if (tbls[j] < 0 || tbls[j] > MSM_TBL_WIRE + 2) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "bad MSM base table");
+        if (tbls[j] && !c->msm->tbl_table(tbls[j])) return set_err(c, ZKT_ERR_NOT_LOADED, "no Lagrange-basis table built");
+        if (ns[j] == 0 || ns[j] > c->msm->tbl_count(tbls[j]))
             return set_err(c, ZKT_ERR_TOO_MANY_COEFFICIENTS, "TooManyCoefficients: polynomial longer than the committer key");
     }
     if (c->curve == ZKT_CURVE_BN254) return msm_enqueue_batch<Bn254Curve>(c, k, d_scalars, ns, offs, mont, slots, tbls);

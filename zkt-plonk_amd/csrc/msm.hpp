@@ -73,6 +73,26 @@ struct MsmTailBatch {                // per-slot arguments of a batched tail
 constexpr int MSM_HEAVY = 32;       // buckets with more pieces than this are folded by a whole block
 constexpr int MSM_HEAVY_BLOCKS = 64;     // grid-stride over the (normally empty) list of crowded buckets
 
+// Wire base tables (lagrange.hip): a wire's evaluation vector is a gather of the variable map, a[i] = variables[w[i]], so
+// its commitment is  sum_v variables[v] T_v  with  T_v = sum_{i : w[i] = v} [L_i(tau)] G  -- one scalar per DISTINCT variable
+// of the wire.  The tables depend on the key and the wiring only; they are keyed on the index vectors' addresses and
+// sizes, the key and the domain, and carry a digest of the vectors' contents that every proof checks.
+struct WireBases {
+    void* table[3] = {};       // Affine[W][cnt + 2]: T of every distinct variable (ascending), then the two blinder points
+    uint32_t* u[3] = {};       // the cnt distinct variables, ascending
+    size_t cnt[3] = {};
+    bool use[3] = {};          // false: the wire is committed through its coefficients (too many distinct variables, ...)
+    bool built = false;        // the key below was examined (use[] says what came of it)
+    bool borrowed = false;     // zkt_ctx_fork: the parent's tables (never freed here)
+    bool stale = false;        // a proof found other index contents than the digest: rebuild before the next use
+    const void* w[3] = {};
+    size_t n_rows = 0, n_vars = 0;
+    int log_n = -1;
+    uint64_t srs_generation = 0;
+    uint64_t digest[2] = {};
+};
+constexpr int MSM_TBL_WIRE = 2;      // msm_begin tbl = MSM_TBL_WIRE + k: the table of wire k (0 left, 1 right, 2 output)
+
 struct MsmState {
     size_t count = 0;      // bases loaded
     // index-range sharding: this GPU holds powers [slice_off, slice_off + count) of a key of `total`
@@ -89,6 +109,13 @@ struct MsmState {
     bool lag_failed = false;       // the key is too short (or sharded): evaluations are committed through their coefficients
     // zkt_ctx_fork: the base tables belong to the context this one was forked from (read-only here, never freed here)
     bool table_borrowed = false, table2_borrowed = false;
+    WireBases wb;
+    DevBuf wb_scalars[3];          // per wire: cnt + 2 scalars of the proof being enqueued (read by its grouping launches only)
+    uint64_t* wb_dig = nullptr;    // device: the digest kernel's two sums
+    uint64_t* wb_pin = nullptr;    // pinned: [0..1] digest of the proof in flight, [2..3] the three trimmed lengths (32-bit)
+    // the base table and its bases per window behind a `tbl` selector
+    const void* tbl_table(int tbl) const { return tbl >= MSM_TBL_WIRE ? wb.table[tbl - MSM_TBL_WIRE] : tbl ? table2 : table; }
+    size_t tbl_count(int tbl) const { return tbl >= MSM_TBL_WIRE ? wb.cnt[tbl - MSM_TBL_WIRE] + 2 : tbl ? count2 : count; }
     uint32_t* params[11] = {};     // per slot, device: [0] chunk, [1] pairs (written by k_msm_scan_aux)
     // work buffers (sized for n = count)
     uint32_t* vals2 = nullptr;                     // table indices grouped by bucket
@@ -129,6 +156,7 @@ struct MsmState {
             if (ev_done[i]) (void)hipEventDestroy(ev_done[i]);
         }
         if (side) (void)hipStreamDestroy(side);
+        if (wb_pin) (void)hipHostFree(wb_pin);
     }
 };
 
@@ -165,7 +193,7 @@ void msm_slice(zkt_ctx* c, size_t* off, size_t* count, size_t* total);
 // one MSM, begun and collected
 int msm_g1_dev(zkt_ctx* c, const void* d_scalars, size_t n, size_t base_off, int mont, uint64_t* out_xy, int* out_inf);
 // prover-facing batch form: begin up to MsmState::SLOTS commitments, then collect them (tbl = 1: the Lagrange-prefix
-// table of lagrange.hip)
+// table of lagrange.hip, tbl = MSM_TBL_WIRE + k: the base table of wire k)
 int msm_begin(zkt_ctx* c, const void* d_scalars, size_t n, size_t base_off, int mont, int slot, int tbl = 0);
 int msm_begin_batch(zkt_ctx* c, int k, const void* const* d_scalars, const size_t* ns, int mont, const int* slots, const int* tbls);
 // a round's queued commitments: batches of MSM_BATCH launches-as-one when `grouped`, then the deferred tails; ready(j),
@@ -183,5 +211,17 @@ bool msm_batches_grouping(const zkt_ctx* c);   // a round's commitments are grou
 int lagrange_ensure(zkt_ctx* c, int log_n);
 bool lagrange_ready(const zkt_ctx* c, int log_n);
 size_t lagrange_bases(const zkt_ctx* c);
+// Wire base tables.  _prepare makes the tables of these index vectors current (builds them when the key, the vectors'
+// addresses or sizes changed or a proof found them stale; synchronises the stream then) -- ZKT_OK also when none can be
+// had; wire_bases_use tells per wire.  _digest enqueues the digest of the vectors' present contents (into pinned
+// memory), _lens the copy of the three trimmed lengths; _scalars the gather of wire k's scalars; once the stream has
+// passed them, _check compares: false = wire k has to be committed again through its coefficients.
+int wire_bases_prepare(zkt_ctx* c, int log_n, const uint32_t* const* d_idx, size_t n_rows, size_t n_vars);
+bool wire_bases_use(const zkt_ctx* c, int k);
+int wire_bases_digest(zkt_ctx* c, const uint32_t* const* d_idx, size_t n_rows);
+int wire_bases_lens(zkt_ctx* c, const uint32_t* d_lens);
+int wire_bases_scalars(zkt_ctx* c, int k, const void* d_vars, const void* d_blinders, size_t n, const void** out, size_t* len);
+bool wire_bases_check(zkt_ctx* c, int k, size_t n);
+void wire_bases_drop(zkt_ctx* c);
 
 }  // namespace zkt

@@ -96,6 +96,10 @@ struct CircuitState {
     uint64_t t_commit_xy[12] = {};
     // zkt_ctx_fork: the keys (pk, coset, sigma_ev, q_lookup_ev, roots) belong to the context this one was forked from
     bool keys_borrowed = false;
+    // wire base tables (lagrange.hip): the wires of the round 1 last enqueued that were committed over them; their digest
+    // and trimmed lengths are compared when that round is collected (collect_wires)
+    bool wire_route[3] = {};
+    bool wire_dense_only = false;   // zkt_debug_commit_wires_dev route 0
 };
 
 // ---- host field helpers ------------------------------------------------------------------------------
@@ -299,6 +303,27 @@ struct Prover {
             if (skip && skip[j]) continue;
             memcpy(out[j].x.v, xy + 12 * j, Q::N * 4);
             memcpy(out[j].y.v, xy + 12 * j + Q::N / 2, Q::N * 4);
+        }
+        return ZKT_OK;
+    }
+
+    // Round 1 over wire base tables, once its commitments are collected (the stream has then passed the digest of the
+    // index vectors and the trimmed lengths): a wire whose table was built from other index contents, or whose polynomial
+    // was trimmed (its blinders then sit below X^n), is committed again through the coefficients in S.poly[k], before
+    // anything is absorbed into the transcript.  took[k], when given: wire k kept its table's commitment.
+    int collect_wires(Affine<Q>* cm, int* took = nullptr) {
+        for (int k = 0; k < 3; ++k) {
+            const bool routed = S.wire_route[k];
+            S.wire_route[k] = false;
+            if (took) took[k] = 0;
+            if (!routed) continue;
+            if (wire_bases_check(c, k, S.n)) {
+                if (took) took[k] = 1;
+                continue;
+            }
+            static const int slot[1] = {0};
+            int rc = msm_begin(c, S.poly[k], S.n + 2, 0, 1, 0);
+            if (rc || (rc = commit_collect(slot, nullptr, 1, cm + k))) return rc;
         }
         return ZKT_OK;
     }
@@ -519,6 +544,16 @@ struct Prover {
             }
         }
         const bool host_wires = !from_vars && !in.wires_on_device;
+        // Wire base tables (lagrange.hip): a device-resident variable map and index vectors, a whole key with its
+        // Lagrange-basis table, commitments of evaluations not switched off.  Their digest goes out ahead of the round.
+        for (bool& r : S.wire_route) r = false;
+        bool wire_tables = from_vars && in.wires_on_device && !c->sharded() && !c->lagrange_off && !S.wire_dense_only &&
+                           lagrange_ready(c, S.log_n) && in.n_rows > 0;
+        if (wire_tables) {
+            if ((rc = wire_bases_prepare(c, S.log_n, d_idx, in.n_rows, in.n_vars))) return rc;
+            wire_tables = wire_bases_use(c, 0) || wire_bases_use(c, 1) || wire_bases_use(c, 2);
+            if (wire_tables && (rc = wire_bases_digest(c, d_idx, in.n_rows))) return rc;
+        }
         if (host_wires) {
             // cold path: the three wire vectors cross PCIe inside the call.  They travel on the copy stream while the main
             // stream already transforms and commits the wire before, so only the first upload is exposed.
@@ -547,11 +582,20 @@ struct Prover {
             }
             const PolyJob jobs[3] = {{S.ev[0], S.poly[0], 0, 2, 0}, {S.ev[1], S.poly[1], 2, 2, 1}, {S.ev[2], S.poly[2], 4, 2, 2}};
             if ((rc = evals_to_blinded_polys(jobs, 3))) return rc;
-            {
-                void* const polys[3] = {S.poly[0], S.poly[1], S.poly[2]};
-                const size_t lens[3] = {n + 2, n + 2, n + 2};
-                static const int slots[3] = {0, 1, 2};
-                if ((rc = commit_begin_many(polys, lens, slots, 3))) return rc;
+            if (wire_tables && (rc = wire_bases_lens(c, S.status + 8))) return rc;
+            for (int k = 0; k < 3; ++k) {
+                // a wire with a base table: one scalar per distinct variable (and the two blinders) instead of n + 2
+                // coefficients; the evaluation vector above is still needed by the transforms, z1 and the index check
+                const void* sc = S.poly[k];
+                size_t len = n + 2;
+                int tbl = 0;
+                if (wire_tables && wire_bases_use(c, k)) {
+                    if ((rc = wire_bases_scalars(c, k, d_vars, (const char*)S.small + (size_t)(2 * k) * 32, n, &sc, &len))) return rc;
+                    tbl = MSM_TBL_WIRE + k;
+                    S.wire_route[k] = true;
+                }
+                rc = queueing() ? commit_push(sc, len, k, tbl) : tbl ? msm_begin(c, sc, len, 0, 1, k, tbl) : commit_begin(sc, len, k);
+                if (rc) return rc;
             }
         }
         if ((rc = commit_flush())) return rc;
@@ -642,6 +686,7 @@ struct Prover {
             static const int slots[6] = {0, 1, 2, 3, 4, 5};
             const bool skip[6] = {false, false, false, same_table, false, false};
             if ((rc = commit_collect(slots, skip, 6, cm))) return rc;
+            if ((rc = collect_wires(cm))) return rc;
         }
         mark("wait commits of rounds 1+2");
         if (!same_table) {
@@ -1063,6 +1108,7 @@ void circuit_release(zkt_ctx* c) {
     fr(S.status_alt);
     fr(S.aux_scan_tmp); fr(S.aux_pw);
     for (void* q : S.lag_scalars_q) fr(q);
+    wire_bases_drop(c);   // the wiring is the circuit's
     if (S.aux_stream) {
         (void)hipStreamSynchronize(S.aux_stream);
         (void)hipStreamDestroy(S.aux_stream);
@@ -1858,6 +1904,65 @@ int zkt_debug_open_witness(zkt_ctx* c, const uint64_t* coeffs, size_t len, const
     ZKT_HIP(c, hipMemcpyAsync(out, S.sc[3], (len - 1) * 32, hipMemcpyDeviceToHost, c->stream));
     ZKT_HIP(c, hipStreamSynchronize(c->stream));
     return ZKT_OK;
+}
+
+// Test hook: round 1 of the prover (gather, transforms, the three wire commitments, their collection) on a variable map
+// and index vectors that need satisfy nothing.
+extern "C++" template <class C>
+static int debug_commit_wires_t(zkt_ctx* c, const zkt_prove_inputs& in, int route, uint64_t* out_xy, int* out_inf, int* out_route) {
+    using Q = typename C::Fq;
+    CircuitState& S = *c->circuit;
+    MerlinHostTranscript tr("zkt_debug_commit_wires_dev");
+    Prover<C> p(c, S, tr);
+    S.wire_dense_only = route == 0;
+    int rc = p.enqueue_round_1(in);
+    S.wire_dense_only = false;
+    Affine<Q> cm[3];
+    static const int slots[3] = {0, 1, 2};
+    int took[3] = {0, 0, 0};
+    if (!rc) rc = p.commit_collect(slots, nullptr, 3, cm);
+    if (!rc) rc = p.collect_wires(cm, took);
+    p.wait_end();
+    if (!rc) rc = p.check_status();   // synchronises; an index outside the variable map
+    if (rc) {
+        for (bool& r : S.wire_route) r = false;
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    for (int k = 0; k < 3; ++k) {
+        memcpy(out_xy + (size_t)k * Q::N, cm[k].x.v, Q::N * 4);
+        memcpy(out_xy + (size_t)k * Q::N + Q::N / 2, cm[k].y.v, Q::N * 4);
+        if (out_inf) out_inf[k] = aff_is_inf<Q>(cm[k]) ? 1 : 0;
+        if (out_route) out_route[k] = took[k];
+    }
+    return ZKT_OK;
+}
+
+int zkt_debug_commit_wires_dev(zkt_ctx* c, const void* d_variables, size_t n_vars, const uint32_t* d_w_l, const uint32_t* d_w_r,
+                               const uint32_t* d_w_o, size_t n_rows, const uint64_t* blinders, int route, uint64_t* out_xy,
+                               int* out_is_infinity, int* out_route) {
+    if (!c || !d_variables || !blinders || !out_xy) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
+    if (route != 0 && route != 1) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "route: 0 coefficients, 1 wire base tables");
+    if (!c->circuit) return set_err(c, ZKT_ERR_NOT_LOADED, "no circuit loaded (the domain comes from it)");
+    if (!c->msm) return set_err(c, ZKT_ERR_NOT_LOADED, "no SRS loaded (zkt_srs_load)");
+    if (c->sharded()) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "not available on a sharded key");
+    CircuitState& S = *c->circuit;
+    if (S.has_next) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "zkt_debug_commit_wires_dev: a next proof is announced");
+    (void)hipSetDevice(c->device);
+    S.prefetch_stage = 0;   // the work buffers are shared with an announced proof's early rounds
+    if (route == 1 && !c->lagrange_off)
+        if (int rc1 = lagrange_ensure(c, S.log_n)) return rc1;
+    uint64_t bl[19 * 4] = {};
+    memcpy(bl, blinders, 6 * 32);
+    zkt_prove_inputs in{};
+    in.variables = (const uint64_t*)d_variables;
+    in.n_vars = n_vars;
+    in.w_l = d_w_l; in.w_r = d_w_r; in.w_o = d_w_o;
+    in.n_rows = n_rows;
+    in.wires_on_device = 1;
+    in.blinders = bl;
+    if (c->curve == ZKT_CURVE_BN254) return debug_commit_wires_t<Bn254Curve>(c, in, route, out_xy, out_is_infinity, out_route);
+    return debug_commit_wires_t<Bls381Curve>(c, in, route, out_xy, out_is_infinity, out_route);
 }
 
 int zkt_prove_set_next(zkt_ctx* c, const zkt_prove_inputs* next) {
