@@ -86,6 +86,8 @@ int zkt_ctx_synchronize(zkt_ctx* ctx);
  * The KZG seam (zkt_kzg_commit_batch / zkt_kzg_open): "kzg_commit_batch" (the whole batch of MSMs on the stream),
  * "kzg_open_upload" (the coefficients' copy to HBM), "kzg_open_combine" (power tables and the fused combination /
  * evaluation pass), "kzg_open_divide" (division by X - z) and "kzg_open_msm" (the witness commitment).
+ * "sigma": the key, sort, link and evaluation launches of zkt_circuit_sigma_dev / zkt_circuit_setup_wiring (not the
+ * domain table they read).
  * A scope that covers a batch counts its units in `calls` (the three commitments of a round grouped and accumulated as one
  * batch of launches: 3); "<name>#launches" returns the number of recorded scopes instead.
  * on = 0: off; 1: every scope; 2: only "msm_accumulate" and "host_wait" -- the level for timing the dominant kernel
@@ -351,10 +353,41 @@ int zkt_circuit_load(zkt_ctx* ctx, int log_n, const uint64_t* const* pk_polys, c
  * ExtendedProverKey (as in zkt_circuit_load) and the ten VerifierKey commitments (PC::commit, setup.rs:104-121).
  * out_commitments: 10 x (x, y) in arkworks Montgomery limbs (2 x 4 u64 on BN254, 2 x 6 on BLS12-381), (0, 0) and
  * out_is_infinity[k] = 1 for the identity (an all-zero selector).  The circuit is left loaded: zkt_prove can follow.
- * Needs zkt_srs_load with >= n powers.  The permutation bookkeeping that produces the sigma evaluations
- * (permutation/mod.rs compute_all_sigma_evals) stays with the caller. */
+ * Needs zkt_srs_load with >= n powers.  evals_on_device != 0: the ten entries are device pointers.  The sigma
+ * evaluations are the caller's here (permutation/mod.rs compute_all_sigma_evals); zkt_circuit_setup_wiring below makes
+ * them on the device from the composer's wiring. */
 int zkt_circuit_setup(zkt_ctx* ctx, int log_n, const uint64_t* const* evals, const size_t* eval_lens, int evals_on_device,
                       uint64_t* out_commitments, int* out_is_infinity);
+
+/* compute_all_sigma_evals (permutation/mod.rs:103-177) from the wiring: d_w_l / d_w_r / d_w_o = n_rows variable indices
+ * each (ZKT_VARIABLE_ZERO = Variable::Zero), device pointers; d_sigma[3] receive n = 2^log_n Montgomery elements each.
+ * Number the wires p = 3 gate + column (Left, Right, Output): a wire maps to the next p of the same variable, the last
+ * to the first (the reference's per-variable lists in insertion order, permutation/mod.rs:76-137); wires of rows >=
+ * n_rows map to themselves; the value of a target (col, i) is k_col w^i, k = (1, 7, 13) (permutation/constants.rs).
+ * On the device: a stable radix sort of the 3 n_rows positions by variable (8 bits a pass, only the passes n_vars
+ * needs; deterministic, no result depends on the order of atomics), a neighbour lookup, one evaluation pass.  Scratch
+ * (about 16 bytes a wire plus a table of n elements, ~80 MB at n = 2^20) is the call's own and is freed before it
+ * returns.  Needs no SRS and no loaded circuit and touches neither (nor the Lagrange tables, nor an announced next
+ * proof); works on a forked context; enqueues on the context's stream and synchronises once, at the end.
+ * ZKT_ERR_INVALID_DOMAIN_SIZE unless 0 <= log_n <= 25 (positions are 32-bit); ZKT_ERR_INVALID_ARGUMENT for n_rows > n, a
+ * null pointer (the wiring may be null when n_rows = 0: the identity permutation) and for an index that is neither
+ * < n_vars nor ZKT_VARIABLE_ZERO. */
+int zkt_circuit_sigma_dev(zkt_ctx* ctx, int log_n, const uint32_t* d_w_l, const uint32_t* d_w_r, const uint32_t* d_w_o,
+                          size_t n_rows, size_t n_vars, void* const* d_sigma);
+/* zkt_circuit_setup with sigma1..3 made on the device: evals / eval_lens as there, entries 5, 6, 7 must be NULL / 0.
+ * w_l / w_r / w_o: the composer's wiring as in zkt_prove_inputs, host pointers (uploaded here) or, with
+ * wiring_on_device != 0, device pointers; the other seven entries are host or device as evals_on_device says.  So
+ * setup takes the composer's own data and nothing derived: selectors, table mask, wiring.  Everything else is
+ * zkt_circuit_setup: the circuit left loaded, the ten commitments in ProverKey order, the refusal on a context with
+ * live forks, sharded contexts (every rank computes the whole sigma vectors; they are replicated like all n-domain
+ * work).  ZKT_ERR_INVALID_DOMAIN_SIZE unless 3 <= log_n <= 25; ZKT_ERR_INVALID_ARGUMENT for n_rows > n, a non-NULL
+ * entry 5 / 6 / 7, a NULL wiring pointer with n_rows > 0 and an index outside the variable map -- after any of these
+ * no circuit is loaded (the previous one is released, as by a failing zkt_circuit_setup).
+ * Cost: see docs/EXPERIMENTS.md "sigma from the wiring". */
+int zkt_circuit_setup_wiring(zkt_ctx* ctx, int log_n, const uint64_t* const* evals, const size_t* eval_lens,
+                             int evals_on_device, const uint32_t* w_l, const uint32_t* w_r, const uint32_t* w_o,
+                             size_t n_rows, size_t n_vars, int wiring_on_device,
+                             uint64_t* out_commitments, int* out_is_infinity);
 
 typedef struct {
     /* wire_evals() of the proving composer (prove.rs:49-55,116): n_rows <= n values each, zero padded */

@@ -88,6 +88,12 @@ extern "C" {
                                       mismatch_at: *mut usize) -> c_int;
     pub fn zkt_circuit_setup(ctx: *mut ZktCtx, log_n: c_int, evals: *const *const u64, eval_lens: *const usize,
                              evals_on_device: c_int, out_commitments: *mut u64, out_is_infinity: *mut c_int) -> c_int;
+    pub fn zkt_circuit_sigma_dev(ctx: *mut ZktCtx, log_n: c_int, d_w_l: *const u32, d_w_r: *const u32, d_w_o: *const u32,
+                                 n_rows: usize, n_vars: usize, d_sigma: *const *mut c_void) -> c_int;
+    pub fn zkt_circuit_setup_wiring(ctx: *mut ZktCtx, log_n: c_int, evals: *const *const u64, eval_lens: *const usize,
+                                    evals_on_device: c_int, w_l: *const u32, w_r: *const u32, w_o: *const u32, n_rows: usize,
+                                    n_vars: usize, wiring_on_device: c_int, out_commitments: *mut u64,
+                                    out_is_infinity: *mut c_int) -> c_int;
     pub fn zkt_prove_with(ctx: *mut ZktCtx, inputs: *const ZktProveInputs, transcript: *const ZktTranscriptVtable,
                           proof_out: *mut u8, proof_cap: usize, proof_len: *mut usize) -> c_int;
     pub fn zkt_prove_set_next(ctx: *mut ZktCtx, next: *const ZktProveInputs) -> c_int;

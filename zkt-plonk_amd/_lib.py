@@ -400,6 +400,10 @@ def _bind_prover(L):
     L.zkt_circuit_load.argtypes = [vp, ctypes.c_int, ctypes.POINTER(u64p_), ctypes.POINTER(ctypes.c_size_t)]
     L.zkt_circuit_setup.argtypes = [vp, ctypes.c_int, ctypes.POINTER(u64p_), ctypes.POINTER(ctypes.c_size_t), ctypes.c_int,
                                     u64p_, ctypes.POINTER(ctypes.c_int)]
+    L.zkt_circuit_sigma_dev.argtypes = [vp, ctypes.c_int, vp, vp, vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(vp)]
+    L.zkt_circuit_setup_wiring.argtypes = [vp, ctypes.c_int, ctypes.POINTER(u64p_), ctypes.POINTER(ctypes.c_size_t), ctypes.c_int,
+                                           vp, vp, vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, u64p_,
+                                           ctypes.POINTER(ctypes.c_int)]
     L.zkt_prove.argtypes = [vp, ctypes.POINTER(ProveInputs), vp, u8p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
     L.zkt_prove_set_next.argtypes = [vp, ctypes.POINTER(ProveInputs)]
 
@@ -982,6 +986,49 @@ class Context:
         out = np.zeros((10, 2 * self.fq_limbs), dtype=np.uint64)
         inf = (ctypes.c_int * 10)()
         self.check(self._L.zkt_circuit_setup(self._h, log_n, ptrs, lens, 0, u64p(out), inf))
+        self.circuit_log_n = log_n
+        return out, np.array([bool(x) for x in inf])
+
+    def circuit_sigma(self, log_n: int, d_w_l: int, d_w_r: int, d_w_o: int, n_rows: int, n_vars: int, d_sigma=None):
+        """zkt_circuit_sigma_dev: compute_all_sigma_evals (permutation/mod.rs:103-177) from the wiring resident in HBM
+        (three device pointers to n_rows uint32 indices, 0xFFFFFFFF = Variable::Zero).  d_sigma: three device pointers
+        of n * 32 bytes that receive sigma1..3; None: -> the three vectors as (n, 4) Montgomery uint64 host arrays."""
+        n = 1 << log_n if 0 <= log_n <= 25 else 0
+        own = d_sigma is None
+        if own:
+            d_sigma = [self.alloc(max(n, 1) * 32) for _ in range(3)]
+        try:
+            ptrs = (ctypes.c_void_p * 3)(*d_sigma)
+            self.check(self._L.zkt_circuit_sigma_dev(self._h, log_n, ctypes.c_void_p(d_w_l), ctypes.c_void_p(d_w_r),
+                                                     ctypes.c_void_p(d_w_o), n_rows, n_vars, ptrs))
+            return [self.download(p, (n, 4)) for p in d_sigma] if own else None
+        finally:
+            if own:
+                for p in d_sigma:
+                    self.free(p)
+
+    def circuit_setup_wiring(self, log_n: int, evals, w_l, w_r, w_o, n_vars: int, n_rows: int = None):
+        """zkt_circuit_setup_wiring: proof_system::setup from the composer's own data.  evals: the 10 vectors of
+        circuit_setup with entries 5, 6, 7 (sigma1..3) None; w_l / w_r / w_o: uint32 index arrays (host), or three
+        device pointers (ints) together with n_rows.  -> (commitments, is_infinity) as circuit_setup."""
+        assert len(evals) == 10
+        arrs = [np.zeros((0, 4), dtype=np.uint64) if p is None else np.ascontiguousarray(p, dtype=np.uint64).reshape(-1, 4)
+                for p in evals]
+        ptrs = (ctypes.POINTER(ctypes.c_uint64) * 10)(*[u64p(a) if a.size else ctypes.POINTER(ctypes.c_uint64)() for a in arrs])
+        lens = (ctypes.c_size_t * 10)(*[a.shape[0] for a in arrs])
+        on_device = isinstance(w_l, int)
+        if on_device:
+            assert n_rows is not None
+            w = [ctypes.c_void_p(p) for p in (w_l, w_r, w_o)]
+        else:
+            idx = [np.ascontiguousarray(x, dtype=np.uint32).reshape(-1) for x in (w_l, w_r, w_o)]
+            assert idx[0].shape == idx[1].shape == idx[2].shape
+            n_rows = idx[0].shape[0] if n_rows is None else n_rows
+            w = [x.ctypes.data_as(ctypes.c_void_p) if x.size else ctypes.c_void_p() for x in idx]
+        out = np.zeros((10, 2 * self.fq_limbs), dtype=np.uint64)
+        inf = (ctypes.c_int * 10)()
+        self.check(self._L.zkt_circuit_setup_wiring(self._h, log_n, ptrs, lens, 0, w[0], w[1], w[2], n_rows, n_vars,
+                                                    int(on_device), u64p(out), inf))
         self.circuit_log_n = log_n
         return out, np.array([bool(x) for x in inf])
 

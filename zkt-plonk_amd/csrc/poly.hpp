@@ -102,6 +102,10 @@ int open_pow_tables(zkt_ctx* c, const uint32_t z[8], const uint32_t z_inv[8], vo
 int open_divide(zkt_ctx* c, const void* t, size_t len, void* d_tmp, void* d_scan_tmp, void* out, const void* d_powers);
 // out[r] = sum_b partials[r * nblk + b], r < rows (per-workgroup partial sums of rows evaluations)
 int poly_sum_rows(zkt_ctx* c, const void* d_partials, int nblk, int rows, void* d_out);
+// sigma.hip: compute_all_sigma_evals (permutation/mod.rs:103-177) from the wiring (device pointers, n_rows indices each) into
+// d_sigma[3] of 2^log_n elements; scratch of its own, one synchronisation at the end (the index flag).  "sigma" scope.
+int sigma_build(zkt_ctx* c, int log_n, const uint32_t* d_w_l, const uint32_t* d_w_r, const uint32_t* d_w_o, size_t n_rows, size_t n_vars,
+                void* const* d_sigma);
 // table generation
 int gen_powers(zkt_ctx* c, void* out, size_t n, const uint32_t base[8], const uint32_t scale[8]);
 // Plookup sorted halves h1/h2 (lookup/multiset.rs:103-146)

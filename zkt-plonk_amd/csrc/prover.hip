@@ -1205,7 +1205,7 @@ int circuit_fork(zkt_ctx* child, const zkt_ctx* parent) {
 
 template <class C>
 static int circuit_load_t(zkt_ctx* c, int log_n, const uint64_t* const* polys, const size_t* lens, bool from_evals = false,
-                          bool from_evals_on_device = false) {
+                          unsigned evals_dev_mask = 0) {   // bit k: evaluation vector k is a device pointer
     using R = typename C::Fr;
     using F = Fe<R>;
     if (log_n < 3 || log_n + 2 > R::TWO_ADICITY || log_n + 2 > 27)
@@ -1232,12 +1232,13 @@ static int circuit_load_t(zkt_ctx* c, int log_n, const uint64_t* const* polys, c
         if (from_evals) {
             // setup.rs:72-90: poly_from_evals of the padded selector / sigma / table-mask evaluations
             const void* src = polys[k];
-            if (!from_evals_on_device) {
+            const bool on_device = (evals_dev_mask >> k) & 1u;
+            if (!on_device) {
                 ZKT_HIP(c, hipMemsetAsync(S.qev, 0, n * 32, c->stream));   // the quotient vector doubles as staging
                 if (lens[k]) ZKT_HIP(c, hipMemcpyAsync(S.qev, polys[k], lens[k] * 32, hipMemcpyHostToDevice, c->stream));
                 src = S.qev;
             }
-            if ((rc = ntt_run(c, log_n, 1, 0, src, from_evals_on_device ? lens[k] : n, S.pk[k]))) return rc;
+            if ((rc = ntt_run(c, log_n, 1, 0, src, on_device ? lens[k] : n, S.pk[k]))) return rc;
             S.pk_len[k] = n;
         } else {
             ZKT_HIP(c, hipMemsetAsync(S.pk[k], 0, n * 32, c->stream));
@@ -1302,10 +1303,10 @@ static int circuit_load_t(zkt_ctx* c, int log_n, const uint64_t* const* polys, c
 
 // setup.rs:42-166 on the device: polynomials from the evaluation vectors, ExtendedProverKey, the ten commitments
 template <class C>
-static int circuit_setup_t(zkt_ctx* c, int log_n, const uint64_t* const* evals, const size_t* lens, int on_device,
+static int circuit_setup_t(zkt_ctx* c, int log_n, const uint64_t* const* evals, const size_t* lens, unsigned evals_dev_mask,
                            uint64_t* out_commitments, int* out_is_inf) {
     using Q = typename C::Fq;
-    int rc = circuit_load_t<C>(c, log_n, evals, lens, true, on_device != 0);
+    int rc = circuit_load_t<C>(c, log_n, evals, lens, true, evals_dev_mask);
     if (rc) return rc;
     CircuitState& S = *c->circuit;
     // setup.rs:104-121: PC::commit of the ten labelled polynomials, ProverKey order; batches of the MSM's slot count
@@ -1729,9 +1730,64 @@ int zkt_circuit_setup(zkt_ctx* c, int log_n, const uint64_t* const* evals, const
     (void)hipSetDevice(c->device);
     if (log_n < 3 || log_n > 26) return set_err(c, ZKT_ERR_INVALID_DOMAIN_SIZE, "circuit bound out of range");
     if (int rc0 = check_sharded_key(c)) return rc0;
+    const unsigned mask = evals_on_device ? (1u << PK_COUNT) - 1u : 0u;
     if (c->curve == ZKT_CURVE_BN254)
-        return circuit_setup_t<Bn254Curve>(c, log_n, evals, eval_lens, evals_on_device, out_commitments, out_is_infinity);
-    return circuit_setup_t<Bls381Curve>(c, log_n, evals, eval_lens, evals_on_device, out_commitments, out_is_infinity);
+        return circuit_setup_t<Bn254Curve>(c, log_n, evals, eval_lens, mask, out_commitments, out_is_infinity);
+    return circuit_setup_t<Bls381Curve>(c, log_n, evals, eval_lens, mask, out_commitments, out_is_infinity);
+}
+
+int zkt_circuit_setup_wiring(zkt_ctx* c, int log_n, const uint64_t* const* evals, const size_t* eval_lens, int evals_on_device,
+                             const uint32_t* w_l, const uint32_t* w_r, const uint32_t* w_o, size_t n_rows, size_t n_vars,
+                             int wiring_on_device, uint64_t* out_commitments, int* out_is_infinity) {
+    if (!c || !evals || !eval_lens || !out_commitments) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
+    if (!c->msm) return set_err(c, ZKT_ERR_NOT_LOADED, "no SRS loaded (zkt_srs_load)");
+    (void)hipSetDevice(c->device);
+    const int max_log_n = (c->curve == ZKT_CURVE_BN254 ? Bn254Fr::TWO_ADICITY : Bls381Fr::TWO_ADICITY) - 2;
+    if (log_n < 3 || log_n > 25 || log_n > max_log_n)   // what zkt_circuit_load accepts (the 4n domain), 32-bit wire positions
+        return set_err(c, ZKT_ERR_INVALID_DOMAIN_SIZE, "circuit bound out of range");
+    if (int rc0 = check_sharded_key(c)) return rc0;
+    if (int rf = refuse_if_forked(c, "loading a circuit")) return rf;
+    // from here on as a failing zkt_circuit_setup: the previous circuit is gone
+    circuit_release(c);
+    const size_t n = (size_t)1 << log_n;
+    if (n_rows > n) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "more wiring rows than the domain size");
+    for (int k = PK_S1; k <= PK_S3; ++k)
+        if (evals[k] || eval_lens[k])
+            return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "zkt_circuit_setup_wiring makes sigma1..3 itself: entries 5, 6, 7 must be NULL / 0");
+    if (n_rows && (!w_l || !w_r || !w_o)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null wiring pointer");
+    // the call's own buffers: the three sigma vectors and, for host wiring, the uploaded indices
+    void* held[6] = {};
+    auto release = [&]() {
+        (void)hipStreamSynchronize(c->stream);
+        for (void* p : held) dev_free(c, p);
+    };
+    int rc = ZKT_OK;
+    for (int k = 0; k < 3 && !rc; ++k) rc = dev_alloc(c, &held[k], n * 32);
+    const uint32_t* w[3] = {w_l, w_r, w_o};
+    if (!wiring_on_device && n_rows) {
+        for (int k = 0; k < 3 && !rc; ++k) {
+            rc = dev_alloc(c, &held[3 + k], n_rows * 4);
+            if (!rc && hipMemcpyAsync(held[3 + k], w[k], n_rows * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+                rc = set_err(c, ZKT_ERR_HIP, "uploading the wiring failed");
+            w[k] = (const uint32_t*)held[3 + k];
+        }
+    }
+    if (!rc) rc = sigma_build(c, log_n, w[0], w[1], w[2], n_rows, n_vars, held);
+    if (!rc) {
+        const uint64_t* ev[PK_COUNT];
+        size_t lens[PK_COUNT];
+        for (int k = 0; k < PK_COUNT; ++k) { ev[k] = evals[k]; lens[k] = eval_lens[k]; }
+        unsigned mask = evals_on_device ? (1u << PK_COUNT) - 1u : 0u;
+        for (int k = 0; k < 3; ++k) {
+            ev[PK_S1 + k] = (const uint64_t*)held[k];
+            lens[PK_S1 + k] = n;
+            mask |= 1u << (PK_S1 + k);
+        }
+        rc = c->curve == ZKT_CURVE_BN254 ? circuit_setup_t<Bn254Curve>(c, log_n, ev, lens, mask, out_commitments, out_is_infinity)
+                                         : circuit_setup_t<Bls381Curve>(c, log_n, ev, lens, mask, out_commitments, out_is_infinity);
+    }
+    release();
+    return rc;
 }
 
 // Test hook: the fused quotient pass on its own (quotient_poly.rs:98-224) over the loaded circuit's key cosets and

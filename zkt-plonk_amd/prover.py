@@ -60,6 +60,16 @@ class GpuProver:
         pts, inf = ctx.circuit_setup(log_n, [evals[k] for k in PK_ORDER])
         return self, {k: (pts[i], bool(inf[i])) for i, k in enumerate(PK_ORDER)}
 
+    @classmethod
+    def setup_wiring(cls, ctx: Context, log_n: int, evals7: Dict[str, np.ndarray], w_l, w_r, w_o, n_vars: int, n_rows: int = None):
+        """``setup`` from the composer's own data: the seven selector / table-mask vectors (PK_ORDER names without
+        sigma1..3) and the wiring (uint32 index arrays, 0xFFFFFFFF = Variable::Zero; or three device pointers with
+        ``n_rows``).  The sigma evaluations (permutation/mod.rs:103-177) are made on the device.  -> what ``setup`` returns."""
+        self = cls(ctx, log_n, None)
+        pts, inf = ctx.circuit_setup_wiring(log_n, [None if k.startswith("sigma") else evals7[k] for k in PK_ORDER],
+                                            w_l, w_r, w_o, n_vars, n_rows)
+        return self, {k: (pts[i], bool(inf[i])) for i, k in enumerate(PK_ORDER)}
+
     def prove(self, a, b, c, table, public_inputs: Dict[int, np.ndarray], blinders, transcript: Transcript) -> bytes:
         pos = sorted(public_inputs.keys())
         vals = np.stack([np.asarray(public_inputs[p], dtype=np.uint64).reshape(4) for p in pos]) if pos else \
