@@ -88,6 +88,8 @@ int zkt_ctx_synchronize(zkt_ctx* ctx);
  * evaluation pass), "kzg_open_divide" (division by X - z) and "kzg_open_msm" (the witness commitment).
  * "sigma": the key, sort, link and evaluation launches of zkt_circuit_sigma_dev / zkt_circuit_setup_wiring (not the
  * domain table they read).
+ * "check_witness": every launch of zkt_circuit_check_witness (selector transforms, the sigma launches when the wiring
+ * is checked, the gate, residual and comparison kernels), not its uploads.
  * A scope that covers a batch counts its units in `calls` (the three commitments of a round grouped and accumulated as one
  * batch of launches: 3); "<name>#launches" returns the number of recorded scopes instead.
  * on = 0: off; 1: every scope; 2: only "msm_accumulate" and "host_wait" -- the level for timing the dominant kernel
@@ -437,6 +439,51 @@ int zkt_prove(zkt_ctx* ctx, const zkt_prove_inputs* in, zkt_transcript* transcri
 int zkt_prove_set_next(zkt_ctx* ctx, const zkt_prove_inputs* next);
 int zkt_prove_with(zkt_ctx* ctx, const zkt_prove_inputs* in, const zkt_transcript_vtable* transcript,
                    uint8_t* proof_out, size_t proof_cap, size_t* proof_len);
+
+/* check_gate of the reference's circuit debugger (plonk-core/src/constraint_system/helper.rs:13-75, the
+ * check_circuit_satisfied of its README and gate tests) on the device: which rows of a witness break the loaded circuit,
+ * by which rule, and how many.  zkt_prove only reports THAT a witness is bad (ZKT_ERR_QUOTIENT_TOO_SHORT after four
+ * rounds, ZKT_ERR_NOT_IN_TABLE), never where.  One deliberate difference: the reference's loop is zipped with
+ * setup.pp.get_pos() and so stops after as many rows as there are public inputs; this call checks every row.
+ * `in` is what zkt_prove takes, in either witness form (a_evals / b_evals / c_evals, or variables + w_l / w_r / w_o when
+ * a_evals is NULL; wires_on_device selects host or device pointers); blinders is ignored and may be NULL.  All
+ * n = 2^log_n rows of the loaded circuit are checked; rows >= n_rows carry zero wires, as the prover pads them.
+ *   arithmetic (bit 0): q_m a b + q_l a + q_r b + q_o c + q_c + pi != 0, pi = pi_vals[k] at row pi_pos[k], 0 elsewhere
+ *                       (a wrong public input shows up as a failure at its row);
+ *   lookup (bit 1):     q_lookup c is non-zero and not among table[0 .. table_len) (zero always passes: the prover pads
+ *                       the table with zeros; table_len = 0 is allowed);
+ *   wiring (bit 2):     only with ZKT_CHECK_WIRING, only for the variables form (ZKT_ERR_INVALID_ARGUMENT with a_evals
+ *                       set): the sigma evaluations made from w_l / w_r / w_o (the launches of zkt_circuit_sigma_dev)
+ *                       against the loaded key's, element by element over the 3n wires -- "is this the wiring the key
+ *                       was made from".  The bare evaluation form has no wiring to check: `checked` then lacks bit 2,
+ *                       and copy constraints between its rows are NOT verified.
+ * Returns ZKT_OK whenever the check ran: an unsatisfied witness is a result, not an error.  Errors:
+ * ZKT_ERR_NOT_LOADED without a circuit; ZKT_ERR_INVALID_ARGUMENT for NULL in / out, unknown flag bits, n_rows > n,
+ * table_len >= n, a repeated table value, a public-input position >= n, and an index that is neither < n_vars nor
+ * ZKT_VARIABLE_ZERO.  On any error *out is left untouched.
+ * Needs no SRS; works on a forked context and on one with a communicator (local and replicated, no collective).  Leaves
+ * the circuit's work buffers, the resident lookup keys, the Lagrange and wire tables and a proof announced with
+ * zkt_prove_set_next untouched (that proof's bytes do not change).  The selector evaluations are made per call from the
+ * key's coefficients (five n-point transforms) into the call's own scratch: 5 n x 32 B for them, plus the sorted table,
+ * a host witness's copy and, with ZKT_CHECK_WIRING, 3 n x 32 B and the sort's ~16 B a wire and n x 32 B; grown on demand,
+ * freed by zkt_ctx_destroy.  Enqueues on the context's stream and synchronises once, at the end. */
+enum {                              /* flags */
+    ZKT_CHECK_WIRING = 1            /* also compare the given wiring with the loaded key's permutation */
+};
+#define ZKT_CHECK_NONE ((uint64_t)-1)
+typedef struct {
+    int satisfied;                  /* 1 iff every count below is 0 */
+    int checked;                    /* bit 0 arithmetic, bit 1 lookup, bit 2 wiring: which rules ran */
+    uint64_t n_arithmetic;          /* rows whose gate equation is not 0 */
+    uint64_t first_arithmetic;      /* smallest such row, ZKT_CHECK_NONE when there is none */
+    uint64_t residual[4];           /* the gate equation's value at first_arithmetic, Montgomery limbs (0 when none) */
+    uint64_t n_lookup;              /* rows with q_lookup c != 0 and not in the table */
+    uint64_t first_lookup;
+    uint64_t n_wiring;              /* wires (column, row) whose sigma differs from the key's */
+    uint64_t first_wiring_row;      /* smallest wire in the order p = 3 row + column; ZKT_CHECK_NONE when none */
+    int first_wiring_column;        /* 0 Left, 1 Right, 2 Output; -1 when none */
+} zkt_witness_report;
+int zkt_circuit_check_witness(zkt_ctx* ctx, const zkt_prove_inputs* in, int flags, zkt_witness_report* out);
 
 /* ---- Witness synthesis for Poseidon-heavy circuits as batched field kernels ----------------------
  * (1) The permutation of plonk-hashing/src/hasher/poseidon/spec.rs (rounds :18-111, schedule :267-316, input layout

@@ -47,6 +47,23 @@ pub struct ZktProveInputs {
     pub w_o: *const u32,
 }
 
+/// zkt_witness_report: what zkt_circuit_check_witness found (check_gate, constraint_system/helper.rs:13-75, every row)
+#[repr(C)]
+pub struct ZktWitnessReport {
+    pub satisfied: c_int,
+    pub checked: c_int,
+    pub n_arithmetic: u64,
+    pub first_arithmetic: u64,
+    pub residual: [u64; 4],
+    pub n_lookup: u64,
+    pub first_lookup: u64,
+    pub n_wiring: u64,
+    pub first_wiring_row: u64,
+    pub first_wiring_column: c_int,
+}
+
+pub const ZKT_CHECK_WIRING: c_int = 1;
+pub const ZKT_CHECK_NONE: u64 = u64::MAX;
 pub const ZKT_VARIABLE_ZERO: u32 = 0xFFFF_FFFF;
 pub const ZKT_CURVE_BN254: c_int = 0;
 pub const ZKT_CURVE_BLS12_381: c_int = 1;
@@ -97,6 +114,8 @@ extern "C" {
     pub fn zkt_prove_with(ctx: *mut ZktCtx, inputs: *const ZktProveInputs, transcript: *const ZktTranscriptVtable,
                           proof_out: *mut u8, proof_cap: usize, proof_len: *mut usize) -> c_int;
     pub fn zkt_prove_set_next(ctx: *mut ZktCtx, next: *const ZktProveInputs) -> c_int;
+    pub fn zkt_circuit_check_witness(ctx: *mut ZktCtx, inputs: *const ZktProveInputs, flags: c_int,
+                                     out: *mut ZktWitnessReport) -> c_int;
     pub fn zkt_g1_msm_host(curve_id: c_int, points_xy_mont: *const u64, scalars: *const u64, n: usize, scalars_montgomery: c_int,
                            out_xy_mont: *mut u64, out_is_infinity: *mut c_int) -> c_int;
     pub fn zkt_msm_g1_bases(ctx: *mut ZktCtx, bases_xy_mont: *const u64, scalars: *const u64, n: usize,

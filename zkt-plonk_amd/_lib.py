@@ -370,6 +370,43 @@ class ProveInputs(ctypes.Structure):
                 ("w_o", ctypes.POINTER(ctypes.c_uint32))]
 
 
+class WitnessReport(ctypes.Structure):
+    """zkt_witness_report"""
+    _fields_ = [("satisfied", ctypes.c_int), ("checked", ctypes.c_int),
+                ("n_arithmetic", ctypes.c_uint64), ("first_arithmetic", ctypes.c_uint64), ("residual", ctypes.c_uint64 * 4),
+                ("n_lookup", ctypes.c_uint64), ("first_lookup", ctypes.c_uint64),
+                ("n_wiring", ctypes.c_uint64), ("first_wiring_row", ctypes.c_uint64), ("first_wiring_column", ctypes.c_int)]
+
+
+CHECK_WIRING = 1                  # ZKT_CHECK_WIRING
+CHECK_NONE = (1 << 64) - 1        # ZKT_CHECK_NONE
+
+
+class WitnessCheck:
+    """What zkt_circuit_check_witness found.  `first_*` are rows (None when the rule has no failure), `residual` the gate
+    equation's value at first_arithmetic as (4,) Montgomery uint64 limbs, `first_wiring` a (column, row) pair or None;
+    `raw` are the struct's bytes."""
+
+    def __init__(self, r: WitnessReport):
+        none = lambda v: None if v == CHECK_NONE else int(v)
+        self.satisfied = bool(r.satisfied)
+        self.checked = int(r.checked)
+        self.n_arithmetic, self.first_arithmetic = int(r.n_arithmetic), none(r.first_arithmetic)
+        self.residual = np.array(list(r.residual), dtype=np.uint64)
+        self.n_lookup, self.first_lookup = int(r.n_lookup), none(r.first_lookup)
+        self.n_wiring = int(r.n_wiring)
+        self.first_wiring = None if r.first_wiring_row == CHECK_NONE else (int(r.first_wiring_column), int(r.first_wiring_row))
+        self.raw = bytes(r)
+
+    def __bool__(self):
+        return self.satisfied
+
+    def __repr__(self):
+        return ("WitnessCheck(satisfied=%s, checked=%d, arithmetic=%d first %s, lookup=%d first %s, wiring=%d first %s)"
+                % (self.satisfied, self.checked, self.n_arithmetic, self.first_arithmetic, self.n_lookup, self.first_lookup,
+                   self.n_wiring, self.first_wiring))
+
+
 class PreparedInputs:
     """A zkt_prove_inputs struct together with the arrays it points into."""
 
@@ -406,6 +443,7 @@ def _bind_prover(L):
                                            ctypes.POINTER(ctypes.c_int)]
     L.zkt_prove.argtypes = [vp, ctypes.POINTER(ProveInputs), vp, u8p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
     L.zkt_prove_set_next.argtypes = [vp, ctypes.POINTER(ProveInputs)]
+    L.zkt_circuit_check_witness.argtypes = [vp, ctypes.POINTER(ProveInputs), ctypes.c_int, ctypes.POINTER(WitnessReport)]
 
 
 def g1_sum_host(curve, points) -> tuple:
@@ -1035,12 +1073,15 @@ class Context:
     def _prepare(self, wires, n_rows, table, pi_pos, pi_vals, blinders, on_device, variables=None, idx=None, keep=()):
         table = np.ascontiguousarray(table, dtype=np.uint64).reshape(-1, 4)
         pi_vals = np.ascontiguousarray(pi_vals, dtype=np.uint64).reshape(-1, 4)
-        blinders = np.ascontiguousarray(blinders, dtype=np.uint64).reshape(19, 4)
+        if blinders is None:          # zkt_circuit_check_witness ignores them; zkt_prove refuses a NULL pointer
+            blinders = np.zeros((0, 4), dtype=np.uint64)
+        else:
+            blinders = np.ascontiguousarray(blinders, dtype=np.uint64).reshape(19, 4)
         pos = (ctypes.c_size_t * max(1, len(pi_pos)))(*pi_pos)
         null = ctypes.POINTER(ctypes.c_uint64)()
         null32 = ctypes.POINTER(ctypes.c_uint32)()
         inp = ProveInputs(wires[0], wires[1], wires[2], n_rows, u64p(table) if table.size else null, table.shape[0],
-                          pos, u64p(pi_vals) if pi_vals.size else null, len(pi_pos), u64p(blinders), int(on_device),
+                          pos, u64p(pi_vals) if pi_vals.size else null, len(pi_pos), u64p(blinders) if blinders.size else null, int(on_device),
                           variables[0] if variables else null, variables[1] if variables else 0,
                           idx[0] if idx else null32, idx[1] if idx else null32, idx[2] if idx else null32)
         return PreparedInputs(inp, (table, pi_vals, blinders, pos) + tuple(keep))
@@ -1088,6 +1129,15 @@ class Context:
         n = ctypes.c_size_t(0)
         self.check(self._L.zkt_prove(self._h, ctypes.byref(prep.struct), transcript.handle, out, 2048, ctypes.byref(n)))
         return bytes(out[:n.value])
+
+    def check_witness(self, prep: "PreparedInputs", flags: int = 0) -> "WitnessCheck":
+        """zkt_circuit_check_witness: check_gate (constraint_system/helper.rs:13-75) over every row of the loaded circuit
+        on prepared inputs (any of prepare_host / prepare_dev / prepare_vars / prepare_vars_dev; the blinders are ignored).
+        flags = CHECK_WIRING also compares the wiring of a variables-form witness with the key's permutation.  An
+        unsatisfied witness is a result, not an error."""
+        rep = WitnessReport()
+        self.check(self._L.zkt_circuit_check_witness(self._h, ctypes.byref(prep.struct), int(flags), ctypes.byref(rep)))
+        return WitnessCheck(rep)
 
     def prove_dev(self, d_a: int, d_b: int, d_c: int, n_rows: int, table, pi_pos, pi_vals, blinders, transcript) -> bytes:
         """Same as prove() with the three wire vectors already resident in HBM (device pointers)."""

@@ -44,6 +44,8 @@ struct zkt_ctx {
     size_t io_a_bytes = 0;
     void* io_b = nullptr;
     size_t io_b_bytes = 0;
+    void* check_scratch = nullptr;   // zkt_circuit_check_witness (check.hip): the call's own, never shared with a fork
+    size_t check_scratch_bytes = 0;
 
     // optional per-kernel HIP-event timing (bench.py's live roofline measurement)
     int prof_on = 0;   // 0 off, 1 every scope, 2 only the dominant kernel's scope ("msm_accumulate")

@@ -106,6 +106,22 @@ int poly_sum_rows(zkt_ctx* c, const void* d_partials, int nblk, int rows, void* 
 // d_sigma[3] of 2^log_n elements; scratch of its own, one synchronisation at the end (the index flag).  "sigma" scope.
 int sigma_build(zkt_ctx* c, int log_n, const uint32_t* d_w_l, const uint32_t* d_w_r, const uint32_t* d_w_o, size_t n_rows, size_t n_vars,
                 void* const* d_sigma);
+// The launches of sigma_build alone, for a caller that brings the memory and waits itself (check.hip): d_scratch holds
+// sigma_scratch_bytes(log_n, n_rows) bytes (256-byte aligned); *d_flag, cleared by the caller, is set when an index is
+// outside the variable map.  Enqueues on the context's stream, no synchronisation.  Arguments are not checked here.
+size_t sigma_scratch_bytes(int log_n, size_t n_rows);
+int sigma_enqueue(zkt_ctx* c, int log_n, const uint32_t* d_w_l, const uint32_t* d_w_r, const uint32_t* d_w_o, size_t n_rows, size_t n_vars,
+                  void* const* d_sigma, void* d_scratch, uint32_t* d_flag);
+// check.hip: zkt_circuit_check_witness on the loaded circuit's keys (all device pointers of 2^log_n elements; pk = the
+// coefficients of q_m q_l q_r q_o q_c, zero-padded to 2^log_n).  `in` and `flags` are validated by the caller except for what
+// needs the data (table duplicates, indices).  *out is written only on ZKT_OK.
+struct WitnessCheckKeys {
+    int log_n;
+    const void* pk[5];
+    const void* q_lookup_ev;
+    const void* sigma_ev[3];
+};
+int witness_check(zkt_ctx* c, const WitnessCheckKeys& keys, const zkt_prove_inputs& in, int flags, zkt_witness_report* out);
 // table generation
 int gen_powers(zkt_ctx* c, void* out, size_t n, const uint32_t base[8], const uint32_t scale[8]);
 // Plookup sorted halves h1/h2 (lookup/multiset.rs:103-146)

@@ -1790,6 +1790,41 @@ int zkt_circuit_setup_wiring(zkt_ctx* c, int log_n, const uint64_t* const* evals
     return rc;
 }
 
+// helper.rs:13-75 check_gate over every row (check.hip).  Reads the loaded keys, writes nothing of the circuit state: the
+// work buffers, the resident lookup keys and an announced proof's early rounds stay as they are.
+int zkt_circuit_check_witness(zkt_ctx* c, const zkt_prove_inputs* in, int flags, zkt_witness_report* out) {
+    if (!c) return ZKT_ERR_INVALID_ARGUMENT;
+    if (!in || !out) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
+    if (!c->circuit) return set_err(c, ZKT_ERR_NOT_LOADED, "no circuit loaded (zkt_circuit_load)");
+    if (flags & ~ZKT_CHECK_WIRING) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "unknown flag bits");
+    const CircuitState& S = *c->circuit;
+    const size_t n = S.n;
+    if (in->n_rows > n) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "more rows than the circuit bound");
+    if (in->table_len >= n) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "max table size is equal or larger than n");
+    if (in->table_len && !in->table) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null lookup table");
+    if (in->n_pi && (!in->pi_pos || !in->pi_vals)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null public inputs");
+    for (size_t i = 0; i < in->n_pi; ++i)
+        if (in->pi_pos[i] >= n) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "public input position out of range");
+    if (in->a_evals) {
+        if (flags & ZKT_CHECK_WIRING)
+            return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "ZKT_CHECK_WIRING needs the witness as variables + w_l / w_r / w_o: evaluation vectors carry no wiring");
+        if (in->n_rows && (!in->b_evals || !in->c_evals)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null wire vector");
+    } else {
+        if (in->n_rows && (!in->w_l || !in->w_r || !in->w_o)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null wire index vector");
+        if (in->n_vars && !in->variables) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null variable map");
+        if (in->n_vars > 0xFFFFFFFEull) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "too many variables");
+        if ((flags & ZKT_CHECK_WIRING) && S.log_n > 25)
+            return set_err(c, ZKT_ERR_INVALID_DOMAIN_SIZE, "InvalidEvalDomainSize: the wiring's positions are 32-bit (log_n <= 25)");
+    }
+    (void)hipSetDevice(c->device);
+    WitnessCheckKeys keys{};
+    keys.log_n = S.log_n;
+    for (int k = 0; k < 5; ++k) keys.pk[k] = S.pk[PK_QM + k];   // PK_QM .. PK_QC
+    keys.q_lookup_ev = S.q_lookup_ev;
+    for (int k = 0; k < 3; ++k) keys.sigma_ev[k] = S.sigma_ev[k];
+    return witness_check(c, keys, *in, flags, out);
+}
+
 // Test hook: the fused quotient pass on its own (quotient_poly.rs:98-224) over the loaded circuit's key cosets and
 // caller-supplied witness cosets, so that the kernel is compared point by point on inputs that satisfy nothing.
 extern "C++" template <class C>

@@ -20,7 +20,7 @@
 // wave ballots and a per-wave count table walked in wave order, never by the arrival order of an atomic.
 #include "poly.hpp"
 
-#include <vector>
+#include <algorithm>
 
 namespace zkt {
 
@@ -213,56 +213,60 @@ __global__ __launch_bounds__(SG_THREADS) void k_sigma_eval(const uint32_t* next,
 }
 
 namespace {
-// the call's own device memory: released (after the stream has drained) when the call returns
-struct SigmaScratch {
-    zkt_ctx* c;
-    std::vector<void*> held;
-    explicit SigmaScratch(zkt_ctx* ctx) : c(ctx) {}
-    template <class T> int get(T** p, size_t bytes) {
-        void* q = nullptr;
-        const int rc = dev_alloc(c, &q, bytes);
-        if (!rc) held.push_back(q);
-        *p = (T*)q;
-        return rc;
-    }
-    ~SigmaScratch() {
-        (void)hipStreamSynchronize(c->stream);
-        for (void* q : held) dev_free(c, q);
+// how the launches below carve the caller's block: every part starts on a 256-byte boundary
+struct SigmaLayout {
+    uint32_t count, nb, nchunks;
+    size_t hist_len;
+    size_t roots, keys[2], vals[2], hist, sums, total;
+    SigmaLayout(int log_n, size_t n_rows) {
+        const size_t n = (size_t)1 << log_n;
+        count = (uint32_t)(3 * n_rows);                                                 // log_n <= 25: below 2^32
+        nb = (count + SG_TILE - 1) / SG_TILE;
+        hist_len = ((size_t)256 * nb + SG_SCAN_CHUNK - 1) / SG_SCAN_CHUNK * SG_SCAN_CHUNK;
+        nchunks = (uint32_t)(hist_len / SG_SCAN_CHUNK);
+        size_t at = 0;
+        auto take = [&](size_t bytes) {
+            const size_t here = at;
+            at += (bytes + 255) / 256 * 256;
+            return here;
+        };
+        roots = take(n * 32);
+        for (int k = 0; k < 2; ++k) {
+            keys[k] = take((size_t)count * 4);
+            vals[k] = take((size_t)count * 4);
+        }
+        hist = take(hist_len * 4);
+        sums = take((size_t)nchunks * 4);
+        total = at + 256;
     }
 };
 }  // namespace
 
+size_t sigma_scratch_bytes(int log_n, size_t n_rows) { return SigmaLayout(log_n, n_rows).total; }
+
 template <class P>
-static int sigma_build_t(zkt_ctx* c, int log_n, const uint32_t* d_w_l, const uint32_t* d_w_r, const uint32_t* d_w_o, size_t n_rows,
-                         size_t n_vars, void* const* d_sigma, bool* bad_index) {
+static int sigma_enqueue_t(zkt_ctx* c, int log_n, const uint32_t* d_w_l, const uint32_t* d_w_r, const uint32_t* d_w_o, size_t n_rows,
+                           size_t n_vars, void* const* d_sigma, void* d_scratch, uint32_t* flag) {
     const size_t n = (size_t)1 << log_n;
-    const uint32_t count = (uint32_t)(3 * n_rows);                                  // log_n <= 25: below 2^32
+    const SigmaLayout L(log_n, n_rows);
+    const uint32_t count = L.count, nb = L.nb, nchunks = L.nchunks;
     const uint32_t vars = (uint32_t)std::min<size_t>(n_vars, 0xFFFFFFFFu);         // keys v + 1 stay 32-bit
     int key_bits = 0;
     while (key_bits < 32 && ((uint64_t)vars >> key_bits)) ++key_bits;               // keys are 0 .. vars
     const int npass = (key_bits + 7) / 8;
-    const uint32_t nb = (count + SG_TILE - 1) / SG_TILE;
-    const size_t hist_len = ((size_t)256 * nb + SG_SCAN_CHUNK - 1) / SG_SCAN_CHUNK * SG_SCAN_CHUNK;
-    const uint32_t nchunks = (uint32_t)(hist_len / SG_SCAN_CHUNK);
 
-    SigmaScratch scratch(c);
-    uint32_t *keys[2] = {}, *vals[2] = {}, *hist = nullptr, *sums = nullptr, *flag = nullptr;
-    Fe<P>* roots = nullptr;
+    char* const base = (char*)d_scratch;
+    Fe<P>* const roots = (Fe<P>*)(base + L.roots);
+    uint32_t* const keys[2] = {(uint32_t*)(base + L.keys[0]), (uint32_t*)(base + L.keys[1])};
+    uint32_t* const vals[2] = {(uint32_t*)(base + L.vals[0]), (uint32_t*)(base + L.vals[1])};
+    uint32_t* const hist = (uint32_t*)(base + L.hist);
+    uint32_t* const sums = (uint32_t*)(base + L.sums);
     int rc;
-    if ((rc = scratch.get(&roots, n * sizeof(Fe<P>)))) return rc;
-    if ((rc = scratch.get(&flag, 4))) return rc;
     if (count) {
-        for (int k = 0; k < 2; ++k) {
-            if ((rc = scratch.get(&keys[k], (size_t)count * 4))) return rc;
-            if ((rc = scratch.get(&vals[k], (size_t)count * 4))) return rc;
-        }
-        if ((rc = scratch.get(&hist, hist_len * 4))) return rc;
-        if ((rc = scratch.get(&sums, (size_t)nchunks * 4))) return rc;
         // the scan works on whole chunks: the tail behind the 256 nb real entries only has to be defined (what a scan
         // leaves there comes after every real entry, so it reaches none of them in the next pass)
-        ZKT_HIP(c, hipMemsetAsync(hist, 0, hist_len * 4, c->stream));
+        ZKT_HIP(c, hipMemsetAsync(hist, 0, L.hist_len * 4, c->stream));
     }
-    ZKT_HIP(c, hipMemsetAsync(flag, 0, 4, c->stream));
     const Fe<P> one = fe_one<P>(), w = root_of_unity<P>(log_n);
     if ((rc = gen_powers(c, roots, n, w.v, one.v))) return rc;                      // domain.elements()
     {
@@ -300,6 +304,34 @@ static int sigma_build_t(zkt_ctx* c, int log_n, const uint32_t* d_w_l, const uin
                            fe_from_u32<P>(13), (Fe<P>*)d_sigma[0], (Fe<P>*)d_sigma[1], (Fe<P>*)d_sigma[2]);   // permutation/constants.rs K1, K2
         ZKT_HIP(c, hipGetLastError());
     }
+    return ZKT_OK;
+}
+
+int sigma_enqueue(zkt_ctx* c, int log_n, const uint32_t* d_w_l, const uint32_t* d_w_r, const uint32_t* d_w_o, size_t n_rows, size_t n_vars,
+                  void* const* d_sigma, void* d_scratch, uint32_t* d_flag) {
+    return c->curve == ZKT_CURVE_BN254 ? sigma_enqueue_t<Bn254Fr>(c, log_n, d_w_l, d_w_r, d_w_o, n_rows, n_vars, d_sigma, d_scratch, d_flag)
+                                       : sigma_enqueue_t<Bls381Fr>(c, log_n, d_w_l, d_w_r, d_w_o, n_rows, n_vars, d_sigma, d_scratch, d_flag);
+}
+
+// zkt_circuit_sigma_dev / zkt_circuit_setup_wiring: scratch of the call's own, released (after the stream has drained)
+// when the call returns
+static int sigma_build_run(zkt_ctx* c, int log_n, const uint32_t* d_w_l, const uint32_t* d_w_r, const uint32_t* d_w_o, size_t n_rows,
+                           size_t n_vars, void* const* d_sigma, bool* bad_index) {
+    void* block = nullptr;
+    int rc = dev_alloc(c, &block, sigma_scratch_bytes(log_n, n_rows));
+    if (rc) return rc;
+    struct Release {
+        zkt_ctx* c;
+        void* p;
+        ~Release() {
+            (void)hipStreamSynchronize(c->stream);
+            dev_free(c, p);
+        }
+    } release{c, block};
+    // the flag lives in the block's spare last 256 bytes
+    uint32_t* flag = (uint32_t*)((char*)block + sigma_scratch_bytes(log_n, n_rows) - 256);
+    ZKT_HIP(c, hipMemsetAsync(flag, 0, 4, c->stream));
+    if ((rc = sigma_enqueue(c, log_n, d_w_l, d_w_r, d_w_o, n_rows, n_vars, d_sigma, block, flag))) return rc;
     uint32_t h_flag = 0;
     ZKT_HIP(c, hipMemcpyAsync(&h_flag, flag, 4, hipMemcpyDeviceToHost, c->stream));
     ZKT_HIP(c, hipStreamSynchronize(c->stream));
@@ -314,8 +346,7 @@ int sigma_build(zkt_ctx* c, int log_n, const uint32_t* d_w_l, const uint32_t* d_
     if (!d_sigma || !d_sigma[0] || !d_sigma[1] || !d_sigma[2] || (n_rows && (!d_w_l || !d_w_r || !d_w_o)))
         return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
     bool bad = false;
-    const int rc = c->curve == ZKT_CURVE_BN254 ? sigma_build_t<Bn254Fr>(c, log_n, d_w_l, d_w_r, d_w_o, n_rows, n_vars, d_sigma, &bad)
-                                               : sigma_build_t<Bls381Fr>(c, log_n, d_w_l, d_w_r, d_w_o, n_rows, n_vars, d_sigma, &bad);
+    const int rc = sigma_build_run(c, log_n, d_w_l, d_w_r, d_w_o, n_rows, n_vars, d_sigma, &bad);
     if (rc) return rc;
     if (bad) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "wiring index outside the variable map: every entry must be < n_vars or ZKT_VARIABLE_ZERO");
     return ZKT_OK;

@@ -10,7 +10,7 @@ from typing import Dict, Optional, Sequence
 
 import numpy as np
 
-from ._lib import Context, Transcript
+from ._lib import Context, Transcript, CHECK_WIRING  # noqa: F401
 
 PK_ORDER = ("q_m", "q_l", "q_r", "q_o", "q_c", "sigma1", "sigma2", "sigma3", "q_lookup", "q_table")
 NUM_BLINDERS = 19  # a(2) b(2) c(2) h1(3) h2(2) z1(3) z2(3) b0 b1 -- prove.rs:125-127,170-171,225,244,296
@@ -75,3 +75,9 @@ class GpuProver:
         vals = np.stack([np.asarray(public_inputs[p], dtype=np.uint64).reshape(4) for p in pos]) if pos else \
             np.zeros((0, 4), dtype=np.uint64)
         return self.ctx.prove(a, b, c, table, pos, vals, blinders, transcript)
+
+    def check_witness(self, prep, flags: int = 0):
+        """``check_circuit_satisfied`` of the reference (constraint_system/helper.rs:13-75) on the device, over every row:
+        ``prep`` is what ``Context.prepare_*`` returns (the inputs ``prove_prepared`` takes), ``flags`` 0 or
+        ``CHECK_WIRING``.  -> ``WitnessCheck``: counts and first rows per rule; falsy when a rule is broken."""
+        return self.ctx.check_witness(prep, flags)
