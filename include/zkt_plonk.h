@@ -604,6 +604,71 @@ int zkt_verify(int curve_id, const zkt_verify_inputs* in, zkt_transcript* transc
 int zkt_verify_batch(int curve_id, const zkt_verify_inputs* ins, zkt_transcript* const* transcripts, size_t count,
                      const uint64_t* h_g2_mont, const uint64_t* beta_h_g2_mont, int* accepted);
 
+/* Checked GroupAffine::deserialize (ark-serialize 0.3, compressed form) of n G1 points on the device, one thread per point
+ * on the context's stream (csrc/g1decomp.hip).  compressed: n x nb bytes, nb = ceil((MODULUS_BITS + 2) / 8) = 32 on
+ * BN254, 48 on BLS12-381: x little-endian, the top two bits of the last byte are SWFlags (bit 7: y is the larger root,
+ * bit 6: infinity).  out_xy_mont: n x (x, y) Montgomery limbs in arkworks' layout, (0,0) for the identity AND for every
+ * refused point; out_status: one byte per point,
+ *   ZKT_G1_VALID 0            a point of G1
+ *   ZKT_G1_IDENTITY 1         the infinity flag; the x bits must still be below the modulus and are then ignored
+ *   ZKT_G1_NOT_CANONICAL 2    x >= q after the flag bits are stripped (under the infinity flag too)
+ *   ZKT_G1_BOTH_FLAGS 3       both flag bits set (decided before x is looked at)
+ *   ZKT_G1_NOT_ON_CURVE 4     x^3 + b is not a square
+ *   ZKT_G1_NOT_IN_SUBGROUP 5  on the curve, outside the prime-order subgroup (BLS12-381 only; BN254 has cofactor one)
+ * -- the rules of the host verifier's deserialisation, which agrees with this one on every input.  The bytes may come
+ * from anyone: a refusal is a status, never an error code or a fault.  n = 0 -> ZKT_OK, nothing touched; n >
+ * ZKT_G1_DECOMPRESS_MAX -> ZKT_ERR_INVALID_ARGUMENT; a failed allocation -> ZKT_ERR_HIP.  Needs no SRS and no circuit,
+ * works on any context (forked, with a communicator: local, no collective); its scratch memory is shared with
+ * zkt_verify_batch_dev only.  The host form synchronises the stream.
+ * _dev: all three buffers in HBM (input and points 16-byte aligned, else ZKT_ERR_INVALID_ARGUMENT); only enqueues. */
+#define ZKT_G1_DECOMPRESS_MAX ((size_t)1 << 22)
+enum {
+    ZKT_G1_VALID = 0,
+    ZKT_G1_IDENTITY = 1,
+    ZKT_G1_NOT_CANONICAL = 2,
+    ZKT_G1_BOTH_FLAGS = 3,
+    ZKT_G1_NOT_ON_CURVE = 4,
+    ZKT_G1_NOT_IN_SUBGROUP = 5
+};
+int zkt_g1_decompress(zkt_ctx* ctx, const uint8_t* compressed, size_t n, uint64_t* out_xy_mont, uint8_t* out_status);
+int zkt_g1_decompress_dev(zkt_ctx* ctx, const void* d_compressed, size_t n, void* d_out_xy_mont, void* d_out_status);
+
+/* zkt_verify_batch with the two costs that grow with `count` moved to the device (csrc/verify.hip): the 13 * count
+ * compressed commitments are decompressed and checked in ONE zkt_g1_decompress launch, and the 2 * count folded openings
+ * are multiplied out as two device MSMs (the machinery of zkt_msm_g1_bases) instead of ~35 host scalar multiplications per
+ * proof.  For a verifier of many proofs under one SRS (a relayer, an aggregator); for one proof or a handful use
+ * zkt_verify / zkt_verify_batch -- where the device route overtakes the host one is UNMEASURED (docs/EXPERIMENTS.md
+ * "batch verification on the device"), and there is no automatic fallback: the caller chooses the entry point.
+ * Arguments as zkt_verify_batch (every transcript seeded like its prover's, consumed exactly as zkt_verify_prepare
+ * consumes it), with a context in place of the curve id (the context's curve is used).  Per proof the host keeps the byte-level checks (length, the two Option::None bytes,
+ * canonical evaluations), the transcript, r0 and the scalars of the two openings; it never forms the pairs (L_j, W_j).
+ * With rho_0 = 1, rho_j = the low 128 bits of Keccak-256(seed || j) for opening j < 2 * count, and seed = Keccak-256 over
+ * the curve id, count, and per proof its bytes, n, the ten verifier-key commitments and flags, pi_roots, the public
+ * inputs and g, then h and beta h, the call computes
+ *     A = sum_j rho_j L_j  (terms on one point added up: inside a proof, and across proofs for verifier-key points and g
+ *                           that are EQUAL BY CONTENT; identities dropped; at most 24 bases per proof),
+ *     B = sum_j rho_j W_j,
+ * and the batch is accepted iff e(A, h) e(-B, beta h) == 1.  zkt_verify_batch hashes the pairs (L_j, W_j) themselves, so
+ * the two entry points draw DIFFERENT coefficients; the inputs hashed here determine every pair, so this binds at least
+ * as much, and the two have the same accept set up to 2^-128.
+ * zkt_verify_batch_prepare_dev stops before the pairing: out_ab = A, B as (x, y) Montgomery limbs, out_ab_is_infinity 2
+ * flags (may be NULL), out_rho (may be NULL) the 2 * count coefficients as 4 canonical u64 words each -- for a caller who
+ * keeps arkworks' product_of_pairings.  zkt_verify_batch_dev runs the host pairing of zkt_pairing_product_is_one and
+ * sets *accepted; a rejected batch does not say which proof failed.
+ * Errors: count = 0 or count > ZKT_VERIFY_BATCH_DEV_MAX (24 * count <= ZKT_MSM_BASES_MAX) -> ZKT_ERR_INVALID_ARGUMENT;
+ * malformed bytes, or a commitment whose status is neither ZKT_G1_VALID nor ZKT_G1_IDENTITY -> ZKT_ERR_INVALID_ARGUMENT,
+ * zkt_last_error names the proof index and the commitment; otherwise as zkt_verify_prepare.
+ * Needs no SRS and no circuit; works on a forked context and on one with a communicator (local, no collective).  Its
+ * scratch memory is its own (allocated on first use, grown as needed, freed by zkt_ctx_destroy); the key, the circuit,
+ * the Lagrange and wire tables stay untouched, and a proof announced with zkt_prove_set_next yields the same bytes.
+ * Synchronises the stream.  Profile scopes: "verify_decompress", "verify_msm". */
+#define ZKT_VERIFY_BATCH_DEV_MAX (ZKT_MSM_BASES_MAX / 24)
+int zkt_verify_batch_prepare_dev(zkt_ctx* ctx, const zkt_verify_inputs* ins, zkt_transcript* const* transcripts, size_t count,
+                                 const uint64_t* h_g2_mont, const uint64_t* beta_h_g2_mont, uint64_t* out_ab,
+                                 int* out_ab_is_infinity, uint64_t* out_rho);
+int zkt_verify_batch_dev(zkt_ctx* ctx, const zkt_verify_inputs* ins, zkt_transcript* const* transcripts, size_t count,
+                         const uint64_t* h_g2_mont, const uint64_t* beta_h_g2_mont, int* accepted);
+
 /* HomomorphicCommitment::multi_scalar_mul (commitment.rs:32-45) for ARBITRARY points: the verifier's 13-point
  * linearisation commitment and similar short combinations.  Host arithmetic (double-and-add on 64-bit limbs): at this
  * size a device launch would cost more than the sum.  scalars: 4 limbs each, Montgomery or canonical. */

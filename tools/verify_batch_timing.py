@@ -1,0 +1,85 @@
+"""Times batch verification on the host (zkt_verify_batch) against the device route (zkt_verify_batch_dev) in one run, on
+batches of 1, 16, 256 and 4096 proofs made by repeating three oracle proofs (circuits of 150 / 90 / 150 gates, one SRS).
+Needs an MI355X; run it under a time limit:
+
+    timeout -k 10 900 python tools/verify_batch_timing.py [--reps 3] [--counts 1,16,256,4096] [--curves bn254,bls12_381]
+
+Only the C calls are timed (the argument arrays and the seeded transcripts are made before the clock starts); host and
+device alternate within every repetition and the figure is the median wall time of whole calls.  Per-stage device times
+come from the profile scopes "verify_decompress" and "verify_msm" of one more, profiled call; "host part" is that call's
+wall time minus the two.  The last line per curve names the smallest measured count at which the device route is faster."""
+import argparse
+import ctypes
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np
+import zkt_plonk_amd as z
+from zkt_plonk_amd import _lib
+from oracle import fields as F
+from test_gpu_verify_batch import _made, _items, _cycle
+
+CURVES = {"bn254": F.BN254, "bls12_381": F.BLS12_381}
+
+
+def _call(fn, handle, cv, entries, h, beta_h):
+    """one timed C call on fresh transcripts -> (ms, accepted)"""
+    cid = _lib.curve_id(cv.name)
+    ins, trs, k, hh, bh, keep = _lib._verify_batch_args(cid, _items(cv, entries), h, beta_h)
+    ok = ctypes.c_int(0)
+    u = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+    t0 = time.perf_counter()
+    rc = fn(handle if handle is not None else cid, ins, trs, k, u(hh), u(bh), ctypes.byref(ok))
+    ms = (time.perf_counter() - t0) * 1e3
+    assert rc == 0, rc
+    return ms, bool(ok.value)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--counts", default="1,16,256,4096")
+    ap.add_argument("--curves", default="bn254,bls12_381")
+    args = ap.parse_args()
+    counts = [int(x) for x in args.counts.split(",")]
+    L = z.lib()
+    for name in args.curves.split(","):
+        cv = CURVES[name]
+        made, srs, h, beta_h, wrong = _made(cv)
+        ctx = z.Context(cv.name, 0)
+        try:
+            assert _lib.verify_batch(cv.name, _items(cv, made), h, beta_h)      # binds the host entry's argument types
+            _call(L.zkt_verify_batch_dev, ctx.handle, cv, made, h, beta_h)      # first use: allocations, code load
+            print("%s: count | host ms | dev ms | host/dev | dev stages: decompress ms, msm ms, host part ms | per proof host, dev ms" % name)
+            crossover = None
+            for count in counts:
+                entries = _cycle(made, count)
+                reps = args.reps if count <= 256 else max(1, args.reps // 3)
+                th, td = [], []
+                for _ in range(reps):
+                    ms, ok = _call(L.zkt_verify_batch, None, cv, entries, h, beta_h)
+                    assert ok
+                    th.append(ms)
+                    ms, ok = _call(L.zkt_verify_batch_dev, ctx.handle, cv, entries, h, beta_h)
+                    assert ok
+                    td.append(ms)
+                ctx.profile_enable(True)
+                wall, ok = _call(L.zkt_verify_batch_dev, ctx.handle, cv, entries, h, beta_h)
+                dec, msm = ctx.profile_get("verify_decompress")[1], ctx.profile_get("verify_msm")[1]
+                ctx.profile_enable(False)
+                host, dev = float(np.median(th)), float(np.median(td))
+                if crossover is None and dev < host:
+                    crossover = count
+                print("%s: %5d | %9.2f | %9.2f | %5.2f | %8.2f %8.2f %8.2f | %.3f %.3f"
+                      % (name, count, host, dev, host / dev, dec, msm, wall - dec - msm, host / count, dev / count), flush=True)
+            print("%s: the device route is faster from count = %s on (of the counts measured)" % (name, crossover), flush=True)
+        finally:
+            ctx.close()
+
+
+if __name__ == "__main__":
+    main()

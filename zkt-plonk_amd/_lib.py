@@ -14,6 +14,8 @@ _LIB = os.environ.get("ZKT_LIB_PATH") or os.path.join(_HERE, "libzkt_plonk_hip.s
 _HEADER = os.path.join(_HERE, "..", "include", "zkt_plonk.h")
 
 MSM_BASES_MAX = 1 << 22   # ZKT_MSM_BASES_MAX: most points zkt_msm_g1_bases takes
+G1_DECOMPRESS_MAX = 1 << 22              # ZKT_G1_DECOMPRESS_MAX: most points one zkt_g1_decompress takes
+VERIFY_BATCH_DEV_MAX = MSM_BASES_MAX // 24   # ZKT_VERIFY_BATCH_DEV_MAX: most proofs one zkt_verify_batch_dev takes
 KZG_BATCH_MAX = 32        # ZKT_KZG_BATCH_MAX: most polynomials one zkt_kzg_commit_batch / zkt_kzg_open takes
 CURVE_BN254 = 0
 CURVE_BLS12_381 = 1
@@ -127,6 +129,12 @@ def _bind_optional(L):
         L.zkt_msm_g1_bases.argtypes = [vp, u64p, u64p, ctypes.c_size_t, ctypes.c_int, u64p, ip]
         L.zkt_msm_g1_bases_dev.argtypes = [vp, vp, vp, ctypes.c_size_t, ctypes.c_int, u64p, ip]
         L.zkt_msm_bases_info.argtypes = [vp, ctypes.c_size_t, ctypes.c_int, ip, ip]
+    if hasattr(L, "zkt_g1_decompress"):
+        L.zkt_g1_decompress.argtypes = [vp, vp, ctypes.c_size_t, u64p, vp]
+        L.zkt_g1_decompress_dev.argtypes = [vp, vp, ctypes.c_size_t, vp, vp]
+        vi, tp = ctypes.POINTER(VerifyInputs), ctypes.POINTER(vp)
+        L.zkt_verify_batch_prepare_dev.argtypes = [vp, vi, tp, ctypes.c_size_t, u64p, u64p, u64p, ip, u64p]
+        L.zkt_verify_batch_dev.argtypes = [vp, vi, tp, ctypes.c_size_t, u64p, u64p, ip]
     if hasattr(L, "zkt_kzg_commit_batch"):
         pp, szp = ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)
         L.zkt_kzg_commit_batch.argtypes = [vp, pp, szp, ctypes.c_int, ctypes.c_int, u64p, ip]
@@ -324,11 +332,8 @@ def verify(curve, n: int, vk_commits, vk_inf, pi_roots, pub_inputs, proof: bytes
     return bool(ok.value)
 
 
-def verify_batch(curve, items, h_g2, beta_h_g2) -> bool:
-    """zkt_verify_batch: `items` = [(n, vk_commits, vk_inf, pi_roots, pub_inputs, proof bytes, g_xy, seeded Transcript), ...];
-    True iff every proof verifies (one product of two pairings for the whole batch)."""
-    L = lib()
-    cid = curve_id(curve)
+def _verify_batch_args(cid, items, h_g2, beta_h_g2):
+    """The C arrays of a batch of verifier inputs -> (ins, transcripts, count, h, beta_h, keep-alive list)."""
     words = 8 if cid == CURVE_BN254 else 12
     h = np.ascontiguousarray(h_g2, dtype=np.uint64).reshape(2 * words)
     bh = np.ascontiguousarray(beta_h_g2, dtype=np.uint64).reshape(2 * words)
@@ -344,10 +349,19 @@ def verify_batch(curve, items, h_g2, beta_h_g2) -> bool:
         assert pi_roots.shape == pub_inputs.shape
         g_xy = np.ascontiguousarray(g_xy, dtype=np.uint64).reshape(words)
         inf = (ctypes.c_int * 10)(*[int(bool(x)) for x in vk_inf])
-        keep.append((vk_commits, pi_roots, pub_inputs, g_xy, inf, proof))
+        keep.append((vk_commits, pi_roots, pub_inputs, g_xy, inf, proof, transcript))   # the handle dies with its Transcript
         ins[i] = VerifyInputs(n, u64p(vk_commits), inf, u64p(pi_roots) if pi_roots.size else null,
                               u64p(pub_inputs) if pub_inputs.size else null, pi_roots.shape[0], proof, len(proof), u64p(g_xy))
         trs[i] = transcript.handle
+    return ins, trs, k, h, bh, keep
+
+
+def verify_batch(curve, items, h_g2, beta_h_g2) -> bool:
+    """zkt_verify_batch: `items` = [(n, vk_commits, vk_inf, pi_roots, pub_inputs, proof bytes, g_xy, seeded Transcript), ...];
+    True iff every proof verifies (one product of two pairings for the whole batch)."""
+    L = lib()
+    cid = curve_id(curve)
+    ins, trs, k, h, bh, keep = _verify_batch_args(cid, items, h_g2, beta_h_g2)
     P64 = ctypes.POINTER(ctypes.c_uint64)
     L.zkt_verify_batch.argtypes = [ctypes.c_int, ctypes.POINTER(VerifyInputs), ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t,
                                    P64, P64, ctypes.POINTER(ctypes.c_int)]
@@ -910,6 +924,46 @@ class Context:
         self.check(self._L.zkt_msm_g1_bases_dev(self._h, ctypes.c_void_p(d_bases), ctypes.c_void_p(d_scalars), n,
                                                 int(montgomery), u64p(out), ctypes.byref(inf)))
         return out, bool(inf.value)
+
+    # ---- untrusted bytes: checked deserialisation and batch verification on the device ----
+    def g1_decompress(self, data):
+        """zkt_g1_decompress: `data` = n compressed G1 points (bytes, 32 each on BN254, 48 on BLS12-381) ->
+        (points (n, 2*fq_limbs) Montgomery limbs, (0,0) for the identity and refused points; status (n,) uint8)"""
+        nb = 8 * self.fq_limbs
+        data = bytes(data)
+        if len(data) % nb:
+            raise ValueError("g1_decompress: %d bytes is not a whole number of %d-byte points" % (len(data), nb))
+        n = len(data) // nb
+        out = np.zeros((n, 2 * self.fq_limbs), dtype=np.uint64)
+        status = np.zeros(n, dtype=np.uint8)
+        self.check(self._L.zkt_g1_decompress(self._h, data if n else None, n, u64p(out) if n else None,
+                                             status.ctypes.data_as(ctypes.c_void_p) if n else None))
+        return out, status
+
+    def g1_decompress_dev(self, d_in: int, n: int, d_out: int, d_status: int):
+        """zkt_g1_decompress_dev: n x nb bytes in HBM -> n points and n status bytes in HBM; only enqueues."""
+        self.check(self._L.zkt_g1_decompress_dev(self._h, ctypes.c_void_p(d_in), n, ctypes.c_void_p(d_out),
+                                                 ctypes.c_void_p(d_status)))
+
+    def verify_batch_prepare_dev(self, items, h_g2, beta_h_g2, want_rho: bool = True):
+        """zkt_verify_batch_prepare_dev: `items` as _lib.verify_batch -> (A, B) as a (2, 2*fq_limbs) array of Montgomery limbs,
+        their two infinity flags, and the 2 * len(items) folding coefficients as (m, 4) canonical words (None unless
+        want_rho).  The batch is valid iff e(A, h) e(-B, beta h) == 1."""
+        ins, trs, k, h, bh, keep = _verify_batch_args(self.curve, items, h_g2, beta_h_g2)
+        ab = np.zeros((2, 2 * self.fq_limbs), dtype=np.uint64)
+        inf = (ctypes.c_int * 2)()
+        rho = np.zeros((2 * max(k, 1), 4), dtype=np.uint64) if want_rho else None
+        self.check(self._L.zkt_verify_batch_prepare_dev(self._h, ins, trs, k, u64p(h), u64p(bh), u64p(ab), inf,
+                                                        u64p(rho) if want_rho else None))
+        return ab, np.array([bool(x) for x in inf]), (rho[:2 * k] if want_rho else None)
+
+    def verify_batch_dev(self, items, h_g2, beta_h_g2) -> bool:
+        """zkt_verify_batch_dev: `items` as _lib.verify_batch; True iff every proof verifies.  Decompression and the two
+        combinations run on the device, the transcripts and the one pairing product on the host."""
+        ins, trs, k, h, bh, keep = _verify_batch_args(self.curve, items, h_g2, beta_h_g2)
+        ok = ctypes.c_int(0)
+        self.check(self._L.zkt_verify_batch_dev(self._h, ins, trs, k, u64p(h), u64p(bh), ctypes.byref(ok)))
+        return bool(ok.value)
 
     def msm_bases_info(self, n: int, montgomery: bool = True):
         """-> dict(window_bits, windows) that zkt_msm_g1_bases uses for n points"""

@@ -46,6 +46,8 @@ struct zkt_ctx {
     size_t io_b_bytes = 0;
     void* check_scratch = nullptr;   // zkt_circuit_check_witness (check.hip): the call's own, never shared with a fork
     size_t check_scratch_bytes = 0;
+    void* verify_scratch = nullptr;  // zkt_g1_decompress / zkt_verify_batch_dev (g1decomp.hip, verify.hip): the call's own
+    size_t verify_scratch_bytes = 0;
 
     // optional per-kernel HIP-event timing (bench.py's live roofline measurement)
     int prof_on = 0;   // 0 off, 1 every scope, 2 only the dominant kernel's scope ("msm_accumulate")

@@ -192,6 +192,10 @@ int msm_fork(zkt_ctx* child, const zkt_ctx* parent);
 void msm_slice(zkt_ctx* c, size_t* off, size_t* count, size_t* total);
 // one MSM, begun and collected
 int msm_g1_dev(zkt_ctx* c, const void* d_scalars, size_t n, size_t base_off, int mont, uint64_t* out_xy, int* out_inf);
+// zkt_msm_g1_bases: sum scalars[i] * bases[i] over the caller's affine points (host or device memory each), affine result in
+// host memory; n <= ZKT_MSM_BASES_MAX is checked here.  Synchronises the stream.
+int msm_bases(zkt_ctx* c, const void* bases, bool bases_on_device, const void* scalars, bool scalars_on_device, size_t n, int mont,
+              uint64_t* out_xy, int* out_inf);
 // prover-facing batch form: begin up to MsmState::SLOTS commitments, then collect them (tbl = 1: the Lagrange-prefix
 // table of lagrange.hip, tbl = MSM_TBL_WIRE + k: the base table of wire k)
 int msm_begin(zkt_ctx* c, const void* d_scalars, size_t n, size_t base_off, int mont, int slot, int tbl = 0);

@@ -1,19 +1,25 @@
 // Verifier, everything but the pairings: plonk-core/src/proof_system/proof.rs:285-503 up to the two
-// SonicKZG10::check calls.  Host-only code: one proof is 13 + 9 + 4 short scalar multiplications (~4 ms of host time on
-// the 64-bit-limb arithmetic of hostec.hpp); a GPU has nothing to add at that size.  The result is, for each of the
-// two openings, the pair (L, W) with
+// SonicKZG10::check calls.  This comment describes the SINGLE-PROOF case, which is host-only code: one proof is
+// 13 + 9 + 4 short scalar multiplications (~4 ms of host time on the 64-bit-limb arithmetic of hostec.hpp); a GPU has
+// nothing to add at that size.  (A batch of many proofs under one SRS is another matter: zkt_verify_batch_dev further
+// down moves the decompressions and the combinations, the two costs that grow with the batch, to the device.)  The
+// result is, for each of the two openings, the pair (L, W) with
 //     L = sum_i eta^i C_i - (sum_i eta^i v_i) G + z W
 // so that the opening is valid iff e(L, h) == e(W, beta h) -- the two pairings stay with the caller (arkworks'
 // `PairingEngine::product_of_pairings`), which also holds h and beta h (SonicKZG10's VerifierKey).
 #include "ctx.hpp"
 #include "ec.hpp"
 #include "hostec.hpp"
+#include "g1decomp.hpp"
 #include "hostinv.hpp"
+#include "msm.hpp"
 #include "pairing.hpp"
 #include "transcript.hpp"
 
 #include <cstring>
+#include <map>
 #include <memory>
+#include <string>
 #include <vector>
 
 namespace zkt {
@@ -266,31 +272,56 @@ struct Verifier {
         return from_le(b);
     }
 
-    static int run(const zkt_verify_inputs& in, HostTranscript& tr, uint64_t* out_pairs, int* out_inf) {
+    // Where a term's point comes from: the proof's 13 commitments in wire order, the ten verifier-key commitments, g.
+    // Z1, Z2, T, H1, g and the verifier-key points occur in both openings; a consumer that adds the two lists up (the
+    // batch verifier on the device) is left with at most SRC_COUNT bases per proof.
+    enum { SRC_CM = 0, SRC_VK = 13, SRC_G = 23, SRC_COUNT = 24 };
+    static constexpr int MAX_TERMS = 13 + 8 + 2;
+    // Step 2's result: opening o is L_o = sum_k sc[o][k] * base[src[o][k]], checked against W_o = base[wit[o]]
+    struct Terms {
+        Affine<Q> base[SRC_COUNT];
+        int n[2];
+        int src[2][MAX_TERMS];
+        F sc[2][MAX_TERMS];
+        int wit[2];
+    };
+
+    static int shape(const zkt_verify_inputs& in, int* out_log_n) {
         const size_t nb = Q::N * 4;
-        const int L64 = Q::N / 2;
         if (in.proof_len != 13 * nb + 2 + 12 * 32) return ZKT_ERR_INVALID_ARGUMENT;
         if (in.n == 0 || (in.n & (in.n - 1))) return ZKT_ERR_INVALID_DOMAIN_SIZE;
         int log_n = 0;
         while (((uint64_t)1 << log_n) < in.n) ++log_n;
         if (log_n > R::TWO_ADICITY) return ZKT_ERR_INVALID_DOMAIN_SIZE;
-        // ---- Proof::deserialize (proof.rs:98-155): 11 commitments, 2 x (opening, Option::None), 12 evaluations ----
-        Affine<Q> cm[13];
+        *out_log_n = log_n;
+        return ZKT_OK;
+    }
+
+    // ---- Proof::deserialize (proof.rs:98-155): 11 commitments, 2 x (opening, Option::None), 12 evaluations ----
+    // points_done: the commitments were decompressed and checked elsewhere (cm is filled); only the other bytes are looked at
+    static int parse(const zkt_verify_inputs& in, Affine<Q>* cm, F* ev, bool points_done) {
+        const size_t nb = Q::N * 4;
         size_t pos = 0;
         for (int k = 0; k < 13; ++k) {
             bool inf = false;
-            if (!decompress<C>(in.proof + pos, &cm[k], &inf)) return ZKT_ERR_INVALID_ARGUMENT;
+            if (!points_done && !decompress<C>(in.proof + pos, &cm[k], &inf)) return ZKT_ERR_INVALID_ARGUMENT;
             pos += nb;
             if (k >= 11) {
                 if (in.proof[pos] != 0) return ZKT_ERR_INVALID_ARGUMENT;   // kzg10::Proof::random_v must be None
                 pos += 1;
             }
         }
-        F ev[12];
         for (int k = 0; k < 12; ++k) {
             if (!canonical_from_bytes<R>(in.proof + pos, 0, &ev[k])) return ZKT_ERR_INVALID_ARGUMENT;
             pos += 32;
         }
+        return ZKT_OK;
+    }
+
+    // Step 2: the transcript, r0 and the scalars of both openings; no group arithmetic
+    static int terms(const zkt_verify_inputs& in, int log_n, const Affine<Q>* cm, const F* ev, HostTranscript& tr, Terms& out) {
+        const size_t nb = Q::N * 4;
+        const int L64 = Q::N / 2;
         enum { A, B, Cc, T, H1, H2, Z1, Z2, QLO, QMID, QHI, AW, SAW };
         const F &e_a = ev[0], &e_b = ev[1], &e_c = ev[2], &e_s1 = ev[3], &e_s2 = ev[4], &e_z1n = ev[5], &e_ql = ev[6],
                 &e_t = ev[7], &e_tn = ev[8], &e_z2n = ev[9], &e_h1n = ev[10], &e_h2 = ev[11];
@@ -379,8 +410,8 @@ struct Verifier {
         const F xn2 = fe_mul<R>(fe_mul<R>(fe_add<R>(zh, one), xi), xi), nzh = fe_neg<R>(zh);
         const F sc[13] = {fe_mul<R>(e_a, e_b), e_a, e_b, e_c, one, s_z1, s_s3, s_z2, s_h1, s_qt,
                           nzh, fe_mul<R>(nzh, xn2), fe_mul<R>(nzh, fe_sqr<R>(xn2))};
-        const Affine<Q>* pt[13] = {&vk[QM], &vk[QL], &vk[QR], &vk[QO], &vk[QC], &cm[Z1], &vk[S3], &cm[Z2], &cm[H1], &vk[QTABLE],
-                                   &cm[QLO], &cm[QMID], &cm[QHI]};
+        const int pt[13] = {SRC_VK + QM, SRC_VK + QL, SRC_VK + QR, SRC_VK + QO, SRC_VK + QC, SRC_CM + Z1, SRC_VK + S3, SRC_CM + Z2,
+                            SRC_CM + H1, SRC_VK + QTABLE, SRC_CM + QLO, SRC_CM + QMID, SRC_CM + QHI};
         static const char* EL[12] = {"a_eval", "b_eval", "c_eval", "sigma1_eval", "sigma2_eval", "z1_next_eval",
                                      "q_lookup_eval", "t_eval", "t_next_eval", "z2_next_eval", "h1_next_eval", "h2_eval"};
         for (int k = 0; k < 12; ++k) {
@@ -390,57 +421,77 @@ struct Verifier {
         }
         const F eta = challenge(tr, "eta");
         // ---- the two openings (proof.rs:420-500) ----
-        // L = sum_i eta^i C_i - (sum_i eta^i v_i) g + z W as ONE short multi-scalar multiplication; the linearisation
-        // commitment (C_0 of the first opening, coefficient eta^0 = 1) enters through its own 13 terms
+        // L = sum_i eta^i C_i - (sum_i eta^i v_i) g + z W as ONE list of terms; the linearisation commitment (C_0 of the
+        // first opening, coefficient eta^0 = 1) enters through its own 13 terms
         Affine<Q> g;
         memcpy(g.x.v, in.g, nb);
         memcpy(g.y.v, in.g + L64, nb);
         const F w = root_of_unity<R>(log_n);
-        auto emit = [&](std::vector<HX>& pts, std::vector<F>& scs, const Affine<Q>& wit, int slot) {
-            const HX L = msm_wnaf<C>(pts.data(), scs.data(), (int)pts.size());
-            const Affine<Q> la = xyzz_to_affine_host<Q>(hostec::hx_to<Q>(L));
-            uint64_t* o = out_pairs + (size_t)slot * 4 * L64;
-            memcpy(o, la.x.v, nb);
-            memcpy(o + L64, la.y.v, nb);
-            memcpy(o + 2 * L64, wit.x.v, nb);
-            memcpy(o + 3 * L64, wit.y.v, nb);
-            if (out_inf) {
-                out_inf[2 * slot] = aff_is_inf<Q>(la) ? 1 : 0;
-                out_inf[2 * slot + 1] = aff_is_inf<Q>(wit) ? 1 : 0;
-            }
+        for (int k = 0; k < 13; ++k) out.base[SRC_CM + k] = cm[k];
+        for (int k = 0; k < 10; ++k) out.base[SRC_VK + k] = vk[k];
+        out.base[SRC_G] = g;
+        auto push = [&](int o, int src, const F& s) {
+            out.src[o][out.n[o]] = src;
+            out.sc[o][out.n[o]] = s;
+            ++out.n[o];
         };
-        auto fold = [&](std::vector<HX>& pts, std::vector<F>& scs, const Affine<Q>* const* commits, const F* values, int k,
-                        F ch, F comb_v, const F& z, const Affine<Q>& wit) {
+        auto fold = [&](int o, const int* commits, const F* values, int k, F ch, F comb_v, const F& z, int wit) {
             for (int i = 0; i < k; ++i) {
-                pts.push_back(to_hx(*commits[i]));
-                scs.push_back(ch);
+                push(o, commits[i], ch);
                 comb_v = fe_add<R>(comb_v, fe_mul<R>(ch, values[i]));
                 ch = fe_mul<R>(ch, eta);
             }
-            pts.push_back(to_hx(g));
-            scs.push_back(fe_neg<R>(comb_v));
-            pts.push_back(to_hx(wit));
-            scs.push_back(z);
+            push(o, SRC_G, fe_neg<R>(comb_v));
+            push(o, wit, z);
+            out.wit[o] = wit;
         };
+        out.n[0] = out.n[1] = 0;
         {
-            std::vector<HX> pts;
-            std::vector<F> scs;
-            for (int k = 0; k < 13; ++k) {
-                pts.push_back(to_hx(*pt[k]));
-                scs.push_back(sc[k]);
-            }
-            const Affine<Q>* cs[8] = {&cm[A], &cm[B], &cm[Cc], &vk[S1], &vk[S2], &vk[QLOOKUP], &cm[T], &cm[H2]};
+            for (int k = 0; k < 13; ++k) push(0, pt[k], sc[k]);
+            const int cs[8] = {SRC_CM + A, SRC_CM + B, SRC_CM + Cc, SRC_VK + S1, SRC_VK + S2, SRC_VK + QLOOKUP, SRC_CM + T, SRC_CM + H2};
             const F vs[8] = {e_a, e_b, e_c, e_s1, e_s2, e_ql, e_t, e_h2};
-            fold(pts, scs, cs, vs, 8, eta, r0, xi, cm[AW]);
-            emit(pts, scs, cm[AW], 0);
+            fold(0, cs, vs, 8, eta, r0, xi, SRC_CM + AW);
         }
         {
+            const int cs[4] = {SRC_CM + Z1, SRC_CM + Z2, SRC_CM + T, SRC_CM + H1};
+            const F vs[4] = {e_z1n, e_z2n, e_tn, e_h1n};
+            fold(1, cs, vs, 4, one, fe_zero<R>(), fe_mul<R>(xi, w), SRC_CM + SAW);
+        }
+        return ZKT_OK;
+    }
+
+    // Steps 1 to 3 for one proof: the pairs (L, W) of both openings
+    static int run(const zkt_verify_inputs& in, HostTranscript& tr, uint64_t* out_pairs, int* out_inf) {
+        const size_t nb = Q::N * 4;
+        const int L64 = Q::N / 2;
+        int log_n = 0;
+        int rc = shape(in, &log_n);
+        if (rc) return rc;
+        Affine<Q> cm[13];
+        F ev[12];
+        if ((rc = parse(in, cm, ev, false))) return rc;
+        auto t = std::make_unique<Terms>();
+        if ((rc = terms(in, log_n, cm, ev, tr, *t))) return rc;
+        // Step 3: each list as ONE short multi-scalar multiplication
+        for (int o = 0; o < 2; ++o) {
             std::vector<HX> pts;
             std::vector<F> scs;
-            const Affine<Q>* cs[4] = {&cm[Z1], &cm[Z2], &cm[T], &cm[H1]};
-            const F vs[4] = {e_z1n, e_z2n, e_tn, e_h1n};
-            fold(pts, scs, cs, vs, 4, one, fe_zero<R>(), fe_mul<R>(xi, w), cm[SAW]);
-            emit(pts, scs, cm[SAW], 1);
+            for (int k = 0; k < t->n[o]; ++k) {
+                pts.push_back(to_hx(t->base[t->src[o][k]]));
+                scs.push_back(t->sc[o][k]);
+            }
+            const HX L = msm_wnaf<C>(pts.data(), scs.data(), (int)pts.size());
+            const Affine<Q> la = xyzz_to_affine_host<Q>(hostec::hx_to<Q>(L));
+            const Affine<Q>& wit = t->base[t->wit[o]];
+            uint64_t* o_ = out_pairs + (size_t)o * 4 * L64;
+            memcpy(o_, la.x.v, nb);
+            memcpy(o_ + L64, la.y.v, nb);
+            memcpy(o_ + 2 * L64, wit.x.v, nb);
+            memcpy(o_ + 3 * L64, wit.y.v, nb);
+            if (out_inf) {
+                out_inf[2 * o] = aff_is_inf<Q>(la) ? 1 : 0;
+                out_inf[2 * o + 1] = aff_is_inf<Q>(wit) ? 1 : 0;
+            }
         }
         return ZKT_OK;
     }
@@ -668,6 +719,230 @@ static int verify_batch_t(int curve_id, const zkt_verify_inputs* ins, zkt_transc
     if (rc) return rc;
     *accepted = one ? 1 : 0;
     return ZKT_OK;
+}
+
+// ---- zkt_verify_batch_dev: the batch above with its two per-proof costs on the device ------------------------------
+// Stage 1: the 13 k compressed commitments go up in one copy and through ONE k_g1_decompress launch (g1decomp.hip); the
+//          other bytes of a proof (length, Option::None, evaluations) are checked here.
+// Stage 2: Verifier::terms per proof, on the host: transcript, r0, the scalars of both openings -- no group arithmetic.
+// Stage 3: rho_0 = 1, rho_j = low 128 bits of Keccak-256(seed || j); the seed is hashed from everything that determines the
+//          pairs (L_j, W_j), which this route never forms (verify_batch_t hashes the pairs: other coefficients, the same
+//          soundness argument).
+// Stage 4: the 2 k term lists, scaled by their rho_j, are added up per point: inside a proof by source, across proofs for
+//          verifier-key points and g of equal CONTENT (a caller may pass one array or a copy per proof).
+// Stage 5: A = sum s_k P_k and B = sum rho_j W_j as two variable-base MSMs (msm_bases), canonical scalars.
+// The host keeps what is serial and small per proof (a Strobe / Keccak transcript and ~150 Fr products); the device takes
+// what is wide: 13 k square roots and subgroup checks, and a (<= 24 k)-point and a 2 k-point MSM.
+template <class C>
+static int verify_batch_prepare_dev_t(zkt_ctx* c, const zkt_verify_inputs* ins, zkt_transcript* const* trs, size_t k,
+                                      const uint64_t* h, const uint64_t* beta_h, uint64_t* out_ab, int* out_inf, uint64_t* out_rho) {
+    using V = Verifier<C>;
+    using Q = typename C::Fq;
+    using R = typename C::Fr;
+    using F = Fe<R>;
+    constexpr int L64 = Q::N / 2;
+    const size_t nb = Q::N * 4, npts = 13 * k;
+    static const char* const CM_NAME[13] = {"a", "b", "c", "t", "h1", "h2", "z1", "z2", "q_lo", "q_mid", "q_hi", "aw", "saw"};
+    auto fail = [&](int rc, size_t i, const std::string& what) {
+        return set_err(c, rc, "verify_batch_dev: proof " + std::to_string(i) + ": " + what);
+    };
+    // ---- stage 1 ----
+    std::vector<int> log_n(k);
+    std::vector<F> ev(12 * k);
+    std::vector<uint8_t> comp(npts * nb);
+    for (size_t i = 0; i < k; ++i) {
+        const zkt_verify_inputs& in = ins[i];
+        if (!trs[i] || !in.proof || !in.vk_commitments || !in.g || (in.n_pi && (!in.pi_roots || !in.pub_inputs)))
+            return fail(ZKT_ERR_INVALID_ARGUMENT, i, "null pointer");
+        int rc = V::shape(in, &log_n[i]);
+        if (rc) return fail(rc, i, rc == ZKT_ERR_INVALID_DOMAIN_SIZE ? "n is not a supported power of two" : "wrong proof length");
+        if ((rc = V::parse(in, nullptr, &ev[12 * i], true)))
+            return fail(rc, i, "malformed bytes (an Option that is not None, or an evaluation that is not canonical)");
+        size_t pos = 0;
+        for (int j = 0; j < 13; ++j) {
+            memcpy(comp.data() + (13 * i + j) * nb, in.proof + pos, nb);
+            pos += nb + (j >= 11 ? 1 : 0);
+        }
+    }
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t o_out = up(npts * nb), o_st = o_out + up(npts * 2 * nb);
+    int rc = ensure_buffer(c, &c->verify_scratch, &c->verify_scratch_bytes, o_st + up(npts));
+    if (rc) return rc;
+    char* const base = (char*)c->verify_scratch;
+    std::vector<Affine<Q>> cm(npts);
+    std::vector<uint8_t> status(npts);
+    {
+        ProfScope prof(c, "verify_decompress");
+        ZKT_HIP(c, hipMemcpyAsync(base, comp.data(), npts * nb, hipMemcpyHostToDevice, c->stream));
+        if ((rc = g1_decompress_enqueue(c, base, npts, base + o_out, base + o_st))) {
+            (void)hipStreamSynchronize(c->stream);
+            return rc;
+        }
+        ZKT_HIP(c, hipMemcpyAsync(cm.data(), base + o_out, npts * 2 * nb, hipMemcpyDeviceToHost, c->stream));
+        ZKT_HIP(c, hipMemcpyAsync(status.data(), base + o_st, npts, hipMemcpyDeviceToHost, c->stream));
+    }
+    ZKT_HIP(c, hipStreamSynchronize(c->stream));
+    for (size_t p = 0; p < npts; ++p)
+        if (status[p] > ZKT_G1_IDENTITY) {
+            static const char* const WHY[6] = {"", "", "x is not below the modulus", "both flag bits set", "not on the curve",
+                                               "outside the prime-order subgroup"};
+            return fail(ZKT_ERR_INVALID_ARGUMENT, p / 13,
+                        std::string("commitment ") + std::to_string(p % 13) + " (" + CM_NAME[p % 13] + ") refused: " +
+                            (status[p] < 6 ? WHY[status[p]] : "unknown status"));
+        }
+    // ---- stage 3's seed (hashed before the transcripts are consumed: it depends on the inputs alone) ----
+    uint8_t seed[32];
+    {
+        std::vector<uint8_t> buf;
+        auto put = [&](const void* p, size_t bytes) {
+            const uint8_t* b = (const uint8_t*)p;
+            buf.insert(buf.end(), b, b + bytes);
+        };
+        auto put64 = [&](uint64_t v) { put(&v, 8); };
+        const uint32_t cid = (uint32_t)C::ID;
+        put(&cid, 4);
+        put64((uint64_t)k);
+        for (size_t i = 0; i < k; ++i) {
+            const zkt_verify_inputs& in = ins[i];
+            put64((uint64_t)in.proof_len);
+            put(in.proof, in.proof_len);
+            put64(in.n);
+            for (int j = 0; j < 10; ++j) {
+                const uint8_t inf = in.vk_is_infinity && in.vk_is_infinity[j] ? 1 : 0;
+                uint64_t w[2 * 6] = {0};
+                if (!inf) memcpy(w, in.vk_commitments + (size_t)j * 2 * L64, 2 * nb);
+                put(w, 2 * nb);
+                put(&inf, 1);
+            }
+            put64((uint64_t)in.n_pi);
+            if (in.n_pi) {
+                put(in.pi_roots, in.n_pi * 32);
+                put(in.pub_inputs, in.n_pi * 32);
+            }
+            put(in.g, 2 * nb);
+        }
+        put(h, 4 * nb);
+        put(beta_h, 4 * nb);
+        keccak256(buf.data(), buf.size(), seed);
+    }
+    const size_t m = 2 * k;
+    std::vector<F> rho(m);          // Montgomery
+    std::vector<uint64_t> rho_c(4 * m, 0);   // canonical words: B's scalars, out_rho
+    for (size_t j = 0; j < m; ++j) {
+        F r = fe_zero<R>();
+        if (j == 0) {
+            r.v[0] = 1;
+        } else {
+            uint8_t msg[40], dg[32];
+            const uint64_t jj = (uint64_t)j;
+            memcpy(msg, seed, 32);
+            memcpy(msg + 32, &jj, 8);
+            keccak256(msg, sizeof msg, dg);
+            memcpy(r.v, dg, 16);                       // 128 bits: below both scalar moduli
+        }
+        memcpy(&rho_c[4 * j], r.v, 32);
+        rho[j] = fe_to_mont<R>(r);
+    }
+    // ---- stages 2 and 4 ----
+    std::vector<Affine<Q>> a_bases, b_bases(m);
+    std::vector<F> a_acc;                              // Montgomery sums, one per entry of a_bases
+    std::map<std::string, size_t> shared;              // verifier-key points and g, by content
+    a_bases.reserve(V::SRC_COUNT * (k < 64 ? k : 64) + 13 * k);
+    auto t = std::make_unique<typename V::Terms>();
+    for (size_t i = 0; i < k; ++i) {
+        if ((rc = V::terms(ins[i], log_n[i], &cm[13 * i], &ev[12 * i], *trs[i]->impl, *t)))
+            return fail(rc, i, rc == ZKT_ERR_EQUAL_CHALLENGES ? "two challenges are equal" : "a Lagrange denominator is zero");
+        F acc[V::SRC_COUNT];
+        for (int s = 0; s < V::SRC_COUNT; ++s) acc[s] = fe_zero<R>();
+        for (int o = 0; o < 2; ++o) {
+            for (int q = 0; q < t->n[o]; ++q)
+                acc[t->src[o][q]] = fe_add<R>(acc[t->src[o][q]], fe_mul<R>(rho[2 * i + o], t->sc[o][q]));
+            b_bases[2 * i + o] = t->base[t->wit[o]];
+        }
+        for (int s = 0; s < V::SRC_COUNT; ++s) {
+            const Affine<Q>& pt = t->base[s];
+            if (aff_is_inf<Q>(pt)) continue;
+            if (s >= V::SRC_VK) {
+                auto ins_ = shared.emplace(std::string((const char*)&pt, sizeof(pt)), a_bases.size());
+                if (!ins_.second) {
+                    a_acc[ins_.first->second] = fe_add<R>(a_acc[ins_.first->second], acc[s]);
+                    continue;
+                }
+            }
+            a_bases.push_back(pt);
+            a_acc.push_back(acc[s]);
+        }
+    }
+    std::vector<uint64_t> a_sc(4 * a_bases.size());
+    for (size_t q = 0; q < a_acc.size(); ++q) {
+        const F s = fe_from_mont<R>(a_acc[q]);
+        memcpy(&a_sc[4 * q], s.v, 32);
+    }
+    // ---- stage 5 ----
+    int inf[2] = {0, 0};
+    {
+        ProfScope prof(c, "verify_msm");
+        if ((rc = msm_bases(c, a_bases.data(), false, a_sc.data(), false, a_bases.size(), 0, out_ab, &inf[0])) ||
+            (rc = msm_bases(c, b_bases.data(), false, rho_c.data(), false, m, 0, out_ab + 2 * L64, &inf[1])))
+            return rc;
+    }
+    if (out_inf) {
+        out_inf[0] = inf[0];
+        out_inf[1] = inf[1];
+    }
+    if (out_rho) memcpy(out_rho, rho_c.data(), m * 32);
+    return ZKT_OK;
+}
+
+template <class C>
+static int verify_batch_dev_t(zkt_ctx* c, const zkt_verify_inputs* ins, zkt_transcript* const* trs, size_t k, const uint64_t* h,
+                              const uint64_t* beta_h, int* accepted) {
+    using Q = typename C::Fq;
+    constexpr int L64 = Q::N / 2;
+    uint64_t g1[2 * 12], g2[2 * 4 * 6];
+    int rc = verify_batch_prepare_dev_t<C>(c, ins, trs, k, h, beta_h, g1, nullptr, nullptr);
+    if (rc) return rc;
+    Affine<Q> wc;
+    memcpy(wc.x.v, g1 + 2 * L64, L64 * 8);
+    memcpy(wc.y.v, g1 + 3 * L64, L64 * 8);
+    if (!aff_is_inf<Q>(wc)) wc.y = fe_neg<Q>(wc.y);
+    memcpy(g1 + 3 * L64, wc.y.v, L64 * 8);
+    memcpy(g2, h, 4 * L64 * 8);
+    memcpy(g2 + 4 * L64, beta_h, 4 * L64 * 8);
+    int one = 0;
+    if ((rc = pairing_check_t<C>(g1, g2, 2, &one))) return set_err(c, rc, "verify_batch_dev: the pairing refused its arguments");
+    *accepted = one ? 1 : 0;
+    return ZKT_OK;
+}
+
+static int verify_batch_dev_args(zkt_ctx* c, const void* ins, const void* trs, size_t count, const void* h, const void* bh,
+                                 const void* out) {
+    if (!c) return ZKT_ERR_INVALID_ARGUMENT;
+    if (count == 0) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "verify_batch_dev: an empty batch");
+    if (count > ZKT_VERIFY_BATCH_DEV_MAX)
+        return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "verify_batch_dev: more proofs than ZKT_VERIFY_BATCH_DEV_MAX");
+    if (!ins || !trs || !h || !bh || !out) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
+    (void)hipSetDevice(c->device);
+    return ZKT_OK;
+}
+
+extern "C" int zkt_verify_batch_prepare_dev(zkt_ctx* c, const zkt_verify_inputs* ins, zkt_transcript* const* transcripts,
+                                            size_t count, const uint64_t* h_g2_mont, const uint64_t* beta_h_g2_mont,
+                                            uint64_t* out_ab, int* out_ab_is_infinity, uint64_t* out_rho) {
+    if (int rc = verify_batch_dev_args(c, ins, transcripts, count, h_g2_mont, beta_h_g2_mont, out_ab)) return rc;
+    if (c->curve == ZKT_CURVE_BN254)
+        return verify_batch_prepare_dev_t<Bn254Curve>(c, ins, transcripts, count, h_g2_mont, beta_h_g2_mont, out_ab,
+                                                      out_ab_is_infinity, out_rho);
+    return verify_batch_prepare_dev_t<Bls381Curve>(c, ins, transcripts, count, h_g2_mont, beta_h_g2_mont, out_ab,
+                                                   out_ab_is_infinity, out_rho);
+}
+
+extern "C" int zkt_verify_batch_dev(zkt_ctx* c, const zkt_verify_inputs* ins, zkt_transcript* const* transcripts, size_t count,
+                                    const uint64_t* h_g2_mont, const uint64_t* beta_h_g2_mont, int* accepted) {
+    if (int rc = verify_batch_dev_args(c, ins, transcripts, count, h_g2_mont, beta_h_g2_mont, accepted)) return rc;
+    if (c->curve == ZKT_CURVE_BN254)
+        return verify_batch_dev_t<Bn254Curve>(c, ins, transcripts, count, h_g2_mont, beta_h_g2_mont, accepted);
+    return verify_batch_dev_t<Bls381Curve>(c, ins, transcripts, count, h_g2_mont, beta_h_g2_mont, accepted);
 }
 
 // ---- the G2 half of the test / bench SRS (zkt_srs_generate is the G1 half): h = the G2 generator of ark-bn254 /
