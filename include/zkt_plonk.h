@@ -553,6 +553,47 @@ int zkt_poseidon_gadget_check(zkt_ctx* ctx, const zkt_poseidon* params);
  * (the proof then fails to verify).  ZKT_ERR_INVALID_ARGUMENT names the rule.  Run it once per circuit layout. */
 int zkt_poseidon_gadget_validate(zkt_ctx* ctx, const zkt_poseidon* params, const zkt_poseidon_gadget_args* args);
 
+/* (3) The WITNESS of the Merkle-path gadget merkle_proof (plonk-hashing/src/merkle/binary.rs:8-30) for `batch` paths of
+ * `height` levels, ONE launch: a chain in which each level hashes two conditional_selects of the level below, so it cannot
+ * be a launch of independent hashes unless the host walks every path first.  Per level, for the bit b, the sibling s and
+ * the running hash cur (the leaf at level 0), the composer allocates, in this order (constraint_system/mod.rs:339-354 for
+ * one select, binary.rs:23-24 for the two),
+ *     x_l = b s, y_l = (1 - b) cur, z_l = x_l + y_l,   x_r = b cur, y_r = (1 - b) s, z_r = x_r + y_r,
+ * and then the zkt_poseidon_gadget_vars_per_hash variables of hash_two(z_l, z_r) (hasher/mod.rs:26-33: arity 2).  A level is
+ *     zkt_merkle_path_vars_per_level = 6 + zkt_poseidon_gadget_vars_per_hash
+ * consecutive variables, a path `height` consecutive levels: path p fills d_variables[base .. base + height *
+ * vars_per_level) with base = d_path_base[p], or path_base0 + p * height * vars_per_level when d_path_base is NULL.  The
+ * root is the hash variable of the last level, base + (height - 1) * vars_per_level + 6 + (vars_per_hash - 1 - (W - 2) W);
+ * d_out_roots (optional) receives it as well.  The running hash stays in registers: the kernel reads no variable it wrote.
+ * Inputs are plain variables (coeff 1, offset 0: binary.rs:42-78 assigns the bits and the siblings itself, and every caller
+ * in circuits/src/withdraw.rs passes a hash variable as the leaf), given as INDICES into d_variables
+ * (ZKT_VARIABLE_ZERO = Variable::Zero reads as 0).  A leaf, bit or sibling may not be a variable the same launch writes.
+ * width >= 3 (hash_two on width 2 is FullBuffer, spec.rs:253-257) and height >= 0, else ZKT_ERR_INVALID_ARGUMENT; batch =
+ * 0 or height = 0 enqueues nothing.  Device pointers, no allocation, no synchronisation.  A path whose range leaves
+ * [0, n_vars), one of whose indices is neither < n_vars nor ZKT_VARIABLE_ZERO, or one of whose bits holds a value other
+ * than 0 or 1 (conditional_select asserts that; the library never aborts) is skipped as a whole -- nothing of it is
+ * written, the other paths of the launch are unaffected -- and raises the flag zkt_poseidon_gadget_check reports.
+ * Cost: the levels of a path are serial, one permutation's latency each whatever the batch -- measured 0.22-0.23 ms per
+ * level on an MI355X, 14.8 ms for 8 paths of 64 levels on Bn254x5 (docs/EXPERIMENTS.md, "Merkle path on the device"). */
+typedef struct {
+    size_t batch;
+    int height;
+    void* d_variables;               /* VariableMap::values, n_vars scalars */
+    size_t n_vars;
+    const uint32_t* d_leaf_var;      /* batch */
+    const uint32_t* d_bit_vars;      /* batch x height, level 0 first */
+    const uint32_t* d_sibling_vars;  /* batch x height */
+    const uint32_t* d_path_base;     /* batch, or NULL */
+    size_t path_base0;
+    void* d_out_roots;               /* optional: batch scalars */
+} zkt_merkle_path_args;
+size_t zkt_merkle_path_vars_per_level(const zkt_poseidon* params);
+int zkt_poseidon_merkle_path_witness_dev(zkt_ctx* ctx, const zkt_poseidon* params, const zkt_merkle_path_args* args);
+/* Optional validation of ONE launch's arguments on the host (downloads the index vectors, synchronises): the paths' ranges
+ * must be pairwise disjoint and inside the map, and no leaf, bit or sibling index may lie inside a range the launch
+ * writes.  ZKT_ERR_INVALID_ARGUMENT names the rule.  Run it once per circuit layout. */
+int zkt_poseidon_merkle_path_validate(zkt_ctx* ctx, const zkt_poseidon* params, const zkt_merkle_path_args* args);
+
 /* ---- Verifier (proof_system/proof.rs:285-503): zkt_verify_prepare = everything but the pairings,
  * ---- zkt_pairing_product_is_one = the pairings, zkt_verify = both ------------------------------------------------
  * Deserialises the proof (proof.rs:98-155; points are decompressed and checked to be on the curve), replays the

@@ -141,6 +141,9 @@ extern "C" {
     pub fn zkt_poseidon_gadget_vars_per_hash(params: *const c_void) -> usize;
     pub fn zkt_poseidon_gadget_witness_dev(ctx: *mut ZktCtx, params: *const c_void, args: *const ZktPoseidonGadgetArgs) -> c_int;
     pub fn zkt_poseidon_gadget_check(ctx: *mut ZktCtx, params: *const c_void) -> c_int;
+    pub fn zkt_merkle_path_vars_per_level(params: *const c_void) -> usize;
+    pub fn zkt_poseidon_merkle_path_witness_dev(ctx: *mut ZktCtx, params: *const c_void, args: *const ZktMerklePathArgs) -> c_int;
+    pub fn zkt_poseidon_merkle_path_validate(ctx: *mut ZktCtx, params: *const c_void, args: *const ZktMerklePathArgs) -> c_int;
     pub fn zkt_dev_alloc(ctx: *mut ZktCtx, bytes: usize, dptr: *mut *mut c_void) -> c_int;
     pub fn zkt_dev_free(ctx: *mut ZktCtx, dptr: *mut c_void) -> c_int;
     pub fn zkt_dev_upload(ctx: *mut ZktCtx, dptr: *mut c_void, host: *const c_void, bytes: usize) -> c_int;
@@ -170,6 +173,20 @@ pub struct ZktPoseidonGadgetArgs {
     pub trace_base0: usize,
     pub d_out_hashes: *mut c_void,
     pub kernel: c_int,
+}
+
+#[repr(C)]
+pub struct ZktMerklePathArgs {
+    pub batch: usize,
+    pub height: c_int,
+    pub d_variables: *mut c_void,
+    pub n_vars: usize,
+    pub d_leaf_var: *const u32,
+    pub d_bit_vars: *const u32,
+    pub d_sibling_vars: *const u32,
+    pub d_path_base: *const u32,
+    pub path_base0: usize,
+    pub d_out_roots: *mut c_void,
 }
 
 #[repr(C)]

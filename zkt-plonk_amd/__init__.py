@@ -7,7 +7,8 @@ Host-side mirror of the reference's two generic seams:
                          (plonk-core/src/commitment.rs:10-46)
 * ``GpuProver.prove``  ~ ``proof_system::prove``  (plonk-core/src/proof_system/prove.rs:59-470; the openings live inside it)
 * ``PoseidonGadget``   ~ ``PoseidonRef<ConstraintSystem, PlonkSpecRef, ..>::hash`` as the proving composer sees it: the gadget's
-                         variables, made on the device (plonk-hashing/src/hasher/poseidon/spec.rs:174-375)
+                         variables, made on the device (plonk-hashing/src/hasher/poseidon/spec.rs:174-375);
+                         ``merkle_path`` ~ ``merkle_proof`` (plonk-hashing/src/merkle/binary.rs:8-30), a path per launch lane group
 * ``parallel``         ~ one proof or many across the GPUs of a node (communicators, SRS slices)
 
 These are thin ctypes mirrors for the tests and ``bench.py``; the product is the C-ABI (include/zkt_plonk.h).

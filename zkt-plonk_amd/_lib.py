@@ -143,6 +143,14 @@ def _bind_optional(L):
         L.zkt_kzg_open_dev.argtypes = [vp, pp, szp, ctypes.c_int, u64p, u64p, u64p, ip, u64p]
 
 
+class MerklePathArgs(ctypes.Structure):
+    """zkt_merkle_path_args (include/zkt_plonk.h), field for field."""
+    _fields_ = [("batch", ctypes.c_size_t), ("height", ctypes.c_int), ("d_variables", ctypes.c_void_p),
+                ("n_vars", ctypes.c_size_t), ("d_leaf_var", ctypes.c_void_p), ("d_bit_vars", ctypes.c_void_p),
+                ("d_sibling_vars", ctypes.c_void_p), ("d_path_base", ctypes.c_void_p), ("path_base0", ctypes.c_size_t),
+                ("d_out_roots", ctypes.c_void_p)]
+
+
 ALL_GATHER_CB = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
                                  ctypes.c_int, ctypes.c_void_p)
 
@@ -822,6 +830,27 @@ class Context:
         L = self._L
         L.zkt_poseidon_gadget_check.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         self.check(L.zkt_poseidon_gadget_check(self._h, ctypes.c_void_p(handle)))
+
+    def merkle_path_vars_per_level(self, handle: int) -> int:
+        """zkt_merkle_path_vars_per_level: 6 select variables + the hash's vars_per_hash."""
+        L = self._L
+        L.zkt_merkle_path_vars_per_level.argtypes = [ctypes.c_void_p]
+        L.zkt_merkle_path_vars_per_level.restype = ctypes.c_size_t
+        return int(L.zkt_merkle_path_vars_per_level(ctypes.c_void_p(handle)))
+
+    def poseidon_merkle_path_witness_dev(self, handle: int, batch: int, height: int, d_variables: int, n_vars: int,
+                                         d_leaf_var: int, d_bit_vars: int, d_sibling_vars: int, d_path_base: int = 0,
+                                         path_base0: int = 0, d_out_roots: int = 0, validate_only: bool = False):
+        """zkt_poseidon_merkle_path_witness_dev: the variables merkle_proof allocates for `batch` paths of `height` levels
+        (per level two conditional_selects and hash_two), one launch, written into the variable map at d_variables (device
+        pointers; enqueue only).  validate_only: zkt_poseidon_merkle_path_validate on the same arguments instead (disjoint
+        ranges, no input made by the same launch; synchronises, launches nothing)."""
+        a = MerklePathArgs(batch, height, d_variables or None, n_vars, d_leaf_var or None, d_bit_vars or None,
+                           d_sibling_vars or None, d_path_base or None, path_base0, d_out_roots or None)
+        L = self._L
+        fn = L.zkt_poseidon_merkle_path_validate if validate_only else L.zkt_poseidon_merkle_path_witness_dev
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MerklePathArgs)]
+        self.check(fn(self._h, ctypes.c_void_p(handle), ctypes.byref(a)))
 
     # -- device memory ------------------------------------------------------------------------
     def alloc(self, nbytes: int) -> int:

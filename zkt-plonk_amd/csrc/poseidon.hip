@@ -301,6 +301,51 @@ ZKT_D Fx<P> fx_shfl(const Fx<P>& a, int src_lane) {
     return r;
 }
 
+// The rounds of one permutation in that layout, shared by k_poseidon_gadget_lanes and k_poseidon_merkle_path.  Lane
+// l = j W + i of the segment starting at lane seg0 enters with element i of the initial state in x and leaves with element
+// i of the final one; m is its matrix entry m[i][j] (H form), rc points at ITS round constant of the first round
+// (rc_a + 9 i).  With store set (the hash runs and the lane is live) the variables go to out[0 .. vars_per_hash) in
+// allocation order.  Every lane of the wavefront must call it: the shuffles are wave-wide.
+template <class P, int W>
+ZKT_D Fx<P> poseidon_lanes_rounds(Fx<P> x, const Fx<P>& m, const uint32_t* rc, Fe<P>* out, bool store, int half_full, int partial,
+                                  int lane, int seg0, int l, int i, int j) {
+    const int rounds = 2 * half_full + partial;
+#pragma unroll 1
+    for (int r = 0; r < rounds; ++r) {
+        const bool full = r < half_full || r >= half_full + partial;
+        x = fx_cond_sub_p<P>(fx_add<P>(x, fx_load_limbs<P>(rc)));     // add_constant: no gate
+        rc += 9 * W;
+        // power_of_5 of my element; kept where the round has an s-box for it
+        const Fx<P> xs = fx_shl_sh<P>(x);
+        const Fx<P> x2 = gadget_mul<P>(x, xs);
+        const Fx<P> x4 = gadget_mul<P>(x2, fx_shl_sh<P>(x2));
+        const Fx<P> x5 = gadget_mul<P>(x4, xs);
+        const bool boxed = full || i == 0;
+        if (store && j == 0 && boxed) {
+            Fe<P>* o = out + 3 * i;
+            fe_store<P>(o, fx_pack<P>(x2));
+            fe_store<P>(o + 1, fx_pack<P>(x4));
+            fe_store<P>(o + 2, fx_pack<P>(x5));
+        }
+        out += full ? 3 * W : 3;
+        Fx<P> s;
+#pragma unroll
+        for (int k = 0; k < FxP<P>::L; ++k) s.l[k] = boxed ? x5.l[k] : x.l[k];
+        // product_mds: my term, then the running sums over i inside segment j (inclusive scan, log2 W steps)
+        Fx<P> t = fx_cond_sub_p<P>(fx_mul<P>(s, m));
+#pragma unroll
+        for (int d = 1; d < W; d <<= 1) {
+            const Fx<P> o = fx_shfl<P>(t, lane - d);      // lane - d >= 0 whenever it is used (i >= d)
+            if (i >= d) t = fx_cond_sub_p<P>(fx_add<P>(t, o));
+        }
+        if (store) fe_store<P>(out + l, fx_pack<P>(t));
+        out += W * W;
+        // next state: element i = the last running sum of segment i
+        x = fx_shfl<P>(t, seg0 + i * W + (W - 1));
+    }
+    return x;
+}
+
 template <class P, int W>
 __global__ __launch_bounds__(256) void k_poseidon_gadget_lanes(PoseidonGadgetArgs<P> a) {
     static_assert(FxP<P>::L == 9 && FxP<P>::SH == 5, "scalar fields: nine limbs, R' = 32 R");
@@ -315,7 +360,6 @@ __global__ __launch_bounds__(256) void k_poseidon_gadget_lanes(PoseidonGadgetArg
     const uint64_t h = wave * PER_WAVE + sub;
     const bool have = h < a.batch;              // lanes without a hash run along (shuffles are wave-wide) and store nothing
     const uint64_t hh = have ? h : 0;
-    const int rounds = 2 * a.half_full + a.partial;
     const uint64_t per_hash = (uint64_t)2 * a.half_full * (3 * W + W * W) + (uint64_t)a.partial * (3 + W * W);
     const uint64_t base = a.trace_base ? (uint64_t)a.trace_base[hh] : a.base0 + hh * per_hash;
     bool ok = base <= a.n_vars && per_hash <= a.n_vars - base;
@@ -341,44 +385,151 @@ __global__ __launch_bounds__(256) void k_poseidon_gadget_lanes(PoseidonGadgetArg
     const bool run = have && (bad & mine) == 0;
     if (have && l == 0 && !run) atomicOr(a.status, 1u);
     const Fx<P> m = fx_load_limbs<P>(a.mds + 9 * (i * W + j));    // my matrix entry, H form, for every round
-    Fe<P>* out = a.vars + base;
-    const uint32_t* rc = a.rc_a + 9 * i;
-#pragma unroll 1
-    for (int r = 0; r < rounds; ++r) {
-        const bool full = r < a.half_full || r >= a.half_full + a.partial;
-        x = fx_cond_sub_p<P>(fx_add<P>(x, fx_load_limbs<P>(rc)));     // add_constant: no gate
-        rc += 9 * W;
-        // power_of_5 of my element; kept where the round has an s-box for it
-        const Fx<P> xs = fx_shl_sh<P>(x);
-        const Fx<P> x2 = gadget_mul<P>(x, xs);
-        const Fx<P> x4 = gadget_mul<P>(x2, fx_shl_sh<P>(x2));
-        const Fx<P> x5 = gadget_mul<P>(x4, xs);
-        const bool boxed = full || i == 0;
-        if (run && live && j == 0 && boxed) {
-            Fe<P>* o = out + 3 * i;
-            fe_store<P>(o, fx_pack<P>(x2));
-            fe_store<P>(o + 1, fx_pack<P>(x4));
-            fe_store<P>(o + 2, fx_pack<P>(x5));
-        }
-        out += full ? 3 * W : 3;
-        Fx<P> s;
-#pragma unroll
-        for (int k = 0; k < FxP<P>::L; ++k) s.l[k] = boxed ? x5.l[k] : x.l[k];
-        // product_mds: my term, then the running sums over i inside segment j (inclusive scan, log2 W steps)
-        Fx<P> t = fx_cond_sub_p<P>(fx_mul<P>(s, m));
-#pragma unroll
-        for (int d = 1; d < W; d <<= 1) {
-            const Fx<P> o = fx_shfl<P>(t, lane - d);      // lane - d >= 0 whenever it is used (i >= d)
-            if (i >= d) t = fx_cond_sub_p<P>(fx_add<P>(t, o));
-        }
-        if (run && live) fe_store<P>(out + l, fx_pack<P>(t));
-        out += W * W;
-        // next state: element i = the last running sum of segment i
-        x = fx_shfl<P>(t, seg0 + i * W + (W - 1));
-    }
+    x = poseidon_lanes_rounds<P, W>(x, m, a.rc_a + 9 * i, a.vars + base, run && live, a.half_full, a.partial, lane, seg0, l, i, j);
     if (a.out && run && l == 1 % W) {   // spec.rs:315: elements[1] (W >= 2: lane 1 holds element 1)
         fe_store<P>(a.out + h, fx_pack<P>(x));
     }
+}
+
+// ---- the Merkle-path gadget's witness ----------------------------------------------------------------------------------
+// merkle_proof (plonk-hashing/src/merkle/binary.rs:8-30) is a CHAIN: level k hashes the two conditional_selects of the
+// running hash of level k - 1 and the sibling.  One path per LPH lanes, in the layout above; the levels are walked inside
+// the kernel and the running hash stays in registers (element 1 of the final state, broadcast to the segment), so the
+// kernel never reads a variable it wrote.  Per level, in the proving composer's allocation order
+// (constraint_system/mod.rs:339-354 for each select, binary.rs:23-24 for their order):
+//     x_l = b s, y_l = (1 - b) cur, z_l = x_l + y_l,   x_r = b cur, y_r = (1 - b) s, z_r = x_r + y_r,
+// then the vars_per_hash variables of hash_two(z_l, z_r) (hasher/mod.rs:26-33: arity 2, state [tag, z_l, z_r, 0 ...]).
+// With b in {0, 1} the six are copies and zeros.  A path whose range, indices or bit values are not valid is skipped as a
+// whole, before its first store, and raises the status word.
+template <class P>
+struct MerklePathArgs {
+    const uint32_t* rc_a;      // round constants as A-form limbs (canonical)
+    const uint32_t* mds;       // H form, m[i][j] at (i * W + j)
+    uint32_t tag_a[FxP<P>::L];
+    Fe<P>* vars;               // the variable map
+    uint64_t n_vars;
+    const uint32_t* leaf_var;  // batch
+    const uint32_t* bit_vars;  // batch x height
+    const uint32_t* sibling_vars;
+    const uint32_t* path_base; // per path, or null: base0 + p * height * per_level
+    uint64_t base0;
+    Fe<P>* out;                // optional: batch roots
+    uint32_t* status;
+    uint64_t batch;
+    int half_full, partial, height;
+};
+
+// a plain variable's value; Variable::Zero reads as 0.  The index was validated (or the path does not run).
+template <class P>
+ZKT_D Fe<P> merkle_read(const Fe<P>* vars, uint32_t v, bool run) {
+    Fe<P> r;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) r.v[k] = 0;
+    if (run && v != ZKT_VARIABLE_ZERO) r = fe_load<P>(vars + v);
+    return r;
+}
+
+template <class P>
+ZKT_D bool fe_is_zero_words(const Fe<P>& a) {
+    uint32_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) acc |= a.v[k];
+    return acc == 0;
+}
+
+template <class P>
+ZKT_D bool fe_is_one_words(const Fe<P>& a) {   // R mod p: the canonical 1 of the map's form
+    uint32_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) acc |= a.v[k] ^ P::one(k);
+    return acc == 0;
+}
+
+template <class P, int W>
+__global__ __launch_bounds__(256) void k_poseidon_merkle_path(MerklePathArgs<P> a) {
+    static_assert(FxP<P>::L == 9 && FxP<P>::SH == 5, "scalar fields: nine limbs, R' = 32 R");
+    static_assert(W >= 3, "hash_two needs two input elements behind the tag");
+    static_assert(sizeof(Fe<P>) == 32, "a variable is eight 32-bit words");
+    constexpr int LPH = PoseidonLanes<W>::LPH, PER_WAVE = PoseidonLanes<W>::PER_WAVE;
+    static_assert(LPH >= 6, "one lane per select variable");
+    const int lane = threadIdx.x & 63;
+    const int sub = lane / LPH;                 // which path of this wavefront
+    const int l = lane % LPH;                   // lane inside the path
+    const int seg0 = lane - l;
+    const bool live = l < W * W;
+    const int i = live ? l % W : 0, j = live ? l / W : 0;
+    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint64_t pth = wave * PER_WAVE + sub;
+    const bool have = pth < a.batch;            // lanes without a path run along (shuffles are wave-wide) and store nothing
+    const uint64_t pp = have ? pth : 0;
+    const uint64_t per_hash = (uint64_t)2 * a.half_full * (3 * W + W * W) + (uint64_t)a.partial * (3 + W * W);
+    const uint64_t per_level = 6 + per_hash, span = (uint64_t)a.height * per_level;
+    const uint64_t base = a.path_base ? (uint64_t)a.path_base[pp] : a.base0 + pp * span;
+    const uint32_t* bit_idx = a.bit_vars + pp * (uint64_t)a.height;
+    const uint32_t* sib_idx = a.sibling_vars + pp * (uint64_t)a.height;
+    const uint32_t leaf_idx = a.leaf_var[pp];
+    // validation, all of it before the first store: the range, every index, every bit's value (the levels are dealt out
+    // to the lanes of the segment)
+    bool ok = base <= a.n_vars && span <= a.n_vars - base;
+    ok = ok && (leaf_idx == ZKT_VARIABLE_ZERO || leaf_idx < a.n_vars);
+    for (int k = l; k < a.height; k += LPH) {
+        const uint32_t bv = bit_idx[k], sv = sib_idx[k];
+        if (sv != ZKT_VARIABLE_ZERO && sv >= a.n_vars) ok = false;
+        if (bv != ZKT_VARIABLE_ZERO) {
+            if (bv >= a.n_vars) {
+                ok = false;
+            } else {
+                const Fe<P> b = fe_load<P>(a.vars + bv);
+                if (!fe_is_zero_words<P>(b) && !fe_is_one_words<P>(b)) ok = false;   // conditional_select asserts a bit
+            }
+        }
+    }
+    const unsigned long long bad = __ballot(have && !ok);
+    const unsigned long long mine = (LPH == 64) ? ~0ull : (((1ull << LPH) - 1ull) << seg0);
+    const bool run = have && (bad & mine) == 0;
+    if (have && l == 0 && !run) atomicOr(a.status, 1u);
+    const bool store = run && live;
+    const Fx<P> m = fx_load_limbs<P>(a.mds + 9 * (i * W + j));
+    Fx<P> tag;
+#pragma unroll
+    for (int k = 0; k < FxP<P>::L; ++k) tag.l[k] = a.tag_a[k];
+    Fe<P> cur = merkle_read<P>(a.vars, leaf_idx, run);            // the running hash, the same in every lane of the path
+    Fe<P>* out = a.vars + base;
+    // the bit and the sibling of the level ahead are fetched while the level in hand runs its rounds
+    Fe<P> sib = a.height > 0 ? merkle_read<P>(a.vars, sib_idx[0], run) : cur;
+    bool bit = a.height > 0 && !fe_is_zero_words<P>(merkle_read<P>(a.vars, bit_idx[0], run));
+#pragma unroll 1
+    for (int k = 0; k < a.height; ++k) {
+        const Fe<P> s = sib;
+        const bool b = bit;
+        if (k + 1 < a.height) {
+            sib = merkle_read<P>(a.vars, sib_idx[k + 1], run);
+            bit = !fe_is_zero_words<P>(merkle_read<P>(a.vars, bit_idx[k + 1], run));
+        }
+        // lanes 0 .. 5 hold x_l, y_l, z_l, x_r, y_r, z_r: each is s, cur or 0
+        const bool left = l < 3;
+        const int q = left ? l : l - 3;                       // 0: x = b * first, 1: y = (1 - b) * second, 2: z
+        const bool first_is_s = left;                         // select(b, s, cur) on the left, select(b, cur, s) on the right
+        const bool take_first = b ? q != 1 : false, take_second = b ? false : q != 0;
+        const bool take_s = first_is_s ? take_first : take_second, take_cur = first_is_s ? take_second : take_first;
+        Fe<P> sel, zl, zr;
+#pragma unroll
+        for (int w = 0; w < 8; ++w) {
+            sel.v[w] = take_s ? s.v[w] : take_cur ? cur.v[w] : 0u;
+            zl.v[w] = b ? s.v[w] : cur.v[w];
+            zr.v[w] = b ? cur.v[w] : s.v[w];
+        }
+        if (run && l < 6) fe_store<P>(out + l, sel);
+        // hash_two(z_l, z_r): state [tag, z_l, z_r, 0 ...]
+        Fx<P> x = fx_zero<P>();
+        if (i == 0) x = tag;
+        else if (i == 1) x = fx_unpack<P>(zl);
+        else if (i == 2) x = fx_unpack<P>(zr);
+        x = poseidon_lanes_rounds<P, W>(x, m, a.rc_a + 9 * i, out + 6, store, a.half_full, a.partial, lane, seg0, l, i, j);
+        cur = fx_pack<P>(fx_shfl<P>(x, seg0 + 1));            // elements[1] (spec.rs:315): lane 1 of the segment holds it
+        out += per_level;
+    }
+    if (a.out && run && l == 0) fe_store<P>(a.out + pth, cur);
 }
 
 }  // namespace zkt
@@ -524,6 +675,63 @@ static int poseidon_gadget_enqueue_t(zkt_ctx* c, const zkt_poseidon* h, const zk
     return ZKT_OK;
 }
 
+template <class P, int W>
+static void merkle_path_launch_w(zkt_ctx* c, const MerklePathArgs<P>& a) {
+    if constexpr (W >= 3) {
+        constexpr uint64_t per_block = 4 * PoseidonLanes<W>::PER_WAVE;    // 256 threads = 4 wavefronts
+        hipLaunchKernelGGL((k_poseidon_merkle_path<P, W>), dim3((unsigned)((a.batch + per_block - 1) / per_block)), dim3(256), 0,
+                           c->stream, a);
+    }
+}
+
+template <class P>
+static int merkle_path_enqueue_t(zkt_ctx* c, const zkt_poseidon* h, const zkt_merkle_path_args& g) {
+    MerklePathArgs<P> a{};
+    a.rc_a = (const uint32_t*)h->d_rc_a;
+    a.mds = (const uint32_t*)h->d_mds;
+    for (int i = 0; i < 9; ++i) a.tag_a[i] = h->tag_a[i];
+    a.vars = (Fe<P>*)g.d_variables;
+    a.n_vars = g.n_vars;
+    a.leaf_var = g.d_leaf_var;
+    a.bit_vars = g.d_bit_vars;
+    a.sibling_vars = g.d_sibling_vars;
+    a.path_base = g.d_path_base;
+    a.base0 = g.path_base0;
+    a.out = (Fe<P>*)g.d_out_roots;
+    a.status = (uint32_t*)h->d_status;
+    a.batch = g.batch;
+    a.half_full = h->half_full;
+    a.partial = h->partial;
+    a.height = g.height;
+    switch (h->width) {
+        case 3: merkle_path_launch_w<P, 3>(c, a); break;
+        case 4: merkle_path_launch_w<P, 4>(c, a); break;
+        case 5: merkle_path_launch_w<P, 5>(c, a); break;
+        case 6: merkle_path_launch_w<P, 6>(c, a); break;
+        case 7: merkle_path_launch_w<P, 7>(c, a); break;
+        default: merkle_path_launch_w<P, 8>(c, a); break;
+    }
+    ZKT_HIP(c, hipGetLastError());
+    return ZKT_OK;
+}
+
+// the argument rules zkt_poseidon_merkle_path_witness_dev and _validate share; *enqueue = 0 when there is nothing to do
+static int merkle_path_check_args(zkt_ctx* c, const zkt_poseidon* h, const zkt_merkle_path_args* g, bool* enqueue) {
+    *enqueue = false;
+    if (!c || !h || !g) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
+    if (h->curve != c->curve) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "poseidon parameters belong to another curve");
+    if (h->width < 3)
+        return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "merkle path: hash_two needs width >= 3 (spec.rs:253-257 FullBuffer)");
+    if (g->height < 0) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "merkle path: height >= 0");
+    if (g->batch == 0 || g->height == 0) return ZKT_OK;
+    if (!g->d_variables) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null variable map");
+    if (!g->d_leaf_var || !g->d_bit_vars || !g->d_sibling_vars)
+        return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "merkle path: null leaf, bit or sibling index vector");
+    if (g->n_vars > 0xFFFFFFFFull) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "variable indices are 32 bits wide");
+    *enqueue = true;
+    return ZKT_OK;
+}
+
 static int poseidon_check_params(zkt_ctx* c, const zkt_poseidon_params* p) {
     if (!p || !p->round_constants || !p->mds || !p->domain_tag) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
     // output_hash (spec.rs:267-316) always runs one full and one partial round before its `1..n` loops: a schedule with
@@ -654,6 +862,65 @@ int zkt_poseidon_gadget_validate(zkt_ctx* c, const zkt_poseidon* h, const zkt_po
     return ZKT_OK;
 }
 
+size_t zkt_merkle_path_vars_per_level(const zkt_poseidon* h) {
+    return h ? 6 + zkt_poseidon_gadget_vars_per_hash(h) : 0;
+}
+
+int zkt_poseidon_merkle_path_witness_dev(zkt_ctx* c, const zkt_poseidon* h, const zkt_merkle_path_args* g) {
+    bool enqueue;
+    if (int rc = merkle_path_check_args(c, h, g, &enqueue)) return rc;
+    if (!enqueue) return ZKT_OK;
+    const size_t span = (size_t)g->height * zkt_merkle_path_vars_per_level(h);
+    if (!g->d_path_base && (g->path_base0 > g->n_vars || g->batch > (g->n_vars - g->path_base0) / span))
+        return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "merkle path: the paths do not fit the variable map");
+    (void)hipSetDevice(c->device);
+    if (c->curve == ZKT_CURVE_BN254) return merkle_path_enqueue_t<Bn254Fr>(c, h, *g);
+    return merkle_path_enqueue_t<Bls381Fr>(c, h, *g);
+}
+
+// Host-side validation of one launch's structure (downloads the index vectors; synchronises): the ranges
+// [base, base + height * vars_per_level) must be pairwise disjoint and inside the map, and no leaf, bit or sibling index may
+// lie inside a range of the SAME launch (the kernel reads its inputs while other paths are being written).
+int zkt_poseidon_merkle_path_validate(zkt_ctx* c, const zkt_poseidon* h, const zkt_merkle_path_args* g) {
+    bool enqueue;
+    if (int rc = merkle_path_check_args(c, h, g, &enqueue)) return rc;
+    if (!enqueue) return ZKT_OK;
+    (void)hipSetDevice(c->device);
+    const size_t span = (size_t)g->height * zkt_merkle_path_vars_per_level(h), levels = g->batch * (size_t)g->height;
+    std::vector<uint64_t> base(g->batch);
+    std::vector<uint32_t> leaf(g->batch), bits(levels), sibs(levels);
+    if (g->d_path_base) {
+        std::vector<uint32_t> b32(g->batch);
+        ZKT_HIP(c, hipMemcpyAsync(b32.data(), g->d_path_base, g->batch * 4, hipMemcpyDeviceToHost, c->stream));
+        ZKT_HIP(c, hipStreamSynchronize(c->stream));
+        for (size_t i = 0; i < g->batch; ++i) base[i] = b32[i];
+    } else {
+        for (size_t i = 0; i < g->batch; ++i) base[i] = g->path_base0 + i * span;
+    }
+    ZKT_HIP(c, hipMemcpyAsync(leaf.data(), g->d_leaf_var, g->batch * 4, hipMemcpyDeviceToHost, c->stream));
+    ZKT_HIP(c, hipMemcpyAsync(bits.data(), g->d_bit_vars, levels * 4, hipMemcpyDeviceToHost, c->stream));
+    ZKT_HIP(c, hipMemcpyAsync(sibs.data(), g->d_sibling_vars, levels * 4, hipMemcpyDeviceToHost, c->stream));
+    ZKT_HIP(c, hipStreamSynchronize(c->stream));
+    std::sort(base.begin(), base.end());
+    for (size_t i = 0; i < base.size(); ++i) {
+        if (base[i] > g->n_vars || span > g->n_vars - base[i])
+            return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "merkle path: a path's range lies outside the variable map");
+        if (i && base[i] < base[i - 1] + span)
+            return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "merkle path: two paths' ranges of one launch overlap");
+    }
+    for (const std::vector<uint32_t>* idx : {&leaf, &bits, &sibs}) {
+        for (uint32_t v : *idx) {
+            if (v == 0xFFFFFFFFu) continue;   // Variable::Zero
+            if (v >= g->n_vars) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "merkle path: an input index lies outside the variable map");
+            auto it = std::upper_bound(base.begin(), base.end(), (uint64_t)v);
+            if (it != base.begin() && (uint64_t)v < *(it - 1) + span)
+                return set_err(c, ZKT_ERR_INVALID_ARGUMENT,
+                               "merkle path: an input is a variable the same launch writes (run it in a later launch)");
+        }
+    }
+    return ZKT_OK;
+}
+
 int zkt_poseidon_gadget_check(zkt_ctx* c, const zkt_poseidon* h) {
     if (!c || !h) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
     (void)hipSetDevice(c->device);
@@ -662,7 +929,8 @@ int zkt_poseidon_gadget_check(zkt_ctx* c, const zkt_poseidon* h) {
     ZKT_HIP(c, hipStreamSynchronize(c->stream));
     if (st) {
         ZKT_HIP(c, hipMemsetAsync(h->d_status, 0, 4, c->stream));
-        return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "poseidon gadget: a trace base or an input index lies outside the variable map");
+        return set_err(c, ZKT_ERR_INVALID_ARGUMENT,
+                       "poseidon gadget: a trace base or an input index lies outside the variable map, or a path's bit is not 0 or 1");
     }
     return ZKT_OK;
 }
