@@ -427,7 +427,21 @@ typedef struct {
  * Proof<F, D, KZG10<E>> (proof.rs:106-155): 802 bytes on BN254, 1010 on BLS12-381.  The transcript must
  * already be seeded by VerifierKey::seed_transcript (keys/mod.rs:260-275), as in plonk.rs:105-108.
  * Needs zkt_srs_load (>= n + 8 powers) and zkt_circuit_load.  Errors mirror the reference's Err / panics:
- * ZKT_ERR_NOT_IN_TABLE, ZKT_ERR_EQUAL_CHALLENGES, ZKT_ERR_ZERO_DENOMINATOR, ZKT_ERR_QUOTIENT_TOO_SHORT. */
+ * ZKT_ERR_NOT_IN_TABLE, ZKT_ERR_EQUAL_CHALLENGES, ZKT_ERR_ZERO_DENOMINATOR, ZKT_ERR_QUOTIENT_TOO_SHORT.
+ * Challenge values that are refused, as the reference refuses them (tests/forced_challenges.py holds the table):
+ *  - two of beta, gamma, delta, epsilon equal (any of the six pairs): ZKT_ERR_EQUAL_CHALLENGES, in round 3
+ *    (assert_ne!, prove.rs:202-207);
+ *  - a denominator of the permutation or the lookup grand product that vanishes at a row 0 .. n - 2 -- for one of the
+ *    three factors beta sigma_k(w^i) + wire_i + gamma, or for epsilon (1 + delta) + h1_i + delta h2_i or its neighbour;
+ *    epsilon = 0 and delta = -1 do wherever h1_i = h2_i = 0 resp. h1_i = h2_i, which the zeros of the padded table bring
+ *    about: ZKT_ERR_ZERO_DENOMINATOR, after the scans of round 3.  Row n - 1 enters no product: a zero there proves;
+ *  - alpha = 0, and beta = 0 with blinders (z1 = 1 is trimmed and its blinders land at X^1..X^3): the quotient is too short
+ *    or no polynomial, ZKT_ERR_QUOTIENT_TOO_SHORT, reported with the evaluations of round 5 (for beta = 0 the reference
+ *    fails later, committing q_hi, with TooManyCoefficients);
+ *  - xi = 1 (L_1(xi) divides by n (xi - 1)): ZKT_ERR_ZERO_DENOMINATOR, in round 5.
+ * Everything else is proved, in particular xi on the domain (Z_H(xi) = 0), xi w = 1, xi = 0 (the opening witnesses are then
+ * the combinations shifted down by one coefficient), eta in {0, 1}, alpha = 1, gamma = 0, delta = 0.  A refusal withdraws
+ * an announced successor (zkt_prove_set_next) and leaves the context ready for the next proof. */
 int zkt_prove(zkt_ctx* ctx, const zkt_prove_inputs* in, zkt_transcript* transcript, uint8_t* proof_out,
               size_t proof_cap, size_t* proof_len);
 /* Optional, for back-to-back proofs on one context: announces the inputs of the proof that will follow the next

@@ -976,7 +976,17 @@ struct Prover {
         void* work = S.poly[12];
         wait_end();
         if ((rc = poly_lincomb(c, lr, work, cap))) return rc;
-        if (fe_is_zero<R>(xi) || fe_is_zero<R>(shifted)) return set_err(c, ZKT_ERR_ZERO_DENOMINATOR, "evaluation challenge is zero");
+        // The witness of an opening at z is (p(X) - p(z)) / (X - z).  At z = 0 (xi = 0 makes both points zero; the reference
+        // proves there) that is p shifted down by one coefficient, and no power of 1/z is needed: one copy on the stream
+        // the opening uses.
+        auto witness = [&](const void* comb, const F& z, void* ta, void* tb, void* scan, void* out, void* pw) -> int {
+            if (fe_is_zero<R>(z)) {
+                ZKT_HIP(c, hipMemcpyAsync(out, (const char*)comb + 32, (cap - 1) * 32, hipMemcpyDeviceToDevice, c->stream));
+                return ZKT_OK;
+            }
+            const F zi = fe_inv_host<R>(z);
+            return open_witness(c, comb, cap, z.v, zi.v, ta, tb, scan, out, pw);
+        };
         Affine<Q> aw, saw;
         {
             LinCombArgs lo{};
@@ -990,8 +1000,7 @@ struct Prover {
             }
             void* comb = S.sc[0];  // n + 8 fits: sc buffers hold n + 8 elements
             if ((rc = poly_lincomb(c, lo, comb, cap))) return rc;
-            F zi = fe_inv_host<R>(xi);
-            if ((rc = open_witness(c, comb, cap, xi.v, zi.v, S.sc[1], S.sc[2], S.scan_tmp, S.sc[3], S.eval_pw))) return rc;
+            if ((rc = witness(comb, xi, S.sc[1], S.sc[2], S.scan_tmp, S.sc[3], S.eval_pw))) return rc;
         }
         // saw opening (prove.rs:427-451): (z1, z2, t, h1) at xi * omega.  Its linear combination and division depend on
         // nothing the first opening computes: on a single GPU they run on a second stream beside the first opening's
@@ -1012,9 +1021,7 @@ struct Prover {
             }
             int r2;
             if ((r2 = poly_lincomb(c, lo, comb2, cap))) return r2;
-            F zi = fe_inv_host<R>(shifted);
-            return open_witness(c, comb2, cap, shifted.v, zi.v, ta2, tb2, aux ? S.aux_scan_tmp : S.scan_tmp, out2,
-                                aux ? S.aux_pw : S.eval_pw);
+            return witness(comb2, shifted, ta2, tb2, aux ? S.aux_scan_tmp : S.scan_tmp, out2, aux ? S.aux_pw : S.eval_pw);
         };
         if (aux) {
             ZKT_HIP(c, hipEventRecord(S.ev_aux_go, c->stream));
@@ -1901,6 +1908,8 @@ int zkt_debug_grand_products(zkt_ctx* c, const uint64_t* challenges, const uint6
     if (!c->circuit) return set_err(c, ZKT_ERR_NOT_LOADED, "no circuit loaded (zkt_circuit_load)");
     (void)hipSetDevice(c->device);
     c->circuit->prefetch_stage = 0;   // the work buffers are shared with an announced proof's early rounds
+    // the caller's t replaces the evaluations of the cached table polynomial: the next proof rebuilds it
+    c->circuit->t_cached = false;
     if (c->curve == ZKT_CURVE_BN254) return debug_grand_products_t<Bn254Curve>(c, challenges, vectors, out_z1, out_z2);
     return debug_grand_products_t<Bls381Curve>(c, challenges, vectors, out_z1, out_z2);
 }
