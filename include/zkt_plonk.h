@@ -295,8 +295,32 @@ int zkt_kzg_open_dev(zkt_ctx* ctx, const void* const* d_coeffs, const size_t* le
  * Fallbacks, per wire, to the coefficient route: too many distinct variables; a T_v that is the identity (a degenerate
  * tau); a table that cannot be allocated; a blinded polynomial trimmed below n coefficients (a constant or all-Zero
  * wire: its blinders then sit below X^n; found with the digest, committed again).  Sharded keys and host-resident
- * witnesses keep dense wire commitments.  The proof bytes are the same on either route. */
+ * witnesses keep dense wire commitments.  The proof bytes are the same on either route.
+ *
+ * Wire polynomials over the circuit's free variables (measured on MI355X: docs/EXPERIMENTS.md; the kernel trace and
+ * counter passes of this route have not been run).  Most variables of
+ * a circuit are not free.  Walking the rows in ascending order, a row with q_m = 0 and q_o = 1 or -1 that is no
+ * public-input position of the proof, whose output is a real variable seen on no wire of an earlier row and on no input
+ * wire of this one, DEFINES that output as an affine function of earlier variables; a variable first seen anywhere else
+ * is free.  Substituting, x_v = kappa_v + sum_f M[v][f] x_f over free f (at most 16 terms: a longer form makes v free), so
+ *     commit(wire k) = sum_f x_f A^k_f + C^k + blinder terms,   A^k_f = sum_v M[v][f] T^k_v,   C^k = sum_v kappa_v T^k_v:
+ * one scalar per free variable that reaches the wire (the withdraw circuit at n = 2^20: 0.20 n, 0.11 n and 0.20 n bases
+ * on the left, right and output wire, against 0.83 n, 0.27 n and 1.00 n distinct variables; the tables are built inside
+ * the first proof that brings a wiring, 5.3 s there, 1.2 s at 2^18).
+ * THE ROUTE PRESUMES A WITNESS THAT SATISFIES THE CIRCUIT.  For such a witness the commitments are the same group elements
+ * and the proof the same bytes.  For any other witness the round-1 commitments may differ from the reference's; the
+ * quotient is still computed from the true wire polynomials, so such a proof is refused exactly as without the route
+ * (ZKT_ERR_QUOTIENT_TOO_SHORT).  Nothing is ever proved that the reference would not prove.
+ * Taken, per wire, on top of the rules above when the table has fewer than 0.9 of the bases the wire uses otherwise (the
+ * constant point counted); a point that has to be a base and is the identity, or a failed allocation, leaves the wire
+ * on its other route.  Built with the wire tables (host pass over the rows, then T^k_v of every variable and one
+ * double-and-add per non-zero of M on the device), keyed additionally on the proof's public-input positions, which
+ * every proof compares on the host: other positions rebuild the tables (a context whose forks read its tables commits
+ * densely instead).  Digest, trimmed-length fallback and fork rules are those of the wire tables.
+ * zkt_ctx_set_wire_elimination(ctx, mode): 0 = off, 1 = automatic (the default): circuits of 2^17 rows and more, where an
+ * MSM's time is its additions, 2 = whenever a table can be built.  Forks inherit the mode. */
 int zkt_ctx_set_lagrange(zkt_ctx* ctx, int on);
+int zkt_ctx_set_wire_elimination(zkt_ctx* ctx, int mode);
 /* *log_n = domain the table serves (-1: none, evaluations go through their coefficients), *bases = its points */
 int zkt_lagrange_info(zkt_ctx* ctx, int* log_n, size_t* bases);
 /* PC::commit of poly_from_evals(domain, evals) (util.rs:63-86) with k in 0..3 blinders added as add_blinders_to_poly
@@ -834,6 +858,24 @@ int zkt_debug_combine_split(zkt_ctx* ctx, const uint64_t* table, size_t table_le
 int zkt_debug_commit_wires_dev(zkt_ctx* ctx, const void* d_variables, size_t n_vars, const uint32_t* d_w_l, const uint32_t* d_w_r,
                                const uint32_t* d_w_o, size_t n_rows, const uint64_t* blinders, int route, uint64_t* out_xy_mont,
                                int* out_is_infinity, int* out_route);
+/* The same with route 2 as well: over the tables of the circuit's free variables, for a proof whose public inputs stand at
+ * pi_pos[0 .. n_pi) (host).  The loaded circuit's selectors define the rows, so the points equal route 0's only for a
+ * variable map that satisfies them; out_route[k] = 2 for a wire that went over free variables.  Routes 0 and 1 ignore
+ * pi_pos and behave as zkt_debug_commit_wires_dev. */
+int zkt_debug_commit_wires_pi_dev(zkt_ctx* ctx, const void* d_variables, size_t n_vars, const uint32_t* d_w_l, const uint32_t* d_w_r,
+                                  const uint32_t* d_w_o, size_t n_rows, const uint64_t* blinders, int route, const size_t* pi_pos,
+                                  size_t n_pi, uint64_t* out_xy_mont, int* out_is_infinity, int* out_route);
+/* The host pass behind the tables over free variables, alone; needs no device and no context.  selectors: q_m q_l q_r q_o
+ * q_c, n_rows x 4 Montgomery words each; w_l / w_r / w_o: n_rows indices each (ZKT_VARIABLE_ZERO allowed); pi_pos: the
+ * proof's public-input positions; K in 1 .. 64: the support cap (the prover uses 16).  Outputs, caller-allocated:
+ * out_kind[n_vars] (0 on no wire, 1 free, 2 defined), out_free[n_vars] (*out_n_free filled, in order of appearance), the
+ * terms (v, f, M[v][f]) in out_term_v / out_term_f / out_term_coef (capacity K x n_vars; 4 Montgomery words a
+ * coefficient; *out_n_terms filled; grouped by v in defining order, f ascending), out_kappa[n_vars x 4 words]
+ * (zero for a variable that is not defined). */
+int zkt_debug_wire_elimination(int curve, const uint64_t* const* selectors, const uint32_t* w_l, const uint32_t* w_r, const uint32_t* w_o,
+                               size_t n_rows, size_t n_vars, const size_t* pi_pos, size_t n_pi, int K, uint8_t* out_kind,
+                               uint32_t* out_free, size_t* out_n_free, uint32_t* out_term_v, uint32_t* out_term_f,
+                               uint64_t* out_term_coef, size_t* out_n_terms, uint64_t* out_kappa);
 /* kzg10's witness polynomial alone (row a12): out[0 .. len - 1) = (p(X) - p(z)) / (X - z) for the len <= n + 8 coefficients
  * p, as the prover computes it (scaled suffix sums).  Host pointers, Montgomery words. */
 int zkt_debug_open_witness(zkt_ctx* ctx, const uint64_t* coeffs, size_t len, const uint64_t* z4, uint64_t* out);

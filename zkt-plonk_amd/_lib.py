@@ -577,6 +577,39 @@ def g1_msm_host(curve, points, scalars, montgomery: bool = True) -> tuple:
     return out, bool(inf.value)
 
 
+def wire_elimination(curve, selectors, w_l, w_r, w_o, n_vars: int, pi_pos=(), K: int = 16):
+    """zkt_debug_wire_elimination: the host pass behind the wire tables over free variables (no device).  selectors: q_m q_l
+    q_r q_o q_c as (n_rows, 4) Montgomery words; w_*: n_rows uint32 indices (0xFFFFFFFF = Variable::Zero).  -> (kind (n_vars,)
+    uint8: 0 on no wire, 1 free, 2 defined; free (n_free,) uint32; term_v, term_f (n_terms,) uint32; term_coef (n_terms, 4)
+    Montgomery words; kappa (n_vars, 4) Montgomery words)."""
+    L = lib()
+    sel = [np.ascontiguousarray(q, dtype=np.uint64).reshape(-1, 4) for q in selectors]
+    w = [np.ascontiguousarray(x, dtype=np.uint32) for x in (w_l, w_r, w_o)]
+    n_rows = len(w[0])
+    assert len(sel) == 5 and all(q.shape[0] == n_rows for q in sel) and all(len(x) == n_rows for x in w)
+    pi = (ctypes.c_size_t * max(len(pi_pos), 1))(*[int(x) for x in pi_pos])
+    cap = max(K * n_vars, 1)
+    kind = np.zeros(max(n_vars, 1), dtype=np.uint8)
+    free = np.zeros(max(n_vars, 1), dtype=np.uint32)
+    tv, tf = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32)
+    tc = np.zeros((cap, 4), dtype=np.uint64)
+    kappa = np.zeros((max(n_vars, 1), 4), dtype=np.uint64)
+    n_free, n_terms = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    P64, P32 = ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)
+    sp = (P64 * 5)(*[u64p(q) for q in sel])
+    L.zkt_debug_wire_elimination.argtypes = [ctypes.c_int, ctypes.POINTER(P64), P32, P32, P32, ctypes.c_size_t, ctypes.c_size_t,
+                                             ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t, ctypes.c_int,
+                                             ctypes.POINTER(ctypes.c_uint8), P32, ctypes.POINTER(ctypes.c_size_t), P32, P32, P64,
+                                             ctypes.POINTER(ctypes.c_size_t), P64]
+    rc = L.zkt_debug_wire_elimination(curve_id(curve), sp, _u32p(w[0]), _u32p(w[1]), _u32p(w[2]), n_rows, n_vars, pi, len(pi_pos),
+                                      int(K), kind.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), _u32p(free), ctypes.byref(n_free),
+                                      _u32p(tv), _u32p(tf), u64p(tc), ctypes.byref(n_terms), u64p(kappa))
+    if rc:
+        raise ZktError(rc, "zkt_debug_wire_elimination")
+    nt = n_terms.value
+    return kind[:n_vars], free[:n_free.value].copy(), tv[:nt].copy(), tf[:nt].copy(), tc[:nt].copy(), kappa[:n_vars]
+
+
 class Transcript:
     """Built-in host transcript (T: TranscriptProtocol): kind 'merlin' (plonk-core/src/transcript.rs:46-109)
     or 'ethereum' (gadgets/src/transcript.rs:8-90).  Scalars / coordinates are canonical integers."""
@@ -1067,6 +1100,11 @@ class Context:
         self._L.zkt_ctx_set_lagrange.argtypes = [ctypes.c_void_p, ctypes.c_int]
         self.check(self._L.zkt_ctx_set_lagrange(self._h, int(on)))
 
+    def set_wire_elimination(self, mode: int = 1):
+        """zkt_ctx_set_wire_elimination: 0 off, 1 automatic (circuits of 2^17 rows and more), 2 whenever a table can be built"""
+        self._L.zkt_ctx_set_wire_elimination.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        self.check(self._L.zkt_ctx_set_wire_elimination(self._h, int(mode)))
+
     def lagrange_info(self):
         self._L.zkt_lagrange_info.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_size_t)]
         lg, nb = ctypes.c_int(0), ctypes.c_size_t(0)
@@ -1307,14 +1345,28 @@ class Context:
         return h1, h2
 
     def debug_commit_wires_dev(self, d_variables: int, n_vars: int, d_w_l: int, d_w_r: int, d_w_o: int, n_rows: int, blinders,
-                               route: int = 1):
+                               route: int = 1, pi_pos=None):
         """zkt_debug_commit_wires_dev: the prover's round-1 commitments of the three wires for a variable map and index
         vectors in HBM (device addresses).  blinders (6, 4).  -> (xy (3, 2*fq_limbs) Montgomery limbs, is_infinity (3,),
-        route taken (3,): 1 = over the wire's base table)."""
+        route taken (3,): 1 = over the wire's base table, 2 = over its table of free variables).  route 2, or any route with
+        pi_pos (the proof's public-input positions), goes through zkt_debug_commit_wires_pi_dev."""
         bl = np.ascontiguousarray(blinders, dtype=np.uint64).reshape(6, 4)
         out = np.zeros((3, 2 * self.fq_limbs), dtype=np.uint64)
         inf = (ctypes.c_int * 3)()
         took = (ctypes.c_int * 3)()
+        if route == 2 or pi_pos is not None:
+            pos = [int(x) for x in (pi_pos or ())]
+            pi = (ctypes.c_size_t * max(len(pos), 1))(*pos)
+            self._L.zkt_debug_commit_wires_pi_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                                              ctypes.POINTER(ctypes.c_uint64), ctypes.c_int,
+                                                              ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t,
+                                                              ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int),
+                                                              ctypes.POINTER(ctypes.c_int)]
+            self.check(self._L.zkt_debug_commit_wires_pi_dev(self._h, ctypes.c_void_p(d_variables), n_vars, ctypes.c_void_p(d_w_l),
+                                                             ctypes.c_void_p(d_w_r), ctypes.c_void_p(d_w_o), n_rows, u64p(bl),
+                                                             int(route), pi, len(pos), u64p(out), inf, took))
+            return out, [bool(x) for x in inf], [int(x) for x in took]
         self._L.zkt_debug_commit_wires_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
                                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
                                                        ctypes.POINTER(ctypes.c_uint64), ctypes.c_int,

@@ -204,6 +204,15 @@ static unsigned ck_blocks(size_t n) {
     return (unsigned)std::min<size_t>(std::max<size_t>((n + per - 1) / per, 1), CK_MAX_BLOCKS);
 }
 
+int selector_evals_enqueue(zkt_ctx* c, int log_n, const void* const* pk, void* const* outs) {
+    const size_t n = (size_t)1 << log_n;
+    size_t lens[5];
+    for (size_t& l : lens) l = n;   // the key's buffers hold n coefficients, zero above their length
+    static_assert(NTT_MAX_BATCH >= 4, "four selectors in one batch");
+    if (int rc = ntt_run_batch(c, log_n, 0, 0, 4, pk, lens, outs)) return rc;
+    return ntt_run_batch(c, log_n, 0, 0, 1, pk + 4, lens + 4, outs + 4);
+}
+
 template <class P>
 static int witness_check_t(zkt_ctx* c, const WitnessCheckKeys& K, const zkt_prove_inputs& in, int flags, zkt_witness_report* out) {
     using F = Fe<P>;
@@ -317,18 +326,9 @@ static int witness_check_t(zkt_ctx* c, const WitnessCheckKeys& K, const zkt_prov
 
     {
         ProfScope prof(c, "check_witness");
-        // selector evaluations: fft(n) of the key's coefficients, four transforms in one launch per pass, then q_c
-        const void* ins[5];
         void* outs[5];
-        size_t lens[5];
-        for (int k = 0; k < 5; ++k) {
-            ins[k] = K.pk[k];
-            lens[k] = n;   // the key's buffers hold n coefficients, zero above their length
-            outs[k] = base + o_sel[k];
-        }
-        static_assert(NTT_MAX_BATCH >= 4, "four selectors in one batch");
-        if ((rc = ntt_run_batch(c, log_n, 0, 0, 4, ins, lens, outs))) return rc;
-        if ((rc = ntt_run_batch(c, log_n, 0, 0, 1, ins + 4, lens + 4, outs + 4))) return rc;
+        for (int k = 0; k < 5; ++k) outs[k] = base + o_sel[k];
+        if ((rc = selector_evals_enqueue(c, log_n, K.pk, outs))) return rc;
 
         if (vars) {
             hipLaunchKernelGGL((k_check_gates<P, true>), dim3(ck_blocks(n)), dim3(CK_THREADS), 0, c->stream, q);

@@ -82,6 +82,7 @@ struct zkt_ctx {
     bool aux_off = false;          // A/B builds: ZKT_NO_AUX keeps round 5's second opening on the main stream
     bool batch_off = false;        // A/B builds: ZKT_MSM_NO_BATCH commits a round's polynomials one launch sequence each
     bool lagrange_off = false;     // zkt_ctx_set_lagrange(ctx, 0): evaluations are committed through their coefficients
+    int wire_elim_mode = 1;        // zkt_ctx_set_wire_elimination: 0 off, 1 automatic (large circuits), 2 whenever a table can be built
     std::shared_ptr<zkt::CircuitState> circuit;
     std::vector<void*> owned;  // every hipMalloc made on behalf of this ctx
 };

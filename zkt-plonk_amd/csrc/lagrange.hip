@@ -22,9 +22,13 @@
 #include "ec.hpp"
 #include "hostec.hpp"
 #include "msm.hpp"
+#include "poly.hpp"
+#include "wire_elim.hpp"
 
 #include <algorithm>
+#include <chrono>
 #include <cstdio>
+#include <cstring>
 #include <cstdlib>
 #include <vector>
 
@@ -372,12 +376,13 @@ __global__ __launch_bounds__(256) void k_wire_digest(const uint32_t* w0, const u
     }
 }
 
-// s[j] = variables[u[j]] / n for the distinct variables, then the wire's two blinders (as lagrange_scalars places them)
+// s[j] = variables[u[j]] / n for the cnt variables of the table, then 1 / n for the constant point of a table over free
+// variables (extra = 1, else 0), then the wire's two blinders (as lagrange_scalars places them)
 template <class P>
-__global__ void k_wire_scalars(const Fe<P>* vars, const uint32_t* u, size_t cnt, const Fe<P>* bl, Fe<P> ninv, Fe<P>* out) {
+__global__ void k_wire_scalars(const Fe<P>* vars, const uint32_t* u, size_t cnt, size_t extra, const Fe<P>* bl, Fe<P> ninv, Fe<P>* out) {
     const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= cnt + 2) return;
-    fe_store<P>(out + j, j < cnt ? fe_mul<P>(fe_load<P>(vars + u[j]), ninv) : fe_load<P>(bl + (j - cnt)));
+    if (j >= cnt + extra + 2) return;
+    fe_store<P>(out + j, j < cnt ? fe_mul<P>(fe_load<P>(vars + u[j]), ninv) : j < cnt + extra ? ninv : fe_load<P>(bl + (j - cnt - extra)));
 }
 
 void wire_bases_drop(zkt_ctx* c) {
@@ -409,62 +414,93 @@ static int wire_digest_enqueue(zkt_ctx* c, const uint32_t* const* d_idx, size_t 
     return ZKT_OK;
 }
 
+// a wire's rows grouped by variable: the counts come from the device, their scan is the host's
+struct WireGroups {
+    void *d_cnt = nullptr, *d_start = nullptr, *d_grouped = nullptr, *d_ofs = nullptr, *d_bad = nullptr;
+    std::vector<uint32_t> start;   // per variable: the first slot of its rows
+    std::vector<uint32_t> u, ofs;  // the distinct variables, ascending, and the first slot of each (d + 1 entries)
+    size_t d = 0;
+    uint32_t at = 0;               // rows that carry a variable
+};
+static void wire_groups_free(zkt_ctx* c, WireGroups& g) {
+    dev_free(c, g.d_cnt); dev_free(c, g.d_start); dev_free(c, g.d_grouped); dev_free(c, g.d_ofs); dev_free(c, g.d_bad);
+    g = WireGroups{};
+}
+// false: an allocation or a copy failed.  Synchronises the stream.
+static bool wire_groups_count(zkt_ctx* c, const uint32_t* d_idx, size_t n_rows, size_t n_vars, WireGroups& g) {
+    if (dev_alloc(c, &g.d_cnt, (n_vars + 1) * 4)) return false;
+    if (hipMemsetAsync(g.d_cnt, 0, (n_vars + 1) * 4, c->stream) != hipSuccess) return false;
+    const unsigned rb = (unsigned)((n_rows + 255) / 256);
+    if (n_rows) hipLaunchKernelGGL(k_wire_count, dim3(rb), dim3(256), 0, c->stream, d_idx, n_rows, (uint32_t)n_vars, (uint32_t*)g.d_cnt);
+    g.start.assign(n_vars + 1, 0);
+    if (hipMemcpyAsync(g.start.data(), g.d_cnt, n_vars * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess)
+        return false;
+    uint32_t at = 0;
+    for (size_t v = 0; v < n_vars; ++v) {
+        const uint32_t m = g.start[v];
+        g.start[v] = at;
+        if (m) {
+            g.u.push_back((uint32_t)v);
+            g.ofs.push_back(at);
+            at += m;
+        }
+    }
+    g.ofs.push_back(at);
+    g.at = at;
+    g.d = g.u.size();
+    return true;
+}
+// out[j] = T of g.u[j], j < g.d, as an affine point in arkworks form.  false: a failure, or a T_v that is the identity (a
+// degenerate tau).  Synchronises the stream.
+template <class C>
+static bool wire_points(zkt_ctx* c, const uint32_t* d_idx, size_t n_rows, size_t n_vars, WireGroups& g, Affine<typename C::Fq>* out) {
+    using Q = typename C::Fq;
+    MsmState& st = *c->msm;
+    const size_t d = g.d;
+    if (dev_alloc(c, &g.d_start, (n_vars + 1) * 4) || dev_alloc(c, &g.d_grouped, ((size_t)g.at + 1) * 4) ||
+        dev_alloc(c, &g.d_ofs, (d + 1) * 4) || dev_alloc(c, &g.d_bad, 4))
+        return false;
+    if (hipMemcpyAsync(g.d_start, g.start.data(), n_vars * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(g.d_ofs, g.ofs.data(), (d + 1) * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipMemsetAsync(g.d_cnt, 0, (n_vars + 1) * 4, c->stream) != hipSuccess || hipMemsetAsync(g.d_bad, 0, 4, c->stream) != hipSuccess)
+        return false;
+    const unsigned rb = (unsigned)((n_rows + 255) / 256);
+    if (n_rows)
+        hipLaunchKernelGGL(k_wire_fill, dim3(rb), dim3(256), 0, c->stream, d_idx, n_rows, (uint32_t)n_vars, (const uint32_t*)g.d_start,
+                           (uint32_t*)g.d_cnt, (uint32_t*)g.d_grouped);
+    if (d)
+        hipLaunchKernelGGL(k_wire_sum<C>, dim3((unsigned)((d + 63) / 64)), dim3(64), 0, c->stream, (const Affine<Q>*)st.table2,
+                           (const uint32_t*)g.d_grouped, (const uint32_t*)g.d_ofs, d, out, (uint32_t*)g.d_bad);
+    uint32_t bad = 0;
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&bad, g.d_bad, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess)   // (the staging vectors may go after this)
+        return false;
+    return bad == 0;
+}
+
 template <class C>
 static int wire_bases_build_wire(zkt_ctx* c, int log_n, int k, const uint32_t* d_idx, size_t n_rows, size_t n_vars, double frac) {
     using Q = typename C::Fq;
     MsmState& st = *c->msm;
     WireBases& wb = st.wb;
     const size_t n = (size_t)1 << log_n;
-    void *d_cnt = nullptr, *d_start = nullptr, *d_grouped = nullptr, *d_ofs = nullptr, *d_bad = nullptr, *table = nullptr, *d_u = nullptr;
+    WireGroups g;
+    void *table = nullptr, *d_u = nullptr;
     auto done = [&](bool keep) {   // a wire that cannot have its table is committed through its coefficients: never an error
-        dev_free(c, d_cnt); dev_free(c, d_start); dev_free(c, d_grouped); dev_free(c, d_ofs); dev_free(c, d_bad);
+        wire_groups_free(c, g);
         if (!keep) { dev_free(c, table); dev_free(c, d_u); }
         (void)hipGetLastError();
         return ZKT_OK;
     };
-    if (dev_alloc(c, &d_cnt, (n_vars + 1) * 4)) return done(false);
-    ZKT_HIP(c, hipMemsetAsync(d_cnt, 0, (n_vars + 1) * 4, c->stream));
-    const unsigned rb = (unsigned)((n_rows + 255) / 256);
-    if (n_rows) hipLaunchKernelGGL(k_wire_count, dim3(rb), dim3(256), 0, c->stream, d_idx, n_rows, (uint32_t)n_vars, (uint32_t*)d_cnt);
-    std::vector<uint32_t> cnt(n_vars + 1);
-    if (hipMemcpyAsync(cnt.data(), d_cnt, n_vars * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        hipStreamSynchronize(c->stream) != hipSuccess)
-        return done(false);
-    std::vector<uint32_t> u, ofs;
-    uint32_t at = 0;
-    for (size_t v = 0; v < n_vars; ++v) {
-        const uint32_t m = cnt[v];
-        cnt[v] = at;             // becomes start[v]
-        if (m) {
-            u.push_back((uint32_t)v);
-            ofs.push_back(at);
-            at += m;
-        }
-    }
-    ofs.push_back(at);
-    const size_t d = u.size();
+    if (!wire_groups_count(c, d_idx, n_rows, n_vars, g)) return done(false);
+    const size_t d = g.d;
     if ((double)d >= frac * (double)n_rows || (uint64_t)st.plan.W * (d + 2) >= ((uint64_t)1 << 31)) return done(false);
-    if (dev_alloc(c, &table, (size_t)st.plan.W * (d + 2) * sizeof(Affine<Q>)) || dev_alloc(c, &d_u, (d + 1) * 4) ||
-        dev_alloc(c, &d_start, (n_vars + 1) * 4) || dev_alloc(c, &d_grouped, ((size_t)at + 1) * 4) || dev_alloc(c, &d_ofs, (d + 1) * 4) ||
-        dev_alloc(c, &d_bad, 4))
-        return done(false);
-    ZKT_HIP(c, hipMemcpyAsync(d_start, cnt.data(), n_vars * 4, hipMemcpyHostToDevice, c->stream));
-    ZKT_HIP(c, hipMemcpyAsync(d_u, u.data(), d * 4, hipMemcpyHostToDevice, c->stream));
-    ZKT_HIP(c, hipMemcpyAsync(d_ofs, ofs.data(), (d + 1) * 4, hipMemcpyHostToDevice, c->stream));
-    ZKT_HIP(c, hipMemsetAsync(d_cnt, 0, (n_vars + 1) * 4, c->stream));
-    ZKT_HIP(c, hipMemsetAsync(d_bad, 0, 4, c->stream));
-    if (n_rows)
-        hipLaunchKernelGGL(k_wire_fill, dim3(rb), dim3(256), 0, c->stream, d_idx, n_rows, (uint32_t)n_vars, (const uint32_t*)d_start,
-                           (uint32_t*)d_cnt, (uint32_t*)d_grouped);
-    if (d)
-        hipLaunchKernelGGL(k_wire_sum<C>, dim3((unsigned)((d + 63) / 64)), dim3(64), 0, c->stream, (const Affine<Q>*)st.table2,
-                           (const uint32_t*)d_grouped, (const uint32_t*)d_ofs, d, (Affine<Q>*)table, (uint32_t*)d_bad);
+    if (dev_alloc(c, &table, (size_t)st.plan.W * (d + 2) * sizeof(Affine<Q>)) || dev_alloc(c, &d_u, (d + 1) * 4)) return done(false);
+    if (hipMemcpyAsync(d_u, g.u.data(), d * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess) return done(false);
+    if (!wire_points<C>(c, d_idx, n_rows, n_vars, g, (Affine<Q>*)table)) return done(false);
     hipLaunchKernelGGL(k_wire_blinder_points<C>, dim3(1), dim3(64), 0, c->stream, (const Affine<Q>*)st.table2, n, d, (Affine<Q>*)table);
-    uint32_t bad = 0;
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        hipStreamSynchronize(c->stream) != hipSuccess)   // (the staging vectors may go after this)
-        return done(false);
-    if (bad || msm_table_finish(c, table, d + 2)) return done(false);
+    if (hipGetLastError() != hipSuccess || msm_table_finish(c, table, d + 2)) return done(false);
     wb.table[k] = table;
     wb.u[k] = (uint32_t*)d_u;
     wb.cnt[k] = d;
@@ -472,15 +508,291 @@ static int wire_bases_build_wire(zkt_ctx* c, int log_n, int k, const uint32_t* d
     return done(true);
 }
 
-int wire_bases_prepare(zkt_ctx* c, int log_n, const uint32_t* const* d_idx, size_t n_rows, size_t n_vars) {
+// ---- wire tables over the circuit's free variables -------------------------------------------------------------
+// Most variables of a circuit are not free: a row with q_m = 0 and q_o = +-1 whose output appears there for the first time
+// DEFINES it as an affine function of earlier variables (wire_elim.hpp: the host pass, once per wiring, public-input
+// positions, circuit and key).  With x_v = kappa_v + sum_f M[v][f] x_f over the free variables f,
+//     commit(wire k) = sum_v x_v T^k_v + blinder terms = sum_f x_f A^k_f + C^k + blinder terms,
+//     A^k_f = sum_v M[v][f] T^k_v  (f itself with coefficient 1),   C^k = sum_v kappa_v T^k_v :
+// one scalar per free variable that reaches the wire, and one for the constant point.  The same group element WHENEVER THE
+// WITNESS SATISFIES THE DEFINING ROWS; for any other witness the proof is refused as before, because the quotient is
+// still made from the true wire polynomials (status bit 2).
+// Build, per wire: T^k_v of every distinct variable (the kernels above; no threshold); the terms of every free variable
+// -- and those of the constant point, which is one more group -- cut into pieces of WIRE_FOLD_PIECE, one thread per piece
+// multiplying each T^k_v by its full-size coefficient (double-and-add, as k_lag_level) and summing (a variable that
+// nearly every row reaches would otherwise be one thread's work); one thread per group adding its pieces; the blinder
+// points; msm_table_finish.  The table holds the A^k_f
+// of the free variables that reach the wire, then C^k unless it is the identity, then the two blinder points.  A wire
+// keeps its present route (its per-variable table, or its coefficients) when a point that has to be a base is the
+// identity, when an allocation fails, or when its base count would be WIRE_BASES_MAX_FRAC or more of what it uses now.
+constexpr uint32_t WIRE_NONE = 0xFFFFFFFFu;
+constexpr uint32_t WIRE_FOLD_PIECE = 32;
+
+// sum over the entries [lo, hi) of coefficient x T of the entry's variable; variables that are not on this wire are skipped
+template <class C>
+ZKT_D Xyzz<typename C::Fq> wire_fold_range(const Affine<typename C::Fq>* T, const uint32_t* pos, const uint32_t* ent_v,
+                                           const Fe<typename C::Fr>* ent_c, uint32_t lo, uint32_t hi) {
+    using Q = typename C::Fq;
+    using R = typename C::Fr;
+    const Fe<R> one = fe_one<R>();
+    Xyzz<Q> acc = xyzz_identity<Q>();
+#pragma unroll 1
+    for (uint32_t e = lo; e < hi; ++e) {
+        const uint32_t j = pos[ent_v[e]];
+        if (j == WIRE_NONE) continue;
+        const Affine<Q> p = aff_load<Q>(T + j);   // never the identity: k_wire_sum reports one and the wire is left alone
+        const Fe<R> cm = fe_load<R>(ent_c + e);
+        if (fe_eq<R>(cm, one)) acc = xyzz_add_mixed<Q>(acc, p);
+        else acc = xyzz_add<Q>(acc, xyzz_scalar_mul<Q, R>(xyzz_from_affine<Q>(p), fe_from_mont<R>(cm)));
+    }
+    return acc;
+}
+// part[t] = the sum over piece t = the entries [piece[t].x, piece[t].y)
+template <class C>
+__global__ __launch_bounds__(64) void k_wire_fold(const Affine<typename C::Fq>* T, const uint32_t* pos, const uint32_t* ent_v,
+                                                   const Fe<typename C::Fr>* ent_c, const uint2* piece, size_t np,
+                                                   Xyzz<typename C::Fq>* part) {
+    using Q = typename C::Fq;
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= np) return;
+    const uint2 pc = piece[t];
+    xyzz_store<Q>(part + t, wire_fold_range<C>(T, pos, ent_v, ent_c, pc.x, pc.y));
+}
+// out[j] = the sum of the pieces [pstart[j], pstart[j + 1]) of group j, affine.  The first cnt groups are free variables:
+// flags[0] is set when one of their points is the identity.  A group behind them is the constant point: flags[1] is set
+// when it is NOT the identity.
+template <class C>
+__global__ __launch_bounds__(64) void k_wire_fold_sum(const Xyzz<typename C::Fq>* part, const uint32_t* pstart, size_t cnt, size_t groups,
+                                                       Affine<typename C::Fq>* out, uint32_t* flags) {
+    using Q = typename C::Fq;
+    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= groups) return;
+    Xyzz<Q> acc = xyzz_identity<Q>();
+#pragma unroll 1
+    for (uint32_t t = pstart[j]; t < pstart[j + 1]; ++t) acc = xyzz_add<Q>(acc, xyzz_load<Q>(part + t));
+    const bool none = xyzz_is_identity<Q>(acc);
+    if (j < cnt ? none : !none) atomicOr(flags + (j < cnt ? 0 : 1), 1u);
+    aff_store<Q>(out + j, xyzz_to_affine<Q>(acc));
+}
+
+// what the host pass leaves for the three wires: the forms grouped by free variable (group g = free variable free_vars[g]:
+// itself with coefficient 1, then every defined variable that holds it), then one group of the constants (kappa_v per
+// defined variable that has one); ofs has free_vars.size() + 2 entries
+struct WireElimShared {
+    std::vector<uint32_t> free_vars, ofs, ent_v;
+    size_t n_defined = 0, n_const = 0;
+    void *d_ent_v = nullptr, *d_ent_c = nullptr;
+};
+static void wire_elim_shared_free(zkt_ctx* c, WireElimShared& D) {
+    dev_free(c, D.d_ent_v); dev_free(c, D.d_ent_c);
+    D = WireElimShared{};
+}
+
+// The host pass: selector evaluations and index vectors to the host, the elimination, the transposed forms to the device.
+// false: it could not be done (memory); the wires then keep their present routes.
+template <class C>
+static bool wire_elim_host(zkt_ctx* c, int log_n, const uint32_t* const* d_idx, size_t n_rows, size_t n_vars, const WireElimKeys& ew,
+                           WireElimShared& D) {
+    using R = typename C::Fr;
+    using F = Fe<R>;
+    const size_t n = (size_t)1 << log_n;
+    void* d_sel[5] = {};
+    std::vector<F> sel_h[5];
+    std::vector<uint32_t> w_h[3];
+    bool ok = true;
+    for (int k = 0; k < 5 && ok; ++k) ok = dev_alloc(c, &d_sel[k], n * sizeof(F)) == ZKT_OK;
+    if (ok) ok = selector_evals_enqueue(c, log_n, ew.pk, d_sel) == ZKT_OK;
+    for (int k = 0; k < 5 && ok; ++k) {
+        sel_h[k].resize(n_rows);
+        ok = hipMemcpyAsync(sel_h[k].data(), d_sel[k], n_rows * sizeof(F), hipMemcpyDeviceToHost, c->stream) == hipSuccess;
+    }
+    for (int k = 0; k < 3 && ok; ++k) {
+        w_h[k].resize(n_rows);
+        ok = hipMemcpyAsync(w_h[k].data(), d_idx[k], n_rows * 4, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
+    }
+    if (hipStreamSynchronize(c->stream) != hipSuccess) ok = false;
+    for (void* p : d_sel) dev_free(c, p);
+    if (!ok) {
+        (void)hipGetLastError();
+        return false;
+    }
+    WireElim<R> E;
+    {
+        const F* sp[5] = {sel_h[0].data(), sel_h[1].data(), sel_h[2].data(), sel_h[3].data(), sel_h[4].data()};
+        const uint32_t* wp[3] = {w_h[0].data(), w_h[1].data(), w_h[2].data()};
+        wire_eliminate<R>(sp, wp, n_rows, n_vars, ew.pi_pos, ew.n_pi, WIRE_ELIM_K, E);
+    }
+    const size_t nf = E.free_vars.size(), nd = E.def_vars.size();
+    if (!nf || !nd) return false;   // nothing is defined: the per-variable tables are the best there is
+    size_t nk = 0;
+    for (const F& k : E.kappa) nk += !fe_is_zero<R>(k);
+    const uint64_t total = (uint64_t)nf + E.term_f.size() + nk;
+    if (total >= 0xFFFFFFFFull) return false;
+    std::vector<uint32_t> fid(n_vars, 0), cur(nf + 1, 0);
+    for (size_t g = 0; g < nf; ++g) fid[E.free_vars[g]] = (uint32_t)g;
+    D.ofs.assign(nf + 2, 0);
+    for (size_t g = 0; g < nf; ++g) D.ofs[g + 1] = 1;
+    for (uint32_t f : E.term_f) ++D.ofs[fid[f] + 1];
+    D.ofs[nf + 1] = (uint32_t)nk;
+    for (size_t g = 0; g <= nf; ++g) D.ofs[g + 1] += D.ofs[g];
+    D.ent_v.resize(total);
+    std::vector<F> ent_c(total);
+    const F one = fe_one<R>();
+    for (size_t g = 0; g < nf; ++g) {
+        cur[g] = D.ofs[g];
+        D.ent_v[cur[g]] = E.free_vars[g];
+        ent_c[cur[g]++] = one;
+    }
+    cur[nf] = D.ofs[nf];
+    for (size_t d = 0; d < nd; ++d) {
+        for (uint64_t t = E.def_start[d]; t < E.def_start[d + 1]; ++t) {
+            const uint32_t g = fid[E.term_f[t]];
+            D.ent_v[cur[g]] = E.def_vars[d];
+            ent_c[cur[g]++] = E.term_c[t];
+        }
+        if (!fe_is_zero<R>(E.kappa[d])) {
+            D.ent_v[cur[nf]] = E.def_vars[d];
+            ent_c[cur[nf]++] = E.kappa[d];
+        }
+    }
+    D.free_vars.swap(E.free_vars);
+    D.n_defined = nd;
+    D.n_const = nk;
+    ok = !dev_alloc(c, &D.d_ent_v, total * 4) && !dev_alloc(c, &D.d_ent_c, total * sizeof(F));
+    ok = ok && hipMemcpyAsync(D.d_ent_v, D.ent_v.data(), total * 4, hipMemcpyHostToDevice, c->stream) == hipSuccess &&
+         hipMemcpyAsync(D.d_ent_c, ent_c.data(), total * sizeof(F), hipMemcpyHostToDevice, c->stream) == hipSuccess;
+    if (hipStreamSynchronize(c->stream) != hipSuccess) ok = false;   // the staging vectors go with this frame
+    if (!ok) {
+        (void)hipGetLastError();
+        wire_elim_shared_free(c, D);
+    }
+    return ok;
+}
+
+// true: wire k got its table over free variables; false: it keeps its present route (nothing of it is left behind)
+template <class C>
+static bool wire_elim_build_wire(zkt_ctx* c, int log_n, int k, const uint32_t* d_idx, size_t n_rows, size_t n_vars, double frac,
+                                 const WireElimShared& D, size_t* nonzeros) {
+    using Q = typename C::Fq;
+    using R = typename C::Fr;
+    MsmState& st = *c->msm;
+    WireBases& wb = st.wb;
+    const size_t n = (size_t)1 << log_n;
+    WireGroups g;
+    void *d_T = nullptr, *d_pos = nullptr, *d_piece = nullptr, *d_pstart = nullptr, *d_part = nullptr, *d_flag = nullptr, *table = nullptr,
+         *d_u = nullptr;
+    auto done = [&](bool keep) {
+        wire_groups_free(c, g);
+        dev_free(c, d_T); dev_free(c, d_pos); dev_free(c, d_piece); dev_free(c, d_pstart); dev_free(c, d_part); dev_free(c, d_flag);
+        if (!keep) { dev_free(c, table); dev_free(c, d_u); }
+        (void)hipGetLastError();
+        return keep;
+    };
+    *nonzeros = 0;
+    if (!wire_groups_count(c, d_idx, n_rows, n_vars, g)) return done(false);
+    const size_t d = g.d;
+    if (!d) return done(false);
+    const size_t present = (double)d < frac * (double)n_rows ? d : n_rows;   // bases of its present route
+    std::vector<uint32_t> pos(n_vars, WIRE_NONE), u, pstart(1, 0);
+    std::vector<uint2> piece;
+    for (size_t j = 0; j < d; ++j) pos[g.u[j]] = (uint32_t)j;
+    const size_t nf = D.free_vars.size();
+    auto cut = [&](size_t grp) {   // the pieces of a group
+        for (uint32_t lo = D.ofs[grp]; lo < D.ofs[grp + 1]; lo += WIRE_FOLD_PIECE)
+            piece.push_back(make_uint2(lo, std::min(lo + WIRE_FOLD_PIECE, D.ofs[grp + 1])));
+        pstart.push_back((uint32_t)piece.size());
+    };
+    for (size_t f = 0; f < nf; ++f) {
+        size_t here = 0;
+        for (uint32_t e = D.ofs[f]; e < D.ofs[f + 1]; ++e) here += pos[D.ent_v[e]] != WIRE_NONE;
+        if (here) {
+            u.push_back(D.free_vars[f]);
+            cut(f);
+            *nonzeros += here;
+        }
+    }
+    const size_t cnt = u.size();
+    // the constant point counts as a base here whether or not it turns out to be the identity
+    if (!cnt || (double)(cnt + 1) >= frac * (double)present || (uint64_t)st.plan.W * (cnt + 3) >= ((uint64_t)1 << 31)) return done(false);
+    if (D.n_const) cut(nf);
+    const size_t groups = pstart.size() - 1, np = piece.size();
+    if (dev_alloc(c, &d_T, d * sizeof(Affine<Q>)) || dev_alloc(c, &d_pos, n_vars * 4) || dev_alloc(c, &d_piece, np * sizeof(uint2)) ||
+        dev_alloc(c, &d_pstart, (groups + 1) * 4) || dev_alloc(c, &d_u, (cnt + 1) * 4) || dev_alloc(c, &d_part, np * sizeof(Xyzz<Q>)) ||
+        dev_alloc(c, &d_flag, 8) || dev_alloc(c, &table, (size_t)st.plan.W * (cnt + 3) * sizeof(Affine<Q>)))
+        return done(false);
+    if (hipMemcpyAsync(d_pos, pos.data(), n_vars * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(d_piece, piece.data(), np * sizeof(uint2), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(d_pstart, pstart.data(), (groups + 1) * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(d_u, u.data(), cnt * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipMemsetAsync(d_flag, 0, 8, c->stream) != hipSuccess)
+        return done(false);
+    if (!wire_points<C>(c, d_idx, n_rows, n_vars, g, (Affine<Q>*)d_T)) return done(false);   // synchronises: the staging vectors may go
+    hipLaunchKernelGGL(k_wire_fold<C>, dim3((unsigned)((np + 63) / 64)), dim3(64), 0, c->stream, (const Affine<Q>*)d_T,
+                       (const uint32_t*)d_pos, (const uint32_t*)D.d_ent_v, (const Fe<R>*)D.d_ent_c, (const uint2*)d_piece, np,
+                       (Xyzz<Q>*)d_part);
+    hipLaunchKernelGGL(k_wire_fold_sum<C>, dim3((unsigned)((groups + 63) / 64)), dim3(64), 0, c->stream, (const Xyzz<Q>*)d_part,
+                       (const uint32_t*)d_pstart, cnt, groups, (Affine<Q>*)table, (uint32_t*)d_flag);
+    uint32_t flags[2] = {0, 0};
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(flags, d_flag, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess)
+        return done(false);
+    if (flags[0]) return done(false);   // an A_f that is the identity
+    const size_t has_c = flags[1] ? 1 : 0;
+    hipLaunchKernelGGL(k_wire_blinder_points<C>, dim3(1), dim3(64), 0, c->stream, (const Affine<Q>*)st.table2, n, cnt + has_c,
+                       (Affine<Q>*)table);
+    if (hipGetLastError() != hipSuccess || msm_table_finish(c, table, cnt + has_c + 2)) return done(false);
+    wb.table[k] = table;
+    wb.u[k] = (uint32_t*)d_u;
+    wb.cnt[k] = cnt;
+    wb.use[k] = true;
+    wb.elim[k] = true;
+    wb.has_c[k] = has_c != 0;
+    return done(true);
+}
+
+template <class C>
+static int wire_bases_build_all(zkt_ctx* c, int log_n, const uint32_t* const* d_idx, size_t n_rows, size_t n_vars, double frac,
+                                const WireElimKeys* ew, bool trace) {
+    using clk = std::chrono::steady_clock;
+    auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    WireElimShared D;
+    bool elim = false;
+    const auto t0 = clk::now();
+    if (ew) elim = wire_elim_host<C>(c, log_n, d_idx, n_rows, n_vars, *ew, D);
+    const auto t1 = clk::now();
+    size_t nz[3] = {};
+    int rc = ZKT_OK;
+    for (int k = 0; k < 3 && !rc; ++k)
+        if (!elim || !wire_elim_build_wire<C>(c, log_n, k, d_idx[k], n_rows, n_vars, frac, D, &nz[k]))
+            rc = wire_bases_build_wire<C>(c, log_n, k, d_idx[k], n_rows, n_vars, frac);
+    if (trace && ew) {
+        const WireBases& wb = c->msm->wb;
+        fprintf(stderr, "[zkt host] wire elimination%s: %zu free, %zu defined (%zu with a constant); non-zeros per wire %zu / %zu / %zu; "
+                "routes %d / %d / %d (2 = free variables); host pass %.1f ms, device build %.1f ms\n", elim ? "" : " (not possible)",
+                D.free_vars.size(), D.n_defined, D.n_const, nz[0], nz[1], nz[2], wb.use[0] + wb.elim[0], wb.use[1] + wb.elim[1],
+                wb.use[2] + wb.elim[2], ms(t0, t1), ms(t1, clk::now()));
+    }
+    wire_elim_shared_free(c, D);
+    return rc;
+}
+
+int wire_bases_prepare(zkt_ctx* c, int log_n, const uint32_t* const* d_idx, size_t n_rows, size_t n_vars, const WireElimKeys* ew) {
     if (!c->msm) return ZKT_OK;
     MsmState& st = *c->msm;
     WireBases& wb = st.wb;
     const size_t n = (size_t)1 << log_n;
     const bool possible = lagrange_ready(c, log_n) && !c->sharded() && !c->lagrange_off && st.count2 >= n + 2 && n_rows <= n &&
                           n_vars <= 0xFFFFFFFEull && !(exp_env("ZKT_WIRE_BASES") && atoi(exp_env("ZKT_WIRE_BASES")) == 0);
+    if (ew && exp_env("ZKT_WIRE_ELIM") && atoi(exp_env("ZKT_WIRE_ELIM")) == 0) ew = nullptr;   // experiment: same-build A/B
+    // tables over free variables also depend on where the proof's public inputs stand
+    std::vector<size_t> pi;
+    if (ew) {
+        pi.assign(ew->pi_pos, ew->pi_pos + ew->n_pi);
+        std::sort(pi.begin(), pi.end());
+    }
     const bool same = wb.built && !wb.stale && wb.w[0] == d_idx[0] && wb.w[1] == d_idx[1] && wb.w[2] == d_idx[2] &&
-                      wb.n_rows == n_rows && wb.n_vars == n_vars && wb.log_n == log_n && wb.srs_generation == c->srs_generation;
+                      wb.n_rows == n_rows && wb.n_vars == n_vars && wb.log_n == log_n && wb.srs_generation == c->srs_generation &&
+                      wb.elim_wanted == (ew != nullptr) && wb.pi_pos == pi;
     if (possible && same) return ZKT_OK;
     // tables that forks of this context read stay where they are: this context then commits densely until they are gone
     if (wb.built && !wb.borrowed && c->forks.load() > 0) {
@@ -497,17 +809,15 @@ int wire_bases_prepare(zkt_ctx* c, int log_n, const uint32_t* const* d_idx, size
         (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
         (void)hipEventRecord(e0, c->stream);
     }
-    for (int k = 0; k < 3; ++k) {
-        const int rc = c->curve == ZKT_CURVE_BN254 ? wire_bases_build_wire<Bn254Curve>(c, log_n, k, d_idx[k], n_rows, n_vars, frac)
-                                                    : wire_bases_build_wire<Bls381Curve>(c, log_n, k, d_idx[k], n_rows, n_vars, frac);
-        if (rc) return rc;
-    }
+    if (int rc = c->curve == ZKT_CURVE_BN254 ? wire_bases_build_all<Bn254Curve>(c, log_n, d_idx, n_rows, n_vars, frac, ew, trace)
+                                             : wire_bases_build_all<Bls381Curve>(c, log_n, d_idx, n_rows, n_vars, frac, ew, trace))
+        return rc;
     if (int rc = wire_digest_enqueue(c, d_idx, n_rows)) return rc;
     ZKT_HIP(c, hipStreamSynchronize(c->stream));
     if (trace) {
         float ms = 0;
         (void)hipEventRecord(e1, c->stream); (void)hipEventSynchronize(e1); (void)hipEventElapsedTime(&ms, e0, e1);
-        fprintf(stderr, "[zkt host] wire base tables: %zu / %zu / %zu distinct of %zu rows (0 = dense), %.1f ms\n",
+        fprintf(stderr, "[zkt host] wire base tables: %zu / %zu / %zu bases of %zu rows (0 = dense), %.1f ms\n",
                 wb.use[0] ? wb.cnt[0] : 0, wb.use[1] ? wb.cnt[1] : 0, wb.use[2] ? wb.cnt[2] : 0, n_rows, ms);
         (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     }
@@ -515,6 +825,8 @@ int wire_bases_prepare(zkt_ctx* c, int log_n, const uint32_t* const* d_idx, size
     wb.digest[1] = st.wb_pin[1];
     for (int k = 0; k < 3; ++k) wb.w[k] = d_idx[k];
     wb.n_rows = n_rows; wb.n_vars = n_vars; wb.log_n = log_n; wb.srs_generation = c->srs_generation;
+    wb.elim_wanted = ew != nullptr;
+    wb.pi_pos.swap(pi);
     wb.built = true;
     ++c->msm_epoch;
     return ZKT_OK;
@@ -523,6 +835,7 @@ int wire_bases_prepare(zkt_ctx* c, int log_n, const uint32_t* const* d_idx, size
 bool wire_bases_use(const zkt_ctx* c, int k) {
     return c->msm && c->msm->wb.built && !c->msm->wb.stale && c->msm->wb.use[k];
 }
+int wire_bases_route(const zkt_ctx* c, int k) { return !wire_bases_use(c, k) ? 0 : c->msm->wb.elim[k] ? 2 : 1; }
 int wire_bases_digest(zkt_ctx* c, const uint32_t* const* d_idx, size_t n_rows) { return wire_digest_enqueue(c, d_idx, n_rows); }
 int wire_bases_lens(zkt_ctx* c, const uint32_t* d_lens) {
     ZKT_HIP(c, hipMemcpyAsync(c->msm->wb_pin + 2, d_lens, 12, hipMemcpyDeviceToHost, c->stream));
@@ -533,17 +846,17 @@ template <class C>
 static int wire_scalars_t(zkt_ctx* c, int k, const void* d_vars, const void* d_bl, size_t n, const void** out, size_t* len) {
     using R = typename C::Fr;
     MsmState& st = *c->msm;
-    const size_t cnt = st.wb.cnt[k];
-    if (int rc = grow(c, st.wb_scalars[k], (cnt + 2) * sizeof(Fe<R>))) return rc;
+    const size_t cnt = st.wb.cnt[k], extra = st.wb.has_c[k] ? 1 : 0;
+    if (int rc = grow(c, st.wb_scalars[k], (cnt + extra + 2) * sizeof(Fe<R>))) return rc;
     Fe<R> nn = fe_zero<R>();
     nn.v[0] = (uint32_t)(n & 0xffffffffu);
     nn.v[1] = (uint32_t)((uint64_t)n >> 32);
     const Fe<R> ninv = fe_inv_host<R>(fe_to_mont<R>(nn));
-    hipLaunchKernelGGL(k_wire_scalars<R>, dim3((unsigned)((cnt + 2 + 255) / 256)), dim3(256), 0, c->stream, (const Fe<R>*)d_vars,
-                       (const uint32_t*)st.wb.u[k], cnt, (const Fe<R>*)d_bl, ninv, (Fe<R>*)st.wb_scalars[k].p);
+    hipLaunchKernelGGL(k_wire_scalars<R>, dim3((unsigned)((cnt + extra + 2 + 255) / 256)), dim3(256), 0, c->stream, (const Fe<R>*)d_vars,
+                       (const uint32_t*)st.wb.u[k], cnt, extra, (const Fe<R>*)d_bl, ninv, (Fe<R>*)st.wb_scalars[k].p);
     ZKT_HIP(c, hipGetLastError());
     *out = st.wb_scalars[k].p;
-    *len = cnt + 2;
+    *len = cnt + extra + 2;
     return ZKT_OK;
 }
 int wire_bases_scalars(zkt_ctx* c, int k, const void* d_vars, const void* d_blinders, size_t n, const void** out, size_t* len) {
@@ -561,4 +874,55 @@ bool wire_bases_check(zkt_ctx* c, int k, size_t n) {
     return ((const uint32_t*)(st.wb_pin + 2))[k] == (uint32_t)n;
 }
 
+// zkt_debug_wire_elimination: the host pass alone, on caller-supplied selectors and wiring (no device, no context)
+template <class R>
+static int debug_wire_elimination_t(const uint64_t* const* selectors, const uint32_t* const* w, size_t n_rows, size_t n_vars,
+                                    const size_t* pi_pos, size_t n_pi, int K, uint8_t* out_kind, uint32_t* out_free, size_t* out_n_free,
+                                    uint32_t* out_term_v, uint32_t* out_term_f, uint64_t* out_term_coef, size_t* out_n_terms,
+                                    uint64_t* out_kappa) {
+    using F = Fe<R>;
+    static_assert(sizeof(F) == 32, "scalar field element = 4 x 64-bit words");
+    const F* sel[5];
+    for (int k = 0; k < 5; ++k) sel[k] = reinterpret_cast<const F*>(selectors[k]);
+    WireElim<R> E;
+    wire_eliminate<R>(sel, w, n_rows, n_vars, pi_pos, n_pi, K, E);
+    if (n_vars) memcpy(out_kind, E.kind.data(), n_vars);
+    if (!E.free_vars.empty()) memcpy(out_free, E.free_vars.data(), E.free_vars.size() * 4);
+    *out_n_free = E.free_vars.size();
+    memset(out_kappa, 0, n_vars * 32);
+    size_t t = 0;
+    for (size_t d = 0; d < E.def_vars.size(); ++d) {
+        memcpy(out_kappa + 4 * (size_t)E.def_vars[d], E.kappa[d].v, 32);
+        for (uint64_t e = E.def_start[d]; e < E.def_start[d + 1]; ++e, ++t) {
+            out_term_v[t] = E.def_vars[d];
+            out_term_f[t] = E.term_f[e];
+            memcpy(out_term_coef + 4 * t, E.term_c[e].v, 32);
+        }
+    }
+    *out_n_terms = t;
+    return ZKT_OK;
+}
+
 }  // namespace zkt
+
+using namespace zkt;
+
+int zkt_debug_wire_elimination(int curve, const uint64_t* const* selectors, const uint32_t* w_l, const uint32_t* w_r, const uint32_t* w_o,
+                               size_t n_rows, size_t n_vars, const size_t* pi_pos, size_t n_pi, int K, uint8_t* out_kind,
+                               uint32_t* out_free, size_t* out_n_free, uint32_t* out_term_v, uint32_t* out_term_f,
+                               uint64_t* out_term_coef, size_t* out_n_terms, uint64_t* out_kappa) {
+    if (!selectors || !out_kind || !out_free || !out_n_free || !out_term_v || !out_term_f || !out_term_coef || !out_n_terms || !out_kappa ||
+        (n_pi && !pi_pos) || (n_rows && (!w_l || !w_r || !w_o)))
+        return ZKT_ERR_INVALID_ARGUMENT;
+    for (int k = 0; k < 5; ++k)
+        if (n_rows && !selectors[k]) return ZKT_ERR_INVALID_ARGUMENT;
+    if (K < 1 || K > WIRE_ELIM_K_MAX || n_vars > 0xFFFFFFFEull) return ZKT_ERR_INVALID_ARGUMENT;
+    const uint32_t* w[3] = {w_l, w_r, w_o};
+    if (curve == ZKT_CURVE_BN254)
+        return debug_wire_elimination_t<Bn254Fr>(selectors, w, n_rows, n_vars, pi_pos, n_pi, K, out_kind, out_free, out_n_free, out_term_v,
+                                                 out_term_f, out_term_coef, out_n_terms, out_kappa);
+    if (curve == ZKT_CURVE_BLS12_381)
+        return debug_wire_elimination_t<Bls381Fr>(selectors, w, n_rows, n_vars, pi_pos, n_pi, K, out_kind, out_free, out_n_free, out_term_v,
+                                                  out_term_f, out_term_coef, out_n_terms, out_kappa);
+    return ZKT_ERR_INVALID_ARGUMENT;
+}

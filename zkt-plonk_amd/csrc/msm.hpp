@@ -82,6 +82,12 @@ struct WireBases {
     uint32_t* u[3] = {};       // the cnt distinct variables, ascending
     size_t cnt[3] = {};
     bool use[3] = {};          // false: the wire is committed through its coefficients (too many distinct variables, ...)
+    // Tables over the circuit's FREE variables (lagrange.hip): u holds the free variables that reach the wire, the table their
+    // points A_f, then the constant point C when has_c, then the two blinder points
+    bool elim[3] = {};
+    bool has_c[3] = {};
+    bool elim_wanted = false;  // part of the key: the build was asked to eliminate, for the public-input positions below
+    std::vector<size_t> pi_pos;   // ascending
     bool built = false;        // the key below was examined (use[] says what came of it)
     bool borrowed = false;     // zkt_ctx_fork: the parent's tables (never freed here)
     bool stale = false;        // a proof found other index contents than the digest: rebuild before the next use
@@ -115,7 +121,9 @@ struct MsmState {
     uint64_t* wb_pin = nullptr;    // pinned: [0..1] digest of the proof in flight, [2..3] the three trimmed lengths (32-bit)
     // the base table and its bases per window behind a `tbl` selector
     const void* tbl_table(int tbl) const { return tbl >= MSM_TBL_WIRE ? wb.table[tbl - MSM_TBL_WIRE] : tbl ? table2 : table; }
-    size_t tbl_count(int tbl) const { return tbl >= MSM_TBL_WIRE ? wb.cnt[tbl - MSM_TBL_WIRE] + 2 : tbl ? count2 : count; }
+    size_t tbl_count(int tbl) const {
+        return tbl >= MSM_TBL_WIRE ? wb.cnt[tbl - MSM_TBL_WIRE] + (wb.has_c[tbl - MSM_TBL_WIRE] ? 1 : 0) + 2 : tbl ? count2 : count;
+    }
     uint32_t* params[11] = {};     // per slot, device: [0] chunk, [1] pairs (written by k_msm_scan_aux)
     // work buffers (sized for n = count)
     uint32_t* vals2 = nullptr;                     // table indices grouped by bucket
@@ -220,8 +228,18 @@ size_t lagrange_bases(const zkt_ctx* c);
 // had; wire_bases_use tells per wire.  _digest enqueues the digest of the vectors' present contents (into pinned
 // memory), _lens the copy of the three trimmed lengths; _scalars the gather of wire k's scalars; once the stream has
 // passed them, _check compares: false = wire k has to be committed again through its coefficients.
-int wire_bases_prepare(zkt_ctx* c, int log_n, const uint32_t* const* d_idx, size_t n_rows, size_t n_vars);
+// `elim`, when given, asks for tables over the circuit's free variables where they shrink a wire: the key's selector
+// coefficients q_m q_l q_r q_o q_c (device, zero-padded to the domain) and the proof's public-input positions (host).  The
+// positions are compared in every call; other positions rebuild the tables.  _route: 0 coefficients, 1 the wire's
+// per-variable table, 2 its table over free variables.
+struct WireElimKeys {
+    const void* pk[5];
+    const size_t* pi_pos;
+    size_t n_pi;
+};
+int wire_bases_prepare(zkt_ctx* c, int log_n, const uint32_t* const* d_idx, size_t n_rows, size_t n_vars, const WireElimKeys* elim = nullptr);
 bool wire_bases_use(const zkt_ctx* c, int k);
+int wire_bases_route(const zkt_ctx* c, int k);
 int wire_bases_digest(zkt_ctx* c, const uint32_t* const* d_idx, size_t n_rows);
 int wire_bases_lens(zkt_ctx* c, const uint32_t* d_lens);
 int wire_bases_scalars(zkt_ctx* c, int k, const void* d_vars, const void* d_blinders, size_t n, const void** out, size_t* len);

@@ -121,6 +121,9 @@ struct WitnessCheckKeys {
     const void* q_lookup_ev;
     const void* sigma_ev[3];
 };
+// the evaluations of q_m q_l q_r q_o q_c over the domain: fft(n) of the key's coefficients pk[0..4] (zero-padded to n) into
+// outs[0..4] (n elements each, device), four transforms in one launch per pass and one more.  Enqueues only.
+int selector_evals_enqueue(zkt_ctx* c, int log_n, const void* const* pk, void* const* outs);
 int witness_check(zkt_ctx* c, const WitnessCheckKeys& keys, const zkt_prove_inputs& in, int flags, zkt_witness_report* out);
 // table generation
 int gen_powers(zkt_ctx* c, void* out, size_t n, const uint32_t base[8], const uint32_t scale[8]);

@@ -100,6 +100,7 @@ struct CircuitState {
     // and trimmed lengths are compared when that round is collected (collect_wires)
     bool wire_route[3] = {};
     bool wire_dense_only = false;   // zkt_debug_commit_wires_dev route 0
+    int wire_elim_force = -1;       // zkt_debug_commit_wires_dev: 0 = per-variable tables only (route 1), 1 = over free variables (route 2)
 };
 
 // ---- host field helpers ------------------------------------------------------------------------------
@@ -152,6 +153,8 @@ static void serialize_point(const Affine<Q>& p, std::vector<uint8_t>& out) {
     }
     out.insert(out.end(), b.begin(), b.end());
 }
+
+constexpr int WIRE_ELIM_MIN_LOG_N = 17;   // zkt_ctx_set_wire_elimination mode 1: circuits from this size on
 
 template <class C>
 struct Prover {
@@ -318,7 +321,7 @@ struct Prover {
             if (took) took[k] = 0;
             if (!routed) continue;
             if (wire_bases_check(c, k, S.n)) {
-                if (took) took[k] = 1;
+                if (took) took[k] = wire_bases_route(c, k);
                 continue;
             }
             static const int slot[1] = {0};
@@ -550,7 +553,15 @@ struct Prover {
         bool wire_tables = from_vars && in.wires_on_device && !c->sharded() && !c->lagrange_off && !S.wire_dense_only &&
                            lagrange_ready(c, S.log_n) && in.n_rows > 0;
         if (wire_tables) {
-            if ((rc = wire_bases_prepare(c, S.log_n, d_idx, in.n_rows, in.n_vars))) return rc;
+            // Over the circuit's free variables (lagrange.hip) in the large-key regime, where an MSM's time is its additions
+            // (DESIGN.md 3.1); below it a proof is a chain of latencies and a shorter MSM buys nothing.
+            const bool eliminate = S.wire_elim_force >= 0 ? S.wire_elim_force != 0
+                                                          : c->wire_elim_mode == 2 || (c->wire_elim_mode == 1 && S.log_n >= WIRE_ELIM_MIN_LOG_N);
+            WireElimKeys ek{};
+            for (int k = 0; k < 5; ++k) ek.pk[k] = S.pk[PK_QM + k];
+            ek.pi_pos = in.pi_pos;
+            ek.n_pi = in.pi_pos ? in.n_pi : 0;
+            if ((rc = wire_bases_prepare(c, S.log_n, d_idx, in.n_rows, in.n_vars, eliminate ? &ek : nullptr))) return rc;
             wire_tables = wire_bases_use(c, 0) || wire_bases_use(c, 1) || wire_bases_use(c, 2);
             if (wire_tables && (rc = wire_bases_digest(c, d_idx, in.n_rows))) return rc;
         }
@@ -1680,6 +1691,14 @@ int zkt_ctx_set_lagrange(zkt_ctx* c, int on) {
     return ZKT_OK;
 }
 
+int zkt_ctx_set_wire_elimination(zkt_ctx* c, int mode) {
+    if (!c) return ZKT_ERR_INVALID_ARGUMENT;
+    if (mode < 0 || mode > 2) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "mode: 0 off, 1 automatic, 2 whenever a table can be built");
+    c->wire_elim_mode = mode;
+    ++c->msm_epoch;   // early work of an announced proof was issued under the other setting
+    return ZKT_OK;
+}
+
 int zkt_lagrange_info(zkt_ctx* c, int* log_n, size_t* bases) {
     if (!c) return ZKT_ERR_INVALID_ARGUMENT;
     const bool ready = c->circuit && lagrange_ready(c, c->circuit->log_n) && !c->lagrange_off;
@@ -2015,8 +2034,10 @@ static int debug_commit_wires_t(zkt_ctx* c, const zkt_prove_inputs& in, int rout
     MerlinHostTranscript tr("zkt_debug_commit_wires_dev");
     Prover<C> p(c, S, tr);
     S.wire_dense_only = route == 0;
+    S.wire_elim_force = route == 2 ? 1 : 0;
     int rc = p.enqueue_round_1(in);
     S.wire_dense_only = false;
+    S.wire_elim_force = -1;
     Affine<Q> cm[3];
     static const int slots[3] = {0, 1, 2};
     int took[3] = {0, 0, 0};
@@ -2041,8 +2062,17 @@ static int debug_commit_wires_t(zkt_ctx* c, const zkt_prove_inputs& in, int rout
 int zkt_debug_commit_wires_dev(zkt_ctx* c, const void* d_variables, size_t n_vars, const uint32_t* d_w_l, const uint32_t* d_w_r,
                                const uint32_t* d_w_o, size_t n_rows, const uint64_t* blinders, int route, uint64_t* out_xy,
                                int* out_is_infinity, int* out_route) {
-    if (!c || !d_variables || !blinders || !out_xy) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
     if (route != 0 && route != 1) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "route: 0 coefficients, 1 wire base tables");
+    return zkt_debug_commit_wires_pi_dev(c, d_variables, n_vars, d_w_l, d_w_r, d_w_o, n_rows, blinders, route, nullptr, 0, out_xy,
+                                         out_is_infinity, out_route);
+}
+
+int zkt_debug_commit_wires_pi_dev(zkt_ctx* c, const void* d_variables, size_t n_vars, const uint32_t* d_w_l, const uint32_t* d_w_r,
+                                  const uint32_t* d_w_o, size_t n_rows, const uint64_t* blinders, int route, const size_t* pi_pos,
+                                  size_t n_pi, uint64_t* out_xy, int* out_is_infinity, int* out_route) {
+    if (!c || !d_variables || !blinders || !out_xy || (n_pi && !pi_pos)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
+    if (route < 0 || route > 2)
+        return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "route: 0 coefficients, 1 wire base tables, 2 tables over free variables");
     if (!c->circuit) return set_err(c, ZKT_ERR_NOT_LOADED, "no circuit loaded (the domain comes from it)");
     if (!c->msm) return set_err(c, ZKT_ERR_NOT_LOADED, "no SRS loaded (zkt_srs_load)");
     if (c->sharded()) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "not available on a sharded key");
@@ -2050,7 +2080,7 @@ int zkt_debug_commit_wires_dev(zkt_ctx* c, const void* d_variables, size_t n_var
     if (S.has_next) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "zkt_debug_commit_wires_dev: a next proof is announced");
     (void)hipSetDevice(c->device);
     S.prefetch_stage = 0;   // the work buffers are shared with an announced proof's early rounds
-    if (route == 1 && !c->lagrange_off)
+    if (route >= 1 && !c->lagrange_off)
         if (int rc1 = lagrange_ensure(c, S.log_n)) return rc1;
     uint64_t bl[19 * 4] = {};
     memcpy(bl, blinders, 6 * 32);
@@ -2061,6 +2091,8 @@ int zkt_debug_commit_wires_dev(zkt_ctx* c, const void* d_variables, size_t n_var
     in.n_rows = n_rows;
     in.wires_on_device = 1;
     in.blinders = bl;
+    in.pi_pos = pi_pos;
+    in.n_pi = n_pi;
     if (c->curve == ZKT_CURVE_BN254) return debug_commit_wires_t<Bn254Curve>(c, in, route, out_xy, out_is_infinity, out_route);
     return debug_commit_wires_t<Bls381Curve>(c, in, route, out_xy, out_is_infinity, out_route);
 }
