@@ -90,6 +90,8 @@ int zkt_ctx_synchronize(zkt_ctx* ctx);
  * domain table they read).
  * "check_witness": every launch of zkt_circuit_check_witness (selector transforms, the sigma launches when the wiring
  * is checked, the gate, residual and comparison kernels), not its uploads.
+ * "merkle_append": the copy of the leaves into layer 0 and every level launch of one zkt_merkle_tree_append(_dev);
+ * "merkle_paths": the table upload and the gather launch of zkt_merkle_tree_paths / _paths_to_variables_dev.
  * A scope that covers a batch counts its units in `calls` (the three commitments of a round grouped and accumulated as one
  * batch of launches: 3); "<name>#launches" returns the number of recorded scopes instead.
  * on = 0: off; 1: every scope; 2: only "msm_accumulate" and "host_wait" -- the level for timing the dominant kernel
@@ -632,6 +634,70 @@ int zkt_poseidon_merkle_path_witness_dev(zkt_ctx* ctx, const zkt_poseidon* param
  * writes.  ZKT_ERR_INVALID_ARGUMENT names the rule.  Run it once per circuit layout. */
 int zkt_poseidon_merkle_path_validate(zkt_ctx* ctx, const zkt_poseidon* params, const zkt_merkle_path_args* args);
 
+/* (4) The note tree itself: MerkleTree<F, G, H, HEIGHT> (gadgets/src/merkle_tree.rs:39-111) kept in HBM and appended to
+ * there.  The reference's add_leaf (merkle_tree.rs:89-106) walks HEIGHT hash_two calls per leaf, one after the other; m
+ * appended leaves need only ~2 m + HEIGHT hashes, at most HEIGHT of them dependent, because the tree after add_leaf of
+ * leaves 0 .. n - 1 is the dense one in which every stored node (layer, idx), idx < ceil(n / 2^layer), is hash_two of its two
+ * children with nodes[layer - 1] standing in for a right child that does not exist yet.  Levels with many parents are one
+ * launch each (a thread per parent), all the narrow ones are ONE launch of one workgroup that walks them with a lane group
+ * per parent and passes each level to the next through LDS; the threshold between the two (64 parents) comes from a sweep
+ * on an MI355X with the BN254 x5 tables
+ * (docs/EXPERIMENTS.md, "note tree on the device").  The siblings merkle_path returns are exactly what
+ * zkt_poseidon_merkle_path_witness_dev reads out of the variable map: zkt_merkle_tree_paths_to_variables_dev writes them
+ * there without a trip to the host.
+ * The handle is bound to a loaded zkt_poseidon, which is BORROWED and must outlive the tree; width >= 3 (hash_two).  Every
+ * call enqueues on the stream of the context it is given -- use one context per tree, or order the streams yourself.  Any
+ * context will do: forked, with a communicator (the tree is local, no collective is made), with or without SRS or circuit
+ * -- the tree touches none of their memory.  Everything in Montgomery words.
+ * Out of scope: reading or writing the reference's serialised MerkleTreeStore file (zkt_merkle_tree_layer of layer 0 and an
+ * append of what it returned is the persistence path); deleting or updating leaves (the reference has neither); a tree
+ * sharded over ranks. */
+#define ZKT_MERKLE_TREE_MAX ((size_t)1 << 24)      /* most leaves a tree holds */
+#define ZKT_MERKLE_TREE_PATHS_MAX 4096             /* most paths one zkt_merkle_tree_paths* call takes */
+typedef struct zkt_merkle_tree zkt_merkle_tree;
+/* MerkleTree::new over an empty store (merkle_tree.rs:57-75).  1 <= height <= 64 and 1 <= capacity <= min(2^height,
+ * ZKT_MERKLE_TREE_MAX), else ZKT_ERR_INVALID_ARGUMENT; a failed allocation gives ZKT_ERR_HIP.  Layer L (0 <= L < height) is a
+ * dense array of max(1, ceil(capacity / 2^L)) scalars, ~2 x capacity x 32 B in all.  The `height` empty-subtree values are
+ * computed on the device: nodes[0] = H::empty_hash() = 0, nodes[L + 1] = hash_two(nodes[L], nodes[L]) (merkle_tree.rs:58-67).
+ * Synchronises. */
+int zkt_merkle_tree_create(zkt_ctx* ctx, const zkt_poseidon* params, int height, size_t capacity, zkt_merkle_tree** out);
+void zkt_merkle_tree_free(zkt_ctx* ctx, zkt_merkle_tree* tree);
+/* add_leaf (merkle_tree.rs:89-106) for the m scalars of d_leaves (DEVICE memory) in order; *first_index (optional) receives
+ * the index of the first, i.e. the number of leaves before the call.  Enqueue only: no allocation, no synchronisation.
+ * m = 0: ZKT_OK, nothing enqueued.  count + m > capacity: ZKT_ERR_INVALID_ARGUMENT, the tree unchanged, nothing enqueued.
+ * Afterwards every stored node of every layer and the root equal what the reference holds after the same add_leaf calls,
+ * however the leaves were split into batches.  ZKT_ERR_HIP (a copy or a launch the runtime refused) leaves the count as it
+ * was, but nodes above layer 0 may be half made: free the tree and rebuild it from its leaves.  Measured on an MI355X: docs/EXPERIMENTS.md, "note tree on the device". */
+int zkt_merkle_tree_append_dev(zkt_ctx* ctx, zkt_merkle_tree* tree, const void* d_leaves, size_t m, uint64_t* first_index);
+/* The same with HOST leaves: uploads them, enqueues as the _dev form does, synchronises. */
+int zkt_merkle_tree_append(zkt_ctx* ctx, zkt_merkle_tree* tree, const uint64_t* leaves, size_t m, uint64_t* first_index);
+/* MerkleTree::root (merkle_tree.rs:108-110): synchronises and writes four words.  A tree without a leaf has the root 0, as
+ * MerkleTreeStore::default().root is (merkle_tree.rs:8-13) -- NOT the hash of an empty tree. */
+int zkt_merkle_tree_root(zkt_ctx* ctx, zkt_merkle_tree* tree, uint64_t* out4);
+/* Any of the outputs may be NULL.  count: MerkleTreeStore::next_index. */
+int zkt_merkle_tree_info(const zkt_merkle_tree* tree, int* height, uint64_t* count, uint64_t* capacity);
+/* Downloads the stored nodes (layer, first .. first + n): the content of the reference's BTreeMap<(usize, usize), F>
+ * (merkle_tree.rs:10, :94), for persistence and for tests.  Synchronises.  Layer L holds ceil(count / 2^L) nodes; a range
+ * that reaches past them, or a layer outside [0, height), gives ZKT_ERR_INVALID_ARGUMENT (layer = height is not a layer: the
+ * root has its own call). */
+int zkt_merkle_tree_layer(zkt_ctx* ctx, zkt_merkle_tree* tree, int layer, uint64_t first, size_t n, uint64_t* out);
+/* merkle_path(index) (merkle_tree.rs:77-87) for k HOST indices: k x height scalars to HOST memory, level 0 first.  Any index
+ * below 2^height is valid, as in the reference: the sibling (layer, idx ^ 1), idx = index >> layer, is the stored node when
+ * idx ^ 1 < ceil(count / 2^layer) and nodes[layer] otherwise.  An index >= 2^height or k > ZKT_MERKLE_TREE_PATHS_MAX gives
+ * ZKT_ERR_INVALID_ARGUMENT; everything is checked on the host before anything is enqueued.  Synchronises. */
+int zkt_merkle_tree_paths(zkt_ctx* ctx, zkt_merkle_tree* tree, const uint64_t* indices, size_t k, uint64_t* out_siblings);
+/* The same paths written into the prover's variable map (DEVICE memory, n_vars scalars): path p puts its `height` siblings
+ * at d_variables[sibling_var0[p] + layer] and, when bit_var0 is not NULL, its position bits (index >> layer) & 1 at
+ * d_variables[bit_var0[p] + layer] as the Montgomery 0 or 1 -- where PoECircuit::synthesize (plonk-hashing/src/merkle/
+ * binary.rs:42-78) allocates them: `height` consecutive bits, then `height` consecutive siblings.  indices, bit_var0 and
+ * sibling_var0 are HOST arrays of k entries, free on return: the small table goes up on the stream from a pinned buffer the
+ * tree owns (a second call waits for the first one's table to have left that buffer, nothing else).  Ranges that leave
+ * [0, n_vars) or overlap each other, an index >= 2^height and k > ZKT_MERKLE_TREE_PATHS_MAX give ZKT_ERR_INVALID_ARGUMENT
+ * before anything is enqueued.  Enqueue only: no allocation, no synchronisation of the stream. */
+int zkt_merkle_tree_paths_to_variables_dev(zkt_ctx* ctx, zkt_merkle_tree* tree, const uint64_t* indices, size_t k,
+                                           void* d_variables, size_t n_vars, const uint32_t* bit_var0,
+                                           const uint32_t* sibling_var0);
+
 /* ---- Verifier (proof_system/proof.rs:285-503): zkt_verify_prepare = everything but the pairings,
  * ---- zkt_pairing_product_is_one = the pairings, zkt_verify = both ------------------------------------------------
  * Deserialises the proof (proof.rs:98-155; points are decompressed and checked to be on the curve), replays the
@@ -822,6 +888,12 @@ int zkt_debug_ntt_batch(zkt_ctx* ctx, int log_n, int inverse, int coset, int nb,
  * size that is not the product of the radices.  (A tile that would not fit its pass is refused as well, but no two or
  * three radices of 2^5 and more have one: that check is a guard, not a reachable refusal.) */
 int zkt_debug_ntt_split(zkt_ctx* ctx, int npass, const int* log_r);
+/* Overrides where the appends of this tree change from one launch per level to the single-workgroup tail: levels with at
+ * least wide_min_parents parents are hashed by the wide kernel, the others by the tail kernel.  1 sends every level to the
+ * wide kernel, INT_MAX every level to the tail kernel (up to the 512 parents a level of the tail may have: it keeps the
+ * level in LDS, a wider one is a launch of its own whatever is asked), 0 restores the policy.  Tests use it to run both
+ * kernels on every level of small trees.  A negative value gives ZKT_ERR_INVALID_ARGUMENT. */
+int zkt_debug_merkle_tree_split(zkt_merkle_tree* tree, int wide_min_parents);
 /* Self-check of the host pairing's shortcuts against their plain definitions (Frobenius maps = powers by p, sparse
  * and cyclotomic products = dense ones, the final exponentiation leaves an element of order r).  0 = all good. */
 int zkt_debug_pairing_selftest(int curve_id);

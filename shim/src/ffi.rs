@@ -145,6 +145,19 @@ extern "C" {
     pub fn zkt_merkle_path_vars_per_level(params: *const c_void) -> usize;
     pub fn zkt_poseidon_merkle_path_witness_dev(ctx: *mut ZktCtx, params: *const c_void, args: *const ZktMerklePathArgs) -> c_int;
     pub fn zkt_poseidon_merkle_path_validate(ctx: *mut ZktCtx, params: *const c_void, args: *const ZktMerklePathArgs) -> c_int;
+    // the note tree (gadgets/src/merkle_tree.rs) kept on the device; `tree` is the opaque zkt_merkle_tree
+    pub fn zkt_merkle_tree_create(ctx: *mut ZktCtx, params: *const c_void, height: c_int, capacity: usize, out: *mut *mut c_void) -> c_int;
+    pub fn zkt_merkle_tree_free(ctx: *mut ZktCtx, tree: *mut c_void);
+    pub fn zkt_merkle_tree_append_dev(ctx: *mut ZktCtx, tree: *mut c_void, d_leaves: *const c_void, m: usize, first_index: *mut u64) -> c_int;
+    pub fn zkt_merkle_tree_append(ctx: *mut ZktCtx, tree: *mut c_void, leaves: *const u64, m: usize, first_index: *mut u64) -> c_int;
+    pub fn zkt_merkle_tree_root(ctx: *mut ZktCtx, tree: *mut c_void, out4: *mut u64) -> c_int;
+    pub fn zkt_merkle_tree_info(tree: *const c_void, height: *mut c_int, count: *mut u64, capacity: *mut u64) -> c_int;
+    pub fn zkt_merkle_tree_layer(ctx: *mut ZktCtx, tree: *mut c_void, layer: c_int, first: u64, n: usize, out: *mut u64) -> c_int;
+    pub fn zkt_merkle_tree_paths(ctx: *mut ZktCtx, tree: *mut c_void, indices: *const u64, k: usize, out_siblings: *mut u64) -> c_int;
+    pub fn zkt_merkle_tree_paths_to_variables_dev(ctx: *mut ZktCtx, tree: *mut c_void, indices: *const u64, k: usize,
+                                                  d_variables: *mut c_void, n_vars: usize, bit_var0: *const u32,
+                                                  sibling_var0: *const u32) -> c_int;
+    pub fn zkt_debug_merkle_tree_split(tree: *mut c_void, wide_min_parents: c_int) -> c_int;
     pub fn zkt_dev_alloc(ctx: *mut ZktCtx, bytes: usize, dptr: *mut *mut c_void) -> c_int;
     pub fn zkt_dev_free(ctx: *mut ZktCtx, dptr: *mut c_void) -> c_int;
     pub fn zkt_dev_upload(ctx: *mut ZktCtx, dptr: *mut c_void, host: *const c_void, bytes: usize) -> c_int;

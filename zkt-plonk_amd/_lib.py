@@ -885,6 +885,95 @@ class Context:
         fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MerklePathArgs)]
         self.check(fn(self._h, ctypes.c_void_p(handle), ctypes.byref(a)))
 
+    # -- the note tree (gadgets/src/merkle_tree.rs) ----------------------------------------------------
+    def merkle_tree_create(self, poseidon_handle: int, height: int, capacity: int) -> int:
+        """zkt_merkle_tree_create: an empty tree in HBM over a loaded Poseidon (borrowed) -> opaque handle."""
+        L, vp = self._L, ctypes.c_void_p
+        L.zkt_merkle_tree_create.argtypes = [vp, vp, ctypes.c_int, ctypes.c_size_t, ctypes.POINTER(vp)]
+        t = vp()
+        self.check(L.zkt_merkle_tree_create(self._h, vp(poseidon_handle), height, capacity, ctypes.byref(t)))
+        return t.value
+
+    def merkle_tree_free(self, tree: int):
+        L = self._L
+        L.zkt_merkle_tree_free.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        L.zkt_merkle_tree_free.restype = None
+        L.zkt_merkle_tree_free(self._h, ctypes.c_void_p(tree))
+
+    def merkle_tree_append_dev(self, tree: int, d_leaves: int, m: int) -> int:
+        """zkt_merkle_tree_append_dev: add_leaf for m device scalars, enqueue only -> index of the first."""
+        L, vp = self._L, ctypes.c_void_p
+        L.zkt_merkle_tree_append_dev.argtypes = [vp, vp, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64)]
+        first = ctypes.c_uint64(0)
+        self.check(L.zkt_merkle_tree_append_dev(self._h, vp(tree), vp(d_leaves) if d_leaves else None, m, ctypes.byref(first)))
+        return first.value
+
+    def merkle_tree_append(self, tree: int, leaves) -> int:
+        """zkt_merkle_tree_append: the same with host leaves (m x 4 Montgomery words); synchronises."""
+        L, vp = self._L, ctypes.c_void_p
+        a = np.ascontiguousarray(leaves, dtype=np.uint64).reshape(-1, 4)
+        L.zkt_merkle_tree_append.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64)]
+        first = ctypes.c_uint64(0)
+        self.check(L.zkt_merkle_tree_append(self._h, vp(tree), u64p(a) if a.size else None, a.shape[0], ctypes.byref(first)))
+        return first.value
+
+    def merkle_tree_root(self, tree: int) -> np.ndarray:
+        L, vp = self._L, ctypes.c_void_p
+        L.zkt_merkle_tree_root.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_uint64)]
+        out = np.empty(4, dtype=np.uint64)
+        self.check(L.zkt_merkle_tree_root(self._h, vp(tree), u64p(out)))
+        return out
+
+    def merkle_tree_info(self, tree: int):
+        """-> (height, count, capacity)"""
+        L = self._L
+        L.zkt_merkle_tree_info.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint64),
+                                           ctypes.POINTER(ctypes.c_uint64)]
+        h, n, cap = ctypes.c_int(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        rc = L.zkt_merkle_tree_info(ctypes.c_void_p(tree), ctypes.byref(h), ctypes.byref(n), ctypes.byref(cap))
+        if rc:
+            raise ZktError(rc, "zkt_merkle_tree_info: null tree")
+        return h.value, n.value, cap.value
+
+    def merkle_tree_layer(self, tree: int, layer: int, first: int, n: int) -> np.ndarray:
+        """zkt_merkle_tree_layer: the stored nodes (layer, first .. first + n) as n x 4 Montgomery words."""
+        L, vp = self._L, ctypes.c_void_p
+        L.zkt_merkle_tree_layer.argtypes = [vp, vp, ctypes.c_int, ctypes.c_uint64, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64)]
+        out = np.empty((n, 4), dtype=np.uint64)
+        self.check(L.zkt_merkle_tree_layer(self._h, vp(tree), layer, first, n, u64p(out) if n else None))
+        return out
+
+    def merkle_tree_paths(self, tree: int, indices) -> np.ndarray:
+        """zkt_merkle_tree_paths: merkle_path of every index -> k x height x 4 Montgomery words, level 0 first."""
+        L, vp = self._L, ctypes.c_void_p
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        L.zkt_merkle_tree_paths.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64)]
+        out = np.empty((idx.size, self.merkle_tree_info(tree)[0], 4), dtype=np.uint64)
+        self.check(L.zkt_merkle_tree_paths(self._h, vp(tree), u64p(idx) if idx.size else None, idx.size, u64p(out) if idx.size else None))
+        return out
+
+    def merkle_tree_paths_to_variables_dev(self, tree: int, indices, d_variables: int, n_vars: int, sibling_var0, bit_var0=None):
+        """zkt_merkle_tree_paths_to_variables_dev: the siblings (and, with bit_var0, the position bits) of every index
+        written into the variable map at d_variables; enqueue only."""
+        L, vp, u32p = self._L, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        sib = np.ascontiguousarray(sibling_var0, dtype=np.uint32).reshape(-1)
+        bit = None if bit_var0 is None else np.ascontiguousarray(bit_var0, dtype=np.uint32).reshape(-1)
+        assert sib.size == idx.size and (bit is None or bit.size == idx.size)
+        L.zkt_merkle_tree_paths_to_variables_dev.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t, vp,
+                                                             ctypes.c_size_t, u32p, u32p]
+        self.check(L.zkt_merkle_tree_paths_to_variables_dev(
+            self._h, vp(tree), u64p(idx) if idx.size else None, idx.size, vp(d_variables) if d_variables else None, n_vars,
+            bit.ctypes.data_as(u32p) if bit is not None else None, sib.ctypes.data_as(u32p)))
+
+    def debug_merkle_tree_split(self, tree: int, wide_min_parents: int):
+        """zkt_debug_merkle_tree_split: 1 = every level wide, 2^31 - 1 = every level in the tail, 0 = the policy."""
+        L = self._L
+        L.zkt_debug_merkle_tree_split.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        rc = L.zkt_debug_merkle_tree_split(ctypes.c_void_p(tree), wide_min_parents)
+        if rc:
+            raise ZktError(rc, "zkt_debug_merkle_tree_split: null tree or negative threshold")
+
     # -- device memory ------------------------------------------------------------------------
     def alloc(self, nbytes: int) -> int:
         p = ctypes.c_void_p()

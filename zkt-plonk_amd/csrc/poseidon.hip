@@ -532,6 +532,254 @@ __global__ __launch_bounds__(256) void k_poseidon_merkle_path(MerklePathArgs<P> 
     if (a.out && run && l == 0) fe_store<P>(a.out + pth, cur);
 }
 
+// ---- the note tree (gadgets/src/merkle_tree.rs:57-111) ------------------------------------------------------------------
+// Layer L (0 <= L < height) is a dense array in HBM; the root (the "layer" above the last) has a slot of its own.  After
+// add_leaf of leaves 0 .. n - 1 the stored node (L, idx), idx < ceil(n / 2^L), is hash_two of its children, the empty value
+// nodes[L - 1] standing in for a right child that does not exist yet (pinned on the CPU by
+// tests/test_merkle_tree_cases_oracle.py).  Appending m leaves at s therefore recomputes, per level L, the parents
+// (s >> (L + 1)) .. ((s + m - 1) >> (L + 1)): level by level, one launch per WIDE level (k_merkle_level, one thread per
+// parent) and ONE launch of one workgroup for all the narrow ones (k_merkle_tail, PoseidonLanes<W>::LPH lanes per parent).
+// Native hashes, H form throughout: nothing of the gadget's per-step canonical variables is needed here.
+constexpr int MERKLE_TAIL_THREADS = 256;
+constexpr int MERKLE_TAIL_MAX_PARENTS = 512;    // a level the tail hashes stays in LDS for the next one: 16 + 8 KiB
+
+template <class P>
+struct MerkleHashConsts {
+    const uint32_t* rc;        // H form
+    const uint32_t* mds;       // H form, m[i][j] at (i * W + j)
+    uint32_t tag[FxP<P>::L];   // H form
+    int half_full, partial;
+};
+
+ZKT_D uint64_t merkle_shr(uint64_t x, int k) { return k >= 64 ? 0 : x >> k; }
+
+template <class P>
+struct MerkleLevelArgs {
+    MerkleHashConsts<P> h;
+    const Fe<P>* child;        // layer L
+    Fe<P>* parent;             // layer L + 1, or the root slot (its only parent is 0)
+    const Fe<P>* empty;        // nodes[L]
+    uint64_t p_lo, n_parents;  // the parents p_lo .. p_lo + n_parents - 1
+    uint64_t n_child;          // nodes of layer L after this append
+};
+
+// The permutation of k_poseidon_fx on a state held by one thread, without its optional trace: H-form limbs, the same lazy
+// bounds (state < 5.72 p on entry to every round, see the top of this file).  Kernels that hash natively with one thread per
+// hash call this; k_poseidon_fx keeps its own loop because it stores the round states in between.
+template <class P, int W>
+ZKT_D void poseidon_fx_rounds(Fx<P> (&st)[W], const uint32_t* rc, const uint32_t* mds, int half_full, int partial) {
+    static_assert(FxP<P>::L == 9, "scalar fields use nine limbs");
+    static_assert(poseidon_lazy_bound_ok<P>(), "lazy reduction needs R' >= 64 p (state < 5.72 p, its square < R' p)");
+    Fx<P> nx[W];
+    const int rounds = 2 * half_full + partial;
+#pragma unroll 1
+    for (int r = 0; r < rounds; ++r) {
+        const bool full = r < half_full || r >= half_full + partial;   // spec.rs:267-316
+#pragma unroll
+        for (int i = 0; i < W; ++i) st[i] = fx_add<P>(st[i], fx_load_limbs<P>(rc + 9 * i));
+        rc += 9 * W;
+        if (full) {
+#pragma unroll
+            for (int i = 0; i < W; ++i) {
+                const Fx<P> x2 = fx_mul<P>(st[i], st[i]);
+                st[i] = fx_mul<P>(fx_mul<P>(x2, x2), st[i]);
+            }
+        } else {
+            const Fx<P> x2 = fx_mul<P>(st[0], st[0]);
+            st[0] = fx_mul<P>(fx_mul<P>(x2, x2), st[0]);
+        }
+        // spec.rs:73-88: result[j] = sum_i m[i][j] * state[i], two products per reduction
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+            Fx<P> acc;
+            bool have = false;
+#pragma unroll
+            for (int i = 0; i + 1 < W; i += 2) {
+                const Fx<P> t = fx_mul2_inl<P>(st[i], fx_load_limbs<P>(mds + 9 * (i * W + j)), st[i + 1],
+                                               fx_load_limbs<P>(mds + 9 * ((i + 1) * W + j)));
+                acc = have ? fx_add<P>(acc, t) : t;
+                have = true;
+            }
+            if (W & 1) {
+                const Fx<P> t = fx_mul<P>(st[W - 1], fx_load_limbs<P>(mds + 9 * ((W - 1) * W + j)));
+                acc = have ? fx_add<P>(acc, t) : t;
+            }
+            nx[j] = acc;
+        }
+#pragma unroll
+        for (int j = 0; j < W; ++j) st[j] = nx[j];
+    }
+}
+
+// One thread per parent: hash_two on state [tag, left, right, 0 ...].  The two children are one contiguous 64-byte pair; a
+// right child past the end of the layer is the empty value.
+template <class P, int W>
+__global__ __launch_bounds__(128) void k_merkle_level(MerkleLevelArgs<P> a) {
+    static_assert(W >= 3, "hash_two needs two input elements behind the tag");
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= a.n_parents) return;
+    const uint64_t p = a.p_lo + t;
+    Fx<P> st[W];
+#pragma unroll
+    for (int i = 0; i < FxP<P>::L; ++i) st[0].l[i] = a.h.tag[i];
+    st[1] = fx_from_ark<P>(fe_load<P>(a.child + 2 * p));
+    st[2] = fx_from_ark<P>(fe_load<P>(2 * p + 1 < a.n_child ? a.child + 2 * p + 1 : a.empty));
+#pragma unroll
+    for (int i = 3; i < W; ++i) st[i] = fx_zero<P>();
+    poseidon_fx_rounds<P, W>(st, a.h.rc, a.h.mds, a.h.half_full, a.h.partial);
+    fe_store<P>(a.parent + p, fx_to_ark<P>(st[1]));   // spec.rs:315: elements[1]
+}
+
+// hash_two(left, right) spread over the LPH lanes of a segment (the layout of poseidon_lanes_rounds), natively: H-form
+// limbs, no variable leaves, so the only canonical values are the terms of the matrix product (a sum of up to eight of
+// them would otherwise reach 10 p, and (10 p)^2 > R' p on BLS12-381).  Bounds: a term is cond_sub(product) < p, the running
+// sums stay < p, the state entering a round is < 2p (first round < 3p: from_ark gives < 2p), plus its constant < 3p (< 4p);
+// the s-box squares that: 16 p^2 < 64 p^2 <= R' p; its later products take operands < 2p and < 4p.  Every lane of the
+// wavefront must call it.  Returns the hash (canonical, arkworks form) in EVERY lane of the segment.
+template <class P, int W>
+ZKT_D Fe<P> merkle_hash_two_lanes(const MerkleHashConsts<P>& h, const Fx<P>& m, const Fe<P>& left, const Fe<P>& right, int lane,
+                                  int seg0, int i) {
+    Fx<P> x = fx_from_ark<P>(i == 1 ? left : right);
+    if (i == 0) {
+#pragma unroll
+        for (int k = 0; k < FxP<P>::L; ++k) x.l[k] = h.tag[k];
+    } else if (i > 2) {
+        x = fx_zero<P>();
+    }
+    const uint32_t* rc = h.rc + 9 * i;
+    const int rounds = 2 * h.half_full + h.partial;
+#pragma unroll 1
+    for (int r = 0; r < rounds; ++r) {
+        const bool full = r < h.half_full || r >= h.half_full + h.partial;
+        x = fx_add<P>(x, fx_load_limbs<P>(rc));
+        rc += 9 * W;
+        const Fx<P> x2 = fx_mul<P>(x, x);
+        const Fx<P> x5 = fx_mul<P>(fx_mul<P>(x2, x2), x);
+        const bool boxed = full || i == 0;
+        Fx<P> s;
+#pragma unroll
+        for (int k = 0; k < FxP<P>::L; ++k) s.l[k] = boxed ? x5.l[k] : x.l[k];
+        Fx<P> t = fx_cond_sub_p<P>(fx_mul<P>(s, m));
+#pragma unroll
+        for (int d = 1; d < W; d <<= 1) {
+            const Fx<P> o = fx_shfl<P>(t, lane - d);      // lane - d >= 0 whenever it is used (i >= d)
+            if (i >= d) t = fx_cond_sub_p<P>(fx_add<P>(t, o));
+        }
+        x = fx_shfl<P>(t, seg0 + i * W + (W - 1));
+    }
+    return fx_to_ark<P>(fx_shfl<P>(x, seg0 + 1));          // elements[1] (spec.rs:315)
+}
+
+template <class P>
+struct MerkleTailArgs {
+    MerkleHashConsts<P> h;
+    Fe<P>* const* layers;      // height device pointers
+    Fe<P>* root;
+    const Fe<P>* empties;      // nodes[0 .. height)
+    uint64_t s, m;             // the append: leaves s .. s + m - 1 (m >= 1)
+    int level0, height;        // levels level0 .. height - 1; at most MERKLE_TAIL_MAX_PARENTS parents at level0
+};
+
+// All the narrow levels of one append in one workgroup.  Per level the parents are dealt out to the workgroup's
+// 4 PER_WAVE lane groups, round after round when there are more.  A parent goes to its layer in HBM and to LDS, where
+// the next level finds it after the barrier: the kernel never reads from HBM a node it wrote.  What it does read from
+// there: both children at level0 (an earlier launch wrote them), the left neighbour of the first new child (an earlier
+// append), the empty values.
+template <class P, int W>
+__global__ __launch_bounds__(MERKLE_TAIL_THREADS) void k_merkle_tail(MerkleTailArgs<P> a) {
+    static_assert(FxP<P>::L == 9 && poseidon_lazy_bound_ok<P>(), "scalar fields: nine limbs, R' >= 64 p");
+    static_assert(W >= 3, "hash_two needs two input elements behind the tag");
+    constexpr int LPH = PoseidonLanes<W>::LPH, PER_WAVE = PoseidonLanes<W>::PER_WAVE;
+    constexpr int GROUPS = MERKLE_TAIL_THREADS / 64 * PER_WAVE;
+    __shared__ Fe<P> lds_a[MERKLE_TAIL_MAX_PARENTS], lds_b[MERKLE_TAIL_MAX_PARENTS / 2 + 1];
+    const int lane = threadIdx.x & 63;
+    const int l = lane % LPH, seg0 = lane - l;
+    const int group = (threadIdx.x >> 6) * PER_WAVE + lane / LPH;
+    const bool live = l < W * W;
+    const int i = live ? l % W : 0, j = live ? l / W : 0;
+    const Fx<P> m = fx_load_limbs<P>(a.h.mds + 9 * (i * W + j));
+    const Fe<P>* cur = nullptr;      // the nodes lo_c .. hi_c of layer L made by this launch (L > level0)
+    Fe<P>* nxt = lds_a;
+    const uint64_t last = a.s + (a.m - 1);
+#pragma unroll 1
+    for (int L = a.level0; L < a.height; ++L) {
+        const uint64_t lo_c = merkle_shr(a.s, L), hi_c = merkle_shr(last, L);
+        const uint64_t p_lo = lo_c >> 1, n_parents = (hi_c >> 1) - p_lo + 1;
+        const Fe<P>* child = a.layers[L];
+        Fe<P>* parent = L + 1 < a.height ? a.layers[L + 1] : a.root;
+        const Fe<P>* empty = a.empties + L;
+#pragma unroll 1
+        for (uint64_t base = 0; base < n_parents; base += GROUPS) {
+            const bool have = base + group < n_parents;   // groups without a parent run along (the shuffles are wave-wide)
+            const uint64_t p = p_lo + (have ? base + group : 0);
+            const uint64_t cl = 2 * p, cr = 2 * p + 1;
+            const Fe<P> left = (cur && cl >= lo_c) ? cur[cl - lo_c] : fe_load<P>(child + cl);
+            const Fe<P> right = cr > hi_c ? fe_load<P>(empty) : cur ? cur[cr - lo_c] : fe_load<P>(child + cr);
+            const Fe<P> hsh = merkle_hash_two_lanes<P, W>(a.h, m, left, right, lane, seg0, i);
+            if (have && l == 0) {
+                fe_store<P>(parent + p, hsh);
+                nxt[p - p_lo] = hsh;
+            }
+        }
+        __syncthreads();
+        cur = nxt;
+        nxt = nxt == lds_a ? lds_b : lds_a;
+    }
+}
+
+// The empty-subtree values at create time (merkle_tree.rs:57-67): nodes[0] = 0, nodes[L + 1] = hash_two(nodes[L], nodes[L]).
+// One wavefront, the chain in the registers of its first lane group (the other groups run along).
+template <class P, int W>
+__global__ __launch_bounds__(64) void k_merkle_empty(MerkleHashConsts<P> h, Fe<P>* empties, int height) {
+    constexpr int LPH = PoseidonLanes<W>::LPH;
+    const int lane = threadIdx.x & 63;
+    const int l = lane % LPH, seg0 = lane - l;
+    const bool live = l < W * W;
+    const int i = live ? l % W : 0, j = live ? l / W : 0;
+    const Fx<P> m = fx_load_limbs<P>(h.mds + 9 * (i * W + j));
+    Fe<P> cur;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) cur.v[k] = 0;
+#pragma unroll 1
+    for (int L = 0; L < height; ++L) {
+        if (lane == 0) fe_store<P>(empties + L, cur);
+        if (L + 1 < height) cur = merkle_hash_two_lanes<P, W>(h, m, cur, cur, lane, seg0, i);
+    }
+}
+
+template <class P>
+struct MerklePathsArgs {
+    const Fe<P>* const* layers;
+    const Fe<P>* empties;
+    const uint64_t* index;     // k leaf indices
+    const uint32_t* sib0;      // per path, or null: p * height
+    const uint32_t* bit0;      // per path, or null: no bits
+    Fe<P>* dst;                // the variable map, or k x height siblings
+    uint64_t count, total;     // leaves in the tree; k * height threads
+    int height;
+};
+
+// merkle_path (merkle_tree.rs:77-87): one thread per (path, layer) moves one 32-byte element -- the stored sibling, or
+// nodes[layer] when the tree has none there -- and, optionally, writes the position bit as the Montgomery 0 or 1.
+template <class P>
+__global__ __launch_bounds__(256) void k_merkle_paths(MerklePathsArgs<P> a) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= a.total) return;
+    const uint64_t p = t / (uint64_t)a.height;
+    const int layer = (int)(t - p * (uint64_t)a.height);
+    const uint64_t idx = a.index[p] >> layer;                       // layer < height <= 64
+    const uint64_t sib = idx ^ 1;
+    const uint64_t n_layer = a.count ? ((a.count - 1) >> layer) + 1 : 0;
+    const Fe<P> v = fe_load<P>(sib < n_layer ? a.layers[layer] + sib : a.empties + layer);
+    fe_store<P>(a.dst + (a.sib0 ? (uint64_t)a.sib0[p] : p * (uint64_t)a.height) + layer, v);
+    if (a.bit0) {
+        Fe<P> b;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) b.v[k] = (idx & 1) ? P::one(k) : 0u;
+        fe_store<P>(a.dst + (uint64_t)a.bit0[p] + layer, b);
+    }
+}
+
 }  // namespace zkt
 
 // the opaque handle of include/zkt_plonk.h: PoseidonConstants resident in HBM
@@ -729,6 +977,178 @@ static int merkle_path_check_args(zkt_ctx* c, const zkt_poseidon* h, const zkt_m
         return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "merkle path: null leaf, bit or sibling index vector");
     if (g->n_vars > 0xFFFFFFFFull) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "variable indices are 32 bits wide");
     *enqueue = true;
+    return ZKT_OK;
+}
+
+}  // namespace zkt
+
+// the opaque handle of include/zkt_plonk.h: MerkleTree<F, G, H, HEIGHT> resident in HBM
+struct zkt_merkle_tree {
+    int curve = 0, height = 0;
+    const zkt_poseidon* pos = nullptr;   // borrowed
+    uint64_t count = 0, capacity = 0;
+    std::vector<size_t> layer_len;       // elements of layer L: max(1, ceil(capacity / 2^L))
+    void* d_nodes = nullptr;             // all the layers, one after the other
+    void* d_layers = nullptr;            // height device pointers into d_nodes
+    void* d_empties = nullptr;           // nodes[0 .. height)
+    void* d_root = nullptr;
+    // the index table of zkt_merkle_tree_paths*: k x (u64 index), k x (u32 sibling_var0), k x (u32 bit_var0), packed
+    void* d_table = nullptr;
+    void* h_table = nullptr;             // pinned: the upload is a stream copy, the caller's arrays are free on return
+    hipEvent_t table_up = nullptr;       // the last upload out of h_table
+    bool table_busy = false;
+    int wide_min_parents = 0;            // zkt_debug_merkle_tree_split: 0 = the policy
+};
+
+namespace zkt {
+
+// Levels with at least this many parents get a launch of their own (one thread per parent: a permutation's full serial
+// latency, whatever the count); narrower ones share the tail's single workgroup (a W-th of that latency per 4 PER_WAVE
+// parents).  64 is the minimum of the sweep 2 .. 512 on an MI355X at x5, m = 2^10 and 2^16 (32 within 1 %, 128 4 - 5 % worse):
+// docs/EXPERIMENTS.md, "note tree on the device".  Other widths were not swept.
+constexpr int MERKLE_WIDE_MIN_PARENTS = 64;
+
+static uint64_t merkle_shr_h(uint64_t x, int k) { return k >= 64 ? 0 : x >> k; }
+
+template <class P>
+static MerkleHashConsts<P> merkle_consts(const zkt_poseidon* h) {
+    MerkleHashConsts<P> k{};
+    k.rc = (const uint32_t*)h->d_rc;
+    k.mds = (const uint32_t*)h->d_mds;
+    for (int i = 0; i < 9; ++i) k.tag[i] = h->tag[i];
+    k.half_full = h->half_full;
+    k.partial = h->partial;
+    return k;
+}
+
+template <class P>
+static Fe<P>* merkle_layer(const zkt_merkle_tree* t, int L) {
+    size_t off = 0;
+    for (int k = 0; k < L; ++k) off += t->layer_len[k];
+    return (Fe<P>*)t->d_nodes + off;
+}
+
+template <class P, int W>
+static void merkle_launch_w(zkt_ctx* c, const MerkleLevelArgs<P>* lv, const MerkleTailArgs<P>* tail, const MerkleHashConsts<P>* empty,
+                            Fe<P>* empties, int height) {
+    if constexpr (W >= 3) {
+        if (lv)
+            hipLaunchKernelGGL((k_merkle_level<P, W>), dim3((unsigned)((lv->n_parents + 127) / 128)), dim3(128), 0, c->stream, *lv);
+        if (tail) hipLaunchKernelGGL((k_merkle_tail<P, W>), dim3(1), dim3(MERKLE_TAIL_THREADS), 0, c->stream, *tail);
+        if (empty) hipLaunchKernelGGL((k_merkle_empty<P, W>), dim3(1), dim3(64), 0, c->stream, *empty, empties, height);
+    }
+}
+
+template <class P>
+static void merkle_launch(zkt_ctx* c, int width, const MerkleLevelArgs<P>* lv, const MerkleTailArgs<P>* tail,
+                          const MerkleHashConsts<P>* empty = nullptr, Fe<P>* empties = nullptr, int height = 0) {
+    switch (width) {
+        case 3: merkle_launch_w<P, 3>(c, lv, tail, empty, empties, height); break;
+        case 4: merkle_launch_w<P, 4>(c, lv, tail, empty, empties, height); break;
+        case 5: merkle_launch_w<P, 5>(c, lv, tail, empty, empties, height); break;
+        case 6: merkle_launch_w<P, 6>(c, lv, tail, empty, empties, height); break;
+        case 7: merkle_launch_w<P, 7>(c, lv, tail, empty, empties, height); break;
+        default: merkle_launch_w<P, 8>(c, lv, tail, empty, empties, height); break;
+    }
+}
+
+// the launches of one append after the leaves are in layer 0: leaves s .. s + m - 1, m >= 1
+template <class P>
+static int merkle_append_levels_t(zkt_ctx* c, zkt_merkle_tree* t, uint64_t s, uint64_t m) {
+    const uint64_t last = s + (m - 1);
+    const uint64_t thr = t->wide_min_parents ? (uint64_t)t->wide_min_parents : (uint64_t)MERKLE_WIDE_MIN_PARENTS;
+    const MerkleHashConsts<P> k = merkle_consts<P>(t->pos);
+    int L = 0;
+    for (; L < t->height; ++L) {
+        const uint64_t p_lo = merkle_shr_h(s, L + 1), n_parents = merkle_shr_h(last, L + 1) - p_lo + 1;
+        // the tail keeps a level in LDS: a level it cannot hold is a launch of its own whatever the threshold says
+        if (n_parents < thr && n_parents <= (uint64_t)MERKLE_TAIL_MAX_PARENTS) break;
+        MerkleLevelArgs<P> a{};
+        a.h = k;
+        a.child = merkle_layer<P>(t, L);
+        a.parent = L + 1 < t->height ? merkle_layer<P>(t, L + 1) : (Fe<P>*)t->d_root;
+        a.empty = (const Fe<P>*)t->d_empties + L;
+        a.p_lo = p_lo;
+        a.n_parents = n_parents;
+        a.n_child = merkle_shr_h(last, L) + 1;
+        merkle_launch<P>(c, t->pos->width, &a, nullptr);
+    }
+    if (L < t->height) {
+        MerkleTailArgs<P> a{};
+        a.h = k;
+        a.layers = (Fe<P>* const*)t->d_layers;
+        a.root = (Fe<P>*)t->d_root;
+        a.empties = (const Fe<P>*)t->d_empties;
+        a.s = s;
+        a.m = m;
+        a.level0 = L;
+        a.height = t->height;
+        merkle_launch<P>(c, t->pos->width, nullptr, &a);
+    }
+    ZKT_HIP(c, hipGetLastError());
+    return ZKT_OK;
+}
+
+template <class P>
+static int merkle_create_t(zkt_ctx* c, zkt_merkle_tree* t) {
+    std::vector<Fe<P>*> ptrs(t->height);
+    for (int L = 0; L < t->height; ++L) ptrs[L] = merkle_layer<P>(t, L);
+    ZKT_HIP(c, hipMemcpyAsync(t->d_layers, ptrs.data(), ptrs.size() * sizeof(void*), hipMemcpyHostToDevice, c->stream));
+    ZKT_HIP(c, hipMemsetAsync(t->d_root, 0, 32, c->stream));
+    const MerkleHashConsts<P> k = merkle_consts<P>(t->pos);
+    merkle_launch<P>(c, t->pos->width, nullptr, nullptr, &k, (Fe<P>*)t->d_empties, t->height);
+    ZKT_HIP(c, hipGetLastError());
+    ZKT_HIP(c, hipStreamSynchronize(c->stream));   // the pointer table dies with this call
+    return ZKT_OK;
+}
+
+template <class P>
+static int merkle_paths_enqueue_t(zkt_ctx* c, zkt_merkle_tree* t, size_t k, bool scattered, bool bits, void* dst) {
+    MerklePathsArgs<P> a{};
+    a.layers = (const Fe<P>* const*)t->d_layers;
+    a.empties = (const Fe<P>*)t->d_empties;
+    a.index = (const uint64_t*)t->d_table;
+    a.sib0 = scattered ? (const uint32_t*)((const char*)t->d_table + 8 * k) : nullptr;
+    a.bit0 = bits ? (const uint32_t*)((const char*)t->d_table + 12 * k) : nullptr;
+    a.dst = (Fe<P>*)dst;
+    a.count = t->count;
+    a.total = (uint64_t)k * (uint64_t)t->height;
+    a.height = t->height;
+    hipLaunchKernelGGL((k_merkle_paths<P>), dim3((unsigned)((a.total + 255) / 256)), dim3(256), 0, c->stream, a);
+    ZKT_HIP(c, hipGetLastError());
+    return ZKT_OK;
+}
+
+static int merkle_check(zkt_ctx* c, const zkt_merkle_tree* t) {
+    if (!c || !t) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
+    if (t->curve != c->curve) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "merkle tree: the tree belongs to another curve");
+    return ZKT_OK;
+}
+
+// the index table of one paths call goes up from the tree's pinned buffer; a table still on its way (the previous call's) is
+// waited for first -- the only wait of the enqueue-only entry, and only when two calls follow each other that closely
+static int merkle_table_upload(zkt_ctx* c, zkt_merkle_tree* t, const uint64_t* indices, size_t k, const uint32_t* sib0,
+                               const uint32_t* bit0) {
+    if (t->table_busy) {
+        ZKT_HIP(c, hipEventSynchronize(t->table_up));
+        t->table_busy = false;
+    }
+    char* h = (char*)t->h_table;
+    memcpy(h, indices, 8 * k);
+    if (sib0) memcpy(h + 8 * k, sib0, 4 * k);
+    if (bit0) memcpy(h + 12 * k, bit0, 4 * k);
+    ZKT_HIP(c, hipMemcpyAsync(t->d_table, h, 16 * k, hipMemcpyHostToDevice, c->stream));
+    ZKT_HIP(c, hipEventRecord(t->table_up, c->stream));
+    t->table_busy = true;
+    return ZKT_OK;
+}
+
+static int merkle_check_indices(zkt_ctx* c, const zkt_merkle_tree* t, const uint64_t* indices, size_t k) {
+    if (k > ZKT_MERKLE_TREE_PATHS_MAX) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "merkle tree: at most ZKT_MERKLE_TREE_PATHS_MAX paths a call");
+    if (k && !indices) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
+    if (t->height < 64)
+        for (size_t i = 0; i < k; ++i)
+            if (indices[i] >> t->height) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "merkle tree: a leaf index is not below 2^height");
     return ZKT_OK;
 }
 
@@ -968,6 +1388,180 @@ int zkt_poseidon_hash_batch(zkt_ctx* c, const zkt_poseidon_params* p, const uint
     dev_free(c, d_st);
     zkt_poseidon_free(c, h);
     return rc;
+}
+
+// ---- the note tree -------------------------------------------------------------------------------------------------------
+int zkt_merkle_tree_create(zkt_ctx* c, const zkt_poseidon* h, int height, size_t capacity, zkt_merkle_tree** out) {
+    if (!c || !h || !out) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
+    if (h->curve != c->curve) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "poseidon parameters belong to another curve");
+    if (h->width < 3)
+        return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "merkle tree: hash_two needs width >= 3 (spec.rs:253-257 FullBuffer)");
+    if (height < 1 || height > 64) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "merkle tree: 1 <= height <= 64");
+    if (capacity < 1 || capacity > ZKT_MERKLE_TREE_MAX || (height < 64 && (capacity >> height) && capacity != ((size_t)1 << height)))
+        return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "merkle tree: 1 <= capacity <= min(2^height, ZKT_MERKLE_TREE_MAX)");
+    (void)hipSetDevice(c->device);
+    zkt_merkle_tree* t = new zkt_merkle_tree();
+    t->curve = c->curve;
+    t->height = height;
+    t->pos = h;
+    t->capacity = capacity;
+    size_t total = 0;
+    for (int L = 0; L < height; ++L) {
+        const size_t len = std::max<size_t>(1, (size_t)merkle_shr_h(capacity - 1, L) + 1);
+        t->layer_len.push_back(len);
+        total += len;
+    }
+    auto make = [&]() -> int {
+        int rc;
+        if ((rc = dev_alloc(c, &t->d_nodes, total * 32))) return rc;
+        if ((rc = dev_alloc(c, &t->d_layers, (size_t)height * sizeof(void*)))) return rc;
+        if ((rc = dev_alloc(c, &t->d_empties, (size_t)height * 32))) return rc;
+        if ((rc = dev_alloc(c, &t->d_root, 32))) return rc;
+        if ((rc = dev_alloc(c, &t->d_table, (size_t)ZKT_MERKLE_TREE_PATHS_MAX * 16))) return rc;
+        ZKT_HIP(c, hipHostMalloc(&t->h_table, (size_t)ZKT_MERKLE_TREE_PATHS_MAX * 16));
+        ZKT_HIP(c, hipEventCreateWithFlags(&t->table_up, hipEventDisableTiming));
+        return c->curve == ZKT_CURVE_BN254 ? merkle_create_t<Bn254Fr>(c, t) : merkle_create_t<Bls381Fr>(c, t);
+    };
+    if (const int rc = make()) {
+        zkt_merkle_tree_free(c, t);
+        return rc;
+    }
+    *out = t;
+    return ZKT_OK;
+}
+
+void zkt_merkle_tree_free(zkt_ctx* c, zkt_merkle_tree* t) {
+    if (!t) return;
+    if (c) {
+        (void)hipStreamSynchronize(c->stream);
+        dev_free(c, t->d_nodes);
+        dev_free(c, t->d_layers);
+        dev_free(c, t->d_empties);
+        dev_free(c, t->d_root);
+        dev_free(c, t->d_table);
+    }
+    if (t->h_table) (void)hipHostFree(t->h_table);
+    if (t->table_up) (void)hipEventDestroy(t->table_up);
+    delete t;
+}
+
+int zkt_merkle_tree_info(const zkt_merkle_tree* t, int* height, uint64_t* count, uint64_t* capacity) {
+    if (!t) return ZKT_ERR_INVALID_ARGUMENT;
+    if (height) *height = t->height;
+    if (count) *count = t->count;
+    if (capacity) *capacity = t->capacity;
+    return ZKT_OK;
+}
+
+// host = the leaves are in host memory: they go straight into layer 0 and the call synchronises
+static int merkle_append(zkt_ctx* c, zkt_merkle_tree* t, const void* leaves, size_t m, uint64_t* first_index, bool host) {
+    if (int rc = merkle_check(c, t)) return rc;
+    if (first_index) *first_index = t->count;
+    if (m == 0) return ZKT_OK;
+    if (!leaves) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
+    if (m > t->capacity - t->count) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "merkle tree: the leaves do not fit the tree's capacity");
+    (void)hipSetDevice(c->device);
+    const uint64_t s = t->count;
+    {
+        ProfScope ps(c, "merkle_append");
+        ZKT_HIP(c, hipMemcpyAsync((char*)t->d_nodes + s * 32, leaves, m * 32, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice,
+                                  c->stream));
+        const int rc = c->curve == ZKT_CURVE_BN254 ? merkle_append_levels_t<Bn254Fr>(c, t, s, m) : merkle_append_levels_t<Bls381Fr>(c, t, s, m);
+        if (rc) return rc;   // a launch was refused: the count stays, but layers above 0 may be half made (see the header)
+        t->count = s + m;
+    }
+    if (host) ZKT_HIP(c, hipStreamSynchronize(c->stream));
+    return ZKT_OK;
+}
+
+int zkt_merkle_tree_append_dev(zkt_ctx* c, zkt_merkle_tree* t, const void* d_leaves, size_t m, uint64_t* first_index) {
+    return merkle_append(c, t, d_leaves, m, first_index, false);
+}
+
+int zkt_merkle_tree_append(zkt_ctx* c, zkt_merkle_tree* t, const uint64_t* leaves, size_t m, uint64_t* first_index) {
+    return merkle_append(c, t, leaves, m, first_index, true);
+}
+
+int zkt_merkle_tree_root(zkt_ctx* c, zkt_merkle_tree* t, uint64_t* out4) {
+    if (int rc = merkle_check(c, t)) return rc;
+    if (!out4) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
+    (void)hipSetDevice(c->device);
+    ZKT_HIP(c, hipMemcpyAsync(out4, t->d_root, 32, hipMemcpyDeviceToHost, c->stream));
+    ZKT_HIP(c, hipStreamSynchronize(c->stream));
+    return ZKT_OK;
+}
+
+int zkt_merkle_tree_layer(zkt_ctx* c, zkt_merkle_tree* t, int layer, uint64_t first, size_t n, uint64_t* out) {
+    if (int rc = merkle_check(c, t)) return rc;
+    if (layer < 0 || layer >= t->height) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "merkle tree: 0 <= layer < height (the root has its own call)");
+    const uint64_t have = t->count ? merkle_shr_h(t->count - 1, layer) + 1 : 0;
+    if (first > have || n > have - first) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "merkle tree: the range reaches past the layer's stored nodes");
+    if (n == 0) return ZKT_OK;
+    if (!out) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
+    (void)hipSetDevice(c->device);
+    size_t off = first;
+    for (int k = 0; k < layer; ++k) off += t->layer_len[k];
+    ZKT_HIP(c, hipMemcpyAsync(out, (const char*)t->d_nodes + off * 32, n * 32, hipMemcpyDeviceToHost, c->stream));
+    ZKT_HIP(c, hipStreamSynchronize(c->stream));
+    return ZKT_OK;
+}
+
+int zkt_merkle_tree_paths(zkt_ctx* c, zkt_merkle_tree* t, const uint64_t* indices, size_t k, uint64_t* out_siblings) {
+    if (int rc = merkle_check(c, t)) return rc;
+    if (int rc = merkle_check_indices(c, t, indices, k)) return rc;
+    if (k == 0) return ZKT_OK;
+    if (!out_siblings) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
+    (void)hipSetDevice(c->device);
+    const size_t bytes = k * (size_t)t->height * 32;
+    void* d_out = nullptr;
+    auto run = [&]() -> int {
+        int rc;
+        if ((rc = dev_alloc(c, &d_out, bytes))) return rc;
+        {
+            ProfScope ps(c, "merkle_paths");
+            if ((rc = merkle_table_upload(c, t, indices, k, nullptr, nullptr))) return rc;
+            rc = c->curve == ZKT_CURVE_BN254 ? merkle_paths_enqueue_t<Bn254Fr>(c, t, k, false, false, d_out)
+                                             : merkle_paths_enqueue_t<Bls381Fr>(c, t, k, false, false, d_out);
+            if (rc) return rc;
+        }
+        ZKT_HIP(c, hipMemcpyAsync(out_siblings, d_out, bytes, hipMemcpyDeviceToHost, c->stream));
+        ZKT_HIP(c, hipStreamSynchronize(c->stream));
+        return ZKT_OK;
+    };
+    const int rc = run();
+    if (rc) (void)hipStreamSynchronize(c->stream);
+    dev_free(c, d_out);
+    return rc;
+}
+
+int zkt_merkle_tree_paths_to_variables_dev(zkt_ctx* c, zkt_merkle_tree* t, const uint64_t* indices, size_t k, void* d_variables,
+                                           size_t n_vars, const uint32_t* bit_var0, const uint32_t* sibling_var0) {
+    if (int rc = merkle_check(c, t)) return rc;
+    if (int rc = merkle_check_indices(c, t, indices, k)) return rc;
+    if (k == 0) return ZKT_OK;
+    if (!d_variables || !sibling_var0) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
+    // every range inside the map, no two of them overlapping: sorted by their first variable, neighbours are >= height apart
+    const uint64_t H = (uint64_t)t->height;
+    std::vector<uint64_t> starts(sibling_var0, sibling_var0 + k);
+    if (bit_var0) starts.insert(starts.end(), bit_var0, bit_var0 + k);
+    std::sort(starts.begin(), starts.end());
+    for (size_t i = 0; i < starts.size(); ++i) {
+        if (starts[i] > n_vars || H > n_vars - starts[i])
+            return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "merkle tree: a sibling or bit range lies outside the variable map");
+        if (i && starts[i] < starts[i - 1] + H)
+            return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "merkle tree: two sibling or bit ranges overlap");
+    }
+    (void)hipSetDevice(c->device);
+    ProfScope ps(c, "merkle_paths");
+    if (int rc = merkle_table_upload(c, t, indices, k, sibling_var0, bit_var0)) return rc;
+    return c->curve == ZKT_CURVE_BN254 ? merkle_paths_enqueue_t<Bn254Fr>(c, t, k, true, bit_var0 != nullptr, d_variables)
+                                       : merkle_paths_enqueue_t<Bls381Fr>(c, t, k, true, bit_var0 != nullptr, d_variables);
+}
+
+int zkt_debug_merkle_tree_split(zkt_merkle_tree* t, int wide_min_parents) {
+    if (!t || wide_min_parents < 0) return ZKT_ERR_INVALID_ARGUMENT;
+    t->wide_min_parents = wide_min_parents;
+    return ZKT_OK;
 }
 
 }  // extern "C"
