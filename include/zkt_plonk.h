@@ -323,6 +323,19 @@ int zkt_kzg_open_dev(zkt_ctx* ctx, const void* const* d_coeffs, const size_t* le
  * MSM's time is its additions, 2 = whenever a table can be built.  Forks inherit the mode. */
 int zkt_ctx_set_lagrange(zkt_ctx* ctx, int on);
 int zkt_ctx_set_wire_elimination(zkt_ctx* ctx, int mode);
+/* The quotient of round 4 on three classes of the 4n coset (single GPU).  The quotient has 3n + 6 coefficients, six of
+ * them fixed by the blinded polynomials' top coefficients alone, so its values on the classes 0, 1, 2 of g <w_4n> (the
+ * points g w_4n^(j + 4i)) determine it: seven witness polynomials go through three n-point class transforms instead of
+ * one of 4n points, the quotient kernel covers 3n points, and three inverse class transforms, one 3 x 3 combination and
+ * the six top coefficients (formed on the host from windows of 14 coefficients) give the same 4n coefficients.  The
+ * proof bytes are those of the whole-coset route.  An unsatisfied circuit, which the whole coset shows as coefficients
+ * above 3n + 5, is refused through the verifier's identity at xi instead (r(xi) against the constant of compute_r0), with
+ * the same code, ZKT_ERR_QUOTIENT_TOO_SHORT.  Costs [3][n] class copies of the twelve coset tables (36 n elements of
+ * device memory, made by the first proof that takes the route; forks made afterwards share them).
+ * zkt_ctx_set_quotient_route(ctx, mode): 0 = automatic (the default): three classes for single-GPU circuits of 2^20 rows
+ * and more, 1 = three classes, 2 = the whole coset.  A sharded context always uses the whole coset (each GPU its class).
+ * Forks inherit the mode. */
+int zkt_ctx_set_quotient_route(zkt_ctx* ctx, int mode);
 /* *log_n = domain the table serves (-1: none, evaluations go through their coefficients), *bases = its points */
 int zkt_lagrange_info(zkt_ctx* ctx, int* log_n, size_t* bases);
 /* PC::commit of poly_from_evals(domain, evals) (util.rs:63-86) with k in 0..3 blinders added as add_blinders_to_poly
@@ -905,6 +918,17 @@ int zkt_debug_pairing_selftest(int curve_id);
  * Montgomery words.  Whole-coset (single-GPU) circuits only. */
 int zkt_debug_quotient(zkt_ctx* ctx, const uint64_t* challenges, const uint64_t* const* wit, const uint64_t* pi_pos,
                        const uint64_t* pi_vals, size_t n_pi, uint64_t* out);
+/* The quotient on three classes (zkt_ctx_set_quotient_route).  _top: the six top coefficients u = t_{3n} .. t_{3n+5} the
+ * host formed for the last proof that took the route (6 x 4 words, zero before the first); *out_on_classes (may be NULL) = the last proof's
+ * route.  _coeffs: the first `count` <= 4n elements of the quotient vector as the last proof left it (the coefficients
+ * of t on either route).  _classes_host: the host arithmetic alone, no device and no context: windows = the
+ * coefficients n - 6 .. n + 7 of a b c z1 z2 t sigma1 sigma2 sigma3 q_lookup (10 x 14 x 4 words), challenges = alpha
+ * beta delta (3 x 4 words); out_u: 6 x 4 words; out_consts: 16 x 4 words: X^n on the classes 0..3, the inverse of the
+ * Vandermonde matrix in the first three (row-major), the first three powers of the fourth.  Montgomery words. */
+int zkt_debug_quotient_top(zkt_ctx* ctx, uint64_t* out_u, int* out_on_classes);
+int zkt_debug_quotient_coeffs(zkt_ctx* ctx, uint64_t* out, size_t count);
+int zkt_debug_quotient_classes_host(int curve, int log_n, const uint64_t* windows, const uint64_t* challenges, uint64_t* out_u,
+                                    uint64_t* out_consts);
 /* The two grand products alone over the loaded circuit's permutation and domain (rows a8 / a9: compute_z1_poly's and
  * compute_z2_poly's evaluation vectors, permutation/mod.rs:181-254, lookup/mod.rs:94-151), through the launches round 3 of
  * the prover makes.  challenges: beta gamma delta epsilon (4 x 4 words); vectors: a b c f t h1 h2, n elements each, host;

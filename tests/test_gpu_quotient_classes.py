@@ -1,0 +1,243 @@
+"""The quotient of round 4 on three classes of the 4n coset (zkt_ctx_set_quotient_route, csrc/prover.hip "quotient on
+classes") against the whole-coset route and the CPU oracle: the same proof bytes, the same refusals.  Sizes: n = 8 and 16
+(the degree bounds behind the six top coefficients are tight; single-workgroup transforms), 128, and 2048 (multi-pass
+transforms, a second scan block, a second evaluation segment, more public inputs than the quotient kernel evaluates
+directly)."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+from oracle import fields as F, plonk as P, coracle as K
+from helpers import field_elems
+
+CURVES = [F.BN254, F.BLS12_381]
+SIZES = [8, 16, 128, 2048]
+SHAPE = {8: dict(gates=7, table=4, n_public=1, lookup_every=3), 16: dict(gates=14, table=8, n_public=2, lookup_every=5),
+         128: dict(gates=120, table=16, n_public=7, lookup_every=16), 2048: dict(gates=2000, table=64, n_public=20, lookup_every=16)}
+CLASSES, WHOLE = 1, 2
+
+
+def _synthetic(cv, n, value_seed):
+    s = SHAPE[n]
+    cs = P.synthetic_circuit(cv, s["gates"], s["table"], seed=n, n_public=s["n_public"], lookup_every=s["lookup_every"],
+                             value_seed=value_seed)
+    assert cs.check_satisfied() and cs.circuit_bound() == n
+    return cs
+
+
+def _constant_b(cv, n):
+    """Every gate's right wire is Variable::Zero: b's evaluations are all zero, its polynomial is trimmed to nothing and its
+    blinders land at X^0 and X^1, where add_blinders_to_poly (prove.rs:472-483) cancels them again.  (Any other constant
+    leaves a polynomial the reference cannot prove with: blinders below X^n change its values on the domain.)"""
+    s = SHAPE[n]
+    table = [3 + 7 * i for i in range(s["table"])]
+    cs = P.ConstraintSystem(cv, table, s["table"])
+    x = cs.assign_variable(11)
+    while cs.n_gates < s["gates"] - 1:
+        g = cs.n_gates
+        if g % 4 == 3:
+            cs.lookup_constrain(cs.assign_variable(table[g % len(table)]))
+        else:
+            ql, qc = 2 + g, 5 + g
+            z = cs.assign_variable(ql * cs.value_of(x) + qc)
+            cs.arith_constrain(x, P.ZERO_VAR, z, q_l=ql, q_o=-1, q_c=qc)
+            x = z
+    cs.set_variable_public(x)
+    assert cs.check_satisfied() and cs.circuit_bound() == n
+    assert set(cs.wire_evals(n)[1]) == {0}
+    return cs
+
+
+class Case:
+    """One circuit shape (several witnesses of it), its keys and the oracle's proofs, made once per (curve, n)."""
+
+    def __init__(self, cv, n, css):
+        self.cv, self.n, self.css = cv, n, css
+        self.srs = K.srs_mont(cv, 0x51DE + n, n + 8)
+        self.be = K.CBackend(cv, self.srs)
+        self.pk, self.epk, self.vk = P.setup(self.be, [None] * (n + 8), css[0], True)
+        for cs in css[1:]:
+            assert P.setup_evals(self.be, cs) == P.setup_evals(self.be, css[0])
+        self.pkm = None
+        self._want = {}
+
+    def want(self, k, seed):
+        if (k, seed) not in self._want:
+            bl = field_elems(self.cv.fr.p, seed, P.NUM_BLINDERS)
+            self._want[(k, seed)] = P.prove(self.be, [None] * (self.n + 8), self.pk, self.epk, self.vk, self.css[k],
+                                            P.new_seeded_transcript(self.cv, self.vk), bl).serialize(self.cv)
+        return self._want[(k, seed)]
+
+    def load(self, z, ctx):
+        cv = self.cv
+        if self.pkm is None:
+            self.pkm = {k: K.fr_to_mont(cv, self.pk.polys[k]) if self.pk.polys[k] else np.zeros((0, 4), dtype=np.uint64)
+                        for k in z.PK_ORDER}
+        ctx.srs_load(self.srs)
+        z.GpuProver(ctx, self.n.bit_length() - 1, self.pkm)
+
+    def tr(self, z):
+        cv = self.cv
+        return z.seed_transcript(z.Transcript("merlin", "ZKT Plonk", fr_bits=cv.fr.bits, fq_bytes=cv.fq.limbs64 * 8), self.vk.n,
+                                 self.vk.commits)
+
+    def inputs(self, k, seed, wires=None):
+        cv, cs = self.cv, self.css[k]
+        a, b, c = wires if wires is not None else cs.wire_evals(cs.n_gates)
+        pos = sorted(cs.pi)
+        return (K.fr_to_mont(cv, a), K.fr_to_mont(cv, b), K.fr_to_mont(cv, c),
+                K.fr_to_mont(cv, cs.table) if cs.table else np.zeros((0, 4), dtype=np.uint64), pos,
+                K.fr_to_mont(cv, [cs.pi[i] for i in pos]), K.fr_to_mont(cv, field_elems(cv.fr.p, seed, P.NUM_BLINDERS)))
+
+    def prove(self, z, ctx, k, seed, wires=None):
+        return ctx.prove(*self.inputs(k, seed, wires), self.tr(z))
+
+
+_CASES = {}
+
+
+def _case(cv, n, kind="synthetic"):
+    key = (cv.name, n, kind)
+    if key not in _CASES:
+        css = [_constant_b(cv, n)] if kind == "constant_b" else [_synthetic(cv, n, 40 + k) for k in range(3)]
+        _CASES[key] = Case(cv, n, css)
+    return _CASES[key]
+
+
+@pytest.fixture(scope="module")
+def ctxs():
+    import zkt_plonk_amd as z
+    c = {cv.name: z.Context(cv.name, 0) for cv in CURVES}
+    yield c
+    for x in c.values():
+        x.close()
+
+
+params = pytest.mark.parametrize("cv,n", [(cv, n) for cv in CURVES for n in SIZES], ids=lambda v: getattr(v, "name", str(v)))
+
+
+@params
+def test_both_routes_prove_the_oracles_bytes_and_the_same_quotient(cv, n, ctxs):
+    """A satisfying witness: route 1, route 2 and the oracle give the same bytes; the quotient's 4n coefficients are the same
+    on both routes, and the six the host formed (u) are coefficients 3n .. 3n + 5 of the whole-coset quotient."""
+    import zkt_plonk_amd as z
+    ctx, cs = ctxs[cv.name], _case(cv, n)
+    cs.load(z, ctx)
+    ctx.set_quotient_route(WHOLE)
+    assert cs.prove(z, ctx, 0, 900) == cs.want(0, 900)
+    q_whole = ctx.debug_quotient_coeffs(4 * n)
+    ctx.set_quotient_route(CLASSES)
+    assert cs.prove(z, ctx, 0, 900) == cs.want(0, 900)
+    q_classes = ctx.debug_quotient_coeffs(4 * n)
+    u, on_classes = ctx.debug_quotient_top()
+    assert on_classes
+    assert np.array_equal(u, q_whole[3 * n:3 * n + 6]) and u[5].any()
+    assert np.array_equal(q_classes, q_whole)
+    assert not q_whole[3 * n + 6:].any()
+    ctx.set_quotient_route(0)
+    assert cs.prove(z, ctx, 0, 901) == cs.want(0, 901)   # automatic: circuits this small stay on the whole coset
+    assert not ctx.debug_quotient_top()[1]
+
+
+@params
+def test_constant_b_wire(cv, n, ctxs):
+    """b's polynomial trimmed to nothing: its two blinders land at X^0 and X^1 and its window above n - 6 is all zero."""
+    import zkt_plonk_amd as z
+    ctx, cs = ctxs[cv.name], _case(cv, n, "constant_b")
+    cs.load(z, ctx)
+    for route in (CLASSES, WHOLE):
+        ctx.set_quotient_route(route)
+        assert cs.prove(z, ctx, 0, 910) == cs.want(0, 910), route
+    ctx.set_quotient_route(0)
+
+
+@params
+def test_fresh_and_reused_lookup_tables_and_announced_successors(cv, n, ctxs):
+    """Witnesses of one circuit with different lookup tables and public inputs.  A fresh table, the same table again (its
+    polynomial and class cosets stay resident), another table; then the same chain with every successor announced
+    (zkt_prove_set_next: rounds 1 and 2 of the next proof are transformed under the current proof's route), and a change
+    of route in the middle of a chain, which drops what was transformed ahead."""
+    import zkt_plonk_amd as z
+    ctx, cs = ctxs[cv.name], _case(cv, n)
+    assert cs.css[0].table != cs.css[1].table
+    cs.load(z, ctx)
+    ctx.set_quotient_route(CLASSES)
+    order = [(0, 900), (0, 901), (1, 931), (1, 900), (0, 900)]
+    for k, seed in order:
+        assert cs.prove(z, ctx, k, seed) == cs.want(k, seed), (k, seed)
+    preps = [ctx.prepare_host(*cs.inputs(k, seed)) for k, seed in order]
+    for i, (k, seed) in enumerate(order):
+        nxt = preps[i + 1] if i + 1 < len(order) else None
+        if i == 3:
+            ctx.set_quotient_route(WHOLE)
+        assert ctx.prove_prepared(preps[i], cs.tr(z), nxt) == cs.want(k, seed), (i, k, seed)
+    ctx.set_quotient_route(CLASSES)
+    assert ctx.prove_prepared(preps[2], cs.tr(z), preps[0]) == cs.want(*order[2])
+    assert ctx.prove_prepared(preps[0], cs.tr(z)) == cs.want(*order[0])
+    ctx.set_quotient_route(0)
+
+
+@params
+def test_forked_contexts(cv, n):
+    """A fork made after the parent's first proof on classes shares its class tables; a fork of a parent that never took
+    the route builds its own.  Both prove the oracle's bytes, and the mode is inherited."""
+    import zkt_plonk_amd as z
+    cs = _case(cv, n)
+    parent = z.Context(cv.name, 0)
+    try:
+        cs.load(z, parent)
+        early = parent.fork()                      # before any class table exists
+        parent.set_quotient_route(CLASSES)
+        assert cs.prove(z, parent, 0, 900) == cs.want(0, 900)
+        late = parent.fork()                       # inherits mode 1 and the tables
+        assert cs.prove(z, late, 1, 931) == cs.want(1, 931)
+        assert late.debug_quotient_top()[1]
+        assert cs.prove(z, early, 0, 900) == cs.want(0, 900)
+        assert not early.debug_quotient_top()[1]
+        early.set_quotient_route(CLASSES)
+        assert cs.prove(z, early, 1, 931) == cs.want(1, 931)
+        assert early.debug_quotient_top()[1]
+        assert cs.prove(z, parent, 0, 900) == cs.want(0, 900)
+        early.close()
+        late.close()
+    finally:
+        parent.close()
+
+
+def _broken(cs, what):
+    """Wire vectors of witness 0 that break one thing: a gate, a copy constraint (every gate still holds), a lookup."""
+    c0 = cs.css[0]
+    p = cs.cv.fr.p
+    a, b, c = (list(w) for w in c0.wire_evals(c0.n_gates))
+    if what == "gate":
+        row = next(i for i in range(c0.n_gates) if not c0.q_lookup[i] and c0.q_o[i] % p)
+        c[row] = (c[row] + 1) % p
+    elif what == "copy":   # q_l (a + 1) + q_r b - (c + q_l) + q_c = 0 still, but a and c left their variables' cycles
+        row = next(i for i in range(c0.n_gates) if not c0.q_lookup[i] and not c0.q_m[i] % p and c0.q_l[i] % p and c0.q_o[i] % p == p - 1)
+        a[row] = (a[row] + 1) % p
+        c[row] = (c[row] + c0.q_l[row]) % p
+        assert (c0.q_l[row] * a[row] + c0.q_r[row] * b[row] - c[row] + c0.q_c[row] + c0.pi.get(row, 0)) % p == 0
+    else:
+        row = next(i for i in range(c0.n_gates) if c0.q_lookup[i])
+        v = next(x for x in range(1, 1000) if (c[row] + x) % p not in c0.table and (c[row] + x) % p)
+        c[row] = (c[row] + v) % p
+    return a, b, c
+
+
+@pytest.mark.parametrize("what,code", [("gate", 9), ("copy", 9), ("lookup", 8)])
+@params
+def test_refusals(cv, n, what, code, ctxs):
+    """An unsatisfied circuit is refused with the whole-coset route's code on both routes, and the next proof is the
+    oracle's again."""
+    import zkt_plonk_amd as z
+    ctx, cs = ctxs[cv.name], _case(cv, n)
+    cs.load(z, ctx)
+    wires = _broken(cs, what)
+    for route in (WHOLE, CLASSES):
+        ctx.set_quotient_route(route)
+        with pytest.raises(z.ZktError) as e:
+            cs.prove(z, ctx, 0, 940, wires)
+        assert e.value.code == code, (route, e.value.code)
+        assert cs.prove(z, ctx, 0, 900) == cs.want(0, 900), route
+    ctx.set_quotient_route(0)

@@ -577,6 +577,23 @@ def g1_msm_host(curve, points, scalars, montgomery: bool = True) -> tuple:
     return out, bool(inf.value)
 
 
+def quotient_classes_host(curve, log_n: int, windows, challenges):
+    """zkt_debug_quotient_classes_host: the host arithmetic of the quotient on three classes (no device).  windows: (10, 14, 4)
+    Montgomery words, the coefficients n - 6 .. n + 7 of a b c z1 z2 t sigma1 sigma2 sigma3 q_lookup; challenges: (3, 4) alpha
+    beta delta.  -> (u (6, 4), consts (16, 4): X^n on classes 0..3, the inverse Vandermonde matrix row-major, gamma_3^1..3)."""
+    L = lib()
+    w = np.ascontiguousarray(windows, dtype=np.uint64).reshape(10, 14, 4)
+    ch = np.ascontiguousarray(challenges, dtype=np.uint64).reshape(3, 4)
+    u = np.zeros((6, 4), dtype=np.uint64)
+    consts = np.zeros((16, 4), dtype=np.uint64)
+    P64 = ctypes.POINTER(ctypes.c_uint64)
+    L.zkt_debug_quotient_classes_host.argtypes = [ctypes.c_int, ctypes.c_int, P64, P64, P64, P64]
+    rc = L.zkt_debug_quotient_classes_host(curve_id(curve), int(log_n), u64p(w), u64p(ch), u64p(u), u64p(consts))
+    if rc:
+        raise ZktError(rc, "zkt_debug_quotient_classes_host")
+    return u, consts
+
+
 def wire_elimination(curve, selectors, w_l, w_r, w_o, n_vars: int, pi_pos=(), K: int = 16):
     """zkt_debug_wire_elimination: the host pass behind the wire tables over free variables (no device).  selectors: q_m q_l
     q_r q_o q_c as (n_rows, 4) Montgomery words; w_*: n_rows uint32 indices (0xFFFFFFFF = Variable::Zero).  -> (kind (n_vars,)
@@ -1502,6 +1519,27 @@ class Context:
         self._L.zkt_debug_open_witness.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t,
                                                    ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
         self.check(self._L.zkt_debug_open_witness(self._h, u64p(p_), p_.shape[0], u64p(zz), u64p(out)))
+        return out
+
+    def set_quotient_route(self, mode: int = 0):
+        """zkt_ctx_set_quotient_route: 0 automatic (three classes for single-GPU circuits of 2^20 rows and more), 1 the
+        quotient on three classes of the 4n coset, 2 on the whole coset"""
+        self._L.zkt_ctx_set_quotient_route.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        self.check(self._L.zkt_ctx_set_quotient_route(self._h, int(mode)))
+
+    def debug_quotient_top(self):
+        """zkt_debug_quotient_top -> (u (6, 4) Montgomery words, whether the last proof took the quotient on classes)"""
+        u = np.zeros((6, 4), dtype=np.uint64)
+        on = ctypes.c_int(0)
+        self._L.zkt_debug_quotient_top.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int)]
+        self.check(self._L.zkt_debug_quotient_top(self._h, u64p(u), ctypes.byref(on)))
+        return u, bool(on.value)
+
+    def debug_quotient_coeffs(self, count: int) -> np.ndarray:
+        """zkt_debug_quotient_coeffs: the first `count` coefficients of the quotient as the last proof left them"""
+        out = np.zeros((count, 4), dtype=np.uint64)
+        self._L.zkt_debug_quotient_coeffs.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t]
+        self.check(self._L.zkt_debug_quotient_coeffs(self._h, u64p(out), int(count)))
         return out
 
     def debug_quotient(self, n: int, challenges, wit, pi_pos=(), pi_vals=None) -> np.ndarray:

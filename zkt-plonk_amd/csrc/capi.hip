@@ -232,6 +232,7 @@ int zkt_ctx_fork(zkt_ctx* parent, zkt_ctx** out) {
     (void)hipStreamSynchronize(parent->stream);   // the tables are complete
     c->lagrange_off = parent->lagrange_off;
     c->wire_elim_mode = parent->wire_elim_mode;
+    c->quotient_route = parent->quotient_route;
     c->batch_off = parent->batch_off;
     c->aux_off = parent->aux_off;
     c->ntt_plans = parent->ntt_plans;             // twiddle tables: immutable, owned by the root

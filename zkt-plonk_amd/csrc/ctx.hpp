@@ -83,6 +83,7 @@ struct zkt_ctx {
     bool batch_off = false;        // A/B builds: ZKT_MSM_NO_BATCH commits a round's polynomials one launch sequence each
     bool lagrange_off = false;     // zkt_ctx_set_lagrange(ctx, 0): evaluations are committed through their coefficients
     int wire_elim_mode = 1;        // zkt_ctx_set_wire_elimination: 0 off, 1 automatic (large circuits), 2 whenever a table can be built
+    int quotient_route = 0;        // zkt_ctx_set_quotient_route: 0 automatic (three classes on large single-GPU circuits), 1 three classes, 2 the whole coset
     std::shared_ptr<zkt::CircuitState> circuit;
     std::vector<void*> owned;  // every hipMalloc made on behalf of this ctx
 };
@@ -142,8 +143,12 @@ Fe<P> root_of_unity(int log_n);
 // coset: 0 none, 1 the generator g, ntt_class_code(log_big, cls) a class of a larger coset (see ntt.hip)
 int ntt_run(zkt_ctx* c, int log_n, int inverse, int coset, const void* d_in, size_t in_len, void* d_out);
 // nb <= NTT_MAX_BATCH transforms of one plan, one launch per pass; distinct outputs, out[y] == in[y] allowed
+// d_head (forward only): NTT_HEAD elements per polynomial that stand in for its coefficients 0 .. NTT_HEAD - 1
 int ntt_run_batch(zkt_ctx* c, int log_n, int inverse, int coset, int nb, const void* const* d_in, const size_t* in_len,
-                  void* const* d_out);
+                  void* const* d_out, const void* d_head = nullptr);
+// heads of nb polynomials of n + NTT_HEAD coefficients folded modulo X^n - gammas[j], j < 3 (host, 8 words each), into
+// d_out[(j * NTT_MAX_BATCH + y) * NTT_HEAD + i]: what ntt_run_batch takes as d_head for class j
+int ntt_fold_heads(zkt_ctx* c, int nb, const void* const* d_in, size_t n, const uint32_t* gammas, void* d_out);
 int ntt_class_code(int log_big, int cls);
 // zkt_debug_ntt_split: npass = 0 restores the policy; transforms above 2^10 built afterwards use the given radices
 int ntt_force_split(zkt_ctx* c, int npass, const int* log_r);

@@ -2,6 +2,7 @@
 #include "ctx.hpp"
 #include "hostinv.hpp"
 #include <cstdlib>
+#include <cstring>
 
 namespace zkt {
 
@@ -248,7 +249,9 @@ __global__ __launch_bounds__(NTT_THREADS, (LOG_R <= 7 ? 4 : 3)) void k_ntt_pass(
             const uint4* rlo = reinterpret_cast<const uint4*>(in_p);
             x = tile_get<P>(rlo, rlo + a.raw_n, reinterpret_cast<const uint32_t*>(rlo + 2 * a.raw_n), (int64_t)g);
         } else {
-            x = (g < in_len) ? fx_unpack<P>(fe_load<P>(in + g)) : fx_zero<P>();
+            const Fe<P>* src = in + g;
+            if (a.head && g < NTT_HEAD) src = reinterpret_cast<const Fe<P>*>(a.head) + py * NTT_HEAD + g;
+            x = (g < in_len) ? fx_unpack<P>(fe_load<P>(src)) : fx_zero<P>();
         }
         // the prover's coset transforms are fed n + 8 coefficients on a domain of 4n: three rows in four are padding,
         // and whole wavefronts see nothing but padding (a wave covers consecutive rows), so the branch is uniform
@@ -314,12 +317,12 @@ __global__ void k_table_to_shoup(const Fe<P>* t, void* out, uint64_t n, Fx<P> np
 template <class P>
 __global__ __launch_bounds__(NTT_THREADS) void k_ntt_small(const Fe<P>* in, uint64_t in_len, Fe<P>* out, int log_n,
                                                            const Fe<P>* w, const Fe<P>* in_scale,
-                                                           const Fe<P>* out_scale) {
+                                                           const Fe<P>* out_scale, const Fe<P>* head) {
     __shared__ Fe<P> buf[TILE];
     const int n = 1 << log_n;
     const int tid = threadIdx.x;
     for (int i = tid; i < n; i += NTT_THREADS) {
-        Fe<P> x = ((uint64_t)i < in_len) ? fe_load<P>(in + i) : fe_zero<P>();
+        Fe<P> x = ((uint64_t)i < in_len) ? fe_load<P>(head && i < NTT_HEAD ? head + i : in + i) : fe_zero<P>();
         if (in_scale) x = fe_mul<P>(x, fe_load<P>(in_scale + i));
         buf[i] = x;
     }
@@ -660,7 +663,7 @@ static void launch_pass(zkt_ctx* c, int log_r, unsigned blocks, unsigned nb, con
 // transform alone is a single wave of workgroups whose ramp and tail are a third of its time.
 template <class P>
 static int ntt_run_batch_t(zkt_ctx* c, int log_n, int inverse, int coset, int nb, const void* const* d_in, const size_t* in_len,
-                           void* const* d_out) {
+                           void* const* d_out, const void* d_head = nullptr) {
     if (nb < 1 || nb > NTT_MAX_BATCH) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "transform batch out of range");
     if (log_n < 0 || log_n > P::TWO_ADICITY)
         return set_err(c, ZKT_ERR_INVALID_DOMAIN_SIZE,
@@ -688,7 +691,8 @@ static int ntt_run_batch_t(zkt_ctx* c, int log_n, int inverse, int coset, int nb
         for (int y = 0; y < nb; ++y)
             hipLaunchKernelGGL(k_ntt_small<P>, dim3(1), dim3(NTT_THREADS), 0, c->stream, (const Fe<P>*)d_in[y],
                                (uint64_t)in_len[y], (Fe<P>*)d_out[y], log_n, (const Fe<P>*)pl.small_w,
-                               (const Fe<P>*)pl.small_in, (const Fe<P>*)pl.small_out);
+                               (const Fe<P>*)pl.small_in, (const Fe<P>*)pl.small_out,
+                               d_head ? (const Fe<P>*)d_head + (size_t)y * NTT_HEAD : nullptr);
         ZKT_HIP(c, hipGetLastError());
         return 0;
     }
@@ -709,6 +713,7 @@ static int ntt_run_batch_t(zkt_ctx* c, int log_n, int inverse, int coset, int nb
         a.w_inner = pl.w_inner[i];
         a.w_inner_s = pl.w_inner_s[i];
         a.in_row = (i == 0) ? pl.in_row : nullptr;
+        a.head = (i == 0) ? d_head : nullptr;
         a.tw = pl.tw[i];
         a.out_row = last ? pl.out_row : nullptr;
         a.log_n = (uint32_t)log_n;
@@ -735,9 +740,41 @@ static int ntt_run_t(zkt_ctx* c, int log_n, int inverse, int coset, const void* 
 }
 
 int ntt_run_batch(zkt_ctx* c, int log_n, int inverse, int coset, int nb, const void* const* d_in, const size_t* in_len,
-                  void* const* d_out) {
-    if (c->curve == ZKT_CURVE_BN254) return ntt_run_batch_t<Bn254Fr>(c, log_n, inverse, coset, nb, d_in, in_len, d_out);
-    return ntt_run_batch_t<Bls381Fr>(c, log_n, inverse, coset, nb, d_in, in_len, d_out);
+                  void* const* d_out, const void* d_head) {
+    if (d_head && (inverse || log_n < 3)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "folded heads go with forward transforms of 8 points and more");
+    if (c->curve == ZKT_CURVE_BN254) return ntt_run_batch_t<Bn254Fr>(c, log_n, inverse, coset, nb, d_in, in_len, d_out, d_head);
+    return ntt_run_batch_t<Bls381Fr>(c, log_n, inverse, coset, nb, d_in, in_len, d_out, d_head);
+}
+
+// The heads of nb polynomials of n + NTT_HEAD coefficients folded modulo X^n - gamma_j, j < 3 (gammas: three elements,
+// passed by value): out[(j * NTT_MAX_BATCH + y) * NTT_HEAD + i] = in[y][i] + gamma_j in[y][n + i].  One workgroup.
+template <class P>
+struct FoldHeadsArgs {
+    const Fe<P>* in[NTT_MAX_BATCH];
+    Fe<P> gamma[3];
+};
+template <class P>
+__global__ void k_fold_heads(FoldHeadsArgs<P> a, uint64_t n, int nb, Fe<P>* out) {
+    const int t = threadIdx.x;
+    const int i = t % NTT_HEAD, y = (t / NTT_HEAD) % NTT_MAX_BATCH, j = t / (NTT_HEAD * NTT_MAX_BATCH);
+    if (j >= 3 || y >= nb) return;
+    const Fe<P>* in = y == 0 ? a.in[0] : y == 1 ? a.in[1] : y == 2 ? a.in[2] : a.in[3];
+    const Fe<P> g = j == 0 ? a.gamma[0] : j == 1 ? a.gamma[1] : a.gamma[2];
+    fe_store<P>(out + t, fe_add<P>(fe_load<P>(in + i), fe_mul<P>(g, fe_load<P>(in + n + i))));
+}
+template <class P>
+static int ntt_fold_heads_t(zkt_ctx* c, int nb, const void* const* d_in, size_t n, const uint32_t* gammas, void* d_out) {
+    FoldHeadsArgs<P> a{};
+    for (int y = 0; y < NTT_MAX_BATCH; ++y) a.in[y] = (const Fe<P>*)d_in[y < nb ? y : 0];
+    for (int j = 0; j < 3; ++j) memcpy(a.gamma[j].v, gammas + 8 * j, 32);
+    hipLaunchKernelGGL(k_fold_heads<P>, dim3(1), dim3(3 * NTT_MAX_BATCH * NTT_HEAD), 0, c->stream, a, (uint64_t)n, nb, (Fe<P>*)d_out);
+    ZKT_HIP(c, hipGetLastError());
+    return ZKT_OK;
+}
+int ntt_fold_heads(zkt_ctx* c, int nb, const void* const* d_in, size_t n, const uint32_t* gammas, void* d_out) {
+    if (nb < 1 || nb > NTT_MAX_BATCH) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "transform batch out of range");
+    if (c->curve == ZKT_CURVE_BN254) return ntt_fold_heads_t<Bn254Fr>(c, nb, d_in, n, gammas, d_out);
+    return ntt_fold_heads_t<Bls381Fr>(c, nb, d_in, n, gammas, d_out);
 }
 
 int ntt_run(zkt_ctx* c, int log_n, int inverse, int coset, const void* d_in, size_t in_len, void* d_out) {

@@ -20,6 +20,7 @@
 
 namespace zkt {
 
+constexpr int NTT_HEAD = 8;        // coefficients a transform may take from a folded head (NttPassArgs::head)
 constexpr int NTT_MAX_BATCH = 4;   // transforms of one plan issued as ONE launch per pass (gridDim.y = polynomial)
 
 struct NttPassArgs {
@@ -31,6 +32,9 @@ struct NttPassArgs {
     const void* tw;        // optional boundary twiddles (row-shared or tile-shaped)
     const void* out_row;   // optional R-entry output row scale (inverse coset, last pass)
     uint64_t in_len[NTT_MAX_BATCH];   // elements of `in` that exist (rest read as zero); pass 1 only
+    // optional, pass 1 only: polynomial y reads its coefficients 0..7 from head + 8 y instead of in[y] (a polynomial of
+    // n + 8 coefficients folded modulo X^n - c differs from its first n coefficients in those eight only: ntt_fold_heads)
+    const void* head;
     uint32_t log_n;
     uint32_t log_s;        // non-last: log2 of the inner stride S (columns); last: unused
     uint32_t log_r1;       // last: log2 R1

@@ -973,6 +973,93 @@ int quotient_split_blind(zkt_ctx* c, const void* q, size_t n, const void* d_b0b1
     ZKT_DISPATCH(c, quot_split_t, q, n, d_b0b1, q_lo, q_mid, q_hi, d_status);
 }
 
+
+// ---- the quotient on three classes of the 4n coset (prover.hip "quotient on classes") ----
+// classes 0, 1, 2 of a whole-coset table as [3][n]: out[j n + i] = in[4 i + j]
+template <class P>
+__global__ void k_classes_of_coset(const Fe<P>* in, Fe<P>* out, uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) fe_store<P>(out + (uint64_t)j * n + i, fe_load<P>(in + 4 * i + j));
+}
+template <class P> static int classes_of_coset_t(zkt_ctx* c, const void* in, void* out, size_t n) {
+    hipLaunchKernelGGL(k_classes_of_coset<P>, dim3(nblocks(n)), dim3(256), 0, c->stream, (const Fe<P>*)in, (Fe<P>*)out, (uint64_t)n);
+    ZKT_HIP(c, hipGetLastError());
+    return ZKT_OK;
+}
+int quotient_classes_of_coset(zkt_ctx* c, const void* in, void* out, size_t n) { ZKT_DISPATCH(c, classes_of_coset_t, in, out, n); }
+
+// coefficients [first, first + QC_WIN) of QC_WIN_POLYS polynomials, back to back
+struct WindowPtrs {
+    const void* p[QC_WIN_POLYS];
+};
+template <class P>
+__global__ void k_gather_windows(WindowPtrs w, uint64_t first, Fe<P>* out) {
+    const int t = threadIdx.x;
+    if (t >= QC_WIN_POLYS * QC_WIN) return;
+    const int k = t / QC_WIN, i = t % QC_WIN;
+    const void* p = w.p[0];
+#pragma unroll
+    for (int e = 1; e < QC_WIN_POLYS; ++e) p = (k == e) ? w.p[e] : p;
+    fe_store<P>(out + t, fe_load<P>((const Fe<P>*)p + first + i));
+}
+template <class P> static int gather_windows_t(zkt_ctx* c, const void* const* polys, size_t first, void* out) {
+    WindowPtrs w{};
+    for (int k = 0; k < QC_WIN_POLYS; ++k) w.p[k] = polys[k];
+    hipLaunchKernelGGL(k_gather_windows<P>, dim3(1), dim3(128), 0, c->stream, w, (uint64_t)first, (Fe<P>*)out);
+    ZKT_HIP(c, hipGetLastError());
+    return ZKT_OK;
+}
+int quotient_gather_windows(zkt_ctx* c, const void* const* polys, size_t first, void* out) {
+    static_assert(QC_WIN_POLYS * QC_WIN <= 128, "one workgroup of 128");
+    ZKT_DISPATCH(c, gather_windows_t, polys, first, out);
+}
+
+// q holds E_j = t mod (X^n - gamma_j), j < 3, as [3][n] coefficients.  With t~ = t mod Z3 = T0 + X^n T1 + X^2n T2 they are
+// E_j = T0 + gamma_j T1 + gamma_j^2 T2: T_k = sum_j vinv[3 k + j] E_j.  t = t~ + u Z3, Z3 = X^3n + g3 X^2n + g3^2 X^n + g3^3,
+// u of degree 5: q becomes the 4n coefficients of t, zero above 3n + 5.
+template <class P>
+struct CombineArgs {
+    Fe<P> vinv[9];
+    Fe<P> u[6];
+    Fe<P> g3[3];   // gamma_3, gamma_3^2, gamma_3^3
+};
+template <class P>
+__global__ __launch_bounds__(256) void k_classes_combine(Fe<P>* q, uint64_t n, CombineArgs<P> a) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const Fe<P> e0 = fe_load<P>(q + i), e1 = fe_load<P>(q + n + i), e2 = fe_load<P>(q + 2 * n + i);
+    Fe<P> t[4];
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        t[k] = fe_add<P>(fe_add<P>(fe_mul<P>(a.vinv[3 * k], e0), fe_mul<P>(a.vinv[3 * k + 1], e1)), fe_mul<P>(a.vinv[3 * k + 2], e2));
+    t[3] = fe_zero<P>();
+    if (i < 6) {
+        Fe<P> u = a.u[0];
+#pragma unroll
+        for (int e = 1; e < 6; ++e) u = (i == (uint64_t)e) ? a.u[e] : u;
+        t[3] = u;
+        t[2] = fe_add<P>(t[2], fe_mul<P>(u, a.g3[0]));
+        t[1] = fe_add<P>(t[1], fe_mul<P>(u, a.g3[1]));
+        t[0] = fe_add<P>(t[0], fe_mul<P>(u, a.g3[2]));
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) fe_store<P>(q + (uint64_t)k * n + i, t[k]);
+}
+template <class P> static int classes_combine_t(zkt_ctx* c, void* q, size_t n, const uint32_t* vinv, const uint32_t* u, const uint32_t* g3) {
+    CombineArgs<P> a{};
+    for (int k = 0; k < 9; ++k) a.vinv[k] = host_fe<P>(vinv + 8 * k);
+    for (int k = 0; k < 6; ++k) a.u[k] = host_fe<P>(u + 8 * k);
+    for (int k = 0; k < 3; ++k) a.g3[k] = host_fe<P>(g3 + 8 * k);
+    hipLaunchKernelGGL(k_classes_combine<P>, dim3(nblocks(n)), dim3(256), 0, c->stream, (Fe<P>*)q, (uint64_t)n, a);
+    ZKT_HIP(c, hipGetLastError());
+    return ZKT_OK;
+}
+int quotient_classes_combine(zkt_ctx* c, void* q, size_t n, const uint32_t* vinv, const uint32_t* u, const uint32_t* g3) {
+    ZKT_DISPATCH(c, classes_combine_t, q, n, vinv, u, g3);
+}
+
 int open_elems(size_t len) { return ow_elems(len); }
 size_t open_blocks(size_t len) { return ow_blocks(len); }
 template <class P> static int open_pow_tables_t(zkt_ctx* c, const uint32_t* z, const uint32_t* zinv, void* d_powers, size_t len) {

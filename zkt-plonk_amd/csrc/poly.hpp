@@ -88,6 +88,15 @@ int to_hat_form(zkt_ctx* c, void* v, size_t n, int k32);
 int quotient_interleave(zkt_ctx* c, const void* in, void* out, size_t n4, uint32_t G, uint32_t chunks = 1);
 int quotient_split_blind(zkt_ctx* c, const void* q, size_t n, const void* d_b0b1, void* q_lo, void* q_mid, void* q_hi,
                          uint32_t* d_status);                                                   // prove.rs:287-300
+// The quotient on classes 0, 1, 2 of the 4n coset (prover.hip): [3][n] class arrays of a whole-coset table (4n elements);
+// the windows [first, first + QC_WIN) of QC_WIN_POLYS polynomials gathered back to back for one copy to the host; and the
+// way back from the three inverse class transforms (q: 4n elements, [3][n] on entry) to the 4n coefficients of t:
+// vinv = the inverse of the Vandermonde matrix in gamma_0..2 (row-major), u = the six top coefficients of t, g3 = the
+// first three powers of gamma_3 (host words, Montgomery form; quotient_classes.hpp makes them).
+constexpr int QC_WIN = 14, QC_WIN_POLYS = 6;
+int quotient_classes_of_coset(zkt_ctx* c, const void* in, void* out, size_t n);
+int quotient_gather_windows(zkt_ctx* c, const void* const* polys, size_t first, void* out);
+int quotient_classes_combine(zkt_ctx* c, void* q, size_t n, const uint32_t* vinv, const uint32_t* u, const uint32_t* g3);
 // KZG opening witness: w = p / (X - z)  (kzg10::compute_witness_polynomial)
 int open_witness(zkt_ctx* c, const void* p, size_t len, const uint32_t z[8], const uint32_t z_inv[8], void* d_tmp_a, void* d_tmp_b,
                  void* d_scan_tmp, void* out, void* d_powers /* open_witness_powers(len) elements of scratch */);

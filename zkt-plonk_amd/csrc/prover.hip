@@ -11,6 +11,7 @@
 #include "keyfile.hpp"
 #include "msm.hpp"
 #include "poly.hpp"
+#include "quotient_classes.hpp"
 #include "transcript.hpp"
 
 #include <algorithm>
@@ -101,6 +102,20 @@ struct CircuitState {
     bool wire_route[3] = {};
     bool wire_dense_only = false;   // zkt_debug_commit_wires_dev route 0
     int wire_elim_force = -1;       // zkt_debug_commit_wires_dev: 0 = per-variable tables only (route 1), 1 = over free variables (route 2)
+    // The quotient on classes 0, 1, 2 of the 4n coset (single GPU, zkt_ctx_set_quotient_route; quotient_classes.hpp).
+    // ccoset[] are coset[] as [3][n] class arrays, built on first use (circuit_class_tables) and shared with forks made
+    // afterwards; wcos[] then hold [3][n] as well.  key_win: the windows of sigma1..3 and q_lookup.
+    void* ccoset[CS_COUNT] = {};
+    bool ccoset_borrowed = false, ccoset_ready = false;
+    uint32_t key_win[4][QCW][8] = {};
+    uint32_t qc_gamma[4][8] = {}, qc_vinv[9][8] = {}, qc_g3[3][8] = {};
+    bool use_classes = false;       // the route of the proof in flight: layout of wcos[] and of the resident t coset
+    void* heads = nullptr;          // 3 x NTT_MAX_BATCH x NTT_HEAD folded head coefficients of the batch being transformed
+    void* d_win = nullptr;          // QC_WIN_POLYS windows (a b c z1 z2 t), gathered in round 3 ...
+    void* pinned_win = nullptr;     // ... and copied here behind them
+    hipEvent_t ev_win = nullptr;
+    uint32_t last_u[6][8] = {};     // zkt_debug_quotient_top
+    bool last_u_valid = false;
 };
 
 // ---- host field helpers ------------------------------------------------------------------------------
@@ -155,6 +170,9 @@ static void serialize_point(const Affine<Q>& p, std::vector<uint8_t>& out) {
 }
 
 constexpr int WIRE_ELIM_MIN_LOG_N = 17;   // zkt_ctx_set_wire_elimination mode 1: circuits from this size on
+// zkt_ctx_set_quotient_route mode 0: the quotient on three classes from this size on (docs/EXPERIMENTS.md "Quotient on three
+// classes": it gains at 2^20 and loses at 2^18, where its extra launches cost more than the arithmetic it saves; 2^19 is not measured)
+constexpr int QUOTIENT_CLASSES_MIN_LOG_N = 20;
 
 template <class C>
 struct Prover {
@@ -475,6 +493,7 @@ struct Prover {
         // challenge, so each is issued right behind the commitment of its polynomial, where it hides the latency-bound
         // tail of the last MSM of the round (which runs on the side stream).
         static const int coset_src[W_COUNT] = {0, 1, 2, 8, 6, 7, 3, 4, 5};  // a b c pi z1 z2 t h1 h2
+        if (S.use_classes) return to_coset_classes(&k, 1);
         if (S.G == 1) return ntt_run(c, S.log_n + 2, 0, 1, S.poly[coset_src[k]], S.n + 8, S.wcos[k]);
         // sharded proof: only this GPU's class of the 4n coset, one m-point transform, no exchange
         int rc = ntt_run_class(c, S.log_m, S.log_n + 2, S.cls, S.poly[coset_src[k]], S.n + 8, S.wcos[k], S.fold);
@@ -484,11 +503,38 @@ struct Prover {
         return ntt_run_class(c, S.log_m, S.log_n + 2, (S.cls + 4) & 7, S.poly[coset_src[k]], S.n + 8, S.wnext[next_of[k]], S.fold);
     }
 
+    // Quotient on classes: the polynomials onto classes 0, 1, 2 of the 4n coset, wcos[k] as [3][n].  Per class ONE batched
+    // n-point coset transform; the n + 8 coefficients folded modulo X^n - gamma_j differ from the first n in eight places,
+    // which one small launch per batch prepares for all three classes (ntt_fold_heads).
+    int to_coset_classes(const int* ks, int nb) {
+        static const int coset_src[W_COUNT] = {0, 1, 2, 8, 6, 7, 3, 4, 5};  // a b c pi z1 z2 t h1 h2
+        const void* ins[NTT_MAX_BATCH];
+        void* outs[NTT_MAX_BATCH];
+        size_t lens[NTT_MAX_BATCH];
+        int rc;
+        for (int y = 0; y < nb; ++y) {
+            ins[y] = S.poly[coset_src[ks[y]]];
+            lens[y] = S.n;
+        }
+        if ((rc = ntt_fold_heads(c, nb, ins, S.n, &S.qc_gamma[0][0], S.heads))) return rc;
+        for (int j = 0; j < 3; ++j) {
+            for (int y = 0; y < nb; ++y) outs[y] = (char*)S.wcos[ks[y]] + (size_t)j * S.n * 32;
+            const void* head = (const char*)S.heads + (size_t)j * NTT_MAX_BATCH * NTT_HEAD * 32;
+            if ((rc = ntt_run_batch(c, S.log_n, 0, ntt_class_code(S.log_n + 2, j), nb, ins, lens, outs, head))) return rc;
+        }
+        return ZKT_OK;
+    }
+
     // several witness polynomials onto the 4n coset in one launch per pass (single GPU; a sharded proof transforms its
     // classes one by one)
     int to_coset_many(std::initializer_list<int> ks) {
         static const int coset_src[W_COUNT] = {0, 1, 2, 8, 6, 7, 3, 4, 5};  // a b c pi z1 z2 t h1 h2
         int rc;
+        if (S.use_classes && ks.size() <= (size_t)NTT_MAX_BATCH) {
+            int kk[NTT_MAX_BATCH], nb = 0;
+            for (int k : ks) kk[nb++] = k;
+            return nb ? to_coset_classes(kk, nb) : ZKT_OK;
+        }
         if (S.G != 1 || ks.size() > (size_t)NTT_MAX_BATCH) {
             for (int k : ks) if ((rc = to_coset(k))) return rc;
             return ZKT_OK;
@@ -504,6 +550,43 @@ struct Prover {
             ++nb;
         }
         return nb ? ntt_run_batch(c, S.log_n + 2, 0, 1, nb, ins, lens, outs) : ZKT_OK;
+    }
+
+    // ---- quotient on classes: which route this proof takes, and the route's tables ----
+    // [3][n] class arrays of the twelve coset tables (the same elements, so whatever form a table is kept in carries over),
+    // the windows of the key polynomials and the constants.  Once per circuit; a fork made afterwards shares the arrays.
+    int ensure_class_tables() {
+        if (S.ccoset_ready) return ZKT_OK;
+        const size_t n = S.n;
+        int rc;
+        for (int k = 0; k < CS_COUNT; ++k) {
+            if (!S.ccoset[k] && (rc = dev_alloc(c, &S.ccoset[k], 3 * n * 32))) return rc;
+            if ((rc = quotient_classes_of_coset(c, S.coset[k], S.ccoset[k], n))) return rc;
+        }
+        static const int key_of[4] = {PK_S1, PK_S2, PK_S3, PK_QLOOKUP};
+        memset(S.key_win, 0, sizeof(S.key_win));   // the key polynomials end at n: coefficients n - 6 .. n - 1
+        for (int k = 0; k < 4; ++k)
+            ZKT_HIP(c, hipMemcpyAsync(S.key_win[k], (const char*)S.pk[key_of[k]] + (n - 6) * 32, 6 * 32, hipMemcpyDeviceToHost, c->stream));
+        ZKT_HIP(c, hipStreamSynchronize(c->stream));
+        const QuotientClassConsts<R> q = quotient_class_consts<R>(S.log_n);
+        for (int j = 0; j < 4; ++j) put(S.qc_gamma[j], q.gamma[j]);
+        for (int j = 0; j < 9; ++j) put(S.qc_vinv[j], q.vinv[j]);
+        for (int j = 0; j < 3; ++j) put(S.qc_g3[j], q.g3[j]);
+        S.ccoset_ready = true;
+        return ZKT_OK;
+    }
+    int choose_route() {
+        int mode = c->quotient_route;
+        if (const char* e = exp_env("ZKT_QUOTIENT_ROUTE")) mode = atoi(e);   // A/B runs of bench.py (experiment library only)
+        const bool want = !c->sharded() && S.G == 1 && (mode == 1 || (mode == 0 && S.log_n >= QUOTIENT_CLASSES_MIN_LOG_N));
+        if (want)
+            if (int rc = ensure_class_tables()) return rc;
+        if (want != S.use_classes) {   // what was transformed ahead of time has the other route's layout
+            S.use_classes = want;
+            S.t_coset_valid = false;
+            S.prefetch_stage = 0;
+        }
+        return ZKT_OK;
     }
 
     void swap_work_sets() {   // current <-> alternate copies of what early work of the next proof overwrites
@@ -663,6 +746,8 @@ struct Prover {
         const int log_n = S.log_n;
         int rc;
         mark("start");
+        if ((rc = choose_route())) return rc;
+        const bool classes = S.use_classes;
         bool same_table = false;
         if (S.prefetch_stage == 2 && S.prefetch_epoch == c->msm_epoch && same_inputs(S.prefetch_in, in)) {
             same_table = S.prefetch_same_table;   // rounds 1 and 2 are already in flight, in the alternate work set
@@ -759,6 +844,14 @@ struct Prover {
             const PolyJob jobs[2] = {{S.ev[7], S.poly[6], 11, 3, 6}, {S.sc[0], S.poly[7], 14, 3, 7}};   // z1, z2: 3 blinders each
             if ((rc = evals_to_blinded_polys(jobs, 2))) return rc;
         }
+        if (classes) {
+            // the coefficients n - 6 .. n + 7 of a b c z1 z2 t (the six top coefficients of the quotient come from them):
+            // one small launch and one copy, on the host well before this round's commitments are
+            const void* const wp[QC_WIN_POLYS] = {S.poly[0], S.poly[1], S.poly[2], S.poly[6], S.poly[7], S.poly[3]};
+            if ((rc = quotient_gather_windows(c, wp, n - 6, S.d_win))) return rc;
+            ZKT_HIP(c, hipMemcpyAsync(S.pinned_win, S.d_win, QC_WIN_POLYS * QC_WIN * 32, hipMemcpyDeviceToHost, c->stream));
+            ZKT_HIP(c, hipEventRecord(S.ev_win, c->stream));
+        }
         {
             void* const z1p[1] = {S.poly[6]};
             const size_t z1l[1] = {n + 3};
@@ -777,7 +870,7 @@ struct Prover {
         if (pi_direct) {
             uint32_t* tab = (uint32_t*)S.pinned_pi;
             for (size_t i = 0; i < in.n_pi; ++i) {
-                tab[10 * i] = (uint32_t)(4 * in.pi_pos[i] / (size_t)S.G);   // rotation in entries of the class
+                tab[10 * i] = (uint32_t)(4 * in.pi_pos[i] / (size_t)(classes ? 4 : S.G));   // rotation in entries of the class
                 const Fx<R> v = fx_unpack<R>(H::from_words(in.pi_vals + 4 * i));
                 for (int w = 0; w < 9; ++w) tab[10 * i + 1 + w] = v.l[w];
             }
@@ -818,7 +911,44 @@ struct Prover {
             q.n4 = S.m;
             q.pi_tab = pi_direct ? S.pi_tab : nullptr;
             q.n_pi_direct = pi_direct ? (uint32_t)in.n_pi : 0;
-            if (S.G > 1) {
+            if (classes) {
+                // classes 0, 1, 2 of the coset, each as a sharded proof over four GPUs computes its own (the class mode of
+                // the kernel), then back class by class: E_j = t mod (X^n - gamma_j)
+                q.G = 4;
+                q.next_off = 1;
+                q.n4 = n;
+                const void** in_ptrs[] = {&q.a, &q.b, &q.c, &q.pi, &q.z1, &q.z2, &q.t, &q.h1, &q.h2};
+                const int cs_of[12] = {CS_QM, CS_QL, CS_QR, CS_QO, CS_QC, CS_QLOOKUP, CS_QTABLE, CS_S1, CS_S2, CS_S3, CS_X, CS_L1};
+                const void** key_ptrs[12] = {&q.q_m, &q.q_l, &q.q_r, &q.q_o, &q.q_c, &q.q_lookup, &q.q_table,
+                                             &q.sigma1, &q.sigma2, &q.sigma3, &q.x, &q.l1};
+                static const int w_of[9] = {W_A, W_B, W_C, W_PI, W_Z1, W_Z2, W_T, W_H1, W_H2};
+                for (int j = 0; j < 3; ++j) {
+                    const size_t off = (size_t)j * n * 32;
+                    for (int k = 0; k < 9; ++k) *in_ptrs[k] = (const char*)S.wcos[w_of[k]] + off;
+                    for (int k = 0; k < 12; ++k) *key_ptrs[k] = (const char*)S.ccoset[cs_of[k]] + off;
+                    q.cls = (uint32_t)j;
+                    q.z1_next = q.z1; q.z2_next = q.z2; q.t_next = q.t; q.h1_next = q.h1;
+                    q.out = (char*)S.qev + off;
+                    if ((rc = quotient_pointwise(c, q))) return rc;
+                }
+                for (int j = 0; j < 3; ++j) {
+                    void* e = (char*)S.qev + (size_t)j * n * 32;
+                    if ((rc = ntt_run(c, log_n, 1, ntt_class_code(log_n + 2, j), e, n, e))) return rc;
+                }
+                // the six top coefficients, from the windows that came with round 3 (the launches above are under way)
+                ZKT_HIP(c, hipEventSynchronize(S.ev_win));
+                const uint32_t* pw = (const uint32_t*)S.pinned_win;
+                QuotientWindows W{};
+                W.a = pw; W.b = pw + QCW * 8; W.c = pw + 2 * QCW * 8; W.z1 = pw + 3 * QCW * 8; W.z2 = pw + 4 * QCW * 8;
+                W.t = pw + 5 * QCW * 8;
+                W.sigma1 = &S.key_win[0][0][0]; W.sigma2 = &S.key_win[1][0][0]; W.sigma3 = &S.key_win[2][0][0];
+                W.q_lookup = &S.key_win[3][0][0];
+                F u[6];
+                quotient_top_coefficients<R>(log_n, W, alpha, beta, delta, u);
+                for (int e = 0; e < 6; ++e) put(S.last_u[e], u[e]);
+                S.last_u_valid = true;
+                if ((rc = quotient_classes_combine(c, S.qev, n, &S.qc_vinv[0][0], &S.last_u[0][0], &S.qc_g3[0][0]))) return rc;
+            } else if (S.G > 1) {
                 // this GPU's class of the coset, written where the all-gather wants it; then the one real exchange of a
                 // sharded proof: 4n x 32 B in total, and the classes go back to natural order for the inverse transform
                 q.G = (uint32_t)S.G;
@@ -858,7 +988,7 @@ struct Prover {
             } else if ((rc = quotient_pointwise(c, q))) {
                 return rc;
             }
-            if ((rc = ntt_run(c, log_n + 2, 1, 1, S.qev, 4 * n, S.qev))) return rc;         // quotient_poly.rs:226
+            if (!classes && (rc = ntt_run(c, log_n + 2, 1, 1, S.qev, 4 * n, S.qev))) return rc;         // quotient_poly.rs:226
             if ((rc = quotient_split_blind(c, S.qev, n, (const char*)S.small + 17 * 32, S.poly[9], S.poly[10], S.poly[11], S.status)))
                 return rc;
             // an unsatisfied circuit shows up as status bits here; they are read with the evaluations of round 5
@@ -987,6 +1117,19 @@ struct Prover {
         void* work = S.poly[12];
         wait_end();
         if ((rc = poly_lincomb(c, lr, work, cap))) return rc;
+        if (classes) {
+            // An unsatisfied circuit leaves no trace in the quotient's coefficients on this route (there are no
+            // evaluations on a fourth class for it to spill into).  The verifier's identity at xi takes over: r(xi), one more
+            // evaluation that comes back with the round's last collect, against the constant the verifier derives.
+            EvalArgs er{};
+            er.count = 1;
+            er.poly[0] = work;
+            er.len[0] = cap;
+            put(er.point[0], xi);
+            if ((rc = poly_eval_many(c, er, d_partials, d_results, S.eval_pw))) return rc;
+            ZKT_HIP(c, hipMemcpyAsync(pin + 16, d_results, 32, hipMemcpyDeviceToHost, c->stream));
+            ZKT_HIP(c, hipEventRecord(S.ev_win, c->stream));
+        }
         // The witness of an opening at z is (p(X) - p(z)) / (X - z).  At z = 0 (xi = 0 makes both points zero; the reference
         // proves there) that is p shifted down by one coefficient, and no power of 1/z is needed: one copy on the stream
         // the opening uses.
@@ -1083,6 +1226,40 @@ struct Prover {
         }
         wait_end();
         prof_round.reset();
+        if (classes) {
+            // compute_r0 (proof.rs:163-217) with the prover's own values; L_j(xi) = zh w^j / (n (xi - w^j)), 1 or 0 on the domain
+            F r0 = fe_zero<R>();
+            std::vector<F> root(in.n_pi), den(in.n_pi), before(in.n_pi);   // before[i]: product of the non-zero den[k], k < i
+            F run_prod = one;
+            for (size_t i = 0; i < in.n_pi; ++i) {
+                root[i] = fe_pow_u64<R>(w, (uint64_t)in.pi_pos[i]);
+                den[i] = fe_mul<R>(nn, fe_sub<R>(xi, root[i]));
+                before[i] = run_prod;
+                if (!fe_is_zero<R>(den[i])) run_prod = fe_mul<R>(run_prod, den[i]);
+            }
+            F inv_all = in.n_pi ? fe_inv_host<R>(run_prod) : one;
+            for (size_t i = in.n_pi; i-- > 0;) {   // one inversion for all denominators
+                const F v = H::from_words(in.pi_vals + 4 * i);
+                if (fe_is_zero<R>(den[i])) {
+                    r0 = fe_sub<R>(r0, v);
+                    continue;
+                }
+                const F di = fe_mul<R>(inv_all, before[i]);
+                inv_all = fe_mul<R>(inv_all, den[i]);
+                r0 = fe_sub<R>(r0, fe_mul<R>(fe_mul<R>(fe_mul<R>(zh, root[i]), di), v));
+            }
+            F p2 = fe_mul<R>(alpha, e_z1n);
+            p2 = fe_mul<R>(p2, fe_add<R>(fe_add<R>(e_a, fe_mul<R>(beta, e_s1)), gamma));
+            p2 = fe_mul<R>(p2, fe_add<R>(fe_add<R>(e_b, fe_mul<R>(beta, e_s2)), gamma));
+            p2 = fe_mul<R>(p2, fe_add<R>(e_c, gamma));
+            F p4 = fe_mul<R>(a3, e_z2n);
+            p4 = fe_mul<R>(p4, fe_add<R>(eopd, fe_mul<R>(delta, e_h2)));
+            p4 = fe_mul<R>(p4, fe_add<R>(fe_add<R>(eopd, e_h2), fe_mul<R>(delta, e_h1n)));
+            r0 = fe_add<R>(fe_add<R>(r0, p2), fe_add<R>(fe_mul<R>(l1, a2), fe_add<R>(p4, fe_mul<R>(l1, a4))));
+            ZKT_HIP(c, hipEventSynchronize(S.ev_win));
+            if (!fe_eq<R>(pin[16], r0))
+                return set_err(c, ZKT_ERR_QUOTIENT_TOO_SHORT, "the opening identity fails at xi: the circuit is not satisfied");
+        }
 
         // ---- Proof (proof.rs:106-155), CanonicalSerialize ----
         proof.clear();
@@ -1120,6 +1297,10 @@ void circuit_release(zkt_ctx* c) {
     fr(S.scan_tmp);
     for (void* p : S.poly) fr(p);
     for (void* p : S.wcos) fr(p);
+    if (!S.ccoset_borrowed) for (void* p : S.ccoset) fr(p);
+    fr(S.heads); fr(S.d_win);
+    if (S.pinned_win) (void)hipHostFree(S.pinned_win);
+    if (S.ev_win) (void)hipEventDestroy(S.ev_win);
     for (void* p : S.wnext) fr(p);
     fr(S.fold); fr(S.qgather);
     for (void* p : S.poly_alt) fr(p);
@@ -1167,11 +1348,17 @@ static int circuit_alloc_work(zkt_ctx* c, CircuitState& S) {
     if ((rc = alloc(&S.scan_tmp, 2 * ((n + 8) / 1024 + 4096)))) return rc;
     for (auto& p : S.poly) if ((rc = alloc(&p, n + 8))) return rc;
     for (int k = 0; k < W_COUNT; ++k)   // the z1 slot doubles as 2n elements of scan scratch in round 3
-        if ((rc = alloc(&S.wcos[k], k == W_Z1 ? std::max(m, 2 * n) : m))) return rc;
+        if ((rc = alloc(&S.wcos[k], k == W_Z1 ? std::max(std::max(m, 2 * n), 3 * (n + 8)) : m))) return rc;   // (round 5's second opening borrows 3 (n + 8))
     const size_t eval_blocks = (n + 8 + 2047) / 2048 + 1;
     if ((rc = alloc(&S.small, 64 + 16 * eval_blocks))) return rc;
     if ((rc = alloc(&S.lag_scalars, n + 16))) return rc;   // n + 8 scalars, then the blinders of zkt_commit_evals_dev
     for (auto& q : S.lag_scalars_q) if ((rc = alloc(&q, n + 16))) return rc;
+    if (S.G == 1) {   // quotient on classes
+        if ((rc = alloc(&S.heads, 3 * NTT_MAX_BATCH * NTT_HEAD))) return rc;
+        if ((rc = alloc(&S.d_win, QC_WIN_POLYS * QC_WIN))) return rc;
+        ZKT_HIP(c, hipHostMalloc(&S.pinned_win, QC_WIN_POLYS * QC_WIN * 32));
+        ZKT_HIP(c, hipEventCreateWithFlags(&S.ev_win, hipEventDisableTiming));
+    }
     if ((rc = dev_alloc(c, (void**)&S.status, 64 * 4))) return rc;
     if ((rc = dev_alloc(c, (void**)&S.status_alt, 64 * 4))) return rc;
     for (auto& p : S.poly_alt) if ((rc = alloc(&p, n + 8))) return rc;
@@ -1215,6 +1402,14 @@ int circuit_fork(zkt_ctx* child, const zkt_ctx* parent) {
     S.roots = P0.roots;
     memcpy(S.zh_inv, P0.zh_inv, sizeof(S.zh_inv));
     S.keys_borrowed = true;
+    if (P0.ccoset_ready) {   // the class arrays of the quotient on classes are keys as well
+        for (int k = 0; k < CS_COUNT; ++k) S.ccoset[k] = P0.ccoset[k];
+        memcpy(S.key_win, P0.key_win, sizeof(S.key_win));
+        memcpy(S.qc_gamma, P0.qc_gamma, sizeof(S.qc_gamma));
+        memcpy(S.qc_vinv, P0.qc_vinv, sizeof(S.qc_vinv));
+        memcpy(S.qc_g3, P0.qc_g3, sizeof(S.qc_g3));
+        S.ccoset_borrowed = S.ccoset_ready = true;
+    }
     child->circuit = st;                      // from here on circuit_release cleans up after a failure
     const int rc = circuit_alloc_work(child, S);
     if (rc) circuit_release(child);
@@ -1696,6 +1891,68 @@ int zkt_ctx_set_wire_elimination(zkt_ctx* c, int mode) {
     if (mode < 0 || mode > 2) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "mode: 0 off, 1 automatic, 2 whenever a table can be built");
     c->wire_elim_mode = mode;
     ++c->msm_epoch;   // early work of an announced proof was issued under the other setting
+    return ZKT_OK;
+}
+
+int zkt_ctx_set_quotient_route(zkt_ctx* c, int mode) {
+    if (!c) return ZKT_ERR_INVALID_ARGUMENT;
+    if (mode < 0 || mode > 2) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "mode: 0 automatic, 1 three classes, 2 the whole coset");
+    c->quotient_route = mode;   // the next proof compares its route with what was transformed ahead of time (choose_route)
+    return ZKT_OK;
+}
+
+int zkt_debug_quotient_top(zkt_ctx* c, uint64_t* out_u, int* out_on_classes) {
+    if (!c || !out_u) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
+    if (!c->circuit) return set_err(c, ZKT_ERR_NOT_LOADED, "no circuit loaded (zkt_circuit_load)");
+    const CircuitState& S = *c->circuit;
+    if (out_on_classes) *out_on_classes = S.use_classes ? 1 : 0;
+    memcpy(out_u, S.last_u, sizeof(S.last_u));   // zero until a proof has taken the route
+    return ZKT_OK;
+}
+
+int zkt_debug_quotient_coeffs(zkt_ctx* c, uint64_t* out, size_t count) {
+    if (!c || !out) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
+    if (!c->circuit) return set_err(c, ZKT_ERR_NOT_LOADED, "no circuit loaded (zkt_circuit_load)");
+    const CircuitState& S = *c->circuit;
+    if (count > 4 * S.n) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "the quotient vector holds 4n elements");
+    (void)hipSetDevice(c->device);
+    ZKT_HIP(c, hipStreamSynchronize(c->stream));
+    ZKT_HIP(c, hipMemcpy(out, S.qev, count * 32, hipMemcpyDeviceToHost));
+    return ZKT_OK;
+}
+
+extern "C++" template <class R>
+static void debug_quotient_classes_host_t(int log_n, const uint64_t* windows, const uint64_t* challenges, uint64_t* out_u,
+                                          uint64_t* out_consts) {
+    typedef Fe<R> F;
+    const QuotientClassConsts<R> q = quotient_class_consts<R>(log_n);
+    for (int k = 0; k < 4; ++k) memcpy(out_consts + 4 * k, q.gamma[k].v, 32);
+    for (int k = 0; k < 9; ++k) memcpy(out_consts + 4 * (4 + k), q.vinv[k].v, 32);
+    for (int k = 0; k < 3; ++k) memcpy(out_consts + 4 * (13 + k), q.g3[k].v, 32);
+    const uint32_t* w = (const uint32_t*)windows;
+    QuotientWindows W{};
+    const uint32_t** slot[10] = {&W.a, &W.b, &W.c, &W.z1, &W.z2, &W.t, &W.sigma1, &W.sigma2, &W.sigma3, &W.q_lookup};
+    for (int k = 0; k < 10; ++k) *slot[k] = w + (size_t)k * QCW * 8;
+    F alpha, beta, delta, u[6];
+    memcpy(alpha.v, challenges, 32);
+    memcpy(beta.v, challenges + 4, 32);
+    memcpy(delta.v, challenges + 8, 32);
+    quotient_top_coefficients<R>(log_n, W, alpha, beta, delta, u);
+    for (int e = 0; e < 6; ++e) memcpy(out_u + 4 * e, u[e].v, 32);
+}
+
+int zkt_debug_quotient_classes_host(int curve, int log_n, const uint64_t* windows, const uint64_t* challenges, uint64_t* out_u,
+                                    uint64_t* out_consts) {
+    if (!windows || !challenges || !out_u || !out_consts) return ZKT_ERR_INVALID_ARGUMENT;
+    if (curve == ZKT_CURVE_BN254) {
+        if (log_n < 3 || log_n + 2 > Bn254Fr::TWO_ADICITY) return ZKT_ERR_INVALID_DOMAIN_SIZE;
+        debug_quotient_classes_host_t<Bn254Fr>(log_n, windows, challenges, out_u, out_consts);
+    } else if (curve == ZKT_CURVE_BLS12_381) {
+        if (log_n < 3 || log_n + 2 > Bls381Fr::TWO_ADICITY) return ZKT_ERR_INVALID_DOMAIN_SIZE;
+        debug_quotient_classes_host_t<Bls381Fr>(log_n, windows, challenges, out_u, out_consts);
+    } else {
+        return ZKT_ERR_INVALID_ARGUMENT;
+    }
     return ZKT_OK;
 }
 
