@@ -336,6 +336,18 @@ int zkt_ctx_set_wire_elimination(zkt_ctx* ctx, int mode);
  * and more, 1 = three classes, 2 = the whole coset.  A sharded context always uses the whole coset (each GPU its class).
  * Forks inherit the mode. */
 int zkt_ctx_set_quotient_route(zkt_ctx* ctx, int mode);
+/* Fused streaming passes of the prover (single launches where the reference sequence makes several and stores vectors
+ * that the next kernel reads back).  Round 5: each opening's linear combination, r included, is one pass that also scales
+ * by xi^i; r(xi) of the three-classes route is the total of the division's suffix sums minus the evaluations the host
+ * holds, not a second evaluation; the scan's block prefixes are added by the kernel that scales by xi^-(j+1).  Round 3:
+ * each grand product is one kernel that forms the terms and scans them within blocks, the scan of the block totals,
+ * and one kernel that applies prefixes and inverted total.  Blinding: one launch per batch of polynomials finds the
+ * trimmed lengths and places the blinders.  The proof bytes, the error codes and the trimmed-length slots are the same
+ * in every mode.
+ * zkt_ctx_set_fused_passes(ctx, mode): 0 = automatic (the default: fused), 1 = fused, 2 = one launch per step, the
+ * sequence the fused one is tested against.  zkt_debug_grand_products follows the mode.  Sharded contexts honour it like
+ * any other context.  Forks inherit the mode. */
+int zkt_ctx_set_fused_passes(zkt_ctx* ctx, int mode);
 /* *log_n = domain the table serves (-1: none, evaluations go through their coefficients), *bases = its points */
 int zkt_lagrange_info(zkt_ctx* ctx, int* log_n, size_t* bases);
 /* PC::commit of poly_from_evals(domain, evals) (util.rs:63-86) with k in 0..3 blinders added as add_blinders_to_poly

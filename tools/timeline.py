@@ -4,8 +4,9 @@ import csv, glob, sys, collections
 f = glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True)[0]
 rows = [r for r in csv.DictReader(open(f))]
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-# a proof starts with the first k_ntt/k_msm after the witness copy; use k_quotient as the anchor
-anchors = [i for i, r in enumerate(rows) if "k_quotient" in r["Kernel_Name"]]
+# a proof starts with the first k_ntt/k_msm after the witness copy; the anchor is the split of the quotient, which every
+# proof launches once on either quotient route (k_quotient itself runs three times on the classes route)
+anchors = [i for i, r in enumerate(rows) if "k_quot_split" in r["Kernel_Name"]]
 if len(anchors) < 3:
     sys.exit("need >= 3 proofs in the trace")
 # which pair of consecutive proofs: k-th from the end (bench.py: warm-up, the timed proofs, then a profiling pass with every
@@ -16,7 +17,7 @@ if len(anchors) < k + 1:
 a0, a1 = anchors[-k - 1], anchors[-k]
 t0, t1 = int(rows[a0]["Start_Timestamp"]), int(rows[a1]["Start_Timestamp"])
 sel = [r for r in rows if t0 <= int(r["Start_Timestamp"]) < t1]
-print("window (quotient to quotient): %.3f ms, %d dispatches" % ((t1 - t0) / 1e6, len(sel)))
+print("window (quotient split to quotient split): %.3f ms, %d dispatches" % ((t1 - t0) / 1e6, len(sel)))
 byq = collections.defaultdict(list)
 for r in sel:
     byq[r["Queue_Id"]].append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]))

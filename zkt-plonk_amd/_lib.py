@@ -1527,6 +1527,12 @@ class Context:
         self._L.zkt_ctx_set_quotient_route.argtypes = [ctypes.c_void_p, ctypes.c_int]
         self.check(self._L.zkt_ctx_set_quotient_route(self._h, int(mode)))
 
+    def set_fused_passes(self, mode: int = 0):
+        """zkt_ctx_set_fused_passes: 0 automatic (fused), 1 the fused streaming passes of rounds 3 and 5 and of the blinding,
+        2 one launch per step (the sequence the fused one is tested against)"""
+        self._L.zkt_ctx_set_fused_passes.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        self.check(self._L.zkt_ctx_set_fused_passes(self._h, int(mode)))
+
     def debug_quotient_top(self):
         """zkt_debug_quotient_top -> (u (6, 4) Montgomery words, whether the last proof took the quotient on classes)"""
         u = np.zeros((6, 4), dtype=np.uint64)

@@ -209,6 +209,7 @@ int zkt_ctx_create(int curve_id, int device_id, zkt_ctx** out) {
     zkt_ctx* c = new zkt_ctx();
     c->batch_off = exp_env("ZKT_MSM_NO_BATCH") != nullptr;
     c->aux_off = exp_env("ZKT_NO_AUX") != nullptr;
+    if (const char* parts = exp_env("ZKT_FUSED_PARTS")) c->fused_parts = atoi(parts) & 7;
     c->curve = curve_id;
     c->device = device_id;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
@@ -233,6 +234,8 @@ int zkt_ctx_fork(zkt_ctx* parent, zkt_ctx** out) {
     c->lagrange_off = parent->lagrange_off;
     c->wire_elim_mode = parent->wire_elim_mode;
     c->quotient_route = parent->quotient_route;
+    c->fused_passes = parent->fused_passes;
+    c->fused_parts = parent->fused_parts;
     c->batch_off = parent->batch_off;
     c->aux_off = parent->aux_off;
     c->ntt_plans = parent->ntt_plans;             // twiddle tables: immutable, owned by the root

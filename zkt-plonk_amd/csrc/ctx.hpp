@@ -84,6 +84,11 @@ struct zkt_ctx {
     bool lagrange_off = false;     // zkt_ctx_set_lagrange(ctx, 0): evaluations are committed through their coefficients
     int wire_elim_mode = 1;        // zkt_ctx_set_wire_elimination: 0 off, 1 automatic (large circuits), 2 whenever a table can be built
     int quotient_route = 0;        // zkt_ctx_set_quotient_route: 0 automatic (three classes on large single-GPU circuits), 1 three classes, 2 the whole coset
+    int fused_passes = 0;          // zkt_ctx_set_fused_passes: 0 automatic (fused), 1 fused, 2 one launch per step (the reference sequence)
+    // the parts of the fused sequences, one bit each: 1 = round 5's openings, 2 = round 3's grand products, 4 = blinding
+    // (A/B builds: ZKT_FUSED_PARTS picks the parts that modes 0 and 1 fuse)
+    int fused_parts = 7;
+    bool fused(int part) const { return fused_passes != 2 && (fused_parts & part); }
     std::shared_ptr<zkt::CircuitState> circuit;
     std::vector<void*> owned;  // every hipMalloc made on behalf of this ctx
 };

@@ -65,8 +65,10 @@ struct LinCombDev {
     uint32_t scalar[LC_MAX_TERMS + 1][9];
     int nterms;
 };
-template <class P>
-__global__ void k_lincomb(LinCombDev a, Fe<P>* out, size_t n) {
+// SCALE: out[i] = x^i sum_k ..., x^i = blk[i / (256 E)] pw[i % 256] (x^256)^(i / 256 % E) from the tables of open_pow_tables
+// (round 5's openings: the combination and the first scaling of open_witness in one pass)
+template <class P, bool SCALE>
+__global__ void k_lincomb(LinCombDev a, Fe<P>* out, size_t n, const Fe<P>* pw, const Fe<P>* blk, int E) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     Fx<P> acc = fx_zero<P>();
@@ -82,7 +84,13 @@ __global__ void k_lincomb(LinCombDev a, Fe<P>* out, size_t n) {
         }
         acc = fx_add<P>(acc, fx_mul2_inl<P>(p[0], sc[0], p[1], sc[1]));   // < 2p each: at most LC_MAX_TERMS p in all
     }
-    fe_store<P>(out + i, fx_pack<P>(fx_canon<P>(acc)));
+    Fe<P> v = fx_pack<P>(fx_canon<P>(acc));
+    if (SCALE) {
+        Fe<P> r = fe_mul<P>(fe_load<P>(blk + blockIdx.x / E), fe_load<P>(pw + threadIdx.x));
+        for (int j = blockIdx.x % E; j > 0; --j) r = fe_mul<P>(r, fe_load<P>(pw + 256));
+        v = fe_mul<P>(v, r);
+    }
+    fe_store<P>(out + i, v);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -106,12 +114,15 @@ __global__ void k_eval_powers(EvalArgs a, Fe<P>* pw, int nblk) {
 // One workgroup per 2048 consecutive coefficients: thread t takes c[base + 256 j + t], j = 0..7 (coalesced), runs
 // Horner in x^256 over j, multiplies by x^t, and the workgroup's sum is multiplied by x^base: one product per
 // coefficient.
-template <class P>
-__global__ __launch_bounds__(256) void k_eval_partial(EvalArgs a, const Fe<P>* pw, Fe<P>* partials, int nblk) {
+// OPEN (bstride > 0): the powers come from the tables of open_pow_tables instead, table a.table[k] of the two at pw and
+// pw + tstride, whose block powers z^(256 E b) are read with stride bstride = 2048 / (256 E)
+template <class P, bool OPEN>
+__global__ __launch_bounds__(256) void k_eval_partial(EvalArgs a, const Fe<P>* pw, Fe<P>* partials, int nblk, size_t tstride, int bstride) {
     __shared__ Fe<P> red[256];
     const int k = blockIdx.y;
     const Fe<P>* poly = (const Fe<P>*)a.poly[k];
-    const Fe<P>* row = pw + (size_t)k * (EV_PW + nblk);
+    const Fe<P>* row = OPEN ? pw + (size_t)a.table[k] * tstride : pw + (size_t)k * (EV_PW + nblk);
+    const Fe<P>* seg = OPEN ? row + 2 * EV_PW + (size_t)bstride * blockIdx.x : row + EV_PW + blockIdx.x;   // x^(2048 blockIdx.x)
     const uint64_t len = a.len[k];
     const uint64_t base = (uint64_t)blockIdx.x * EV_SEG;
     const int t = threadIdx.x;
@@ -124,7 +135,7 @@ __global__ __launch_bounds__(256) void k_eval_partial(EvalArgs a, const Fe<P>* p
             const uint64_t i = base + (uint64_t)j * 256 + t;
             c[j] = (i < len) ? fe_load<P>(poly + i) : fe_zero<P>();
         }
-#pragma unroll 1
+#pragma unroll   // (a rolled loop indexes c[] dynamically: the coefficients then live in scratch memory)
         for (int j = EV_E - 1; j >= 0; --j) acc = fe_add<P>(fe_mul<P>(acc, x256), c[j]);
         acc = fe_mul<P>(acc, fe_load<P>(row + t));
     }
@@ -136,7 +147,7 @@ __global__ __launch_bounds__(256) void k_eval_partial(EvalArgs a, const Fe<P>* p
     }
     if (t == 0)
         fe_store<P>(partials + (size_t)k * nblk + blockIdx.x,
-                    base < len ? fe_mul<P>(red[0], fe_load<P>(row + EV_PW + blockIdx.x)) : fe_zero<P>());
+                    base < len ? fe_mul<P>(red[0], fe_load<P>(seg)) : fe_zero<P>());
 }
 
 template <class P>
@@ -296,6 +307,155 @@ __global__ void k_z_combine(const Fe<P>* pn, const Fe<P>* sd, Fe<P> inv_total, F
     Fe<P> v = fe_mul<P>(fe_load<P>(sd + i), inv_total);
     if (i > 0) v = fe_mul<P>(v, fe_load<P>(pn + i - 1));
     fe_store<P>(out + i, v);
+}
+
+// ---- fused form (zkt_ctx_set_fused_passes): terms and block-local scans in one kernel, prefixes and total in another ----
+// one term of a grand product at row i, the numerator or the denominator alone (k_z1_terms / k_z2_terms make both)
+template <class P, int WHICH, bool DEN>
+ZKT_D Fe<P> z_term(const ZTermsArgs& a, size_t i) {
+    if (i + 1 >= a.n) return fe_one<P>();
+    if (WHICH == 1) {
+        const Fe<P> beta = arg_fe<P>(a.beta), gamma = arg_fe<P>(a.gamma);
+        const Fe<P> ag = fe_add<P>(fe_load<P>((const Fe<P>*)a.a + i), gamma), bg = fe_add<P>(fe_load<P>((const Fe<P>*)a.b + i), gamma),
+                    cg = fe_add<P>(fe_load<P>((const Fe<P>*)a.c + i), gamma);
+        if (DEN)
+            return fe_mul<P>(fe_mul<P>(fe_add<P>(fe_mul<P>(beta, fe_load<P>((const Fe<P>*)a.s1 + i)), ag),
+                                       fe_add<P>(fe_mul<P>(beta, fe_load<P>((const Fe<P>*)a.s2 + i)), bg)),
+                             fe_add<P>(fe_mul<P>(beta, fe_load<P>((const Fe<P>*)a.s3 + i)), cg));
+        const Fe<P> br = fe_mul<P>(beta, fe_load<P>((const Fe<P>*)a.roots + i));
+        const Fe<P> d2 = fe_dbl<P>(br), d4 = fe_dbl<P>(d2), d8 = fe_dbl<P>(d4);
+        const Fe<P> k1br = fe_sub<P>(d8, br);                       // K1 = 7
+        const Fe<P> k2br = fe_add<P>(fe_add<P>(d8, d4), br);        // K2 = 13
+        return fe_mul<P>(fe_mul<P>(fe_add<P>(br, ag), fe_add<P>(k1br, bg)), fe_add<P>(k2br, cg));
+    }
+    const Fe<P> delta = arg_fe<P>(a.delta), eps = arg_fe<P>(a.epsilon);
+    const Fe<P> opd = fe_add<P>(fe_one<P>(), delta);
+    const Fe<P> eopd = fe_mul<P>(eps, opd);
+    if (DEN) {
+        const Fe<P> h1i = fe_load<P>((const Fe<P>*)a.h1 + i), h1n = fe_load<P>((const Fe<P>*)a.h1 + i + 1),
+                    h2i = fe_load<P>((const Fe<P>*)a.h2 + i);
+        return fe_mul<P>(fe_add<P>(fe_add<P>(fe_mul<P>(delta, h2i), eopd), h1i), fe_add<P>(fe_add<P>(fe_mul<P>(delta, h1n), eopd), h2i));
+    }
+    const Fe<P> ti = fe_load<P>((const Fe<P>*)a.t + i), tn = fe_load<P>((const Fe<P>*)a.t + i + 1);
+    return fe_mul<P>(fe_mul<P>(opd, fe_add<P>(eps, fe_load<P>((const Fe<P>*)a.f + i))), fe_add<P>(fe_add<P>(fe_mul<P>(delta, tn), eopd), ti));
+}
+
+// k_scan_local over terms that are never stored: scan position li stands for row li (numerators, forward) or row
+// n - 1 - li (denominators, reversed); out and totals as k_scan_local writes them
+template <class P, int WHICH, bool DEN>
+ZKT_D void z_terms_scan(const ZTermsArgs& a, Fe<P>* out, Fe<P>* totals, Fe<P>* s) {
+    const int t = threadIdx.x;
+    const size_t n = a.n;
+    const size_t i0 = (size_t)blockIdx.x * SC_BLK + (size_t)t * SC_E;
+    Fe<P> x[SC_E];
+#pragma unroll
+    for (int e = 0; e < SC_E; ++e) {
+        const size_t li = i0 + e;
+        x[e] = (li < n) ? z_term<P, WHICH, DEN>(a, DEN ? n - 1 - li : li) : fe_one<P>();
+        if (e) x[e] = fe_mul<P>(x[e - 1], x[e]);
+    }
+    s[t] = x[SC_E - 1];
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {
+        Fe<P> v = s[t];
+        if (t >= d) v = fe_mul<P>(s[t - d], v);
+        __syncthreads();
+        s[t] = v;
+        __syncthreads();
+    }
+    const Fe<P> pre = (t > 0) ? s[t - 1] : fe_one<P>();
+#pragma unroll
+    for (int e = 0; e < SC_E; ++e) {
+        const size_t li = i0 + e;
+        if (li < n) fe_store<P>(out + (DEN ? n - 1 - li : li), t > 0 ? fe_mul<P>(pre, x[e]) : x[e]);
+    }
+    if (t == 255) fe_store<P>(totals + blockIdx.x, s[255]);
+}
+// blockIdx.y = 0: the numerators' block, 1: the denominators' (rows mirrored)
+template <class P, int WHICH>
+__global__ __launch_bounds__(256) void k_z_terms_scan(ZTermsArgs a, Fe<P>* pn, Fe<P>* sd, Fe<P>* tot_n, Fe<P>* tot_d) {
+    __shared__ Fe<P> s[256];
+    if (blockIdx.y) z_terms_scan<P, WHICH, true>(a, sd, tot_d, s);
+    else z_terms_scan<P, WHICH, false>(a, pn, tot_n, s);
+}
+
+// z[i] = PN[i-1] SD[i] / prod(den) from the block-local scans: PN[j] = pre_n[j / 1024 - 1] pn[j], SD[i] = pre_d[rb - 1] sd[i]
+// with rb = nb - 1 - i / 1024 the block of the reversed scan (n is a power of two: the blocks of both scans coincide), and
+// PN[i-1] = pre_n[b - 1] alone where i starts block b.  One workgroup per scan block.
+template <class P>
+__global__ __launch_bounds__(256) void k_z_apply_combine(const Fe<P>* pn, const Fe<P>* sd, const Fe<P>* pre_n, const Fe<P>* pre_d,
+                                                         Fe<P> inv_total, Fe<P>* out, size_t n) {
+    const size_t b = blockIdx.x, rb = gridDim.x - 1 - b;
+    Fe<P> k = inv_total;
+    if (b) k = fe_mul<P>(k, fe_load<P>(pre_n + b - 1));
+    if (rb) k = fe_mul<P>(k, fe_load<P>(pre_d + rb - 1));
+#pragma unroll
+    for (int e = 0; e < SC_E; ++e) {
+        const size_t i = b * SC_BLK + (size_t)e * 256 + threadIdx.x;
+        if (i >= n) break;
+        Fe<P> v = fe_mul<P>(fe_load<P>(sd + i), k);
+        if (i % SC_BLK) v = fe_mul<P>(v, fe_load<P>(pn + i - 1));
+        fe_store<P>(out + i, v);
+    }
+}
+
+// ---- trimmed length and blinders of a batch of polynomials in one launch (zkt_ctx_set_fused_passes) ----
+constexpr int TB_THREADS = 1024;
+// Number of coefficients of p[0..n) after stripping trailing zeros, by the whole workgroup (the same value in every
+// thread).  The polynomials are dense: the top TB_THREADS coefficients nearly always hold the answer; if they are all zero
+// the workgroup walks down the rest itself.
+template <class P>
+ZKT_D uint32_t wg_trim_len(const Fe<P>* p, size_t n, uint32_t* best) {
+    const int t = threadIdx.x;
+    __syncthreads();
+    if (t == 0) *best = 0;
+    __syncthreads();
+    for (size_t hi = n; hi > 0;) {
+        const size_t lo = hi > (size_t)TB_THREADS ? hi - TB_THREADS : 0;
+        const size_t i = lo + t;
+        uint32_t v = 0;
+        if (i < hi && !fe_is_zero<P>(fe_load<P>(p + i))) v = (uint32_t)(i + 1);
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            uint32_t o = __shfl_down(v, d);
+            v = o > v ? o : v;
+        }
+        if ((t & 63) == 0 && v) atomicMax(best, v);
+        __syncthreads();
+        const uint32_t found = *best;
+        __syncthreads();
+        if (found) return found;
+        hi = lo;
+    }
+    return 0;
+}
+struct TrimBlindJob {
+    void* poly;
+    const void* bl;
+    uint32_t* len;
+    int k;
+};
+struct TrimBlindArgs {
+    TrimBlindJob job[NTT_MAX_BATCH];
+};
+// one workgroup per polynomial: what k_trim_len (both launches) and k_add_blinders do; k < 0 only clears the slack
+template <class P>
+__global__ __launch_bounds__(TB_THREADS) void k_trim_blind(TrimBlindArgs a, size_t n, int zero_count) {
+    __shared__ uint32_t best;
+    const TrimBlindJob j = a.job[blockIdx.x];
+    Fe<P>* p = (Fe<P>*)j.poly;
+    const int t = threadIdx.x;
+    if (t < zero_count) fe_store<P>(p + n + t, fe_zero<P>());
+    if (j.k < 0) return;
+    const uint32_t L = wg_trim_len<P>(p, n, &best);   // (its barriers order the stores above before the blinders)
+    if (t == 0) *j.len = L;
+    Fe<P> b = fe_zero<P>();
+    if (t < j.k) {
+        b = fe_load<P>((const Fe<P>*)j.bl + t);
+        fe_store<P>(p + L + t, b);
+    }
+    __syncthreads();
+    if (t < j.k) fe_store<P>(p + t, fe_sub<P>(fe_load<P>(p + t), b));
 }
 
 // Scalars of a commitment taken in the Lagrange basis (lagrange.hip): the polynomial with evaluations e_i (plus, when
@@ -471,6 +631,25 @@ __global__ void k_quot_blind(Fe<P>* lo, Fe<P>* mid, Fe<P>* hi, const uint32_t* l
     fe_store<P>(hi, fe_sub<P>(fe_load<P>(hi), b1));
 }
 
+// the three trims of the quotient's chunks and k_quot_blind in one launch (lens[3] is there already)
+template <class P>
+__global__ __launch_bounds__(TB_THREADS) void k_quot_trim_blind(Fe<P>* lo, Fe<P>* mid, Fe<P>* hi, size_t chunk, uint32_t* lens,
+                                                                const Fe<P>* b0b1, uint32_t n, uint32_t* status) {
+    __shared__ uint32_t best;
+    const uint32_t l0 = wg_trim_len<P>(lo, chunk, &best), l1 = wg_trim_len<P>(mid, chunk, &best), l2 = wg_trim_len<P>(hi, chunk, &best);
+    if (threadIdx.x != 0) return;
+    lens[0] = l0;
+    lens[1] = l1;
+    lens[2] = l2;
+    if (lens[3] > 3 * (n + 2)) { atomicOr(status, 2u); return; }
+    if (l1 == 0 || l2 == 0) { atomicOr(status, 1u); return; }
+    Fe<P> b0 = fe_load<P>(b0b1), b1 = fe_load<P>(b0b1 + 1);
+    fe_store<P>(lo + l0, b0);
+    fe_store<P>(mid, fe_sub<P>(fe_load<P>(mid), b0));
+    fe_store<P>(mid + l1, b1);
+    fe_store<P>(hi, fe_sub<P>(fe_load<P>(hi), b1));
+}
+
 // ---------------------------------------------------------------------------------------------
 // opening witness
 // ---------------------------------------------------------------------------------------------
@@ -508,8 +687,8 @@ ZKT_D void pow_rounds(Fe<P>* tab, const Fe<P>& x, int cnt, int lt) {
 }
 // pw[0][t] = z^t, pw[1][t] = zinv^t, t = 0..256 (two rows of EV_PW), then blk[0][b] = z^(256 E b), blk[1][b] = zinv^(256 E b), b < nblk
 template <class P>
-__global__ __launch_bounds__(OW_THREADS) void k_pow_tables(Fe<P> z, Fe<P> zinv, Fe<P>* pw, int nblk, int E) {
-    __shared__ Fe<P> row[2][EV_PW], seg[2][EV_PW], top[2][EV_PW];
+ZKT_D void pow_tables(const Fe<P>& z, const Fe<P>& zinv, Fe<P>* pw, int nblk, int E, Fe<P> (*row)[EV_PW], Fe<P> (*seg)[EV_PW],
+                      Fe<P> (*top)[EV_PW]) {
     const int half = threadIdx.x / (OW_THREADS / 2), lt = threadIdx.x % (OW_THREADS / 2);
     pow_rounds<P>(row[half], half ? zinv : z, 256, lt);
     Fe<P> y = row[half][256];                       // x^(256 E)
@@ -520,6 +699,19 @@ __global__ __launch_bounds__(OW_THREADS) void k_pow_tables(Fe<P> z, Fe<P> zinv, 
     for (int t = lt; t < EV_PW; t += OW_THREADS / 2) fe_store<P>(pw + half * EV_PW + t, row[half][t]);
     Fe<P>* blk = pw + 2 * EV_PW + (size_t)half * nblk;
     for (int b = lt; b < nblk; b += OW_THREADS / 2) fe_store<P>(blk + b, fe_mul<P>(seg[half][b & 255], top[half][b >> 8]));
+}
+template <class P>
+__global__ __launch_bounds__(OW_THREADS) void k_pow_tables(Fe<P> z, Fe<P> zinv, Fe<P>* pw, int nblk, int E) {
+    __shared__ Fe<P> row[2][EV_PW], seg[2][EV_PW], top[2][EV_PW];
+    pow_tables<P>(z, zinv, pw, nblk, E, row, seg, top);
+}
+// the tables of two points in one launch, one workgroup each: table j at pw + j * stride
+template <class P>
+__global__ __launch_bounds__(OW_THREADS) void k_pow_tables2(Fe<P> z0, Fe<P> z0inv, Fe<P> z1, Fe<P> z1inv, Fe<P>* pw, size_t stride, int nblk,
+                                                            int E) {
+    __shared__ Fe<P> row[2][EV_PW], seg[2][EV_PW], top[2][EV_PW];
+    if (blockIdx.x) pow_tables<P>(z1, z1inv, pw + stride, nblk, E, row, seg, top);
+    else pow_tables<P>(z0, z0inv, pw, nblk, E, row, seg, top);
 }
 // out[i] = in[i] * x^(i + shift) for i < n, zero for n <= i < cap (shift 0 or 1).  One workgroup per 256 E consecutive elements,
 // thread t takes i = base + 256 j + t (coalesced): x^(i + shift) = blk[workgroup] * pw[t + shift] * (x^256)^j.
@@ -533,6 +725,28 @@ __global__ __launch_bounds__(256) void k_mul_pow(const Fe<P>* in, Fe<P>* out, si
         const size_t i = base + (size_t)j * 256 + threadIdx.x;
         if (i >= cap) break;
         fe_store<P>(out + i, i < n ? fe_mul<P>(fe_load<P>(in + i), r) : fe_zero<P>());
+        if (j + 1 < E) r = fe_mul<P>(r, fe_load<P>(pw + 256));
+    }
+}
+
+// open_divide's last two launches in one: S[i] = tb[i] + prefix of its scan block (k_scan_apply of the reversed sum scan),
+// out[j] = S[j + 1] zinv^(j + 1) for j + 1 < len and zero at j = len - 1 (k_mul_pow with shift 1); *total = S[0] = sum_i t_i
+template <class P>
+__global__ __launch_bounds__(256) void k_divide_apply(const Fe<P>* tb, const Fe<P>* block_prefix, Fe<P>* out, size_t len, const Fe<P>* pw,
+                                                      const Fe<P>* blk, int E, Fe<P>* total) {
+    const size_t base = (size_t)blockIdx.x * 256 * E;
+    auto S = [&](size_t i) {
+        const size_t sb = (len - 1 - i) / SC_BLK;
+        const Fe<P> v = fe_load<P>(tb + i);
+        return sb ? fe_add<P>(fe_load<P>(block_prefix + sb - 1), v) : v;
+    };
+    if (blockIdx.x == 0 && threadIdx.x == 0) fe_store<P>(total, S(0));
+    Fe<P> r = fe_mul<P>(fe_load<P>(blk + blockIdx.x), fe_load<P>(pw + threadIdx.x + 1));
+#pragma unroll 1
+    for (int j = 0; j < E; ++j) {
+        const size_t i = base + (size_t)j * 256 + threadIdx.x;
+        if (i >= len) break;
+        fe_store<P>(out + i, i + 1 < len ? fe_mul<P>(S(i + 1), r) : fe_zero<P>());
         if (j + 1 < E) r = fe_mul<P>(r, fe_load<P>(pw + 256));
     }
 }
@@ -771,7 +985,20 @@ int poly_add_blinders(zkt_ctx* c, void* p, const uint32_t* d_len, const void* d_
     ZKT_DISPATCH(c, add_blinders_t, p, d_len, d_blinders, k);
 }
 
-template <class P> static int lincomb_t(zkt_ctx* c, const LinCombArgs& a, void* out, size_t n) {
+template <class P> static int trim_blind_t(zkt_ctx* c, const TrimBlindSpec* jobs, int nb, size_t n, int zero_count) {
+    if (nb <= 0 || !n) return ZKT_OK;
+    if (nb > NTT_MAX_BATCH || zero_count > TB_THREADS) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "trim_blind: batch too large");
+    TrimBlindArgs a{};
+    for (int y = 0; y < nb; ++y) a.job[y] = TrimBlindJob{jobs[y].poly, jobs[y].d_blinders, jobs[y].d_len, jobs[y].k};
+    hipLaunchKernelGGL(k_trim_blind<P>, dim3(nb), dim3(TB_THREADS), 0, c->stream, a, n, zero_count);
+    ZKT_HIP(c, hipGetLastError());
+    return ZKT_OK;
+}
+int poly_trim_blind(zkt_ctx* c, const TrimBlindSpec* jobs, int nb, size_t n, int zero_count) {
+    ZKT_DISPATCH(c, trim_blind_t, jobs, nb, n, zero_count);
+}
+
+template <class P> static int lincomb_t(zkt_ctx* c, const LinCombArgs& a, void* out, size_t n, const void* d_powers) {
     static_assert(LC_MAX_TERMS <= 32, "the lazy sum of the terms must stay below 2^6 p");
     LinCombDev d{};
     d.nterms = a.nterms;
@@ -781,19 +1008,29 @@ template <class P> static int lincomb_t(zkt_ctx* c, const LinCombArgs& a, void* 
         const Fx<P> h = fx_cond_sub_p<P>(fx_from_ark<P>(host_fe<P>(a.scalar[k])));
         for (int w = 0; w < 9; ++w) d.scalar[k][w] = h.l[w];
     }
-    hipLaunchKernelGGL(k_lincomb<P>, dim3(nblocks(n)), dim3(256), 0, c->stream, d, (Fe<P>*)out, n);
+    if (d_powers) {
+        const Fe<P>* pw = (const Fe<P>*)d_powers;
+        hipLaunchKernelGGL((k_lincomb<P, true>), dim3(nblocks(n)), dim3(256), 0, c->stream, d, (Fe<P>*)out, n, pw,
+                           pw + 2 * EV_PW, ow_elems(n));
+    } else {
+        hipLaunchKernelGGL((k_lincomb<P, false>), dim3(nblocks(n)), dim3(256), 0, c->stream, d, (Fe<P>*)out, n, (const Fe<P>*)nullptr,
+                           (const Fe<P>*)nullptr, 1);
+    }
     ZKT_HIP(c, hipGetLastError());
     return ZKT_OK;
 }
-int poly_lincomb(zkt_ctx* c, const LinCombArgs& a, void* out, size_t n) { ZKT_DISPATCH(c, lincomb_t, a, out, n); }
+int poly_lincomb(zkt_ctx* c, const LinCombArgs& a, void* out, size_t n) { ZKT_DISPATCH(c, lincomb_t, a, out, n, nullptr); }
+int open_combine(zkt_ctx* c, const LinCombArgs& a, void* out, size_t len, const void* d_powers) {
+    ZKT_DISPATCH(c, lincomb_t, a, out, len, d_powers);
+}
 
 template <class P> static int eval_many_t(zkt_ctx* c, const EvalArgs& a, void* d_partials, void* d_results, void* d_powers) {
     uint64_t maxlen = 1;
     for (int k = 0; k < a.count; ++k) if (a.len[k] > maxlen) maxlen = a.len[k];
     int nblk = (int)((maxlen + EV_SEG - 1) / EV_SEG);
     hipLaunchKernelGGL(k_eval_powers<P>, dim3(a.count), dim3(1024), 0, c->stream, a, (Fe<P>*)d_powers, nblk);
-    hipLaunchKernelGGL(k_eval_partial<P>, dim3(nblk, a.count), dim3(256), 0, c->stream, a, (const Fe<P>*)d_powers,
-                       (Fe<P>*)d_partials, nblk);
+    hipLaunchKernelGGL((k_eval_partial<P, false>), dim3(nblk, a.count), dim3(256), 0, c->stream, a, (const Fe<P>*)d_powers,
+                       (Fe<P>*)d_partials, nblk, (size_t)0, 0);
     ZKT_HIP(c, hipGetLastError());
     hipLaunchKernelGGL(k_eval_final<P>, dim3(a.count), dim3(256), 0, c->stream, (const Fe<P>*)d_partials, nblk, (Fe<P>*)d_results);
     ZKT_HIP(c, hipGetLastError());
@@ -801,6 +1038,31 @@ template <class P> static int eval_many_t(zkt_ctx* c, const EvalArgs& a, void* d
 }
 int poly_eval_many(zkt_ctx* c, const EvalArgs& a, void* d_partials, void* d_results, void* d_powers) {
     ZKT_DISPATCH(c, eval_many_t, a, d_partials, d_results, d_powers);
+}
+
+// poly_eval_many at no more than two distinct points whose opening tables (for polynomials of `len` coefficients) are built
+// in the same sequence, one launch for both: a.table[k] says which of z0, z1 polynomial k is evaluated at
+template <class P> static int eval_open_tables_t(zkt_ctx* c, const EvalArgs& a, const uint32_t* z0, const uint32_t* z0inv, const uint32_t* z1,
+                                                 const uint32_t* z1inv, size_t len, void* d_partials, void* d_results, void* d_powers) {
+    const int E = ow_elems(len);
+    if (EV_SEG % (256 * E)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "polynomials too long for the shared power tables");
+    for (int k = 0; k < a.count; ++k)
+        if (a.len[k] > len) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "polynomial longer than the power tables");
+    const int nblk = (int)((len + EV_SEG - 1) / EV_SEG);
+    const size_t stride = open_witness_powers(len);
+    hipLaunchKernelGGL(k_pow_tables2<P>, dim3(2), dim3(OW_THREADS), 0, c->stream, host_fe<P>(z0), host_fe<P>(z0inv), host_fe<P>(z1),
+                       host_fe<P>(z1inv), (Fe<P>*)d_powers, stride, (int)ow_blocks(len), E);
+    ZKT_HIP(c, hipGetLastError());
+    hipLaunchKernelGGL((k_eval_partial<P, true>), dim3(nblk, a.count), dim3(256), 0, c->stream, a, (const Fe<P>*)d_powers, (Fe<P>*)d_partials,
+                       nblk, stride, EV_SEG / (256 * E));
+    ZKT_HIP(c, hipGetLastError());
+    hipLaunchKernelGGL(k_eval_final<P>, dim3(a.count), dim3(256), 0, c->stream, (const Fe<P>*)d_partials, nblk, (Fe<P>*)d_results);
+    ZKT_HIP(c, hipGetLastError());
+    return ZKT_OK;
+}
+int poly_eval_open_tables(zkt_ctx* c, const EvalArgs& a, const uint32_t z0[8], const uint32_t z0_inv[8], const uint32_t z1[8],
+                          const uint32_t z1_inv[8], size_t len, void* d_partials, void* d_results, void* d_powers) {
+    ZKT_DISPATCH(c, eval_open_tables_t, a, z0, z0_inv, z1, z1_inv, len, d_partials, d_results, d_powers);
 }
 
 template <class P> static int z1_terms_t(zkt_ctx* c, const ZTermsArgs& a) {
@@ -831,6 +1093,54 @@ template <class P> static int z_combine_t(zkt_ctx* c, const void* pn, const void
     return ZKT_OK;
 }
 int z_combine(zkt_ctx* c, const void* pn, const void* sd, const uint32_t inv_total[8], void* out, size_t n) { ZKT_DISPATCH(c, z_combine_t, pn, sd, inv_total, out, n); }
+
+// scratch of one scan_t over n elements (totals and prefixes of every level)
+static size_t scan_tmp_elems(size_t n) {
+    size_t nb = (n + SC_BLK - 1) / SC_BLK, need = 1;
+    while (nb > 1) {
+        need += 2 * nb;
+        nb = (nb + SC_BLK - 1) / SC_BLK;
+    }
+    return need;
+}
+size_t grand_product_tmp_elems(size_t n) { return 2 * scan_tmp_elems(n); }
+template <class P> static int grand_product_scan_t(zkt_ctx* c, const ZTermsArgs& a, int which, void* pn, void* sd, void* tmp,
+                                                   const void** d_total_den) {
+    const size_t n = a.n;
+    if (n == 0 || (n & (n - 1))) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "grand product: n must be a power of two");
+    const size_t nb = (n + SC_BLK - 1) / SC_BLK;
+    Fe<P>* tn = (Fe<P>*)tmp;                       // [totals nb][prefix nb][deeper levels]
+    Fe<P>* td = tn + scan_tmp_elems(n);
+    if (which == 1)
+        hipLaunchKernelGGL((k_z_terms_scan<P, 1>), dim3((unsigned)nb, 2), dim3(256), 0, c->stream, a, (Fe<P>*)pn, (Fe<P>*)sd, tn, td);
+    else
+        hipLaunchKernelGGL((k_z_terms_scan<P, 2>), dim3((unsigned)nb, 2), dim3(256), 0, c->stream, a, (Fe<P>*)pn, (Fe<P>*)sd, tn, td);
+    ZKT_HIP(c, hipGetLastError());
+    if (nb > 1) {
+        int rc;
+        if ((rc = scan_t<P, OpMul>(c, tn, tn + nb, nb, false, tn + 2 * nb))) return rc;
+        if ((rc = scan_t<P, OpMul>(c, td, td + nb, nb, false, td + 2 * nb))) return rc;
+    }
+    *d_total_den = nb > 1 ? td + nb + (nb - 1) : td;
+    return ZKT_OK;
+}
+int grand_product_scan(zkt_ctx* c, const ZTermsArgs& a, int which, void* pn_local, void* sd_local, void* d_tmp, const void** d_total_den) {
+    ZKT_DISPATCH(c, grand_product_scan_t, a, which, pn_local, sd_local, d_tmp, d_total_den);
+}
+template <class P> static int grand_product_combine_t(zkt_ctx* c, const void* pn, const void* sd, const void* tmp, const uint32_t* inv,
+                                                      void* out, size_t n) {
+    const size_t nb = (n + SC_BLK - 1) / SC_BLK;
+    const Fe<P>* tn = (const Fe<P>*)tmp;
+    const Fe<P>* td = tn + scan_tmp_elems(n);
+    hipLaunchKernelGGL(k_z_apply_combine<P>, dim3((unsigned)nb), dim3(256), 0, c->stream, (const Fe<P>*)pn, (const Fe<P>*)sd, tn + nb, td + nb,
+                       host_fe<P>(inv), (Fe<P>*)out, n);
+    ZKT_HIP(c, hipGetLastError());
+    return ZKT_OK;
+}
+int grand_product_combine(zkt_ctx* c, const void* pn_local, const void* sd_local, const void* d_tmp, const uint32_t inv_total[8], void* out,
+                          size_t n) {
+    ZKT_DISPATCH(c, grand_product_combine_t, pn_local, sd_local, d_tmp, inv_total, out, n);
+}
 
 template <class P> static int lagrange_scalars_t(zkt_ctx* c, const void* ev, size_t n, const uint32_t* d_len, const void* d_bl, int k,
                                                  const void* roots, void* out) {
@@ -947,7 +1257,8 @@ __global__ void k_quot_split(const Fe<P>* q, size_t chunk, size_t cap, Fe<P>* lo
     fe_store<P>(hi + i, in ? fe_load<P>(q + 2 * chunk + i) : z);
 }
 
-template <class P> static int quot_split_t(zkt_ctx* c, const void* q, size_t n, const void* b0b1, void* lo, void* mid, void* hi, uint32_t* d_status) {
+template <class P> static int quot_split_t(zkt_ctx* c, const void* q, size_t n, const void* b0b1, void* lo, void* mid, void* hi, uint32_t* d_status,
+                                            bool fused) {
     // d_status[0] = error bits ; d_status[4..7] = lens (lo, mid, hi, q), zero on entry
     const Fe<P>* Q = (const Fe<P>*)q;
     const size_t cap = n + 8, chunk = n + 2;
@@ -956,6 +1267,15 @@ template <class P> static int quot_split_t(zkt_ctx* c, const void* q, size_t n, 
     ZKT_HIP(c, hipGetLastError());
     uint32_t* lens = d_status + 4;
     int rc;
+    if (fused) {   // the quotient's own check first, then the three trims and the blinders as one launch
+        const size_t qlo = 3 * chunk, qhi = 4 * n;
+        hipLaunchKernelGGL(k_trim_len<P>, dim3(nblocks(qhi - qlo)), dim3(256), 0, c->stream, Q, qlo, qhi, lens + 3, 0, (Fe<P>*)nullptr, 0);
+        ZKT_HIP(c, hipGetLastError());
+        hipLaunchKernelGGL(k_quot_trim_blind<P>, dim3(1), dim3(TB_THREADS), 0, c->stream, (Fe<P>*)lo, (Fe<P>*)mid, (Fe<P>*)hi, chunk, lens,
+                           (const Fe<P>*)b0b1, (uint32_t)n, d_status);
+        ZKT_HIP(c, hipGetLastError());
+        return ZKT_OK;
+    }
     if ((rc = trim_len_t<P>(c, lo, chunk, lens + 0))) return rc;
     if ((rc = trim_len_t<P>(c, mid, chunk, lens + 1))) return rc;
     if ((rc = trim_len_t<P>(c, hi, chunk, lens + 2))) return rc;
@@ -969,8 +1289,9 @@ template <class P> static int quot_split_t(zkt_ctx* c, const void* q, size_t n, 
     ZKT_HIP(c, hipGetLastError());
     return ZKT_OK;
 }
-int quotient_split_blind(zkt_ctx* c, const void* q, size_t n, const void* d_b0b1, void* q_lo, void* q_mid, void* q_hi, uint32_t* d_status) {
-    ZKT_DISPATCH(c, quot_split_t, q, n, d_b0b1, q_lo, q_mid, q_hi, d_status);
+int quotient_split_blind(zkt_ctx* c, const void* q, size_t n, const void* d_b0b1, void* q_lo, void* q_mid, void* q_hi, uint32_t* d_status,
+                         bool fused) {
+    ZKT_DISPATCH(c, quot_split_t, q, n, d_b0b1, q_lo, q_mid, q_hi, d_status, fused);
 }
 
 
@@ -1072,11 +1393,26 @@ int open_pow_tables(zkt_ctx* c, const uint32_t z[8], const uint32_t z_inv[8], vo
     ZKT_DISPATCH(c, open_pow_tables_t, z, z_inv, d_powers, len);
 }
 // out[j] = S[j + 1] * zinv^(j + 1) for j + 1 < len, zero at j = len - 1, where S is the suffix sum of t (t_i = p_i z^i)
-template <class P> static int open_divide_t(zkt_ctx* c, const void* t, size_t len, void* tb, void* scan_tmp, void* out, const void* d_powers) {
+template <class P> static int open_divide_t(zkt_ctx* c, const void* t, size_t len, void* tb, void* scan_tmp, void* out, const void* d_powers,
+                                             void* d_total = nullptr) {
     if (len == 0) return ZKT_OK;
     const Fe<P>* pw = (const Fe<P>*)d_powers;
     const int E = ow_elems(len);
     const unsigned blocks = (unsigned)ow_blocks(len);
+    if (d_total) {   // the scan without its apply pass: k_divide_apply adds the block prefixes as it scales
+        Fe<P>* tmp = (Fe<P>*)scan_tmp;
+        const size_t nb = (len + SC_BLK - 1) / SC_BLK;
+        hipLaunchKernelGGL((k_scan_local<P, OpAdd>), dim3((unsigned)nb), dim3(256), 0, c->stream, (const Fe<P>*)t, (Fe<P>*)tb, len, 1, tmp);
+        ZKT_HIP(c, hipGetLastError());
+        if (nb > 1) {
+            int rc = scan_t<P, OpAdd>(c, tmp, tmp + nb, nb, false, tmp + 2 * nb);
+            if (rc) return rc;
+        }
+        hipLaunchKernelGGL(k_divide_apply<P>, dim3(blocks), dim3(256), 0, c->stream, (const Fe<P>*)tb, (const Fe<P>*)tmp + nb, (Fe<P>*)out, len,
+                           pw + EV_PW, pw + 2 * EV_PW + blocks, E, (Fe<P>*)d_total);
+        ZKT_HIP(c, hipGetLastError());
+        return ZKT_OK;
+    }
     int rc = scan_t<P, OpAdd>(c, (const Fe<P>*)t, (Fe<P>*)tb, len, true, (Fe<P>*)scan_tmp);
     if (rc) return rc;
     hipLaunchKernelGGL(k_mul_pow<P>, dim3(blocks), dim3(256), 0, c->stream, (const Fe<P>*)tb + 1, (Fe<P>*)out, len - 1, len,
@@ -1084,8 +1420,8 @@ template <class P> static int open_divide_t(zkt_ctx* c, const void* t, size_t le
     ZKT_HIP(c, hipGetLastError());
     return ZKT_OK;
 }
-int open_divide(zkt_ctx* c, const void* t, size_t len, void* d_tmp, void* d_scan_tmp, void* out, const void* d_powers) {
-    ZKT_DISPATCH(c, open_divide_t, t, len, d_tmp, d_scan_tmp, out, d_powers);
+int open_divide(zkt_ctx* c, const void* t, size_t len, void* d_tmp, void* d_scan_tmp, void* out, const void* d_powers, void* d_total) {
+    ZKT_DISPATCH(c, open_divide_t, t, len, d_tmp, d_scan_tmp, out, d_powers, d_total);
 }
 
 template <class P> static int open_witness_t(zkt_ctx* c, const void* p, size_t len, const uint32_t* z, const uint32_t* zinv, void* ta, void* tb, void* scan_tmp, void* out, void* d_powers) {

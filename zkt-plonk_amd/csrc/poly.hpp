@@ -5,7 +5,7 @@
 
 namespace zkt {
 
-constexpr int LC_MAX_TERMS = 16;
+constexpr int LC_MAX_TERMS = 24;   // round 5's first opening: r's 13 terms and 8 more
 struct LinCombArgs {            // out[i] = sum_k scalar[k] * poly[k][i]  (poly k read as zero beyond len[k])
     const void* poly[LC_MAX_TERMS];
     uint64_t len[LC_MAX_TERMS];
@@ -19,6 +19,7 @@ struct EvalArgs {               // result[k] = poly[k](point[k])
     uint64_t len[EVAL_MAX];
     uint32_t point[EVAL_MAX][8];
     int count;
+    uint8_t table[EVAL_MAX];    // poly_eval_open_tables: which of the two points (point[] is not read there)
 };
 
 struct QuotientArgs {           // all vectors hold 4n coset evaluations
@@ -66,18 +67,41 @@ int poly_gather_pad(zkt_ctx* c, const void* d_values, size_t n_vars, const uint3
                     uint32_t* d_status);
 int poly_add_blinders(zkt_ctx* c, void* p, const uint32_t* d_len, const void* d_blinders, int k, size_t cap);  // prove.rs:472-483
 int poly_lincomb(zkt_ctx* c, const LinCombArgs& a, void* out, size_t n);
+// k_trim_len (both launches) and k_add_blinders for up to NTT_MAX_BATCH polynomials of n coefficients in ONE launch, one
+// workgroup each: clears zero_count coefficients at poly + n, writes the trimmed length to *d_len and places the k blinders;
+// k < 0: only the clearing.
+struct TrimBlindSpec {
+    void* poly;
+    const void* d_blinders;
+    uint32_t* d_len;
+    int k;
+};
+int poly_trim_blind(zkt_ctx* c, const TrimBlindSpec* jobs, int nb, size_t n, int zero_count);
 // scalars (n + k of them) of a commitment taken against the Lagrange-prefix table (lagrange.hip) for the polynomial with
 // evaluations ev[0..n) and, when k > 0, the k blinders of prove.rs:472-483 appended at its trimmed length *d_len
 int lagrange_scalars(zkt_ctx* c, const void* ev, size_t n, const uint32_t* d_len, const void* d_blinders, int k, const void* d_roots,
                      void* out);
 // d_powers: scratch of EVAL_MAX * (257 + ceil(maxlen / 2048)) elements (powers of each evaluation point)
 int poly_eval_many(zkt_ctx* c, const EvalArgs& a, void* d_partials, void* d_results, void* d_powers);         // linearization_poly.rs:55-75
+// The fused form for round 5: the polynomials (at most `len` coefficients) are evaluated at z0 (table[k] = 0) or z1 (1), and
+// the powers come from the opening tables of both points, built here in ONE launch and left in d_powers for the openings:
+// the tables of z0 at d_powers, those of z1 at d_powers + open_witness_powers(len) elements (layout of open_pow_tables).
+int poly_eval_open_tables(zkt_ctx* c, const EvalArgs& a, const uint32_t z0[8], const uint32_t z0_inv[8], const uint32_t z1[8],
+                          const uint32_t z1_inv[8], size_t len, void* d_partials, void* d_results, void* d_powers);
 // grand products (permutation/mod.rs:181-254, lookup/mod.rs:94-151)
 int z1_terms(zkt_ctx* c, const ZTermsArgs& a);
 int z2_terms(zkt_ctx* c, const ZTermsArgs& a);
 int scan_mul(zkt_ctx* c, const void* in, void* out, size_t n, bool reverse, void* d_tmp /* >= 2*(n/1024 + 2048) elems */);
 int scan_add(zkt_ctx* c, const void* in, void* out, size_t n, bool reverse, void* d_tmp);
 int z_combine(zkt_ctx* c, const void* pn, const void* sd, const uint32_t inv_total[8], void* out, size_t n);
+// A grand product in its fused form (which = 1 permutation, 2 lookup; a.num / a.den are not used): one kernel forms the
+// terms and scans them within blocks of 1024 into pn_local (forward) and sd_local (reversed), the block totals are scanned
+// in d_tmp (grand_product_tmp_elems(n) elements), *d_total_den points at the product of all denominators (device).  After the
+// host inverted it, grand_product_combine writes z from the local scans, the block prefixes in d_tmp and the inverse.
+size_t grand_product_tmp_elems(size_t n);
+int grand_product_scan(zkt_ctx* c, const ZTermsArgs& a, int which, void* pn_local, void* sd_local, void* d_tmp, const void** d_total_den);
+int grand_product_combine(zkt_ctx* c, const void* pn_local, const void* sd_local, const void* d_tmp, const uint32_t inv_total[8], void* out,
+                          size_t n);
 // quotient (quotient_poly.rs:98-224)
 int quotient_pointwise(zkt_ctx* c, const QuotientArgs& a);
 // in place: arkworks Montgomery form -> the quotient kernel's R' = 2^261 form times 32^k32 (k32 in {0, 1}).
@@ -86,8 +110,9 @@ int to_hat_form(zkt_ctx* c, void* v, size_t n, int k32);
 // class-major (rank r's n4 / G points at [r * n4 / G, ...)) -> natural order of the 4n coset: out[cls + G i] = in[cls * (n4 / G) + i].
 // chunks > 1: the exchange went out in pieces, `in` is [chunk][class][n4 / G / chunks]
 int quotient_interleave(zkt_ctx* c, const void* in, void* out, size_t n4, uint32_t G, uint32_t chunks = 1);
+// fused: the three trims and the blinders as one launch
 int quotient_split_blind(zkt_ctx* c, const void* q, size_t n, const void* d_b0b1, void* q_lo, void* q_mid, void* q_hi,
-                         uint32_t* d_status);                                                   // prove.rs:287-300
+                         uint32_t* d_status, bool fused = false);                               // prove.rs:287-300
 // The quotient on classes 0, 1, 2 of the 4n coset (prover.hip): [3][n] class arrays of a whole-coset table (4n elements);
 // the windows [first, first + QC_WIN) of QC_WIN_POLYS polynomials gathered back to back for one copy to the host; and the
 // way back from the three inverse class transforms (q: 4n elements, [3][n] on entry) to the 4n coefficients of t:
@@ -108,7 +133,12 @@ constexpr int OPEN_PW_ROW = 257;
 int open_elems(size_t len);
 size_t open_blocks(size_t len);
 int open_pow_tables(zkt_ctx* c, const uint32_t z[8], const uint32_t z_inv[8], void* d_powers, size_t len);
-int open_divide(zkt_ctx* c, const void* t, size_t len, void* d_tmp, void* d_scan_tmp, void* out, const void* d_powers);
+// d_total (device, one element) given: the fused form -- the scan's block prefixes are added by the kernel that scales, and
+// *d_total = sum_i t_i = p(z)
+int open_divide(zkt_ctx* c, const void* t, size_t len, void* d_tmp, void* d_scan_tmp, void* out, const void* d_powers,
+                void* d_total = nullptr);
+// sum_k scalar[k] poly[k][i] times z^i in one pass (i < len; the tables of open_pow_tables for this len): the t of open_divide
+int open_combine(zkt_ctx* c, const LinCombArgs& a, void* out, size_t len, const void* d_powers);
 // out[r] = sum_b partials[r * nblk + b], r < rows (per-workgroup partial sums of rows evaluations)
 int poly_sum_rows(zkt_ctx* c, const void* d_partials, int nblk, int rows, void* d_out);
 // sigma.hip: compute_all_sigma_evals (permutation/mod.rs:103-177) from the wiring (device pointers, n_rows indices each) into

@@ -88,7 +88,7 @@ struct CircuitState {
     hipEvent_t ev_copy[4] = {};          // a, b, c uploaded; [3]: main stream reached the upload point
     void* pinned_pi = nullptr;      // host staging of pi_tab
     uint32_t* pi_tab = nullptr;     // device: QUOTIENT_PI_DIRECT_MAX entries of {rotation, 9 limbs}
-    void* eval_pw = nullptr;        // EVAL_MAX x 257 powers of the evaluation points (round 5)
+    void* eval_pw = nullptr;        // round 5: EVAL_MAX x 257 powers of the evaluation points, or (fused passes) the opening tables of xi and xi w
     // The table polynomial depends on the lookup table only: while consecutive proofs pass the same table its
     // evaluations, coefficients, 4n-coset and commitment are reused (one MSM and two transforms less).
     std::vector<uint64_t> cached_table;
@@ -368,6 +368,13 @@ struct Prover {
             lens[y] = n;
         }
         if ((rc = ntt_run_batch(c, S.log_n, 1, 0, nb, ins, lens, outs))) return rc;
+        if (c->fused(4)) {   // one launch for the batch: slack, trimmed lengths, blinders
+            TrimBlindSpec tb[NTT_MAX_BATCH];
+            for (int y = 0; y < nb; ++y)
+                tb[y] = TrimBlindSpec{jobs[y].poly, (const char*)S.small + (size_t)jobs[y].blinder_off * 32, S.status + 8 + jobs[y].len_slot,
+                                      jobs[y].k > 0 ? jobs[y].k : -1};
+            return poly_trim_blind(c, tb, nb, n, 8);
+        }
         for (int y = 0; y < nb; ++y) {
             void* poly = jobs[y].poly;
             if (jobs[y].k > 0) {
@@ -821,14 +828,24 @@ struct Prover {
         std::optional<ProfScope> prof_round;   // stream time of a round, first launch to last (zkt_profile_get "round3" ...)
         wait_end();
         prof_round.emplace(c, "round3");
-        if ((rc = z1_terms(c, za))) return rc;
-        if ((rc = scan_mul(c, S.sc[0], S.sc[2], n, false, S.scan_tmp))) return rc;   // PN
-        if ((rc = scan_mul(c, S.sc[1], S.sc[3], n, true, S.scan_tmp))) return rc;    // SD
-        if ((rc = z2_terms(c, za))) return rc;
-        if ((rc = scan_mul(c, S.sc[0], pn2, n, false, S.scan_tmp))) return rc;
-        if ((rc = scan_mul(c, S.sc[1], sd2, n, true, S.scan_tmp))) return rc;
-        ZKT_HIP(c, hipMemcpyAsync(pin, S.sc[3], 32, hipMemcpyDeviceToHost, c->stream));
-        ZKT_HIP(c, hipMemcpyAsync(pin + 1, sd2, 32, hipMemcpyDeviceToHost, c->stream));
+        // Fused (zkt_ctx_set_fused_passes): the terms are never stored, so num / den hold the scans' block totals and prefixes
+        const bool fused3 = c->fused(2) && grand_product_tmp_elems(n) <= n + 8;
+        if (fused3) {
+            const void *tot1, *tot2;
+            if ((rc = grand_product_scan(c, za, 1, S.sc[2], S.sc[3], S.sc[0], &tot1))) return rc;
+            if ((rc = grand_product_scan(c, za, 2, pn2, sd2, S.sc[1], &tot2))) return rc;
+            ZKT_HIP(c, hipMemcpyAsync(pin, tot1, 32, hipMemcpyDeviceToHost, c->stream));
+            ZKT_HIP(c, hipMemcpyAsync(pin + 1, tot2, 32, hipMemcpyDeviceToHost, c->stream));
+        } else {
+            if ((rc = z1_terms(c, za))) return rc;
+            if ((rc = scan_mul(c, S.sc[0], S.sc[2], n, false, S.scan_tmp))) return rc;   // PN
+            if ((rc = scan_mul(c, S.sc[1], S.sc[3], n, true, S.scan_tmp))) return rc;    // SD
+            if ((rc = z2_terms(c, za))) return rc;
+            if ((rc = scan_mul(c, S.sc[0], pn2, n, false, S.scan_tmp))) return rc;
+            if ((rc = scan_mul(c, S.sc[1], sd2, n, true, S.scan_tmp))) return rc;
+            ZKT_HIP(c, hipMemcpyAsync(pin, S.sc[3], 32, hipMemcpyDeviceToHost, c->stream));
+            ZKT_HIP(c, hipMemcpyAsync(pin + 1, sd2, 32, hipMemcpyDeviceToHost, c->stream));
+        }
         mark("enqueue grand products");
         if ((rc = check_status())) return rc;   // synchronises; reports a lookup outside the table (round 2)
         mark("wait grand products");
@@ -839,8 +856,13 @@ struct Prover {
             const F inv12 = fe_inv_host<R>(fe_mul<R>(d1, d2));
             const F inv1 = fe_mul<R>(inv12, d2), inv2 = fe_mul<R>(inv12, d1);
             wait_end();
-            if ((rc = z_combine(c, S.sc[2], S.sc[3], inv1.v, S.ev[7], n))) return rc;
-            if ((rc = z_combine(c, pn2, sd2, inv2.v, S.sc[0], n))) return rc;              // num / den are free again
+            if (fused3) {
+                if ((rc = grand_product_combine(c, S.sc[2], S.sc[3], S.sc[0], inv1.v, S.ev[7], n))) return rc;
+                if ((rc = grand_product_combine(c, pn2, sd2, S.sc[1], inv2.v, S.sc[0], n))) return rc;
+            } else {
+                if ((rc = z_combine(c, S.sc[2], S.sc[3], inv1.v, S.ev[7], n))) return rc;
+                if ((rc = z_combine(c, pn2, sd2, inv2.v, S.sc[0], n))) return rc;              // num / den are free again
+            }
             const PolyJob jobs[2] = {{S.ev[7], S.poly[6], 11, 3, 6}, {S.sc[0], S.poly[7], 14, 3, 7}};   // z1, z2: 3 blinders each
             if ((rc = evals_to_blinded_polys(jobs, 2))) return rc;
         }
@@ -989,7 +1011,8 @@ struct Prover {
                 return rc;
             }
             if (!classes && (rc = ntt_run(c, log_n + 2, 1, 1, S.qev, 4 * n, S.qev))) return rc;         // quotient_poly.rs:226
-            if ((rc = quotient_split_blind(c, S.qev, n, (const char*)S.small + 17 * 32, S.poly[9], S.poly[10], S.poly[11], S.status)))
+            if ((rc = quotient_split_blind(c, S.qev, n, (const char*)S.small + 17 * 32, S.poly[9], S.poly[10], S.poly[11], S.status,
+                                           c->fused(4))))
                 return rc;
             // an unsatisfied circuit shows up as status bits here; they are read with the evaluations of round 5
         }
@@ -1042,7 +1065,20 @@ struct Prover {
         }
         void* d_partials = (char*)S.small + 64 * 32;
         void* d_results = (char*)S.small + 32 * 32;
-        if ((rc = poly_eval_many(c, ea, d_partials, d_results, S.eval_pw))) return rc;
+        // Fused (zkt_ctx_set_fused_passes): the powers of xi and xi w the evaluations need are those of the openings' tables,
+        // so both tables (and those of the inverses) are built here in one launch and stay in eval_pw for the openings
+        const bool fused5 = c->fused(1);
+        void* const pw_xi = S.eval_pw;
+        void* const pw_shifted = (char*)S.eval_pw + open_witness_powers(cap) * 32;
+        if (fused5) {
+            const F xi_inv = fe_is_zero<R>(xi) ? xi : fe_inv_host<R>(xi);
+            const F shifted_inv = fe_mul<R>(xi_inv, fe_inv_host<R>(w));
+            for (int k = 0; k < 12; ++k) ea.table[k] = sh[k] ? 1 : 0;
+            if ((rc = poly_eval_open_tables(c, ea, xi.v, xi_inv.v, shifted.v, shifted_inv.v, cap, d_partials, d_results, S.eval_pw)))
+                return rc;
+        } else if ((rc = poly_eval_many(c, ea, d_partials, d_results, S.eval_pw))) {
+            return rc;
+        }
         ZKT_HIP(c, hipMemcpyAsync(pin, d_results, 12 * 32, hipMemcpyDeviceToHost, c->stream));
         mark("enqueue evaluations");
         if ((rc = check_status())) return rc;   // synchronises the stream
@@ -1114,10 +1150,28 @@ struct Prover {
         // or the transcript, so it is not computed.
         // aw opening (prove.rs:381-420): sum_k eta^k p_k over (r, a, b, c, sigma1, sigma2, q_lookup, t, h2)
         // = eta^0 * r + ... : fold r's 13 terms and the 8 others into two passes
+        // Fused (zkt_ctx_set_fused_passes): r is never formed.  An opening is one pass over its polynomials (for the first, r's
+        // 13 and the 8 others) that also scales by z^i (`pw`: the point's tables, made with the evaluations), then the suffix
+        // scan, whose block prefixes the last scaling adds itself; the scan's total is the combination's value at z, from
+        // which the host takes r(xi) with the evaluations it holds.
+        void* d_f1 = (char*)d_results + 15 * 32;   // the totals of the two openings: free slots of the evaluations' results
+        void* d_f2 = (char*)d_results + 14 * 32;
+        auto opening = [&](const LinCombArgs& L, const F& z, void* comb, void* ta, void* tb, void* scan, void* out, void* pw,
+                           void* d_total) -> int {
+            int r;
+            if (fe_is_zero<R>(z)) {   // the witness is the combination shifted down by one, its value the constant coefficient
+                if ((r = poly_lincomb(c, L, comb, cap))) return r;
+                ZKT_HIP(c, hipMemcpyAsync(out, (const char*)comb + 32, (cap - 1) * 32, hipMemcpyDeviceToDevice, c->stream));
+                ZKT_HIP(c, hipMemcpyAsync(d_total, comb, 32, hipMemcpyDeviceToDevice, c->stream));
+                return ZKT_OK;
+            }
+            if ((r = open_combine(c, L, ta, cap, pw))) return r;
+            return open_divide(c, ta, cap, tb, scan, out, pw, d_total);
+        };
         void* work = S.poly[12];
         wait_end();
-        if ((rc = poly_lincomb(c, lr, work, cap))) return rc;
-        if (classes) {
+        if (!fused5 && (rc = poly_lincomb(c, lr, work, cap))) return rc;
+        if (classes && !fused5) {
             // An unsatisfied circuit leaves no trace in the quotient's coefficients on this route (there are no
             // evaluations on a fourth class for it to spill into).  The verifier's identity at xi takes over: r(xi), one more
             // evaluation that comes back with the round's last collect, against the constant the verifier derives.
@@ -1145,7 +1199,8 @@ struct Prover {
         {
             LinCombArgs lo{};
             F pw = one;
-            term(lo, work, cap, pw);
+            if (fused5) lo = lr;
+            else term(lo, work, cap, pw);
             const void* ps[8] = {S.poly[0], S.poly[1], S.poly[2], S.pk[PK_S1], S.pk[PK_S2], S.pk[PK_QLOOKUP], S.poly[3], S.poly[5]};
             const size_t pl[8] = {cap, cap, cap, S.pk_len[PK_S1], S.pk_len[PK_S2], S.pk_len[PK_QLOOKUP], cap, cap};
             for (int k = 0; k < 8; ++k) {
@@ -1153,8 +1208,16 @@ struct Prover {
                 term(lo, ps[k], pl[k], pw);
             }
             void* comb = S.sc[0];  // n + 8 fits: sc buffers hold n + 8 elements
-            if ((rc = poly_lincomb(c, lo, comb, cap))) return rc;
-            if ((rc = witness(comb, xi, S.sc[1], S.sc[2], S.scan_tmp, S.sc[3], S.eval_pw))) return rc;
+            if (fused5) {
+                if ((rc = opening(lo, xi, comb, S.sc[1], S.sc[2], S.scan_tmp, S.sc[3], pw_xi, d_f1))) return rc;
+                if (classes) {   // (r + sum_k eta^k p_k)(xi) comes back with the round's last collect
+                    ZKT_HIP(c, hipMemcpyAsync(pin + 16, d_f1, 32, hipMemcpyDeviceToHost, c->stream));
+                    ZKT_HIP(c, hipEventRecord(S.ev_win, c->stream));
+                }
+            } else {
+                if ((rc = poly_lincomb(c, lo, comb, cap))) return rc;
+                if ((rc = witness(comb, xi, S.sc[1], S.sc[2], S.scan_tmp, S.sc[3], S.eval_pw))) return rc;
+            }
         }
         // saw opening (prove.rs:427-451): (z1, z2, t, h1) at xi * omega.  Its linear combination and division depend on
         // nothing the first opening computes: on a single GPU they run on a second stream beside the first opening's
@@ -1174,6 +1237,7 @@ struct Prover {
                 pw = fe_mul<R>(pw, eta);
             }
             int r2;
+            if (fused5) return opening(lo, shifted, comb2, ta2, tb2, aux ? S.aux_scan_tmp : S.scan_tmp, out2, pw_shifted, d_f2);
             if ((r2 = poly_lincomb(c, lo, comb2, cap))) return r2;
             return witness(comb2, shifted, ta2, tb2, aux ? S.aux_scan_tmp : S.scan_tmp, out2, aux ? S.aux_pw : S.eval_pw);
         };
@@ -1257,7 +1321,16 @@ struct Prover {
             p4 = fe_mul<R>(p4, fe_add<R>(fe_add<R>(eopd, e_h2), fe_mul<R>(delta, e_h1n)));
             r0 = fe_add<R>(fe_add<R>(r0, p2), fe_add<R>(fe_mul<R>(l1, a2), fe_add<R>(p4, fe_mul<R>(l1, a4))));
             ZKT_HIP(c, hipEventSynchronize(S.ev_win));
-            if (!fe_eq<R>(pin[16], r0))
+            F r_xi = pin[16];
+            if (fused5) {   // the first opening's combination at xi, less eta^k times a b c sigma1 sigma2 q_lookup t h2 at xi
+                static const int at_xi[8] = {0, 1, 2, 3, 4, 6, 7, 11};
+                F pw = one;
+                for (int k = 0; k < 8; ++k) {
+                    pw = fe_mul<R>(pw, eta);
+                    r_xi = fe_sub<R>(r_xi, fe_mul<R>(pw, ev[at_xi[k]]));
+                }
+            }
+            if (!fe_eq<R>(r_xi, r0))
                 return set_err(c, ZKT_ERR_QUOTIENT_TOO_SHORT, "the opening identity fails at xi: the circuit is not satisfied");
         }
 
@@ -1375,7 +1448,7 @@ static int circuit_alloc_work(zkt_ctx* c, CircuitState& S) {
     for (auto& e : S.ev_copy) ZKT_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     ZKT_HIP(c, hipHostMalloc(&S.pinned_pi, QUOTIENT_PI_DIRECT_MAX * 40));
     if ((rc = dev_alloc(c, (void**)&S.pi_tab, QUOTIENT_PI_DIRECT_MAX * 40))) return rc;
-    if ((rc = alloc(&S.eval_pw, std::max((size_t)EVAL_MAX * (257 + eval_blocks), open_witness_powers(n + 8))))) return rc;
+    if ((rc = alloc(&S.eval_pw, std::max((size_t)EVAL_MAX * (257 + eval_blocks), 2 * open_witness_powers(n + 8))))) return rc;
     if (S.G == 1) {
         if ((rc = alloc(&S.aux_scan_tmp, 2 * ((n + 8) / 1024 + 4096)))) return rc;
         if ((rc = alloc(&S.aux_pw, open_witness_powers(n + 8)))) return rc;
@@ -1623,22 +1696,36 @@ static int debug_grand_products_t(zkt_ctx* c, const uint64_t* ch, const uint64_t
     void* sd2 = (char*)S.wcos[W_Z1] + n * 32;
     F* pin = (F*)S.pinned;
     int rc;
-    if ((rc = z1_terms(c, za))) return rc;
-    if ((rc = scan_mul(c, S.sc[0], S.sc[2], n, false, S.scan_tmp))) return rc;
-    if ((rc = scan_mul(c, S.sc[1], S.sc[3], n, true, S.scan_tmp))) return rc;
-    if ((rc = z2_terms(c, za))) return rc;
-    if ((rc = scan_mul(c, S.sc[0], pn2, n, false, S.scan_tmp))) return rc;
-    if ((rc = scan_mul(c, S.sc[1], sd2, n, true, S.scan_tmp))) return rc;
-    ZKT_HIP(c, hipMemcpyAsync(pin, S.sc[3], 32, hipMemcpyDeviceToHost, c->stream));
-    ZKT_HIP(c, hipMemcpyAsync(pin + 1, sd2, 32, hipMemcpyDeviceToHost, c->stream));
+    const bool fused3 = c->fused(2) && grand_product_tmp_elems(n) <= n + 8;   // as round 3 decides
+    if (fused3) {
+        const void *tot1, *tot2;
+        if ((rc = grand_product_scan(c, za, 1, S.sc[2], S.sc[3], S.sc[0], &tot1))) return rc;
+        if ((rc = grand_product_scan(c, za, 2, pn2, sd2, S.sc[1], &tot2))) return rc;
+        ZKT_HIP(c, hipMemcpyAsync(pin, tot1, 32, hipMemcpyDeviceToHost, c->stream));
+        ZKT_HIP(c, hipMemcpyAsync(pin + 1, tot2, 32, hipMemcpyDeviceToHost, c->stream));
+    } else {
+        if ((rc = z1_terms(c, za))) return rc;
+        if ((rc = scan_mul(c, S.sc[0], S.sc[2], n, false, S.scan_tmp))) return rc;
+        if ((rc = scan_mul(c, S.sc[1], S.sc[3], n, true, S.scan_tmp))) return rc;
+        if ((rc = z2_terms(c, za))) return rc;
+        if ((rc = scan_mul(c, S.sc[0], pn2, n, false, S.scan_tmp))) return rc;
+        if ((rc = scan_mul(c, S.sc[1], sd2, n, true, S.scan_tmp))) return rc;
+        ZKT_HIP(c, hipMemcpyAsync(pin, S.sc[3], 32, hipMemcpyDeviceToHost, c->stream));
+        ZKT_HIP(c, hipMemcpyAsync(pin + 1, sd2, 32, hipMemcpyDeviceToHost, c->stream));
+    }
     ZKT_HIP(c, hipStreamSynchronize(c->stream));
     if (fe_is_zero<R>(pin[0])) return set_err(c, ZKT_ERR_ZERO_DENOMINATOR, "zero denominator in the permutation grand product");
     if (fe_is_zero<R>(pin[1])) return set_err(c, ZKT_ERR_ZERO_DENOMINATOR, "zero denominator in the lookup grand product");
     const F d1 = pin[0], d2 = pin[1];
     const F inv12 = fe_inv_host<R>(fe_mul<R>(d1, d2));
     const F inv1 = fe_mul<R>(inv12, d2), inv2 = fe_mul<R>(inv12, d1);
-    if ((rc = z_combine(c, S.sc[2], S.sc[3], inv1.v, S.ev[7], n))) return rc;
-    if ((rc = z_combine(c, pn2, sd2, inv2.v, S.sc[0], n))) return rc;
+    if (fused3) {
+        if ((rc = grand_product_combine(c, S.sc[2], S.sc[3], S.sc[0], inv1.v, S.ev[7], n))) return rc;
+        if ((rc = grand_product_combine(c, pn2, sd2, S.sc[1], inv2.v, S.sc[0], n))) return rc;
+    } else {
+        if ((rc = z_combine(c, S.sc[2], S.sc[3], inv1.v, S.ev[7], n))) return rc;
+        if ((rc = z_combine(c, pn2, sd2, inv2.v, S.sc[0], n))) return rc;
+    }
     ZKT_HIP(c, hipMemcpyAsync(out_z1, S.ev[7], n * 32, hipMemcpyDeviceToHost, c->stream));
     ZKT_HIP(c, hipMemcpyAsync(out_z2, S.sc[0], n * 32, hipMemcpyDeviceToHost, c->stream));
     ZKT_HIP(c, hipStreamSynchronize(c->stream));
@@ -1901,6 +1988,13 @@ int zkt_ctx_set_quotient_route(zkt_ctx* c, int mode) {
     return ZKT_OK;
 }
 
+int zkt_ctx_set_fused_passes(zkt_ctx* c, int mode) {
+    if (!c) return ZKT_ERR_INVALID_ARGUMENT;
+    if (mode < 0 || mode > 2) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "mode: 0 automatic, 1 fused, 2 one launch per step");
+    c->fused_passes = mode;   // read by every round as it is enqueued; early work of an announced proof stays valid (same values)
+    return ZKT_OK;
+}
+
 int zkt_debug_quotient_top(zkt_ctx* c, uint64_t* out_u, int* out_on_classes) {
     if (!c || !out_u) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
     if (!c->circuit) return set_err(c, ZKT_ERR_NOT_LOADED, "no circuit loaded (zkt_circuit_load)");
@@ -1989,8 +2083,13 @@ int zkt_commit_evals_dev(zkt_ctx* c, const void* d_evals, const uint64_t* blinde
     if (k) ZKT_HIP(c, hipMemcpyAsync(d_bl, blinders, (size_t)k * 32, hipMemcpyHostToDevice, c->stream));
     // poly_from_evals + add_blinders_to_poly (util.rs:63-86, prove.rs:472-483)
     if ((rc = ntt_run(c, S.log_n, 1, 0, d_evals, n, poly))) return rc;
-    if ((rc = poly_trim_len(c, poly, n, d_len, (char*)poly + n * 32, 8))) return rc;
-    if (k && (rc = poly_add_blinders(c, poly, d_len, d_bl, k, n + 8))) return rc;
+    if (c->fused(4)) {
+        const TrimBlindSpec tb{poly, d_bl, d_len, k};
+        if ((rc = poly_trim_blind(c, &tb, 1, n, 8))) return rc;
+    } else {
+        if ((rc = poly_trim_len(c, poly, n, d_len, (char*)poly + n * 32, 8))) return rc;
+        if (k && (rc = poly_add_blinders(c, poly, d_len, d_bl, k, n + 8))) return rc;
+    }
     if (path == 0) return msm_g1_dev(c, poly, n + (size_t)k, 0, 1, out_xy, out_is_infinity);
     if ((rc = lagrange_scalars(c, d_evals, n, d_len, d_bl, k, S.roots, S.lag_scalars))) return rc;
     if ((rc = msm_begin(c, S.lag_scalars, n + (size_t)k, 0, 1, 0, 1))) return rc;
