@@ -110,4 +110,13 @@ inline Fe<P> fe_inv_host(const Fe<P>& a) {
     return fe_mul<P>(fe_mul<P>(t, r2), r2);
 }
 
+// a domain size (or any 64-bit count) as a field element
+template <class P>
+inline Fe<P> fe_from_u64(uint64_t x) {
+    Fe<P> a = fe_zero<P>();
+    a.v[0] = (uint32_t)x;
+    a.v[1] = (uint32_t)(x >> 32);
+    return fe_to_mont<P>(a);
+}
+
 }  // namespace zkt

@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include "ec.hpp"
 #include "keyfile.hpp"
+#include "linearisation.hpp"
 #include "msm.hpp"
 #include "poly.hpp"
 #include "quotient_classes.hpp"
@@ -136,7 +137,6 @@ struct HostF {
         memcpy(c.v, in, 32);
         return fe_to_mont<P>(c);
     }
-    static F pow_u64(F a, uint64_t e) { return fe_pow_u64<P>(a, e); }
 };
 
 template <class Q>
@@ -169,6 +169,38 @@ static void serialize_point(const Affine<Q>& p, std::vector<uint8_t>& out) {
     out.insert(out.end(), b.begin(), b.end());
 }
 
+// Public inputs the quotient kernel evaluates itself (poly.hpp): rows of {rotation, nine 29-bit limbs of the value}; the
+// rotation 4 pos / G is in entries of a class of a coset split G ways (1: the whole coset)
+template <class R>
+static void pi_rows(const uint64_t* pi_pos, const uint64_t* pi_vals, size_t n_pi, size_t G, uint32_t* tab) {
+    for (size_t i = 0; i < n_pi; ++i) {
+        tab[10 * i] = (uint32_t)(4 * pi_pos[i] / G);
+        const Fx<R> v = fx_unpack<R>(HostF<R>::from_words(pi_vals + 4 * i));
+        for (int w = 0; w < 9; ++w) tab[10 * i + 1 + w] = v.l[w];
+    }
+}
+
+// The quotient kernel's arguments (quotient_poly.rs:52-224).  _vectors: the twelve coset tables and the nine witness cosets,
+// each `off` bytes into its vector (the classes route's [3][n] arrays); quotient_args: the whole-coset keys, the witness,
+// the challenges (8 Montgomery words each) and zh_inv.  Output, size and public inputs are the caller's.
+static void quotient_vectors(QuotientArgs& q, void* const cs[CS_COUNT], void* const w[W_COUNT], size_t off) {
+    auto at = [&](void* const* v, int k) { return (const void*)((const char*)v[k] + off); };
+    q.q_m = at(cs, CS_QM); q.q_l = at(cs, CS_QL); q.q_r = at(cs, CS_QR); q.q_o = at(cs, CS_QO); q.q_c = at(cs, CS_QC);
+    q.q_lookup = at(cs, CS_QLOOKUP); q.q_table = at(cs, CS_QTABLE); q.x = at(cs, CS_X); q.l1 = at(cs, CS_L1);
+    q.sigma1 = at(cs, CS_S1); q.sigma2 = at(cs, CS_S2); q.sigma3 = at(cs, CS_S3);
+    q.a = at(w, W_A); q.b = at(w, W_B); q.c = at(w, W_C); q.pi = at(w, W_PI);
+    q.z1 = at(w, W_Z1); q.z2 = at(w, W_Z2); q.t = at(w, W_T); q.h1 = at(w, W_H1); q.h2 = at(w, W_H2);
+}
+static QuotientArgs quotient_args(const CircuitState& S, void* const w[W_COUNT], const void* alpha, const void* beta,
+                                  const void* gamma, const void* delta, const void* epsilon) {
+    QuotientArgs q{};
+    quotient_vectors(q, S.coset, w, 0);
+    memcpy(q.alpha, alpha, 32); memcpy(q.beta, beta, 32); memcpy(q.gamma, gamma, 32);
+    memcpy(q.delta, delta, 32); memcpy(q.epsilon, epsilon, 32);
+    memcpy(q.zh_inv, S.zh_inv, sizeof(q.zh_inv));
+    return q;
+}
+
 constexpr int WIRE_ELIM_MIN_LOG_N = 17;   // zkt_ctx_set_wire_elimination mode 1: circuits from this size on
 // zkt_ctx_set_quotient_route mode 0: the quotient on three classes from this size on (docs/EXPERIMENTS.md "Quotient on three
 // classes": it gains at 2^20 and loses at 2^18, where its extra launches cost more than the arithmetic it saves; 2^19 is not measured)
@@ -184,7 +216,10 @@ struct Prover {
     zkt_ctx* c;
     CircuitState& S;
     HostTranscript& tr;
-    Prover(zkt_ctx* ctx, CircuitState& st, HostTranscript& t) : c(ctx), S(st), tr(t) {
+    const size_t cap;   // elements of a polynomial's buffer
+    void *const d_partials, *const d_results;   // round 5's small device results; the openings' totals go behind the evaluations
+    Prover(zkt_ctx* ctx, CircuitState& st, HostTranscript& t)
+        : c(ctx), S(st), tr(t), cap(st.n + 8), d_partials((char*)st.small + 64 * 32), d_results((char*)st.small + 32 * 32) {
         trace_on = exp_env("ZKT_HOST_TRACE") != nullptr;
     }
     bool copy_fenced = false;   // the copy stream already waits for the main stream's earlier work (run(), cold path)
@@ -495,11 +530,11 @@ struct Prover {
                a.n_pi == b.n_pi && a.blinders == b.blinders && a.wires_on_device == b.wires_on_device &&
                a.variables == b.variables && a.n_vars == b.n_vars && a.w_l == b.w_l && a.w_r == b.w_r && a.w_o == b.w_o;
     }
+    static constexpr int coset_src[W_COUNT] = {0, 1, 2, 8, 6, 7, 3, 4, 5};  // S.poly[] of a b c pi z1 z2 t h1 h2
     int to_coset(int k) {
         // quotient_poly.rs:52-96 needs every witness polynomial on the 4n coset.  None of those transforms depends on a
         // challenge, so each is issued right behind the commitment of its polynomial, where it hides the latency-bound
         // tail of the last MSM of the round (which runs on the side stream).
-        static const int coset_src[W_COUNT] = {0, 1, 2, 8, 6, 7, 3, 4, 5};  // a b c pi z1 z2 t h1 h2
         if (S.use_classes) return to_coset_classes(&k, 1);
         if (S.G == 1) return ntt_run(c, S.log_n + 2, 0, 1, S.poly[coset_src[k]], S.n + 8, S.wcos[k]);
         // sharded proof: only this GPU's class of the 4n coset, one m-point transform, no exchange
@@ -514,7 +549,6 @@ struct Prover {
     // n-point coset transform; the n + 8 coefficients folded modulo X^n - gamma_j differ from the first n in eight places,
     // which one small launch per batch prepares for all three classes (ntt_fold_heads).
     int to_coset_classes(const int* ks, int nb) {
-        static const int coset_src[W_COUNT] = {0, 1, 2, 8, 6, 7, 3, 4, 5};  // a b c pi z1 z2 t h1 h2
         const void* ins[NTT_MAX_BATCH];
         void* outs[NTT_MAX_BATCH];
         size_t lens[NTT_MAX_BATCH];
@@ -535,13 +569,8 @@ struct Prover {
     // several witness polynomials onto the 4n coset in one launch per pass (single GPU; a sharded proof transforms its
     // classes one by one)
     int to_coset_many(std::initializer_list<int> ks) {
-        static const int coset_src[W_COUNT] = {0, 1, 2, 8, 6, 7, 3, 4, 5};  // a b c pi z1 z2 t h1 h2
         int rc;
-        if (S.use_classes && ks.size() <= (size_t)NTT_MAX_BATCH) {
-            int kk[NTT_MAX_BATCH], nb = 0;
-            for (int k : ks) kk[nb++] = k;
-            return nb ? to_coset_classes(kk, nb) : ZKT_OK;
-        }
+        if (S.use_classes && ks.size() <= (size_t)NTT_MAX_BATCH) return ks.size() ? to_coset_classes(ks.begin(), (int)ks.size()) : ZKT_OK;
         if (S.G != 1 || ks.size() > (size_t)NTT_MAX_BATCH) {
             for (int k : ks) if ((rc = to_coset(k))) return rc;
             return ZKT_OK;
@@ -748,49 +777,45 @@ struct Prover {
         return to_coset_many({W_H1, W_H2});   // unchanged table: its coset is still resident
     }
 
-    int run(const zkt_prove_inputs& in, std::vector<uint8_t>& proof) {
-        const size_t n = S.n;
-        const int log_n = S.log_n;
+    // ---- the proof in flight: what run()'s steps hand to each other ----
+    Challenges<R> ch;
+    XiPoint<R> at;              // zh(xi), L_1(xi), the powers of alpha, epsilon (1 + delta)
+    F ev[EV_COUNT];             // the twelve evaluations
+    Affine<Q> cm[11], wit[2];   // the eleven commitments, the witnesses aw and saw of the openings
+    F w, shifted;               // the domain's generator, xi w
+    bool same_table = false, classes = false, pi_direct = false, fused3 = false, fused5 = false;
+
+    // Rounds 1 and 2: in flight already when the proof was announced (zkt_prove_set_next), issued here otherwise
+    int rounds_1_2(const zkt_prove_inputs& in) {
         int rc;
-        mark("start");
-        if ((rc = choose_route())) return rc;
-        const bool classes = S.use_classes;
-        bool same_table = false;
         if (S.prefetch_stage == 2 && S.prefetch_epoch == c->msm_epoch && same_inputs(S.prefetch_in, in)) {
-            same_table = S.prefetch_same_table;   // rounds 1 and 2 are already in flight, in the alternate work set
+            same_table = S.prefetch_same_table;   // in the alternate work set
             swap_work_sets();
             S.prefetch_stage = 0;
-        } else {
-            S.prefetch_stage = 0;
-            // nobody announced this proof: a fresh lookup table's polynomial goes first (it waits for nothing, and its
-            // commitment covers the first wire upload of a cold proof)
-            const bool table_first = !table_is_cached(in);
-            if (table_first && in.a_evals && !in.wires_on_device) {
-                // host wire vectors: the copy stream is fenced HERE, so that the uploads run beside the table's work
-                // instead of behind it
-                ZKT_HIP(c, hipEventRecord(S.ev_copy[3], c->stream));
-                ZKT_HIP(c, hipStreamWaitEvent(S.copy_stream, S.ev_copy[3], 0));
-                copy_fenced = true;
-            }
-            if (table_first && (rc = enqueue_table(in, true))) return rc;
-            if ((rc = enqueue_round_1(in))) return rc;
-            if ((rc = enqueue_round_2(in, &same_table, table_first))) return rc;
+            return ZKT_OK;
         }
+        S.prefetch_stage = 0;
+        // nobody announced this proof: a fresh lookup table's polynomial goes first (it waits for nothing, and its
+        // commitment covers the first wire upload of a cold proof)
+        const bool table_first = !table_is_cached(in);
+        if (table_first && in.a_evals && !in.wires_on_device) {
+            // host wire vectors: the copy stream is fenced HERE, so that the uploads run beside the table's work
+            ZKT_HIP(c, hipEventRecord(S.ev_copy[3], c->stream));
+            ZKT_HIP(c, hipStreamWaitEvent(S.copy_stream, S.ev_copy[3], 0));
+            copy_fenced = true;
+        }
+        if (table_first && (rc = enqueue_table(in, true))) return rc;
+        if ((rc = enqueue_round_1(in))) return rc;
+        return enqueue_round_2(in, &same_table, table_first);
+    }
 
-        // prove.rs:110 -- public inputs (BTreeMap order = ascending position)
-        {
-            std::vector<uint8_t> b(in.n_pi * 32);
-            for (size_t i = 0; i < in.n_pi; ++i) H::to_le_bytes(H::from_words(in.pi_vals + 4 * i), b.data() + 32 * i);
-            tr.append_scalars("pi", b.data(), in.n_pi, 32, false);
-        }
-        Affine<Q> cm[11];
-        mark("enqueue rounds 1+2");
-        {
-            static const int slots[6] = {0, 1, 2, 3, 4, 5};
-            const bool skip[6] = {false, false, false, same_table, false, false};
-            if ((rc = commit_collect(slots, skip, 6, cm))) return rc;
-            if ((rc = collect_wires(cm))) return rc;
-        }
+    // The six commitments of rounds 1 and 2; the table's is kept for the proofs that pass the same table
+    int collect_rounds_1_2(const zkt_prove_inputs& in) {
+        static const int slots[6] = {0, 1, 2, 3, 4, 5};
+        const bool skip[6] = {false, false, false, same_table, false, false};
+        int rc;
+        if ((rc = commit_collect(slots, skip, 6, cm))) return rc;
+        if ((rc = collect_wires(cm))) return rc;
         mark("wait commits of rounds 1+2");
         if (!same_table) {
             memcpy(S.t_commit_xy, cm[3].x.v, Q::N * 4);
@@ -802,255 +827,247 @@ struct Prover {
             memcpy(cm[3].x.v, S.t_commit_xy, Q::N * 4);
             memcpy(cm[3].y.v, S.t_commit_xy + Q::N / 2, Q::N * 4);
         }
-        static const char* L12[6] = {"a_commit", "b_commit", "c_commit", "t_commit", "h1_commit", "h2_commit"};
-        for (int k = 0; k < 6; ++k) tr_commit(L12[k], cm[k]);
-        mark("transcript rounds 1+2");
+        return ZKT_OK;
+    }
 
-        // ---- round 3 (prove.rs:190-255) ----
-        const F beta = tr_challenge("beta"), gamma = tr_challenge("gamma"), delta = tr_challenge("delta"),
-                epsilon = tr_challenge("epsilon");
-        if (fe_eq<R>(beta, gamma) || fe_eq<R>(beta, delta) || fe_eq<R>(beta, epsilon) || fe_eq<R>(gamma, delta) ||
-            fe_eq<R>(gamma, epsilon) || fe_eq<R>(delta, epsilon))
-            return set_err(c, ZKT_ERR_EQUAL_CHALLENGES, "challenges must be different (prove.rs:202-207)");
+    // ---- round 3 (prove.rs:190-255) ----
+    // Both grand products are prefix products of num/den ratios; the division is one inversion of the total
+    // denominator on the host.  The two products are independent, so both pairs of scans run before the single
+    // host round trip (the second pair borrows the still unused z1 coset buffer).
+    // _begin: the scans and the copies of the two totals; the caller synchronises; _finish: the inversion and the
+    // combines, z1 into ev[7] and z2 into sc[0].  zkt_debug_grand_products runs the same two.
+    void* pn2() const { return S.wcos[W_Z1]; }
+    void* sd2() const { return (char*)S.wcos[W_Z1] + S.n * 32; }
+    int grand_products_begin() {
+        const size_t n = S.n;
+        int rc;
         ZTermsArgs za{};
         za.a = S.ev[0]; za.b = S.ev[1]; za.c = S.ev[2];
         za.s1 = S.sigma_ev[0]; za.s2 = S.sigma_ev[1]; za.s3 = S.sigma_ev[2]; za.roots = S.roots;
         za.f = S.ev[4]; za.t = S.ev[3]; za.h1 = S.ev[5]; za.h2 = S.ev[6];
         za.num = S.sc[0]; za.den = S.sc[1]; za.n = n;
-        put(za.beta, beta); put(za.gamma, gamma); put(za.delta, delta); put(za.epsilon, epsilon);
+        put(za.beta, ch.beta); put(za.gamma, ch.gamma); put(za.delta, ch.delta); put(za.epsilon, ch.epsilon);
         F* pin = (F*)S.pinned;
-        // Both grand products are prefix products of num/den ratios; the division is one inversion of the total
-        // denominator on the host.  The two products are independent, so both pairs of scans run before the single
-        // host round trip (the second pair borrows the still unused z1 coset buffer).
-        void* pn2 = S.wcos[W_Z1];
-        void* sd2 = (char*)S.wcos[W_Z1] + n * 32;
-        mark("challenges round 3");
-        std::optional<ProfScope> prof_round;   // stream time of a round, first launch to last (zkt_profile_get "round3" ...)
-        wait_end();
-        prof_round.emplace(c, "round3");
         // Fused (zkt_ctx_set_fused_passes): the terms are never stored, so num / den hold the scans' block totals and prefixes
-        const bool fused3 = c->fused(2) && grand_product_tmp_elems(n) <= n + 8;
+        fused3 = c->fused(2) && grand_product_tmp_elems(n) <= n + 8;
+        const void *tot1 = S.sc[3], *tot2 = sd2();
         if (fused3) {
-            const void *tot1, *tot2;
             if ((rc = grand_product_scan(c, za, 1, S.sc[2], S.sc[3], S.sc[0], &tot1))) return rc;
-            if ((rc = grand_product_scan(c, za, 2, pn2, sd2, S.sc[1], &tot2))) return rc;
-            ZKT_HIP(c, hipMemcpyAsync(pin, tot1, 32, hipMemcpyDeviceToHost, c->stream));
-            ZKT_HIP(c, hipMemcpyAsync(pin + 1, tot2, 32, hipMemcpyDeviceToHost, c->stream));
+            if ((rc = grand_product_scan(c, za, 2, pn2(), sd2(), S.sc[1], &tot2))) return rc;
         } else {
             if ((rc = z1_terms(c, za))) return rc;
             if ((rc = scan_mul(c, S.sc[0], S.sc[2], n, false, S.scan_tmp))) return rc;   // PN
             if ((rc = scan_mul(c, S.sc[1], S.sc[3], n, true, S.scan_tmp))) return rc;    // SD
             if ((rc = z2_terms(c, za))) return rc;
-            if ((rc = scan_mul(c, S.sc[0], pn2, n, false, S.scan_tmp))) return rc;
-            if ((rc = scan_mul(c, S.sc[1], sd2, n, true, S.scan_tmp))) return rc;
-            ZKT_HIP(c, hipMemcpyAsync(pin, S.sc[3], 32, hipMemcpyDeviceToHost, c->stream));
-            ZKT_HIP(c, hipMemcpyAsync(pin + 1, sd2, 32, hipMemcpyDeviceToHost, c->stream));
+            if ((rc = scan_mul(c, S.sc[0], pn2(), n, false, S.scan_tmp))) return rc;
+            if ((rc = scan_mul(c, S.sc[1], sd2(), n, true, S.scan_tmp))) return rc;
         }
-        mark("enqueue grand products");
-        if ((rc = check_status())) return rc;   // synchronises; reports a lookup outside the table (round 2)
-        mark("wait grand products");
+        ZKT_HIP(c, hipMemcpyAsync(pin, tot1, 32, hipMemcpyDeviceToHost, c->stream));
+        ZKT_HIP(c, hipMemcpyAsync(pin + 1, tot2, 32, hipMemcpyDeviceToHost, c->stream));
+        return ZKT_OK;
+    }
+    int grand_products_finish() {
+        const size_t n = S.n;
+        const F* pin = (const F*)S.pinned;
+        int rc;
         if (fe_is_zero<R>(pin[0])) return set_err(c, ZKT_ERR_ZERO_DENOMINATOR, "zero denominator in the permutation grand product");
         if (fe_is_zero<R>(pin[1])) return set_err(c, ZKT_ERR_ZERO_DENOMINATOR, "zero denominator in the lookup grand product");
-        {
-            const F d1 = pin[0], d2 = pin[1];
-            const F inv12 = fe_inv_host<R>(fe_mul<R>(d1, d2));
-            const F inv1 = fe_mul<R>(inv12, d2), inv2 = fe_mul<R>(inv12, d1);
-            wait_end();
-            if (fused3) {
-                if ((rc = grand_product_combine(c, S.sc[2], S.sc[3], S.sc[0], inv1.v, S.ev[7], n))) return rc;
-                if ((rc = grand_product_combine(c, pn2, sd2, S.sc[1], inv2.v, S.sc[0], n))) return rc;
-            } else {
-                if ((rc = z_combine(c, S.sc[2], S.sc[3], inv1.v, S.ev[7], n))) return rc;
-                if ((rc = z_combine(c, pn2, sd2, inv2.v, S.sc[0], n))) return rc;              // num / den are free again
-            }
-            const PolyJob jobs[2] = {{S.ev[7], S.poly[6], 11, 3, 6}, {S.sc[0], S.poly[7], 14, 3, 7}};   // z1, z2: 3 blinders each
-            if ((rc = evals_to_blinded_polys(jobs, 2))) return rc;
+        const F inv12 = fe_inv_host<R>(fe_mul<R>(pin[0], pin[1]));
+        const F inv1 = fe_mul<R>(inv12, pin[1]), inv2 = fe_mul<R>(inv12, pin[0]);
+        wait_end();
+        if (fused3) {
+            if ((rc = grand_product_combine(c, S.sc[2], S.sc[3], S.sc[0], inv1.v, S.ev[7], n))) return rc;
+            return grand_product_combine(c, pn2(), sd2(), S.sc[1], inv2.v, S.sc[0], n);
         }
-        if (classes) {
-            // the coefficients n - 6 .. n + 7 of a b c z1 z2 t (the six top coefficients of the quotient come from them):
-            // one small launch and one copy, on the host well before this round's commitments are
-            const void* const wp[QC_WIN_POLYS] = {S.poly[0], S.poly[1], S.poly[2], S.poly[6], S.poly[7], S.poly[3]};
-            if ((rc = quotient_gather_windows(c, wp, n - 6, S.d_win))) return rc;
-            ZKT_HIP(c, hipMemcpyAsync(S.pinned_win, S.d_win, QC_WIN_POLYS * QC_WIN * 32, hipMemcpyDeviceToHost, c->stream));
-            ZKT_HIP(c, hipEventRecord(S.ev_win, c->stream));
-        }
-        {
-            void* const z1p[1] = {S.poly[6]};
-            const size_t z1l[1] = {n + 3};
-            static const int z1s[1] = {0};
-            if ((rc = commit_begin_many(z1p, z1l, z1s, 1))) return rc;
-        }
-        if ((rc = commit_evals_begin(S.sc[0], S.poly[7], 14, 3, 7, 1))) return rc;
-        if ((rc = commit_flush())) return rc;
-        if ((rc = to_coset_many({W_Z1, W_Z2}))) return rc;
-        // the public-input polynomial of round 4 (prove.rs:258-262) is challenge-free as well.  With a handful of
-        // public inputs it is never built: the quotient kernel evaluates it from rotations of l1 (poly.hpp).
+        if ((rc = z_combine(c, S.sc[2], S.sc[3], inv1.v, S.ev[7], n))) return rc;
+        return z_combine(c, pn2(), sd2(), inv2.v, S.sc[0], n);              // num / den are free again
+    }
+
+    // Classes route: the coefficients n - 6 .. n + 7 of a b c z1 z2 t (the six top coefficients of the quotient come from
+    // them): one small launch and one copy, on the host well before this round's commitments are
+    int gather_windows() {
+        const void* const wp[QC_WIN_POLYS] = {S.poly[0], S.poly[1], S.poly[2], S.poly[6], S.poly[7], S.poly[3]};
+        if (int rc = quotient_gather_windows(c, wp, S.n - 6, S.d_win)) return rc;
+        ZKT_HIP(c, hipMemcpyAsync(S.pinned_win, S.d_win, QC_WIN_POLYS * QC_WIN * 32, hipMemcpyDeviceToHost, c->stream));
+        ZKT_HIP(c, hipEventRecord(S.ev_win, c->stream));
+        return ZKT_OK;
+    }
+
+    // The public-input polynomial of round 4 (prove.rs:258-262) is challenge-free as well.  With a handful of
+    // public inputs it is never built: the quotient kernel evaluates it from rotations of l1 (poly.hpp).
+    int public_inputs(const zkt_prove_inputs& in) {
+        const size_t n = S.n;
+        int rc;
         for (size_t i = 0; i < in.n_pi; ++i)
             if (in.pi_pos[i] >= n) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "public input position out of range");
         // (with 8 GPUs a rotation by 4 pos leaves the class for odd pos: the polynomial is transformed instead)
-        const bool pi_direct = in.n_pi <= (size_t)QUOTIENT_PI_DIRECT_MAX && S.G <= 4;
+        pi_direct = in.n_pi <= (size_t)QUOTIENT_PI_DIRECT_MAX && S.G <= 4;
         if (pi_direct) {
             uint32_t* tab = (uint32_t*)S.pinned_pi;
-            for (size_t i = 0; i < in.n_pi; ++i) {
-                tab[10 * i] = (uint32_t)(4 * in.pi_pos[i] / (size_t)(classes ? 4 : S.G));   // rotation in entries of the class
-                const Fx<R> v = fx_unpack<R>(H::from_words(in.pi_vals + 4 * i));
-                for (int w = 0; w < 9; ++w) tab[10 * i + 1 + w] = v.l[w];
-            }
+            pi_rows<R>(in.pi_pos, in.pi_vals, in.n_pi, classes ? 4 : (size_t)S.G, tab);   // rotations in entries of the class
             if (in.n_pi)
                 ZKT_HIP(c, hipMemcpyAsync(S.pi_tab, tab, in.n_pi * 40, hipMemcpyHostToDevice, c->stream));
-        } else {
-            ZKT_HIP(c, hipMemsetAsync(S.ev[7], 0, n * 32, c->stream));
-            for (size_t i = 0; i < in.n_pi; ++i)
-                ZKT_HIP(c, hipMemcpyAsync((char*)S.ev[7] + in.pi_pos[i] * 32, in.pi_vals + 4 * i, 32, hipMemcpyHostToDevice, c->stream));
-            if ((rc = evals_to_blinded_poly(S.ev[7], S.poly[8], 0, 0, 8))) return rc;      // pi
-            if ((rc = to_coset(W_PI))) return rc;
+            return ZKT_OK;
         }
-        {
-            static const int slots[2] = {0, 1};
-            if ((rc = commit_collect(slots, nullptr, 2, cm + 6))) return rc;
-        }
-        prof_round.reset();
-        tr_commit("z1_commit", cm[6]);
-        tr_commit("z2_commit", cm[7]);
-        mark("round 3 finish + commits");
+        ZKT_HIP(c, hipMemsetAsync(S.ev[7], 0, n * 32, c->stream));
+        for (size_t i = 0; i < in.n_pi; ++i)
+            ZKT_HIP(c, hipMemcpyAsync((char*)S.ev[7] + in.pi_pos[i] * 32, in.pi_vals + 4 * i, 32, hipMemcpyHostToDevice, c->stream));
+        if ((rc = evals_to_blinded_poly(S.ev[7], S.poly[8], 0, 0, 8))) return rc;      // pi
+        return to_coset(W_PI);
+    }
 
-        // ---- round 4 (prove.rs:258-313) ----
-        const F alpha = tr_challenge("alpha");
-        wait_end();
-        prof_round.emplace(c, "round4");
-        {
-            S.t_coset_valid = S.t_cached;
-            QuotientArgs q{};
-            q.a = S.wcos[W_A]; q.b = S.wcos[W_B]; q.c = S.wcos[W_C]; q.pi = S.wcos[W_PI];
-            q.z1 = S.wcos[W_Z1]; q.z2 = S.wcos[W_Z2]; q.t = S.wcos[W_T]; q.h1 = S.wcos[W_H1]; q.h2 = S.wcos[W_H2];
-            q.q_m = S.coset[CS_QM]; q.q_l = S.coset[CS_QL]; q.q_r = S.coset[CS_QR]; q.q_o = S.coset[CS_QO];
-            q.q_c = S.coset[CS_QC]; q.q_lookup = S.coset[CS_QLOOKUP]; q.q_table = S.coset[CS_QTABLE];
-            q.sigma1 = S.coset[CS_S1]; q.sigma2 = S.coset[CS_S2]; q.sigma3 = S.coset[CS_S3];
-            q.x = S.coset[CS_X]; q.l1 = S.coset[CS_L1];
-            q.out = S.qev;
-            put(q.alpha, alpha); put(q.beta, beta); put(q.gamma, gamma); put(q.delta, delta); put(q.epsilon, epsilon);
-            memcpy(q.zh_inv, S.zh_inv, sizeof(q.zh_inv));
-            q.n4 = S.m;
-            q.pi_tab = pi_direct ? S.pi_tab : nullptr;
-            q.n_pi_direct = pi_direct ? (uint32_t)in.n_pi : 0;
-            if (classes) {
-                // classes 0, 1, 2 of the coset, each as a sharded proof over four GPUs computes its own (the class mode of
-                // the kernel), then back class by class: E_j = t mod (X^n - gamma_j)
-                q.G = 4;
-                q.next_off = 1;
-                q.n4 = n;
-                const void** in_ptrs[] = {&q.a, &q.b, &q.c, &q.pi, &q.z1, &q.z2, &q.t, &q.h1, &q.h2};
-                const int cs_of[12] = {CS_QM, CS_QL, CS_QR, CS_QO, CS_QC, CS_QLOOKUP, CS_QTABLE, CS_S1, CS_S2, CS_S3, CS_X, CS_L1};
-                const void** key_ptrs[12] = {&q.q_m, &q.q_l, &q.q_r, &q.q_o, &q.q_c, &q.q_lookup, &q.q_table,
-                                             &q.sigma1, &q.sigma2, &q.sigma3, &q.x, &q.l1};
-                static const int w_of[9] = {W_A, W_B, W_C, W_PI, W_Z1, W_Z2, W_T, W_H1, W_H2};
-                for (int j = 0; j < 3; ++j) {
-                    const size_t off = (size_t)j * n * 32;
-                    for (int k = 0; k < 9; ++k) *in_ptrs[k] = (const char*)S.wcos[w_of[k]] + off;
-                    for (int k = 0; k < 12; ++k) *key_ptrs[k] = (const char*)S.ccoset[cs_of[k]] + off;
-                    q.cls = (uint32_t)j;
-                    q.z1_next = q.z1; q.z2_next = q.z2; q.t_next = q.t; q.h1_next = q.h1;
-                    q.out = (char*)S.qev + off;
-                    if ((rc = quotient_pointwise(c, q))) return rc;
-                }
-                for (int j = 0; j < 3; ++j) {
-                    void* e = (char*)S.qev + (size_t)j * n * 32;
-                    if ((rc = ntt_run(c, log_n, 1, ntt_class_code(log_n + 2, j), e, n, e))) return rc;
-                }
-                // the six top coefficients, from the windows that came with round 3 (the launches above are under way)
-                ZKT_HIP(c, hipEventSynchronize(S.ev_win));
-                const uint32_t* pw = (const uint32_t*)S.pinned_win;
-                QuotientWindows W{};
-                W.a = pw; W.b = pw + QCW * 8; W.c = pw + 2 * QCW * 8; W.z1 = pw + 3 * QCW * 8; W.z2 = pw + 4 * QCW * 8;
-                W.t = pw + 5 * QCW * 8;
-                W.sigma1 = &S.key_win[0][0][0]; W.sigma2 = &S.key_win[1][0][0]; W.sigma3 = &S.key_win[2][0][0];
-                W.q_lookup = &S.key_win[3][0][0];
-                F u[6];
-                quotient_top_coefficients<R>(log_n, W, alpha, beta, delta, u);
-                for (int e = 0; e < 6; ++e) put(S.last_u[e], u[e]);
-                S.last_u_valid = true;
-                if ((rc = quotient_classes_combine(c, S.qev, n, &S.qc_vinv[0][0], &S.last_u[0][0], &S.qc_g3[0][0]))) return rc;
-            } else if (S.G > 1) {
-                // this GPU's class of the coset, written where the all-gather wants it; then the one real exchange of a
-                // sharded proof: 4n x 32 B in total, and the classes go back to natural order for the inverse transform
-                q.G = (uint32_t)S.G;
-                q.cls = (uint32_t)S.cls;
-                q.next_off = S.G <= 4 ? 4u / (uint32_t)S.G : (uint32_t)((S.cls + 4) >> 3);
-                q.z1_next = S.G == 8 ? S.wnext[0] : q.z1;
-                q.z2_next = S.G == 8 ? S.wnext[1] : q.z2;
-                q.t_next = S.G == 8 ? S.wnext[2] : q.t;
-                q.h1_next = S.G == 8 ? S.wnext[3] : q.h1;
-                const size_t pieces = ZKT_QUOTIENT_CHUNKS;
-                if (comm_async_available(c) && S.comm_stream && S.m % pieces == 0 && S.m / pieces >= 1024) {
-                    // the exchange in pieces, stream-ordered, on a stream of its own: piece j's collective travels while
-                    // piece j + 1 is computed, and the host never waits (zkt_comm_vtable::all_gather_async).  The gathered
-                    // layout is [piece][class][m / pieces]; this rank's share of a piece is written where RCCL's in-place
-                    // form wants it (recv + rank * bytes).
-                    const size_t mp = S.m / pieces;
-                    for (size_t j = 0; j < pieces; ++j) {
-                        char* recv = (char*)S.qgather + j * (size_t)S.G * mp * 32;
-                        char* mine = recv + (size_t)S.cls * mp * 32;
-                        q.first = j * mp;
-                        q.count = mp;
-                        q.out = mine - q.first * 32;     // out[i] for i in the piece lands in `mine`
-                        if ((rc = quotient_pointwise(c, q))) return rc;
-                        ZKT_HIP(c, hipEventRecord(S.ev_piece[j], c->stream));
-                        ZKT_HIP(c, hipStreamWaitEvent(S.comm_stream, S.ev_piece[j], 0));
-                        if ((rc = comm_all_gather_async(c, mine, recv, mp * 32, S.comm_stream))) return rc;
-                    }
-                    ZKT_HIP(c, hipEventRecord(S.ev_gathered, S.comm_stream));
-                    ZKT_HIP(c, hipStreamWaitEvent(c->stream, S.ev_gathered, 0));
-                    if ((rc = quotient_interleave(c, S.qgather, S.qev, 4 * n, (uint32_t)S.G, (uint32_t)pieces))) return rc;
-                } else {
-                    q.out = (char*)S.qgather + (size_t)S.cls * S.m * 32;
-                    if ((rc = quotient_pointwise(c, q))) return rc;
-                    if ((rc = comm_all_gather_dev(c, q.out, S.qgather, S.m * 32))) return rc;
-                    if ((rc = quotient_interleave(c, S.qgather, S.qev, 4 * n, (uint32_t)S.G))) return rc;
-                }
-            } else if ((rc = quotient_pointwise(c, q))) {
-                return rc;
-            }
-            if (!classes && (rc = ntt_run(c, log_n + 2, 1, 1, S.qev, 4 * n, S.qev))) return rc;         // quotient_poly.rs:226
-            if ((rc = quotient_split_blind(c, S.qev, n, (const char*)S.small + 17 * 32, S.poly[9], S.poly[10], S.poly[11], S.status,
-                                           c->fused(4))))
-                return rc;
-            // an unsatisfied circuit shows up as status bits here; they are read with the evaluations of round 5
-        }
-        {
-            void* const polys[3] = {S.poly[9], S.poly[10], S.poly[11]};
-            const size_t lens[3] = {n + 3, n + 3, n + 3};
-            static const int slots[3] = {8, 9, 10};
-            if ((rc = commit_begin_many(polys, lens, slots, 3))) return rc;
-            if ((rc = commit_flush())) return rc;
-        }
-        if (S.has_next) {   // zkt_prove_set_next: round 1 of the next proof hides the tail of the quotient commitments
-            S.has_next = false;
-            swap_work_sets();
-            const int r1 = enqueue_round_1(S.next_in);
-            swap_work_sets();
-            S.prefetch_stage = (r1 == ZKT_OK) ? 1 : 0;   // on failure the next zkt_prove redoes the work and reports
-        }
-        {
-            static const int slots[3] = {8, 9, 10};
-            if ((rc = commit_collect(slots, nullptr, 3, cm + 8))) return rc;
-        }
-        prof_round.reset();
-        tr_commit("q_lo_commit", cm[8]);
-        tr_commit("q_mid_commit", cm[9]);
-        tr_commit("q_hi_commit", cm[10]);
-        mark("round 4");
+    int round_3(const zkt_prove_inputs& in) {
+        const size_t n = S.n;
+        int rc;
+        if ((rc = grand_products_begin())) return rc;
+        mark("enqueue grand products");
+        if ((rc = check_status())) return rc;   // synchronises; reports a lookup outside the table (round 2)
+        mark("wait grand products");
+        if ((rc = grand_products_finish())) return rc;
+        const PolyJob jobs[2] = {{S.ev[7], S.poly[6], 11, 3, 6}, {S.sc[0], S.poly[7], 14, 3, 7}};   // z1, z2: 3 blinders each
+        if ((rc = evals_to_blinded_polys(jobs, 2))) return rc;
+        if (classes && (rc = gather_windows())) return rc;
+        void* const z1p[1] = {S.poly[6]};
+        const size_t z1l[1] = {n + 3};
+        static const int slots[2] = {0, 1};
+        if ((rc = commit_begin_many(z1p, z1l, slots, 1))) return rc;
+        if ((rc = commit_evals_begin(S.sc[0], S.poly[7], 14, 3, 7, 1))) return rc;
+        if ((rc = commit_flush())) return rc;
+        if ((rc = to_coset_many({W_Z1, W_Z2}))) return rc;
+        if ((rc = public_inputs(in))) return rc;
+        return commit_collect(slots, nullptr, 2, cm + 6);
+    }
 
-        // ---- round 5 (prove.rs:318-451, linearization_poly.rs:19-121) ----
-        const F xi = tr_challenge("xi");
-        wait_end();
-        prof_round.emplace(c, "round5");
-        F w;
-        {
-            Fe<R> g = root_of_unity<R>(log_n);
-            w = g;
+    // ---- round 4 (prove.rs:258-313): the quotient's 4n coefficients into qev, by one of three routes ----
+
+    // Classes 0, 1, 2 of the coset, each as a sharded proof over four GPUs computes its own (the class mode of
+    // the kernel), then back class by class: E_j = t mod (X^n - gamma_j); the top coefficients and the combine give t
+    int quotient_on_classes(QuotientArgs q) {
+        const size_t n = S.n;
+        const int log_n = S.log_n;
+        int rc;
+        q.G = 4;
+        q.next_off = 1;
+        q.n4 = n;
+        for (int j = 0; j < 3; ++j) {
+            const size_t off = (size_t)j * n * 32;
+            quotient_vectors(q, S.ccoset, S.wcos, off);
+            q.cls = (uint32_t)j;
+            q.z1_next = q.z1; q.z2_next = q.z2; q.t_next = q.t; q.h1_next = q.h1;
+            q.out = (char*)S.qev + off;
+            if ((rc = quotient_pointwise(c, q))) return rc;
         }
-        const F shifted = fe_mul<R>(xi, w);
-        const size_t cap = n + 8;
+        for (int j = 0; j < 3; ++j) {
+            void* e = (char*)S.qev + (size_t)j * n * 32;
+            if ((rc = ntt_run(c, log_n, 1, ntt_class_code(log_n + 2, j), e, n, e))) return rc;
+        }
+        // the six top coefficients, from the windows that came with round 3 (the launches above are under way)
+        ZKT_HIP(c, hipEventSynchronize(S.ev_win));
+        const uint32_t* pw = (const uint32_t*)S.pinned_win;
+        QuotientWindows W{};
+        W.a = pw; W.b = pw + QCW * 8; W.c = pw + 2 * QCW * 8; W.z1 = pw + 3 * QCW * 8; W.z2 = pw + 4 * QCW * 8;
+        W.t = pw + 5 * QCW * 8;
+        W.sigma1 = &S.key_win[0][0][0]; W.sigma2 = &S.key_win[1][0][0]; W.sigma3 = &S.key_win[2][0][0];
+        W.q_lookup = &S.key_win[3][0][0];
+        F u[6];
+        quotient_top_coefficients<R>(log_n, W, ch.alpha, ch.beta, ch.delta, u);
+        for (int e = 0; e < 6; ++e) put(S.last_u[e], u[e]);
+        S.last_u_valid = true;
+        return quotient_classes_combine(c, S.qev, n, &S.qc_vinv[0][0], &S.last_u[0][0], &S.qc_g3[0][0]);
+    }
+
+    // This GPU's class of the coset, written where the all-gather wants it; then the one real exchange of a
+    // sharded proof: 4n x 32 B in total, and the classes go back to natural order for the inverse transform
+    int quotient_sharded(QuotientArgs q) {
+        const size_t n = S.n;
+        int rc;
+        q.G = (uint32_t)S.G;
+        q.cls = (uint32_t)S.cls;
+        q.next_off = S.G <= 4 ? 4u / (uint32_t)S.G : (uint32_t)((S.cls + 4) >> 3);
+        q.z1_next = S.G == 8 ? S.wnext[0] : q.z1;
+        q.z2_next = S.G == 8 ? S.wnext[1] : q.z2;
+        q.t_next = S.G == 8 ? S.wnext[2] : q.t;
+        q.h1_next = S.G == 8 ? S.wnext[3] : q.h1;
+        const size_t pieces = ZKT_QUOTIENT_CHUNKS;
+        if (!(comm_async_available(c) && S.comm_stream && S.m % pieces == 0 && S.m / pieces >= 1024)) {
+            q.out = (char*)S.qgather + (size_t)S.cls * S.m * 32;
+            if ((rc = quotient_pointwise(c, q))) return rc;
+            if ((rc = comm_all_gather_dev(c, q.out, S.qgather, S.m * 32))) return rc;
+            return quotient_interleave(c, S.qgather, S.qev, 4 * n, (uint32_t)S.G);
+        }
+        // the exchange in pieces, stream-ordered, on a stream of its own: piece j's collective travels while
+        // piece j + 1 is computed, and the host never waits (zkt_comm_vtable::all_gather_async).  The gathered
+        // layout is [piece][class][m / pieces]; this rank's share of a piece is written where RCCL's in-place
+        // form wants it (recv + rank * bytes).
+        const size_t mp = S.m / pieces;
+        for (size_t j = 0; j < pieces; ++j) {
+            char* recv = (char*)S.qgather + j * (size_t)S.G * mp * 32;
+            char* mine = recv + (size_t)S.cls * mp * 32;
+            q.first = j * mp;
+            q.count = mp;
+            q.out = mine - q.first * 32;     // out[i] for i in the piece lands in `mine`
+            if ((rc = quotient_pointwise(c, q))) return rc;
+            ZKT_HIP(c, hipEventRecord(S.ev_piece[j], c->stream));
+            ZKT_HIP(c, hipStreamWaitEvent(S.comm_stream, S.ev_piece[j], 0));
+            if ((rc = comm_all_gather_async(c, mine, recv, mp * 32, S.comm_stream))) return rc;
+        }
+        ZKT_HIP(c, hipEventRecord(S.ev_gathered, S.comm_stream));
+        ZKT_HIP(c, hipStreamWaitEvent(c->stream, S.ev_gathered, 0));
+        return quotient_interleave(c, S.qgather, S.qev, 4 * n, (uint32_t)S.G, (uint32_t)pieces);
+    }
+
+    void issue_next_round_1() {   // zkt_prove_set_next: round 1 of the next proof hides the tail of the quotient commitments
+        if (!S.has_next) return;
+        S.has_next = false;
+        swap_work_sets();
+        const int r1 = enqueue_round_1(S.next_in);
+        swap_work_sets();
+        S.prefetch_stage = (r1 == ZKT_OK) ? 1 : 0;   // on failure the next zkt_prove redoes the work and reports
+    }
+    void issue_next_round_2() {   // ... and its round 2 keeps the GPU fed across the proof boundary
+        if (S.prefetch_stage != 1) return;
+        bool st = false;
+        swap_work_sets();
+        const int r2 = enqueue_round_2(S.next_in, &st);
+        swap_work_sets();
+        S.prefetch_stage = 0;
+        if (r2 != ZKT_OK) return;
+        S.prefetch_stage = 2;
+        S.prefetch_in = S.next_in;
+        S.prefetch_same_table = st;
+        S.prefetch_epoch = c->msm_epoch;   // any other MSM before the next proof invalidates it
+    }
+
+    int round_4(const zkt_prove_inputs& in) {
+        const size_t n = S.n;
+        int rc;
+        S.t_coset_valid = S.t_cached;
+        QuotientArgs q = quotient_args(S, S.wcos, ch.alpha.v, ch.beta.v, ch.gamma.v, ch.delta.v, ch.epsilon.v);
+        q.out = S.qev;
+        q.n4 = S.m;
+        q.pi_tab = pi_direct ? S.pi_tab : nullptr;
+        q.n_pi_direct = pi_direct ? (uint32_t)in.n_pi : 0;
+        if ((rc = classes ? quotient_on_classes(q) : S.G > 1 ? quotient_sharded(q) : quotient_pointwise(c, q))) return rc;
+        if (!classes && (rc = ntt_run(c, S.log_n + 2, 1, 1, S.qev, 4 * n, S.qev))) return rc;         // quotient_poly.rs:226
+        // an unsatisfied circuit shows up as status bits here; they are read with the evaluations of round 5
+        if ((rc = quotient_split_blind(c, S.qev, n, (const char*)S.small + 17 * 32, S.poly[9], S.poly[10], S.poly[11], S.status,
+                                       c->fused(4))))
+            return rc;
+        void* const polys[3] = {S.poly[9], S.poly[10], S.poly[11]};
+        const size_t lens[3] = {n + 3, n + 3, n + 3};
+        static const int slots[3] = {8, 9, 10};
+        if ((rc = commit_begin_many(polys, lens, slots, 3))) return rc;
+        if ((rc = commit_flush())) return rc;
+        issue_next_round_1();
+        return commit_collect(slots, nullptr, 3, cm + 8);
+    }
+
+    // ---- round 5 (prove.rs:318-451, linearization_poly.rs:19-121) ----
+    // The twelve evaluations at xi and xi w, on the host when this returns
+    int evaluations() {
+        int rc;
+        w = root_of_unity<R>(S.log_n);
+        shifted = fe_mul<R>(ch.xi, w);
         EvalArgs ea{};
         // order of ProofEvaluations: a b c | sigma1 sigma2 z1_next | q_lookup t t_next z2_next h1_next h2
         const void* ep[12] = {S.poly[0], S.poly[1], S.poly[2], S.pk[PK_S1], S.pk[PK_S2], S.poly[6],
@@ -1061,296 +1078,294 @@ struct Prover {
         for (int k = 0; k < 12; ++k) {
             ea.poly[k] = ep[k];
             ea.len[k] = el[k];
-            put(ea.point[k], sh[k] ? shifted : xi);
+            put(ea.point[k], sh[k] ? shifted : ch.xi);
         }
-        void* d_partials = (char*)S.small + 64 * 32;
-        void* d_results = (char*)S.small + 32 * 32;
         // Fused (zkt_ctx_set_fused_passes): the powers of xi and xi w the evaluations need are those of the openings' tables,
         // so both tables (and those of the inverses) are built here in one launch and stay in eval_pw for the openings
-        const bool fused5 = c->fused(1);
-        void* const pw_xi = S.eval_pw;
-        void* const pw_shifted = (char*)S.eval_pw + open_witness_powers(cap) * 32;
+        fused5 = c->fused(1);
         if (fused5) {
-            const F xi_inv = fe_is_zero<R>(xi) ? xi : fe_inv_host<R>(xi);
+            const F xi_inv = fe_is_zero<R>(ch.xi) ? ch.xi : fe_inv_host<R>(ch.xi);
             const F shifted_inv = fe_mul<R>(xi_inv, fe_inv_host<R>(w));
             for (int k = 0; k < 12; ++k) ea.table[k] = sh[k] ? 1 : 0;
-            if ((rc = poly_eval_open_tables(c, ea, xi.v, xi_inv.v, shifted.v, shifted_inv.v, cap, d_partials, d_results, S.eval_pw)))
+            if ((rc = poly_eval_open_tables(c, ea, ch.xi.v, xi_inv.v, shifted.v, shifted_inv.v, cap, d_partials, d_results, S.eval_pw)))
                 return rc;
         } else if ((rc = poly_eval_many(c, ea, d_partials, d_results, S.eval_pw))) {
             return rc;
         }
-        ZKT_HIP(c, hipMemcpyAsync(pin, d_results, 12 * 32, hipMemcpyDeviceToHost, c->stream));
+        const F* pin = (const F*)S.pinned;
+        ZKT_HIP(c, hipMemcpyAsync(S.pinned, d_results, 12 * 32, hipMemcpyDeviceToHost, c->stream));
         mark("enqueue evaluations");
         if ((rc = check_status())) return rc;   // synchronises the stream
         mark("wait evaluations");
-        F ev[12];
         for (int k = 0; k < 12; ++k) ev[k] = pin[k];
-        const F &e_a = ev[0], &e_b = ev[1], &e_c = ev[2], &e_s1 = ev[3], &e_s2 = ev[4], &e_z1n = ev[5], &e_ql = ev[6],
-                &e_t = ev[7], &e_tn = ev[8], &e_z2n = ev[9], &e_h1n = ev[10], &e_h2 = ev[11];
-        const F one = fe_one<R>();
-        // zh(xi) = xi^n - 1 ; L_1(xi) = zh * 1 / (n * (xi - 1))   (util.rs:185-195)
-        const F xi_n = fe_pow_u64<R>(xi, (uint64_t)n);
-        const F zh = fe_sub<R>(xi_n, one);
-        F nn = fe_zero<R>();
-        nn.v[0] = (uint32_t)(n & 0xffffffffu);
-        nn.v[1] = (uint32_t)((uint64_t)n >> 32);
-        nn = fe_to_mont<R>(nn);
-        const F l1den = fe_mul<R>(nn, fe_sub<R>(xi, one));
-        if (fe_is_zero<R>(l1den)) return set_err(c, ZKT_ERR_ZERO_DENOMINATOR, "xi = 1");
-        const F l1 = fe_mul<R>(zh, fe_inv_host<R>(l1den));
-        const F a2 = fe_sqr<R>(alpha), a3 = fe_mul<R>(a2, alpha), a4 = fe_mul<R>(a3, alpha), a5 = fe_mul<R>(a4, alpha);
-        const F k1 = fe_from_u32<R>(7), k2 = fe_from_u32<R>(13);
-        const F bxi = fe_mul<R>(beta, xi);
-        // keys/permutation.rs:34-69
-        F s_z1 = fe_mul<R>(alpha, fe_add<R>(fe_add<R>(bxi, e_a), gamma));
-        s_z1 = fe_mul<R>(s_z1, fe_add<R>(fe_add<R>(fe_mul<R>(bxi, k1), e_b), gamma));
-        s_z1 = fe_mul<R>(s_z1, fe_add<R>(fe_add<R>(fe_mul<R>(bxi, k2), e_c), gamma));
-        s_z1 = fe_add<R>(s_z1, fe_mul<R>(l1, a2));
-        F s_s3 = fe_mul<R>(fe_neg<R>(alpha), beta);
-        s_s3 = fe_mul<R>(s_s3, e_z1n);
-        s_s3 = fe_mul<R>(s_s3, fe_add<R>(fe_add<R>(fe_mul<R>(beta, e_s1), e_a), gamma));
-        s_s3 = fe_mul<R>(s_s3, fe_add<R>(fe_add<R>(fe_mul<R>(beta, e_s2), e_b), gamma));
-        // keys/lookup.rs:29-65
-        const F opd = fe_add<R>(delta, one), eopd = fe_mul<R>(epsilon, opd);
-        F s_z2 = fe_mul<R>(a3, opd);
-        s_z2 = fe_mul<R>(s_z2, fe_add<R>(epsilon, fe_mul<R>(e_ql, e_c)));
-        s_z2 = fe_mul<R>(s_z2, fe_add<R>(fe_add<R>(eopd, e_t), fe_mul<R>(delta, e_tn)));
-        s_z2 = fe_add<R>(s_z2, fe_mul<R>(a4, l1));
-        F s_h1 = fe_mul<R>(fe_neg<R>(a3), e_z2n);
-        s_h1 = fe_mul<R>(s_h1, fe_add<R>(fe_add<R>(eopd, e_h2), fe_mul<R>(delta, e_h1n)));
-        const F s_qt = fe_mul<R>(a5, e_t);
-        // linearization_poly.rs:100-109: -zh * (q_lo + xi^(n+2) q_mid + xi^(2n+4) q_hi)
-        const F xn2 = fe_mul<R>(fe_mul<R>(fe_add<R>(zh, one), xi), xi);
-        const F nzh = fe_neg<R>(zh);
+        return ZKT_OK;
+    }
+
+    static void term(LinCombArgs& L, const void* p, size_t len, const F& s) {
+        L.poly[L.nterms] = p; L.len[L.nterms] = len;
+        put(L.scalar[L.nterms], s);
+        ++L.nterms;
+    }
+    // r(X): the thirteen scalars of linearisation.hpp against the prover's polynomials
+    LinCombArgs linearisation() {
+        F sc[LIN_COUNT];
+        linearisation_scalars<R>(ch, at, ev, sc);
+        const void* const p[LIN_COUNT] = {S.pk[PK_QM], S.pk[PK_QL], S.pk[PK_QR], S.pk[PK_QO], S.pk[PK_QC], S.poly[6], S.pk[PK_S3],
+                                          S.poly[7], S.poly[4], S.pk[PK_QTABLE], S.poly[9], S.poly[10], S.poly[11]};
+        const size_t l[LIN_COUNT] = {S.pk_len[PK_QM], S.pk_len[PK_QL], S.pk_len[PK_QR], S.pk_len[PK_QO], S.pk_len[PK_QC], cap,
+                                     S.pk_len[PK_S3], cap, cap, S.pk_len[PK_QTABLE], cap, cap, cap};
         LinCombArgs lr{};
-        auto term = [&](LinCombArgs& L, const void* p, size_t len, const F& s) {
-            L.poly[L.nterms] = p;
-            L.len[L.nterms] = len;
-            put(L.scalar[L.nterms], s);
-            ++L.nterms;
-        };
-        term(lr, S.pk[PK_QM], S.pk_len[PK_QM], fe_mul<R>(e_a, e_b));   // keys/arithmetic.rs:37-46
-        term(lr, S.pk[PK_QL], S.pk_len[PK_QL], e_a);
-        term(lr, S.pk[PK_QR], S.pk_len[PK_QR], e_b);
-        term(lr, S.pk[PK_QO], S.pk_len[PK_QO], e_c);
-        term(lr, S.pk[PK_QC], S.pk_len[PK_QC], one);
-        term(lr, S.poly[6], cap, s_z1);
-        term(lr, S.pk[PK_S3], S.pk_len[PK_S3], s_s3);
-        term(lr, S.poly[7], cap, s_z2);
-        term(lr, S.poly[4], cap, s_h1);
-        term(lr, S.pk[PK_QTABLE], S.pk_len[PK_QTABLE], s_qt);
-        term(lr, S.poly[9], cap, nzh);
-        term(lr, S.poly[10], cap, fe_mul<R>(nzh, xn2));
-        term(lr, S.poly[11], cap, fe_mul<R>(nzh, fe_sqr<R>(xn2)));
-        static const char* EL[12] = {"a_eval", "b_eval", "c_eval", "sigma1_eval", "sigma2_eval", "z1_next_eval",
-                                     "q_lookup_eval", "t_eval", "t_next_eval", "z2_next_eval", "h1_next_eval", "h2_eval"};
-        for (int k = 0; k < 12; ++k) tr_scalar(EL[k], ev[k]);
-        const F eta = tr_challenge("eta");
-        // r(X) lives in the work buffer; its own commitment (prove.rs:372-375) is never part of the proof
-        // or the transcript, so it is not computed.
-        // aw opening (prove.rs:381-420): sum_k eta^k p_k over (r, a, b, c, sigma1, sigma2, q_lookup, t, h2)
-        // = eta^0 * r + ... : fold r's 13 terms and the 8 others into two passes
-        // Fused (zkt_ctx_set_fused_passes): r is never formed.  An opening is one pass over its polynomials (for the first, r's
-        // 13 and the 8 others) that also scales by z^i (`pw`: the point's tables, made with the evaluations), then the suffix
-        // scan, whose block prefixes the last scaling adds itself; the scan's total is the combination's value at z, from
-        // which the host takes r(xi) with the evaluations it holds.
-        void* d_f1 = (char*)d_results + 15 * 32;   // the totals of the two openings: free slots of the evaluations' results
-        void* d_f2 = (char*)d_results + 14 * 32;
-        auto opening = [&](const LinCombArgs& L, const F& z, void* comb, void* ta, void* tb, void* scan, void* out, void* pw,
-                           void* d_total) -> int {
-            int r;
-            if (fe_is_zero<R>(z)) {   // the witness is the combination shifted down by one, its value the constant coefficient
-                if ((r = poly_lincomb(c, L, comb, cap))) return r;
-                ZKT_HIP(c, hipMemcpyAsync(out, (const char*)comb + 32, (cap - 1) * 32, hipMemcpyDeviceToDevice, c->stream));
-                ZKT_HIP(c, hipMemcpyAsync(d_total, comb, 32, hipMemcpyDeviceToDevice, c->stream));
-                return ZKT_OK;
-            }
-            if ((r = open_combine(c, L, ta, cap, pw))) return r;
-            return open_divide(c, ta, cap, tb, scan, out, pw, d_total);
-        };
-        void* work = S.poly[12];
+        for (int k = 0; k < LIN_COUNT; ++k) term(lr, p[k], l[k], sc[k]);
+        return lr;
+    }
+
+    // The witness of an opening at z is (p(X) - p(z)) / (X - z).  At z = 0 (xi = 0 makes both points zero; the reference
+    // proves there) that is p shifted down by one coefficient, and no power of 1/z is needed: one copy on the stream
+    // the opening uses.
+    int witness(const void* comb, const F& z, void* ta, void* tb, void* scan, void* out, void* pw) {
+        if (fe_is_zero<R>(z)) {
+            ZKT_HIP(c, hipMemcpyAsync(out, (const char*)comb + 32, (cap - 1) * 32, hipMemcpyDeviceToDevice, c->stream));
+            return ZKT_OK;
+        }
+        const F zi = fe_inv_host<R>(z);
+        return open_witness(c, comb, cap, z.v, zi.v, ta, tb, scan, out, pw);
+    }
+    // Fused (zkt_ctx_set_fused_passes): an opening is one pass over its polynomials (for the first, r's 13 and the 8
+    // others; r is never formed) that also scales by z^i (`pw`: the point's tables, made with the evaluations), then the
+    // suffix scan, whose block prefixes the last scaling adds itself; the scan's total is the combination's value at z.
+    int opening(const LinCombArgs& L, const F& z, void* comb, void* ta, void* tb, void* scan, void* out, void* pw, void* d_total) {
+        int rc;
+        if (fe_is_zero<R>(z)) {   // the raw combination: its witness as above, its value the constant coefficient
+            if ((rc = poly_lincomb(c, L, comb, cap))) return rc;
+            if ((rc = witness(comb, z, ta, tb, scan, out, pw))) return rc;
+            ZKT_HIP(c, hipMemcpyAsync(d_total, comb, 32, hipMemcpyDeviceToDevice, c->stream));
+            return ZKT_OK;
+        }
+        if ((rc = open_combine(c, L, ta, cap, pw))) return rc;
+        return open_divide(c, ta, cap, tb, scan, out, pw, d_total);
+    }
+
+    // Classes route, issue side of check_identity.  An unsatisfied circuit leaves no trace in the quotient's coefficients
+    // on this route (there are no evaluations on a fourth class for it to spill into).  The verifier's identity at xi
+    // takes over: one more value, r(xi) or (fused) (r + sum_k eta^k p_k)(xi), comes back with the round's last collect.
+    int identity_value(const void* d_value) {
+        ZKT_HIP(c, hipMemcpyAsync((F*)S.pinned + 16, d_value, 32, hipMemcpyDeviceToHost, c->stream));
+        ZKT_HIP(c, hipEventRecord(S.ev_win, c->stream));
+        return ZKT_OK;
+    }
+
+    // aw opening (prove.rs:381-420): sum_k eta^k p_k over (r, a, b, c, sigma1, sigma2, q_lookup, t, h2), witness into sc[3].
+    // r(X) lives in the work buffer; its own commitment (prove.rs:372-375) is never part of the proof or the transcript.
+    int first_opening() {
+        int rc;
+        const LinCombArgs lr = linearisation();
+        void *work = S.poly[12], *d_f1 = (char*)d_results + 15 * 32;
+        LinCombArgs lo{};
+        F pw = fe_one<R>();
         wait_end();
-        if (!fused5 && (rc = poly_lincomb(c, lr, work, cap))) return rc;
-        if (classes && !fused5) {
-            // An unsatisfied circuit leaves no trace in the quotient's coefficients on this route (there are no
-            // evaluations on a fourth class for it to spill into).  The verifier's identity at xi takes over: r(xi), one more
-            // evaluation that comes back with the round's last collect, against the constant the verifier derives.
-            EvalArgs er{};
-            er.count = 1;
-            er.poly[0] = work;
-            er.len[0] = cap;
-            put(er.point[0], xi);
-            if ((rc = poly_eval_many(c, er, d_partials, d_results, S.eval_pw))) return rc;
-            ZKT_HIP(c, hipMemcpyAsync(pin + 16, d_results, 32, hipMemcpyDeviceToHost, c->stream));
-            ZKT_HIP(c, hipEventRecord(S.ev_win, c->stream));
+        if (fused5) {
+            lo = lr;
+        } else {
+            if ((rc = poly_lincomb(c, lr, work, cap))) return rc;
+            if (classes) {
+                EvalArgs er{};
+                er.count = 1;
+                er.poly[0] = work;
+                er.len[0] = cap;
+                put(er.point[0], ch.xi);
+                if ((rc = poly_eval_many(c, er, d_partials, d_results, S.eval_pw))) return rc;
+                if ((rc = identity_value(d_results))) return rc;
+            }
+            term(lo, work, cap, pw);
         }
-        // The witness of an opening at z is (p(X) - p(z)) / (X - z).  At z = 0 (xi = 0 makes both points zero; the reference
-        // proves there) that is p shifted down by one coefficient, and no power of 1/z is needed: one copy on the stream
-        // the opening uses.
-        auto witness = [&](const void* comb, const F& z, void* ta, void* tb, void* scan, void* out, void* pw) -> int {
-            if (fe_is_zero<R>(z)) {
-                ZKT_HIP(c, hipMemcpyAsync(out, (const char*)comb + 32, (cap - 1) * 32, hipMemcpyDeviceToDevice, c->stream));
-                return ZKT_OK;
-            }
-            const F zi = fe_inv_host<R>(z);
-            return open_witness(c, comb, cap, z.v, zi.v, ta, tb, scan, out, pw);
-        };
-        Affine<Q> aw, saw;
-        {
-            LinCombArgs lo{};
-            F pw = one;
-            if (fused5) lo = lr;
-            else term(lo, work, cap, pw);
-            const void* ps[8] = {S.poly[0], S.poly[1], S.poly[2], S.pk[PK_S1], S.pk[PK_S2], S.pk[PK_QLOOKUP], S.poly[3], S.poly[5]};
-            const size_t pl[8] = {cap, cap, cap, S.pk_len[PK_S1], S.pk_len[PK_S2], S.pk_len[PK_QLOOKUP], cap, cap};
-            for (int k = 0; k < 8; ++k) {
-                pw = fe_mul<R>(pw, eta);
-                term(lo, ps[k], pl[k], pw);
-            }
-            void* comb = S.sc[0];  // n + 8 fits: sc buffers hold n + 8 elements
-            if (fused5) {
-                if ((rc = opening(lo, xi, comb, S.sc[1], S.sc[2], S.scan_tmp, S.sc[3], pw_xi, d_f1))) return rc;
-                if (classes) {   // (r + sum_k eta^k p_k)(xi) comes back with the round's last collect
-                    ZKT_HIP(c, hipMemcpyAsync(pin + 16, d_f1, 32, hipMemcpyDeviceToHost, c->stream));
-                    ZKT_HIP(c, hipEventRecord(S.ev_win, c->stream));
-                }
-            } else {
-                if ((rc = poly_lincomb(c, lo, comb, cap))) return rc;
-                if ((rc = witness(comb, xi, S.sc[1], S.sc[2], S.scan_tmp, S.sc[3], S.eval_pw))) return rc;
-            }
+        const void* ps[8] = {S.poly[0], S.poly[1], S.poly[2], S.pk[PK_S1], S.pk[PK_S2], S.pk[PK_QLOOKUP], S.poly[3], S.poly[5]};
+        const size_t pl[8] = {cap, cap, cap, S.pk_len[PK_S1], S.pk_len[PK_S2], S.pk_len[PK_QLOOKUP], cap, cap};
+        for (int k = 0; k < 8; ++k) {
+            pw = fe_mul<R>(pw, ch.eta);
+            term(lo, ps[k], pl[k], pw);
         }
-        // saw opening (prove.rs:427-451): (z1, z2, t, h1) at xi * omega.  Its linear combination and division depend on
-        // nothing the first opening computes: on a single GPU they run on a second stream beside the first opening's
-        // commitment (memory-bound work beside an integer-ALU-bound kernel), in the z cosets' buffers, which are dead since
-        // the quotient pass.
-        const bool aux = S.aux_stream != nullptr && !c->aux_off;
+        void* comb = S.sc[0];  // n + 8 fits: sc buffers hold n + 8 elements
+        if (fused5) {
+            if ((rc = opening(lo, ch.xi, comb, S.sc[1], S.sc[2], S.scan_tmp, S.sc[3], S.eval_pw, d_f1))) return rc;
+            return classes ? identity_value(d_f1) : ZKT_OK;
+        }
+        if ((rc = poly_lincomb(c, lo, comb, cap))) return rc;
+        return witness(comb, ch.xi, S.sc[1], S.sc[2], S.scan_tmp, S.sc[3], S.eval_pw);
+    }
+
+    // saw opening (prove.rs:427-451): (z1, z2, t, h1) at xi * omega.  Its linear combination and division depend on
+    // nothing the first opening computes: on a single GPU they run on a second stream beside the first opening's
+    // commitment (memory-bound work beside an integer-ALU-bound kernel), in the z cosets' buffers, which are dead since
+    // the quotient pass.
+    void* second_witness(bool aux) const { return aux ? S.wcos[W_Z2] : S.sc[3]; }
+    int second_opening(bool aux) {
         void* comb2 = aux ? S.wcos[W_Z1] : S.sc[0];
         void* ta2 = aux ? (void*)((char*)S.wcos[W_Z1] + cap * 32) : S.sc[1];
         void* tb2 = aux ? (void*)((char*)S.wcos[W_Z1] + 2 * cap * 32) : S.sc[2];
-        void* out2 = aux ? S.wcos[W_Z2] : S.sc[3];
-        auto second_opening = [&]() -> int {
-            LinCombArgs lo{};
-            F pw = one;
-            const void* ps[4] = {S.poly[6], S.poly[7], S.poly[3], S.poly[4]};
-            for (int k = 0; k < 4; ++k) {
-                term(lo, ps[k], cap, pw);
-                pw = fe_mul<R>(pw, eta);
-            }
-            int r2;
-            if (fused5) return opening(lo, shifted, comb2, ta2, tb2, aux ? S.aux_scan_tmp : S.scan_tmp, out2, pw_shifted, d_f2);
-            if ((r2 = poly_lincomb(c, lo, comb2, cap))) return r2;
-            return witness(comb2, shifted, ta2, tb2, aux ? S.aux_scan_tmp : S.scan_tmp, out2, aux ? S.aux_pw : S.eval_pw);
-        };
-        if (aux) {
-            ZKT_HIP(c, hipEventRecord(S.ev_aux_go, c->stream));
-            ZKT_HIP(c, hipStreamWaitEvent(S.aux_stream, S.ev_aux_go, 0));
-            hipStream_t main_stream = c->stream;
-            c->stream = S.aux_stream;           // the polynomial kernels launch on the context's stream
-            const int r2 = second_opening();
-            c->stream = main_stream;
-            if (r2) return r2;
-            ZKT_HIP(c, hipEventRecord(S.ev_aux_done, S.aux_stream));
+        void* scan = aux ? S.aux_scan_tmp : S.scan_tmp;
+        LinCombArgs lo{};
+        F pw = fe_one<R>();
+        const void* ps[4] = {S.poly[6], S.poly[7], S.poly[3], S.poly[4]};
+        for (int k = 0; k < 4; ++k) {
+            term(lo, ps[k], cap, pw);
+            pw = fe_mul<R>(pw, ch.eta);
         }
+        if (fused5) return opening(lo, shifted, comb2, ta2, tb2, scan, second_witness(aux), (char*)S.eval_pw + open_witness_powers(cap) * 32,
+                                   (char*)d_results + 14 * 32);   // xi w's tables lie behind xi's
+        if (int rc = poly_lincomb(c, lo, comb2, cap)) return rc;
+        return witness(comb2, shifted, ta2, tb2, scan, second_witness(aux), aux ? S.aux_pw : S.eval_pw);
+    }
+    int second_opening_on_aux_stream() {
+        ZKT_HIP(c, hipEventRecord(S.ev_aux_go, c->stream));
+        ZKT_HIP(c, hipStreamWaitEvent(S.aux_stream, S.ev_aux_go, 0));
+        hipStream_t main_stream = c->stream;
+        c->stream = S.aux_stream;           // the polynomial kernels launch on the context's stream
+        const int rc = second_opening(true);
+        c->stream = main_stream;
+        if (rc) return rc;
+        ZKT_HIP(c, hipEventRecord(S.ev_aux_done, S.aux_stream));
+        return ZKT_OK;
+    }
+
+    // Both openings and their commitments aw, saw; the next proof's round 2 goes behind them
+    int openings() {
+        int rc;
+        if ((rc = first_opening())) return rc;
+        const bool aux = S.aux_stream != nullptr && !c->aux_off;
+        if (aux && (rc = second_opening_on_aux_stream())) return rc;
         // (small and mid-size keys: both commitments as one batch, which the second witness' own buffers allow)
         const bool both = aux && queueing();
         if (!both && (rc = commit_begin(S.sc[3], cap - 1, 6))) return rc;  // the scalars are consumed by the first kernels
-        {
-            if (aux) ZKT_HIP(c, hipStreamWaitEvent(c->stream, S.ev_aux_done, 0));
-            else if ((rc = second_opening())) return rc;
-            if (both) {
-                void* const wp[2] = {S.sc[3], out2};
-                const size_t wl[2] = {cap - 1, cap - 1};
-                static const int ws[2] = {6, 7};
-                if ((rc = commit_begin_many(wp, wl, ws, 2))) return rc;
-            } else if ((rc = commit_begin(out2, cap - 1, 7))) {
-                return rc;
-            }
-            if ((rc = commit_flush())) return rc;
-            if (S.prefetch_stage == 1) {   // ... and its round 2 keeps the GPU fed across the proof boundary
-                bool st = false;
-                swap_work_sets();
-                const int r2 = enqueue_round_2(S.next_in, &st);
-                swap_work_sets();
-                if (r2 == ZKT_OK) {
-                    S.prefetch_stage = 2;
-                    S.prefetch_in = S.next_in;
-                    S.prefetch_same_table = st;
-                    S.prefetch_epoch = c->msm_epoch;   // any other MSM before the next proof invalidates it
-                } else {
-                    S.prefetch_stage = 0;
-                }
-            }
-            {
-                static const int slots[2] = {6, 7};
-                Affine<Q> w2[2];
-                if ((rc = commit_collect(slots, nullptr, 2, w2))) return rc;
-                aw = w2[0];
-                saw = w2[1];
-            }
+        if (aux) ZKT_HIP(c, hipStreamWaitEvent(c->stream, S.ev_aux_done, 0));
+        else if ((rc = second_opening(false))) return rc;
+        static const int slots[2] = {6, 7};
+        if (both) {
+            void* const wp[2] = {S.sc[3], second_witness(aux)};
+            const size_t wl[2] = {cap - 1, cap - 1};
+            if ((rc = commit_begin_many(wp, wl, slots, 2))) return rc;
+        } else if ((rc = commit_begin(second_witness(aux), cap - 1, 7))) {
+            return rc;
         }
-        wait_end();
-        prof_round.reset();
-        if (classes) {
-            // compute_r0 (proof.rs:163-217) with the prover's own values; L_j(xi) = zh w^j / (n (xi - w^j)), 1 or 0 on the domain
-            F r0 = fe_zero<R>();
-            std::vector<F> root(in.n_pi), den(in.n_pi), before(in.n_pi);   // before[i]: product of the non-zero den[k], k < i
-            F run_prod = one;
-            for (size_t i = 0; i < in.n_pi; ++i) {
-                root[i] = fe_pow_u64<R>(w, (uint64_t)in.pi_pos[i]);
-                den[i] = fe_mul<R>(nn, fe_sub<R>(xi, root[i]));
-                before[i] = run_prod;
-                if (!fe_is_zero<R>(den[i])) run_prod = fe_mul<R>(run_prod, den[i]);
-            }
-            F inv_all = in.n_pi ? fe_inv_host<R>(run_prod) : one;
-            for (size_t i = in.n_pi; i-- > 0;) {   // one inversion for all denominators
-                const F v = H::from_words(in.pi_vals + 4 * i);
-                if (fe_is_zero<R>(den[i])) {
-                    r0 = fe_sub<R>(r0, v);
-                    continue;
-                }
-                const F di = fe_mul<R>(inv_all, before[i]);
-                inv_all = fe_mul<R>(inv_all, den[i]);
-                r0 = fe_sub<R>(r0, fe_mul<R>(fe_mul<R>(fe_mul<R>(zh, root[i]), di), v));
-            }
-            F p2 = fe_mul<R>(alpha, e_z1n);
-            p2 = fe_mul<R>(p2, fe_add<R>(fe_add<R>(e_a, fe_mul<R>(beta, e_s1)), gamma));
-            p2 = fe_mul<R>(p2, fe_add<R>(fe_add<R>(e_b, fe_mul<R>(beta, e_s2)), gamma));
-            p2 = fe_mul<R>(p2, fe_add<R>(e_c, gamma));
-            F p4 = fe_mul<R>(a3, e_z2n);
-            p4 = fe_mul<R>(p4, fe_add<R>(eopd, fe_mul<R>(delta, e_h2)));
-            p4 = fe_mul<R>(p4, fe_add<R>(fe_add<R>(eopd, e_h2), fe_mul<R>(delta, e_h1n)));
-            r0 = fe_add<R>(fe_add<R>(r0, p2), fe_add<R>(fe_mul<R>(l1, a2), fe_add<R>(p4, fe_mul<R>(l1, a4))));
-            ZKT_HIP(c, hipEventSynchronize(S.ev_win));
-            F r_xi = pin[16];
-            if (fused5) {   // the first opening's combination at xi, less eta^k times a b c sigma1 sigma2 q_lookup t h2 at xi
-                static const int at_xi[8] = {0, 1, 2, 3, 4, 6, 7, 11};
-                F pw = one;
-                for (int k = 0; k < 8; ++k) {
-                    pw = fe_mul<R>(pw, eta);
-                    r_xi = fe_sub<R>(r_xi, fe_mul<R>(pw, ev[at_xi[k]]));
-                }
-            }
-            if (!fe_eq<R>(r_xi, r0))
-                return set_err(c, ZKT_ERR_QUOTIENT_TOO_SHORT, "the opening identity fails at xi: the circuit is not satisfied");
-        }
+        if ((rc = commit_flush())) return rc;
+        issue_next_round_2();
+        return commit_collect(slots, nullptr, 2, wit);
+    }
 
-        // ---- Proof (proof.rs:106-155), CanonicalSerialize ----
+    // Classes route, check side: r(xi) against compute_r0 (proof.rs:163-217) made from the prover's own values.  A public
+    // input's root equal to xi has L_j = 1 there and the proof goes on.
+    int check_identity(const zkt_prove_inputs& in) {
+        std::vector<F> root(in.n_pi);
+        for (size_t i = 0; i < in.n_pi; ++i) root[i] = fe_pow_u64<R>(w, (uint64_t)in.pi_pos[i]);
+        F r0;
+        (void)compute_r0<R>(ch, at, ev, root.data(), in.pi_vals, in.n_pi, &r0);
+        ZKT_HIP(c, hipEventSynchronize(S.ev_win));
+        F r_xi = ((const F*)S.pinned)[16];
+        if (fused5) {   // the first opening's combination at xi, less eta^k times a b c sigma1 sigma2 q_lookup t h2 at xi
+            static const int at_xi[8] = {EV_A, EV_B, EV_C, EV_S1, EV_S2, EV_QL, EV_T, EV_H2};
+            F pw = fe_one<R>();
+            for (int k = 0; k < 8; ++k) {
+                pw = fe_mul<R>(pw, ch.eta);
+                r_xi = fe_sub<R>(r_xi, fe_mul<R>(pw, ev[at_xi[k]]));
+            }
+        }
+        if (!fe_eq<R>(r_xi, r0))
+            return set_err(c, ZKT_ERR_QUOTIENT_TOO_SHORT, "the opening identity fails at xi: the circuit is not satisfied");
+        return ZKT_OK;
+    }
+
+    // ---- Proof (proof.rs:106-155), CanonicalSerialize ----
+    void serialize(std::vector<uint8_t>& proof) const {
         proof.clear();
         for (int k = 0; k < 11; ++k) serialize_point<Q>(cm[k], proof);
-        serialize_point<Q>(aw, proof);
+        serialize_point<Q>(wit[0], proof);
         proof.push_back(0);   // kzg10::Proof::random_v = None
-        serialize_point<Q>(saw, proof);
+        serialize_point<Q>(wit[1], proof);
         proof.push_back(0);
-        for (int k = 0; k < 12; ++k) {
+        for (int k = 0; k < EV_COUNT; ++k) {
             uint8_t b[32];
             H::to_le_bytes(ev[k], b);
             proof.insert(proof.end(), b, b + 32);
         }
+    }
+
+    // The five rounds, with the transcript's traffic between them.  prof_round: stream time of a round, first launch to
+    // last (zkt_profile_get "round3" ...)
+    int run(const zkt_prove_inputs& in, std::vector<uint8_t>& proof) {
+        int rc;
+        mark("start");
+        if ((rc = choose_route())) return rc;
+        classes = S.use_classes;
+        if ((rc = rounds_1_2(in))) return rc;
+        // prove.rs:110 -- public inputs (BTreeMap order = ascending position)
+        {
+            std::vector<uint8_t> b(in.n_pi * 32);
+            for (size_t i = 0; i < in.n_pi; ++i) H::to_le_bytes(H::from_words(in.pi_vals + 4 * i), b.data() + 32 * i);
+            tr.append_scalars("pi", b.data(), in.n_pi, 32, false);
+        }
+        mark("enqueue rounds 1+2");
+        if ((rc = collect_rounds_1_2(in))) return rc;
+        static const char* L12[6] = {"a_commit", "b_commit", "c_commit", "t_commit", "h1_commit", "h2_commit"};
+        for (int k = 0; k < 6; ++k) tr_commit(L12[k], cm[k]);
+        mark("transcript rounds 1+2");
+
+        ch.beta = tr_challenge("beta"); ch.gamma = tr_challenge("gamma");
+        ch.delta = tr_challenge("delta"); ch.epsilon = tr_challenge("epsilon");
+        if (fe_eq<R>(ch.beta, ch.gamma) || fe_eq<R>(ch.beta, ch.delta) || fe_eq<R>(ch.beta, ch.epsilon) ||
+            fe_eq<R>(ch.gamma, ch.delta) || fe_eq<R>(ch.gamma, ch.epsilon) || fe_eq<R>(ch.delta, ch.epsilon))
+            return set_err(c, ZKT_ERR_EQUAL_CHALLENGES, "challenges must be different (prove.rs:202-207)");
+        mark("challenges round 3");
+        std::optional<ProfScope> prof_round;
+        wait_end();
+        prof_round.emplace(c, "round3");
+        if ((rc = round_3(in))) return rc;
+        prof_round.reset();
+        tr_commit("z1_commit", cm[6]);
+        tr_commit("z2_commit", cm[7]);
+        mark("round 3 finish + commits");
+
+        ch.alpha = tr_challenge("alpha");
+        wait_end();
+        prof_round.emplace(c, "round4");
+        if ((rc = round_4(in))) return rc;
+        prof_round.reset();
+        tr_commit("q_lo_commit", cm[8]);
+        tr_commit("q_mid_commit", cm[9]);
+        tr_commit("q_hi_commit", cm[10]);
+        mark("round 4");
+
+        ch.xi = tr_challenge("xi");
+        wait_end();
+        prof_round.emplace(c, "round5");
+        if ((rc = evaluations())) return rc;
+        // zh(xi) = xi^n - 1 ; L_1(xi) = zh * 1 / (n * (xi - 1))   (util.rs:185-195)
+        if (!xi_point<R>(ch, (uint64_t)S.n, at)) return set_err(c, ZKT_ERR_ZERO_DENOMINATOR, "xi = 1");
+        for (int k = 0; k < EV_COUNT; ++k) tr_scalar(EV_LABEL[k], ev[k]);
+        ch.eta = tr_challenge("eta");
+        if ((rc = openings())) return rc;
+        wait_end();
+        prof_round.reset();
+        if (classes && (rc = check_identity(in))) return rc;
+
+        serialize(proof);
         mark("round 5 finish");
         dump_marks();
         return ZKT_OK;
     }
 };
+
+// One proof; a failed one drains every stream it may have left work on
+template <class C>
+static int run_prover(zkt_ctx* c, const zkt_prove_inputs& in, HostTranscript& tr, std::vector<uint8_t>& proof) {
+    Prover<C> p(c, *c->circuit, tr);
+    const int rc = p.run(in, proof);
+    if (rc) {   // an early return may leave staged copies in flight
+        (void)hipStreamSynchronize(c->circuit->copy_stream);
+        if (c->circuit->comm_stream) (void)hipStreamSynchronize(c->circuit->comm_stream);
+        if (c->circuit->aux_stream) (void)hipStreamSynchronize(c->circuit->aux_stream);
+        (void)hipStreamSynchronize(c->stream);
+    }
+    return rc;
+}
 
 // ---- circuit (ProverKey + ExtendedProverKey) ------------------------------------------------------
 void circuit_release(zkt_ctx* c) {
@@ -1559,10 +1574,7 @@ static int circuit_load_t(zkt_ctx* c, int log_n, const uint64_t* const* polys, c
         if ((rc = gen_powers(c, S.coset[CS_X], m, step.v, first.v))) return rc;
     }
     {   // l_1_coset = coset_fft(L_1), L_1 = ifft(1, 0, ..., 0) = (1/n, ..., 1/n)  (keys/mod.rs:119-120)
-        F nn = fe_zero<R>();
-        nn.v[0] = (uint32_t)(n & 0xffffffffu);
-        nn.v[1] = (uint32_t)((uint64_t)n >> 32);
-        F ninv = fe_inv_host<R>(fe_to_mont<R>(nn));
+        const F ninv = fe_inv_host<R>(fe_from_u64<R>(n));
         if ((rc = gen_powers(c, S.ev[0], n, one.v, ninv.v))) return rc;
         if ((rc = key_coset(S.ev[0], n, S.coset[CS_L1]))) return rc;
     }
@@ -1676,56 +1688,23 @@ struct VtableAdapter : HostTranscript {
 }  // namespace zkt
 
 // The two grand products alone (rows a8 / a9 of SURVEY.md section 8: permutation/mod.rs:181-254, lookup/mod.rs:94-151) over
-// the loaded circuit's sigma evaluations and domain: the same launches round 3 of the prover makes (term kernels, prefix
-// and suffix product scans, ONE host inversion for both denominators, z_combine), on caller-supplied vectors.
+// the loaded circuit's sigma evaluations and domain: round 3's own grand_products_begin / _finish (term kernels, prefix and
+// suffix product scans, ONE host inversion for both denominators, z_combine), on caller-supplied vectors.
 template <class C>
 static int debug_grand_products_t(zkt_ctx* c, const uint64_t* ch, const uint64_t* const* v, uint64_t* out_z1, uint64_t* out_z2) {
-    using R = typename C::Fr;
-    using F = Fe<R>;
+    using H = HostF<typename C::Fr>;
     CircuitState& S = *c->circuit;
     const size_t n = S.n;
     void* dst[7] = {S.ev[0], S.ev[1], S.ev[2], S.ev[4], S.ev[3], S.ev[5], S.ev[6]};   // a b c f t h1 h2
     for (int k = 0; k < 7; ++k) ZKT_HIP(c, hipMemcpyAsync(dst[k], v[k], n * 32, hipMemcpyHostToDevice, c->stream));
-    ZTermsArgs za{};
-    za.a = S.ev[0]; za.b = S.ev[1]; za.c = S.ev[2];
-    za.s1 = S.sigma_ev[0]; za.s2 = S.sigma_ev[1]; za.s3 = S.sigma_ev[2]; za.roots = S.roots;
-    za.f = S.ev[4]; za.t = S.ev[3]; za.h1 = S.ev[5]; za.h2 = S.ev[6];
-    za.num = S.sc[0]; za.den = S.sc[1]; za.n = n;
-    memcpy(za.beta, ch, 32); memcpy(za.gamma, ch + 4, 32); memcpy(za.delta, ch + 8, 32); memcpy(za.epsilon, ch + 12, 32);
-    void* pn2 = S.wcos[W_Z1];
-    void* sd2 = (char*)S.wcos[W_Z1] + n * 32;
-    F* pin = (F*)S.pinned;
+    MerlinHostTranscript tr("zkt_debug_grand_products");   // no challenge is drawn: they are the caller's
+    Prover<C> p(c, S, tr);
+    p.ch.beta = H::from_words(ch); p.ch.gamma = H::from_words(ch + 4); p.ch.delta = H::from_words(ch + 8);
+    p.ch.epsilon = H::from_words(ch + 12);
     int rc;
-    const bool fused3 = c->fused(2) && grand_product_tmp_elems(n) <= n + 8;   // as round 3 decides
-    if (fused3) {
-        const void *tot1, *tot2;
-        if ((rc = grand_product_scan(c, za, 1, S.sc[2], S.sc[3], S.sc[0], &tot1))) return rc;
-        if ((rc = grand_product_scan(c, za, 2, pn2, sd2, S.sc[1], &tot2))) return rc;
-        ZKT_HIP(c, hipMemcpyAsync(pin, tot1, 32, hipMemcpyDeviceToHost, c->stream));
-        ZKT_HIP(c, hipMemcpyAsync(pin + 1, tot2, 32, hipMemcpyDeviceToHost, c->stream));
-    } else {
-        if ((rc = z1_terms(c, za))) return rc;
-        if ((rc = scan_mul(c, S.sc[0], S.sc[2], n, false, S.scan_tmp))) return rc;
-        if ((rc = scan_mul(c, S.sc[1], S.sc[3], n, true, S.scan_tmp))) return rc;
-        if ((rc = z2_terms(c, za))) return rc;
-        if ((rc = scan_mul(c, S.sc[0], pn2, n, false, S.scan_tmp))) return rc;
-        if ((rc = scan_mul(c, S.sc[1], sd2, n, true, S.scan_tmp))) return rc;
-        ZKT_HIP(c, hipMemcpyAsync(pin, S.sc[3], 32, hipMemcpyDeviceToHost, c->stream));
-        ZKT_HIP(c, hipMemcpyAsync(pin + 1, sd2, 32, hipMemcpyDeviceToHost, c->stream));
-    }
+    if ((rc = p.grand_products_begin())) return rc;
     ZKT_HIP(c, hipStreamSynchronize(c->stream));
-    if (fe_is_zero<R>(pin[0])) return set_err(c, ZKT_ERR_ZERO_DENOMINATOR, "zero denominator in the permutation grand product");
-    if (fe_is_zero<R>(pin[1])) return set_err(c, ZKT_ERR_ZERO_DENOMINATOR, "zero denominator in the lookup grand product");
-    const F d1 = pin[0], d2 = pin[1];
-    const F inv12 = fe_inv_host<R>(fe_mul<R>(d1, d2));
-    const F inv1 = fe_mul<R>(inv12, d2), inv2 = fe_mul<R>(inv12, d1);
-    if (fused3) {
-        if ((rc = grand_product_combine(c, S.sc[2], S.sc[3], S.sc[0], inv1.v, S.ev[7], n))) return rc;
-        if ((rc = grand_product_combine(c, pn2, sd2, S.sc[1], inv2.v, S.sc[0], n))) return rc;
-    } else {
-        if ((rc = z_combine(c, S.sc[2], S.sc[3], inv1.v, S.ev[7], n))) return rc;
-        if ((rc = z_combine(c, pn2, sd2, inv2.v, S.sc[0], n))) return rc;
-    }
+    if ((rc = p.grand_products_finish())) return rc;
     ZKT_HIP(c, hipMemcpyAsync(out_z1, S.ev[7], n * 32, hipMemcpyDeviceToHost, c->stream));
     ZKT_HIP(c, hipMemcpyAsync(out_z2, S.sc[0], n * 32, hipMemcpyDeviceToHost, c->stream));
     ZKT_HIP(c, hipStreamSynchronize(c->stream));
@@ -1813,10 +1792,7 @@ static int circuit_check_epk_t(zkt_ctx* c, const char* path, int* vec_out, size_
             } else if (k == EPK_X_C) {
                 src = S.coset[CS_X];
             } else {              // l_1_coset = coset_fft(ifft(1, 0, ..., 0)) (keys/mod.rs:119-120)
-                F nn = fe_zero<R>();
-                nn.v[0] = (uint32_t)(n & 0xffffffffu);
-                nn.v[1] = (uint32_t)((uint64_t)n >> 32);
-                const F ninv = fe_inv_host<R>(fe_to_mont<R>(nn));
+                const F ninv = fe_inv_host<R>(fe_from_u64<R>(n));
                 if ((rc = gen_powers(c, S.ev[0], n, one.v, ninv.v))) return rc;
                 if ((rc = ntt_run(c, log_n + 2, 0, 1, S.ev[0], n, plain))) return rc;
             }
@@ -1932,26 +1908,7 @@ static int prove_impl(zkt_ctx* c, const zkt_prove_inputs* in, HostTranscript& tr
     if (!c->lagrange_off)
         if (int rc1 = lagrange_ensure(c, c->circuit->log_n)) return rc1;
     std::vector<uint8_t> proof;
-    int rc;
-    if (c->curve == ZKT_CURVE_BN254) {
-        Prover<Bn254Curve> p(c, *c->circuit, tr);
-        rc = p.run(*in, proof);
-        if (rc) {   // an early return may leave staged copies in flight
-            (void)hipStreamSynchronize(c->circuit->copy_stream);
-            if (c->circuit->comm_stream) (void)hipStreamSynchronize(c->circuit->comm_stream);
-            if (c->circuit->aux_stream) (void)hipStreamSynchronize(c->circuit->aux_stream);
-            (void)hipStreamSynchronize(c->stream);
-        }
-    } else {
-        Prover<Bls381Curve> p(c, *c->circuit, tr);
-        rc = p.run(*in, proof);
-        if (rc) {
-            (void)hipStreamSynchronize(c->circuit->copy_stream);
-            if (c->circuit->comm_stream) (void)hipStreamSynchronize(c->circuit->comm_stream);
-            if (c->circuit->aux_stream) (void)hipStreamSynchronize(c->circuit->aux_stream);
-            (void)hipStreamSynchronize(c->stream);
-        }
-    }
+    const int rc = c->curve == ZKT_CURVE_BN254 ? run_prover<Bn254Curve>(c, *in, tr, proof) : run_prover<Bls381Curve>(c, *in, tr, proof);
     if (rc) {
         // a failed proof withdraws the announcement of its successor: the next call must not issue early work from
         // pointers the caller may have released meanwhile, nor pick up half-issued early rounds
@@ -2209,16 +2166,6 @@ int zkt_circuit_check_witness(zkt_ctx* c, const zkt_prove_inputs* in, int flags,
 
 // Test hook: the fused quotient pass on its own (quotient_poly.rs:98-224) over the loaded circuit's key cosets and
 // caller-supplied witness cosets, so that the kernel is compared point by point on inputs that satisfy nothing.
-extern "C++" template <class C>
-static void debug_pi_rows(const uint64_t* pi_pos, const uint64_t* pi_vals, size_t n_pi, uint32_t* tab) {
-    using R = typename C::Fr;
-    for (size_t i = 0; i < n_pi; ++i) {
-        tab[10 * i] = (uint32_t)(4 * pi_pos[i]);
-        const Fx<R> v = fx_unpack<R>(HostF<R>::from_words(pi_vals + 4 * i));
-        for (int w = 0; w < 9; ++w) tab[10 * i + 1 + w] = v.l[w];
-    }
-}
-
 int zkt_debug_quotient(zkt_ctx* c, const uint64_t* challenges, const uint64_t* const* wit, const uint64_t* pi_pos,
                        const uint64_t* pi_vals, size_t n_pi, uint64_t* out) {
     if (!c || !challenges || !wit || !out || (n_pi && (!pi_pos || !pi_vals)))
@@ -2244,24 +2191,15 @@ int zkt_debug_quotient(zkt_ctx* c, const uint64_t* challenges, const uint64_t* c
     if (!rc) rc = dev_alloc(c, &d_out, bytes);
     if (!rc && n_pi) {
         std::vector<uint32_t> tab(10 * n_pi);
-        if (c->curve == ZKT_CURVE_BN254) debug_pi_rows<Bn254Curve>(pi_pos, pi_vals, n_pi, tab.data());
-        else debug_pi_rows<Bls381Curve>(pi_pos, pi_vals, n_pi, tab.data());
+        if (c->curve == ZKT_CURVE_BN254) pi_rows<Bn254Curve::Fr>(pi_pos, pi_vals, n_pi, 1, tab.data());
+        else pi_rows<Bls381Curve::Fr>(pi_pos, pi_vals, n_pi, 1, tab.data());
         if (!(rc = dev_alloc(c, (void**)&d_tab, tab.size() * 4)) &&
             hipMemcpy(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
             rc = set_err(c, ZKT_ERR_HIP, "copy of the public-input rows failed");
     }
     if (!rc) {
-        QuotientArgs q{};
-        q.a = d[W_A]; q.b = d[W_B]; q.c = d[W_C]; q.pi = d[W_PI];
-        q.z1 = d[W_Z1]; q.z2 = d[W_Z2]; q.t = d[W_T]; q.h1 = d[W_H1]; q.h2 = d[W_H2];
-        q.q_m = S.coset[CS_QM]; q.q_l = S.coset[CS_QL]; q.q_r = S.coset[CS_QR]; q.q_o = S.coset[CS_QO];
-        q.q_c = S.coset[CS_QC]; q.q_lookup = S.coset[CS_QLOOKUP]; q.q_table = S.coset[CS_QTABLE];
-        q.sigma1 = S.coset[CS_S1]; q.sigma2 = S.coset[CS_S2]; q.sigma3 = S.coset[CS_S3];
-        q.x = S.coset[CS_X]; q.l1 = S.coset[CS_L1];
+        QuotientArgs q = quotient_args(S, d, challenges, challenges + 4, challenges + 8, challenges + 12, challenges + 16);
         q.out = d_out;
-        memcpy(q.alpha, challenges, 32); memcpy(q.beta, challenges + 4, 32); memcpy(q.gamma, challenges + 8, 32);
-        memcpy(q.delta, challenges + 12, 32); memcpy(q.epsilon, challenges + 16, 32);
-        memcpy(q.zh_inv, S.zh_inv, sizeof(q.zh_inv));
         q.n4 = 4 * S.n;
         q.pi_tab = n_pi ? d_tab : nullptr;
         q.n_pi_direct = (uint32_t)n_pi;
@@ -2362,17 +2300,8 @@ int zkt_debug_open_witness(zkt_ctx* c, const uint64_t* coeffs, size_t len, const
     bool zero = true;
     for (int i = 0; i < 8; ++i) zero = zero && z[i] == 0;
     if (zero) return set_err(c, ZKT_ERR_ZERO_DENOMINATOR, "evaluation point is zero");
-    if (c->curve == ZKT_CURVE_BN254) {
-        Fe<Bn254Fr> x;
-        memcpy(x.v, z, 32);
-        x = fe_inv_host<Bn254Fr>(x);
-        memcpy(zi, x.v, 32);
-    } else {
-        Fe<Bls381Fr> x;
-        memcpy(x.v, z, 32);
-        x = fe_inv_host<Bls381Fr>(x);
-        memcpy(zi, x.v, 32);
-    }
+    if (c->curve == ZKT_CURVE_BN254) memcpy(zi, fe_inv_host<Bn254Fr>(HostF<Bn254Fr>::from_words(z4)).v, 32);
+    else memcpy(zi, fe_inv_host<Bls381Fr>(HostF<Bls381Fr>::from_words(z4)).v, 32);
     ZKT_HIP(c, hipMemcpyAsync(S.sc[0], coeffs, len * 32, hipMemcpyHostToDevice, c->stream));
     int rc = open_witness(c, S.sc[0], len, z, zi, S.sc[1], S.sc[2], S.scan_tmp, S.sc[3], S.eval_pw);
     if (rc) return rc;

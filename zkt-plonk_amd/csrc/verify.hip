@@ -12,6 +12,7 @@
 #include "hostec.hpp"
 #include "g1decomp.hpp"
 #include "hostinv.hpp"
+#include "linearisation.hpp"
 #include "msm.hpp"
 #include "pairing.hpp"
 #include "transcript.hpp"
@@ -323,8 +324,6 @@ struct Verifier {
         const size_t nb = Q::N * 4;
         const int L64 = Q::N / 2;
         enum { A, B, Cc, T, H1, H2, Z1, Z2, QLO, QMID, QHI, AW, SAW };
-        const F &e_a = ev[0], &e_b = ev[1], &e_c = ev[2], &e_s1 = ev[3], &e_s2 = ev[4], &e_z1n = ev[5], &e_ql = ev[6],
-                &e_t = ev[7], &e_tn = ev[8], &e_z2n = ev[9], &e_h1n = ev[10], &e_h2 = ev[11];
         Affine<Q> vk[10];
         for (int k = 0; k < 10; ++k) {
             if (in.vk_is_infinity && in.vk_is_infinity[k]) {
@@ -357,67 +356,21 @@ struct Verifier {
         const F alpha = challenge(tr, "alpha");
         tr_commit(tr, "q_lo_commit", cm[QLO]); tr_commit(tr, "q_mid_commit", cm[QMID]); tr_commit(tr, "q_hi_commit", cm[QHI]);
         const F xi = challenge(tr, "xi");
-        // ---- scalars (proof.rs:362-378, compute_r0 163-217, util.rs:185-195) ----
-        const F one = fe_one<R>();
-        const F zh = fe_sub<R>(fe_pow_u64<R>(xi, in.n), one);
-        F nn = fe_zero<R>();
-        nn.v[0] = (uint32_t)(in.n & 0xffffffffu);
-        nn.v[1] = (uint32_t)(in.n >> 32);
-        nn = fe_to_mont<R>(nn);
-        auto lagrange = [&](const F& point, F* out) {   // zh * point / (n * (xi - point))
-            const F den = fe_mul<R>(nn, fe_sub<R>(xi, point));
-            if (fe_is_zero<R>(den)) return false;
-            *out = fe_mul<R>(fe_mul<R>(zh, point), fe_inv_host<R>(den));
-            return true;
-        };
-        F l1;
-        if (!lagrange(one, &l1)) return ZKT_ERR_ZERO_DENOMINATOR;
-        const F a2 = fe_sqr<R>(alpha), a3 = fe_mul<R>(a2, alpha), a4 = fe_mul<R>(a3, alpha), a5 = fe_mul<R>(a4, alpha);
-        const F opd = fe_add<R>(one, delta), eopd = fe_mul<R>(epsilon, opd);
-        const F k1 = fe_from_u32<R>(7), k2 = fe_from_u32<R>(13);
-        F r0 = fe_zero<R>();
-        for (size_t i = 0; i < in.n_pi; ++i) {
-            F root, v, li;
-            memcpy(root.v, in.pi_roots + 4 * i, 32);
-            memcpy(v.v, in.pub_inputs + 4 * i, 32);
-            if (!lagrange(root, &li)) return ZKT_ERR_ZERO_DENOMINATOR;
-            r0 = fe_sub<R>(r0, fe_mul<R>(li, v));
-        }
-        {
-            F p2 = fe_mul<R>(alpha, e_z1n);
-            p2 = fe_mul<R>(p2, fe_add<R>(fe_add<R>(e_a, fe_mul<R>(beta, e_s1)), gamma));
-            p2 = fe_mul<R>(p2, fe_add<R>(fe_add<R>(e_b, fe_mul<R>(beta, e_s2)), gamma));
-            p2 = fe_mul<R>(p2, fe_add<R>(e_c, gamma));
-            F p4 = fe_mul<R>(a3, e_z2n);
-            p4 = fe_mul<R>(p4, fe_add<R>(eopd, fe_mul<R>(delta, e_h2)));
-            p4 = fe_mul<R>(p4, fe_add<R>(fe_add<R>(eopd, e_h2), fe_mul<R>(delta, e_h1n)));
-            r0 = fe_add<R>(fe_add<R>(r0, p2), fe_add<R>(fe_mul<R>(l1, a2), fe_add<R>(p4, fe_mul<R>(l1, a4))));
-        }
+        // ---- scalars (linearisation.hpp: proof.rs:362-378, compute_r0 163-217, util.rs:185-195) ----
+        const Challenges<R> ch{beta, gamma, delta, epsilon, alpha, xi, fe_zero<R>()};
+        XiPoint<R> at;
+        if (!xi_point<R>(ch, in.n, at)) return ZKT_ERR_ZERO_DENOMINATOR;
+        F r0;
+        if (compute_r0<R>(ch, at, ev, in.pi_roots, in.pub_inputs, in.n_pi, &r0)) return ZKT_ERR_ZERO_DENOMINATOR;
         // ---- linearisation commitment (proof.rs:220-282; the 13-point MSM of commitment.rs:32-45) ----
-        const F bz = fe_mul<R>(beta, xi);
-        F s_z1 = fe_mul<R>(alpha, fe_add<R>(fe_add<R>(bz, e_a), gamma));
-        s_z1 = fe_mul<R>(s_z1, fe_add<R>(fe_add<R>(fe_mul<R>(bz, k1), e_b), gamma));
-        s_z1 = fe_mul<R>(s_z1, fe_add<R>(fe_add<R>(fe_mul<R>(bz, k2), e_c), gamma));
-        s_z1 = fe_add<R>(s_z1, fe_mul<R>(l1, a2));
-        F s_s3 = fe_mul<R>(fe_mul<R>(fe_neg<R>(alpha), beta), e_z1n);
-        s_s3 = fe_mul<R>(s_s3, fe_add<R>(fe_add<R>(fe_mul<R>(beta, e_s1), e_a), gamma));
-        s_s3 = fe_mul<R>(s_s3, fe_add<R>(fe_add<R>(fe_mul<R>(beta, e_s2), e_b), gamma));
-        F s_z2 = fe_mul<R>(fe_mul<R>(a3, opd), fe_add<R>(epsilon, fe_mul<R>(e_ql, e_c)));
-        s_z2 = fe_mul<R>(s_z2, fe_add<R>(fe_add<R>(eopd, e_t), fe_mul<R>(delta, e_tn)));
-        s_z2 = fe_add<R>(s_z2, fe_mul<R>(a4, l1));
-        F s_h1 = fe_mul<R>(fe_mul<R>(fe_neg<R>(a3), e_z2n), fe_add<R>(fe_add<R>(eopd, e_h2), fe_mul<R>(delta, e_h1n)));
-        const F s_qt = fe_mul<R>(a5, e_t);
-        const F xn2 = fe_mul<R>(fe_mul<R>(fe_add<R>(zh, one), xi), xi), nzh = fe_neg<R>(zh);
-        const F sc[13] = {fe_mul<R>(e_a, e_b), e_a, e_b, e_c, one, s_z1, s_s3, s_z2, s_h1, s_qt,
-                          nzh, fe_mul<R>(nzh, xn2), fe_mul<R>(nzh, fe_sqr<R>(xn2))};
+        F sc[LIN_COUNT];
+        linearisation_scalars<R>(ch, at, ev, sc);
         const int pt[13] = {SRC_VK + QM, SRC_VK + QL, SRC_VK + QR, SRC_VK + QO, SRC_VK + QC, SRC_CM + Z1, SRC_VK + S3, SRC_CM + Z2,
                             SRC_CM + H1, SRC_VK + QTABLE, SRC_CM + QLO, SRC_CM + QMID, SRC_CM + QHI};
-        static const char* EL[12] = {"a_eval", "b_eval", "c_eval", "sigma1_eval", "sigma2_eval", "z1_next_eval",
-                                     "q_lookup_eval", "t_eval", "t_next_eval", "z2_next_eval", "h1_next_eval", "h2_eval"};
-        for (int k = 0; k < 12; ++k) {
+        for (int k = 0; k < EV_COUNT; ++k) {
             uint8_t b[32];
             to_le(ev[k], b);
-            tr.append_scalars(EL[k], b, 1, 32, true);
+            tr.append_scalars(EV_LABEL[k], b, 1, 32, true);
         }
         const F eta = challenge(tr, "eta");
         // ---- the two openings (proof.rs:420-500) ----
@@ -449,13 +402,13 @@ struct Verifier {
         {
             for (int k = 0; k < 13; ++k) push(0, pt[k], sc[k]);
             const int cs[8] = {SRC_CM + A, SRC_CM + B, SRC_CM + Cc, SRC_VK + S1, SRC_VK + S2, SRC_VK + QLOOKUP, SRC_CM + T, SRC_CM + H2};
-            const F vs[8] = {e_a, e_b, e_c, e_s1, e_s2, e_ql, e_t, e_h2};
+            const F vs[8] = {ev[EV_A], ev[EV_B], ev[EV_C], ev[EV_S1], ev[EV_S2], ev[EV_QL], ev[EV_T], ev[EV_H2]};
             fold(0, cs, vs, 8, eta, r0, xi, SRC_CM + AW);
         }
         {
             const int cs[4] = {SRC_CM + Z1, SRC_CM + Z2, SRC_CM + T, SRC_CM + H1};
-            const F vs[4] = {e_z1n, e_z2n, e_tn, e_h1n};
-            fold(1, cs, vs, 4, one, fe_zero<R>(), fe_mul<R>(xi, w), SRC_CM + SAW);
+            const F vs[4] = {ev[EV_Z1N], ev[EV_Z2N], ev[EV_TN], ev[EV_H1N]};
+            fold(1, cs, vs, 4, fe_one<R>(), fe_zero<R>(), fe_mul<R>(xi, w), SRC_CM + SAW);
         }
         return ZKT_OK;
     }
