@@ -69,7 +69,21 @@ void zkt_ctx_destroy(zkt_ctx* ctx);
  * Create and destroy contexts from one thread (or serialise those calls); prove on them concurrently. */
 int zkt_ctx_fork(zkt_ctx* ctx, zkt_ctx** out);
 const char* zkt_last_error(const zkt_ctx* ctx);
-/* Use an existing hipStream_t (e.g. PyTorch's current stream) for every launch of this context. */
+/* Use an existing hipStream_t (e.g. PyTorch's current stream; NULL is the device's default stream) for every launch of
+ * this context.  The stream stays the caller's, and the caller may have work of its own on it when it calls the
+ * library (tests/test_gpu_caller_stream.py pins the four rules):
+ *  1. Everything that reads caller memory -- a _dev entry's device pointers, the device witness of zkt_prove /
+ *     zkt_prove_set_next / zkt_circuit_check_witness -- is ordered behind the work already on the stream at the time of
+ *     the call: a buffer the caller's own kernel on this stream is still to write is read after that kernel.  The
+ *     library's internal streams (MSM tails, the prover's copy / aux / comm streams, the KZG seam's copy stream) are
+ *     ordered against the context's stream with events; none of them reads caller memory ahead of it.
+ *  2. Results that an enqueue-only entry leaves in device memory are visible to whatever the caller enqueues on the
+ *     stream afterwards, without a synchronisation.  Entries that hand a result to HOST memory synchronise and say so.
+ *  3. zkt_ctx_set_stream synchronises the OLD stream before it switches.  MSMs begun with zkt_msm_enqueue_dev and a
+ *     proof announced with zkt_prove_set_next carry over: their tails are ordered by events, not by the stream's
+ *     identity, and the next call on the new stream collects or continues them with the same results.
+ *  4. The library never destroys a caller's stream: zkt_ctx_set_stream to another stream and zkt_ctx_destroy leave it
+ *     usable (only the stream zkt_ctx_create made is the library's to destroy). */
 int zkt_ctx_set_stream(zkt_ctx* ctx, void* hip_stream);
 int zkt_ctx_synchronize(zkt_ctx* ctx);
 /* Timing with HIP events on the stream the kernels run on (each event pair costs a few microseconds of stream time,
@@ -175,7 +189,10 @@ int zkt_domain_group_gen(zkt_ctx* ctx, int log_n, uint64_t* out4);
 /* Loads `count` G1 powers (ck.powers_of_g of SonicKZG10's CommitterKey, produced by PC::trim at
  * plonk.rs:79-85) and precomputes the window multiples used by the MSM.  One-time per key.  The
  * prover never commits to more than n + 7 coefficients (the opening witnesses), so loading n + 8 of the 4n + 1 powers the reference keeps is
- * enough.  Replaces nothing at run time: it is the device-resident form of `ck`. */
+ * enough.  Replaces nothing at run time: it is the device-resident form of `ck`.
+ * _dev: the powers already in HBM, read behind the work already on the context's stream.  Both forms release the
+ * previous key and allocate the new tables, which waits for the device: unlike the other _dev entries this one is no
+ * enqueue.  Synchronises the stream. */
 int zkt_srs_load(zkt_ctx* ctx, const uint64_t* g1_xy_mont, size_t count);
 int zkt_srs_load_dev(zkt_ctx* ctx, const void* d_g1_xy_mont, size_t count);
 /* Test/bench SRS with a KNOWN trapdoor: powers_of_g[i] = tau^i * G (tau: 4 canonical limbs).
@@ -492,7 +509,9 @@ typedef struct {
  *  - xi = 1 (L_1(xi) divides by n (xi - 1)): ZKT_ERR_ZERO_DENOMINATOR, in round 5.
  * Everything else is proved, in particular xi on the domain (Z_H(xi) = 0), xi w = 1, xi = 0 (the opening witnesses are then
  * the combinations shifted down by one coefficient), eta in {0, 1}, alpha = 1, gamma = 0, delta = 0.  A refusal withdraws
- * an announced successor (zkt_prove_set_next) and leaves the context ready for the next proof. */
+ * an announced successor (zkt_prove_set_next) and leaves the context ready for the next proof.
+ * A device witness (wires_on_device != 0) is read behind the work already on the context's stream.  The proof goes to
+ * host memory and the transcript is fed on the host between the rounds.  Synchronises the stream. */
 int zkt_prove(zkt_ctx* ctx, const zkt_prove_inputs* in, zkt_transcript* transcript, uint8_t* proof_out,
               size_t proof_cap, size_t* proof_len);
 /* Optional, for back-to-back proofs on one context: announces the inputs of the proof that will follow the next
@@ -500,7 +519,9 @@ int zkt_prove(zkt_ctx* ctx, const zkt_prove_inputs* in, zkt_transcript* transcri
  * `next` behind its own quotient commitments (round 1) and opening commitments (round 2): their bucket reductions
  * are latency-bound and leave the GPU nearly empty otherwise, and it no longer drains between the two proofs.  The following zkt_prove must
  * be given the same inputs (same pointers and sizes; the data they point to must stay unchanged meanwhile) - otherwise
- * the early work is simply redone.  NULL withdraws the announcement.  Proof bytes are the same either way. */
+ * the early work is simply redone.  NULL withdraws the announcement.  Proof bytes are the same either way.
+ * The call itself only records the announcement: nothing is enqueued, no synchronisation; the announced device
+ * witness is first read by that next zkt_prove, behind the work on the context's stream at that time. */
 int zkt_prove_set_next(zkt_ctx* ctx, const zkt_prove_inputs* next);
 int zkt_prove_with(zkt_ctx* ctx, const zkt_prove_inputs* in, const zkt_transcript_vtable* transcript,
                    uint8_t* proof_out, size_t proof_cap, size_t* proof_len);

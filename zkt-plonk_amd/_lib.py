@@ -1030,6 +1030,10 @@ class Context:
         pts = np.ascontiguousarray(pts, dtype=np.uint64).reshape(-1, 2 * self.fq_limbs)
         self.check(self._L.zkt_srs_load(self._h, u64p(pts), pts.shape[0]))
 
+    def srs_load_dev(self, d_pts: int, count: int):
+        """zkt_srs_load_dev: `count` powers (x || y Montgomery limbs each) already resident in HBM (device pointer)."""
+        self.check(self._L.zkt_srs_load_dev(self._h, ctypes.c_void_p(d_pts), count))
+
     def srs_load_file(self, ck_path: str, max_powers: int = 0):
         """zkt_srs_load from the reference CLI's --ck file (CommitterKey.powers_of_g)."""
         L = self._L
