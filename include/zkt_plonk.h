@@ -788,7 +788,8 @@ int zkt_verify(int curve_id, const zkt_verify_inputs* in, zkt_transcript* transc
  * taken through zkt_verify_prepare with its own seeded transcript, and all 2 * count opening checks are folded into ONE
  * product of two pairings with 128-bit coefficients hashed from every (L, W), h and beta h (see csrc/verify.hip).
  * *accepted = 1 iff every proof verifies (a batch holding a bad proof passes with probability 2^-128); a rejected batch
- * does not say which proof failed -- fall back to zkt_verify.  Cost per proof: the transcript, r0 and the two short
+ * does not say which proof failed -- zkt_verify_batch_locate names the bad proofs, or fall back to zkt_verify per
+ * proof.  Cost per proof: the transcript, r0 and the two short
  * multi-scalar multiplications; the pairings (~0.5 ms on BN254) are paid once per batch.  The reference verifies proof by
  * proof (proof.rs:285-503); this is the batch form SURVEY.md 8f.4 lists.  Errors as zkt_verify_prepare (a malformed
  * proof fails the call, not just the batch). */
@@ -828,8 +829,10 @@ int zkt_g1_decompress_dev(zkt_ctx* ctx, const void* d_compressed, size_t n, void
  * compressed commitments are decompressed and checked in ONE zkt_g1_decompress launch, and the 2 * count folded openings
  * are multiplied out as two device MSMs (the machinery of zkt_msm_g1_bases) instead of ~35 host scalar multiplications per
  * proof.  For a verifier of many proofs under one SRS (a relayer, an aggregator); for one proof or a handful use
- * zkt_verify / zkt_verify_batch -- where the device route overtakes the host one is UNMEASURED (docs/EXPERIMENTS.md
- * "batch verification on the device"), and there is no automatic fallback: the caller chooses the entry point.
+ * zkt_verify / zkt_verify_batch -- measured on an MI355X (docs/EXPERIMENTS.md "locating the bad proofs of a batch"), the
+ * host route is faster for a single proof (1.3 ms against 1.5 ms on BN254, 2.8 against 4.1 on BLS12-381) and the device
+ * route from 16 proofs on, the next count measured (3.1x / 4.3x there, 5.7x / 14x at 4096, where the per-proof host stage
+ * is all that is left: 0.11 ms / 0.12 ms per proof); there is no automatic fallback: the caller chooses the entry point.
  * Arguments as zkt_verify_batch (every transcript seeded like its prover's, consumed exactly as zkt_verify_prepare
  * consumes it), with a context in place of the curve id (the context's curve is used).  Per proof the host keeps the byte-level checks (length, the two Option::None bytes,
  * canonical evaluations), the transcript, r0 and the scalars of the two openings; it never forms the pairs (L_j, W_j).
@@ -845,7 +848,7 @@ int zkt_g1_decompress_dev(zkt_ctx* ctx, const void* d_compressed, size_t n, void
  * zkt_verify_batch_prepare_dev stops before the pairing: out_ab = A, B as (x, y) Montgomery limbs, out_ab_is_infinity 2
  * flags (may be NULL), out_rho (may be NULL) the 2 * count coefficients as 4 canonical u64 words each -- for a caller who
  * keeps arkworks' product_of_pairings.  zkt_verify_batch_dev runs the host pairing of zkt_pairing_product_is_one and
- * sets *accepted; a rejected batch does not say which proof failed.
+ * sets *accepted; a rejected batch does not say which proof failed: zkt_verify_batch_locate below does.
  * Errors: count = 0 or count > ZKT_VERIFY_BATCH_DEV_MAX (24 * count <= ZKT_MSM_BASES_MAX) -> ZKT_ERR_INVALID_ARGUMENT;
  * malformed bytes, or a commitment whose status is neither ZKT_G1_VALID nor ZKT_G1_IDENTITY -> ZKT_ERR_INVALID_ARGUMENT,
  * zkt_last_error names the proof index and the commitment; otherwise as zkt_verify_prepare.
@@ -859,6 +862,54 @@ int zkt_verify_batch_prepare_dev(zkt_ctx* ctx, const zkt_verify_inputs* ins, zkt
                                  int* out_ab_is_infinity, uint64_t* out_rho);
 int zkt_verify_batch_dev(zkt_ctx* ctx, const zkt_verify_inputs* ins, zkt_transcript* const* transcripts, size_t count,
                          const uint64_t* h_g2_mont, const uint64_t* beta_h_g2_mont, int* accepted);
+
+/* zkt_verify_batch_dev that also names the bad proofs of a rejected batch.  The batch check is linear in the proofs: with
+ * the coefficients rho_j of zkt_verify_batch_dev (same seed), proof i has the pair
+ *     P_i = rho_2i L_2i + rho_2i+1 L_2i+1,   Q_i = rho_2i W_2i + rho_2i+1 W_2i+1,
+ * which passes e(P_i, h) e(-Q_i, beta h) == 1 iff the proof verifies (up to 2^-128), and (A, B) is the sum of all pairs.
+ * The call runs zkt_verify_batch_dev's stages and its one pairing check.  If that passes: *accepted = 1, out_bad all zero,
+ * *n_checks = 1, and nothing else ran -- an accepted batch costs what zkt_verify_batch_dev costs.  If it fails, the device
+ * forms the `count` pairs (csrc/verify_leaves.hip: per proof at most 24 full-width scalar multiplications for P_i, one per
+ * source point, and two by 128-bit coefficients for Q_i) and adds neighbours (2m, 2m + 1) level by level into a binary
+ * tree whose root is (A, B), an unpaired last node moving up unchanged; the tree comes down in one copy and the host walks
+ * it from the root: at a failing node the left child is checked; if it passes the right child fails without a check,
+ * otherwise the right child is checked too.  A failing leaf is a bad proof: out_bad[i] = 1 (count bytes, all written),
+ * *accepted = 0, *n_bad = their number b, *n_checks = the pairing checks made, root included:
+ *     n_checks <= 1 + 2 * b * ceil(log2(count)),   and exactly 1 for count = 1.
+ * The verdicts are those of zkt_verify per proof, at one host stage for the batch plus one pairing check per node visited
+ * instead of a whole zkt_verify per proof.  Measured on an MI355X (docs/EXPERIMENTS.md "locating the bad proofs of a
+ * batch"), one bad proof among 4096: 485 ms against 5277 ms for the zkt_verify loop on BN254 (24 checks), 562 ms against
+ * 11364 ms on BLS12-381; among 256: 44 against 330 ms and 58 against 709 ms; the loop wins only for a single proof.
+ * Arguments, limits, errors and context rules are those of zkt_verify_batch_dev (1 <= count <= ZKT_VERIFY_BATCH_DEV_MAX; a
+ * malformed proof or a refused commitment fails the call and zkt_last_error names the proof; transcripts are consumed as
+ * zkt_verify_prepare consumes them; forked contexts and contexts with a communicator work; no key, circuit or table is
+ * touched and an announced proof keeps its bytes).  accepted and out_bad are required, n_bad and n_checks may be NULL; on
+ * an error none of the four is written.
+ * Scratch: the call's own (shared with zkt_verify_batch_dev and zkt_g1_decompress, grown on demand).  A rejected batch needs,
+ * behind the 13 * count * 3 * nb + 13 * count bytes of the decompression (nb = 32 / 48), per proof 11 * 2 * nb bytes of
+ * bases, 24 * 32 of scalars, 2 * 32 of coefficients and 26 * 16 * L of products (L = 9 / 14 limbs: 144 / 224 bytes each),
+ * and 2 * nodes * 4 * nb bytes of tree, nodes = count + ceil(count / 2) + ... + 1 < 2 * count + 64; each part rounded up to
+ * 256 bytes.  That is ~5.8 KB (BN254) / ~8.5 KB (BLS12-381) per proof.
+ * Synchronises the stream.  Profile scopes: those of zkt_verify_batch_dev, then "verify_leaves", "verify_tree".
+ * Of zkt_verify_batch_dev's family (host arguments, work on the context's stream); its run on a stream the caller
+ * keeps busy is tests/test_gpu_verify_locate_stream.py. */
+int zkt_verify_batch_locate(zkt_ctx* ctx, const zkt_verify_inputs* ins, zkt_transcript* const* transcripts,
+                            size_t count, const uint64_t* h_g2_mont, const uint64_t* beta_h_g2_mont,
+                            int* accepted, uint8_t* out_bad, size_t* n_bad, size_t* n_checks);
+/* Test hooks of the call above.  Both return the tree: out_nodes_xy_mont = 2 * nodes affine points as (x, y) Montgomery
+ * limbs, P's tree then Q's, each level by level with the leaves first ((0, 0) for the identity), out_is_infinity 2 * nodes
+ * flags, out_rho the 2 * count coefficients as 4 canonical words each; all normalised with ONE field inversion.
+ * zkt_debug_verify_batch_tree builds leaves and levels on the device whatever the verdict (errors as the call above).
+ * zkt_debug_verify_locate_host runs the whole call on the host, with no context and no device: the host verifier's own
+ * deserialisation, and leaves and levels through the very code the kernels run (csrc/verify_leaves.hpp); the three tree
+ * outputs may be NULL.  It returns the error code only. */
+int zkt_debug_verify_batch_tree(zkt_ctx* ctx, const zkt_verify_inputs* ins, zkt_transcript* const* transcripts,
+                                size_t count, const uint64_t* h_g2_mont, const uint64_t* beta_h_g2_mont,
+                                uint64_t* out_nodes_xy_mont, int* out_is_infinity, uint64_t* out_rho);
+int zkt_debug_verify_locate_host(int curve_id, const zkt_verify_inputs* ins, zkt_transcript* const* transcripts,
+                                 size_t count, const uint64_t* h_g2_mont, const uint64_t* beta_h_g2_mont,
+                                 int* accepted, uint8_t* out_bad, size_t* n_bad, size_t* n_checks,
+                                 uint64_t* out_nodes_xy_mont, int* out_is_infinity, uint64_t* out_rho);
 
 /* HomomorphicCommitment::multi_scalar_mul (commitment.rs:32-45) for ARBITRARY points: the verifier's 13-point
  * linearisation commitment and similar short combinations.  Host arithmetic (double-and-add on 64-bit limbs): at this

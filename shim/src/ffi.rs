@@ -134,6 +134,9 @@ extern "C" {
                                         out_ab_is_infinity: *mut c_int, out_rho: *mut u64) -> c_int;
     pub fn zkt_verify_batch_dev(ctx: *mut ZktCtx, inputs: *const ZktVerifyInputs, transcripts: *const *mut c_void, count: usize,
                                 h_g2_mont: *const u64, beta_h_g2_mont: *const u64, accepted: *mut c_int) -> c_int;
+    pub fn zkt_verify_batch_locate(ctx: *mut ZktCtx, inputs: *const ZktVerifyInputs, transcripts: *const *mut c_void, count: usize,
+                                   h_g2_mont: *const u64, beta_h_g2_mont: *const u64, accepted: *mut c_int, out_bad: *mut u8,
+                                   n_bad: *mut usize, n_checks: *mut usize) -> c_int;
     pub fn zkt_g1_decompress(ctx: *mut ZktCtx, compressed: *const u8, n: usize, out_xy_mont: *mut u64, out_status: *mut u8) -> c_int;
     pub fn zkt_g1_decompress_dev(ctx: *mut ZktCtx, d_compressed: *const c_void, n: usize, d_out_xy_mont: *mut c_void,
                                  d_out_status: *mut c_void) -> c_int;

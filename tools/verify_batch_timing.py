@@ -1,13 +1,16 @@
 """Times batch verification on the host (zkt_verify_batch) against the device route (zkt_verify_batch_dev) in one run, on
-batches of 1, 16, 256 and 4096 proofs made by repeating three oracle proofs (circuits of 150 / 90 / 150 gates, one SRS).
-Needs an MI355X; run it under a time limit:
+batches of 1, 16, 256 and 4096 proofs made by repeating three oracle proofs (circuits of 150 / 90 / 150 gates, one SRS),
+and then zkt_verify_batch_locate with 0, 1 and 8 bad proofs (a flipped evaluation byte) against a loop of zkt_verify
+over the same batch.  Needs an MI355X; run it under a time limit:
 
     timeout -k 10 900 python tools/verify_batch_timing.py [--reps 3] [--counts 1,16,256,4096] [--curves bn254,bls12_381]
 
 Only the C calls are timed (the argument arrays and the seeded transcripts are made before the clock starts); host and
 device alternate within every repetition and the figure is the median wall time of whole calls.  Per-stage device times
-come from the profile scopes "verify_decompress" and "verify_msm" of one more, profiled call; "host part" is that call's
-wall time minus the two.  The last line per curve names the smallest measured count at which the device route is faster."""
+come from the profile scopes "verify_decompress" and "verify_msm" ("verify_leaves" and "verify_tree" in the second table)
+of one more, profiled call; "host part" is that call's wall time minus the scopes.  The zkt_verify loop runs once per
+count, over the batch with one bad proof.  The last line per curve and table names the smallest measured count at which
+the device route (the locate call) is faster."""
 import argparse
 import ctypes
 import os
@@ -37,6 +40,82 @@ def _call(fn, handle, cv, entries, h, beta_h):
     ms = (time.perf_counter() - t0) * 1e3
     assert rc == 0, rc
     return ms, bool(ok.value)
+
+
+def _locate(L, ctx, cv, entries, h, beta_h):
+    """one timed zkt_verify_batch_locate on fresh transcripts -> (ms, accepted, bad positions, n_checks)"""
+    ins, trs, k, hh, bh, keep = _lib._verify_batch_args(ctx.curve, _items(cv, entries), h, beta_h)
+    ok, n_bad, n_chk = ctypes.c_int(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+    bad = np.zeros(k, dtype=np.uint8)
+    u = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+    t0 = time.perf_counter()
+    rc = L.zkt_verify_batch_locate(ctx.handle, ins, trs, k, u(hh), u(bh), ctypes.byref(ok),
+                                   bad.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), ctypes.byref(n_bad), ctypes.byref(n_chk))
+    ms = (time.perf_counter() - t0) * 1e3
+    assert rc == 0, rc
+    return ms, bool(ok.value), np.flatnonzero(bad).tolist(), n_chk.value
+
+
+def _verify_loop(L, cv, entries, h, beta_h):
+    """zkt_verify proof by proof over the batch -> (ms, bad positions)"""
+    cid = _lib.curve_id(cv.name)
+    ins, trs, k, hh, bh, keep = _lib._verify_batch_args(cid, _items(cv, entries), h, beta_h)
+    u = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+    ph, pbh, ok, bad = u(hh), u(bh), ctypes.c_int(0), []
+    t0 = time.perf_counter()
+    for i in range(k):
+        rc = L.zkt_verify(cid, ctypes.byref(ins[i]), trs[i], ph, pbh, ctypes.byref(ok))
+        assert rc == 0, rc
+        if not ok.value:
+            bad.append(i)
+    return (time.perf_counter() - t0) * 1e3, bad
+
+
+def _flip(entries, positions):
+    out = list(entries)
+    for i in positions:
+        vk, pis, proof, kind = out[i]
+        raw = bytearray(proof)
+        raw[-40] ^= 1
+        out[i] = (vk, pis, bytes(raw), kind)
+    return out
+
+
+def locate_leg(L, ctx, cv, made, h, beta_h, counts, reps_arg):
+    name = cv.name
+    _lib.verify(cv.name, *_items(cv, made[:1])[0][:7], h, beta_h, _items(cv, made[:1])[0][7])   # binds zkt_verify's argument types
+    _locate(L, ctx, cv, _flip(made, [1]), h, beta_h)                            # first use: allocations, code load
+    print("%s: count | bad | locate ms | n_checks | stages: leaves ms, tree ms, rest ms | zkt_verify loop ms | loop/locate" % name)
+    wins = None
+    for count in counts:
+        entries = _cycle(made, count)
+        reps = reps_arg if count <= 256 else max(1, reps_arg // 3)
+        one_bad = [count // 2]
+        loop_ms, loop_bad = _verify_loop(L, cv, _flip(entries, one_bad), h, beta_h)
+        assert loop_bad == one_bad
+        for n_bad in (0, 1, 8):
+            if n_bad > count:
+                continue
+            positions = one_bad if n_bad == 1 else [(2 * j + 1) * count // (2 * n_bad) for j in range(n_bad)]
+            batch = _flip(entries, positions)
+            t = []
+            for _ in range(reps):
+                ms, ok, bad, n_checks = _locate(L, ctx, cv, batch, h, beta_h)
+                assert bad == sorted(positions) and ok == (not positions)
+                t.append(ms)
+            ctx.profile_enable(True)
+            wall, ok, bad, n_checks = _locate(L, ctx, cv, batch, h, beta_h)
+            leaves = ctx.profile_get("verify_leaves")[1] if n_bad else 0.0
+            tree = ctx.profile_get("verify_tree")[1] if n_bad else 0.0
+            ctx.profile_enable(False)
+            loc = float(np.median(t))
+            tail = "%9.2f | %6.2f" % (loop_ms, loop_ms / loc) if n_bad == 1 else "        - |      -"
+            if n_bad == 1 and wins is None and loc < loop_ms:
+                wins = count
+            print("%s: %5d | %d | %9.2f | %3d | %8.2f %8.2f %8.2f | %s"
+                  % (name, count, n_bad, loc, n_checks, leaves, tree, wall - leaves - tree, tail), flush=True)
+    print("%s: locating one bad proof is faster than the zkt_verify loop from count = %s on (of the counts measured)" % (name, wins),
+          flush=True)
 
 
 def main():
@@ -77,6 +156,7 @@ def main():
                 print("%s: %5d | %9.2f | %9.2f | %5.2f | %8.2f %8.2f %8.2f | %.3f %.3f"
                       % (name, count, host, dev, host / dev, dec, msm, wall - dec - msm, host / count, dev / count), flush=True)
             print("%s: the device route is faster from count = %s on (of the counts measured)" % (name, crossover), flush=True)
+            locate_leg(L, ctx, cv, made, h, beta_h, counts, args.reps)
         finally:
             ctx.close()
 

@@ -135,6 +135,13 @@ def _bind_optional(L):
         vi, tp = ctypes.POINTER(VerifyInputs), ctypes.POINTER(vp)
         L.zkt_verify_batch_prepare_dev.argtypes = [vp, vi, tp, ctypes.c_size_t, u64p, u64p, u64p, ip, u64p]
         L.zkt_verify_batch_dev.argtypes = [vp, vi, tp, ctypes.c_size_t, u64p, u64p, ip]
+    if hasattr(L, "zkt_verify_batch_locate"):
+        vi, tp = ctypes.POINTER(VerifyInputs), ctypes.POINTER(vp)
+        u8p, szp = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_size_t)
+        L.zkt_verify_batch_locate.argtypes = [vp, vi, tp, ctypes.c_size_t, u64p, u64p, ip, u8p, szp, szp]
+        L.zkt_debug_verify_batch_tree.argtypes = [vp, vi, tp, ctypes.c_size_t, u64p, u64p, u64p, ip, u64p]
+        L.zkt_debug_verify_locate_host.argtypes = [ctypes.c_int, vi, tp, ctypes.c_size_t, u64p, u64p, ip, u8p, szp, szp,
+                                                   u64p, ip, u64p]
     if hasattr(L, "zkt_kzg_commit_batch"):
         pp, szp = ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)
         L.zkt_kzg_commit_batch.argtypes = [vp, pp, szp, ctypes.c_int, ctypes.c_int, u64p, ip]
@@ -378,6 +385,41 @@ def verify_batch(curve, items, h_g2, beta_h_g2) -> bool:
     if rc:
         raise ZktError(rc, "zkt_verify_batch")
     return bool(ok.value)
+
+
+def verify_tree_levels(count: int):
+    """The level sizes of the tree zkt_verify_batch_locate builds over `count` proofs, leaves first: count,
+    ceil(count / 2), ..., 1."""
+    sizes = [int(count)]
+    while sizes[-1] > 1:
+        sizes.append((sizes[-1] + 1) // 2)
+    return sizes
+
+
+def debug_verify_locate_host(curve, items, h_g2, beta_h_g2, want_tree: bool = True):
+    """zkt_debug_verify_locate_host: zkt_verify_batch_locate run on the host, leaves and levels through the code the
+    kernels run (no context, no device).  `items` as verify_batch -> (accepted, bad (count,) bool, n_checks, tree), tree =
+    None or (nodes (2, n_nodes, 2*fq_limbs) Montgomery limbs for P's and Q's tree, level by level with the leaves first,
+    is_infinity (2, n_nodes) bool, rho (2*count, 4) canonical words)."""
+    L = lib()
+    cid = curve_id(curve)
+    words = 8 if cid == CURVE_BN254 else 12
+    ins, trs, k, h, bh, keep = _verify_batch_args(cid, items, h_g2, beta_h_g2)
+    n_nodes = sum(verify_tree_levels(max(k, 1)))
+    ok, nbad, nchk = ctypes.c_int(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+    bad = np.zeros(max(k, 1), dtype=np.uint8)
+    nodes = np.zeros((2, n_nodes, words), dtype=np.uint64)
+    inf = (ctypes.c_int * (2 * n_nodes))()
+    rho = np.zeros((2 * max(k, 1), 4), dtype=np.uint64)
+    rc = L.zkt_debug_verify_locate_host(cid, ins, trs, k, u64p(h), u64p(bh), ctypes.byref(ok),
+                                        bad.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), ctypes.byref(nbad), ctypes.byref(nchk),
+                                        u64p(nodes) if want_tree else None, inf if want_tree else None,
+                                        u64p(rho) if want_tree else None)
+    if rc:
+        raise ZktError(rc, "zkt_debug_verify_locate_host")
+    assert nbad.value == int(bad.sum())
+    tree = (nodes, np.array([bool(x) for x in inf]).reshape(2, n_nodes), rho[:2 * k]) if want_tree else None
+    return bool(ok.value), bad[:k].astype(bool), nchk.value, tree
 
 
 class ProveInputs(ctypes.Structure):
@@ -1136,6 +1178,31 @@ class Context:
         ok = ctypes.c_int(0)
         self.check(self._L.zkt_verify_batch_dev(self._h, ins, trs, k, u64p(h), u64p(bh), ctypes.byref(ok)))
         return bool(ok.value)
+
+    def verify_batch_locate(self, items, h_g2, beta_h_g2):
+        """zkt_verify_batch_locate: `items` as _lib.verify_batch -> (accepted, bad, n_checks): whether every proof verifies,
+        a (count,) bool array naming the proofs that do not, and the pairing checks made (1 for an accepted batch, at most
+        1 + 2 * bad.sum() * ceil(log2(count)) otherwise).  The pairs of a rejected batch and their tree are formed on the
+        device, the tree is searched on the host."""
+        ins, trs, k, h, bh, keep = _verify_batch_args(self.curve, items, h_g2, beta_h_g2)
+        ok, nbad, nchk = ctypes.c_int(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+        bad = np.zeros(max(k, 1), dtype=np.uint8)
+        self.check(self._L.zkt_verify_batch_locate(self._h, ins, trs, k, u64p(h), u64p(bh), ctypes.byref(ok),
+                                                   bad.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), ctypes.byref(nbad),
+                                                   ctypes.byref(nchk)))
+        assert nbad.value == int(bad.sum())
+        return bool(ok.value), bad[:k].astype(bool), nchk.value
+
+    def debug_verify_batch_tree(self, items, h_g2, beta_h_g2):
+        """zkt_debug_verify_batch_tree: the pairs of every proof and their tree from the device, whatever the verdict ->
+        (nodes (2, n_nodes, 2*fq_limbs), is_infinity (2, n_nodes), rho (2*count, 4)) as _lib.debug_verify_locate_host."""
+        ins, trs, k, h, bh, keep = _verify_batch_args(self.curve, items, h_g2, beta_h_g2)
+        n_nodes = sum(verify_tree_levels(max(k, 1)))
+        nodes = np.zeros((2, n_nodes, 2 * self.fq_limbs), dtype=np.uint64)
+        inf = (ctypes.c_int * (2 * n_nodes))()
+        rho = np.zeros((2 * max(k, 1), 4), dtype=np.uint64)
+        self.check(self._L.zkt_debug_verify_batch_tree(self._h, ins, trs, k, u64p(h), u64p(bh), u64p(nodes), inf, u64p(rho)))
+        return nodes, np.array([bool(x) for x in inf]).reshape(2, n_nodes), rho[:2 * k]
 
     def msm_bases_info(self, n: int, montgomery: bool = True):
         """-> dict(window_bits, windows) that zkt_msm_g1_bases uses for n points"""

@@ -16,6 +16,7 @@
 #include "msm.hpp"
 #include "pairing.hpp"
 #include "transcript.hpp"
+#include "verify_leaves.hpp"
 
 #include <cstring>
 #include <map>
@@ -674,76 +675,66 @@ static int verify_batch_t(int curve_id, const zkt_verify_inputs* ins, zkt_transc
     return ZKT_OK;
 }
 
-// ---- zkt_verify_batch_dev: the batch above with its two per-proof costs on the device ------------------------------
-// Stage 1: the 13 k compressed commitments go up in one copy and through ONE k_g1_decompress launch (g1decomp.hip); the
-//          other bytes of a proof (length, Option::None, evaluations) are checked here.
-// Stage 2: Verifier::terms per proof, on the host: transcript, r0, the scalars of both openings -- no group arithmetic.
-// Stage 3: rho_0 = 1, rho_j = low 128 bits of Keccak-256(seed || j); the seed is hashed from everything that determines the
-//          pairs (L_j, W_j), which this route never forms (verify_batch_t hashes the pairs: other coefficients, the same
-//          soundness argument).
-// Stage 4: the 2 k term lists, scaled by their rho_j, are added up per point: inside a proof by source, across proofs for
-//          verifier-key points and g of equal CONTENT (a caller may pass one array or a copy per proof).
-// Stage 5: A = sum s_k P_k and B = sum rho_j W_j as two variable-base MSMs (msm_bases), canonical scalars.
-// The host keeps what is serial and small per proof (a Strobe / Keccak transcript and ~150 Fr products); the device takes
-// what is wide: 13 k square roots and subgroup checks, and a (<= 24 k)-point and a 2 k-point MSM.
+// What the stages leave behind for one batch.  zkt_verify_batch_locate reads the per-proof results again when the
+// batch is rejected: the leaves of its tree are made of them (verify_leaves.hpp).
 template <class C>
-static int verify_batch_prepare_dev_t(zkt_ctx* c, const zkt_verify_inputs* ins, zkt_transcript* const* trs, size_t k,
-                                      const uint64_t* h, const uint64_t* beta_h, uint64_t* out_ab, int* out_inf, uint64_t* out_rho) {
+struct BatchPrep {
+    using Q = typename C::Fq;
+    using F = Fe<typename C::Fr>;
+    std::vector<int> log_n;
+    std::vector<F> ev;                  // 12 evaluations per proof
+    std::vector<uint8_t> comp;          // 13 compressed commitments per proof
+    std::vector<Affine<Q>> cm;          // ... decompressed
+    std::vector<F> rho;                 // 2 per proof, Montgomery
+    std::vector<uint64_t> rho_c;        // ... as 4 canonical words: B's scalars, out_rho
+    std::vector<F> acc;                 // SRC_COUNT per proof, Montgomery: sum over both openings of rho * scalar, by source
+    std::vector<Affine<Q>> other;       // 11 per proof: the ten verifier-key points and g (sources SRC_VK ..)
+    size_t points_offset = 0, stage1_end = 0;   // device route: where verify_scratch holds cm, and where stage 1's region ends
+    size_t err_proof = 0;               // a refusal: the proof and the reason
+    std::string err_what;
+    int refuse(int rc, size_t i, const std::string& what) {
+        err_proof = i;
+        err_what = what;
+        return rc;
+    }
+    const Affine<Q>& base(size_t i, int s) const {
+        return s < Verifier<C>::SRC_VK ? cm[13 * i + s] : other[11 * i + (s - Verifier<C>::SRC_VK)];
+    }
+};
+
+// Stage 1, the host's half: lengths, the Option::None bytes, canonical evaluations; the compressed commitments are collected
+template <class C>
+static int batch_bytes(const zkt_verify_inputs* ins, zkt_transcript* const* trs, size_t k, BatchPrep<C>& bp) {
     using V = Verifier<C>;
+    const size_t nb = C::Fq::N * 4;
+    bp.log_n.resize(k);
+    bp.ev.resize(12 * k);
+    bp.comp.resize(13 * k * nb);
+    for (size_t i = 0; i < k; ++i) {
+        const zkt_verify_inputs& in = ins[i];
+        if (!trs[i] || !in.proof || !in.vk_commitments || !in.g || (in.n_pi && (!in.pi_roots || !in.pub_inputs)))
+            return bp.refuse(ZKT_ERR_INVALID_ARGUMENT, i, "null pointer");
+        int rc = V::shape(in, &bp.log_n[i]);
+        if (rc) return bp.refuse(rc, i, rc == ZKT_ERR_INVALID_DOMAIN_SIZE ? "n is not a supported power of two" : "wrong proof length");
+        if ((rc = V::parse(in, nullptr, &bp.ev[12 * i], true)))
+            return bp.refuse(rc, i, "malformed bytes (an Option that is not None, or an evaluation that is not canonical)");
+        size_t pos = 0;
+        for (int j = 0; j < 13; ++j) {
+            memcpy(bp.comp.data() + (13 * i + j) * nb, in.proof + pos, nb);
+            pos += nb + (j >= 11 ? 1 : 0);
+        }
+    }
+    return ZKT_OK;
+}
+
+// Stage 3: the seed (it depends on the inputs alone) and the 2 k coefficients
+template <class C>
+static void batch_coefficients(const zkt_verify_inputs* ins, size_t k, const uint64_t* h, const uint64_t* beta_h, BatchPrep<C>& bp) {
     using Q = typename C::Fq;
     using R = typename C::Fr;
     using F = Fe<R>;
     constexpr int L64 = Q::N / 2;
-    const size_t nb = Q::N * 4, npts = 13 * k;
-    static const char* const CM_NAME[13] = {"a", "b", "c", "t", "h1", "h2", "z1", "z2", "q_lo", "q_mid", "q_hi", "aw", "saw"};
-    auto fail = [&](int rc, size_t i, const std::string& what) {
-        return set_err(c, rc, "verify_batch_dev: proof " + std::to_string(i) + ": " + what);
-    };
-    // ---- stage 1 ----
-    std::vector<int> log_n(k);
-    std::vector<F> ev(12 * k);
-    std::vector<uint8_t> comp(npts * nb);
-    for (size_t i = 0; i < k; ++i) {
-        const zkt_verify_inputs& in = ins[i];
-        if (!trs[i] || !in.proof || !in.vk_commitments || !in.g || (in.n_pi && (!in.pi_roots || !in.pub_inputs)))
-            return fail(ZKT_ERR_INVALID_ARGUMENT, i, "null pointer");
-        int rc = V::shape(in, &log_n[i]);
-        if (rc) return fail(rc, i, rc == ZKT_ERR_INVALID_DOMAIN_SIZE ? "n is not a supported power of two" : "wrong proof length");
-        if ((rc = V::parse(in, nullptr, &ev[12 * i], true)))
-            return fail(rc, i, "malformed bytes (an Option that is not None, or an evaluation that is not canonical)");
-        size_t pos = 0;
-        for (int j = 0; j < 13; ++j) {
-            memcpy(comp.data() + (13 * i + j) * nb, in.proof + pos, nb);
-            pos += nb + (j >= 11 ? 1 : 0);
-        }
-    }
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t o_out = up(npts * nb), o_st = o_out + up(npts * 2 * nb);
-    int rc = ensure_buffer(c, &c->verify_scratch, &c->verify_scratch_bytes, o_st + up(npts));
-    if (rc) return rc;
-    char* const base = (char*)c->verify_scratch;
-    std::vector<Affine<Q>> cm(npts);
-    std::vector<uint8_t> status(npts);
-    {
-        ProfScope prof(c, "verify_decompress");
-        ZKT_HIP(c, hipMemcpyAsync(base, comp.data(), npts * nb, hipMemcpyHostToDevice, c->stream));
-        if ((rc = g1_decompress_enqueue(c, base, npts, base + o_out, base + o_st))) {
-            (void)hipStreamSynchronize(c->stream);
-            return rc;
-        }
-        ZKT_HIP(c, hipMemcpyAsync(cm.data(), base + o_out, npts * 2 * nb, hipMemcpyDeviceToHost, c->stream));
-        ZKT_HIP(c, hipMemcpyAsync(status.data(), base + o_st, npts, hipMemcpyDeviceToHost, c->stream));
-    }
-    ZKT_HIP(c, hipStreamSynchronize(c->stream));
-    for (size_t p = 0; p < npts; ++p)
-        if (status[p] > ZKT_G1_IDENTITY) {
-            static const char* const WHY[6] = {"", "", "x is not below the modulus", "both flag bits set", "not on the curve",
-                                               "outside the prime-order subgroup"};
-            return fail(ZKT_ERR_INVALID_ARGUMENT, p / 13,
-                        std::string("commitment ") + std::to_string(p % 13) + " (" + CM_NAME[p % 13] + ") refused: " +
-                            (status[p] < 6 ? WHY[status[p]] : "unknown status"));
-        }
-    // ---- stage 3's seed (hashed before the transcripts are consumed: it depends on the inputs alone) ----
+    const size_t nb = Q::N * 4;
     uint8_t seed[32];
     {
         std::vector<uint8_t> buf;
@@ -779,8 +770,8 @@ static int verify_batch_prepare_dev_t(zkt_ctx* c, const zkt_verify_inputs* ins, 
         keccak256(buf.data(), buf.size(), seed);
     }
     const size_t m = 2 * k;
-    std::vector<F> rho(m);          // Montgomery
-    std::vector<uint64_t> rho_c(4 * m, 0);   // canonical words: B's scalars, out_rho
+    bp.rho.resize(m);
+    bp.rho_c.assign(4 * m, 0);
     for (size_t j = 0; j < m; ++j) {
         F r = fe_zero<R>();
         if (j == 0) {
@@ -793,37 +784,114 @@ static int verify_batch_prepare_dev_t(zkt_ctx* c, const zkt_verify_inputs* ins, 
             keccak256(msg, sizeof msg, dg);
             memcpy(r.v, dg, 16);                       // 128 bits: below both scalar moduli
         }
-        memcpy(&rho_c[4 * j], r.v, 32);
-        rho[j] = fe_to_mont<R>(r);
+        memcpy(&bp.rho_c[4 * j], r.v, 32);
+        bp.rho[j] = fe_to_mont<R>(r);
     }
-    // ---- stages 2 and 4 ----
+}
+
+// Stage 2 and the per-proof half of stage 4: Verifier::terms, then both openings' scalars times their rho added up by source
+template <class C>
+static int batch_terms(const zkt_verify_inputs* ins, zkt_transcript* const* trs, size_t k, BatchPrep<C>& bp) {
+    using V = Verifier<C>;
+    using R = typename C::Fr;
+    bp.acc.resize(V::SRC_COUNT * k);
+    bp.other.resize(11 * k);
+    auto t = std::make_unique<typename V::Terms>();
+    for (size_t i = 0; i < k; ++i) {
+        if (int rc = V::terms(ins[i], bp.log_n[i], &bp.cm[13 * i], &bp.ev[12 * i], *trs[i]->impl, *t))
+            return bp.refuse(rc, i, rc == ZKT_ERR_EQUAL_CHALLENGES ? "two challenges are equal" : "a Lagrange denominator is zero");
+        Fe<R>* acc = &bp.acc[V::SRC_COUNT * i];
+        for (int s = 0; s < V::SRC_COUNT; ++s) acc[s] = fe_zero<R>();
+        for (int o = 0; o < 2; ++o) {
+            for (int q = 0; q < t->n[o]; ++q)
+                acc[t->src[o][q]] = fe_add<R>(acc[t->src[o][q]], fe_mul<R>(bp.rho[2 * i + o], t->sc[o][q]));
+            if (t->wit[o] != V::SRC_CM + VL_WITNESS0 + o) return bp.refuse(ZKT_ERR_INVALID_ARGUMENT, i, "unexpected witness source");
+        }
+        for (int s = V::SRC_VK; s < V::SRC_COUNT; ++s) bp.other[11 * i + (s - V::SRC_VK)] = t->base[s];
+    }
+    return ZKT_OK;
+}
+
+// ---- zkt_verify_batch_dev: the batch above with its two per-proof costs on the device ------------------------------
+// Stage 1: the 13 k compressed commitments go up in one copy and through ONE k_g1_decompress launch (g1decomp.hip); the
+//          other bytes of a proof (length, Option::None, evaluations) are checked here.
+// Stage 2: Verifier::terms per proof, on the host: transcript, r0, the scalars of both openings -- no group arithmetic.
+// Stage 3: rho_0 = 1, rho_j = low 128 bits of Keccak-256(seed || j); the seed is hashed from everything that determines the
+//          pairs (L_j, W_j), which this route never forms (verify_batch_t hashes the pairs: other coefficients, the same
+//          soundness argument).
+// Stage 4: the 2 k term lists, scaled by their rho_j, are added up per point: inside a proof by source, across proofs for
+//          verifier-key points and g of equal CONTENT (a caller may pass one array or a copy per proof).
+// Stage 5: A = sum s_k P_k and B = sum rho_j W_j as two variable-base MSMs (msm_bases), canonical scalars.
+// The host keeps what is serial and small per proof (a Strobe / Keccak transcript and ~150 Fr products); the device takes
+// what is wide: 13 k square roots and subgroup checks, and a (<= 24 k)-point and a 2 k-point MSM.
+// `who` names the entry point in an error; bp keeps the per-proof results (zkt_verify_batch_locate goes on from them).
+template <class C>
+static int batch_fold_dev(zkt_ctx* c, const char* who, const zkt_verify_inputs* ins, zkt_transcript* const* trs, size_t k,
+                          const uint64_t* h, const uint64_t* beta_h, BatchPrep<C>& bp, uint64_t* out_ab, int* out_inf) {
+    using V = Verifier<C>;
+    using Q = typename C::Fq;
+    using R = typename C::Fr;
+    using F = Fe<R>;
+    constexpr int L64 = Q::N / 2;
+    const size_t nb = Q::N * 4, npts = 13 * k;
+    static const char* const CM_NAME[13] = {"a", "b", "c", "t", "h1", "h2", "z1", "z2", "q_lo", "q_mid", "q_hi", "aw", "saw"};
+    auto fail = [&](int rc, size_t i, const std::string& what) {
+        return set_err(c, rc, std::string(who) + ": proof " + std::to_string(i) + ": " + what);
+    };
+    // ---- stage 1 ----
+    int rc = batch_bytes<C>(ins, trs, k, bp);
+    if (rc) return fail(rc, bp.err_proof, bp.err_what);
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t o_out = up(npts * nb), o_st = o_out + up(npts * 2 * nb);
+    bp.points_offset = o_out;
+    bp.stage1_end = o_st + up(npts);
+    if ((rc = ensure_buffer(c, &c->verify_scratch, &c->verify_scratch_bytes, bp.stage1_end))) return rc;
+    char* const base = (char*)c->verify_scratch;
+    bp.cm.resize(npts);
+    std::vector<uint8_t> status(npts);
+    {
+        ProfScope prof(c, "verify_decompress");
+        ZKT_HIP(c, hipMemcpyAsync(base, bp.comp.data(), npts * nb, hipMemcpyHostToDevice, c->stream));
+        if ((rc = g1_decompress_enqueue(c, base, npts, base + o_out, base + o_st))) {
+            (void)hipStreamSynchronize(c->stream);
+            return rc;
+        }
+        ZKT_HIP(c, hipMemcpyAsync(bp.cm.data(), base + o_out, npts * 2 * nb, hipMemcpyDeviceToHost, c->stream));
+        ZKT_HIP(c, hipMemcpyAsync(status.data(), base + o_st, npts, hipMemcpyDeviceToHost, c->stream));
+    }
+    ZKT_HIP(c, hipStreamSynchronize(c->stream));
+    for (size_t p = 0; p < npts; ++p)
+        if (status[p] > ZKT_G1_IDENTITY) {
+            static const char* const WHY[6] = {"", "", "x is not below the modulus", "both flag bits set", "not on the curve",
+                                               "outside the prime-order subgroup"};
+            return fail(ZKT_ERR_INVALID_ARGUMENT, p / 13,
+                        std::string("commitment ") + std::to_string(p % 13) + " (" + CM_NAME[p % 13] + ") refused: " +
+                            (status[p] < 6 ? WHY[status[p]] : "unknown status"));
+        }
+    // ---- stage 3 (before the transcripts are consumed), stage 2 and the per-proof sums of stage 4 ----
+    batch_coefficients<C>(ins, k, h, beta_h, bp);
+    if ((rc = batch_terms<C>(ins, trs, k, bp))) return fail(rc, bp.err_proof, bp.err_what);
+    // ---- stage 4 across proofs ----
+    const size_t m = 2 * k;
     std::vector<Affine<Q>> a_bases, b_bases(m);
     std::vector<F> a_acc;                              // Montgomery sums, one per entry of a_bases
     std::map<std::string, size_t> shared;              // verifier-key points and g, by content
     a_bases.reserve(V::SRC_COUNT * (k < 64 ? k : 64) + 13 * k);
-    auto t = std::make_unique<typename V::Terms>();
     for (size_t i = 0; i < k; ++i) {
-        if ((rc = V::terms(ins[i], log_n[i], &cm[13 * i], &ev[12 * i], *trs[i]->impl, *t)))
-            return fail(rc, i, rc == ZKT_ERR_EQUAL_CHALLENGES ? "two challenges are equal" : "a Lagrange denominator is zero");
-        F acc[V::SRC_COUNT];
-        for (int s = 0; s < V::SRC_COUNT; ++s) acc[s] = fe_zero<R>();
-        for (int o = 0; o < 2; ++o) {
-            for (int q = 0; q < t->n[o]; ++q)
-                acc[t->src[o][q]] = fe_add<R>(acc[t->src[o][q]], fe_mul<R>(rho[2 * i + o], t->sc[o][q]));
-            b_bases[2 * i + o] = t->base[t->wit[o]];
-        }
+        for (int o = 0; o < 2; ++o) b_bases[2 * i + o] = bp.cm[13 * i + VL_WITNESS0 + o];
         for (int s = 0; s < V::SRC_COUNT; ++s) {
-            const Affine<Q>& pt = t->base[s];
+            const Affine<Q>& pt = bp.base(i, s);
+            const F& sc = bp.acc[V::SRC_COUNT * i + s];
             if (aff_is_inf<Q>(pt)) continue;
             if (s >= V::SRC_VK) {
                 auto ins_ = shared.emplace(std::string((const char*)&pt, sizeof(pt)), a_bases.size());
                 if (!ins_.second) {
-                    a_acc[ins_.first->second] = fe_add<R>(a_acc[ins_.first->second], acc[s]);
+                    a_acc[ins_.first->second] = fe_add<R>(a_acc[ins_.first->second], sc);
                     continue;
                 }
             }
             a_bases.push_back(pt);
-            a_acc.push_back(acc[s]);
+            a_acc.push_back(sc);
         }
     }
     std::vector<uint64_t> a_sc(4 * a_bases.size());
@@ -836,25 +904,33 @@ static int verify_batch_prepare_dev_t(zkt_ctx* c, const zkt_verify_inputs* ins, 
     {
         ProfScope prof(c, "verify_msm");
         if ((rc = msm_bases(c, a_bases.data(), false, a_sc.data(), false, a_bases.size(), 0, out_ab, &inf[0])) ||
-            (rc = msm_bases(c, b_bases.data(), false, rho_c.data(), false, m, 0, out_ab + 2 * L64, &inf[1])))
+            (rc = msm_bases(c, b_bases.data(), false, bp.rho_c.data(), false, m, 0, out_ab + 2 * L64, &inf[1])))
             return rc;
     }
     if (out_inf) {
         out_inf[0] = inf[0];
         out_inf[1] = inf[1];
     }
-    if (out_rho) memcpy(out_rho, rho_c.data(), m * 32);
     return ZKT_OK;
 }
 
 template <class C>
-static int verify_batch_dev_t(zkt_ctx* c, const zkt_verify_inputs* ins, zkt_transcript* const* trs, size_t k, const uint64_t* h,
-                              const uint64_t* beta_h, int* accepted) {
+static int verify_batch_prepare_dev_t(zkt_ctx* c, const zkt_verify_inputs* ins, zkt_transcript* const* trs, size_t k,
+                                      const uint64_t* h, const uint64_t* beta_h, uint64_t* out_ab, int* out_inf, uint64_t* out_rho) {
+    BatchPrep<C> bp;
+    int rc = batch_fold_dev<C>(c, "verify_batch_dev", ins, trs, k, h, beta_h, bp, out_ab, out_inf);
+    if (rc) return rc;
+    if (out_rho) memcpy(out_rho, bp.rho_c.data(), 2 * k * 32);
+    return ZKT_OK;
+}
+
+// e(P, h) e(-Q, beta h) == 1 for P, Q as (x, y) Montgomery limbs: the check of a batch, of a tree node, of one proof
+template <class C>
+static int pair_check(const uint64_t* pq, const uint64_t* h, const uint64_t* beta_h, int* one) {
     using Q = typename C::Fq;
     constexpr int L64 = Q::N / 2;
     uint64_t g1[2 * 12], g2[2 * 4 * 6];
-    int rc = verify_batch_prepare_dev_t<C>(c, ins, trs, k, h, beta_h, g1, nullptr, nullptr);
-    if (rc) return rc;
+    memcpy(g1, pq, 4 * L64 * 8);
     Affine<Q> wc;
     memcpy(wc.x.v, g1 + 2 * L64, L64 * 8);
     memcpy(wc.y.v, g1 + 3 * L64, L64 * 8);
@@ -862,9 +938,302 @@ static int verify_batch_dev_t(zkt_ctx* c, const zkt_verify_inputs* ins, zkt_tran
     memcpy(g1 + 3 * L64, wc.y.v, L64 * 8);
     memcpy(g2, h, 4 * L64 * 8);
     memcpy(g2 + 4 * L64, beta_h, 4 * L64 * 8);
+    return pairing_check_t<C>(g1, g2, 2, one);
+}
+
+template <class C>
+static int verify_batch_dev_t(zkt_ctx* c, const zkt_verify_inputs* ins, zkt_transcript* const* trs, size_t k, const uint64_t* h,
+                              const uint64_t* beta_h, int* accepted) {
+    uint64_t ab[2 * 12];
+    int rc = verify_batch_prepare_dev_t<C>(c, ins, trs, k, h, beta_h, ab, nullptr, nullptr);
+    if (rc) return rc;
     int one = 0;
-    if ((rc = pairing_check_t<C>(g1, g2, 2, &one))) return set_err(c, rc, "verify_batch_dev: the pairing refused its arguments");
+    if ((rc = pair_check<C>(ab, h, beta_h, &one))) return set_err(c, rc, "verify_batch_dev: the pairing refused its arguments");
     *accepted = one ? 1 : 0;
+    return ZKT_OK;
+}
+
+// ---- zkt_verify_batch_locate: which proofs of a rejected batch are bad -----------------------------------------
+// The batch check is linear in the proofs: proof i has the pair (P_i, Q_i) of verify_leaves.hpp, which passes the check
+// iff the proof verifies, and (A, B) is the sum of all pairs.  A rejected batch gets its `count` pairs and their binary
+// tree of sums from the device, and the host walks down from the root at one pairing check per node it visits.
+template <class C>
+struct LocateTree {
+    using Q = typename C::Fq;
+    size_t count = 0, nodes = 0, sizes[VL_MAX_LEVELS], offs[VL_MAX_LEVELS];
+    int levels = 0;
+    std::vector<Xyzz<Q>> node;          // P's tree, then Q's; each level by level, leaves first
+    void shape(size_t k) {
+        count = k;
+        levels = vl_levels(k, sizes, offs, &nodes);
+        node.resize(2 * nodes);
+    }
+};
+
+// the canonical scalars of the leaves: SRC_COUNT per proof
+template <class C>
+static std::vector<uint64_t> leaf_scalars(const BatchPrep<C>& bp) {
+    using R = typename C::Fr;
+    std::vector<uint64_t> sc(4 * bp.acc.size());
+    for (size_t q = 0; q < bp.acc.size(); ++q) {
+        const Fe<R> s = fe_from_mont<R>(bp.acc[q]);
+        memcpy(&sc[4 * q], s.v, 32);
+    }
+    return sc;
+}
+
+// verify_scratch grown with its first `keep` bytes kept (stage 1's decompressed commitments are read again)
+static int verify_scratch_grow(zkt_ctx* c, size_t keep, size_t bytes) {
+    if (c->verify_scratch && c->verify_scratch_bytes >= bytes) return ZKT_OK;
+    void* p = nullptr;
+    int rc = dev_alloc(c, &p, bytes);
+    if (rc) return rc;
+    hipError_t e = hipMemcpyAsync(p, c->verify_scratch, keep, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        dev_free(c, p);
+        return hip_fail(c, e, "verify_scratch_grow");
+    }
+    dev_free(c, c->verify_scratch);
+    c->verify_scratch = p;
+    c->verify_scratch_bytes = bytes;
+    return ZKT_OK;
+}
+
+// Steps 3 and 4 on the device: the leaves from what batch_fold_dev left in verify_scratch and in bp, the levels, one download
+template <class C>
+static int locate_tree_dev(zkt_ctx* c, const BatchPrep<C>& bp, size_t k, LocateTree<C>& tree) {
+    using Q = typename C::Fq;
+    tree.shape(k);
+    const VlLayout lay = vl_layout(bp.stage1_end, k, Q::N * 4, vl_raw_bytes(c->curve));
+    int rc = verify_scratch_grow(c, bp.stage1_end, lay.end);
+    if (rc) return rc;
+    char* const base = (char*)c->verify_scratch;
+    const std::vector<uint64_t> sc = leaf_scalars<C>(bp);
+    // every step records its error and falls through to the one synchronise below: an upload may still be reading sc
+    auto copy = [&](void* dst, const void* src, size_t bytes, hipMemcpyKind kind, const char* what) {
+        if (rc) return;
+        const hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, c->stream);
+        if (e != hipSuccess) rc = hip_fail(c, e, what);
+    };
+    {
+        ProfScope prof(c, "verify_leaves");
+        copy(base + lay.other, bp.other.data(), bp.other.size() * sizeof(Affine<Q>), hipMemcpyHostToDevice, "verify leaves: bases upload");
+        copy(base + lay.scalars, sc.data(), sc.size() * 8, hipMemcpyHostToDevice, "verify leaves: scalars upload");
+        copy(base + lay.rho, bp.rho_c.data(), bp.rho_c.size() * 8, hipMemcpyHostToDevice, "verify leaves: coefficients upload");
+        if (!rc)
+            rc = verify_leaves_enqueue(c, base + bp.points_offset, base + lay.other, base + lay.scalars, base + lay.rho, k,
+                                       base + lay.products, base + lay.tree, tree.nodes);
+    }
+    if (!rc) {
+        ProfScope prof(c, "verify_tree");
+        rc = verify_tree_enqueue(c, base + lay.tree, k, tree.nodes);
+        copy(tree.node.data(), base + lay.tree, tree.node.size() * sizeof(Xyzz<Q>), hipMemcpyDeviceToHost, "verify tree download");
+    }
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    if (!rc && e != hipSuccess) rc = hip_fail(c, e, "verify tree");
+    return rc;
+}
+
+// ... and on the host, through the same per-term, per-leaf and per-node code
+template <class C>
+static void locate_tree_host(const BatchPrep<C>& bp, size_t k, LocateTree<C>& tree) {
+    using Q = typename C::Fq;
+    using V = Verifier<C>;
+    tree.shape(k);
+    const std::vector<uint64_t> sc = leaf_scalars<C>(bp);
+    auto words = [](const uint64_t* w, uint32_t (&out)[8]) { memcpy(out, w, 32); };
+    for (size_t i = 0; i < k; ++i) {
+        XyzzX<Q> prod[VL_TERMS];
+        uint32_t kw[8];
+        for (int s = 0; s < VL_SOURCES; ++s) {
+            words(&sc[4 * (V::SRC_COUNT * i + s)], kw);
+            prod[s] = vl_mul<Q>(bp.base(i, s), kw);
+        }
+        for (int o = 0; o < 2; ++o) {
+            words(&bp.rho_c[4 * (2 * i + o)], kw);
+            prod[VL_SOURCES + o] = vl_mul<Q>(bp.cm[13 * i + VL_WITNESS0 + o], kw);
+        }
+        tree.node[i] = vl_pack<Q>(vl_sum<Q>(VL_SOURCES, [&](int t) { return prod[t]; }));
+        tree.node[tree.nodes + i] = vl_pack<Q>(vl_sum<Q>(2, [&](int t) { return prod[VL_SOURCES + t]; }));
+    }
+    for (int half = 0; half < 2; ++half)
+        for (int l = 0; l + 1 < tree.levels; ++l) {
+            const Xyzz<Q>* src = &tree.node[half * tree.nodes + tree.offs[l]];
+            Xyzz<Q>* dst = &tree.node[half * tree.nodes + tree.offs[l + 1]];
+            for (size_t m = 0; m < tree.sizes[l + 1]; ++m)
+                dst[m] = 2 * m + 1 < tree.sizes[l] ? vl_parent<Q>(src[2 * m], src[2 * m + 1]) : src[2 * m];
+        }
+}
+
+// Step 5: the root is known to fail.  At a failing inner node the left child is checked; if it passes, the right one
+// fails without a check, otherwise the right one is checked too: at most 2 ceil(log2 count) checks per bad proof.
+template <class C>
+static int locate_descend(const LocateTree<C>& tree, const uint64_t* h, const uint64_t* beta_h, std::vector<uint8_t>& bad,
+                          size_t* n_checks) {
+    using Q = typename C::Fq;
+    constexpr int L64 = Q::N / 2;
+    bad.assign(tree.count, 0);
+    auto passes = [&](int l, size_t m, bool* ok) {
+        uint64_t pq[4 * 6];
+        for (int half = 0; half < 2; ++half) {
+            const Affine<Q> a = xyzz_to_affine_host<Q>(tree.node[half * tree.nodes + tree.offs[l] + m]);
+            memcpy(pq + half * 2 * L64, a.x.v, L64 * 8);
+            memcpy(pq + half * 2 * L64 + L64, a.y.v, L64 * 8);
+        }
+        int one = 0;
+        int rc = pair_check<C>(pq, h, beta_h, &one);
+        ++*n_checks;
+        *ok = one != 0;
+        return rc;
+    };
+    std::vector<std::pair<int, size_t>> failing{{tree.levels - 1, 0}};
+    while (!failing.empty()) {
+        const int l = failing.back().first;
+        const size_t m = failing.back().second;
+        failing.pop_back();
+        if (l == 0) {
+            bad[m] = 1;
+            continue;
+        }
+        if (2 * m + 1 >= tree.sizes[l - 1]) {             // the unpaired node moved up unchanged
+            failing.push_back({l - 1, 2 * m});
+            continue;
+        }
+        bool left = false, right = false;
+        if (int rc = passes(l - 1, 2 * m, &left)) return rc;
+        if (!left) {
+            failing.push_back({l - 1, 2 * m});
+            if (int rc = passes(l - 1, 2 * m + 1, &right)) return rc;
+        }
+        if (!right) failing.push_back({l - 1, 2 * m + 1});
+    }
+    return ZKT_OK;
+}
+
+// every node as affine (x, y), one field inversion for all of them (Montgomery's trick)
+template <class C>
+static void tree_affine(const LocateTree<C>& tree, uint64_t* out_xy, int* out_inf) {
+    using Q = typename C::Fq;
+    constexpr int L64 = Q::N / 2;
+    const size_t n = tree.node.size();
+    std::vector<Fe<Q>> pre(n + 1);
+    pre[0] = fe_one<Q>();
+    for (size_t i = 0; i < n; ++i) {
+        const Xyzz<Q>& p = tree.node[i];
+        pre[i + 1] = xyzz_is_identity<Q>(p) ? pre[i] : fe_mul<Q>(pre[i], fe_mul<Q>(p.zz, p.zzz));
+    }
+    Fe<Q> inv = fe_inv_host<Q>(pre[n]);
+    for (size_t i = n; i-- > 0;) {
+        const Xyzz<Q>& p = tree.node[i];
+        Affine<Q> a;
+        a.x = fe_zero<Q>();
+        a.y = fe_zero<Q>();
+        const bool is_inf = xyzz_is_identity<Q>(p);
+        if (!is_inf) {
+            const Fe<Q> d = fe_mul<Q>(inv, pre[i]);       // 1 / (zz zzz)
+            inv = fe_mul<Q>(inv, fe_mul<Q>(p.zz, p.zzz));
+            a.x = fe_mul<Q>(p.x, fe_mul<Q>(d, p.zzz));    // X / ZZ
+            a.y = fe_mul<Q>(p.y, fe_mul<Q>(d, p.zz));     // Y / ZZZ
+        }
+        if (out_xy) {
+            memcpy(out_xy + i * 2 * L64, a.x.v, L64 * 8);
+            memcpy(out_xy + i * 2 * L64 + L64, a.y.v, L64 * 8);
+        }
+        if (out_inf) out_inf[i] = is_inf ? 1 : 0;
+    }
+}
+
+// The verdict from the root's check on: *accepted, out_bad, the two counters (none of them touched on an error).
+// build_tree() fills `tree` when the root fails; it is not called for an accepted batch.  *pairing_refused: the error is a
+// pairing check's, not build_tree's.
+template <class C, class BuildTree>
+static int locate_finish(const uint64_t* root, size_t k, const uint64_t* h, const uint64_t* beta_h, const LocateTree<C>& tree,
+                         BuildTree build_tree, int* accepted, uint8_t* out_bad, size_t* n_bad, size_t* n_checks,
+                         bool* pairing_refused) {
+    int one = 0;
+    *pairing_refused = true;
+    int rc = pair_check<C>(root, h, beta_h, &one);
+    if (rc) return rc;
+    size_t checks = 1, b = 0;
+    std::vector<uint8_t> bad(k, 0);
+    if (!one) {
+        *pairing_refused = false;
+        if ((rc = build_tree())) return rc;
+        *pairing_refused = true;
+        if ((rc = locate_descend<C>(tree, h, beta_h, bad, &checks))) return rc;
+        for (size_t i = 0; i < k; ++i) b += bad[i];
+    }
+    *accepted = one ? 1 : 0;
+    memcpy(out_bad, bad.data(), k);
+    if (n_bad) *n_bad = b;
+    if (n_checks) *n_checks = checks;
+    return ZKT_OK;
+}
+
+template <class C>
+static int verify_batch_locate_t(zkt_ctx* c, const zkt_verify_inputs* ins, zkt_transcript* const* trs, size_t k,
+                                 const uint64_t* h, const uint64_t* beta_h, int* accepted, uint8_t* out_bad, size_t* n_bad,
+                                 size_t* n_checks) {
+    BatchPrep<C> bp;
+    uint64_t ab[2 * 12];
+    int rc = batch_fold_dev<C>(c, "verify_batch_locate", ins, trs, k, h, beta_h, bp, ab, nullptr);
+    if (rc) return rc;
+    LocateTree<C> tree;
+    bool pairing_refused = false;
+    rc = locate_finish<C>(ab, k, h, beta_h, tree, [&] { return locate_tree_dev<C>(c, bp, k, tree); }, accepted, out_bad, n_bad,
+                          n_checks, &pairing_refused);
+    if (rc && pairing_refused) return set_err(c, rc, "verify_batch_locate: the pairing refused its arguments");
+    return rc;
+}
+
+template <class C>
+static int debug_verify_batch_tree_t(zkt_ctx* c, const zkt_verify_inputs* ins, zkt_transcript* const* trs, size_t k,
+                                     const uint64_t* h, const uint64_t* beta_h, uint64_t* out_nodes, int* out_inf, uint64_t* out_rho) {
+    BatchPrep<C> bp;
+    uint64_t ab[2 * 12];
+    int rc = batch_fold_dev<C>(c, "debug_verify_batch_tree", ins, trs, k, h, beta_h, bp, ab, nullptr);
+    if (rc) return rc;
+    LocateTree<C> tree;
+    if ((rc = locate_tree_dev<C>(c, bp, k, tree))) return rc;
+    tree_affine<C>(tree, out_nodes, out_inf);
+    if (out_rho) memcpy(out_rho, bp.rho_c.data(), 2 * k * 32);
+    return ZKT_OK;
+}
+
+// The whole of zkt_verify_batch_locate without a device: the host's own deserialisation for stage 1, the root from the
+// tree, and leaves and levels through the code the kernels run
+template <class C>
+static int debug_verify_locate_host_t(const zkt_verify_inputs* ins, zkt_transcript* const* trs, size_t k, const uint64_t* h,
+                                      const uint64_t* beta_h, int* accepted, uint8_t* out_bad, size_t* n_bad, size_t* n_checks,
+                                      uint64_t* out_nodes, int* out_inf, uint64_t* out_rho) {
+    using Q = typename C::Fq;
+    constexpr int L64 = Q::N / 2;
+    const size_t nb = Q::N * 4;
+    BatchPrep<C> bp;
+    int rc = batch_bytes<C>(ins, trs, k, bp);
+    if (rc) return rc;
+    bp.cm.resize(13 * k);
+    for (size_t p = 0; p < 13 * k; ++p) {
+        bool inf = false;
+        if (!decompress<C>(bp.comp.data() + p * nb, &bp.cm[p], &inf)) return ZKT_ERR_INVALID_ARGUMENT;
+    }
+    batch_coefficients<C>(ins, k, h, beta_h, bp);
+    if ((rc = batch_terms<C>(ins, trs, k, bp))) return rc;
+    LocateTree<C> tree;
+    locate_tree_host<C>(bp, k, tree);
+    uint64_t root[4 * 6];
+    for (int half = 0; half < 2; ++half) {
+        const Affine<Q> a = xyzz_to_affine_host<Q>(tree.node[half * tree.nodes + tree.nodes - 1]);
+        memcpy(root + half * 2 * L64, a.x.v, L64 * 8);
+        memcpy(root + half * 2 * L64 + L64, a.y.v, L64 * 8);
+    }
+    bool pairing_refused = false;
+    if ((rc = locate_finish<C>(root, k, h, beta_h, tree, [] { return (int)ZKT_OK; }, accepted, out_bad, n_bad, n_checks,
+                               &pairing_refused)))
+        return rc;
+    if (out_nodes || out_inf) tree_affine<C>(tree, out_nodes, out_inf);
+    if (out_rho) memcpy(out_rho, bp.rho_c.data(), 2 * k * 32);
     return ZKT_OK;
 }
 
@@ -896,6 +1265,45 @@ extern "C" int zkt_verify_batch_dev(zkt_ctx* c, const zkt_verify_inputs* ins, zk
     if (c->curve == ZKT_CURVE_BN254)
         return verify_batch_dev_t<Bn254Curve>(c, ins, transcripts, count, h_g2_mont, beta_h_g2_mont, accepted);
     return verify_batch_dev_t<Bls381Curve>(c, ins, transcripts, count, h_g2_mont, beta_h_g2_mont, accepted);
+}
+
+extern "C" int zkt_verify_batch_locate(zkt_ctx* c, const zkt_verify_inputs* ins, zkt_transcript* const* transcripts,
+                                       size_t count, const uint64_t* h_g2_mont, const uint64_t* beta_h_g2_mont,
+                                       int* accepted, uint8_t* out_bad, size_t* n_bad, size_t* n_checks) {
+    if (int rc = verify_batch_dev_args(c, ins, transcripts, count, h_g2_mont, beta_h_g2_mont, accepted)) return rc;
+    if (!out_bad) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
+    if (c->curve == ZKT_CURVE_BN254)
+        return verify_batch_locate_t<Bn254Curve>(c, ins, transcripts, count, h_g2_mont, beta_h_g2_mont, accepted, out_bad,
+                                                 n_bad, n_checks);
+    return verify_batch_locate_t<Bls381Curve>(c, ins, transcripts, count, h_g2_mont, beta_h_g2_mont, accepted, out_bad, n_bad,
+                                              n_checks);
+}
+
+extern "C" int zkt_debug_verify_batch_tree(zkt_ctx* c, const zkt_verify_inputs* ins, zkt_transcript* const* transcripts,
+                                           size_t count, const uint64_t* h_g2_mont, const uint64_t* beta_h_g2_mont,
+                                           uint64_t* out_nodes_xy_mont, int* out_is_infinity, uint64_t* out_rho) {
+    if (int rc = verify_batch_dev_args(c, ins, transcripts, count, h_g2_mont, beta_h_g2_mont, out_nodes_xy_mont)) return rc;
+    if (c->curve == ZKT_CURVE_BN254)
+        return debug_verify_batch_tree_t<Bn254Curve>(c, ins, transcripts, count, h_g2_mont, beta_h_g2_mont, out_nodes_xy_mont,
+                                                     out_is_infinity, out_rho);
+    return debug_verify_batch_tree_t<Bls381Curve>(c, ins, transcripts, count, h_g2_mont, beta_h_g2_mont, out_nodes_xy_mont,
+                                                  out_is_infinity, out_rho);
+}
+
+extern "C" int zkt_debug_verify_locate_host(int curve_id, const zkt_verify_inputs* ins, zkt_transcript* const* transcripts,
+                                            size_t count, const uint64_t* h_g2_mont, const uint64_t* beta_h_g2_mont,
+                                            int* accepted, uint8_t* out_bad, size_t* n_bad, size_t* n_checks,
+                                            uint64_t* out_nodes_xy_mont, int* out_is_infinity, uint64_t* out_rho) {
+    if (!ins || !transcripts || count == 0 || count > ZKT_VERIFY_BATCH_DEV_MAX || !h_g2_mont || !beta_h_g2_mont || !accepted ||
+        !out_bad)
+        return ZKT_ERR_INVALID_ARGUMENT;
+    if (curve_id == ZKT_CURVE_BN254)
+        return debug_verify_locate_host_t<Bn254Curve>(ins, transcripts, count, h_g2_mont, beta_h_g2_mont, accepted, out_bad,
+                                                      n_bad, n_checks, out_nodes_xy_mont, out_is_infinity, out_rho);
+    if (curve_id == ZKT_CURVE_BLS12_381)
+        return debug_verify_locate_host_t<Bls381Curve>(ins, transcripts, count, h_g2_mont, beta_h_g2_mont, accepted, out_bad,
+                                                       n_bad, n_checks, out_nodes_xy_mont, out_is_infinity, out_rho);
+    return ZKT_ERR_INVALID_ARGUMENT;
 }
 
 // ---- the G2 half of the test / bench SRS (zkt_srs_generate is the G1 half): h = the G2 generator of ark-bn254 /
