@@ -192,7 +192,8 @@ int zkt_domain_group_gen(zkt_ctx* ctx, int log_n, uint64_t* out4);
  * enough.  Replaces nothing at run time: it is the device-resident form of `ck`.
  * _dev: the powers already in HBM, read behind the work already on the context's stream.  Both forms release the
  * previous key and allocate the new tables, which waits for the device: unlike the other _dev entries this one is no
- * enqueue.  Synchronises the stream. */
+ * enqueue.  Synchronises the stream.  The points are taken as they come, unchecked (as the reference's CLI reads them): for a
+ * key from outside, zkt_srs_check validates it first. */
 int zkt_srs_load(zkt_ctx* ctx, const uint64_t* g1_xy_mont, size_t count);
 int zkt_srs_load_dev(zkt_ctx* ctx, const void* d_g1_xy_mont, size_t count);
 /* Test/bench SRS with a KNOWN trapdoor: powers_of_g[i] = tau^i * G (tau: 4 canonical limbs).
@@ -233,7 +234,7 @@ int zkt_msm_info(zkt_ctx* ctx, int* window_bits, int* windows, size_t* srs_count
  * as full integers: every bit counts, values >= r included (for a point of the prime-order subgroup the result is then
  * sum (s_i mod r) P_i).  Bases may repeat, appear negated, be the identity or carry a zero scalar.  Bases are NOT checked
  * for being on the curve or in the subgroup (as arkworks does not); an invalid point gives an unspecified point, never a
- * fault.  Result: affine, host memory, (0,0) and *out_is_infinity = 1 for the identity (out_is_infinity may be NULL).
+ * fault.  (zkt_g1_check tests them.)  Result: affine, host memory, (0,0) and *out_is_infinity = 1 for the identity (out_is_infinity may be NULL).
  * n = 0 -> the identity; 1 <= n <= ZKT_MSM_BASES_MAX on either curve; a larger n -> ZKT_ERR_INVALID_ARGUMENT, a failed
  * allocation -> ZKT_ERR_HIP.  Needs no SRS: the call works on any context (with or without a key, forked, between proofs)
  * and leaves the loaded SRS, Lagrange-basis table, circuit and the prover's MSM buffers untouched; its scratch memory is
@@ -824,6 +825,71 @@ enum {
 };
 int zkt_g1_decompress(zkt_ctx* ctx, const uint8_t* compressed, size_t n, uint64_t* out_xy_mont, uint8_t* out_status);
 int zkt_g1_decompress_dev(zkt_ctx* ctx, const void* d_compressed, size_t n, void* d_out_xy_mont, void* d_out_status);
+
+/* zkt_g1_check: the per-point test of zkt_g1_decompress for n UNCOMPRESSED G1 points, one thread per point
+ * (csrc/g1check.hip): what a committer key is made of before zkt_srs_load sees it.  points_xy_mont: n x (x, y) as arkworks Montgomery limbs, the layout zkt_srs_load and
+ * zkt_msm_g1_bases take (8 u64 per point on BN254, 12 on BLS12-381), (0,0) = the identity; host memory, or with
+ * points_on_device = 1 device memory, 16-byte aligned (else ZKT_ERR_INVALID_ARGUMENT), read behind the work already on the
+ * context's stream (rule 1 of zkt_ctx_set_stream).  out_status: host, one byte per point, the first that applies of
+ *   ZKT_G1_NOT_CANONICAL      the raw limbs of x or of y are >= q
+ *   ZKT_G1_IDENTITY           the point is (0,0)
+ *   ZKT_G1_NOT_ON_CURVE       y^2 != x^3 + b
+ *   ZKT_G1_NOT_IN_SUBGROUP    on the curve, outside the prime-order subgroup (BLS12-381 only)
+ *   ZKT_G1_VALID              otherwise
+ * (ZKT_G1_BOTH_FLAGS never occurs: there are no flags).  The points may come from anyone: a refusal is a status, never an
+ * error code or a fault.  n = 0 -> ZKT_OK, nothing touched; any n is taken (in pieces of ZKT_MSM_BASES_MAX points); a failed
+ * allocation -> ZKT_ERR_HIP.  Needs no SRS and no circuit, works on any context (forked, with a communicator: local, no
+ * collective); its scratch memory is that of zkt_srs_check.  Synchronises the stream.
+ * zkt_debug_g1_check_host: the same function run on the host (one source text for both), no context, no device. */
+int zkt_g1_check(zkt_ctx* ctx, const void* points_xy_mont, size_t n, int points_on_device, uint8_t* out_status);
+int zkt_debug_g1_check_host(int curve_id, const uint64_t* points, size_t n, uint8_t* out_status);
+
+/* zkt_srs_check: is g1_xy_mont[0 .. count) the powers_of_g of the KZG key whose VerifierKey holds h and beta_h -- is there a tau with
+ * P_i = tau^i P_0 for every i and beta_h = tau h?  For a key file before zkt_srs_load (which takes the points as they come,
+ * as the reference's deserialize_unchecked does): corrupted, truncated and mixed-up keys are named here instead of failing
+ * every proof later.  Two tests, both on the device (csrc/g1check.hip):
+ *   points     every P_i gets its zkt_g1_check status; any status but ZKT_G1_VALID is bad (the identity too: tau^i g never
+ *              is).  The report counts them and names the first; out_status (host, count bytes, may be NULL) receives
+ *              all of them.
+ *   structure  only when every point is valid (a combination of invalid points means nothing).  rho = seed32 read as a
+ *              little-endian integer, reduced mod r; with S = sum_(i < count) rho^i P_i, one device MSM, the key is accepted
+ *              iff e(rho S - rho^count P_(count-1), beta_h) e(P_0 - S, h) == 1, which is sum_i rho^i (P_(i+1) - tau P_i) = 0
+ *              in one pairing equation.  A key with the wrong structure passes for at most count values of rho: with
+ *              probability at most count / r (below 2^-229 at ZKT_SRS_CHECK_MAX) when the seed is drawn after the key
+ *              is fixed.  The CALLER draws the seed, 32 random bytes; the library holds no randomness.  A seed that reduces
+ *              to rho = 0 -> ZKT_ERR_INVALID_ARGUMENT.  count = 1 has nothing to relate: structure_ok = 1, S = P_0.
+ * h, beta_h: G2, arkworks' Fp2 layout as zkt_verify takes them; they are trusted (off the twist -> ZKT_ERR_INVALID_ARGUMENT).
+ * 1 <= count <= ZKT_SRS_CHECK_MAX = 2^24 + 1 (the reference's 4n + 1 powers at n = 2^22), else ZKT_ERR_INVALID_ARGUMENT.
+ * points_on_device as zkt_g1_check: with the key in HBM one upload serves this call and zkt_srs_load_dev.  The points go
+ * through in chunks of at most ZKT_MSM_BASES_MAX: upload (host points), statuses, their reduction, and -- while no point
+ * has been bad -- the powers of rho and the MSM of zkt_msm_g1_bases over the chunk; the chunk sums are added on the host,
+ * which finishes with two short scalar multiplications and zkt_pairing_product_is_one.  After the first bad point the later
+ * chunks still get statuses and counts, and no MSM.  Scratch: that of zkt_msm_g1_bases plus one chunk of points and status
+ * bytes, and that call's rules hold: any context (no key needed, forked, between proofs), the loaded SRS, Lagrange-basis
+ * table, circuit and an announced proof untouched, local on a context with a communicator.  Profile scopes
+ * "srs_check_points" and "srs_check_msm".  Synchronises the stream.
+ * zkt_debug_srs_check_chunk: the chunk size of this context's later calls (tests reach chunk boundaries at small sizes);
+ * 0 restores ZKT_MSM_BASES_MAX, more than that -> ZKT_ERR_INVALID_ARGUMENT.
+ * zkt_debug_srs_check_finish_host: the host's end alone, no context: S (ignored when S_inf), P_0, P_(count-1) affine
+ * Montgomery limbs, rho as four canonical words (non-zero) -> *structure_ok.  S is taken for granted. */
+#define ZKT_SRS_CHECK_MAX (((size_t)1 << 24) + 1)
+typedef struct {
+    uint64_t count, n_bad, first_bad;      /* first_bad = index of the first point whose status is not VALID (count if none) */
+    uint64_t by_status[6];                 /* how many points got each ZKT_G1_* status */
+    int first_bad_status;
+    int points_ok;                         /* n_bad == 0 (an identity among the powers is bad: tau^i g is never the identity) */
+    int structure_checked;                 /* 0 when !points_ok (the combination of invalid points means nothing) */
+    int structure_ok;
+    int ok;                                /* points_ok && structure_ok */
+    uint64_t sum_xy_mont[12];              /* S, affine ((0,0) when sum_is_infinity), when structure_checked */
+    int sum_is_infinity;
+} zkt_srs_report;
+int zkt_srs_check(zkt_ctx* ctx, const void* g1_xy_mont, size_t count, int points_on_device, const uint64_t* h_g2_mont,
+                  const uint64_t* beta_h_g2_mont, const uint8_t seed32[32], uint8_t* out_status, zkt_srs_report* report);
+int zkt_debug_srs_check_chunk(zkt_ctx* ctx, size_t max_points);
+int zkt_debug_srs_check_finish_host(int curve_id, const uint64_t* S, int S_inf, const uint64_t* P0, const uint64_t* Plast,
+                                    uint64_t count, const uint64_t* rho_canonical4, const uint64_t* h, const uint64_t* beta_h,
+                                    int* structure_ok);
 
 /* zkt_verify_batch with the two costs that grow with `count` moved to the device (csrc/verify.hip): the 13 * count
  * compressed commitments are decompressed and checked in ONE zkt_g1_decompress launch, and the 2 * count folded openings

@@ -62,6 +62,22 @@ pub struct ZktWitnessReport {
     pub first_wiring_column: c_int,
 }
 
+/// zkt_srs_report: what zkt_srs_check found in a committer key (per-point statuses, then the structure test)
+#[repr(C)]
+pub struct ZktSrsReport {
+    pub count: u64,
+    pub n_bad: u64,
+    pub first_bad: u64,
+    pub by_status: [u64; 6],
+    pub first_bad_status: c_int,
+    pub points_ok: c_int,
+    pub structure_checked: c_int,
+    pub structure_ok: c_int,
+    pub ok: c_int,
+    pub sum_xy_mont: [u64; 12],
+    pub sum_is_infinity: c_int,
+}
+
 pub const ZKT_CHECK_WIRING: c_int = 1;
 pub const ZKT_CHECK_NONE: u64 = u64::MAX;
 pub const ZKT_VARIABLE_ZERO: u32 = 0xFFFF_FFFF;
@@ -140,6 +156,9 @@ extern "C" {
     pub fn zkt_g1_decompress(ctx: *mut ZktCtx, compressed: *const u8, n: usize, out_xy_mont: *mut u64, out_status: *mut u8) -> c_int;
     pub fn zkt_g1_decompress_dev(ctx: *mut ZktCtx, d_compressed: *const c_void, n: usize, d_out_xy_mont: *mut c_void,
                                  d_out_status: *mut c_void) -> c_int;
+    pub fn zkt_g1_check(ctx: *mut ZktCtx, points_xy_mont: *const c_void, n: usize, points_on_device: c_int, out_status: *mut u8) -> c_int;
+    pub fn zkt_srs_check(ctx: *mut ZktCtx, g1_xy_mont: *const c_void, count: usize, points_on_device: c_int, h_g2_mont: *const u64,
+                         beta_h_g2_mont: *const u64, seed32: *const u8, out_status: *mut u8, report: *mut ZktSrsReport) -> c_int;
     pub fn zkt_poseidon_load(ctx: *mut ZktCtx, params: *const ZktPoseidonParams, out: *mut *mut c_void) -> c_int;
     pub fn zkt_poseidon_free(ctx: *mut ZktCtx, params: *mut c_void);
     pub fn zkt_poseidon_hash_batch_dev(ctx: *mut ZktCtx, params: *const c_void, d_inputs: *const c_void, batch: usize,

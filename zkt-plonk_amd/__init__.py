@@ -20,7 +20,7 @@ importing works without a GPU (so the C-ABI can be inspected), creating a ``Cont
 """
 from ._lib import (  # noqa: F401
     Context, ZktError, Transcript, lib, lib_path, CURVE_BN254, CURVE_BLS12_381, curve_id, declared_symbols,
-    WitnessCheck, WitnessReport, CHECK_WIRING, CHECK_NONE,
+    WitnessCheck, WitnessReport, CHECK_WIRING, CHECK_NONE, SrsCheck, SrsReport,
 )
 from .domain import GpuDomain  # noqa: F401
 from .prover import GpuProver, GpuKZG10, seed_transcript, PK_ORDER, NUM_BLINDERS  # noqa: F401
@@ -29,4 +29,4 @@ from .merkle import MerkleTree  # noqa: F401
 
 __all__ = ["Context", "ZktError", "Transcript", "GpuDomain", "GpuProver", "GpuKZG10", "PoseidonGadget", "MerkleTree", "seed_transcript", "PK_ORDER",
            "NUM_BLINDERS", "lib", "lib_path", "CURVE_BN254", "CURVE_BLS12_381", "curve_id", "declared_symbols",
-           "WitnessCheck", "WitnessReport", "CHECK_WIRING", "CHECK_NONE"]
+           "WitnessCheck", "WitnessReport", "CHECK_WIRING", "CHECK_NONE", "SrsCheck", "SrsReport"]

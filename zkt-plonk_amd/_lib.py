@@ -142,12 +142,92 @@ def _bind_optional(L):
         L.zkt_debug_verify_batch_tree.argtypes = [vp, vi, tp, ctypes.c_size_t, u64p, u64p, u64p, ip, u64p]
         L.zkt_debug_verify_locate_host.argtypes = [ctypes.c_int, vi, tp, ctypes.c_size_t, u64p, u64p, ip, u8p, szp, szp,
                                                    u64p, ip, u64p]
+    if hasattr(L, "zkt_srs_check"):
+        u8p = ctypes.POINTER(ctypes.c_uint8)
+        L.zkt_g1_check.argtypes = [vp, vp, ctypes.c_size_t, ctypes.c_int, u8p]
+        L.zkt_debug_g1_check_host.argtypes = [ctypes.c_int, u64p, ctypes.c_size_t, u8p]
+        L.zkt_srs_check.argtypes = [vp, vp, ctypes.c_size_t, ctypes.c_int, u64p, u64p, u8p, u8p, ctypes.POINTER(SrsReport)]
+        L.zkt_debug_srs_check_chunk.argtypes = [vp, ctypes.c_size_t]
+        L.zkt_debug_srs_check_finish_host.argtypes = [ctypes.c_int, u64p, ctypes.c_int, u64p, u64p, ctypes.c_uint64, u64p, u64p,
+                                                      u64p, ip]
     if hasattr(L, "zkt_kzg_commit_batch"):
         pp, szp = ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)
         L.zkt_kzg_commit_batch.argtypes = [vp, pp, szp, ctypes.c_int, ctypes.c_int, u64p, ip]
         L.zkt_kzg_commit_batch_dev.argtypes = [vp, pp, szp, ctypes.c_int, ctypes.c_int, u64p, ip]
         L.zkt_kzg_open.argtypes = [vp, pp, szp, ctypes.c_int, u64p, u64p, u64p, ip, u64p]
         L.zkt_kzg_open_dev.argtypes = [vp, pp, szp, ctypes.c_int, u64p, u64p, u64p, ip, u64p]
+
+
+SRS_CHECK_MAX = (1 << 24) + 1   # ZKT_SRS_CHECK_MAX: most points one zkt_srs_check takes
+
+
+class SrsReport(ctypes.Structure):
+    """zkt_srs_report (include/zkt_plonk.h), field for field."""
+    _fields_ = [("count", ctypes.c_uint64), ("n_bad", ctypes.c_uint64), ("first_bad", ctypes.c_uint64),
+                ("by_status", ctypes.c_uint64 * 6), ("first_bad_status", ctypes.c_int), ("points_ok", ctypes.c_int),
+                ("structure_checked", ctypes.c_int), ("structure_ok", ctypes.c_int), ("ok", ctypes.c_int),
+                ("sum_xy_mont", ctypes.c_uint64 * 12), ("sum_is_infinity", ctypes.c_int)]
+
+
+class SrsCheck:
+    """What zkt_srs_check found: the report's fields as plain values; `sum` = (S as (2*fq_limbs,) Montgomery limbs,
+    is_infinity) when the structure was checked, else None; `status` the per-point bytes when they were asked for."""
+
+    def __init__(self, r: SrsReport, fq_limbs: int, status=None):
+        self.count, self.n_bad, self.first_bad = int(r.count), int(r.n_bad), int(r.first_bad)
+        self.by_status = [int(v) for v in r.by_status]
+        self.first_bad_status = int(r.first_bad_status)
+        self.points_ok, self.structure_checked = bool(r.points_ok), bool(r.structure_checked)
+        self.structure_ok, self.ok = bool(r.structure_ok), bool(r.ok)
+        self.sum = ((np.array(list(r.sum_xy_mont)[:2 * fq_limbs], dtype=np.uint64), bool(r.sum_is_infinity))
+                    if r.structure_checked else None)
+        self.status = status
+
+    def __bool__(self):
+        return self.ok
+
+    def __repr__(self):
+        return ("SrsCheck(ok=%s, count=%d, n_bad=%d, first_bad=%d status %d, structure_checked=%s, structure_ok=%s)"
+                % (self.ok, self.count, self.n_bad, self.first_bad, self.first_bad_status, self.structure_checked, self.structure_ok))
+
+
+def _seed32(seed) -> bytes:
+    seed = seed.to_bytes(32, "little") if isinstance(seed, int) else bytes(seed)
+    if len(seed) != 32:
+        raise ValueError("srs_check: the seed is 32 bytes")
+    return seed
+
+
+def debug_g1_check_host(curve, points) -> np.ndarray:
+    """zkt_debug_g1_check_host: the per-point rules of zkt_g1_check on the host (no device) -> status (n,) uint8."""
+    L = lib()
+    cid = curve_id(curve)
+    words = 8 if cid == CURVE_BN254 else 12
+    pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, words)
+    status = np.zeros(pts.shape[0], dtype=np.uint8)
+    rc = L.zkt_debug_g1_check_host(cid, u64p(pts) if pts.size else None, pts.shape[0],
+                                   status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)))
+    if rc:
+        raise ZktError(rc, "zkt_debug_g1_check_host")
+    return status
+
+
+def debug_srs_check_finish_host(curve, S, S_inf: bool, P0, Plast, count: int, rho: int, h_g2, beta_h_g2) -> bool:
+    """zkt_debug_srs_check_finish_host: the host's end of zkt_srs_check's structure test (no device).  S, P0, Plast:
+    (2*fq_limbs,) Montgomery limbs; rho: the challenge as an integer below r -> structure_ok."""
+    L = lib()
+    cid = curve_id(curve)
+    words = 8 if cid == CURVE_BN254 else 12
+    arr = lambda a, n: np.ascontiguousarray(a, dtype=np.uint64).reshape(n)
+    S, P0, Plast = arr(S, words), arr(P0, words), arr(Plast, words)
+    h, bh = arr(h_g2, 2 * words), arr(beta_h_g2, 2 * words)
+    r4 = np.array([(int(rho) >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)], dtype=np.uint64)
+    ok = ctypes.c_int(0)
+    rc = L.zkt_debug_srs_check_finish_host(cid, u64p(S), int(bool(S_inf)), u64p(P0), u64p(Plast), count, u64p(r4), u64p(h),
+                                           u64p(bh), ctypes.byref(ok))
+    if rc:
+        raise ZktError(rc, "zkt_debug_srs_check_finish_host")
+    return bool(ok.value)
 
 
 class MerklePathArgs(ctypes.Structure):
@@ -1158,6 +1238,42 @@ class Context:
         """zkt_g1_decompress_dev: n x nb bytes in HBM -> n points and n status bytes in HBM; only enqueues."""
         self.check(self._L.zkt_g1_decompress_dev(self._h, ctypes.c_void_p(d_in), n, ctypes.c_void_p(d_out),
                                                  ctypes.c_void_p(d_status)))
+
+    # ---- an untrusted committer key: per-point validation and the structure test on the device ----
+    def _check_points(self, points, n):
+        """(pointer, count, on_device, keep) of a host array of points, or of a device pointer with its count n"""
+        if isinstance(points, int):
+            if n is None:
+                raise ValueError("a device pointer needs its point count")
+            return ctypes.c_void_p(points), int(n), 1, None
+        pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 2 * self.fq_limbs)
+        return ctypes.c_void_p(pts.ctypes.data if pts.size else None), pts.shape[0], 0, pts
+
+    def g1_check(self, points, n: int = None) -> np.ndarray:
+        """zkt_g1_check: `points` = a (n, 2*fq_limbs) array of (x, y) Montgomery limbs, or a device pointer (int) to n such
+        points -> status (n,) uint8, one ZKT_G1_* value per point.  Synchronises the stream."""
+        ptr, n, on_dev, keep = self._check_points(points, n)
+        status = np.zeros(n, dtype=np.uint8)
+        self.check(self._L.zkt_g1_check(self._h, ptr, n, on_dev, status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
+        return status
+
+    def srs_check(self, points, h_g2, beta_h_g2, seed, n: int = None, want_status: bool = False) -> SrsCheck:
+        """zkt_srs_check: are `points` (array or device pointer, as g1_check) the powers_of_g of the key whose VerifierKey
+        holds h and beta_h?  seed: 32 bytes (or an integer below 2^256) the caller drew at random -> SrsCheck."""
+        ptr, n, on_dev, keep = self._check_points(points, n)
+        h = np.ascontiguousarray(h_g2, dtype=np.uint64).reshape(4 * self.fq_limbs)
+        bh = np.ascontiguousarray(beta_h_g2, dtype=np.uint64).reshape(4 * self.fq_limbs)
+        seed = (ctypes.c_uint8 * 32)(*_seed32(seed))
+        status = np.zeros(max(n, 1), dtype=np.uint8) if want_status else None
+        rep = SrsReport()
+        self.check(self._L.zkt_srs_check(self._h, ptr, n, on_dev, u64p(h), u64p(bh), seed,
+                                         status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)) if want_status else None,
+                                         ctypes.byref(rep)))
+        return SrsCheck(rep, self.fq_limbs, status[:n] if want_status else None)
+
+    def debug_srs_check_chunk(self, max_points: int):
+        """zkt_debug_srs_check_chunk: points per chunk of this context's later srs_check calls; 0 restores the default."""
+        self.check(self._L.zkt_debug_srs_check_chunk(self._h, max_points))
 
     def verify_batch_prepare_dev(self, items, h_g2, beta_h_g2, want_rho: bool = True):
         """zkt_verify_batch_prepare_dev: `items` as _lib.verify_batch -> (A, B) as a (2, 2*fq_limbs) array of Montgomery limbs,

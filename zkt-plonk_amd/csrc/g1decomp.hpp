@@ -142,6 +142,29 @@ ZKT_HD uint32_t g1d_point(Fe<typename C::Fq> xw, const Fx<typename C::Fq>& beta,
     return ZKT_G1_VALID;
 }
 
+// One UNCOMPRESSED point (zkt_g1_check, g1check.hip): the raw words of x and y as zkt_srs_load takes them (arkworks'
+// Montgomery limbs, (0, 0) = the identity) -> status, the first that applies of NOT_CANONICAL, IDENTITY, NOT_ON_CURVE,
+// NOT_IN_SUBGROUP (BLS12-381), VALID.  No square root: y is given.  beta as in g1d_point.  Host and device run the same code.
+template <class C>
+ZKT_HD uint32_t g1c_point(const Fe<typename C::Fq>& xw, const Fe<typename C::Fq>& yw, const Fx<typename C::Fq>& beta) {
+    using Q = typename C::Fq;
+    static_assert(32 * Q::N <= 29 * FxP<Q>::L, "raw words fit the limbs");
+    const Fx<Q> xi = fx_unpack<Q>(xw), yi = fx_unpack<Q>(yw);                // normalised; any words: < 2^(32 N) <= 2^(29 L)
+    if (fx_geq_p<Q>(xi) || fx_geq_p<Q>(yi)) return ZKT_G1_NOT_CANONICAL;
+    if (fx_is_zero_canon<Q>(xi) && fx_is_zero_canon<Q>(yi)) return ZKT_G1_IDENTITY;
+    // the curve equation holds in one Montgomery form as in another; R' is the one fx_mul and g1d_in_subgroup work in
+    const Fx<Q> x = fx_cond_sub_p<Q>(fx_mul<Q>(xi, fx_const_from_ark<Q>()));   // q * q; < 2q -> canonical, R' form
+    const Fx<Q> y = fx_cond_sub_p<Q>(fx_mul<Q>(yi, fx_const_from_ark<Q>()));   // the same
+    Fx<Q> rhs = fx_mul<Q>(fx_mul<Q>(x, x), x);                               // q * q, 2q * q; < 2q
+#pragma unroll
+    for (uint32_t k = 0; k < C::B; ++k) rhs = fx_add<Q>(rhs, fx_one<Q>());   // b <= 4: < 6q
+    if (!fx_eq_limbs<Q>(fx_cond_sub_p<Q>(fx_mul<Q>(y, y)), fx_canon<Q>(rhs))) return ZKT_G1_NOT_ON_CURVE;   // q * q; < 2q
+    if constexpr (C::ID == 1) {
+        if (!g1d_in_subgroup<Q>(x, y, beta)) return ZKT_G1_NOT_IN_SUBGROUP;  // x, y < q, on the curve, not the identity
+    }
+    return ZKT_G1_VALID;
+}
+
 // beta = 2^((q - 1) / 3) in R' form, canonical (host, once per process)
 template <class Q>
 inline Fx<Q> g1d_beta() {

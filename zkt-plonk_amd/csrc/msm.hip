@@ -1928,6 +1928,11 @@ int msm_bases(zkt_ctx* c, const void* bases, bool bases_on_device, const void* s
     return msm_bases_t<Bls381Curve>(c, bases, bases_on_device, scalars, scalars_on_device, n, mont, out_xy, out_inf);
 }
 
+int msm_bases_scratch(zkt_ctx* c, MsmBasesState** out) {
+    if (c->curve == ZKT_CURVE_BN254) return msm_bases_state<Bn254Curve>(c, out);
+    return msm_bases_state<Bls381Curve>(c, out);
+}
+
 void msm_info(zkt_ctx* c, int* cbits, int* windows, size_t* count) {
     if (!c->msm) {
         *cbits = 0; *windows = 0; *count = 0;

@@ -176,7 +176,8 @@ struct MsmBasesState {
     DevBuf scalars;   // zkt_msm_g1_bases: the uploaded scalars
     DevBuf vals, pairs, bin_offs, bin_aux, bin_start, tile_start, tile_desc, cnt2, pos2, chunk_bucket;   // grouping
     DevBuf offsets, heavy, params, pieces, buckets, rowcol;                                              // accumulation, tail
-    void* partials = nullptr;       // pinned: W x (c) rows of partial sums the host combines (Horner over the windows)
+    DevBuf check_points, check_status;   // zkt_g1_check / zkt_srs_check (g1check.hip): a chunk uploaded from the host; totals and status bytes
+    void* partials = nullptr;      // pinned: W x (c) rows of partial sums the host combines (Horner over the windows)
     void* partials_dev = nullptr;
     size_t acc_lds = 0, acc_threads = 0;   // as MsmState's
     ~MsmBasesState() {
@@ -204,6 +205,8 @@ int msm_g1_dev(zkt_ctx* c, const void* d_scalars, size_t n, size_t base_off, int
 // host memory; n <= ZKT_MSM_BASES_MAX is checked here.  Synchronises the stream.
 int msm_bases(zkt_ctx* c, const void* bases, bool bases_on_device, const void* scalars, bool scalars_on_device, size_t n, int mont,
               uint64_t* out_xy, int* out_inf);
+// the context's MsmBasesState, made on first use (g1check.hip keeps its chunk buffers and the powers of rho there)
+int msm_bases_scratch(zkt_ctx* c, MsmBasesState** out);
 // prover-facing batch form: begin up to MsmState::SLOTS commitments, then collect them (tbl = 1: the Lagrange-prefix
 // table of lagrange.hip, tbl = MSM_TBL_WIRE + k: the base table of wire k)
 int msm_begin(zkt_ctx* c, const void* d_scalars, size_t n, size_t base_off, int mont, int slot, int tbl = 0);
