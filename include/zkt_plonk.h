@@ -350,7 +350,7 @@ int zkt_ctx_set_wire_elimination(zkt_ctx* ctx, int mode);
  * above 3n + 5, is refused through the verifier's identity at xi instead (r(xi) against the constant of compute_r0), with
  * the same code, ZKT_ERR_QUOTIENT_TOO_SHORT.  Costs [3][n] class copies of the twelve coset tables (36 n elements of
  * device memory, made by the first proof that takes the route; forks made afterwards share them).
- * zkt_ctx_set_quotient_route(ctx, mode): 0 = automatic (the default): three classes for single-GPU circuits of 2^20 rows
+ * zkt_ctx_set_quotient_route(ctx, mode): 0 = automatic (the default): three classes for single-GPU circuits of 2^18 rows
  * and more, 1 = three classes, 2 = the whole coset.  A sharded context always uses the whole coset (each GPU its class).
  * Forks inherit the mode. */
 int zkt_ctx_set_quotient_route(zkt_ctx* ctx, int mode);
@@ -359,9 +359,13 @@ int zkt_ctx_set_quotient_route(zkt_ctx* ctx, int mode);
  * by xi^i; r(xi) of the three-classes route is the total of the division's suffix sums minus the evaluations the host
  * holds, not a second evaluation; the scan's block prefixes are added by the kernel that scales by xi^-(j+1).  Round 3:
  * each grand product is one kernel that forms the terms and scans them within blocks, the scan of the block totals,
- * and one kernel that applies prefixes and inverted total.  Blinding: one launch per batch of polynomials finds the
- * trimmed lengths and places the blinders.  The proof bytes, the error codes and the trimmed-length slots are the same
- * in every mode.
+ * and one kernel that applies prefixes and inverted total (the four scans of the block totals of both grand products are
+ * one launch where each is a single block).  Blinding: one launch per batch of polynomials finds the trimmed lengths and
+ * places the blinders.  Round 4 on the three-classes route: the three class transforms of a batch are one launch per
+ * pass and the quotient kernel one launch (the class is a dimension of the grid), and one closing pass turns the three
+ * inverse transforms into the quotient's 4n coefficients and its three chunks (the combination, the split and the zeros
+ * above 3n + 5, which are then not scanned).  The proof bytes, the error codes and the trimmed-length slots are the
+ * same in every mode.
  * zkt_ctx_set_fused_passes(ctx, mode): 0 = automatic (the default: fused), 1 = fused, 2 = one launch per step, the
  * sequence the fused one is tested against.  zkt_debug_grand_products follows the mode.  Sharded contexts honour it like
  * any other context.  Forks inherit the mode. */

@@ -5,8 +5,9 @@ f = glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True)[0]
 rows = [r for r in csv.DictReader(open(f))]
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 # a proof starts with the first k_ntt/k_msm after the witness copy; the anchor is the split of the quotient, which every
-# proof launches once on either quotient route (k_quotient itself runs three times on the classes route)
-anchors = [i for i, r in enumerate(rows) if "k_quot_split" in r["Kernel_Name"]]
+# proof launches once on either quotient route (k_quotient itself may run three times on the classes route); the closing
+# pass of the classes route (k_classes_close) does the split itself
+anchors = [i for i, r in enumerate(rows) if "k_quot_split" in r["Kernel_Name"] or "k_classes_close" in r["Kernel_Name"]]
 if len(anchors) < 3:
     sys.exit("need >= 3 proofs in the trace")
 # which pair of consecutive proofs: k-th from the end (bench.py: warm-up, the timed proofs, then a profiling pass with every

@@ -1709,7 +1709,7 @@ class Context:
         return out
 
     def set_quotient_route(self, mode: int = 0):
-        """zkt_ctx_set_quotient_route: 0 automatic (three classes for single-GPU circuits of 2^20 rows and more), 1 the
+        """zkt_ctx_set_quotient_route: 0 automatic (three classes for single-GPU circuits of 2^18 rows and more), 1 the
         quotient on three classes of the 4n coset, 2 on the whole coset"""
         self._L.zkt_ctx_set_quotient_route.argtypes = [ctypes.c_void_p, ctypes.c_int]
         self.check(self._L.zkt_ctx_set_quotient_route(self._h, int(mode)))

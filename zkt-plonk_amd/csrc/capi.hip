@@ -209,7 +209,7 @@ int zkt_ctx_create(int curve_id, int device_id, zkt_ctx** out) {
     zkt_ctx* c = new zkt_ctx();
     c->batch_off = exp_env("ZKT_MSM_NO_BATCH") != nullptr;
     c->aux_off = exp_env("ZKT_NO_AUX") != nullptr;
-    if (const char* parts = exp_env("ZKT_FUSED_PARTS")) c->fused_parts = atoi(parts) & 7;
+    if (const char* parts = exp_env("ZKT_FUSED_PARTS")) c->fused_parts = atoi(parts) & 63;
     c->curve = curve_id;
     c->device = device_id;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {

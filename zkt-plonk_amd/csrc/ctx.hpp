@@ -86,9 +86,11 @@ struct zkt_ctx {
     int wire_elim_mode = 1;        // zkt_ctx_set_wire_elimination: 0 off, 1 automatic (large circuits), 2 whenever a table can be built
     int quotient_route = 0;        // zkt_ctx_set_quotient_route: 0 automatic (three classes on large single-GPU circuits), 1 three classes, 2 the whole coset
     int fused_passes = 0;          // zkt_ctx_set_fused_passes: 0 automatic (fused), 1 fused, 2 one launch per step (the reference sequence)
-    // the parts of the fused sequences, one bit each: 1 = round 5's openings, 2 = round 3's grand products, 4 = blinding
+    // the parts of the fused sequences, one bit each: 1 = round 5's openings, 2 = round 3's grand products, 4 = blinding,
+    // 8 = the classes route's three classes in one grid (transforms and quotient kernel), 16 = its closing pass (combine,
+    // split and the tail's zeros in one kernel), 32 = round 3's four scans of the block totals in one launch
     // (A/B builds: ZKT_FUSED_PARTS picks the parts that modes 0 and 1 fuse)
-    int fused_parts = 7;
+    int fused_parts = 63;
     bool fused(int part) const { return fused_passes != 2 && (fused_parts & part); }
     std::shared_ptr<zkt::CircuitState> circuit;
     std::vector<void*> owned;  // every hipMalloc made on behalf of this ctx
@@ -155,6 +157,11 @@ int ntt_run_batch(zkt_ctx* c, int log_n, int inverse, int coset, int nb, const v
 // heads of nb polynomials of n + NTT_HEAD coefficients folded modulo X^n - gammas[j], j < 3 (host, 8 words each), into
 // d_out[(j * NTT_MAX_BATCH + y) * NTT_HEAD + i]: what ntt_run_batch takes as d_head for class j
 int ntt_fold_heads(zkt_ctx* c, int nb, const void* const* d_in, size_t n, const uint32_t* gammas, void* d_out);
+// ntt_run_batch for the three cosets `codes` at once, one launch per pass (the grid's z = class): class j reads
+// d_in[y] + j * in_stride and writes d_out[y] + j * out_stride (strides in elements; in_stride = 0 shares the inputs).  In
+// place as ntt_run_batch allows, the ranges of different (y, j) disjoint.  d_head: the whole output of ntt_fold_heads.
+int ntt_run_classes(zkt_ctx* c, int log_n, int inverse, const int codes[3], int nb, const void* const* d_in, const size_t* in_len,
+                    void* const* d_out, size_t in_stride, size_t out_stride, const void* d_head = nullptr);
 int ntt_class_code(int log_big, int cls);
 // zkt_debug_ntt_split: npass = 0 restores the policy; transforms above 2^10 built afterwards use the given radices
 int ntt_force_split(zkt_ctx* c, int npass, const int* log_r);

@@ -588,6 +588,97 @@ ZKT_HD Fx<P> fx_mul2_inl(const Fx<P>& a, const Fx<P>& b, const Fx<P>& c, const F
 #endif
 }
 
+#if defined(__HIP_DEVICE_COMPILE__)
+// fx_mont_column for three operand products per term: column COL of (a * b + c * d + e * f) / R'
+template <class P, int COL>
+__device__ __forceinline__ void fx_mont_column3(uint64_t& acc, uint32_t* m, Fx<P>& r, const uint32_t* a, const uint32_t* b,
+                                                const uint32_t* c, const uint32_t* d, const uint32_t* e, const uint32_t* f) {
+    constexpr int L = FxP<P>::L;
+    constexpr int lo = COL < L ? 0 : COL - L + 1, hi = COL < L ? COL : L - 1;     // i + j = COL, both below L
+    constexpr int nv = 3 * (hi - lo + 1);
+    constexpr int skip = COL == 0 ? 1 : 0;                                         // a0 * b0 started the accumulator
+    uint32_t x[nv], y[nv];
+    int n = 0;
+#pragma unroll
+    for (int i = lo; i <= hi; ++i) {
+        const int j = COL - i;
+        x[n] = a[i]; y[n] = b[j]; ++n;
+        x[n] = c[i]; y[n] = d[j]; ++n;
+        x[n] = e[i]; y[n] = f[j]; ++n;
+    }
+    fx_mad_rows<nv - skip, false>(acc, x + skip, y + skip);
+    constexpr int rlo = lo, rhi = COL < L ? COL - 1 : L - 1;                        // m[i] * p[COL - i], COL - i >= 1
+    constexpr int nk = rhi - rlo + 1;
+    if constexpr (nk > 0) {
+        uint32_t xm[nk], yk[nk];
+#pragma unroll
+        for (int t = 0; t < nk; ++t) {
+            xm[t] = m[rlo + t];
+            yk[t] = FxP<P>::mod(COL - rlo - t);
+        }
+        fx_mad_rows<nk, true>(acc, xm, yk);
+    }
+    if constexpr (COL < L) {
+        m[COL] = ((uint32_t)acc * FxP<P>::INV) & FxP<P>::MASK;
+        const uint32_t p0 = FxP<P>::mod(0);
+        MadRow<1>::vk(acc, &m[COL], &p0);
+    } else {
+        r.l[COL - L] = (uint32_t)acc & FxP<P>::MASK;
+    }
+    acc >>= 29;
+}
+template <class P, int... COLS>
+__device__ __forceinline__ Fx<P> fx_mont_chain3_seq(const Fx<P>& a, const Fx<P>& b, const Fx<P>& c, const Fx<P>& d, const Fx<P>& e,
+                                                    const Fx<P>& f, std::integer_sequence<int, COLS...>) {
+    constexpr int L = FxP<P>::L;
+    uint32_t m[L];
+    Fx<P> r;
+    uint64_t acc = fx_mad0(a.l[0], b.l[0]);
+    (fx_mont_column3<P, COLS>(acc, m, r, a.l, b.l, c.l, d.l, e.l, f.l), ...);
+    r.l[L - 1] = (uint32_t)acc;
+    return r;
+}
+#endif
+
+// (a * b + c * d + e * f) / R' with one reduction: 4 L^2 multiply-adds instead of 6 L^2.
+// Needs a * b + c * d + e * f < R' * p and limbs < 2^29; returns normalised limbs, value < 2p.
+// (A column sums at most 3 L operand products and L reduction products, each below 2^58, and a carry below 2^35:
+// under 2^64 for L <= 14.  The result is (sum + m p) / R' with m < R': below p + p.)
+template <class P>
+ZKT_HD Fx<P> fx_mul3_inl(const Fx<P>& a, const Fx<P>& b, const Fx<P>& c, const Fx<P>& d, const Fx<P>& e, const Fx<P>& f) {
+    static_assert(4 * FxP<P>::L < 64, "a column of fx_mul3_inl must fit 64 bits");
+#if defined(__HIP_DEVICE_COMPILE__)
+    return fx_mont_chain3_seq<P>(a, b, c, d, e, f, std::make_integer_sequence<int, 2 * FxP<P>::L - 1>());
+#else
+    constexpr int L = FxP<P>::L;
+    uint32_t m[L];
+    Fx<P> r;
+    uint64_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < 2 * L - 1; ++k) {
+#pragma unroll
+        for (int i = 0; i < L; ++i) {
+            const int j = k - i;
+            if (j >= 0 && j < L) {
+                acc += (uint64_t)a.l[i] * b.l[j];
+                acc += (uint64_t)c.l[i] * d.l[j];
+                acc += (uint64_t)e.l[i] * f.l[j];
+                if (i < k && (k < L || i > k - L)) acc += (uint64_t)m[i] * FxP<P>::mod(j);
+            }
+        }
+        if (k < L) {
+            m[k] = ((uint32_t)acc * FxP<P>::INV) & FxP<P>::MASK;
+            acc += (uint64_t)m[k] * FxP<P>::mod(0);
+        } else {
+            r.l[k - L] = (uint32_t)acc & FxP<P>::MASK;
+        }
+        acc >>= 29;
+    }
+    r.l[L - 1] = (uint32_t)acc;
+    return r;
+#endif
+}
+
 template <class P>
 ZKT_MUL typename FxVec<P>::type fx_mul_raw(typename FxVec<P>::type a, typename FxVec<P>::type b) {
     constexpr int L = FxP<P>::L;

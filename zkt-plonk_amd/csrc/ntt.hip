@@ -177,14 +177,18 @@ __global__ __launch_bounds__(NTT_THREADS, (LOG_R <= 7 ? 4 : 3)) void k_ntt_pass(
     const void* in_p = py == 0 ? a.in[0] : py == 1 ? a.in[1] : py == 2 ? a.in[2] : a.in[3];
     void* out_p = py == 0 ? a.out[0] : py == 1 ? a.out[1] : py == 2 ? a.out[2] : a.out[3];
     const uint64_t in_len = py == 0 ? a.in_len[0] : py == 1 ? a.in_len[1] : py == 2 ? a.in_len[2] : a.in_len[3];
-    if (a.in_raw) in_p = reinterpret_cast<const char*>(a.in[0]) + (uint64_t)py * 36u * a.raw_n;
-    if (a.out_raw) out_p = reinterpret_cast<char*>(a.out[0]) + (uint64_t)py * 36u * a.raw_n;
+    // blockIdx.z = class (uniform as well): the coset's own tables, its outputs (and inputs, where they differ) cls_* further on
+    const uint32_t pz = blockIdx.z;
+    const uint64_t plane = (uint64_t)(pz * gridDim.y + py) * 36u * a.raw_n;
+    in_p = a.in_raw ? reinterpret_cast<const char*>(a.in[0]) + plane : reinterpret_cast<const char*>(in_p) + pz * a.cls_in;
+    out_p = a.out_raw ? reinterpret_cast<char*>(a.out[0]) + plane : reinterpret_cast<char*>(out_p) + pz * a.cls_out;
     const Fe<P>* in = reinterpret_cast<const Fe<P>*>(in_p);
     Fe<P>* out = reinterpret_cast<Fe<P>*>(out_p);
     const Fe<P>* w_inner = reinterpret_cast<const Fe<P>*>(a.w_inner);
-    const Fe<P>* in_row = reinterpret_cast<const Fe<P>*>(a.in_row);
-    const Fe<P>* tw = reinterpret_cast<const Fe<P>*>(a.tw);
-    const Fe<P>* out_row = reinterpret_cast<const Fe<P>*>(a.out_row);
+    const Fe<P>* in_row = reinterpret_cast<const Fe<P>*>(pz == 0 ? a.in_row[0] : pz == 1 ? a.in_row[1] : a.in_row[2]);
+    const Fe<P>* tw = reinterpret_cast<const Fe<P>*>(pz == 0 ? a.tw[0] : pz == 1 ? a.tw[1] : a.tw[2]);
+    const Fe<P>* out_row = reinterpret_cast<const Fe<P>*>(pz == 0 ? a.out_row[0] : pz == 1 ? a.out_row[1] : a.out_row[2]);
+    const Fe<P>* head = reinterpret_cast<const Fe<P>*>(a.head) + (pz * NTT_MAX_BATCH + py) * NTT_HEAD;
 
     for (int i = tid; i < R / 2; i += NTT_THREADS) {
         if constexpr (SHOUP) {   // six planes of R/2 entries: w (lo, hi, top), then wq
@@ -250,7 +254,7 @@ __global__ __launch_bounds__(NTT_THREADS, (LOG_R <= 7 ? 4 : 3)) void k_ntt_pass(
             x = tile_get<P>(rlo, rlo + a.raw_n, reinterpret_cast<const uint32_t*>(rlo + 2 * a.raw_n), (int64_t)g);
         } else {
             const Fe<P>* src = in + g;
-            if (a.head && g < NTT_HEAD) src = reinterpret_cast<const Fe<P>*>(a.head) + py * NTT_HEAD + g;
+            if (a.head && g < NTT_HEAD) src = head + g;
             x = (g < in_len) ? fx_unpack<P>(fe_load<P>(src)) : fx_zero<P>();
         }
         // the prover's coset transforms are fed n + 8 coefficients on a domain of 4n: three rows in four are padding,
@@ -313,14 +317,25 @@ __global__ void k_table_to_shoup(const Fe<P>* t, void* out, uint64_t n, Fx<P> np
     tile_put<P>(ql, ql + n, reinterpret_cast<uint32_t*>(ql + 2 * n), (int64_t)i, wq);
 }
 
-// Whole transform in one workgroup for n <= 1024 (plumbing sizes; not a performance path).
+// Whole transform in one workgroup for n <= 1024 (plumbing sizes; not a performance path).  blockIdx.z = class, as in
+// k_ntt_pass: the coset's own scales, in and out cls_in / cls_out elements further on, the heads of the next class.
+struct NttSmallCls {
+    const void* in_scale[NTT_MAX_CLS];
+    const void* out_scale[NTT_MAX_CLS];
+    uint64_t cls_in, cls_out;
+};
 template <class P>
 __global__ __launch_bounds__(NTT_THREADS) void k_ntt_small(const Fe<P>* in, uint64_t in_len, Fe<P>* out, int log_n,
-                                                           const Fe<P>* w, const Fe<P>* in_scale,
-                                                           const Fe<P>* out_scale, const Fe<P>* head) {
+                                                           const Fe<P>* w, NttSmallCls k, const Fe<P>* head) {
     __shared__ Fe<P> buf[TILE];
     const int n = 1 << log_n;
     const int tid = threadIdx.x;
+    const uint32_t pz = blockIdx.z;
+    const Fe<P>* in_scale = reinterpret_cast<const Fe<P>*>(pz == 0 ? k.in_scale[0] : pz == 1 ? k.in_scale[1] : k.in_scale[2]);
+    const Fe<P>* out_scale = reinterpret_cast<const Fe<P>*>(pz == 0 ? k.out_scale[0] : pz == 1 ? k.out_scale[1] : k.out_scale[2]);
+    in += pz * k.cls_in;
+    out += pz * k.cls_out;
+    if (head) head += pz * NTT_MAX_BATCH * NTT_HEAD;
     for (int i = tid; i < n; i += NTT_THREADS) {
         Fe<P> x = ((uint64_t)i < in_len) ? fe_load<P>(head && i < NTT_HEAD ? head + i : in + i) : fe_zero<P>();
         if (in_scale) x = fe_mul<P>(x, fe_load<P>(in_scale + i));
@@ -647,8 +662,8 @@ static void launch_pass_r(zkt_ctx* c, const dim3& grid, const NttPassArgs& a) {
 }
 
 template <class P, bool LAST>
-static void launch_pass(zkt_ctx* c, int log_r, unsigned blocks, unsigned nb, const NttPassArgs& a) {
-    const dim3 grid(blocks, nb);
+static void launch_pass(zkt_ctx* c, int log_r, unsigned blocks, unsigned nb, unsigned ncls, const NttPassArgs& a) {
+    const dim3 grid(blocks, nb, ncls);
     switch (log_r) {
         case 5: launch_pass_r<P, LAST, 5>(c, grid, a); break;
         case 6: launch_pass_r<P, LAST, 6>(c, grid, a); break;
@@ -658,13 +673,27 @@ static void launch_pass(zkt_ctx* c, int log_r, unsigned blocks, unsigned nb, con
     }
 }
 
-// nb <= NTT_MAX_BATCH transforms of the same plan, one launch per pass (gridDim.y = polynomial): the prover's rounds
-// transform two or three polynomials at a time (prove.rs:120-122,166-167; quotient_poly.rs:52-96), and a 2^20
-// transform alone is a single wave of workgroups whose ramp and tail are a third of its time.
 template <class P>
-static int ntt_run_batch_t(zkt_ctx* c, int log_n, int inverse, int coset, int nb, const void* const* d_in, const size_t* in_len,
-                           void* const* d_out, const void* d_head = nullptr) {
+static int get_plan(zkt_ctx* c, int log_n, int inverse, int coset, bool forced, const NttPlan<P>** out) {
+    auto key = std::make_tuple(log_n, inverse ? 1 : 0, coset, forced ? ntt_split_code(c) : 0);
+    auto it = c->ntt_plans.find(key);
+    if (it == c->ntt_plans.end()) {
+        auto holder = std::make_shared<NttPlan<P>>();
+        int rc = build_plan<P>(c, log_n, inverse ? 1 : 0, coset, forced, *holder);
+        if (rc) return rc;
+        it = c->ntt_plans.emplace(key, std::static_pointer_cast<void>(holder)).first;
+    }
+    *out = static_cast<const NttPlan<P>*>(it->second.get());
+    return 0;
+}
+
+// ncls plans of one shape (same size, direction and split; cosets[z] their shifts), ncls = 1 for a single plan: the
+// grid's z is the class, in and out of class z cls_in / cls_out elements behind those of class 0
+template <class P>
+static int ntt_run_core_t(zkt_ctx* c, int log_n, int inverse, const int* cosets, int ncls, int nb, const void* const* d_in,
+                          const size_t* in_len, void* const* d_out, size_t cls_in, size_t cls_out, const void* d_head) {
     if (nb < 1 || nb > NTT_MAX_BATCH) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "transform batch out of range");
+    if (ncls < 1 || ncls > NTT_MAX_CLS) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "transform classes out of range");
     if (log_n < 0 || log_n > P::TWO_ADICITY)
         return set_err(c, ZKT_ERR_INVALID_DOMAIN_SIZE,
                        "InvalidEvalDomainSize: log_size_of_group " + std::to_string(log_n) + " exceeds adicity " +
@@ -676,27 +705,31 @@ static int ntt_run_batch_t(zkt_ctx* c, int log_n, int inverse, int coset, int nb
     const bool forced = c->ntt_split_npass && log_n > TILE_LOG;   // the single-workgroup kernel has no passes to split
     if (forced && c->ntt_split_log_r[0] + c->ntt_split_log_r[1] + c->ntt_split_log_r[2] != log_n)
         return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "the forced split (zkt_debug_ntt_split) does not multiply to this domain size");
-    auto key = std::make_tuple(log_n, inverse ? 1 : 0, coset, forced ? ntt_split_code(c) : 0);
-    auto it = c->ntt_plans.find(key);
-    if (it == c->ntt_plans.end()) {
-        auto holder = std::make_shared<NttPlan<P>>();
-        int rc = build_plan<P>(c, log_n, inverse ? 1 : 0, coset, forced, *holder);
-        if (rc) return rc;
-        it = c->ntt_plans.emplace(key, std::static_pointer_cast<void>(holder)).first;
+    const NttPlan<P>* pls[NTT_MAX_CLS];
+    for (int z = 0; z < NTT_MAX_CLS; ++z) {
+        if (z >= ncls) { pls[z] = pls[0]; continue; }
+        if (int rc = get_plan<P>(c, log_n, inverse, cosets[z], forced, &pls[z])) return rc;
+        if (z && (!cosets[z] != !cosets[0])) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "transform classes of different shapes");
     }
-    const NttPlan<P>& pl = *static_cast<const NttPlan<P>*>(it->second.get());
+    const NttPlan<P>& pl = *pls[0];   // what the classes share: the split and the butterfly twiddles
     const std::string prof_name = "ntt_" + std::to_string(log_n);  // e.g. "ntt_20", "ntt_22"
-    ProfScope prof_all(c, prof_name.c_str(), nullptr, nb);          // counted per transform
+    ProfScope prof_all(c, prof_name.c_str(), nullptr, nb * ncls);   // counted per transform
     if (pl.npass == 0) {
+        NttSmallCls k{};
+        for (int z = 0; z < NTT_MAX_CLS; ++z) {
+            k.in_scale[z] = pls[z]->small_in;
+            k.out_scale[z] = pls[z]->small_out;
+        }
+        k.cls_in = cls_in;
+        k.cls_out = cls_out;
         for (int y = 0; y < nb; ++y)
-            hipLaunchKernelGGL(k_ntt_small<P>, dim3(1), dim3(NTT_THREADS), 0, c->stream, (const Fe<P>*)d_in[y],
-                               (uint64_t)in_len[y], (Fe<P>*)d_out[y], log_n, (const Fe<P>*)pl.small_w,
-                               (const Fe<P>*)pl.small_in, (const Fe<P>*)pl.small_out,
+            hipLaunchKernelGGL(k_ntt_small<P>, dim3(1, 1, ncls), dim3(NTT_THREADS), 0, c->stream, (const Fe<P>*)d_in[y],
+                               (uint64_t)in_len[y], (Fe<P>*)d_out[y], log_n, (const Fe<P>*)pl.small_w, k,
                                d_head ? (const Fe<P>*)d_head + (size_t)y * NTT_HEAD : nullptr);
         ZKT_HIP(c, hipGetLastError());
         return 0;
     }
-    int rc = ensure_buffer(c, &c->ntt_scratch, &c->ntt_scratch_bytes, N * 36 * (size_t)nb);   // raw limbs between passes
+    int rc = ensure_buffer(c, &c->ntt_scratch, &c->ntt_scratch_bytes, N * 36 * (size_t)nb * (size_t)ncls);   // raw limbs between passes
     if (rc) return rc;
     const int p = pl.npass;
     const unsigned blocks = (unsigned)(N >> TILE_LOG);
@@ -712,10 +745,14 @@ static int ntt_run_batch_t(zkt_ctx* c, int log_n, int inverse, int coset, int nb
         }
         a.w_inner = pl.w_inner[i];
         a.w_inner_s = pl.w_inner_s[i];
-        a.in_row = (i == 0) ? pl.in_row : nullptr;
+        for (int z = 0; z < NTT_MAX_CLS; ++z) {
+            a.in_row[z] = (i == 0) ? pls[z]->in_row : nullptr;
+            a.tw[z] = pls[z]->tw[i];
+            a.out_row[z] = last ? pls[z]->out_row : nullptr;
+        }
+        a.cls_in = (uint64_t)cls_in * sizeof(Fe<P>);
+        a.cls_out = (uint64_t)cls_out * sizeof(Fe<P>);
         a.head = (i == 0) ? d_head : nullptr;
-        a.tw = pl.tw[i];
-        a.out_row = last ? pl.out_row : nullptr;
         a.log_n = (uint32_t)log_n;
         a.in_raw = (i == 0) ? 0u : 1u;
         a.out_raw = last ? 0u : 1u;
@@ -723,15 +760,24 @@ static int ntt_run_batch_t(zkt_ctx* c, int log_n, int inverse, int coset, int nb
         acc += pl.log_r[i];
         if (!last) {
             a.log_s = (uint32_t)(log_n - acc);
-            launch_pass<P, false>(c, pl.log_r[i], blocks, (unsigned)nb, a);
+            launch_pass<P, false>(c, pl.log_r[i], blocks, (unsigned)nb, (unsigned)ncls, a);
         } else {
             a.log_r1 = (uint32_t)pl.log_r[0];
             a.log_mid = (uint32_t)(log_n - pl.log_r[0] - pl.log_r[i]);
-            launch_pass<P, true>(c, pl.log_r[i], blocks, (unsigned)nb, a);
+            launch_pass<P, true>(c, pl.log_r[i], blocks, (unsigned)nb, (unsigned)ncls, a);
         }
         ZKT_HIP(c, hipGetLastError());
     }
     return 0;
+}
+
+// nb <= NTT_MAX_BATCH transforms of the same plan, one launch per pass (gridDim.y = polynomial): the prover's rounds
+// transform two or three polynomials at a time (prove.rs:120-122,166-167; quotient_poly.rs:52-96), and a 2^20
+// transform alone is a single wave of workgroups whose ramp and tail are a third of its time.
+template <class P>
+static int ntt_run_batch_t(zkt_ctx* c, int log_n, int inverse, int coset, int nb, const void* const* d_in, const size_t* in_len,
+                           void* const* d_out, const void* d_head = nullptr) {
+    return ntt_run_core_t<P>(c, log_n, inverse, &coset, 1, nb, d_in, in_len, d_out, 0, 0, d_head);
 }
 
 template <class P>
@@ -775,6 +821,14 @@ int ntt_fold_heads(zkt_ctx* c, int nb, const void* const* d_in, size_t n, const 
     if (nb < 1 || nb > NTT_MAX_BATCH) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "transform batch out of range");
     if (c->curve == ZKT_CURVE_BN254) return ntt_fold_heads_t<Bn254Fr>(c, nb, d_in, n, gammas, d_out);
     return ntt_fold_heads_t<Bls381Fr>(c, nb, d_in, n, gammas, d_out);
+}
+
+int ntt_run_classes(zkt_ctx* c, int log_n, int inverse, const int codes[3], int nb, const void* const* d_in, const size_t* in_len,
+                    void* const* d_out, size_t in_stride, size_t out_stride, const void* d_head) {
+    if (d_head && (inverse || log_n < 3)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "folded heads go with forward transforms of 8 points and more");
+    if (c->curve == ZKT_CURVE_BN254)
+        return ntt_run_core_t<Bn254Fr>(c, log_n, inverse, codes, 3, nb, d_in, in_len, d_out, in_stride, out_stride, d_head);
+    return ntt_run_core_t<Bls381Fr>(c, log_n, inverse, codes, 3, nb, d_in, in_len, d_out, in_stride, out_stride, d_head);
 }
 
 int ntt_run(zkt_ctx* c, int log_n, int inverse, int coset, const void* d_in, size_t in_len, void* d_out) {

@@ -22,15 +22,21 @@ namespace zkt {
 
 constexpr int NTT_HEAD = 8;        // coefficients a transform may take from a folded head (NttPassArgs::head)
 constexpr int NTT_MAX_BATCH = 4;   // transforms of one plan issued as ONE launch per pass (gridDim.y = polynomial)
+constexpr int NTT_MAX_CLS = 3;     // plans of one shape (cosets that differ in their shift) in ONE launch (gridDim.z = class)
 
 struct NttPassArgs {
     const void* in[NTT_MAX_BATCH];    // Fe* (raw passes: polynomial y lives at in[0] + y * 36 * raw_n bytes)
     void* out[NTT_MAX_BATCH];         // Fe*
     const void* w_inner;   // R/2 inner twiddles W_R^j, Montgomery form (packed words)
     const void* w_inner_s; // the same as (w, floor(w 2^261 / p)) pairs of 9 + 9 limbs (fx_mul_shoup)
-    const void* in_row;    // optional R-entry input row scale (forward coset, pass 1)
-    const void* tw;        // optional boundary twiddles (row-shared or tile-shaped)
-    const void* out_row;   // optional R-entry output row scale (inverse coset, last pass)
+    // the tables that depend on the coset's shift, one per class (blockIdx.z; a single transform uses [0]); a launch
+    // has a table for all of its classes or for none
+    const void* in_row[NTT_MAX_CLS];    // optional R-entry input row scale (forward coset, pass 1)
+    const void* tw[NTT_MAX_CLS];        // optional boundary twiddles (row-shared or tile-shaped)
+    const void* out_row[NTT_MAX_CLS];   // optional R-entry output row scale (inverse coset, last pass)
+    // class z reads in[y] + z * cls_in and writes out[y] + z * cls_out (bytes; packed passes), its folded heads are
+    // NTT_MAX_BATCH * NTT_HEAD elements further on per class, and its raw planes follow those of class z - 1
+    uint64_t cls_in, cls_out;
     uint64_t in_len[NTT_MAX_BATCH];   // elements of `in` that exist (rest read as zero); pass 1 only
     // optional, pass 1 only: polynomial y reads its coefficients 0..7 from head + 8 y instead of in[y] (a polynomial of
     // n + 8 coefficients folded modulo X^n - c differs from its first n coefficients in those eight only: ntt_fold_heads)

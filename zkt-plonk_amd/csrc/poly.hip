@@ -180,8 +180,7 @@ constexpr int SC_E = 4;
 constexpr int SC_BLK = 256 * SC_E;
 
 template <class P, class Op>
-__global__ __launch_bounds__(256) void k_scan_local(const Fe<P>* in, Fe<P>* out, size_t n, int reverse, Fe<P>* totals) {
-    __shared__ Fe<P> s[256];
+ZKT_D void scan_local(const Fe<P>* in, Fe<P>* out, size_t n, int reverse, Fe<P>* totals, Fe<P>* s) {
     const int t = threadIdx.x;
     const size_t i0 = (size_t)blockIdx.x * SC_BLK + (size_t)t * SC_E;
     Fe<P> x[SC_E];
@@ -207,6 +206,19 @@ __global__ __launch_bounds__(256) void k_scan_local(const Fe<P>* in, Fe<P>* out,
         if (li < n) fe_store<P>(out + (reverse ? n - 1 - li : li), t > 0 ? Op::template apply<P>(pre, x[e]) : x[e]);
     }
     if (t == 255) fe_store<P>(totals + blockIdx.x, s[255]);
+}
+template <class P, class Op>
+__global__ __launch_bounds__(256) void k_scan_local(const Fe<P>* in, Fe<P>* out, size_t n, int reverse, Fe<P>* totals) {
+    __shared__ Fe<P> s[256];
+    scan_local<P, Op>(in, out, n, reverse, totals, s);
+}
+// four one-block scans in one launch (blockIdx.y = row): row b holds [in nb][out nb][total], what scan_t makes of nb <= SC_BLK
+template <class P, class Op>
+__global__ __launch_bounds__(256) void k_scan_rows4(Fe<P>* b0, Fe<P>* b1, Fe<P>* b2, Fe<P>* b3, size_t nb) {
+    __shared__ Fe<P> s[256];
+    const uint32_t y = blockIdx.y;
+    Fe<P>* b = y == 0 ? b0 : y == 1 ? b1 : y == 2 ? b2 : b3;
+    scan_local<P, Op>(b, b + nb, nb, 0, b + 2 * nb, s);
 }
 
 template <class P, class Op>
@@ -516,6 +528,7 @@ struct QuotientDev {
     uint32_t n_pi_direct;
     uint32_t G, cls, next_off;
     const void *z1_next, *z2_next, *t_next, *h1_next;
+    uint64_t cls_stride;     // blockIdx.y = class cls + y, its vectors cls_stride elements further on per y
 };
 template <class P>
 ZKT_D Fx<P> arg_fx(const FxArg& w) {
@@ -533,7 +546,9 @@ __global__ __launch_bounds__(256) void k_quotient(QuotientDev q) {
     if (i >= q.first + q.count) return;
     // "omega-next": global index + 4, i.e. entry i + next_off of the (possibly neighbouring) class, wrapping
     const uint64_t j = (i + q.next_off < q.n4) ? i + q.next_off : i + q.next_off - q.n4;
-#define LD(ptr, idx) fx_unpack<P>(fe_load<P>((const Fe<P>*)(ptr) + (idx)))   // canonical, < p
+    const uint64_t coff = (uint64_t)blockIdx.y * q.cls_stride;   // uniform: the class of this workgroup (one launch for three)
+    const uint32_t cls = q.cls + blockIdx.y;
+#define LD(ptr, idx) fx_unpack<P>(fe_load<P>((const Fe<P>*)(ptr) + coff + (idx)))   // canonical, < p
     const X beta = arg_fx<P>(q.beta), delta = arg_fx<P>(q.delta), gamma = arg_fx<P>(q.gamma);
     const X a = LD(q.a, i), b = LD(q.b, i), c = LD(q.c, i);
     // keys/arithmetic.rs:67-81 ; q_m is stored as H * 32
@@ -600,8 +615,8 @@ __global__ __launch_bounds__(256) void k_quotient(QuotientDev q) {
     }
 #undef LD
     // quotient_poly.rs:220-224: times zh_coset[i]^-1; x^n - 1 takes 4 values on the 4n coset (global index mod 4)
-    const X r = fx_mul<P>(acc, arg_fx<P>(q.zh_inv[(q.cls + q.G * (uint32_t)i) & 3]));
-    fe_store<P>((Fe<P>*)q.out + i, fx_pack<P>(fx_cond_sub_p<P>(r)));
+    const X r = fx_mul<P>(acc, arg_fx<P>(q.zh_inv[(cls + q.G * (uint32_t)i) & 3]));
+    fe_store<P>((Fe<P>*)q.out + coff + i, fx_pack<P>(fx_cond_sub_p<P>(r)));
 }
 
 // v[i] (A form) -> v[i] * 2^(5 + 5 k32) (H form times 32^k32), canonical packed
@@ -1105,7 +1120,7 @@ static size_t scan_tmp_elems(size_t n) {
 }
 size_t grand_product_tmp_elems(size_t n) { return 2 * scan_tmp_elems(n); }
 template <class P> static int grand_product_scan_t(zkt_ctx* c, const ZTermsArgs& a, int which, void* pn, void* sd, void* tmp,
-                                                   const void** d_total_den) {
+                                                   const void** d_total_den, bool totals_later) {
     const size_t n = a.n;
     if (n == 0 || (n & (n - 1))) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "grand product: n must be a power of two");
     const size_t nb = (n + SC_BLK - 1) / SC_BLK;
@@ -1116,7 +1131,7 @@ template <class P> static int grand_product_scan_t(zkt_ctx* c, const ZTermsArgs&
     else
         hipLaunchKernelGGL((k_z_terms_scan<P, 2>), dim3((unsigned)nb, 2), dim3(256), 0, c->stream, a, (Fe<P>*)pn, (Fe<P>*)sd, tn, td);
     ZKT_HIP(c, hipGetLastError());
-    if (nb > 1) {
+    if (nb > 1 && !totals_later) {
         int rc;
         if ((rc = scan_t<P, OpMul>(c, tn, tn + nb, nb, false, tn + 2 * nb))) return rc;
         if ((rc = scan_t<P, OpMul>(c, td, td + nb, nb, false, td + 2 * nb))) return rc;
@@ -1124,9 +1139,22 @@ template <class P> static int grand_product_scan_t(zkt_ctx* c, const ZTermsArgs&
     *d_total_den = nb > 1 ? td + nb + (nb - 1) : td;
     return ZKT_OK;
 }
-int grand_product_scan(zkt_ctx* c, const ZTermsArgs& a, int which, void* pn_local, void* sd_local, void* d_tmp, const void** d_total_den) {
-    ZKT_DISPATCH(c, grand_product_scan_t, a, which, pn_local, sd_local, d_tmp, d_total_den);
+int grand_product_scan(zkt_ctx* c, const ZTermsArgs& a, int which, void* pn_local, void* sd_local, void* d_tmp, const void** d_total_den,
+                       bool totals_later) {
+    ZKT_DISPATCH(c, grand_product_scan_t, a, which, pn_local, sd_local, d_tmp, d_total_den, totals_later);
 }
+bool grand_product_totals_fit(size_t n) { return (n + SC_BLK - 1) / SC_BLK <= (size_t)SC_BLK; }
+template <class P> static int grand_product_totals2_t(zkt_ctx* c, size_t n, void* tmp1, void* tmp2) {
+    const size_t nb = (n + SC_BLK - 1) / SC_BLK;
+    if (nb <= 1) return ZKT_OK;
+    if (nb > (size_t)SC_BLK) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "grand product: the block totals need more than one block");
+    Fe<P>*tn1 = (Fe<P>*)tmp1, *tn2 = (Fe<P>*)tmp2;
+    hipLaunchKernelGGL((k_scan_rows4<P, OpMul>), dim3(1, 4), dim3(256), 0, c->stream, tn1, tn1 + scan_tmp_elems(n), tn2,
+                       tn2 + scan_tmp_elems(n), nb);
+    ZKT_HIP(c, hipGetLastError());
+    return ZKT_OK;
+}
+int grand_product_totals2(zkt_ctx* c, size_t n, void* d_tmp1, void* d_tmp2) { ZKT_DISPATCH(c, grand_product_totals2_t, n, d_tmp1, d_tmp2); }
 template <class P> static int grand_product_combine_t(zkt_ctx* c, const void* pn, const void* sd, const void* tmp, const uint32_t* inv,
                                                       void* out, size_t n) {
     const size_t nb = (n + SC_BLK - 1) / SC_BLK;
@@ -1208,7 +1236,10 @@ template <class P> static int quotient_t(zkt_ctx* c, const QuotientArgs& a) {
     q.first = a.first;
     q.count = a.count ? a.count : a.n4 - a.first;
     if (q.first + q.count > a.n4) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "quotient range outside the vectors");
-    hipLaunchKernelGGL(k_quotient<P>, dim3(nblocks(q.count)), dim3(256), 0, c->stream, q);
+    const unsigned ncls = a.ncls > 1 ? a.ncls : 1;
+    if (ncls > 1 && (a.G <= 1 || a.cls + ncls > a.G)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "quotient classes outside the coset");
+    q.cls_stride = ncls > 1 ? a.cls_stride : 0;
+    hipLaunchKernelGGL(k_quotient<P>, dim3(nblocks(q.count), ncls), dim3(256), 0, c->stream, q);
     ZKT_HIP(c, hipGetLastError());
     return ZKT_OK;
 }
@@ -1258,19 +1289,24 @@ __global__ void k_quot_split(const Fe<P>* q, size_t chunk, size_t cap, Fe<P>* lo
 }
 
 template <class P> static int quot_split_t(zkt_ctx* c, const void* q, size_t n, const void* b0b1, void* lo, void* mid, void* hi, uint32_t* d_status,
-                                            bool fused) {
+                                            bool fused, bool closed) {
     // d_status[0] = error bits ; d_status[4..7] = lens (lo, mid, hi, q), zero on entry
+    // closed: k_classes_close has filled the chunks and written the zeros of [3(n + 2), 4n) itself (lens[3] stays 0)
     const Fe<P>* Q = (const Fe<P>*)q;
     const size_t cap = n + 8, chunk = n + 2;
-    hipLaunchKernelGGL(k_quot_split<P>, dim3(nblocks(cap)), dim3(256), 0, c->stream, Q, chunk, cap, (Fe<P>*)lo, (Fe<P>*)mid,
-                       (Fe<P>*)hi);
-    ZKT_HIP(c, hipGetLastError());
+    if (!closed) {
+        hipLaunchKernelGGL(k_quot_split<P>, dim3(nblocks(cap)), dim3(256), 0, c->stream, Q, chunk, cap, (Fe<P>*)lo, (Fe<P>*)mid,
+                           (Fe<P>*)hi);
+        ZKT_HIP(c, hipGetLastError());
+    }
     uint32_t* lens = d_status + 4;
     int rc;
     if (fused) {   // the quotient's own check first, then the three trims and the blinders as one launch
         const size_t qlo = 3 * chunk, qhi = 4 * n;
-        hipLaunchKernelGGL(k_trim_len<P>, dim3(nblocks(qhi - qlo)), dim3(256), 0, c->stream, Q, qlo, qhi, lens + 3, 0, (Fe<P>*)nullptr, 0);
-        ZKT_HIP(c, hipGetLastError());
+        if (!closed) {
+            hipLaunchKernelGGL(k_trim_len<P>, dim3(nblocks(qhi - qlo)), dim3(256), 0, c->stream, Q, qlo, qhi, lens + 3, 0, (Fe<P>*)nullptr, 0);
+            ZKT_HIP(c, hipGetLastError());
+        }
         hipLaunchKernelGGL(k_quot_trim_blind<P>, dim3(1), dim3(TB_THREADS), 0, c->stream, (Fe<P>*)lo, (Fe<P>*)mid, (Fe<P>*)hi, chunk, lens,
                            (const Fe<P>*)b0b1, (uint32_t)n, d_status);
         ZKT_HIP(c, hipGetLastError());
@@ -1279,7 +1315,7 @@ template <class P> static int quot_split_t(zkt_ctx* c, const void* q, size_t n, 
     if ((rc = trim_len_t<P>(c, lo, chunk, lens + 0))) return rc;
     if ((rc = trim_len_t<P>(c, mid, chunk, lens + 1))) return rc;
     if ((rc = trim_len_t<P>(c, hi, chunk, lens + 2))) return rc;
-    {   // only "is anything non-zero at or above 3(n+2)?" matters for the quotient itself
+    if (!closed) {   // only "is anything non-zero at or above 3(n+2)?" matters for the quotient itself
         const size_t lo = 3 * chunk, hi = 4 * n;
         hipLaunchKernelGGL(k_trim_len<P>, dim3(nblocks(hi - lo)), dim3(256), 0, c->stream, (const Fe<P>*)q, lo, hi, lens + 3, 0,
                            (Fe<P>*)nullptr, 0);
@@ -1290,8 +1326,8 @@ template <class P> static int quot_split_t(zkt_ctx* c, const void* q, size_t n, 
     return ZKT_OK;
 }
 int quotient_split_blind(zkt_ctx* c, const void* q, size_t n, const void* d_b0b1, void* q_lo, void* q_mid, void* q_hi, uint32_t* d_status,
-                         bool fused) {
-    ZKT_DISPATCH(c, quot_split_t, q, n, d_b0b1, q_lo, q_mid, q_hi, d_status, fused);
+                         bool fused, bool closed) {
+    ZKT_DISPATCH(c, quot_split_t, q, n, d_b0b1, q_lo, q_mid, q_hi, d_status, fused, closed);
 }
 
 
@@ -1379,6 +1415,68 @@ template <class P> static int classes_combine_t(zkt_ctx* c, void* q, size_t n, c
 }
 int quotient_classes_combine(zkt_ctx* c, void* q, size_t n, const uint32_t* vinv, const uint32_t* u, const uint32_t* g3) {
     ZKT_DISPATCH(c, classes_combine_t, q, n, vinv, u, g3);
+}
+
+// The closing pass of the classes route (zkt_ctx_set_fused_passes): k_classes_combine, k_quot_split and the scan of
+// [3n + 6, 4n) in one walk.  Each T_k is one three-term sum of products with one reduction (fx_mul3_inl: E_j canonical in
+// arkworks' form times vinv in canonical R' form, 3 p^2 < R' p, gives T_k in arkworks' form, < 2p).  Coefficient g = k n + i
+// of t goes to q[g] and to its place in the chunks of n + 2 (lo | mid | hi); row 3 is u in its first six places and zero
+// above, so nothing is left to scan; the same six threads clear the slack [n + 2, n + 8) of the three chunks.
+template <class P>
+struct CloseArgs {
+    FxArg vinv[9];   // canonical, R' form
+    Fe<P> u[6];
+    Fe<P> g3[3];     // gamma_3, gamma_3^2, gamma_3^3
+};
+template <class P>
+__global__ __launch_bounds__(256) void k_classes_close(Fe<P>* q, uint64_t n, CloseArgs<P> a, Fe<P>* lo, Fe<P>* mid, Fe<P>* hi) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const Fx<P> e0 = fx_unpack<P>(fe_load<P>(q + i)), e1 = fx_unpack<P>(fe_load<P>(q + n + i)), e2 = fx_unpack<P>(fe_load<P>(q + 2 * n + i));
+    Fe<P> t[4];
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        t[k] = fx_pack<P>(fx_cond_sub_p<P>(
+            fx_mul3_inl<P>(e0, arg_fx<P>(a.vinv[3 * k]), e1, arg_fx<P>(a.vinv[3 * k + 1]), e2, arg_fx<P>(a.vinv[3 * k + 2]))));
+    t[3] = fe_zero<P>();
+    if (i < 6) {
+        Fe<P> u = a.u[0];
+#pragma unroll
+        for (int e = 1; e < 6; ++e) u = (i == (uint64_t)e) ? a.u[e] : u;
+        t[3] = u;
+        t[2] = fe_add<P>(t[2], fe_mul<P>(u, a.g3[0]));
+        t[1] = fe_add<P>(t[1], fe_mul<P>(u, a.g3[1]));
+        t[0] = fe_add<P>(t[0], fe_mul<P>(u, a.g3[2]));
+        const Fe<P> z = fe_zero<P>();
+        fe_store<P>(hi + n - 4 + i, u);          // t[3n + i] = hi[n - 4 + i], the chunk's last six
+        fe_store<P>(lo + n + 2 + i, z);
+        fe_store<P>(mid + n + 2 + i, z);
+        fe_store<P>(hi + n + 2 + i, z);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) fe_store<P>(q + (uint64_t)k * n + i, t[k]);
+    fe_store<P>(lo + i, t[0]);
+    fe_store<P>(i < 2 ? lo + n + i : mid + i - 2, t[1]);       // t[n + i]: the seam lo | mid is at n + 2
+    fe_store<P>(i < 4 ? mid + n - 2 + i : hi + i - 4, t[2]);   // t[2n + i]: the seam mid | hi is at 2n + 4
+}
+template <class P> static int classes_close_t(zkt_ctx* c, void* q, size_t n, const uint32_t* vinv, const uint32_t* u, const uint32_t* g3,
+                                              void* lo, void* mid, void* hi) {
+    if (n < 8) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "classes route: fewer than 8 rows");
+    CloseArgs<P> a{};
+    for (int k = 0; k < 9; ++k) {
+        const Fx<P> v = fx_cond_sub_p<P>(fx_from_ark<P>(host_fe<P>(vinv + 8 * k)));
+        for (int w = 0; w < 9; ++w) a.vinv[k].l[w] = v.l[w];
+    }
+    for (int k = 0; k < 6; ++k) a.u[k] = host_fe<P>(u + 8 * k);
+    for (int k = 0; k < 3; ++k) a.g3[k] = host_fe<P>(g3 + 8 * k);
+    hipLaunchKernelGGL(k_classes_close<P>, dim3(nblocks(n)), dim3(256), 0, c->stream, (Fe<P>*)q, (uint64_t)n, a, (Fe<P>*)lo, (Fe<P>*)mid,
+                       (Fe<P>*)hi);
+    ZKT_HIP(c, hipGetLastError());
+    return ZKT_OK;
+}
+int quotient_classes_close(zkt_ctx* c, void* q, size_t n, const uint32_t* vinv, const uint32_t* u, const uint32_t* g3, void* q_lo,
+                           void* q_mid, void* q_hi) {
+    ZKT_DISPATCH(c, classes_close_t, q, n, vinv, u, g3, q_lo, q_mid, q_hi);
 }
 
 int open_elems(size_t len) { return ow_elems(len); }

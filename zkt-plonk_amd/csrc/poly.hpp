@@ -43,6 +43,10 @@ struct QuotientArgs {           // all vectors hold 4n coset evaluations
     const void *z1_next, *z2_next, *t_next, *h1_next;
     // only the points [first, first + count) of the vectors (count = 0: all n4); out[i] is written for those i
     uint64_t first, count;
+    // ncls > 1: one launch for the classes cls, cls + 1, .. (the grid's y): class cls + y reads and writes every vector,
+    // the *_next ones and `out` included, cls_stride elements further on per y (the classes route's [3][n] arrays)
+    uint32_t ncls;
+    uint64_t cls_stride;
 };
 constexpr int QUOTIENT_PI_DIRECT_MAX = 16;
 
@@ -99,7 +103,12 @@ int z_combine(zkt_ctx* c, const void* pn, const void* sd, const uint32_t inv_tot
 // in d_tmp (grand_product_tmp_elems(n) elements), *d_total_den points at the product of all denominators (device).  After the
 // host inverted it, grand_product_combine writes z from the local scans, the block prefixes in d_tmp and the inverse.
 size_t grand_product_tmp_elems(size_t n);
-int grand_product_scan(zkt_ctx* c, const ZTermsArgs& a, int which, void* pn_local, void* sd_local, void* d_tmp, const void** d_total_den);
+int grand_product_scan(zkt_ctx* c, const ZTermsArgs& a, int which, void* pn_local, void* sd_local, void* d_tmp, const void** d_total_den,
+                       bool totals_later = false);
+// totals_later: the scans of the block totals are left out; grand_product_totals2 then makes those of two grand products
+// (their d_tmp) in ONE launch, where each is a single block (grand_product_totals_fit(n))
+bool grand_product_totals_fit(size_t n);
+int grand_product_totals2(zkt_ctx* c, size_t n, void* d_tmp1, void* d_tmp2);
 int grand_product_combine(zkt_ctx* c, const void* pn_local, const void* sd_local, const void* d_tmp, const uint32_t inv_total[8], void* out,
                           size_t n);
 // quotient (quotient_poly.rs:98-224)
@@ -110,9 +119,9 @@ int to_hat_form(zkt_ctx* c, void* v, size_t n, int k32);
 // class-major (rank r's n4 / G points at [r * n4 / G, ...)) -> natural order of the 4n coset: out[cls + G i] = in[cls * (n4 / G) + i].
 // chunks > 1: the exchange went out in pieces, `in` is [chunk][class][n4 / G / chunks]
 int quotient_interleave(zkt_ctx* c, const void* in, void* out, size_t n4, uint32_t G, uint32_t chunks = 1);
-// fused: the three trims and the blinders as one launch
+// fused: the three trims and the blinders as one launch; closed: quotient_classes_close has made the chunks already
 int quotient_split_blind(zkt_ctx* c, const void* q, size_t n, const void* d_b0b1, void* q_lo, void* q_mid, void* q_hi,
-                         uint32_t* d_status, bool fused = false);                               // prove.rs:287-300
+                         uint32_t* d_status, bool fused = false, bool closed = false);          // prove.rs:287-300
 // The quotient on classes 0, 1, 2 of the 4n coset (prover.hip): [3][n] class arrays of a whole-coset table (4n elements);
 // the windows [first, first + QC_WIN) of QC_WIN_POLYS polynomials gathered back to back for one copy to the host; and the
 // way back from the three inverse class transforms (q: 4n elements, [3][n] on entry) to the 4n coefficients of t:
@@ -122,6 +131,10 @@ constexpr int QC_WIN = 14, QC_WIN_POLYS = 6;
 int quotient_classes_of_coset(zkt_ctx* c, const void* in, void* out, size_t n);
 int quotient_gather_windows(zkt_ctx* c, const void* const* polys, size_t first, void* out);
 int quotient_classes_combine(zkt_ctx* c, void* q, size_t n, const uint32_t* vinv, const uint32_t* u, const uint32_t* g3);
+// quotient_classes_combine and the split of quotient_split_blind in one pass: q as above, and the three chunks of n + 2
+// coefficients into q_lo, q_mid, q_hi (n + 8 elements each, slack cleared).  [3n + 6, 4n) of q is zero by construction.
+int quotient_classes_close(zkt_ctx* c, void* q, size_t n, const uint32_t* vinv, const uint32_t* u, const uint32_t* g3, void* q_lo,
+                           void* q_mid, void* q_hi);
 // KZG opening witness: w = p / (X - z)  (kzg10::compute_witness_polynomial)
 int open_witness(zkt_ctx* c, const void* p, size_t len, const uint32_t z[8], const uint32_t z_inv[8], void* d_tmp_a, void* d_tmp_b,
                  void* d_scan_tmp, void* out, void* d_powers /* open_witness_powers(len) elements of scratch */);

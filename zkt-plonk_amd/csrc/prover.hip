@@ -202,9 +202,10 @@ static QuotientArgs quotient_args(const CircuitState& S, void* const w[W_COUNT],
 }
 
 constexpr int WIRE_ELIM_MIN_LOG_N = 17;   // zkt_ctx_set_wire_elimination mode 1: circuits from this size on
-// zkt_ctx_set_quotient_route mode 0: the quotient on three classes from this size on (docs/EXPERIMENTS.md "Quotient on three
-// classes": it gains at 2^20 and loses at 2^18, where its extra launches cost more than the arithmetic it saves; 2^19 is not measured)
-constexpr int QUOTIENT_CLASSES_MIN_LOG_N = 20;
+// zkt_ctx_set_quotient_route mode 0: the quotient on three classes from this size on (docs/EXPERIMENTS.md "Round 4 on
+// classes: one launch per stage": with the class in the grid every run of the route beats every run of the whole coset at
+// 2^18 and 2^19; nothing below 2^18 was measured)
+constexpr int QUOTIENT_CLASSES_MIN_LOG_N = 18;
 
 template <class C>
 struct Prover {
@@ -558,6 +559,11 @@ struct Prover {
             lens[y] = S.n;
         }
         if ((rc = ntt_fold_heads(c, nb, ins, S.n, &S.qc_gamma[0][0], S.heads))) return rc;
+        if (c->fused(8)) {   // the class in the grid: one launch per pass for the three classes, class j into wcos[k] + j n
+            const int codes[3] = {ntt_class_code(S.log_n + 2, 0), ntt_class_code(S.log_n + 2, 1), ntt_class_code(S.log_n + 2, 2)};
+            for (int y = 0; y < nb; ++y) outs[y] = S.wcos[ks[y]];
+            return ntt_run_classes(c, S.log_n, 0, codes, nb, ins, lens, outs, 0, S.n, S.heads);
+        }
         for (int j = 0; j < 3; ++j) {
             for (int y = 0; y < nb; ++y) outs[y] = (char*)S.wcos[ks[y]] + (size_t)j * S.n * 32;
             const void* head = (const char*)S.heads + (size_t)j * NTT_MAX_BATCH * NTT_HEAD * 32;
@@ -852,8 +858,10 @@ struct Prover {
         fused3 = c->fused(2) && grand_product_tmp_elems(n) <= n + 8;
         const void *tot1 = S.sc[3], *tot2 = sd2();
         if (fused3) {
-            if ((rc = grand_product_scan(c, za, 1, S.sc[2], S.sc[3], S.sc[0], &tot1))) return rc;
-            if ((rc = grand_product_scan(c, za, 2, pn2(), sd2(), S.sc[1], &tot2))) return rc;
+            const bool later = c->fused(32) && grand_product_totals_fit(n);   // the four scans of the totals as one launch
+            if ((rc = grand_product_scan(c, za, 1, S.sc[2], S.sc[3], S.sc[0], &tot1, later))) return rc;
+            if ((rc = grand_product_scan(c, za, 2, pn2(), sd2(), S.sc[1], &tot2, later))) return rc;
+            if (later && (rc = grand_product_totals2(c, n, S.sc[0], S.sc[1]))) return rc;
         } else {
             if ((rc = z1_terms(c, za))) return rc;
             if ((rc = scan_mul(c, S.sc[0], S.sc[2], n, false, S.scan_tmp))) return rc;   // PN
@@ -942,24 +950,35 @@ struct Prover {
 
     // Classes 0, 1, 2 of the coset, each as a sharded proof over four GPUs computes its own (the class mode of
     // the kernel), then back class by class: E_j = t mod (X^n - gamma_j); the top coefficients and the combine give t
-    int quotient_on_classes(QuotientArgs q) {
+    // closed (out): the closing pass has split the quotient into its three chunks as well (quotient_split_blind skips that)
+    int quotient_on_classes(QuotientArgs q, bool* closed) {
         const size_t n = S.n;
         const int log_n = S.log_n;
         int rc;
         q.G = 4;
         q.next_off = 1;
         q.n4 = n;
-        for (int j = 0; j < 3; ++j) {
+        const bool grid = c->fused(8);   // the class in the grid: one launch per stage for the three classes
+        for (int j = 0; j < (grid ? 1 : 3); ++j) {
             const size_t off = (size_t)j * n * 32;
             quotient_vectors(q, S.ccoset, S.wcos, off);
             q.cls = (uint32_t)j;
+            q.ncls = grid ? 3 : 0;
+            q.cls_stride = n;
             q.z1_next = q.z1; q.z2_next = q.z2; q.t_next = q.t; q.h1_next = q.h1;
             q.out = (char*)S.qev + off;
             if ((rc = quotient_pointwise(c, q))) return rc;
         }
-        for (int j = 0; j < 3; ++j) {
-            void* e = (char*)S.qev + (size_t)j * n * 32;
-            if ((rc = ntt_run(c, log_n, 1, ntt_class_code(log_n + 2, j), e, n, e))) return rc;
+        if (grid) {
+            const int codes[3] = {ntt_class_code(log_n + 2, 0), ntt_class_code(log_n + 2, 1), ntt_class_code(log_n + 2, 2)};
+            const void* in = S.qev;
+            void* out = S.qev;
+            if ((rc = ntt_run_classes(c, log_n, 1, codes, 1, &in, &n, &out, n, n))) return rc;
+        } else {
+            for (int j = 0; j < 3; ++j) {
+                void* e = (char*)S.qev + (size_t)j * n * 32;
+                if ((rc = ntt_run(c, log_n, 1, ntt_class_code(log_n + 2, j), e, n, e))) return rc;
+            }
         }
         // the six top coefficients, from the windows that came with round 3 (the launches above are under way)
         ZKT_HIP(c, hipEventSynchronize(S.ev_win));
@@ -973,6 +992,9 @@ struct Prover {
         quotient_top_coefficients<R>(log_n, W, ch.alpha, ch.beta, ch.delta, u);
         for (int e = 0; e < 6; ++e) put(S.last_u[e], u[e]);
         S.last_u_valid = true;
+        *closed = c->fused(16);
+        if (*closed)
+            return quotient_classes_close(c, S.qev, n, &S.qc_vinv[0][0], &S.last_u[0][0], &S.qc_g3[0][0], S.poly[9], S.poly[10], S.poly[11]);
         return quotient_classes_combine(c, S.qev, n, &S.qc_vinv[0][0], &S.last_u[0][0], &S.qc_g3[0][0]);
     }
 
@@ -1047,11 +1069,12 @@ struct Prover {
         q.n4 = S.m;
         q.pi_tab = pi_direct ? S.pi_tab : nullptr;
         q.n_pi_direct = pi_direct ? (uint32_t)in.n_pi : 0;
-        if ((rc = classes ? quotient_on_classes(q) : S.G > 1 ? quotient_sharded(q) : quotient_pointwise(c, q))) return rc;
+        bool closed = false;
+        if ((rc = classes ? quotient_on_classes(q, &closed) : S.G > 1 ? quotient_sharded(q) : quotient_pointwise(c, q))) return rc;
         if (!classes && (rc = ntt_run(c, S.log_n + 2, 1, 1, S.qev, 4 * n, S.qev))) return rc;         // quotient_poly.rs:226
         // an unsatisfied circuit shows up as status bits here; they are read with the evaluations of round 5
         if ((rc = quotient_split_blind(c, S.qev, n, (const char*)S.small + 17 * 32, S.poly[9], S.poly[10], S.poly[11], S.status,
-                                       c->fused(4))))
+                                       c->fused(4), closed)))
             return rc;
         void* const polys[3] = {S.poly[9], S.poly[10], S.poly[11]};
         const size_t lens[3] = {n + 3, n + 3, n + 3};
