@@ -42,14 +42,16 @@ def rand_fr(rng, n):
     return x
 
 
-def sharded_rank_job(z, par, comm, cv, n, srs_arr, evals, vk, jobs, out, rank, world, use_setup):
+def sharded_rank_job(z, par, comm, cv, n, srs_arr, evals, vk, jobs, out, rank, world, use_setup, key_total=None):
     """What one rank of a sharded prover does: its SRS slice, the circuit (laid out for its class of the
-    4n coset), the proofs.  out[rank] = (proofs, comm_stats) or the exception."""
+    4n coset), the proofs.  out[rank] = (proofs, comm_stats) or the exception.  key_total: powers of the whole key the
+    ranks share (srs_arr holds them all); n + 8 when not given."""
     try:
         ctx = z.Context(cv.name, 0)
         ctx.set_comm(comm)
-        lo, hi = par.shard_range(n + 8, rank, world)
-        ctx.srs_load_slice(srs_arr[lo:hi], lo, n + 8)
+        total = n + 8 if key_total is None else key_total
+        lo, hi = par.shard_range(total, rank, world)
+        ctx.srs_load_slice(srs_arr[lo:hi], lo, total)
         log_n = n.bit_length() - 1
         if use_setup:
             prover, commits = z.GpuProver.setup(ctx, log_n, evals["evals"])
@@ -80,7 +82,7 @@ def sharded_rank_job(z, par, comm, cv, n, srs_arr, evals, vk, jobs, out, rank, w
         raise
 
 
-def run_sharded_ranks(z, cv, n, srs_arr, evals, vk, jobs, world, use_setup=True, timeout=900):
+def run_sharded_ranks(z, cv, n, srs_arr, evals, vk, jobs, world, use_setup=True, timeout=900, key_total=None):
     """`world` contexts on ONE GPU play the ranks of a sharded proof (threads + the in-process all-gather of
     parallel.LocalGroup).  Returns [(proofs, (calls, bytes_sent), (setup_calls, setup_bytes))] per rank."""
     import threading
@@ -88,7 +90,7 @@ def run_sharded_ranks(z, cv, n, srs_arr, evals, vk, jobs, world, use_setup=True,
     group = par.LocalGroup(world)
     out = [None] * world
     ths = [threading.Thread(target=sharded_rank_job, args=(z, par, group.comm(r), cv, n, srs_arr, evals, vk, jobs, out, r,
-                                                          world, use_setup)) for r in range(world)]
+                                                          world, use_setup, key_total)) for r in range(world)]
     for t in ths:
         t.start()
     for t in ths:

@@ -162,12 +162,13 @@ def test_witness_gather_on_the_device(ctxs):
     assert e.value.code == 1
 
 
-def _bench_workload(z, ctx, cv, log_n, tau):
+def _bench_workload(z, ctx, cv, log_n, tau, key_count=None):
     """bench.py's workload (BASELINE.json configs[3] shape: TABLE_SIZE 1024, 7 public inputs, 2^log_n rows) set up on
-    the device; returns what both sides need: Montgomery arrays, the SRS the GPU generated, the GPU-made VerifierKey."""
+    the device; returns what both sides need: Montgomery arrays, the SRS the GPU generated, the GPU-made VerifierKey.
+    key_count: powers of the generated key (n + 8 when not given)."""
     import bench as B
     n = 1 << log_n
-    ctx.srs_generate(tau, n + 8)
+    ctx.srs_generate(tau, n + 8 if key_count is None else key_count)
     circ = B.synthetic_circuit(B.FIELDS[cv.name], log_n)
     evals = {name: K.fr_to_mont(cv, circ["sel"][name]) for name in z.PK_ORDER}
     prover, commits = z.GpuProver.setup(ctx, log_n, evals)
