@@ -63,9 +63,12 @@ void zkt_ctx_destroy(zkt_ctx* ctx);
  * what a proof writes: its stream, work buffers and MSM slots (about 3 of the ~7 GiB a context holds at n = 2^20).  For a
  * service that keeps several proofs in flight on one GPU (one host thread per context), which is what hides the latency
  * chain of the reference's real circuit sizes: n = 2^14 385 -> 587 proofs/s with two contexts, n = 2^18 156 -> 186 with
- * three.  The fork proves exactly as `ctx` would (same bytes).  Rules: no communicator on either side; while forks are
- * alive `ctx` refuses zkt_srs_* / zkt_circuit_* / zkt_ctx_set_comm (its tables are in use), and zkt_ctx_destroy(ctx) takes
- * effect when the last fork is destroyed; a fork that loads a key or circuit of its own simply stops sharing that part.
+ * three.  The fork proves exactly as `ctx` would (same bytes), and a fork may be forked in turn.  Rules: no communicator
+ * on either side; while a context forked from `ctx` (or from one of those) still reads one of its key or circuit tables,
+ * `ctx` refuses zkt_srs_* / zkt_circuit_* / zkt_ctx_set_comm (its tables are in use); a fork that loads a key or circuit
+ * of its own simply stops sharing that part, so a context whose forks have all loaded a key and a circuit of their own is
+ * refused nothing.  Contexts may be destroyed in any order: the shared tables belong to no context and are freed when
+ * the last context that reads them is destroyed or lets go of them.
  * Create and destroy contexts from one thread (or serialise those calls); prove on them concurrently. */
 int zkt_ctx_fork(zkt_ctx* ctx, zkt_ctx** out);
 const char* zkt_last_error(const zkt_ctx* ctx);
@@ -1055,6 +1058,11 @@ int zkt_debug_ntt_batch(zkt_ctx* ctx, int log_n, int inverse, int coset, int nb,
  * size that is not the product of the radices.  (A tile that would not fit its pass is refused as well, but no two or
  * three radices of 2^5 and more have one: that check is a guard, not a reachable refusal.) */
 int zkt_debug_ntt_split(zkt_ctx* ctx, int npass, const int* log_r);
+/* The device allocations the library holds at this moment, over all contexts of the process: their number and their bytes
+ * (contexts' buffers and caller allocations of zkt_dev_alloc, shared tables, NTT plans; no pinned host memory).  Leak tests
+ * compare it before the first context is created and after the last is destroyed: unlike the card's free memory it does
+ * not depend on other processes.  No context needed; null pointer -> ZKT_ERR_INVALID_ARGUMENT. */
+int zkt_debug_live_allocations(uint64_t* count, uint64_t* bytes);
 /* Overrides where the appends of this tree change from one launch per level to the single-workgroup tail: levels with at
  * least wide_min_parents parents are hashed by the wide kernel, the others by the tail kernel.  1 sends every level to the
  * wide kernel, INT_MAX every level to the tail kernel (up to the 512 parents a level of the tail may have: it keeps the

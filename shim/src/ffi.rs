@@ -182,6 +182,7 @@ extern "C" {
                                                   d_variables: *mut c_void, n_vars: usize, bit_var0: *const u32,
                                                   sibling_var0: *const u32) -> c_int;
     pub fn zkt_debug_merkle_tree_split(tree: *mut c_void, wide_min_parents: c_int) -> c_int;
+    pub fn zkt_debug_live_allocations(count: *mut u64, bytes: *mut u64) -> c_int;
     pub fn zkt_dev_alloc(ctx: *mut ZktCtx, bytes: usize, dptr: *mut *mut c_void) -> c_int;
     pub fn zkt_dev_free(ctx: *mut ZktCtx, dptr: *mut c_void) -> c_int;
     pub fn zkt_dev_upload(ctx: *mut ZktCtx, dptr: *mut c_void, host: *const c_void, bytes: usize) -> c_int;

@@ -843,8 +843,8 @@ def test_contexts_in_flight_prove_the_same_bytes(cvname, gates):
 def test_forked_contexts_share_tables_and_prove_the_same_bytes(cvname, gates):
     """zkt_ctx_fork: contexts that share one context's SRS / Lagrange / circuit / twiddle tables and own only their work
     buffers.  The parent and two forks prove different proofs concurrently (one thread each): the oracle's bytes everywhere.
-    Lifetime rules: a parent with live forks refuses to reload its key or circuit; destroyed first it lingers until its last
-    fork is gone (the forks keep proving); a fork that loads its own key stops sharing and still proves the same bytes."""
+    Lifetime rules: a parent with live forks refuses to reload its key or circuit; destroyed first, its tables live on until
+    their last reader is gone (the forks keep proving); a fork that loads its own key stops sharing and still proves the same bytes."""
     import threading
     import zkt_plonk_amd as z
     cv = F.CURVES[cvname]
@@ -892,10 +892,10 @@ def test_forked_contexts_share_tables_and_prove_the_same_bytes(cvname, gates):
     for th in ths:
         th.join(timeout=600)
     assert not errors, errors
-    parent.close()                                # lingers: the forks still read its tables
+    parent.close()                                # its tables live on: the forks still read them
     assert forks[0].prove(a, b, c, table, pi_pos, pi_vals, K.fr_to_mont(cv, bl[1]), tr()) == want[1]
     forks[1].srs_load(srs_arr)                    # a key of its own: stops sharing that part, same bytes
     assert forks[1].prove(a, b, c, table, pi_pos, pi_vals, K.fr_to_mont(cv, bl[2]), tr()) == want[2]
     forks[0].close()
     assert forks[1].prove(a, b, c, table, pi_pos, pi_vals, K.fr_to_mont(cv, bl[0]), tr()) == want[0]
-    forks[1].close()                              # the last fork: the parent goes with it
+    forks[1].close()                              # the last reader: what is left of the parent's tables goes with it

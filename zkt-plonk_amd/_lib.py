@@ -198,6 +198,17 @@ def _seed32(seed) -> bytes:
     return seed
 
 
+def debug_live_allocations():
+    """zkt_debug_live_allocations: (count, bytes) of the device allocations the library holds now, over all contexts."""
+    L = lib()
+    L.zkt_debug_live_allocations.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+    count, nbytes = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    rc = L.zkt_debug_live_allocations(ctypes.byref(count), ctypes.byref(nbytes))
+    if rc:
+        raise ZktError(rc, "zkt_debug_live_allocations")
+    return count.value, nbytes.value
+
+
 def debug_g1_check_host(curve, points) -> np.ndarray:
     """zkt_debug_g1_check_host: the per-point rules of zkt_g1_check on the host (no device) -> status (n,) uint8."""
     L = lib()

@@ -8,6 +8,7 @@
 #include "fx_test.hpp"
 #include "msm.hpp"
 
+#include <atomic>
 #include <cstring>
 
 namespace zkt {
@@ -26,7 +27,7 @@ int set_err(zkt_ctx* c, int code, const std::string& msg) {
     return code;
 }
 int refuse_if_forked(zkt_ctx* c, const char* what) {
-    if (c && c->forks.load() > 0)
+    if (c && (msm_tables_have_readers(c) || circuit_tables_have_readers(c)))
         return set_err(c, ZKT_ERR_INVALID_ARGUMENT, std::string(what) + ": contexts forked from this one still use its tables (destroy them first)");
     return ZKT_OK;
 }
@@ -34,23 +35,54 @@ int hip_fail(zkt_ctx* c, hipError_t e, const char* what) {
     return set_err(c, ZKT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 
-int dev_alloc(zkt_ctx* c, void** p, size_t bytes) {
+// every device allocation of the library that is alive, over all contexts (zkt_debug_live_allocations)
+static std::atomic<uint64_t> live_count{0}, live_bytes{0};
+static hipError_t counted_malloc(void** p, size_t* bytes) {
     *p = nullptr;
-    if (bytes == 0) bytes = 16;
-    ZKT_HIP(c, hipMalloc(p, bytes));
-    c->owned.push_back(*p);
-    return ZKT_OK;
+    if (*bytes == 0) *bytes = 16;
+    const hipError_t e = hipMalloc(p, *bytes);
+    if (e == hipSuccess) {
+        ++live_count;
+        live_bytes += *bytes;
+    }
+    return e;
 }
-void dev_free(zkt_ctx* c, void* p) {
+static void counted_free(const std::pair<void*, size_t>& a) {
+    (void)hipFree(a.first);
+    --live_count;
+    live_bytes -= a.second;
+}
+// takes `p` out of `list` and frees it
+static void counted_free_of(std::vector<std::pair<void*, size_t>>& list, void* p) {
     if (!p) return;
-    for (size_t i = 0; i < c->owned.size(); ++i)
-        if (c->owned[i] == p) {
-            c->owned[i] = c->owned.back();
-            c->owned.pop_back();
-            (void)hipFree(p);
+    for (auto& a : list)
+        if (a.first == p) {
+            counted_free(a);
+            a = list.back();
+            list.pop_back();
             return;
         }
 }
+
+int dev_alloc(zkt_ctx* c, void** p, size_t bytes) {
+    ZKT_HIP(c, counted_malloc(p, &bytes));
+    c->owned.emplace_back(*p, bytes);
+    return ZKT_OK;
+}
+void dev_free(zkt_ctx* c, void* p) { counted_free_of(c->owned, p); }
+
+int DevShared::alloc(zkt_ctx* c, void** p, size_t bytes) {
+    ZKT_HIP(c, counted_malloc(p, &bytes));
+    mem.emplace_back(*p, bytes);
+    return ZKT_OK;
+}
+void DevShared::release(void* p) { counted_free_of(mem, p); }
+DevShared::~DevShared() {
+    if (mem.empty()) return;
+    (void)hipSetDevice(device);
+    for (const auto& a : mem) counted_free(a);
+}
+
 int ensure_buffer(zkt_ctx* c, void** p, size_t* cur, size_t bytes) {
     if (*cur >= bytes && *p) return ZKT_OK;
     if (*p) {
@@ -225,12 +257,11 @@ int zkt_ctx_fork(zkt_ctx* parent, zkt_ctx** out) {
     if (!parent || !out) return ZKT_ERR_INVALID_ARGUMENT;
     *out = nullptr;
     if (parent->sharded()) return set_err(parent, ZKT_ERR_INVALID_ARGUMENT, "zkt_ctx_fork: not for a context with a communicator");
-    if (parent->zombie) return set_err(parent, ZKT_ERR_INVALID_ARGUMENT, "zkt_ctx_fork: the context has been destroyed");
-    zkt_ctx* root = parent->parent ? parent->parent : parent;   // forks of a fork hang off the owner of the tables
     zkt_ctx* c = nullptr;
     int rc = zkt_ctx_create(parent->curve, parent->device, &c);
     if (rc) return rc;
     (void)hipStreamSynchronize(parent->stream);   // the tables are complete
+    c->is_fork = true;
     c->lagrange_off = parent->lagrange_off;
     c->wire_elim_mode = parent->wire_elim_mode;
     c->quotient_route = parent->quotient_route;
@@ -238,9 +269,7 @@ int zkt_ctx_fork(zkt_ctx* parent, zkt_ctx** out) {
     c->fused_parts = parent->fused_parts;
     c->batch_off = parent->batch_off;
     c->aux_off = parent->aux_off;
-    c->ntt_plans = parent->ntt_plans;             // twiddle tables: immutable, owned by the root
-    c->parent = root;
-    root->forks.fetch_add(1);
+    c->ntt_plans = parent->ntt_plans;             // twiddle tables: immutable, the plans' own
     if ((rc = msm_fork(c, parent)) || (rc = circuit_fork(c, parent))) {
         parent->err = c->err;
         zkt_ctx_destroy(c);
@@ -250,40 +279,30 @@ int zkt_ctx_fork(zkt_ctx* parent, zkt_ctx** out) {
     return ZKT_OK;
 }
 
+// What the context shares with others (tables, NTT plans) lives on until the last of them lets go.
 void zkt_ctx_destroy(zkt_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    if (c->forks.load() > 0) {   // forks still read this context's tables: linger until the last of them is gone
-        c->zombie = true;
-        return;
-    }
-    zkt_ctx* const owner = c->parent;
     circuit_release(c);
     msm_release(c);
     prof_resolve(c);
     for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
     c->event_pool.clear();
     c->ntt_plans.clear();
-    c->msm.reset();
     c->msmb.reset();   // zkt_msm_g1_bases scratch: its device buffers are freed with c->owned below, its pinned rows here
     c->kzg.reset();    // the KZG seam's copy stream and events; its device buffers go with c->owned
-    c->circuit.reset();
     if (c->comm.pinned) (void)hipHostFree(c->comm.pinned);
-    for (void* p : c->owned) (void)hipFree(p);
+    for (const auto& a : c->owned) counted_free(a);
     c->owned.clear();
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
-    if (owner && owner->forks.fetch_sub(1) == 1 && owner->zombie) {
-        owner->zombie = false;
-        zkt_ctx_destroy(owner);
-    }
 }
 
 int zkt_ctx_set_comm(zkt_ctx* c, const zkt_comm_vtable* comm) {
     if (!c) return ZKT_ERR_INVALID_ARGUMENT;
     if (int rf = refuse_if_forked(c, "zkt_ctx_set_comm")) return rf;
-    if (c->parent && comm && comm->world > 1) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "a forked context cannot take a communicator");
+    if (c->is_fork && comm && comm->world > 1) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "a forked context cannot take a communicator");
     if (comm && comm->world > 1) {
         const int w = comm->world;
         if ((w != 2 && w != 4 && w != 8) || comm->rank < 0 || comm->rank >= w || !comm->all_gather)
@@ -448,6 +467,13 @@ int zkt_domain_group_gen(zkt_ctx* c, int log_n, uint64_t* out4) {
         Fe<Bls381Fr> w = root_of_unity<Bls381Fr>(log_n);
         memcpy(out4, w.v, 32);
     }
+    return ZKT_OK;
+}
+
+int zkt_debug_live_allocations(uint64_t* count, uint64_t* bytes) {
+    if (!count || !bytes) return ZKT_ERR_INVALID_ARGUMENT;
+    *count = live_count.load();
+    *bytes = live_bytes.load();
     return ZKT_OK;
 }
 

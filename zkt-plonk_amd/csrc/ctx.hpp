@@ -8,7 +8,6 @@
 #include <tuple>
 #include <vector>
 #include <memory>
-#include <atomic>
 
 #include "../../include/zkt_plonk.h"
 #include "fp.hpp"
@@ -33,6 +32,7 @@ struct zkt_ctx {
 
     // NTT plans keyed by (log_n, inverse, coset, split); tables live in HBM for the ctx lifetime.  split: 0 = the policy's
     // radices, otherwise the forced ones of zkt_debug_ntt_split (ntt_split_code), so the two never serve each other.
+    // A plan owns its tables (NttPlan::mem), so the pointers a fork copies keep them alive.
     // (A fork copies the map, forced plans included; its own split stays 0, so it never looks one of those up.)
     std::map<std::tuple<int, int, int, int>, std::shared_ptr<void>> ntt_plans;
     int ntt_split_npass = 0;                 // zkt_debug_ntt_split: 0 = policy, else 2 or 3 passes of ntt_split_log_r
@@ -75,11 +75,7 @@ struct zkt_ctx {
     size_t srs_check_chunk = 0;                 // zkt_debug_srs_check_chunk: points per chunk of zkt_srs_check, 0 = ZKT_MSM_BASES_MAX
     uint64_t msm_epoch = 0;   // bumped by every MSM enqueue and SRS (re)load: work issued ahead of time is tied to it
     uint64_t srs_generation = 0;   // bumped by every SRS (re)load: cached commitments are tied to the key they were made under
-    // zkt_ctx_fork: forks share this context's read-only tables.  A parent with live forks refuses to reload them; when it
-    // is destroyed first it lingers (zombie) until its last fork is gone.
-    zkt_ctx* parent = nullptr;
-    std::atomic<int> forks{0};
-    bool zombie = false;
+    bool is_fork = false;     // made by zkt_ctx_fork: no forced NTT split, no communicator
     bool aux_off = false;          // A/B builds: ZKT_NO_AUX keeps round 5's second opening on the main stream
     bool batch_off = false;        // A/B builds: ZKT_MSM_NO_BATCH commits a round's polynomials one launch sequence each
     bool lagrange_off = false;     // zkt_ctx_set_lagrange(ctx, 0): evaluations are committed through their coefficients
@@ -93,7 +89,7 @@ struct zkt_ctx {
     int fused_parts = 63;
     bool fused(int part) const { return fused_passes != 2 && (fused_parts & part); }
     std::shared_ptr<zkt::CircuitState> circuit;
-    std::vector<void*> owned;  // every hipMalloc made on behalf of this ctx
+    std::vector<std::pair<void*, size_t>> owned;  // every dev_alloc made on behalf of this ctx, with its size
 };
 
 namespace zkt {
@@ -104,7 +100,7 @@ namespace zkt {
 const char* exp_env(const char* name);
 
 int set_err(zkt_ctx* c, int code, const std::string& msg);
-// ZKT_ERR_INVALID_ARGUMENT when forks of `c` are alive (their tables are c's)
+// ZKT_ERR_INVALID_ARGUMENT while a context forked from `c` still reads one of c's key or circuit tables
 int refuse_if_forked(zkt_ctx* c, const char* what);
 int hip_fail(zkt_ctx* c, hipError_t e, const char* what);
 
@@ -145,6 +141,30 @@ inline int grow(zkt_ctx* c, DevBuf& b, size_t bytes) { return ensure_buffer(c, &
 int dev_alloc(zkt_ctx* c, void** p, size_t bytes);
 void dev_free(zkt_ctx* c, void* p);
 
+// Device memory that several contexts may read (zkt_ctx_fork): tables that are complete before a second context sees
+// them.  It belongs to no context: it is held through shared_ptr and freed with the last holder, in whatever order the
+// contexts go.  A fork does not copy its source's pointer, it reads through a holder of its own that keeps the source's
+// alive (dev_shared_reader), so use_count() > 1 on a context's holder means exactly: a context forked from this one, or
+// from one forked from it, still reads these tables.
+struct DevShared {
+    const int device;
+    std::vector<std::pair<void*, size_t>> mem;
+    std::shared_ptr<DevShared> from;   // a fork's holder: the tables are this one's
+    explicit DevShared(int dev) : device(dev) {}
+    DevShared(const DevShared&) = delete;
+    DevShared& operator=(const DevShared&) = delete;
+    ~DevShared();
+    int alloc(zkt_ctx* c, void** p, size_t bytes);   // as dev_alloc; the error, if any, is c's
+    void release(void* p);                           // one allocation ahead of the rest (a build that did not succeed)
+};
+inline std::shared_ptr<DevShared> dev_shared_reader(const std::shared_ptr<DevShared>& of) {
+    if (!of) return nullptr;
+    auto r = std::make_shared<DevShared>(of->device);
+    r->from = of;
+    return r;
+}
+inline bool dev_shared_has_readers(const std::shared_ptr<DevShared>& m) { return m && m.use_count() > 1; }
+
 // ntt.hip
 template <class P>
 Fe<P> root_of_unity(int log_n);
@@ -171,5 +191,6 @@ int ntt_run_class(zkt_ctx* c, int log_n, int log_big, int cls, const void* d_in,
 void circuit_release(zkt_ctx* c);
 // a circuit state of its own over the parent's read-only tables (zkt_ctx_fork)
 int circuit_fork(zkt_ctx* child, const zkt_ctx* parent);
+bool circuit_tables_have_readers(const zkt_ctx* c);
 
 }  // namespace zkt

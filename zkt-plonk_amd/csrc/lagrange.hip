@@ -175,12 +175,12 @@ static int lagrange_build_t(zkt_ctx* c, int log_n) {
     const size_t count2 = n + extra;
     int rc;
     void *A = nullptr, *tw = nullptr, *seg = nullptr, *table2 = nullptr;
-    if ((rc = dev_alloc(c, &table2, (size_t)st.plan.W * count2 * sizeof(Affine<Q>)))) return rc;
+    auto mem = std::make_shared<DevShared>(c->device);   // the table goes with it unless the build succeeds
+    if ((rc = mem->alloc(c, &table2, (size_t)st.plan.W * count2 * sizeof(Affine<Q>)))) return rc;
     auto release = [&](int code) {
         dev_free(c, A);
         dev_free(c, tw);
         dev_free(c, seg);
-        if (code) dev_free(c, table2);
         return code;
     };
     if ((rc = dev_alloc(c, &A, n * sizeof(Xyzz<Q>)))) return release(rc);
@@ -222,8 +222,7 @@ static int lagrange_build_t(zkt_ctx* c, int log_n) {
     if (hipGetLastError() != hipSuccess) return release(set_err(c, ZKT_ERR_HIP, "Lagrange key: launch failed"));
     if ((rc = msm_table_finish(c, table2, count2))) return release(rc);   // synchronises: `pre` may go
     wire_bases_drop(c);   // sums of the table being replaced
-    if (!st.table2_borrowed) dev_free(c, st.table2);
-    st.table2_borrowed = false;
+    st.lag_mem = mem;
     st.table2 = table2;
     st.count2 = count2;
     st.lag_log_n = log_n;
@@ -241,10 +240,7 @@ int lagrange_ensure(zkt_ctx* c, int log_n) {
     const bool whole_key = !c->sharded() && st.slice_off == 0 && st.total == st.count;
     if (!whole_key || st.count <= n || log_n > 30 || (uint64_t)st.plan.W * (n + LAG_MAX_EXTRA) >= ((uint64_t)1 << 31)) {
         wire_bases_drop(c);
-        if (!st.table2_borrowed) dev_free(c, st.table2);
-        st.table2_borrowed = false;
-        st.table2 = nullptr;
-        st.count2 = 0;
+        static_cast<LagrangeTable&>(st) = LagrangeTable{};
         st.lag_log_n = log_n;
         st.lag_failed = true;
         return ZKT_OK;
@@ -388,13 +384,7 @@ __global__ void k_wire_scalars(const Fe<P>* vars, const uint32_t* u, size_t cnt,
 void wire_bases_drop(zkt_ctx* c) {
     if (!c->msm) return;
     WireBases& wb = c->msm->wb;
-    if (!wb.borrowed && wb.built) {
-        (void)hipStreamSynchronize(c->stream);
-        for (int k = 0; k < 3; ++k) {
-            dev_free(c, wb.table[k]);
-            dev_free(c, wb.u[k]);
-        }
-    }
+    if (wb.built) (void)hipStreamSynchronize(c->stream);
     wb = WireBases{};
 }
 
@@ -489,14 +479,14 @@ static int wire_bases_build_wire(zkt_ctx* c, int log_n, int k, const uint32_t* d
     void *table = nullptr, *d_u = nullptr;
     auto done = [&](bool keep) {   // a wire that cannot have its table is committed through its coefficients: never an error
         wire_groups_free(c, g);
-        if (!keep) { dev_free(c, table); dev_free(c, d_u); }
+        if (!keep) { wb.mem->release(table); wb.mem->release(d_u); }
         (void)hipGetLastError();
         return ZKT_OK;
     };
     if (!wire_groups_count(c, d_idx, n_rows, n_vars, g)) return done(false);
     const size_t d = g.d;
     if ((double)d >= frac * (double)n_rows || (uint64_t)st.plan.W * (d + 2) >= ((uint64_t)1 << 31)) return done(false);
-    if (dev_alloc(c, &table, (size_t)st.plan.W * (d + 2) * sizeof(Affine<Q>)) || dev_alloc(c, &d_u, (d + 1) * 4)) return done(false);
+    if (wb.mem->alloc(c, &table, (size_t)st.plan.W * (d + 2) * sizeof(Affine<Q>)) || wb.mem->alloc(c, &d_u, (d + 1) * 4)) return done(false);
     if (hipMemcpyAsync(d_u, g.u.data(), d * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess) return done(false);
     if (!wire_points<C>(c, d_idx, n_rows, n_vars, g, (Affine<Q>*)table)) return done(false);
     hipLaunchKernelGGL(k_wire_blinder_points<C>, dim3(1), dim3(64), 0, c->stream, (const Affine<Q>*)st.table2, n, d, (Affine<Q>*)table);
@@ -684,7 +674,7 @@ static bool wire_elim_build_wire(zkt_ctx* c, int log_n, int k, const uint32_t* d
     auto done = [&](bool keep) {
         wire_groups_free(c, g);
         dev_free(c, d_T); dev_free(c, d_pos); dev_free(c, d_piece); dev_free(c, d_pstart); dev_free(c, d_part); dev_free(c, d_flag);
-        if (!keep) { dev_free(c, table); dev_free(c, d_u); }
+        if (!keep) { wb.mem->release(table); wb.mem->release(d_u); }
         (void)hipGetLastError();
         return keep;
     };
@@ -717,8 +707,8 @@ static bool wire_elim_build_wire(zkt_ctx* c, int log_n, int k, const uint32_t* d
     if (D.n_const) cut(nf);
     const size_t groups = pstart.size() - 1, np = piece.size();
     if (dev_alloc(c, &d_T, d * sizeof(Affine<Q>)) || dev_alloc(c, &d_pos, n_vars * 4) || dev_alloc(c, &d_piece, np * sizeof(uint2)) ||
-        dev_alloc(c, &d_pstart, (groups + 1) * 4) || dev_alloc(c, &d_u, (cnt + 1) * 4) || dev_alloc(c, &d_part, np * sizeof(Xyzz<Q>)) ||
-        dev_alloc(c, &d_flag, 8) || dev_alloc(c, &table, (size_t)st.plan.W * (cnt + 3) * sizeof(Affine<Q>)))
+        dev_alloc(c, &d_pstart, (groups + 1) * 4) || wb.mem->alloc(c, &d_u, (cnt + 1) * 4) || dev_alloc(c, &d_part, np * sizeof(Xyzz<Q>)) ||
+        dev_alloc(c, &d_flag, 8) || wb.mem->alloc(c, &table, (size_t)st.plan.W * (cnt + 3) * sizeof(Affine<Q>)))
         return done(false);
     if (hipMemcpyAsync(d_pos, pos.data(), n_vars * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
         hipMemcpyAsync(d_piece, piece.data(), np * sizeof(uint2), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
@@ -794,13 +784,14 @@ int wire_bases_prepare(zkt_ctx* c, int log_n, const uint32_t* const* d_idx, size
                       wb.n_rows == n_rows && wb.n_vars == n_vars && wb.log_n == log_n && wb.srs_generation == c->srs_generation &&
                       wb.elim_wanted == (ew != nullptr) && wb.pi_pos == pi;
     if (possible && same) return ZKT_OK;
-    // tables that forks of this context read stay where they are: this context then commits densely until they are gone
-    if (wb.built && !wb.borrowed && c->forks.load() > 0) {
+    // tables that contexts forked from this one read stay where they are: this context then commits densely until they are gone
+    if (wb.built && dev_shared_has_readers(wb.mem)) {
         if (!same || !possible) wb.stale = true;
         return ZKT_OK;
     }
     wire_bases_drop(c);
     if (!possible) return ZKT_OK;
+    wb.mem = std::make_shared<DevShared>(c->device);
     double frac = WIRE_BASES_MAX_FRAC;
     if (const char* e = exp_env("ZKT_WIRE_BASES_FRAC")) frac = atof(e);   // experiment: the threshold's A/B
     hipEvent_t e0 = nullptr, e1 = nullptr;

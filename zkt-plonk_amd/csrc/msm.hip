@@ -1127,20 +1127,18 @@ static int msm_setup(zkt_ctx* c, size_t count, const MsmState* share = nullptr) 
     const MsmPlan& P = st->plan;
     if (share) {   // zkt_ctx_fork: the parent's tables (same count, hence the same layout), everything below this context's own
         st->table = share->table;
-        st->table_borrowed = true;
-        st->table2 = share->table2;
-        st->table2_borrowed = share->table2 != nullptr;
-        st->count2 = share->count2;
-        st->lag_log_n = share->lag_log_n;
-        st->lag_failed = share->lag_failed;
+        st->table_mem = dev_shared_reader(share->table_mem);
+        static_cast<LagrangeTable&>(*st) = *share;
+        st->lag_mem = dev_shared_reader(share->lag_mem);
         if (share->wb.built && !share->wb.stale) {   // the wire base tables that exist now; later ones this context builds itself
             st->wb = share->wb;
-            st->wb.borrowed = true;
+            st->wb.mem = dev_shared_reader(share->wb.mem);
         }
         st->slice_off = share->slice_off;
         st->total = share->total;
-    } else if ((rc = dev_alloc(c, &st->table, (size_t)P.W * count * sizeof(Affine<Q>)))) {
-        return rc;
+    } else {
+        st->table_mem = std::make_shared<DevShared>(c->device);
+        if ((rc = st->table_mem->alloc(c, &st->table, (size_t)P.W * count * sizeof(Affine<Q>)))) return rc;
     }
     size_t m = (size_t)P.W * count;
     // the main-stream work buffers exist MSM_BATCH times (a round's commitments are grouped and accumulated as one batch:
@@ -1239,14 +1237,18 @@ void msm_release(zkt_ctx* c) {
     wire_bases_drop(c);
     for (DevBuf& b : st.wb_scalars) dev_free(c, b.p);
     dev_free(c, st.wb_dig);
-    void* ptrs[] = {st.table_borrowed ? nullptr : st.table, st.table2_borrowed ? nullptr : st.table2, st.vals2, st.pairs,
-                    st.bin_offs, st.bin_aux, st.bin_start, st.tile_start, st.cnt2, st.pos2, st.chunk_bucket, st.tile_desc};
+    void* ptrs[] = {st.vals2, st.pairs, st.bin_offs, st.bin_aux, st.bin_start, st.tile_start, st.cnt2, st.pos2, st.chunk_bucket,
+                    st.tile_desc};
     for (void* p : ptrs) dev_free(c, p);
     for (int i = 0; i < MsmState::SLOTS; ++i) {
         dev_free(c, st.heavy[i]); dev_free(c, st.offsets[i]); dev_free(c, st.pieces[i]); dev_free(c, st.params[i]);
         dev_free(c, st.buckets[i]); dev_free(c, st.rowcol[i]);
     }
-    c->msm.reset();
+    c->msm.reset();   // lets go of the base tables: they are freed here unless a fork still reads them
+}
+bool msm_tables_have_readers(const zkt_ctx* c) {
+    return c->msm && (dev_shared_has_readers(c->msm->table_mem) || dev_shared_has_readers(c->msm->lag_mem) ||
+                      dev_shared_has_readers(c->msm->wb.mem));
 }
 
 template <class C>

@@ -78,6 +78,7 @@ constexpr int MSM_HEAVY_BLOCKS = 64;     // grid-stride over the (normally empty
 // of the wire.  The tables depend on the key and the wiring only; they are keyed on the index vectors' addresses and
 // sizes, the key and the domain, and carry a digest of the vectors' contents that every proof checks.
 struct WireBases {
+    std::shared_ptr<DevShared> mem;   // owns table[] and u[]; a context forked after the build reads them through it
     void* table[3] = {};       // Affine[W][cnt + 2]: T of every distinct variable (ascending), then the two blinder points
     uint32_t* u[3] = {};       // the cnt distinct variables, ascending
     size_t cnt[3] = {};
@@ -89,7 +90,6 @@ struct WireBases {
     bool elim_wanted = false;  // part of the key: the build was asked to eliminate, for the public-input positions below
     std::vector<size_t> pi_pos;   // ascending
     bool built = false;        // the key below was examined (use[] says what came of it)
-    bool borrowed = false;     // zkt_ctx_fork: the parent's tables (never freed here)
     bool stale = false;        // a proof found other index contents than the digest: rebuild before the next use
     const void* w[3] = {};
     size_t n_rows = 0, n_vars = 0;
@@ -99,22 +99,27 @@ struct WireBases {
 };
 constexpr int MSM_TBL_WIRE = 2;      // msm_begin tbl = MSM_TBL_WIRE + k: the table of wire k (0 left, 1 right, 2 output)
 
-struct MsmState {
+// Second base table (lagrange.hip): prefix sums of the Lagrange-basis key of the domain of size 2^lag_log_n followed by
+// the blinder points, same window layout, count2 <= count bases.  Commitments of polynomials given by their
+// evaluations go through it (msm_begin table = 1).  Null until a circuit of that size asks for it.
+struct LagrangeTable {
+    std::shared_ptr<DevShared> lag_mem;   // owns table2
+    void* table2 = nullptr;
+    size_t count2 = 0;
+    int lag_log_n = -1;
+    bool lag_failed = false;       // the key is too short (or sharded): evaluations are committed through their coefficients
+};
+
+struct MsmState : LagrangeTable {
     size_t count = 0;      // bases loaded
     // index-range sharding: this GPU holds powers [slice_off, slice_off + count) of a key of `total`
     size_t slice_off = 0, total = 0;
     MsmPlan plan;          // window and sort layout for `count` bases (shared buckets)
     uint32_t* heavy[11] = {};   // per slot: [0] = count, [1..] = heavy bucket ids
+    // The key's window table.  It, the Lagrange table and the wire tables are read-only once built: a fork reads its
+    // source's through holders of its own (zkt_ctx_fork), everything else below is each context's own.
+    std::shared_ptr<DevShared> table_mem;
     void* table = nullptr; // Affine[W][count]
-    // Second base table (lagrange.hip): prefix sums of the Lagrange-basis key of the domain of size 2^lag_log_n followed by
-    // the blinder points, same window layout, count2 <= count bases.  Commitments of polynomials given by their
-    // evaluations go through it (msm_begin table = 1).  Null until a circuit of that size asks for it.
-    void* table2 = nullptr;
-    size_t count2 = 0;
-    int lag_log_n = -1;
-    bool lag_failed = false;       // the key is too short (or sharded): evaluations are committed through their coefficients
-    // zkt_ctx_fork: the base tables belong to the context this one was forked from (read-only here, never freed here)
-    bool table_borrowed = false, table2_borrowed = false;
     WireBases wb;
     DevBuf wb_scalars[3];          // per wire: cnt + 2 scalars of the proof being enqueued (read by its grouping launches only)
     uint64_t* wb_dig = nullptr;    // device: the digest kernel's two sums
@@ -194,6 +199,7 @@ constexpr size_t MSM_TAIL_INL_MAX = ((size_t)1 << 18) + 64;   // up to here the 
 int srs_load(zkt_ctx* c, const void* src, size_t count, bool on_device, size_t slice_off = 0, size_t total = 0);
 int srs_generate(zkt_ctx* c, const uint64_t* tau4, size_t count, size_t slice_off = 0, size_t total = 0);
 void msm_release(zkt_ctx* c);
+bool msm_tables_have_readers(const zkt_ctx* c);   // a fork still reads the key's, the Lagrange or the wire tables of `c`
 // window multiples + R' conversion of an affine base table whose first `count` entries are filled (arkworks R form)
 int msm_table_finish(zkt_ctx* c, void* table, size_t count);
 // `child` gets an MSM state of its own (work buffers, slots, side stream) over `parent`'s base tables (zkt_ctx_fork)

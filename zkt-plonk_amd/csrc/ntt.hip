@@ -446,7 +446,7 @@ static int ntt_split_code(const zkt_ctx* c) {
 }
 
 int ntt_force_split(zkt_ctx* c, int npass, const int* log_r) {
-    if (c->parent) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "zkt_debug_ntt_split: a forked context shares its root's plans");
+    if (c->is_fork) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "zkt_debug_ntt_split: a forked context shares its root's plans");
     if (npass == 0) {
         c->ntt_split_npass = 0;
         return ZKT_OK;
@@ -459,18 +459,15 @@ int ntt_force_split(zkt_ctx* c, int npass, const int* log_r) {
 }
 
 template <class P>
-struct PlanHolder {
-    NttPlan<P> plan;
-    zkt_ctx* ctx;
-    ~PlanHolder() {}
-};
-
+static int alloc_bytes(zkt_ctx* c, NttPlan<P>& pl, void** p, size_t bytes) {
+    int rc = pl.mem->alloc(c, p, bytes);
+    if (rc) return rc;
+    pl.table_bytes += bytes;
+    return 0;
+}
 template <class P>
 static int alloc_table(zkt_ctx* c, NttPlan<P>& pl, void** p, size_t count) {
-    int rc = dev_alloc(c, p, count * sizeof(Fe<P>));
-    if (rc) return rc;
-    pl.table_bytes += count * sizeof(Fe<P>);
-    return 0;
+    return alloc_bytes(c, pl, p, count * sizeof(Fe<P>));
 }
 
 template <class P>
@@ -519,6 +516,7 @@ static int build_plan(zkt_ctx* c, int log_n, int inverse, int coset, bool forced
     pl.log_n = log_n;
     pl.inverse = inverse;
     pl.coset = coset;
+    pl.mem = std::make_shared<DevShared>(c->device);
     if (forced) {
         pl.npass = c->ntt_split_npass;
         for (int i = 0; i < 3; ++i) pl.log_r[i] = c->ntt_split_log_r[i];
@@ -615,8 +613,7 @@ static int build_plan(zkt_ctx* c, int log_n, int inverse, int coset, bool forced
         const Fx<P> npinv = fx_neg_p_inverse<P>();
         for (int i = 0; i < p; ++i) {
             const uint64_t cnt = (uint64_t)1 << (pl.log_r[i] - 1);
-            if ((rc = dev_alloc(c, &pl.w_inner_s[i], cnt * 72 + 16))) return rc;
-            pl.table_bytes += cnt * 72 + 16;
+            if ((rc = alloc_bytes(c, pl, &pl.w_inner_s[i], cnt * 72 + 16))) return rc;
             hipLaunchKernelGGL(k_table_to_shoup<P>, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, c->stream,
                                (const Fe<P>*)pl.w_inner[i], pl.w_inner_s[i], cnt, npinv);
             ZKT_HIP(c, hipGetLastError());

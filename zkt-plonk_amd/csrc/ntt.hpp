@@ -17,8 +17,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <memory>
 
 namespace zkt {
+
+struct DevShared;   // ctx.hpp
 
 constexpr int NTT_HEAD = 8;        // coefficients a transform may take from a folded head (NttPassArgs::head)
 constexpr int NTT_MAX_BATCH = 4;   // transforms of one plan issued as ONE launch per pass (gridDim.y = polynomial)
@@ -67,6 +70,8 @@ struct NttPlan {
     void* small_in = nullptr;   // optional N-entry input scale
     void* small_out = nullptr;  // optional N-entry output scale
     size_t table_bytes = 0;
+    // owns every table above: contexts forked from the builder keep the plan, and with it the tables, alive
+    std::shared_ptr<DevShared> mem;
 };
 
 }  // namespace zkt

@@ -29,7 +29,30 @@ enum { PK_QM = 0, PK_QL, PK_QR, PK_QO, PK_QC, PK_S1, PK_S2, PK_S3, PK_QLOOKUP, P
 enum { CS_QM = 0, CS_QL, CS_QR, CS_QO, CS_QC, CS_QLOOKUP, CS_QTABLE, CS_S1, CS_S2, CS_S3, CS_X, CS_L1, CS_COUNT };
 enum { W_A = 0, W_B, W_C, W_PI, W_Z1, W_Z2, W_T, W_H1, W_H2, W_COUNT };  // witness cosets of quotient_poly.rs:52-96
 
-struct CircuitState {
+// The keys (ProverKey polynomials, ExtendedProverKey cosets, sigma / q_lookup evaluations, domain roots): read-only for a
+// prover, so a fork reads its source's (circuit_fork)
+struct CircuitKeys {
+    std::shared_ptr<DevShared> keys_mem;   // owns every array below
+    void* pk[PK_COUNT] = {};
+    size_t pk_len[PK_COUNT] = {};
+    void* coset[CS_COUNT] = {};
+    void* sigma_ev[3] = {};
+    void* q_lookup_ev = nullptr;
+    void* roots = nullptr;
+    uint32_t zh_inv[4][8] = {};
+};
+// The tables of the quotient on classes 0, 1, 2 of the 4n coset (quotient_classes.hpp): ccoset[] are coset[] as [3][n]
+// class arrays, key_win the windows of sigma1..3 and q_lookup.  Built on first use (ensure_class_tables), keys as well:
+// contexts forked afterwards read them.
+struct ClassTables {
+    std::shared_ptr<DevShared> class_mem;   // owns ccoset[]
+    void* ccoset[CS_COUNT] = {};
+    bool ccoset_ready = false;
+    uint32_t key_win[4][QCW][8] = {};
+    uint32_t qc_gamma[4][8] = {}, qc_vinv[9][8] = {}, qc_g3[3][8] = {};
+};
+
+struct CircuitState : CircuitKeys, ClassTables {
     int log_n = 0;
     size_t n = 0;
     // A proof sharded over G GPUs (zkt_ctx_set_comm): this GPU owns the 4n-coset points of global index cls modulo G,
@@ -40,13 +63,6 @@ struct CircuitState {
     void* fold = nullptr;      // m elements: a polynomial folded modulo X^m - shift^m before its class transform
     void* qgather = nullptr;   // 4n elements: every rank's quotient evaluations, class-major (the all-gather's target)
     bool have[16] = {};        // commitment slot -> this rank's SRS slice takes part (an MSM was started)
-    void* pk[PK_COUNT] = {};
-    size_t pk_len[PK_COUNT] = {};
-    void* coset[CS_COUNT] = {};
-    void* sigma_ev[3] = {};
-    void* q_lookup_ev = nullptr;
-    void* roots = nullptr;
-    uint32_t zh_inv[4][8] = {};
     // per-proof work buffers
     void* ev[8] = {};       // a, b, c, t, f, h1, h2, pi   (n each)
     void* sc[4] = {};       // scan scratch: num, den, PN, SD (n each)
@@ -96,20 +112,13 @@ struct CircuitState {
     bool t_cached = false, t_coset_valid = false;
     uint64_t t_srs_generation = 0;   // zkt_ctx::srs_generation the cached commitment was made under
     uint64_t t_commit_xy[12] = {};
-    // zkt_ctx_fork: the keys (pk, coset, sigma_ev, q_lookup_ev, roots) belong to the context this one was forked from
-    bool keys_borrowed = false;
     // wire base tables (lagrange.hip): the wires of the round 1 last enqueued that were committed over them; their digest
     // and trimmed lengths are compared when that round is collected (collect_wires)
     bool wire_route[3] = {};
     bool wire_dense_only = false;   // zkt_debug_commit_wires_dev route 0
     int wire_elim_force = -1;       // zkt_debug_commit_wires_dev: 0 = per-variable tables only (route 1), 1 = over free variables (route 2)
-    // The quotient on classes 0, 1, 2 of the 4n coset (single GPU, zkt_ctx_set_quotient_route; quotient_classes.hpp).
-    // ccoset[] are coset[] as [3][n] class arrays, built on first use (circuit_class_tables) and shared with forks made
-    // afterwards; wcos[] then hold [3][n] as well.  key_win: the windows of sigma1..3 and q_lookup.
-    void* ccoset[CS_COUNT] = {};
-    bool ccoset_borrowed = false, ccoset_ready = false;
-    uint32_t key_win[4][QCW][8] = {};
-    uint32_t qc_gamma[4][8] = {}, qc_vinv[9][8] = {}, qc_g3[3][8] = {};
+    // The quotient on classes 0, 1, 2 of the 4n coset (single GPU, zkt_ctx_set_quotient_route; ClassTables above): wcos[]
+    // then hold [3][n] as well.
     bool use_classes = false;       // the route of the proof in flight: layout of wcos[] and of the resident t coset
     void* heads = nullptr;          // 3 x NTT_MAX_BATCH x NTT_HEAD folded head coefficients of the batch being transformed
     void* d_win = nullptr;          // QC_WIN_POLYS windows (a b c z1 z2 t), gathered in round 3 ...
@@ -601,8 +610,9 @@ struct Prover {
         if (S.ccoset_ready) return ZKT_OK;
         const size_t n = S.n;
         int rc;
+        if (!S.class_mem) S.class_mem = std::make_shared<DevShared>(c->device);
         for (int k = 0; k < CS_COUNT; ++k) {
-            if (!S.ccoset[k] && (rc = dev_alloc(c, &S.ccoset[k], 3 * n * 32))) return rc;
+            if (!S.ccoset[k] && (rc = S.class_mem->alloc(c, &S.ccoset[k], 3 * n * 32))) return rc;
             if ((rc = quotient_classes_of_coset(c, S.coset[k], S.ccoset[k], n))) return rc;
         }
         static const int key_of[4] = {PK_S1, PK_S2, PK_S3, PK_QLOOKUP};
@@ -1397,18 +1407,11 @@ void circuit_release(zkt_ctx* c) {
     CircuitState& S = *c->circuit;
     if (S.copy_stream) (void)hipStreamSynchronize(S.copy_stream);
     auto fr = [&](void* p) { dev_free(c, p); };
-    if (!S.keys_borrowed) {
-        for (void* p : S.pk) fr(p);
-        for (void* p : S.coset) fr(p);
-        for (void* p : S.sigma_ev) fr(p);
-        fr(S.q_lookup_ev); fr(S.roots);
-    }
     for (void* p : S.ev) fr(p);
     for (void* p : S.sc) fr(p);
     fr(S.scan_tmp);
     for (void* p : S.poly) fr(p);
     for (void* p : S.wcos) fr(p);
-    if (!S.ccoset_borrowed) for (void* p : S.ccoset) fr(p);
     fr(S.heads); fr(S.d_win);
     if (S.pinned_win) (void)hipHostFree(S.pinned_win);
     if (S.ev_win) (void)hipEventDestroy(S.ev_win);
@@ -1439,7 +1442,10 @@ void circuit_release(zkt_ctx* c) {
     }
     for (auto e : S.ev_piece) if (e) (void)hipEventDestroy(e);
     if (S.ev_gathered) (void)hipEventDestroy(S.ev_gathered);
-    c->circuit.reset();
+    c->circuit.reset();   // lets go of the keys and class tables: they are freed here unless a fork still reads them
+}
+bool circuit_tables_have_readers(const zkt_ctx* c) {
+    return c->circuit && (dev_shared_has_readers(c->circuit->keys_mem) || dev_shared_has_readers(c->circuit->class_mem));
 }
 
 // Everything a context needs PER PROOF (work buffers, staging, streams, events) for the circuit shape in S (log_n, G, cls
@@ -1497,8 +1503,7 @@ static int circuit_alloc_work(zkt_ctx* c, CircuitState& S) {
     return ZKT_OK;
 }
 
-// zkt_ctx_fork: the parent's keys (ProverKey polynomials, ExtendedProverKey cosets, sigma / q_lookup evaluations, domain
-// roots: all read-only for a prover), this context's own work set
+// zkt_ctx_fork: the parent's keys and, where they exist, its class tables; this context's own work set
 int circuit_fork(zkt_ctx* child, const zkt_ctx* parent) {
     circuit_release(child);
     if (!parent->circuit) return ZKT_OK;
@@ -1506,20 +1511,11 @@ int circuit_fork(zkt_ctx* child, const zkt_ctx* parent) {
     auto st = std::make_shared<CircuitState>();
     CircuitState& S = *st;
     S.log_n = P0.log_n; S.n = P0.n; S.G = P0.G; S.cls = P0.cls; S.log_m = P0.log_m; S.m = P0.m;
-    for (int k = 0; k < PK_COUNT; ++k) { S.pk[k] = P0.pk[k]; S.pk_len[k] = P0.pk_len[k]; }
-    for (int k = 0; k < CS_COUNT; ++k) S.coset[k] = P0.coset[k];
-    for (int k = 0; k < 3; ++k) S.sigma_ev[k] = P0.sigma_ev[k];
-    S.q_lookup_ev = P0.q_lookup_ev;
-    S.roots = P0.roots;
-    memcpy(S.zh_inv, P0.zh_inv, sizeof(S.zh_inv));
-    S.keys_borrowed = true;
-    if (P0.ccoset_ready) {   // the class arrays of the quotient on classes are keys as well
-        for (int k = 0; k < CS_COUNT; ++k) S.ccoset[k] = P0.ccoset[k];
-        memcpy(S.key_win, P0.key_win, sizeof(S.key_win));
-        memcpy(S.qc_gamma, P0.qc_gamma, sizeof(S.qc_gamma));
-        memcpy(S.qc_vinv, P0.qc_vinv, sizeof(S.qc_vinv));
-        memcpy(S.qc_g3, P0.qc_g3, sizeof(S.qc_g3));
-        S.ccoset_borrowed = S.ccoset_ready = true;
+    static_cast<CircuitKeys&>(S) = P0;
+    S.keys_mem = dev_shared_reader(P0.keys_mem);
+    if (P0.ccoset_ready) {
+        static_cast<ClassTables&>(S) = P0;
+        S.class_mem = dev_shared_reader(P0.class_mem);
     }
     child->circuit = st;                      // from here on circuit_release cleans up after a failure
     const int rc = circuit_alloc_work(child, S);
@@ -1548,7 +1544,8 @@ static int circuit_load_t(zkt_ctx* c, int log_n, const uint64_t* const* polys, c
     S.m = (size_t)1 << S.log_m;
     const size_t m = S.m;
     int rc;
-    auto alloc = [&](void** p, size_t elems) { return dev_alloc(c, p, elems * 32); };
+    S.keys_mem = std::make_shared<DevShared>(c->device);
+    auto alloc = [&](void** p, size_t elems) { return S.keys_mem->alloc(c, p, elems * 32); };
     if ((rc = circuit_alloc_work(c, S))) return rc;   // (the quotient vector doubles as staging below)
     for (int k = 0; k < PK_COUNT; ++k) {
         if (lens[k] > n) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "prover-key polynomial longer than n");
