@@ -14,6 +14,7 @@ from helpers import field_elems
 CURVES = [F.BN254, F.BLS12_381]
 SIZES = [8, 16, 128, 2048]
 SHAPE = {8: dict(gates=7, table=4, n_public=1, lookup_every=3), 16: dict(gates=14, table=8, n_public=2, lookup_every=5),
+         32: dict(gates=28, table=8, n_public=3, lookup_every=5),
          128: dict(gates=120, table=16, n_public=7, lookup_every=16), 2048: dict(gates=2000, table=64, n_public=20, lookup_every=16)}
 CLASSES, WHOLE = 1, 2
 

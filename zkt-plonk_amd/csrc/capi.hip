@@ -47,53 +47,67 @@ static hipError_t counted_malloc(void** p, size_t* bytes) {
     }
     return e;
 }
+
+int DevSet::alloc(zkt_ctx* c, void** p, size_t bytes) {
+    ZKT_HIP(c, counted_malloc(p, &bytes));
+    mem.emplace_back(*p, bytes);
+    return ZKT_OK;
+}
 static void counted_free(const std::pair<void*, size_t>& a) {
     (void)hipFree(a.first);
     --live_count;
     live_bytes -= a.second;
 }
-// takes `p` out of `list` and frees it
-static void counted_free_of(std::vector<std::pair<void*, size_t>>& list, void* p) {
+void DevSet::release(void* p) {
     if (!p) return;
-    for (auto& a : list)
+    for (auto& a : mem)
         if (a.first == p) {
             counted_free(a);
-            a = list.back();
-            list.pop_back();
+            a = mem.back();
+            mem.pop_back();
             return;
         }
 }
-
-int dev_alloc(zkt_ctx* c, void** p, size_t bytes) {
-    ZKT_HIP(c, counted_malloc(p, &bytes));
-    c->owned.emplace_back(*p, bytes);
+int DevSet::pinned(zkt_ctx* c, void** p, size_t bytes, unsigned flags) {
+    ZKT_HIP(c, hipHostMalloc(p, bytes, flags));
+    host.push_back(*p);
     return ZKT_OK;
 }
-void dev_free(zkt_ctx* c, void* p) { counted_free_of(c->owned, p); }
-
-int DevShared::alloc(zkt_ctx* c, void** p, size_t bytes) {
-    ZKT_HIP(c, counted_malloc(p, &bytes));
-    mem.emplace_back(*p, bytes);
+int DevSet::stream(zkt_ctx* c, hipStream_t* s) {
+    ZKT_HIP(c, hipStreamCreateWithFlags(s, hipStreamNonBlocking));
+    streams.push_back(*s);
     return ZKT_OK;
 }
-void DevShared::release(void* p) { counted_free_of(mem, p); }
-DevShared::~DevShared() {
-    if (mem.empty()) return;
+int DevSet::event(zkt_ctx* c, hipEvent_t* e) {
+    ZKT_HIP(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
+    events.push_back(*e);
+    return ZKT_OK;
+}
+void DevSet::clear() {
+    if (mem.empty() && host.empty() && streams.empty() && events.empty()) return;
     (void)hipSetDevice(device);
+    for (hipStream_t s : streams) (void)hipStreamSynchronize(s);
+    for (hipEvent_t e : events) (void)hipEventDestroy(e);
+    for (hipStream_t s : streams) (void)hipStreamDestroy(s);
+    for (void* p : host) (void)hipHostFree(p);
     for (const auto& a : mem) counted_free(a);
+    events.clear();
+    streams.clear();
+    host.clear();
+    mem.clear();
 }
 
-int ensure_buffer(zkt_ctx* c, void** p, size_t* cur, size_t bytes) {
-    if (*cur >= bytes && *p) return ZKT_OK;
-    if (*p) {
+int grow(zkt_ctx* c, DevBuf& b, size_t bytes, DevSet* in) {
+    if (b.bytes >= bytes && b.p) return ZKT_OK;
+    DevSet& set = in ? *in : c->owned;
+    if (b.p) {
         ZKT_HIP(c, hipStreamSynchronize(c->stream));
-        dev_free(c, *p);
-        *p = nullptr;
-        *cur = 0;
+        set.release(b.p);
+        b = DevBuf{};
     }
-    int rc = dev_alloc(c, p, bytes);
+    int rc = set.alloc(c, &b.p, bytes);
     if (rc) return rc;
-    *cur = bytes;
+    b.bytes = bytes;
     return ZKT_OK;
 }
 
@@ -238,12 +252,11 @@ int zkt_ctx_create(int curve_id, int device_id, zkt_ctx** out) {
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device_id < 0 || device_id >= count)
         return ZKT_ERR_NO_DEVICE;  // no CPU fallback by design
     if (hipSetDevice(device_id) != hipSuccess) return ZKT_ERR_NO_DEVICE;
-    zkt_ctx* c = new zkt_ctx();
+    zkt_ctx* c = new zkt_ctx(device_id);
     c->batch_off = exp_env("ZKT_MSM_NO_BATCH") != nullptr;
     c->aux_off = exp_env("ZKT_NO_AUX") != nullptr;
     if (const char* parts = exp_env("ZKT_FUSED_PARTS")) c->fused_parts = atoi(parts) & 63;
     c->curve = curve_id;
-    c->device = device_id;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
         delete c;
         return ZKT_ERR_HIP;
@@ -279,7 +292,8 @@ int zkt_ctx_fork(zkt_ctx* parent, zkt_ctx** out) {
     return ZKT_OK;
 }
 
-// What the context shares with others (tables, NTT plans) lives on until the last of them lets go.
+// The states go first, each with its own set, then the context's set, then its stream.  What the context shares with
+// others (tables, NTT plans) lives on until the last of them lets go.
 void zkt_ctx_destroy(zkt_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
@@ -289,11 +303,10 @@ void zkt_ctx_destroy(zkt_ctx* c) {
     prof_resolve(c);
     for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
     c->event_pool.clear();
+    c->msmb.reset();
+    c->kzg.reset();
     c->ntt_plans.clear();
-    c->msmb.reset();   // zkt_msm_g1_bases scratch: its device buffers are freed with c->owned below, its pinned rows here
-    c->kzg.reset();    // the KZG seam's copy stream and events; its device buffers go with c->owned
     if (c->comm.pinned) (void)hipHostFree(c->comm.pinned);
-    for (const auto& a : c->owned) counted_free(a);
     c->owned.clear();
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -431,12 +444,12 @@ int zkt_ntt(zkt_ctx* c, int log_n, int inverse, int coset, const uint64_t* in, s
     (void)hipSetDevice(c->device);
     const size_t n = (size_t)1 << log_n;
     if (in_len > n) return set_err(c, ZKT_ERR_INVALID_DOMAIN_SIZE, "more coefficients than the domain size");
-    int rc = ensure_buffer(c, &c->io_a, &c->io_a_bytes, n * 32);
+    int rc = grow(c, c->io_a, n * 32);
     if (rc) return rc;
-    if (in_len) ZKT_HIP(c, hipMemcpyAsync(c->io_a, in, in_len * 32, hipMemcpyHostToDevice, c->stream));
-    rc = ntt_run(c, log_n, inverse, coset ? 1 : 0, c->io_a, in_len, c->io_a);
+    if (in_len) ZKT_HIP(c, hipMemcpyAsync(c->io_a.p, in, in_len * 32, hipMemcpyHostToDevice, c->stream));
+    rc = ntt_run(c, log_n, inverse, coset ? 1 : 0, c->io_a.p, in_len, c->io_a.p);
     if (rc) return rc;
-    ZKT_HIP(c, hipMemcpyAsync(out, c->io_a, n * 32, hipMemcpyDeviceToHost, c->stream));
+    ZKT_HIP(c, hipMemcpyAsync(out, c->io_a.p, n * 32, hipMemcpyDeviceToHost, c->stream));
     ZKT_HIP(c, hipStreamSynchronize(c->stream));
     return ZKT_OK;
 }
@@ -446,12 +459,12 @@ int zkt_ntt_class(zkt_ctx* c, int log_n, int log_big, int cls, const uint64_t* i
     if (log_n < 0 || log_n > 27) return set_err(c, ZKT_ERR_INVALID_DOMAIN_SIZE, "InvalidEvalDomainSize");
     (void)hipSetDevice(c->device);
     const size_t n = (size_t)1 << log_n;
-    int rc = ensure_buffer(c, &c->io_a, &c->io_a_bytes, (in_len > n ? in_len : n) * 32);
+    int rc = grow(c, c->io_a, (in_len > n ? in_len : n) * 32);
     if (rc) return rc;
-    if ((rc = ensure_buffer(c, &c->io_b, &c->io_b_bytes, n * 32))) return rc;
-    if (in_len) ZKT_HIP(c, hipMemcpyAsync(c->io_a, in, in_len * 32, hipMemcpyHostToDevice, c->stream));
-    if ((rc = ntt_run_class(c, log_n, log_big, cls, c->io_a, in_len, c->io_a, c->io_b))) return rc;
-    ZKT_HIP(c, hipMemcpyAsync(out, c->io_a, n * 32, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = grow(c, c->io_b, n * 32))) return rc;
+    if (in_len) ZKT_HIP(c, hipMemcpyAsync(c->io_a.p, in, in_len * 32, hipMemcpyHostToDevice, c->stream));
+    if ((rc = ntt_run_class(c, log_n, log_big, cls, c->io_a.p, in_len, c->io_a.p, c->io_b.p))) return rc;
+    ZKT_HIP(c, hipMemcpyAsync(out, c->io_a.p, n * 32, hipMemcpyDeviceToHost, c->stream));
     ZKT_HIP(c, hipStreamSynchronize(c->stream));
     return ZKT_OK;
 }
@@ -588,14 +601,14 @@ static int debug_test_launch(zkt_ctx* c, void (*k)(int, const uint32_t*, size_t,
     if (n == 0) return ZKT_OK;
     if (n > FX_TEST_MAX_RECORDS) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "too many records");
     (void)hipSetDevice(c->device);
-    int rc = ensure_buffer(c, &c->io_a, &c->io_a_bytes, n * in_words * 4);
+    int rc = grow(c, c->io_a, n * in_words * 4);
     if (rc) return rc;
-    if ((rc = ensure_buffer(c, &c->io_b, &c->io_b_bytes, n * out_words * 4))) return rc;
-    ZKT_HIP(c, hipMemcpyAsync(c->io_a, in, n * in_words * 4, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, op, (const uint32_t*)c->io_a, n,
-                       (uint32_t*)c->io_b);
+    if ((rc = grow(c, c->io_b, n * out_words * 4))) return rc;
+    ZKT_HIP(c, hipMemcpyAsync(c->io_a.p, in, n * in_words * 4, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, op, (const uint32_t*)c->io_a.p, n,
+                       (uint32_t*)c->io_b.p);
     ZKT_HIP(c, hipGetLastError());
-    ZKT_HIP(c, hipMemcpyAsync(out, c->io_b, n * out_words * 4, hipMemcpyDeviceToHost, c->stream));
+    ZKT_HIP(c, hipMemcpyAsync(out, c->io_b.p, n * out_words * 4, hipMemcpyDeviceToHost, c->stream));
     ZKT_HIP(c, hipStreamSynchronize(c->stream));
     return ZKT_OK;
 }
@@ -641,21 +654,21 @@ int zkt_host_field_op(int curve_id, int which, int op, const uint32_t* a, const 
 int zkt_debug_fr_mul(zkt_ctx* c, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out) {
     if (!c || !a || !b || !out) return ZKT_ERR_INVALID_ARGUMENT;
     (void)hipSetDevice(c->device);
-    int rc = ensure_buffer(c, &c->io_a, &c->io_a_bytes, n * 32);
+    int rc = grow(c, c->io_a, n * 32);
     if (rc) return rc;
-    rc = ensure_buffer(c, &c->io_b, &c->io_b_bytes, n * 32);
+    rc = grow(c, c->io_b, n * 32);
     if (rc) return rc;
-    ZKT_HIP(c, hipMemcpyAsync(c->io_a, a, n * 32, hipMemcpyHostToDevice, c->stream));
-    ZKT_HIP(c, hipMemcpyAsync(c->io_b, b, n * 32, hipMemcpyHostToDevice, c->stream));
+    ZKT_HIP(c, hipMemcpyAsync(c->io_a.p, a, n * 32, hipMemcpyHostToDevice, c->stream));
+    ZKT_HIP(c, hipMemcpyAsync(c->io_b.p, b, n * 32, hipMemcpyHostToDevice, c->stream));
     unsigned blocks = (unsigned)((n + 255) / 256);
     if (c->curve == ZKT_CURVE_BN254)
-        hipLaunchKernelGGL(k_fr_mul<Bn254Fr>, dim3(blocks), dim3(256), 0, c->stream, (const Fe<Bn254Fr>*)c->io_a,
-                           (const Fe<Bn254Fr>*)c->io_b, (Fe<Bn254Fr>*)c->io_a, n);
+        hipLaunchKernelGGL(k_fr_mul<Bn254Fr>, dim3(blocks), dim3(256), 0, c->stream, (const Fe<Bn254Fr>*)c->io_a.p,
+                           (const Fe<Bn254Fr>*)c->io_b.p, (Fe<Bn254Fr>*)c->io_a.p, n);
     else
-        hipLaunchKernelGGL(k_fr_mul<Bls381Fr>, dim3(blocks), dim3(256), 0, c->stream, (const Fe<Bls381Fr>*)c->io_a,
-                           (const Fe<Bls381Fr>*)c->io_b, (Fe<Bls381Fr>*)c->io_a, n);
+        hipLaunchKernelGGL(k_fr_mul<Bls381Fr>, dim3(blocks), dim3(256), 0, c->stream, (const Fe<Bls381Fr>*)c->io_a.p,
+                           (const Fe<Bls381Fr>*)c->io_b.p, (Fe<Bls381Fr>*)c->io_a.p, n);
     ZKT_HIP(c, hipGetLastError());
-    ZKT_HIP(c, hipMemcpyAsync(out, c->io_a, n * 32, hipMemcpyDeviceToHost, c->stream));
+    ZKT_HIP(c, hipMemcpyAsync(out, c->io_a.p, n * 32, hipMemcpyDeviceToHost, c->stream));
     ZKT_HIP(c, hipStreamSynchronize(c->stream));
     return ZKT_OK;
 }

@@ -273,9 +273,9 @@ static int witness_check_t(zkt_ctx* c, const WitnessCheckKeys& K, const zkt_prov
         for (size_t& o : o_made) o = take(n * 32);
         o_sigma = take(sigma_scratch_bytes(log_n, rows));
     }
-    int rc = ensure_buffer(c, &c->check_scratch, &c->check_scratch_bytes, at);
+    int rc = grow(c, c->check_scratch, at);
     if (rc) return rc;
-    char* const base = (char*)c->check_scratch;
+    char* const base = (char*)c->check_scratch.p;
     unsigned long long* const d_status = (unsigned long long*)(base + o_status);
 
     unsigned long long h_status[CK_WORDS] = {};

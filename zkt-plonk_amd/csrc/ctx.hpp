@@ -21,11 +21,41 @@ struct MsmBasesState; // msm.hip (zkt_msm_g1_bases)
 struct KzgState;      // kzg.hip (zkt_kzg_commit_batch / zkt_kzg_open)
 struct CircuitState;  // prover.hip
 
+// Everything one owner takes from the runtime and gives back together: device memory, pinned memory, streams, events.
+// A state's work set, a function's temporaries and the context's own allocations are each one of these, so nothing is
+// released by hand: what the set made goes with the set.
+struct DevSet {
+    const int device;
+    std::vector<std::pair<void*, size_t>> mem;   // device allocations with their sizes (zkt_debug_live_allocations counts them)
+    std::vector<void*> host;
+    std::vector<hipStream_t> streams;
+    std::vector<hipEvent_t> events;
+    explicit DevSet(int dev) : device(dev) {}
+    DevSet(const DevSet&) = delete;
+    DevSet& operator=(const DevSet&) = delete;
+    // waits for the streams it made, then: events, streams, pinned memory, device memory.  Work on any other stream that
+    // still uses the set is the caller's to wait for.
+    ~DevSet() { clear(); }
+    void clear();
+    // each sets c's error as ZKT_HIP does
+    int alloc(zkt_ctx* c, void** p, size_t bytes);
+    void release(void* p);                           // one device allocation ahead of the rest
+    int pinned(zkt_ctx* c, void** p, size_t bytes, unsigned flags = 0);
+    int stream(zkt_ctx* c, hipStream_t* s);          // non-blocking
+    int event(zkt_ctx* c, hipEvent_t* e);            // timing disabled
+};
+// scratch that is allocated on first use and grown when a call needs more (grow), in the set of whoever uses it
+struct DevBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+};
+
 }  // namespace zkt
 
 struct zkt_ctx {
     int curve = 0;
-    int device = 0;
+    const int device;
+    explicit zkt_ctx(int dev) : device(dev), owned(dev) {}
     hipStream_t stream = nullptr;
     bool own_stream = false;
     std::string err;
@@ -38,16 +68,9 @@ struct zkt_ctx {
     int ntt_split_npass = 0;                 // zkt_debug_ntt_split: 0 = policy, else 2 or 3 passes of ntt_split_log_r
     int ntt_split_log_r[3] = {0, 0, 0};
     // scratch (grown on demand, never shrunk)
-    void* ntt_scratch = nullptr;
-    size_t ntt_scratch_bytes = 0;
-    void* io_a = nullptr;
-    size_t io_a_bytes = 0;
-    void* io_b = nullptr;
-    size_t io_b_bytes = 0;
-    void* check_scratch = nullptr;   // zkt_circuit_check_witness (check.hip): the call's own, never shared with a fork
-    size_t check_scratch_bytes = 0;
-    void* verify_scratch = nullptr;  // zkt_g1_decompress / zkt_verify_batch_dev (g1decomp.hip, verify.hip): the call's own
-    size_t verify_scratch_bytes = 0;
+    zkt::DevBuf ntt_scratch, io_a, io_b;
+    zkt::DevBuf check_scratch;    // zkt_circuit_check_witness (check.hip): the call's own, never shared with a fork
+    zkt::DevBuf verify_scratch;   // zkt_g1_decompress / zkt_verify_batch_dev (g1decomp.hip, verify.hip): the call's own
 
     // optional per-kernel HIP-event timing (bench.py's live roofline measurement)
     int prof_on = 0;   // 0 off, 1 every scope, 2 only the dominant kernel's scope ("msm_accumulate")
@@ -89,7 +112,7 @@ struct zkt_ctx {
     int fused_parts = 63;
     bool fused(int part) const { return fused_passes != 2 && (fused_parts & part); }
     std::shared_ptr<zkt::CircuitState> circuit;
-    std::vector<std::pair<void*, size_t>> owned;  // every dev_alloc made on behalf of this ctx, with its size
+    zkt::DevSet owned;   // every dev_alloc made on behalf of this ctx: scratch, caller buffers, Poseidon / Merkle handles
 };
 
 namespace zkt {
@@ -130,32 +153,20 @@ int comm_all_gather_dev(zkt_ctx* c, const void* d_send, void* d_recv, size_t byt
 bool comm_async_available(const zkt_ctx* c);
 int comm_all_gather_async(zkt_ctx* c, const void* d_send, void* d_recv, size_t bytes, hipStream_t st);
 
-// grows *p to at least `bytes`
-int ensure_buffer(zkt_ctx* c, void** p, size_t* cur, size_t bytes);
-// scratch that is allocated on first use and grown when a call needs more (the context's allocation, freed with it)
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-};
-inline int grow(zkt_ctx* c, DevBuf& b, size_t bytes) { return ensure_buffer(c, &b.p, &b.bytes, bytes); }
-int dev_alloc(zkt_ctx* c, void** p, size_t bytes);
-void dev_free(zkt_ctx* c, void* p);
+// grows `b` to at least `bytes`, in the set that owns it (the context's unless named); waits for c's stream before a
+// buffer that exists is replaced
+int grow(zkt_ctx* c, DevBuf& b, size_t bytes, DevSet* in = nullptr);
+inline int dev_alloc(zkt_ctx* c, void** p, size_t bytes) { return c->owned.alloc(c, p, bytes); }
+inline void dev_free(zkt_ctx* c, void* p) { c->owned.release(p); }
 
 // Device memory that several contexts may read (zkt_ctx_fork): tables that are complete before a second context sees
 // them.  It belongs to no context: it is held through shared_ptr and freed with the last holder, in whatever order the
 // contexts go.  A fork does not copy its source's pointer, it reads through a holder of its own that keeps the source's
 // alive (dev_shared_reader), so use_count() > 1 on a context's holder means exactly: a context forked from this one, or
 // from one forked from it, still reads these tables.
-struct DevShared {
-    const int device;
-    std::vector<std::pair<void*, size_t>> mem;
+struct DevShared : DevSet {
+    using DevSet::DevSet;
     std::shared_ptr<DevShared> from;   // a fork's holder: the tables are this one's
-    explicit DevShared(int dev) : device(dev) {}
-    DevShared(const DevShared&) = delete;
-    DevShared& operator=(const DevShared&) = delete;
-    ~DevShared();
-    int alloc(zkt_ctx* c, void** p, size_t bytes);   // as dev_alloc; the error, if any, is c's
-    void release(void* p);                           // one allocation ahead of the rest (a build that did not succeed)
 };
 inline std::shared_ptr<DevShared> dev_shared_reader(const std::shared_ptr<DevShared>& of) {
     if (!of) return nullptr;

@@ -131,11 +131,11 @@ static int g1c_enqueue_t(zkt_ctx* c, MsmBasesState* st, const void* d_pts, size_
 static int g1c_chunk(zkt_ctx* c, MsmBasesState* st, const void* pts, bool on_device, size_t m, const void** d_pts, G1cTotals* tot,
                      uint8_t* out_status) {
     const size_t pt_bytes = c->curve == ZKT_CURVE_BN254 ? 64 : 96;
-    int rc = grow(c, st->check_status, g1c_up(sizeof(G1cTotals)) + g1c_up(m));
+    int rc = grow(c, st->check_status, g1c_up(sizeof(G1cTotals)) + g1c_up(m), &st->mem);
     if (rc) return rc;
     *d_pts = pts;
     if (!on_device) {
-        if ((rc = grow(c, st->check_points, m * pt_bytes))) return rc;
+        if ((rc = grow(c, st->check_points, m * pt_bytes, &st->mem))) return rc;
         ZKT_HIP(c, hipMemcpyAsync(st->check_points.p, pts, m * pt_bytes, hipMemcpyHostToDevice, c->stream));
         *d_pts = st->check_points.p;
     }
@@ -262,7 +262,7 @@ static int srs_check_t(zkt_ctx* c, const void* pts, size_t count, bool on_device
         }
         rep->n_bad += m - tot.by_status[ZKT_G1_VALID];
         if (rep->n_bad) continue;             // the later chunks still get their statuses and counts, and no MSM
-        if ((rc = grow(c, st->scalars, m * 32))) return rc;
+        if ((rc = grow(c, st->scalars, m * 32, &st->mem))) return rc;
         // the key's two ends for the host's finish; msm_bases waits for the stream, and so does every way out before it
         hipError_t e = hipSuccess;
         if (start == 0) e = hipMemcpyAsync(ends[0], d_pts, PT, hipMemcpyDeviceToHost, c->stream);

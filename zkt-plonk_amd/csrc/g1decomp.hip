@@ -90,9 +90,9 @@ int zkt_g1_decompress(zkt_ctx* c, const uint8_t* compressed, size_t n, uint64_t*
     const size_t nb = c->curve == ZKT_CURVE_BN254 ? 32 : 48;
     auto up = [](size_t b) { return (b + 255) / 256 * 256; };
     const size_t o_out = up(n * nb), o_st = o_out + up(n * 2 * nb);
-    int rc = ensure_buffer(c, &c->verify_scratch, &c->verify_scratch_bytes, o_st + up(n));
+    int rc = grow(c, c->verify_scratch, o_st + up(n));
     if (rc) return rc;
-    char* const base = (char*)c->verify_scratch;
+    char* const base = (char*)c->verify_scratch.p;
     ZKT_HIP(c, hipMemcpyAsync(base, compressed, n * nb, hipMemcpyHostToDevice, c->stream));
     if ((rc = g1_decompress_enqueue(c, base, n, base + o_out, base + o_st))) {
         (void)hipStreamSynchronize(c->stream);   // the upload reads the caller's memory

@@ -33,24 +33,19 @@ namespace zkt {
 constexpr int KZG_OPEN_E = 4;
 
 struct KzgState {
+    DevSet mem;   // owns everything below
+    explicit KzgState(int device) : mem(device) {}
     hipStream_t copy = nullptr;
     hipEvent_t ev_up = nullptr, ev_main = nullptr;
-    // device scratch (the context's allocations, freed with it)
     DevBuf up;                         // host forms: the uploaded coefficients
     DevBuf t, tb, w, scan, pw, part, evals;   // zkt_kzg_open
-    ~KzgState() {
-        if (ev_up) (void)hipEventDestroy(ev_up);
-        if (ev_main) (void)hipEventDestroy(ev_main);
-        if (copy) (void)hipStreamDestroy(copy);
-    }
 };
 
 static int kzg_state(zkt_ctx* c, KzgState** out) {
     if (!c->kzg) {
-        auto K = std::make_shared<KzgState>();
-        ZKT_HIP(c, hipStreamCreateWithFlags(&K->copy, hipStreamNonBlocking));
-        ZKT_HIP(c, hipEventCreateWithFlags(&K->ev_up, hipEventDisableTiming));
-        ZKT_HIP(c, hipEventCreateWithFlags(&K->ev_main, hipEventDisableTiming));
+        auto K = std::make_shared<KzgState>(c->device);
+        int rc;
+        if ((rc = K->mem.stream(c, &K->copy)) || (rc = K->mem.event(c, &K->ev_up)) || (rc = K->mem.event(c, &K->ev_main))) return rc;
         c->kzg = K;
     }
     *out = c->kzg.get();
@@ -114,7 +109,7 @@ static int kzg_commit(zkt_ctx* c, const void* const* src, bool host, const size_
             for (size_t i = w0; i < std::min(live.size(), w0 + S); ++i) b += lens[live[i]] * 32;
             most = std::max(most, b);
         }
-        if ((rc = grow(c, K->up, most))) return rc;
+        if ((rc = grow(c, K->up, most, &K->mem))) return rc;
     }
     std::vector<uint64_t> res((size_t)k * W, 0);
     // the prover's rule: grouped launches where the key size gains from them (and not in the A/B builds that turn them off)
@@ -270,11 +265,12 @@ static int kzg_open(zkt_ctx* c, const void* const* src, bool host, const size_t*
     KzgState* K = nullptr;
     if ((rc = kzg_state(c, &K))) return rc;
     const uint32_t nblk = (uint32_t)((L + 256 * KZG_OPEN_E - 1) / (256 * KZG_OPEN_E));
-    if ((rc = grow(c, K->t, L * 32)) || (rc = grow(c, K->tb, L * 32)) || (rc = grow(c, K->w, L * 32)) ||
-        (rc = grow(c, K->scan, (2 * (L / 1024 + 2048)) * 32)) || (rc = grow(c, K->pw, open_witness_powers(L) * 32)) ||
-        (rc = grow(c, K->part, (size_t)k * nblk * 32)) || (rc = grow(c, K->evals, (size_t)k * 32)))
+    auto need = [&](DevBuf& buf, size_t bytes) { return grow(c, buf, bytes, &K->mem); };
+    if ((rc = need(K->t, L * 32)) || (rc = need(K->tb, L * 32)) || (rc = need(K->w, L * 32)) ||
+        (rc = need(K->scan, (2 * (L / 1024 + 2048)) * 32)) || (rc = need(K->pw, open_witness_powers(L) * 32)) ||
+        (rc = need(K->part, (size_t)k * nblk * 32)) || (rc = need(K->evals, (size_t)k * 32)))
         return rc;
-    if (host && (rc = grow(c, K->up, total * 32))) return rc;
+    if (host && (rc = grow(c, K->up, total * 32, &K->mem))) return rc;
     KzgOpenArgs a{};
     a.nterms = k;
     size_t off = 0;

@@ -177,28 +177,23 @@ static int lagrange_build_t(zkt_ctx* c, int log_n) {
     void *A = nullptr, *tw = nullptr, *seg = nullptr, *table2 = nullptr;
     auto mem = std::make_shared<DevShared>(c->device);   // the table goes with it unless the build succeeds
     if ((rc = mem->alloc(c, &table2, (size_t)st.plan.W * count2 * sizeof(Affine<Q>)))) return rc;
-    auto release = [&](int code) {
-        dev_free(c, A);
-        dev_free(c, tw);
-        dev_free(c, seg);
-        return code;
-    };
-    if ((rc = dev_alloc(c, &A, n * sizeof(Xyzz<Q>)))) return release(rc);
+    DevSet tmp(c->device);
+    if ((rc = tmp.alloc(c, &A, n * sizeof(Xyzz<Q>)))) return rc;
     hipLaunchKernelGGL(k_lag_init<C>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
                        (const Affine<Q>*)st.table, (Xyzz<Q>*)A, n);
     if (log_n >= 1) {
         const size_t half = n / 2;
-        if ((rc = dev_alloc(c, &tw, half * sizeof(Fe<R>)))) return release(rc);
+        if ((rc = tmp.alloc(c, &tw, half * sizeof(Fe<R>)))) return rc;
         const Fe<R> winv = fe_inv_host<R>(root_of_unity<R>(log_n));
         hipLaunchKernelGGL(k_lag_twiddles<R>, dim3((unsigned)((half + 255) / 256)), dim3(256), 0, c->stream, (Fe<R>*)tw, half, winv);
         for (size_t h = half; h >= 1; h >>= 1)
             hipLaunchKernelGGL(k_lag_level<C>, dim3((unsigned)((half + 127) / 128)), dim3(128), 0, c->stream, (Xyzz<Q>*)A, n, h,
                                (const Fe<R>*)tw, half / h);
     }
-    if (hipGetLastError() != hipSuccess) return release(set_err(c, ZKT_ERR_HIP, "Lagrange key: launch failed"));
+    if (hipGetLastError() != hipSuccess) return set_err(c, ZKT_ERR_HIP, "Lagrange key: launch failed");
     // prefix sums: segment totals on the device, their scan on the host (a few thousand additions), the rest on the device
     const size_t nseg = std::min(n, LAG_MAX_SEGMENTS), len = n / nseg;
-    if ((rc = dev_alloc(c, &seg, 2 * nseg * sizeof(Xyzz<Q>)))) return release(rc);
+    if ((rc = tmp.alloc(c, &seg, 2 * nseg * sizeof(Xyzz<Q>)))) return rc;
     Xyzz<Q>* d_tot = (Xyzz<Q>*)seg;
     Xyzz<Q>* d_pre = d_tot + nseg;
     hipLaunchKernelGGL(k_lag_seg_sum<C>, dim3((unsigned)((nseg + 63) / 64)), dim3(64), 0, c->stream, (const Xyzz<Q>*)A, log_n, len,
@@ -206,27 +201,27 @@ static int lagrange_build_t(zkt_ctx* c, int log_n) {
     std::vector<Xyzz<Q>> tot(nseg), pre(nseg);
     if (hipMemcpyAsync(tot.data(), d_tot, nseg * sizeof(Xyzz<Q>), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
         hipStreamSynchronize(c->stream) != hipSuccess)
-        return release(set_err(c, ZKT_ERR_HIP, "Lagrange key: the transform failed"));
+        return set_err(c, ZKT_ERR_HIP, "Lagrange key: the transform failed");
     Xyzz<Q> run = xyzz_identity<Q>();
     for (size_t s = 0; s < nseg; ++s) {
         pre[s] = run;
         run = xyzz_add<Q>(run, tot[s]);
     }
     if (hipMemcpyAsync(d_pre, pre.data(), nseg * sizeof(Xyzz<Q>), hipMemcpyHostToDevice, c->stream) != hipSuccess)
-        return release(set_err(c, ZKT_ERR_HIP, "Lagrange key: upload failed"));
+        return set_err(c, ZKT_ERR_HIP, "Lagrange key: upload failed");
     hipLaunchKernelGGL(k_lag_prefix<C>, dim3((unsigned)((nseg + 63) / 64)), dim3(64), 0, c->stream, (const Xyzz<Q>*)A, log_n, len,
                        nseg, (const Xyzz<Q>*)d_pre, (Affine<Q>*)table2);
     if (extra)
         hipLaunchKernelGGL(k_lag_blinder_points<C>, dim3(1), dim3(64), 0, c->stream, (const Affine<Q>*)st.table, n, extra,
                            (Affine<Q>*)table2);
-    if (hipGetLastError() != hipSuccess) return release(set_err(c, ZKT_ERR_HIP, "Lagrange key: launch failed"));
-    if ((rc = msm_table_finish(c, table2, count2))) return release(rc);   // synchronises: `pre` may go
+    if (hipGetLastError() != hipSuccess) return set_err(c, ZKT_ERR_HIP, "Lagrange key: launch failed");
+    if ((rc = msm_table_finish(c, table2, count2))) return rc;   // synchronises: `pre` may go
     wire_bases_drop(c);   // sums of the table being replaced
     st.lag_mem = mem;
     st.table2 = table2;
     st.count2 = count2;
     st.lag_log_n = log_n;
-    return release(ZKT_OK);
+    return ZKT_OK;
 }
 
 // Makes the table for the domain of size 2^log_n available if the key allows it (not sharded, at least n + 1 powers).
@@ -391,8 +386,9 @@ void wire_bases_drop(zkt_ctx* c) {
 static int wire_digest_enqueue(zkt_ctx* c, const uint32_t* const* d_idx, size_t n_rows) {
     MsmState& st = *c->msm;
     if (!st.wb_dig)
-        if (int rc = dev_alloc(c, (void**)&st.wb_dig, 16)) return rc;
-    if (!st.wb_pin) ZKT_HIP(c, hipHostMalloc((void**)&st.wb_pin, 64));
+        if (int rc = st.work.alloc(c, (void**)&st.wb_dig, 16)) return rc;
+    if (!st.wb_pin)
+        if (int rc = st.work.pinned(c, (void**)&st.wb_pin, 64)) return rc;
     ZKT_HIP(c, hipMemsetAsync(st.wb_dig, 0, 16, c->stream));
     if (n_rows) {
         const size_t blocks = std::min<size_t>((3 * n_rows + 2047) / 2048, 4096);
@@ -406,19 +402,17 @@ static int wire_digest_enqueue(zkt_ctx* c, const uint32_t* const* d_idx, size_t 
 
 // a wire's rows grouped by variable: the counts come from the device, their scan is the host's
 struct WireGroups {
+    DevSet mem;   // owns the d_* arrays
+    explicit WireGroups(int device) : mem(device) {}
     void *d_cnt = nullptr, *d_start = nullptr, *d_grouped = nullptr, *d_ofs = nullptr, *d_bad = nullptr;
     std::vector<uint32_t> start;   // per variable: the first slot of its rows
     std::vector<uint32_t> u, ofs;  // the distinct variables, ascending, and the first slot of each (d + 1 entries)
     size_t d = 0;
     uint32_t at = 0;               // rows that carry a variable
 };
-static void wire_groups_free(zkt_ctx* c, WireGroups& g) {
-    dev_free(c, g.d_cnt); dev_free(c, g.d_start); dev_free(c, g.d_grouped); dev_free(c, g.d_ofs); dev_free(c, g.d_bad);
-    g = WireGroups{};
-}
 // false: an allocation or a copy failed.  Synchronises the stream.
 static bool wire_groups_count(zkt_ctx* c, const uint32_t* d_idx, size_t n_rows, size_t n_vars, WireGroups& g) {
-    if (dev_alloc(c, &g.d_cnt, (n_vars + 1) * 4)) return false;
+    if (g.mem.alloc(c, &g.d_cnt, (n_vars + 1) * 4)) return false;
     if (hipMemsetAsync(g.d_cnt, 0, (n_vars + 1) * 4, c->stream) != hipSuccess) return false;
     const unsigned rb = (unsigned)((n_rows + 255) / 256);
     if (n_rows) hipLaunchKernelGGL(k_wire_count, dim3(rb), dim3(256), 0, c->stream, d_idx, n_rows, (uint32_t)n_vars, (uint32_t*)g.d_cnt);
@@ -448,8 +442,8 @@ static bool wire_points(zkt_ctx* c, const uint32_t* d_idx, size_t n_rows, size_t
     using Q = typename C::Fq;
     MsmState& st = *c->msm;
     const size_t d = g.d;
-    if (dev_alloc(c, &g.d_start, (n_vars + 1) * 4) || dev_alloc(c, &g.d_grouped, ((size_t)g.at + 1) * 4) ||
-        dev_alloc(c, &g.d_ofs, (d + 1) * 4) || dev_alloc(c, &g.d_bad, 4))
+    if (g.mem.alloc(c, &g.d_start, (n_vars + 1) * 4) || g.mem.alloc(c, &g.d_grouped, ((size_t)g.at + 1) * 4) ||
+        g.mem.alloc(c, &g.d_ofs, (d + 1) * 4) || g.mem.alloc(c, &g.d_bad, 4))
         return false;
     if (hipMemcpyAsync(g.d_start, g.start.data(), n_vars * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
         hipMemcpyAsync(g.d_ofs, g.ofs.data(), (d + 1) * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
@@ -475,10 +469,9 @@ static int wire_bases_build_wire(zkt_ctx* c, int log_n, int k, const uint32_t* d
     MsmState& st = *c->msm;
     WireBases& wb = st.wb;
     const size_t n = (size_t)1 << log_n;
-    WireGroups g;
+    WireGroups g(c->device);
     void *table = nullptr, *d_u = nullptr;
     auto done = [&](bool keep) {   // a wire that cannot have its table is committed through its coefficients: never an error
-        wire_groups_free(c, g);
         if (!keep) { wb.mem->release(table); wb.mem->release(d_u); }
         (void)hipGetLastError();
         return ZKT_OK;
@@ -571,12 +564,10 @@ __global__ __launch_bounds__(64) void k_wire_fold_sum(const Xyzz<typename C::Fq>
 struct WireElimShared {
     std::vector<uint32_t> free_vars, ofs, ent_v;
     size_t n_defined = 0, n_const = 0;
+    DevSet mem;   // owns the two arrays below
     void *d_ent_v = nullptr, *d_ent_c = nullptr;
+    explicit WireElimShared(int device) : mem(device) {}
 };
-static void wire_elim_shared_free(zkt_ctx* c, WireElimShared& D) {
-    dev_free(c, D.d_ent_v); dev_free(c, D.d_ent_c);
-    D = WireElimShared{};
-}
 
 // The host pass: selector evaluations and index vectors to the host, the elimination, the transposed forms to the device.
 // false: it could not be done (memory); the wires then keep their present routes.
@@ -586,11 +577,12 @@ static bool wire_elim_host(zkt_ctx* c, int log_n, const uint32_t* const* d_idx, 
     using R = typename C::Fr;
     using F = Fe<R>;
     const size_t n = (size_t)1 << log_n;
+    DevSet tmp(c->device);
     void* d_sel[5] = {};
     std::vector<F> sel_h[5];
     std::vector<uint32_t> w_h[3];
     bool ok = true;
-    for (int k = 0; k < 5 && ok; ++k) ok = dev_alloc(c, &d_sel[k], n * sizeof(F)) == ZKT_OK;
+    for (int k = 0; k < 5 && ok; ++k) ok = tmp.alloc(c, &d_sel[k], n * sizeof(F)) == ZKT_OK;
     if (ok) ok = selector_evals_enqueue(c, log_n, ew.pk, d_sel) == ZKT_OK;
     for (int k = 0; k < 5 && ok; ++k) {
         sel_h[k].resize(n_rows);
@@ -601,7 +593,7 @@ static bool wire_elim_host(zkt_ctx* c, int log_n, const uint32_t* const* d_idx, 
         ok = hipMemcpyAsync(w_h[k].data(), d_idx[k], n_rows * 4, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
     }
     if (hipStreamSynchronize(c->stream) != hipSuccess) ok = false;
-    for (void* p : d_sel) dev_free(c, p);
+    tmp.clear();   // the selectors are on the host: the elimination below needs the memory more
     if (!ok) {
         (void)hipGetLastError();
         return false;
@@ -648,14 +640,11 @@ static bool wire_elim_host(zkt_ctx* c, int log_n, const uint32_t* const* d_idx, 
     D.free_vars.swap(E.free_vars);
     D.n_defined = nd;
     D.n_const = nk;
-    ok = !dev_alloc(c, &D.d_ent_v, total * 4) && !dev_alloc(c, &D.d_ent_c, total * sizeof(F));
+    ok = !D.mem.alloc(c, &D.d_ent_v, total * 4) && !D.mem.alloc(c, &D.d_ent_c, total * sizeof(F));
     ok = ok && hipMemcpyAsync(D.d_ent_v, D.ent_v.data(), total * 4, hipMemcpyHostToDevice, c->stream) == hipSuccess &&
          hipMemcpyAsync(D.d_ent_c, ent_c.data(), total * sizeof(F), hipMemcpyHostToDevice, c->stream) == hipSuccess;
     if (hipStreamSynchronize(c->stream) != hipSuccess) ok = false;   // the staging vectors go with this frame
-    if (!ok) {
-        (void)hipGetLastError();
-        wire_elim_shared_free(c, D);
-    }
+    if (!ok) (void)hipGetLastError();
     return ok;
 }
 
@@ -668,12 +657,11 @@ static bool wire_elim_build_wire(zkt_ctx* c, int log_n, int k, const uint32_t* d
     MsmState& st = *c->msm;
     WireBases& wb = st.wb;
     const size_t n = (size_t)1 << log_n;
-    WireGroups g;
+    WireGroups g(c->device);
+    DevSet tmp(c->device);
     void *d_T = nullptr, *d_pos = nullptr, *d_piece = nullptr, *d_pstart = nullptr, *d_part = nullptr, *d_flag = nullptr, *table = nullptr,
          *d_u = nullptr;
     auto done = [&](bool keep) {
-        wire_groups_free(c, g);
-        dev_free(c, d_T); dev_free(c, d_pos); dev_free(c, d_piece); dev_free(c, d_pstart); dev_free(c, d_part); dev_free(c, d_flag);
         if (!keep) { wb.mem->release(table); wb.mem->release(d_u); }
         (void)hipGetLastError();
         return keep;
@@ -706,9 +694,9 @@ static bool wire_elim_build_wire(zkt_ctx* c, int log_n, int k, const uint32_t* d
     if (!cnt || (double)(cnt + 1) >= frac * (double)present || (uint64_t)st.plan.W * (cnt + 3) >= ((uint64_t)1 << 31)) return done(false);
     if (D.n_const) cut(nf);
     const size_t groups = pstart.size() - 1, np = piece.size();
-    if (dev_alloc(c, &d_T, d * sizeof(Affine<Q>)) || dev_alloc(c, &d_pos, n_vars * 4) || dev_alloc(c, &d_piece, np * sizeof(uint2)) ||
-        dev_alloc(c, &d_pstart, (groups + 1) * 4) || wb.mem->alloc(c, &d_u, (cnt + 1) * 4) || dev_alloc(c, &d_part, np * sizeof(Xyzz<Q>)) ||
-        dev_alloc(c, &d_flag, 8) || wb.mem->alloc(c, &table, (size_t)st.plan.W * (cnt + 3) * sizeof(Affine<Q>)))
+    if (tmp.alloc(c, &d_T, d * sizeof(Affine<Q>)) || tmp.alloc(c, &d_pos, n_vars * 4) || tmp.alloc(c, &d_piece, np * sizeof(uint2)) ||
+        tmp.alloc(c, &d_pstart, (groups + 1) * 4) || wb.mem->alloc(c, &d_u, (cnt + 1) * 4) || tmp.alloc(c, &d_part, np * sizeof(Xyzz<Q>)) ||
+        tmp.alloc(c, &d_flag, 8) || wb.mem->alloc(c, &table, (size_t)st.plan.W * (cnt + 3) * sizeof(Affine<Q>)))
         return done(false);
     if (hipMemcpyAsync(d_pos, pos.data(), n_vars * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
         hipMemcpyAsync(d_piece, piece.data(), np * sizeof(uint2), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
@@ -745,7 +733,7 @@ static int wire_bases_build_all(zkt_ctx* c, int log_n, const uint32_t* const* d_
                                 const WireElimKeys* ew, bool trace) {
     using clk = std::chrono::steady_clock;
     auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    WireElimShared D;
+    WireElimShared D(c->device);
     bool elim = false;
     const auto t0 = clk::now();
     if (ew) elim = wire_elim_host<C>(c, log_n, d_idx, n_rows, n_vars, *ew, D);
@@ -762,7 +750,6 @@ static int wire_bases_build_all(zkt_ctx* c, int log_n, const uint32_t* const* d_
                 D.free_vars.size(), D.n_defined, D.n_const, nz[0], nz[1], nz[2], wb.use[0] + wb.elim[0], wb.use[1] + wb.elim[1],
                 wb.use[2] + wb.elim[2], ms(t0, t1), ms(t1, clk::now()));
     }
-    wire_elim_shared_free(c, D);
     return rc;
 }
 
@@ -838,7 +825,7 @@ static int wire_scalars_t(zkt_ctx* c, int k, const void* d_vars, const void* d_b
     using R = typename C::Fr;
     MsmState& st = *c->msm;
     const size_t cnt = st.wb.cnt[k], extra = st.wb.has_c[k] ? 1 : 0;
-    if (int rc = grow(c, st.wb_scalars[k], (cnt + extra + 2) * sizeof(Fe<R>))) return rc;
+    if (int rc = grow(c, st.wb_scalars[k], (cnt + extra + 2) * sizeof(Fe<R>), &st.work)) return rc;
     Fe<R> nn = fe_zero<R>();
     nn.v[0] = (uint32_t)(n & 0xffffffffu);
     nn.v[1] = (uint32_t)((uint64_t)n >> 32);

@@ -1095,7 +1095,12 @@ template <class C>
 static int msm_setup(zkt_ctx* c, size_t count, const MsmState* share = nullptr) {
     using Q = typename C::Fq;
     using R = typename C::Fr;
-    auto st = std::make_shared<MsmState>();
+    auto st = std::make_shared<MsmState>(c->device);
+    // an early return lets `st` go: what was enqueued on the stream for it drains first
+    struct Drain {
+        zkt_ctx* c;
+        ~Drain() { if (!c->msm) (void)hipStreamSynchronize(c->stream); }
+    } drain{c};
     st->count = count;
     // Digit width.  W n additions against 2^(c-1) buckets to reduce and a sort whose pairs stop fitting 32 bits beyond
     // 2^17 buckets: measured on MI355X (profiles/ab_digit_width_r04.txt), BN254 n = 2^20 is best at c = 17 (wider digits
@@ -1147,47 +1152,47 @@ static int msm_setup(zkt_ctx* c, size_t count, const MsmState* share = nullptr) 
     auto up = [](size_t x) { return (x + 63) & ~(size_t)63; };   // keep every copy 256-byte aligned
     st->strides.s_vals = up(m);
     st->strides.s_pairs_bytes = up(m) * 8;
-    if ((rc = dev_alloc(c, (void**)&st->vals2, NB * st->strides.s_vals * 4))) return rc;
-    if ((rc = dev_alloc(c, &st->pairs, NB * st->strides.s_pairs_bytes))) return rc;
+    if ((rc = st->work.alloc(c, (void**)&st->vals2, NB * st->strides.s_vals * 4))) return rc;
+    if ((rc = st->work.alloc(c, &st->pairs, NB * st->strides.s_pairs_bytes))) return rc;
     const size_t max_blk = (count + P.l1_scalars - 1) / P.l1_scalars;
     st->strides.s_bin_offs = up((size_t)P.nb1 * max_blk + 1);
     st->strides.s_bin_aux = up((size_t)P.nb1 * max_blk / MSM_SCAN_TILE + 4);
     st->strides.s_bin = up((size_t)P.nb1 + 1);
     st->strides.s_tile_desc = up(P.l2_items);
     st->strides.s_cnt = up((size_t)P.l2_items << P.lcols);
-    if ((rc = dev_alloc(c, (void**)&st->bin_offs, NB * st->strides.s_bin_offs * 4))) return rc;
-    if ((rc = dev_alloc(c, (void**)&st->bin_aux, NB * st->strides.s_bin_aux * 4))) return rc;
-    if ((rc = dev_alloc(c, (void**)&st->bin_start, NB * st->strides.s_bin * 4))) return rc;
-    if ((rc = dev_alloc(c, (void**)&st->tile_start, NB * st->strides.s_bin * 4))) return rc;
-    if ((rc = dev_alloc(c, &st->tile_desc, NB * st->strides.s_tile_desc * 8))) return rc;
-    if ((rc = dev_alloc(c, (void**)&st->cnt2, NB * st->strides.s_cnt * 4))) return rc;
-    if ((rc = dev_alloc(c, (void**)&st->pos2, NB * st->strides.s_cnt * 4))) return rc;
+    if ((rc = st->work.alloc(c, (void**)&st->bin_offs, NB * st->strides.s_bin_offs * 4))) return rc;
+    if ((rc = st->work.alloc(c, (void**)&st->bin_aux, NB * st->strides.s_bin_aux * 4))) return rc;
+    if ((rc = st->work.alloc(c, (void**)&st->bin_start, NB * st->strides.s_bin * 4))) return rc;
+    if ((rc = st->work.alloc(c, (void**)&st->tile_start, NB * st->strides.s_bin * 4))) return rc;
+    if ((rc = st->work.alloc(c, &st->tile_desc, NB * st->strides.s_tile_desc * 8))) return rc;
+    if ((rc = st->work.alloc(c, (void**)&st->cnt2, NB * st->strides.s_cnt * 4))) return rc;
+    if ((rc = st->work.alloc(c, (void**)&st->pos2, NB * st->strides.s_cnt * 4))) return rc;
     if ((rc = msm_scatter_lds_cap<C, false>(c, P.packed, P.dig))) return rc;
     static_assert(MsmState::SLOTS == 11, "per-slot arrays are sized for 11 slots");
     for (int i = 0; i < MsmState::SLOTS; ++i) {
-        if ((rc = dev_alloc(c, (void**)&st->offsets[i], (((size_t)P.nb1 << P.lb) + 2) * 4))) return rc;
-        if ((rc = dev_alloc(c, (void**)&st->heavy[i], ((size_t)P.keys + 2) * 4))) return rc;
-        if ((rc = dev_alloc(c, (void**)&st->params[i], 16))) return rc;
+        if ((rc = st->work.alloc(c, (void**)&st->offsets[i], (((size_t)P.nb1 << P.lb) + 2) * 4))) return rc;
+        if ((rc = st->work.alloc(c, (void**)&st->heavy[i], ((size_t)P.keys + 2) * 4))) return rc;
+        if ((rc = st->work.alloc(c, (void**)&st->params[i], 16))) return rc;
     }
     if ((rc = msm_acc_setup<C>(c, &st->acc_threads, &st->acc_lds))) return rc;
     // chunk >= ceil(pairs / acc_threads) pairs per thread (k_msm_scan_aux), so an MSM never cuts its pairs into more than
     // acc_threads chunks (nor more than it has pairs): that bounds the piece array of every slot
     size_t max_chunks = std::min(m, st->acc_threads) + 1;
     for (int i = 0; i < MsmState::SLOTS; ++i)
-        if ((rc = dev_alloc(c, &st->pieces[i], (max_chunks + P.keys + 2) * sizeof(XyzzRaw<Q>)))) return rc;
+        if ((rc = st->work.alloc(c, &st->pieces[i], (max_chunks + P.keys + 2) * sizeof(XyzzRaw<Q>)))) return rc;
     st->strides.s_chunk = up(max_chunks + 2);
-    if ((rc = dev_alloc(c, (void**)&st->chunk_bucket, NB * st->strides.s_chunk * 4))) return rc;
-    ZKT_HIP(c, hipStreamCreateWithFlags(&st->side, hipStreamNonBlocking));
+    if ((rc = st->work.alloc(c, (void**)&st->chunk_bucket, NB * st->strides.s_chunk * 4))) return rc;
+    if ((rc = st->work.stream(c, &st->side))) return rc;
     for (int i = 0; i < MsmState::SLOTS; ++i) {
-        if ((rc = dev_alloc(c, &st->buckets[i], ((size_t)P.keys + 1) * sizeof(Xyzz<Q>)))) return rc;
+        if ((rc = st->work.alloc(c, &st->buckets[i], ((size_t)P.keys + 1) * sizeof(Xyzz<Q>)))) return rc;
         {   // 2^q1 row sums + 2^q2 column sums of the bucket matrix (q1 + q2 = c - 1)
             const int q = P.c - 1, q2 = q / 2, q1 = q - q2;
-            if ((rc = dev_alloc(c, &st->rowcol[i], (((size_t)1 << q1) + ((size_t)1 << q2)) * sizeof(Xyzz<Q>)))) return rc;
+            if ((rc = st->work.alloc(c, &st->rowcol[i], (((size_t)1 << q1) + ((size_t)1 << q2)) * sizeof(Xyzz<Q>)))) return rc;
         }
-        ZKT_HIP(c, hipHostMalloc(&st->host_result[i], (size_t)(MSM_MAX_Y + 1) * MSM_R2_BLOCKS * sizeof(Xyzz<Q>), hipHostMallocMapped));
+        if ((rc = st->work.pinned(c, &st->host_result[i], (size_t)(MSM_MAX_Y + 1) * MSM_R2_BLOCKS * sizeof(Xyzz<Q>), hipHostMallocMapped))) return rc;
         ZKT_HIP(c, hipHostGetDevicePointer(&st->host_result_dev[i], st->host_result[i], 0));
-        ZKT_HIP(c, hipEventCreateWithFlags(&st->ev_main[i], hipEventDisableTiming));
-        ZKT_HIP(c, hipEventCreateWithFlags(&st->ev_done[i], hipEventDisableTiming));
+        if ((rc = st->work.event(c, &st->ev_main[i]))) return rc;
+        if ((rc = st->work.event(c, &st->ev_done[i]))) return rc;
     }
     st->defer_tails = count <= MSM_DEFER_MAX;
     if (const char* e = exp_env("ZKT_MSM_DEFER")) st->defer_tails = atoi(e) != 0;
@@ -1229,22 +1234,13 @@ int msm_table_finish(zkt_ctx* c, void* table, size_t count) {
     return table_finish<Bls381Curve>(c, table, count);
 }
 
+// the work set goes here, the base tables too unless a fork still reads them
 void msm_release(zkt_ctx* c) {
     if (!c->msm) return;
-    MsmState& st = *c->msm;
     (void)hipStreamSynchronize(c->stream);
-    if (st.side) (void)hipStreamSynchronize(st.side);
+    (void)hipStreamSynchronize(c->msm->side);
     wire_bases_drop(c);
-    for (DevBuf& b : st.wb_scalars) dev_free(c, b.p);
-    dev_free(c, st.wb_dig);
-    void* ptrs[] = {st.vals2, st.pairs, st.bin_offs, st.bin_aux, st.bin_start, st.tile_start, st.cnt2, st.pos2, st.chunk_bucket,
-                    st.tile_desc};
-    for (void* p : ptrs) dev_free(c, p);
-    for (int i = 0; i < MsmState::SLOTS; ++i) {
-        dev_free(c, st.heavy[i]); dev_free(c, st.offsets[i]); dev_free(c, st.pieces[i]); dev_free(c, st.params[i]);
-        dev_free(c, st.buckets[i]); dev_free(c, st.rowcol[i]);
-    }
-    c->msm.reset();   // lets go of the base tables: they are freed here unless a fork still reads them
+    c->msm.reset();
 }
 bool msm_tables_have_readers(const zkt_ctx* c) {
     return c->msm && (dev_shared_has_readers(c->msm->table_mem) || dev_shared_has_readers(c->msm->lag_mem) ||
@@ -1742,8 +1738,9 @@ static int srs_download_t(zkt_ctx* c, size_t offset, size_t count, uint64_t* out
     // the table holds R^-1 P_i in R' form: hand back the caller's own powers, P_i = [R] (R^-1 P_i), in arkworks' form
     // (test / bench aid; a fixed-scalar multiplication per point on the device)
     if (count == 0) return ZKT_OK;
+    DevSet set(c->device);
     void* tmp = nullptr;
-    int rc = dev_alloc(c, &tmp, count * sizeof(Affine<Q>));
+    int rc = set.alloc(c, &tmp, count * sizeof(Affine<Q>));
     if (rc) return rc;
     const Fe<R> r_canon = fe_one<R>();   // the Montgomery form of one = R mod r, read as an integer
     hipLaunchKernelGGL((k_srs_scale<C, true>), dim3((unsigned)((count + 127) / 128)), dim3(128), 0, c->stream,
@@ -1751,7 +1748,6 @@ static int srs_download_t(zkt_ctx* c, size_t offset, size_t count, uint64_t* out
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(out, tmp, count * sizeof(Affine<Q>), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    dev_free(c, tmp);
     return e == hipSuccess ? ZKT_OK : hip_fail(c, e, "srs_download");
 }
 
@@ -1803,13 +1799,13 @@ template <class C>
 static int msm_bases_state(zkt_ctx* c, MsmBasesState** out) {
     using Q = typename C::Fq;
     if (!c->msmb) {
-        auto st = std::make_shared<MsmBasesState>();
+        auto st = std::make_shared<MsmBasesState>(c->device);
         int rc;
         if ((rc = msm_scatter_lds_cap<C, true>(c, true, 0)) || (rc = msm_scatter_lds_cap<C, true>(c, false, 0)) ||
             (rc = msm_acc_setup<C>(c, &st->acc_threads, &st->acc_lds)))
             return rc;
         const size_t rows = sizeof(MsmWindows::width) * (size_t)(MSM_MAX_Y + 1);
-        ZKT_HIP(c, hipHostMalloc(&st->partials, rows * sizeof(Xyzz<Q>), hipHostMallocMapped));
+        if ((rc = st->mem.pinned(c, &st->partials, rows * sizeof(Xyzz<Q>), hipHostMallocMapped))) return rc;
         ZKT_HIP(c, hipHostGetDevicePointer(&st->partials_dev, st->partials, 0));
         c->msmb = st;
     }
@@ -1837,19 +1833,20 @@ static int msm_bases_t(zkt_ctx* c, const void* bases, bool bases_on_device, cons
         const size_t nblk = (n + P.l1_scalars - 1) / P.l1_scalars;
         const size_t total = P.nb1 * nblk, ntiles = (total + MSM_SCAN_TILE - 1) / MSM_SCAN_TILE;
         const size_t max_chunks = std::min(m, st->acc_threads) + 1, l2 = P.l2_items;
-        if ((rc = grow(c, st->bases, n * sizeof(Affine<Q>))) || (rc = grow(c, st->vals, m * 4)) ||
-            (rc = grow(c, st->pairs, m * (P.packed ? 4 : 8))) || (rc = grow(c, st->bin_offs, (total + 1) * 4)) ||
-            (rc = grow(c, st->bin_aux, (ntiles + 4) * 4)) || (rc = grow(c, st->bin_start, ((size_t)P.nb1 + 1) * 4)) ||
-            (rc = grow(c, st->tile_start, ((size_t)P.nb1 + 1) * 4)) || (rc = grow(c, st->tile_desc, l2 * 8)) ||
-            (rc = grow(c, st->cnt2, (l2 << P.lcols) * 4)) || (rc = grow(c, st->pos2, (l2 << P.lcols) * 4)) ||
-            (rc = grow(c, st->chunk_bucket, (max_chunks + 2) * 4)) || (rc = grow(c, st->offsets, (((size_t)P.nb1 << P.lb) + 2) * 4)) ||
-            (rc = grow(c, st->heavy, ((size_t)P.keys + 2) * 4)) || (rc = grow(c, st->params, 16)) ||
-            (rc = grow(c, st->pieces, (max_chunks + P.keys + 2) * sizeof(XyzzRaw<Q>))) ||
-            (rc = grow(c, st->buckets, ((size_t)P.keys + 1) * sizeof(Xyzz<Q>))) ||
-            (rc = grow(c, st->rowcol, (size_t)W * sums * sizeof(Xyzz<Q>))))
+        auto need = [&](DevBuf& buf, size_t bytes) { return grow(c, buf, bytes, &st->mem); };
+        if ((rc = need(st->bases, n * sizeof(Affine<Q>))) || (rc = need(st->vals, m * 4)) ||
+            (rc = need(st->pairs, m * (P.packed ? 4 : 8))) || (rc = need(st->bin_offs, (total + 1) * 4)) ||
+            (rc = need(st->bin_aux, (ntiles + 4) * 4)) || (rc = need(st->bin_start, ((size_t)P.nb1 + 1) * 4)) ||
+            (rc = need(st->tile_start, ((size_t)P.nb1 + 1) * 4)) || (rc = need(st->tile_desc, l2 * 8)) ||
+            (rc = need(st->cnt2, (l2 << P.lcols) * 4)) || (rc = need(st->pos2, (l2 << P.lcols) * 4)) ||
+            (rc = need(st->chunk_bucket, (max_chunks + 2) * 4)) || (rc = need(st->offsets, (((size_t)P.nb1 << P.lb) + 2) * 4)) ||
+            (rc = need(st->heavy, ((size_t)P.keys + 2) * 4)) || (rc = need(st->params, 16)) ||
+            (rc = need(st->pieces, (max_chunks + P.keys + 2) * sizeof(XyzzRaw<Q>))) ||
+            (rc = need(st->buckets, ((size_t)P.keys + 1) * sizeof(Xyzz<Q>))) ||
+            (rc = need(st->rowcol, (size_t)W * sums * sizeof(Xyzz<Q>))))
             return rc;
         if (!scalars_on_device) {
-            if ((rc = grow(c, st->scalars, n * 32))) return rc;
+            if ((rc = need(st->scalars, n * 32))) return rc;
             ZKT_HIP(c, hipMemcpyAsync(st->scalars.p, scalars, n * 32, hipMemcpyHostToDevice, c->stream));
             scalars = st->scalars.p;
         }
@@ -1996,11 +1993,11 @@ int zkt_msm_g1(zkt_ctx* c, const uint64_t* scalars, size_t len, size_t base_offs
     if (!c || (!scalars && len) || !out_xy_mont) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
     (void)hipSetDevice(c->device);
     if (len) {
-        int rc = ensure_buffer(c, &c->io_a, &c->io_a_bytes, len * 32);
+        int rc = grow(c, c->io_a, len * 32);
         if (rc) return rc;
-        ZKT_HIP(c, hipMemcpyAsync(c->io_a, scalars, len * 32, hipMemcpyHostToDevice, c->stream));
+        ZKT_HIP(c, hipMemcpyAsync(c->io_a.p, scalars, len * 32, hipMemcpyHostToDevice, c->stream));
     }
-    return msm_g1_dev(c, c->io_a, len, base_offset, scalars_montgomery, out_xy_mont, out_is_infinity);
+    return msm_g1_dev(c, c->io_a.p, len, base_offset, scalars_montgomery, out_xy_mont, out_is_infinity);
 }
 
 int zkt_msm_enqueue_dev(zkt_ctx* c, const void* d_scalars, size_t len, size_t base_offset, int scalars_montgomery) {

@@ -111,6 +111,9 @@ struct LagrangeTable {
 };
 
 struct MsmState : LagrangeTable {
+    // owns everything below that is this context's alone: work buffers, slots, pinned rows, the side stream, events
+    DevSet work;
+    explicit MsmState(int device) : work(device) {}
     size_t count = 0;      // bases loaded
     // index-range sharding: this GPU holds powers [slice_off, slice_off + count) of a key of `total`
     size_t slice_off = 0, total = 0;
@@ -162,21 +165,13 @@ struct MsmState : LagrangeTable {
     bool defer_tails = false;
     int tail_wait[SLOTS] = {};     // slots whose accumulation is enqueued and whose tail is not, in order
     int n_tail_wait = 0;
-    ~MsmState() {
-        for (int i = 0; i < SLOTS; ++i) {
-            if (host_result[i]) (void)hipHostFree(host_result[i]);
-            if (ev_main[i]) (void)hipEventDestroy(ev_main[i]);
-            if (ev_done[i]) (void)hipEventDestroy(ev_done[i]);
-        }
-        if (side) (void)hipStreamDestroy(side);
-        if (wb_pin) (void)hipHostFree(wb_pin);
-    }
 };
 
 // Scratch of zkt_msm_g1_bases (variable-base MSM over the caller's points, msm.hip): buffers of its own, allocated on the
 // first call and grown when a call needs more, so that the call never touches the prover's slots, work set or tables.
-// Device buffers are the context's (dev_alloc); only the pinned partial sums are freed here.
 struct MsmBasesState {
+    DevSet mem;   // owns every buffer below and the pinned partial sums
+    explicit MsmBasesState(int device) : mem(device) {}
     DevBuf bases;     // the call's points in the accumulation's packed R' form
     DevBuf scalars;   // zkt_msm_g1_bases: the uploaded scalars
     DevBuf vals, pairs, bin_offs, bin_aux, bin_start, tile_start, tile_desc, cnt2, pos2, chunk_bucket;   // grouping
@@ -185,9 +180,6 @@ struct MsmBasesState {
     void* partials = nullptr;      // pinned: W x (c) rows of partial sums the host combines (Horner over the windows)
     void* partials_dev = nullptr;
     size_t acc_lds = 0, acc_threads = 0;   // as MsmState's
-    ~MsmBasesState() {
-        if (partials) (void)hipHostFree(partials);
-    }
 };
 
 constexpr size_t MSM_DEFER_MAX = ((size_t)1 << 16) + 64;      // small key: latency regime (tails deferred and batched)

@@ -726,7 +726,7 @@ static int ntt_run_core_t(zkt_ctx* c, int log_n, int inverse, const int* cosets,
         ZKT_HIP(c, hipGetLastError());
         return 0;
     }
-    int rc = ensure_buffer(c, &c->ntt_scratch, &c->ntt_scratch_bytes, N * 36 * (size_t)nb * (size_t)ncls);   // raw limbs between passes
+    int rc = grow(c, c->ntt_scratch, N * 36 * (size_t)nb * (size_t)ncls);   // raw limbs between passes
     if (rc) return rc;
     const int p = pl.npass;
     const unsigned blocks = (unsigned)(N >> TILE_LOG);
@@ -736,8 +736,8 @@ static int ntt_run_core_t(zkt_ctx* c, int log_n, int inverse, const int* cosets,
         const bool last = (i == p - 1);
         for (int y = 0; y < NTT_MAX_BATCH; ++y) {
             const int yy = y < nb ? y : 0;
-            a.in[y] = (i == 0) ? d_in[yy] : c->ntt_scratch;
-            a.out[y] = last ? d_out[yy] : c->ntt_scratch;
+            a.in[y] = (i == 0) ? d_in[yy] : c->ntt_scratch.p;
+            a.out[y] = last ? d_out[yy] : c->ntt_scratch.p;
             a.in_len[y] = (i == 0) ? (uint64_t)in_len[yy] : N;
         }
         a.w_inner = pl.w_inner[i];

@@ -1355,7 +1355,7 @@ int zkt_poseidon_gadget_check(zkt_ctx* c, const zkt_poseidon* h) {
     return ZKT_OK;
 }
 
-// host-pointer convenience form: load, stage, run, download, release (every exit path frees what it took)
+// host-pointer convenience form: load, stage, run, download; the staging goes with `tmp`
 int zkt_poseidon_hash_batch(zkt_ctx* c, const zkt_poseidon_params* p, const uint64_t* inputs, size_t batch, int arity,
                             uint64_t* out_hashes, uint64_t* out_states) {
     if (!c || !out_hashes || (!inputs && batch && arity)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
@@ -1367,13 +1367,14 @@ int zkt_poseidon_hash_batch(zkt_ctx* c, const zkt_poseidon_params* p, const uint
     const int W = p->width, rounds = 2 * p->half_full_rounds + p->partial_rounds;
     const size_t n_in = batch * (size_t)arity, n_st = out_states ? batch * (size_t)(rounds + 1) * W : 0;
     zkt_poseidon* h = nullptr;
+    DevSet tmp(c->device);
     void *d_in = nullptr, *d_out = nullptr, *d_st = nullptr;
     auto run = [&]() -> int {
         int rc;
         if ((rc = zkt_poseidon_load(c, p, &h))) return rc;
-        if ((rc = dev_alloc(c, &d_in, (n_in ? n_in : 1) * 32))) return rc;
-        if ((rc = dev_alloc(c, &d_out, batch * 32))) return rc;
-        if (n_st && (rc = dev_alloc(c, &d_st, n_st * 32))) return rc;
+        if ((rc = tmp.alloc(c, &d_in, (n_in ? n_in : 1) * 32))) return rc;
+        if ((rc = tmp.alloc(c, &d_out, batch * 32))) return rc;
+        if (n_st && (rc = tmp.alloc(c, &d_st, n_st * 32))) return rc;
         if (n_in) ZKT_HIP(c, hipMemcpyAsync(d_in, inputs, n_in * 32, hipMemcpyHostToDevice, c->stream));
         if ((rc = zkt_poseidon_hash_batch_dev(c, h, d_in, batch, arity, d_out, d_st))) return rc;
         ZKT_HIP(c, hipMemcpyAsync(out_hashes, d_out, batch * 32, hipMemcpyDeviceToHost, c->stream));
@@ -1383,9 +1384,6 @@ int zkt_poseidon_hash_batch(zkt_ctx* c, const zkt_poseidon_params* p, const uint
     };
     const int rc = run();
     if (rc) (void)hipStreamSynchronize(c->stream);
-    dev_free(c, d_in);
-    dev_free(c, d_out);
-    dev_free(c, d_st);
     zkt_poseidon_free(c, h);
     return rc;
 }
@@ -1513,10 +1511,11 @@ int zkt_merkle_tree_paths(zkt_ctx* c, zkt_merkle_tree* t, const uint64_t* indice
     if (!out_siblings) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
     (void)hipSetDevice(c->device);
     const size_t bytes = k * (size_t)t->height * 32;
+    DevSet tmp(c->device);
     void* d_out = nullptr;
     auto run = [&]() -> int {
         int rc;
-        if ((rc = dev_alloc(c, &d_out, bytes))) return rc;
+        if ((rc = tmp.alloc(c, &d_out, bytes))) return rc;
         {
             ProfScope ps(c, "merkle_paths");
             if ((rc = merkle_table_upload(c, t, indices, k, nullptr, nullptr))) return rc;
@@ -1530,7 +1529,6 @@ int zkt_merkle_tree_paths(zkt_ctx* c, zkt_merkle_tree* t, const uint64_t* indice
     };
     const int rc = run();
     if (rc) (void)hipStreamSynchronize(c->stream);
-    dev_free(c, d_out);
     return rc;
 }
 

@@ -53,6 +53,9 @@ struct ClassTables {
 };
 
 struct CircuitState : CircuitKeys, ClassTables {
+    // owns everything circuit_alloc_work makes: the per-proof buffers, pinned staging, streams and events below
+    DevSet work;
+    explicit CircuitState(int device) : work(device) {}
     int log_n = 0;
     size_t n = 0;
     // A proof sharded over G GPUs (zkt_ctx_set_comm): this GPU owns the 4n-coset points of global index cls modulo G,
@@ -1401,48 +1404,12 @@ static int run_prover(zkt_ctx* c, const zkt_prove_inputs& in, HostTranscript& tr
 }
 
 // ---- circuit (ProverKey + ExtendedProverKey) ------------------------------------------------------
+// the work set, the keys and the class tables go together (the tables unless a fork still reads them)
 void circuit_release(zkt_ctx* c) {
     if (!c->circuit) return;
     (void)hipStreamSynchronize(c->stream);
-    CircuitState& S = *c->circuit;
-    if (S.copy_stream) (void)hipStreamSynchronize(S.copy_stream);
-    auto fr = [&](void* p) { dev_free(c, p); };
-    for (void* p : S.ev) fr(p);
-    for (void* p : S.sc) fr(p);
-    fr(S.scan_tmp);
-    for (void* p : S.poly) fr(p);
-    for (void* p : S.wcos) fr(p);
-    fr(S.heads); fr(S.d_win);
-    if (S.pinned_win) (void)hipHostFree(S.pinned_win);
-    if (S.ev_win) (void)hipEventDestroy(S.ev_win);
-    for (void* p : S.wnext) fr(p);
-    fr(S.fold); fr(S.qgather);
-    for (void* p : S.poly_alt) fr(p);
-    fr(S.status_alt);
-    fr(S.aux_scan_tmp); fr(S.aux_pw);
-    for (void* q : S.lag_scalars_q) fr(q);
     wire_bases_drop(c);   // the wiring is the circuit's
-    if (S.aux_stream) {
-        (void)hipStreamSynchronize(S.aux_stream);
-        (void)hipStreamDestroy(S.aux_stream);
-    }
-    if (S.ev_aux_go) (void)hipEventDestroy(S.ev_aux_go);
-    if (S.ev_aux_done) (void)hipEventDestroy(S.ev_aux_done);
-    fr(S.qev); fr(S.small); fr(S.lag_scalars); fr(S.status); fr(S.lk_u32); fr(S.lk_keys); fr(S.pi_tab); fr(S.eval_pw);
-    if (S.pinned) (void)hipHostFree(S.pinned);
-    if (S.pinned_pi) (void)hipHostFree(S.pinned_pi);
-    if (S.copy_stream) {
-        (void)hipStreamSynchronize(S.copy_stream);
-        (void)hipStreamDestroy(S.copy_stream);
-    }
-    for (auto e : S.ev_copy) if (e) (void)hipEventDestroy(e);
-    if (S.comm_stream) {
-        (void)hipStreamSynchronize(S.comm_stream);
-        (void)hipStreamDestroy(S.comm_stream);
-    }
-    for (auto e : S.ev_piece) if (e) (void)hipEventDestroy(e);
-    if (S.ev_gathered) (void)hipEventDestroy(S.ev_gathered);
-    c->circuit.reset();   // lets go of the keys and class tables: they are freed here unless a fork still reads them
+    c->circuit.reset();
 }
 bool circuit_tables_have_readers(const zkt_ctx* c) {
     return c->circuit && (dev_shared_has_readers(c->circuit->keys_mem) || dev_shared_has_readers(c->circuit->class_mem));
@@ -1453,7 +1420,7 @@ bool circuit_tables_have_readers(const zkt_ctx* c) {
 static int circuit_alloc_work(zkt_ctx* c, CircuitState& S) {
     const size_t n = S.n, m = S.m;
     int rc;
-    auto alloc = [&](void** p, size_t elems) { return dev_alloc(c, p, elems * 32); };
+    auto alloc = [&](void** p, size_t elems) { return S.work.alloc(c, p, elems * 32); };
     if ((rc = alloc(&S.qev, 4 * n))) return rc;
     if (S.G > 1) {
         if ((rc = alloc(&S.fold, m))) return rc;
@@ -1473,32 +1440,32 @@ static int circuit_alloc_work(zkt_ctx* c, CircuitState& S) {
     if (S.G == 1) {   // quotient on classes
         if ((rc = alloc(&S.heads, 3 * NTT_MAX_BATCH * NTT_HEAD))) return rc;
         if ((rc = alloc(&S.d_win, QC_WIN_POLYS * QC_WIN))) return rc;
-        ZKT_HIP(c, hipHostMalloc(&S.pinned_win, QC_WIN_POLYS * QC_WIN * 32));
-        ZKT_HIP(c, hipEventCreateWithFlags(&S.ev_win, hipEventDisableTiming));
+        if ((rc = S.work.pinned(c, &S.pinned_win, QC_WIN_POLYS * QC_WIN * 32))) return rc;
+        if ((rc = S.work.event(c, &S.ev_win))) return rc;
     }
-    if ((rc = dev_alloc(c, (void**)&S.status, 64 * 4))) return rc;
-    if ((rc = dev_alloc(c, (void**)&S.status_alt, 64 * 4))) return rc;
+    if ((rc = S.work.alloc(c, (void**)&S.status, 64 * 4))) return rc;
+    if ((rc = S.work.alloc(c, (void**)&S.status_alt, 64 * 4))) return rc;
     for (auto& p : S.poly_alt) if ((rc = alloc(&p, n + 8))) return rc;
     S.lk_cap = n + 2;
-    if ((rc = dev_alloc(c, (void**)&S.lk_u32, 5 * S.lk_cap * 4 + 16))) return rc;
+    if ((rc = S.work.alloc(c, (void**)&S.lk_u32, 5 * S.lk_cap * 4 + 16))) return rc;
     if ((rc = alloc(&S.lk_keys, 2 * S.lk_cap))) return rc;
-    ZKT_HIP(c, hipHostMalloc(&S.pinned, 64 * 32));
-    ZKT_HIP(c, hipStreamCreateWithFlags(&S.copy_stream, hipStreamNonBlocking));
+    if ((rc = S.work.pinned(c, &S.pinned, 64 * 32))) return rc;
+    if ((rc = S.work.stream(c, &S.copy_stream))) return rc;
     if (S.G > 1) {
-        ZKT_HIP(c, hipStreamCreateWithFlags(&S.comm_stream, hipStreamNonBlocking));
-        for (auto& e : S.ev_piece) ZKT_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        ZKT_HIP(c, hipEventCreateWithFlags(&S.ev_gathered, hipEventDisableTiming));
+        if ((rc = S.work.stream(c, &S.comm_stream))) return rc;
+        for (auto& e : S.ev_piece) if ((rc = S.work.event(c, &e))) return rc;
+        if ((rc = S.work.event(c, &S.ev_gathered))) return rc;
     }
-    for (auto& e : S.ev_copy) ZKT_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    ZKT_HIP(c, hipHostMalloc(&S.pinned_pi, QUOTIENT_PI_DIRECT_MAX * 40));
-    if ((rc = dev_alloc(c, (void**)&S.pi_tab, QUOTIENT_PI_DIRECT_MAX * 40))) return rc;
+    for (auto& e : S.ev_copy) if ((rc = S.work.event(c, &e))) return rc;
+    if ((rc = S.work.pinned(c, &S.pinned_pi, QUOTIENT_PI_DIRECT_MAX * 40))) return rc;
+    if ((rc = S.work.alloc(c, (void**)&S.pi_tab, QUOTIENT_PI_DIRECT_MAX * 40))) return rc;
     if ((rc = alloc(&S.eval_pw, std::max((size_t)EVAL_MAX * (257 + eval_blocks), 2 * open_witness_powers(n + 8))))) return rc;
     if (S.G == 1) {
         if ((rc = alloc(&S.aux_scan_tmp, 2 * ((n + 8) / 1024 + 4096)))) return rc;
         if ((rc = alloc(&S.aux_pw, open_witness_powers(n + 8)))) return rc;
-        ZKT_HIP(c, hipStreamCreateWithFlags(&S.aux_stream, hipStreamNonBlocking));
-        ZKT_HIP(c, hipEventCreateWithFlags(&S.ev_aux_go, hipEventDisableTiming));
-        ZKT_HIP(c, hipEventCreateWithFlags(&S.ev_aux_done, hipEventDisableTiming));
+        if ((rc = S.work.stream(c, &S.aux_stream))) return rc;
+        if ((rc = S.work.event(c, &S.ev_aux_go))) return rc;
+        if ((rc = S.work.event(c, &S.ev_aux_done))) return rc;
     }
     return ZKT_OK;
 }
@@ -1508,7 +1475,7 @@ int circuit_fork(zkt_ctx* child, const zkt_ctx* parent) {
     circuit_release(child);
     if (!parent->circuit) return ZKT_OK;
     const CircuitState& P0 = *parent->circuit;
-    auto st = std::make_shared<CircuitState>();
+    auto st = std::make_shared<CircuitState>(child->device);
     CircuitState& S = *st;
     S.log_n = P0.log_n; S.n = P0.n; S.G = P0.G; S.cls = P0.cls; S.log_m = P0.log_m; S.m = P0.m;
     static_cast<CircuitKeys&>(S) = P0;
@@ -1517,10 +1484,9 @@ int circuit_fork(zkt_ctx* child, const zkt_ctx* parent) {
         static_cast<ClassTables&>(S) = P0;
         S.class_mem = dev_shared_reader(P0.class_mem);
     }
-    child->circuit = st;                      // from here on circuit_release cleans up after a failure
-    const int rc = circuit_alloc_work(child, S);
-    if (rc) circuit_release(child);
-    return rc;
+    if (int rc = circuit_alloc_work(child, S)) return rc;
+    child->circuit = st;
+    return ZKT_OK;
 }
 
 template <class C>
@@ -1532,7 +1498,12 @@ static int circuit_load_t(zkt_ctx* c, int log_n, const uint64_t* const* polys, c
         return set_err(c, ZKT_ERR_INVALID_DOMAIN_SIZE, "InvalidEvalDomainSize: 4n domain unsupported");
     if (int rf = refuse_if_forked(c, "loading a circuit")) return rf;
     circuit_release(c);
-    auto st = std::make_shared<CircuitState>();
+    auto st = std::make_shared<CircuitState>(c->device);
+    // a refused load lets `st` go: what it enqueued on the stream reads the half-built state, so the stream drains first
+    struct Drain {
+        zkt_ctx* c;
+        ~Drain() { if (!c->circuit) (void)hipStreamSynchronize(c->stream); }
+    } drain{c};
     CircuitState& S = *st;
     S.log_n = log_n;
     const size_t n = (size_t)1 << log_n;
@@ -2115,17 +2086,14 @@ int zkt_circuit_setup_wiring(zkt_ctx* c, int log_n, const uint64_t* const* evals
             return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "zkt_circuit_setup_wiring makes sigma1..3 itself: entries 5, 6, 7 must be NULL / 0");
     if (n_rows && (!w_l || !w_r || !w_o)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null wiring pointer");
     // the call's own buffers: the three sigma vectors and, for host wiring, the uploaded indices
+    DevSet tmp(c->device);
     void* held[6] = {};
-    auto release = [&]() {
-        (void)hipStreamSynchronize(c->stream);
-        for (void* p : held) dev_free(c, p);
-    };
     int rc = ZKT_OK;
-    for (int k = 0; k < 3 && !rc; ++k) rc = dev_alloc(c, &held[k], n * 32);
+    for (int k = 0; k < 3 && !rc; ++k) rc = tmp.alloc(c, &held[k], n * 32);
     const uint32_t* w[3] = {w_l, w_r, w_o};
     if (!wiring_on_device && n_rows) {
         for (int k = 0; k < 3 && !rc; ++k) {
-            rc = dev_alloc(c, &held[3 + k], n_rows * 4);
+            rc = tmp.alloc(c, &held[3 + k], n_rows * 4);
             if (!rc && hipMemcpyAsync(held[3 + k], w[k], n_rows * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess)
                 rc = set_err(c, ZKT_ERR_HIP, "uploading the wiring failed");
             w[k] = (const uint32_t*)held[3 + k];
@@ -2145,7 +2113,7 @@ int zkt_circuit_setup_wiring(zkt_ctx* c, int log_n, const uint64_t* const* evals
         rc = c->curve == ZKT_CURVE_BN254 ? circuit_setup_t<Bn254Curve>(c, log_n, ev, lens, mask, out_commitments, out_is_infinity)
                                          : circuit_setup_t<Bls381Curve>(c, log_n, ev, lens, mask, out_commitments, out_is_infinity);
     }
-    release();
+    (void)hipStreamSynchronize(c->stream);   // before `tmp` goes
     return rc;
 }
 
@@ -2198,6 +2166,7 @@ int zkt_debug_quotient(zkt_ctx* c, const uint64_t* challenges, const uint64_t* c
         if (pi_pos[i] >= S.n) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "public input position out of range");
     (void)hipSetDevice(c->device);
     const size_t bytes = 4 * S.n * 32;
+    DevSet tmp(c->device);
     void* d[W_COUNT] = {};
     void* d_out = nullptr;
     uint32_t* d_tab = nullptr;
@@ -2205,15 +2174,15 @@ int zkt_debug_quotient(zkt_ctx* c, const uint64_t* challenges, const uint64_t* c
     for (int k = 0; k < W_COUNT && !rc; ++k) {
         if (k == W_PI && n_pi) continue;
         if (!wit[k]) rc = set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null witness coset");
-        else if (!(rc = dev_alloc(c, &d[k], bytes)) && hipMemcpy(d[k], wit[k], bytes, hipMemcpyHostToDevice) != hipSuccess)
+        else if (!(rc = tmp.alloc(c, &d[k], bytes)) && hipMemcpy(d[k], wit[k], bytes, hipMemcpyHostToDevice) != hipSuccess)
             rc = set_err(c, ZKT_ERR_HIP, "copy of a witness coset failed");
     }
-    if (!rc) rc = dev_alloc(c, &d_out, bytes);
+    if (!rc) rc = tmp.alloc(c, &d_out, bytes);
     if (!rc && n_pi) {
         std::vector<uint32_t> tab(10 * n_pi);
         if (c->curve == ZKT_CURVE_BN254) pi_rows<Bn254Curve::Fr>(pi_pos, pi_vals, n_pi, 1, tab.data());
         else pi_rows<Bls381Curve::Fr>(pi_pos, pi_vals, n_pi, 1, tab.data());
-        if (!(rc = dev_alloc(c, (void**)&d_tab, tab.size() * 4)) &&
+        if (!(rc = tmp.alloc(c, (void**)&d_tab, tab.size() * 4)) &&
             hipMemcpy(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
             rc = set_err(c, ZKT_ERR_HIP, "copy of the public-input rows failed");
     }
@@ -2227,9 +2196,6 @@ int zkt_debug_quotient(zkt_ctx* c, const uint64_t* challenges, const uint64_t* c
         if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = set_err(c, ZKT_ERR_HIP, "quotient kernel failed");
         if (!rc && hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = set_err(c, ZKT_ERR_HIP, "copy back failed");
     }
-    for (int k = 0; k < W_COUNT; ++k) dev_free(c, d[k]);
-    dev_free(c, d_out);
-    dev_free(c, d_tab);
     return rc;
 }
 

@@ -317,17 +317,14 @@ int sigma_enqueue(zkt_ctx* c, int log_n, const uint32_t* d_w_l, const uint32_t* 
 // when the call returns
 static int sigma_build_run(zkt_ctx* c, int log_n, const uint32_t* d_w_l, const uint32_t* d_w_r, const uint32_t* d_w_o, size_t n_rows,
                            size_t n_vars, void* const* d_sigma, bool* bad_index) {
+    DevSet tmp(c->device);
     void* block = nullptr;
-    int rc = dev_alloc(c, &block, sigma_scratch_bytes(log_n, n_rows));
+    int rc = tmp.alloc(c, &block, sigma_scratch_bytes(log_n, n_rows));
     if (rc) return rc;
-    struct Release {
+    struct Drain {   // declared behind `tmp`: it runs first
         zkt_ctx* c;
-        void* p;
-        ~Release() {
-            (void)hipStreamSynchronize(c->stream);
-            dev_free(c, p);
-        }
-    } release{c, block};
+        ~Drain() { (void)hipStreamSynchronize(c->stream); }
+    } drain{c};
     // the flag lives in the block's spare last 256 bytes
     uint32_t* flag = (uint32_t*)((char*)block + sigma_scratch_bytes(log_n, n_rows) - 256);
     ZKT_HIP(c, hipMemsetAsync(flag, 0, 4, c->stream));

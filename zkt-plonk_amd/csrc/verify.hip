@@ -845,8 +845,8 @@ static int batch_fold_dev(zkt_ctx* c, const char* who, const zkt_verify_inputs* 
     const size_t o_out = up(npts * nb), o_st = o_out + up(npts * 2 * nb);
     bp.points_offset = o_out;
     bp.stage1_end = o_st + up(npts);
-    if ((rc = ensure_buffer(c, &c->verify_scratch, &c->verify_scratch_bytes, bp.stage1_end))) return rc;
-    char* const base = (char*)c->verify_scratch;
+    if ((rc = grow(c, c->verify_scratch, bp.stage1_end))) return rc;
+    char* const base = (char*)c->verify_scratch.p;
     bp.cm.resize(npts);
     std::vector<uint8_t> status(npts);
     {
@@ -984,19 +984,18 @@ static std::vector<uint64_t> leaf_scalars(const BatchPrep<C>& bp) {
 
 // verify_scratch grown with its first `keep` bytes kept (stage 1's decompressed commitments are read again)
 static int verify_scratch_grow(zkt_ctx* c, size_t keep, size_t bytes) {
-    if (c->verify_scratch && c->verify_scratch_bytes >= bytes) return ZKT_OK;
+    if (c->verify_scratch.p && c->verify_scratch.bytes >= bytes) return ZKT_OK;
     void* p = nullptr;
     int rc = dev_alloc(c, &p, bytes);
     if (rc) return rc;
-    hipError_t e = hipMemcpyAsync(p, c->verify_scratch, keep, hipMemcpyDeviceToDevice, c->stream);
+    hipError_t e = hipMemcpyAsync(p, c->verify_scratch.p, keep, hipMemcpyDeviceToDevice, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {
         dev_free(c, p);
         return hip_fail(c, e, "verify_scratch_grow");
     }
-    dev_free(c, c->verify_scratch);
-    c->verify_scratch = p;
-    c->verify_scratch_bytes = bytes;
+    dev_free(c, c->verify_scratch.p);
+    c->verify_scratch = DevBuf{p, bytes};
     return ZKT_OK;
 }
 
@@ -1008,7 +1007,7 @@ static int locate_tree_dev(zkt_ctx* c, const BatchPrep<C>& bp, size_t k, LocateT
     const VlLayout lay = vl_layout(bp.stage1_end, k, Q::N * 4, vl_raw_bytes(c->curve));
     int rc = verify_scratch_grow(c, bp.stage1_end, lay.end);
     if (rc) return rc;
-    char* const base = (char*)c->verify_scratch;
+    char* const base = (char*)c->verify_scratch.p;
     const std::vector<uint64_t> sc = leaf_scalars<C>(bp);
     // every step records its error and falls through to the one synchronise below: an upload may still be reading sc
     auto copy = [&](void* dst, const void* src, size_t bytes, hipMemcpyKind kind, const char* what) {
