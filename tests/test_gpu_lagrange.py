@@ -48,7 +48,7 @@ def _vectors(cv, log_n):
 
 
 @pytest.mark.parametrize("cv", CURVES, ids=lambda c: c.name)
-@pytest.mark.parametrize("log_n", [3, 6, 11])
+@pytest.mark.parametrize("log_n", [3, 6, 11, 13])      # 13: the first size whose prefix segments hold more than one element
 def test_commit_evals_equals_the_coefficient_commitment(cv, log_n):
     import zkt_plonk_amd as z
     n = 1 << log_n

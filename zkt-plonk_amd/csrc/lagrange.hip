@@ -264,8 +264,11 @@ size_t lagrange_bases(const zkt_ctx* c) { return c->msm ? c->msm->count2 : 0; }
 // the scan of the counts (host: the distinct variables, ascending, and the start of each one's rows), the rows grouped by
 // variable (device), one thread per distinct variable summing its few points in XYZZ and normalising them, the window
 // multiples.  A wire is left to the coefficient route when its distinct variables are WIRE_BASES_MAX_FRAC of the rows or
-// more (nothing to gain: the output wire), when a T_v is the identity (a degenerate tau: the MSM's tables hold no such
-// base), or when the table cannot be allocated.
+// more (nothing to gain: the output wire), when a T_v is the identity, or when the table cannot be allocated.  An identity
+// T_v means a degenerate tau: one in the circuit's domain, under which all [L_i(tau)] G but one are the identity and so
+// are nearly all T_v.  The MSM itself would take such a table (k_msm_accumulate skips a base at infinity, as it does for
+// a key that holds one); the wire is left alone because the table has nothing to offer then, and because the fold over
+// the free variables below (wire_fold_range) reads every T_v as a plain affine point.
 //
 // Staleness: the tables are keyed on the three vectors' addresses, n_rows, n_vars, the key and the domain -- and a
 // caller may overwrite the vectors in place.  So the build stores a 128-bit digest of their contents (two sums of
