@@ -928,13 +928,65 @@ int zkt_debug_srs_check_finish_host(int curve_id, const uint64_t* S, int S_inf, 
  * Needs no SRS and no circuit; works on a forked context and on one with a communicator (local, no collective).  Its
  * scratch memory is its own (allocated on first use, grown as needed, freed by zkt_ctx_destroy); the key, the circuit,
  * the Lagrange and wire tables stay untouched, and a proof announced with zkt_prove_set_next yields the same bytes.
- * Synchronises the stream.  Profile scopes: "verify_decompress", "verify_msm". */
+ * Synchronises the stream.  Profile scopes: "verify_decompress", "verify_msm".
+ * Under zkt_ctx_set_verify_terms(ctx, 1) (below) the transcript, r0 and the scalars of the two openings move to the
+ * device as well: one kernel, one lane per proof, enqueued directly behind the decompression, with one synchronisation
+ * for both; the host keeps the byte-level checks, the seed hash and the merge across proofs.  A, B, the coefficients, the
+ * verdict, the return codes and the proof named by zkt_last_error are the same under both modes (of several refused
+ * proofs the lowest index is reported, as the serial loop does).  The scratch grows by one more region behind the
+ * decompression's: per proof 128 bytes of description, 12 * 32 of evaluations, 232 of transcript state, 4 of status and
+ * 24 * 32 of sums, and 3 * 32 bytes per public input (roots, values, running products); each part rounded up to 256
+ * bytes; zkt_verify_batch_locate's own parts then start behind it.  Profile scope: "verify_terms".
+ * Measured on an MI355X (docs/EXPERIMENTS.md "the batch verifier's transcripts and scalar stage on the device"): mode 1
+ * wins from 256 proofs on, the next count measured after 16 (8.1 ms against 30.0 ms on BN254, 9.4 against 34.2 on
+ * BLS12-381; at 4096: 46 against 457 ms and 55 against 481 ms, 0.010 - 0.012 ms of host time per proof left), and loses
+ * below: the kernel walks one proof's hash chain per lane and takes 1.6 - 4.2 ms whatever the count (one proof: 3.0
+ * against 1.5 ms and 6.1 against 4.4 ms; 16 proofs: 5.5 against 3.5 ms on BN254, level on BLS12-381).  Mode 0 is the
+ * default and there is no automatic choice: the caller sets the mode. */
 #define ZKT_VERIFY_BATCH_DEV_MAX (ZKT_MSM_BASES_MAX / 24)
 int zkt_verify_batch_prepare_dev(zkt_ctx* ctx, const zkt_verify_inputs* ins, zkt_transcript* const* transcripts, size_t count,
                                  const uint64_t* h_g2_mont, const uint64_t* beta_h_g2_mont, uint64_t* out_ab,
                                  int* out_ab_is_infinity, uint64_t* out_rho);
 int zkt_verify_batch_dev(zkt_ctx* ctx, const zkt_verify_inputs* ins, zkt_transcript* const* transcripts, size_t count,
                          const uint64_t* h_g2_mont, const uint64_t* beta_h_g2_mont, int* accepted);
+
+/* zkt_ctx_set_verify_terms: where zkt_verify_batch_prepare_dev, zkt_verify_batch_dev, zkt_verify_batch_locate and
+ * zkt_debug_verify_batch_tree run the per-proof stage between the decompression and the MSMs -- the Fiat-Shamir replay
+ * (Merlin / STROBE-128 or the Keccak-256 Ethereum transcript), zh(xi), L_1(xi), r0, the 13 linearisation scalars, both
+ * fold lists and their sums by source.  mode 0 (the default): on the host, one proof after the other.  mode 1: on the
+ * device (csrc/verify_terms.hip; the arithmetic is csrc/verify_terms.hpp, shared with a host rehearsal).  Any other value
+ * -> ZKT_ERR_INVALID_ARGUMENT.  A fork inherits the mode.  Results do not depend on the mode.
+ * Mode 1 takes each transcript's state out of its handle, runs the replay on the device, and puts the final state back:
+ * every handle must come from zkt_transcript_new (either kind; a batch may mix kinds), else ZKT_ERR_INVALID_ARGUMENT.
+ * After a successful call each handle holds the state the host route would have left (consumed exactly as
+ * zkt_verify_prepare consumes it).  On an error NO state is written back under mode 1: every handle is as the caller
+ * seeded it (mode 0 leaves the handles in front of the refused proof consumed and that proof's partly consumed).
+ * Test hooks of the stage.  Both take the batch as zkt_verify_batch_dev does, rho_canonical4 = 2 * count coefficients as
+ * 4 canonical words each (NULL: all ones) and forced_mont = NULL or 7 * count Montgomery values beta, gamma, delta,
+ * epsilon, alpha, xi, eta per proof that replace the transcript's answers (the transcript is still fed and asked).  Per
+ * proof they return out_status (ZKT_OK, ZKT_ERR_EQUAL_CHALLENGES or ZKT_ERR_ZERO_DENOMINATOR), out_challenges (7 values,
+ * as far as they were drawn, the rest zero), out_r0 and out_acc (24 sums by source; zero for a refused proof), 4
+ * Montgomery words each, and leave every handle where the route left it, a refused proof's included.  They return ZKT_OK
+ * when they ran: a per-proof refusal is a result.  Malformed bytes or a refused commitment -> the error of the real call.
+ * zkt_debug_verify_terms: on a context, the commitments through the device's decompression; route 0 = the host code
+ * (Verifier::terms and the sums of the batch verifier), route 2 = the kernel.  Synchronises the stream.
+ * zkt_debug_verify_terms_host: no context and no device, the host verifier's own decompression; route 0 as above,
+ * route 1 = the code of csrc/verify_terms.hpp run on the host.
+ * zkt_debug_verify_terms_transcript: ONE transcript call through that code, on the host, on a handle of
+ * zkt_transcript_new (state out, the call, state in), so that its STROBE-128 and Keccak-256 can be held to known answers
+ * and to the handle's own calls.  op 0: a message -- Merlin append_message(label, data[0 .. len)), len <= 104; Ethereum one
+ * item, data little-endian, hashed big-endian, len <= 68.  op 1: a commitment that is not the identity, data = x || y
+ * little-endian, len = both.  op 2: a challenge of len = fr_bits bits (Merlin: (len + 7) / 8 - 1 bytes) -> out32,
+ * little-endian.  Anything else -> ZKT_ERR_INVALID_ARGUMENT. */
+int zkt_ctx_set_verify_terms(zkt_ctx* ctx, int mode);
+int zkt_debug_verify_terms(zkt_ctx* ctx, const zkt_verify_inputs* ins, zkt_transcript* const* transcripts, size_t count,
+                           const uint64_t* rho_canonical4, const uint64_t* forced_mont, int route, uint64_t* out_challenges,
+                           uint64_t* out_r0, uint64_t* out_acc, int* out_status);
+int zkt_debug_verify_terms_host(int curve_id, const zkt_verify_inputs* ins, zkt_transcript* const* transcripts, size_t count,
+                                const uint64_t* rho_canonical4, const uint64_t* forced_mont, int route,
+                                uint64_t* out_challenges, uint64_t* out_r0, uint64_t* out_acc, int* out_status);
+int zkt_debug_verify_terms_transcript(zkt_transcript* transcript, int op, const char* label, const uint8_t* data, size_t len,
+                                      uint8_t out32[32]);
 
 /* zkt_verify_batch_dev that also names the bad proofs of a rejected batch.  The batch check is linear in the proofs: with
  * the coefficients rho_j of zkt_verify_batch_dev (same seed), proof i has the pair

@@ -115,6 +115,7 @@ extern "C" {
     pub fn zkt_ctx_set_wire_elimination(ctx: *mut ZktCtx, mode: c_int) -> c_int;
     pub fn zkt_ctx_set_quotient_route(ctx: *mut ZktCtx, mode: c_int) -> c_int;
     pub fn zkt_ctx_set_fused_passes(ctx: *mut ZktCtx, mode: c_int) -> c_int;
+    pub fn zkt_ctx_set_verify_terms(ctx: *mut ZktCtx, mode: c_int) -> c_int;
     pub fn zkt_lagrange_info(ctx: *mut ZktCtx, log_n: *mut c_int, bases: *mut usize) -> c_int;
     pub fn zkt_circuit_load(ctx: *mut ZktCtx, log_n: c_int, pk_polys: *const *const u64, pk_lens: *const usize) -> c_int;
     pub fn zkt_circuit_load_file(ctx: *mut ZktCtx, pk_path: *const c_char, log_n: c_int) -> c_int;

@@ -10,7 +10,13 @@ device alternate within every repetition and the figure is the median wall time 
 come from the profile scopes "verify_decompress" and "verify_msm" ("verify_leaves" and "verify_tree" in the second table)
 of one more, profiled call; "host part" is that call's wall time minus the scopes.  The zkt_verify loop runs once per
 count, over the batch with one bad proof.  The last line per curve and table names the smallest measured count at which
-the device route (the locate call) is faster."""
+the device route (the locate call) is faster.
+
+A third table (--legs terms alone prints only this one) times zkt_verify_batch_dev with the per-proof term stage on the
+host (zkt_ctx_set_verify_terms mode 0) and on the device (mode 1), the two modes alternating within every repetition:
+median, minimum and maximum of whole C calls, then one profiled call per mode with its scopes ("verify_terms" is the new
+stage) and the host time that is left per proof.  A library without the switch (the parent's, loaded through
+ZKT_LIB_PATH) gets the mode-0 columns only, so that one job can hold both libraries against each other."""
 import argparse
 import ctypes
 import os
@@ -118,8 +124,50 @@ def locate_leg(L, ctx, cv, made, h, beta_h, counts, reps_arg):
           flush=True)
 
 
+def terms_leg(L, ctx, cv, made, h, beta_h, counts, reps_arg):
+    name = cv.name
+    modes = [0, 1] if hasattr(L, "zkt_ctx_set_verify_terms") else [0]
+    for mode in modes:                                                          # first use of either route: allocations, code load
+        if len(modes) > 1:
+            ctx.set_verify_terms(mode)
+        _call(L.zkt_verify_batch_dev, ctx.handle, cv, _cycle(made, max(counts)), h, beta_h)
+    print("%s: library %s" % (name, os.path.basename(_lib.lib_path())))
+    print("%s: count | mode | reps | median ms | min ms | max ms | scopes: decompress ms, terms ms, msm ms | host rest ms | host rest per proof ms"
+          % name)
+    wins = None
+    for count in counts:
+        entries = _cycle(made, count)
+        reps = reps_arg if count <= 256 else max(3, reps_arg // 3)
+        t = {m: [] for m in modes}
+        for _ in range(reps):
+            for mode in modes:
+                if len(modes) > 1:
+                    ctx.set_verify_terms(mode)
+                ms, ok = _call(L.zkt_verify_batch_dev, ctx.handle, cv, entries, h, beta_h)
+                assert ok
+                t[mode].append(ms)
+        for mode in modes:
+            if len(modes) > 1:
+                ctx.set_verify_terms(mode)
+            ctx.profile_enable(True)
+            before = {k: ctx.profile_get(k)[1] for k in ("verify_decompress", "verify_terms", "verify_msm")}
+            wall, ok = _call(L.zkt_verify_batch_dev, ctx.handle, cv, entries, h, beta_h)
+            dec, trm, msm = (ctx.profile_get(k)[1] - before[k] for k in ("verify_decompress", "verify_terms", "verify_msm"))
+            ctx.profile_enable(False)
+            rest = wall - dec - trm - msm
+            print("%s: %5d | %d | %2d | %9.3f | %9.3f | %9.3f | %8.3f %8.3f %8.3f | %9.3f | %.4f"
+                  % (name, count, mode, reps, float(np.median(t[mode])), min(t[mode]), max(t[mode]), dec, trm, msm, rest, rest / count),
+                  flush=True)
+        if len(modes) > 1 and wins is None and np.median(t[1]) < np.median(t[0]):
+            wins = count
+    if len(modes) > 1:
+        ctx.set_verify_terms(0)
+        print("%s: mode 1 is faster than mode 0 from count = %s on (of the counts measured)" % (name, wins), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--legs", default="batch,locate,terms")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--counts", default="1,16,256,4096")
     ap.add_argument("--curves", default="bn254,bls12_381")
@@ -133,6 +181,13 @@ def main():
         try:
             assert _lib.verify_batch(cv.name, _items(cv, made), h, beta_h)      # binds the host entry's argument types
             _call(L.zkt_verify_batch_dev, ctx.handle, cv, made, h, beta_h)      # first use: allocations, code load
+            legs = args.legs.split(",")
+            if "terms" in legs:
+                terms_leg(L, ctx, cv, made, h, beta_h, counts, args.reps)
+            if "batch" not in legs:
+                if "locate" in legs:
+                    locate_leg(L, ctx, cv, made, h, beta_h, counts, args.reps)
+                continue
             print("%s: count | host ms | dev ms | host/dev | dev stages: decompress ms, msm ms, host part ms | per proof host, dev ms" % name)
             crossover = None
             for count in counts:
@@ -156,7 +211,8 @@ def main():
                 print("%s: %5d | %9.2f | %9.2f | %5.2f | %8.2f %8.2f %8.2f | %.3f %.3f"
                       % (name, count, host, dev, host / dev, dec, msm, wall - dec - msm, host / count, dev / count), flush=True)
             print("%s: the device route is faster from count = %s on (of the counts measured)" % (name, crossover), flush=True)
-            locate_leg(L, ctx, cv, made, h, beta_h, counts, args.reps)
+            if "locate" in legs:
+                locate_leg(L, ctx, cv, made, h, beta_h, counts, args.reps)
         finally:
             ctx.close()
 

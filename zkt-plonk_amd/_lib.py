@@ -513,6 +513,53 @@ def debug_verify_locate_host(curve, items, h_g2, beta_h_g2, want_tree: bool = Tr
     return bool(ok.value), bad[:k].astype(bool), nchk.value, tree
 
 
+def _verify_terms_call(fn, first, cid, items, rho, forced, route):
+    """The arguments and results shared by zkt_debug_verify_terms (first = the context handle) and
+    zkt_debug_verify_terms_host (first = the curve id)."""
+    words = 8 if cid == CURVE_BN254 else 12
+    ins, trs, k, _, _, keep = _verify_batch_args(cid, items, np.zeros(2 * words, dtype=np.uint64), np.zeros(2 * words, dtype=np.uint64))
+    P64 = ctypes.POINTER(ctypes.c_uint64)
+    fn.argtypes = [ctypes.c_void_p if isinstance(first, ctypes.c_void_p) else ctypes.c_int, ctypes.POINTER(VerifyInputs),
+                   ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t, P64, P64, ctypes.c_int, P64, P64, P64,
+                   ctypes.POINTER(ctypes.c_int)]
+    rho_a = None if rho is None else np.ascontiguousarray(rho, dtype=np.uint64).reshape(2 * k, 4)
+    forced_a = None if forced is None else np.ascontiguousarray(forced, dtype=np.uint64).reshape(k, 7, 4)
+    ch = np.zeros((max(k, 1), 7, 4), dtype=np.uint64)
+    r0 = np.zeros((max(k, 1), 4), dtype=np.uint64)
+    acc = np.zeros((max(k, 1), 24, 4), dtype=np.uint64)
+    status = (ctypes.c_int * max(k, 1))()
+    rc = fn(first, ins, trs, k, None if rho_a is None else u64p(rho_a), None if forced_a is None else u64p(forced_a), int(route),
+            u64p(ch), u64p(r0), u64p(acc), status)
+    return rc, (ch[:k], r0[:k], acc[:k], np.array(list(status)[:k], dtype=np.int64))
+
+
+def debug_verify_terms_host(curve, items, rho=None, forced=None, route: int = 1):
+    """zkt_debug_verify_terms_host: the batch verifier's per-proof term stage on the host, no context and no device.  route 0:
+    the host verifier's code; route 1: the code the kernel runs.  `items` as verify_batch; rho: None (all ones) or (2*count, 4)
+    canonical words; forced: None or (count, 7, 4) Montgomery words beta gamma delta epsilon alpha xi eta that replace the
+    transcript's answers.  -> (challenges (count, 7, 4), r0 (count, 4), sums (count, 24, 4), all Montgomery words, status
+    (count,) codes); every Transcript of `items` is left where the route left it."""
+    cid = curve_id(curve)
+    rc, out = _verify_terms_call(lib().zkt_debug_verify_terms_host, cid, cid, items, rho, forced, route)
+    if rc:
+        raise ZktError(rc, "zkt_debug_verify_terms_host")
+    return out
+
+
+def debug_verify_terms_transcript(transcript, op: int, label: bytes, data: bytes = b"", bits: int = 0) -> bytes:
+    """zkt_debug_verify_terms_transcript: one transcript call on `transcript` (a Transcript) through the code the term
+    kernel runs, on the host.  op 0: a message (Merlin) or one item given little-endian (Ethereum); op 1: a commitment,
+    data = x || y little-endian; op 2: a challenge of `bits` bits -> its 32 little-endian bytes."""
+    L = lib()
+    L.zkt_debug_verify_terms_transcript.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t,
+                                                    ctypes.POINTER(ctypes.c_uint8)]
+    out = (ctypes.c_uint8 * 32)()
+    rc = L.zkt_debug_verify_terms_transcript(transcript.handle, int(op), label, bytes(data), bits if op == 2 else len(data), out)
+    if rc:
+        raise ZktError(rc, "zkt_debug_verify_terms_transcript")
+    return bytes(out)
+
+
 class ProveInputs(ctypes.Structure):
     _fields_ = [("a_evals", ctypes.POINTER(ctypes.c_uint64)), ("b_evals", ctypes.POINTER(ctypes.c_uint64)),
                 ("c_evals", ctypes.POINTER(ctypes.c_uint64)), ("n_rows", ctypes.c_size_t),
@@ -1330,6 +1377,19 @@ class Context:
         rho = np.zeros((2 * max(k, 1), 4), dtype=np.uint64)
         self.check(self._L.zkt_debug_verify_batch_tree(self._h, ins, trs, k, u64p(h), u64p(bh), u64p(nodes), inf, u64p(rho)))
         return nodes, np.array([bool(x) for x in inf]).reshape(2, n_nodes), rho[:2 * k]
+
+    def set_verify_terms(self, mode: int = 0):
+        """zkt_ctx_set_verify_terms: where the batch verifier runs its transcripts and scalar stage, 0 on the host (the
+        default), 1 on the device; results do not depend on it"""
+        self._L.zkt_ctx_set_verify_terms.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        self.check(self._L.zkt_ctx_set_verify_terms(self._h, int(mode)))
+
+    def debug_verify_terms(self, items, rho=None, forced=None, route: int = 2):
+        """zkt_debug_verify_terms: the term stage alone, the commitments through the device's decompression; route 0 the
+        host code, route 2 the kernel.  Arguments and results as _lib.debug_verify_terms_host."""
+        rc, out = _verify_terms_call(self._L.zkt_debug_verify_terms, self._h, self.curve, items, rho, forced, route)
+        self.check(rc)
+        return out
 
     def msm_bases_info(self, n: int, montgomery: bool = True):
         """-> dict(window_bits, windows) that zkt_msm_g1_bases uses for n points"""

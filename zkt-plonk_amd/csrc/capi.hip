@@ -279,6 +279,7 @@ int zkt_ctx_fork(zkt_ctx* parent, zkt_ctx** out) {
     c->wire_elim_mode = parent->wire_elim_mode;
     c->quotient_route = parent->quotient_route;
     c->fused_passes = parent->fused_passes;
+    c->verify_terms_mode = parent->verify_terms_mode;
     c->fused_parts = parent->fused_parts;
     c->batch_off = parent->batch_off;
     c->aux_off = parent->aux_off;

@@ -104,6 +104,7 @@ struct zkt_ctx {
     bool lagrange_off = false;     // zkt_ctx_set_lagrange(ctx, 0): evaluations are committed through their coefficients
     int wire_elim_mode = 1;        // zkt_ctx_set_wire_elimination: 0 off, 1 automatic (large circuits), 2 whenever a table can be built
     int quotient_route = 0;        // zkt_ctx_set_quotient_route: 0 automatic (three classes on large single-GPU circuits), 1 three classes, 2 the whole coset
+    int verify_terms_mode = 0;     // zkt_ctx_set_verify_terms: the batch verifier's transcripts and scalar stage, 0 on the host, 1 on the device
     int fused_passes = 0;          // zkt_ctx_set_fused_passes: 0 automatic (fused), 1 fused, 2 one launch per step (the reference sequence)
     // the parts of the fused sequences, one bit each: 1 = round 5's openings, 2 = round 3's grand products, 4 = blinding,
     // 8 = the classes route's three classes in one grid (transforms and quotient kernel), 16 = its closing pass (combine,

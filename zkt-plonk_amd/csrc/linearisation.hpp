@@ -14,6 +14,7 @@ namespace zkt {
 enum { EV_A = 0, EV_B, EV_C, EV_S1, EV_S2, EV_Z1N, EV_QL, EV_T, EV_TN, EV_Z2N, EV_H1N, EV_H2, EV_COUNT };
 static const char* const EV_LABEL[EV_COUNT] = {"a_eval", "b_eval", "c_eval", "sigma1_eval", "sigma2_eval", "z1_next_eval",
                                                "q_lookup_eval", "t_eval", "t_next_eval", "z2_next_eval", "h1_next_eval", "h2_eval"};
+// (the device replay of the verifier keeps the same labels in the same order: verify_terms.hpp vt_ev_label)
 // the thirteen terms of the linearisation, in the order of commitment.rs:32-45
 enum { LIN_QM = 0, LIN_QL, LIN_QR, LIN_QO, LIN_QC, LIN_Z1, LIN_S3, LIN_Z2, LIN_H1, LIN_QTABLE, LIN_QLO, LIN_QMID, LIN_QHI, LIN_COUNT };
 
@@ -37,7 +38,7 @@ template <class R> static bool xi_point(const Challenges<R>& ch, uint64_t n, XiP
     return true;
 }
 
-template <class R> static void linearisation_scalars(const Challenges<R>& ch, const XiPoint<R>& at, const Fe<R>* ev, Fe<R> sc[LIN_COUNT]) {
+template <class R> ZKT_HD void linearisation_scalars(const Challenges<R>& ch, const XiPoint<R>& at, const Fe<R>* ev, Fe<R> sc[LIN_COUNT]) {
     typedef Fe<R> F;
     const F &alpha = ch.alpha, &beta = ch.beta, &gamma = ch.gamma, &delta = ch.delta, &epsilon = ch.epsilon, &xi = ch.xi;
     const F one = fe_one<R>(), k1 = fe_from_u32<R>(7), k2 = fe_from_u32<R>(13);

@@ -132,6 +132,23 @@ void Strobe128::prf(uint8_t* out, size_t len, bool more) {
     squeeze(out, len);
 }
 
+void Strobe128::export_state(TranscriptState& out) const {
+    out = TranscriptState();
+    out.kind = 0;
+    out.pos = pos_;
+    out.pos_begin = pos_begin_;
+    out.cur_flags = cur_flags_;
+    memcpy(out.bytes, st_, 200);
+}
+bool Strobe128::import_state(const TranscriptState& in) {
+    if (in.pos >= (uint32_t)R || in.pos_begin > (uint32_t)R || in.cur_flags > 255) return false;
+    pos_ = (uint8_t)in.pos;
+    pos_begin_ = (uint8_t)in.pos_begin;
+    cur_flags_ = (uint8_t)in.cur_flags;
+    memcpy(st_, in.bytes, 200);
+    return true;
+}
+
 // ---- merlin::Transcript --------------------------------------------------------------------------
 Merlin::Merlin(const std::string& label) : strobe_("Merlin v1.0") {
     append_message("dom-sep", reinterpret_cast<const uint8_t*>(label.data()), label.size());
@@ -182,6 +199,21 @@ void MerlinHostTranscript::challenge_scalar(const char* label, size_t fr_bits, u
 EthereumHostTranscript::EthereumHostTranscript() {
     memset(state0_, 0, 32);
     memset(state1_, 0, 32);
+}
+bool EthereumHostTranscript::export_state(TranscriptState& out) const {
+    out = TranscriptState();
+    out.kind = 1;
+    out.counter = counter_;
+    memcpy(out.bytes, state0_, 32);
+    memcpy(out.bytes + 32, state1_, 32);
+    return true;
+}
+bool EthereumHostTranscript::import_state(const TranscriptState& in) {
+    if (in.kind != 1) return false;
+    counter_ = in.counter;
+    memcpy(state0_, in.bytes, 32);
+    memcpy(state1_, in.bytes + 32, 32);
+    return true;
 }
 void EthereumHostTranscript::append_bytes(const uint8_t* item, size_t len) {
     std::vector<uint8_t> data(1 + 64 + len);

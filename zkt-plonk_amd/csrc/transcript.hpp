@@ -16,12 +16,22 @@ namespace zkt {
 void keccak_f1600(uint8_t state[200]);
 void keccak256(const uint8_t* data, size_t len, uint8_t out[32]);
 
+// A built-in transcript's whole state, as it crosses to the device and back (verify_terms.hpp runs the verifier's replay
+// from it).  kind 0, Merlin: bytes = the 200 bytes of the STROBE sponge, with pos / pos_begin / cur_flags.  kind 1,
+// Ethereum: bytes[0 .. 64) = state0 || state1, with counter.  The sponge is read as 25 little-endian 64-bit words.
+struct alignas(8) TranscriptState {
+    uint32_t kind = 0, pos = 0, pos_begin = 0, cur_flags = 0, counter = 0, reserved[3] = {0, 0, 0};
+    uint8_t bytes[200] = {0};
+};
+
 class Strobe128 {
   public:
     explicit Strobe128(const std::string& protocol_label);
     void meta_ad(const uint8_t* data, size_t len, bool more);
     void ad(const uint8_t* data, size_t len, bool more);
     void prf(uint8_t* out, size_t len, bool more);
+    void export_state(TranscriptState& out) const;
+    bool import_state(const TranscriptState& in);   // false: a position outside the rate (nothing is changed)
 
   private:
     static constexpr int R = 166;
@@ -39,6 +49,8 @@ class Merlin {
     void append_message(const std::string& label, const uint8_t* msg, size_t len);
     void append_u64(const std::string& label, uint64_t x);
     void challenge_bytes(const std::string& label, uint8_t* out, size_t len);
+    void export_state(TranscriptState& out) const { strobe_.export_state(out); }
+    bool import_state(const TranscriptState& in) { return strobe_.import_state(in); }
 
   private:
     Strobe128 strobe_;
@@ -56,6 +68,9 @@ struct HostTranscript {
                                    bool infinity) = 0;
     // 32 bytes little-endian canonical challenge
     virtual void challenge_scalar(const char* label, size_t fr_bits, uint8_t out_le[32]) = 0;
+    // the whole state out and in again; false: this transcript has no state of its own to give (a caller's callbacks)
+    virtual bool export_state(TranscriptState&) const { return false; }
+    virtual bool import_state(const TranscriptState&) { return false; }
 };
 
 struct MerlinHostTranscript : HostTranscript {
@@ -65,6 +80,8 @@ struct MerlinHostTranscript : HostTranscript {
     void append_commitment(const char* label, const uint8_t* x_le, const uint8_t* y_le, size_t fq_bytes,
                            bool infinity) override;
     void challenge_scalar(const char* label, size_t fr_bits, uint8_t out_le[32]) override;
+    bool export_state(TranscriptState& out) const override { t.export_state(out); return true; }
+    bool import_state(const TranscriptState& in) override { return in.kind == 0 && t.import_state(in); }
     Merlin t;
 };
 
@@ -75,6 +92,8 @@ struct EthereumHostTranscript : HostTranscript {
     void append_commitment(const char* label, const uint8_t* x_le, const uint8_t* y_le, size_t fq_bytes,
                            bool infinity) override;
     void challenge_scalar(const char* label, size_t fr_bits, uint8_t out_le[32]) override;
+    bool export_state(TranscriptState& out) const override;
+    bool import_state(const TranscriptState& in) override;
 
   private:
     void append_bytes(const uint8_t* item, size_t len);

@@ -17,6 +17,7 @@
 #include "pairing.hpp"
 #include "transcript.hpp"
 #include "verify_leaves.hpp"
+#include "verify_terms.hpp"
 
 #include <cstring>
 #include <map>
@@ -812,10 +813,130 @@ static int batch_terms(const zkt_verify_inputs* ins, zkt_transcript* const* trs,
     return ZKT_OK;
 }
 
+// ---- stage 2 and the per-proof sums of stage 4 on the device (zkt_ctx_set_verify_terms(ctx, 1); verify_terms.hpp) ----
+// the ten verifier-key points and g of one proof, as Verifier::terms reads them: sources SRC_VK .. SRC_G
+template <class C>
+static void other_bases(const zkt_verify_inputs& in, Affine<typename C::Fq>* out11) {
+    using Q = typename C::Fq;
+    const size_t nb = Q::N * 4;
+    const int L64 = Q::N / 2;
+    for (int k = 0; k < 10; ++k) {
+        if (in.vk_is_infinity && in.vk_is_infinity[k]) {
+            out11[k].x = fe_zero<Q>();
+            out11[k].y = fe_zero<Q>();
+        } else {
+            memcpy(out11[k].x.v, in.vk_commitments + (size_t)k * 2 * L64, nb);
+            memcpy(out11[k].y.v, in.vk_commitments + (size_t)k * 2 * L64 + L64, nb);
+        }
+    }
+    memcpy(out11[10].x.v, in.g, nb);
+    memcpy(out11[10].y.v, in.g + L64, nb);
+}
+
+// What stages 1 and 2 on the device bring down: the status of every commitment and the image of the kernel's region
+struct TermsDev {
+    VtLayout lay;
+    std::vector<uint8_t> host;          // the region from lay.desc on, as uploaded and, from lay.states on, as downloaded
+    std::vector<uint8_t> point_status;
+    uint8_t* at(size_t off) { return host.data() + (off - lay.desc); }
+};
+
+// Stage 1's launch and, directly behind it on the stream, the kernel of verify_terms.hip; statuses, points, sums and
+// transcript states come down together and the stream is synchronised ONCE.  In: batch_bytes has run, bp.rho is set.
+// forced_mont: NULL or 7 k values; dbg: the kernel also returns challenges and r0.  *refused: the error is bp's (a proof
+// and a reason), not the runtime's.
+template <class C>
+static int stages12_dev(zkt_ctx* c, const zkt_verify_inputs* ins, zkt_transcript* const* trs, size_t k, BatchPrep<C>& bp,
+                        const uint64_t* forced_mont, bool dbg, TermsDev& td, bool* refused) {
+    using Q = typename C::Fq;
+    using R = typename C::Fr;
+    using F = Fe<R>;
+    const size_t nb = Q::N * 4, npts = 13 * k;
+    *refused = false;
+    size_t total_pi = 0;
+    for (size_t i = 0; i < k; ++i) total_pi += ins[i].n_pi;
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t o_out = up(npts * nb), o_st = o_out + up(npts * 2 * nb);
+    const VtLayout lay = vt_layout(o_st + up(npts), k, total_pi, forced_mont != nullptr, dbg);
+    td.lay = lay;
+    td.host.assign(lay.end - lay.desc, 0);
+    auto* desc = (VtDesc<R>*)td.at(lay.desc);
+    auto* states = (TranscriptState*)td.at(lay.states);
+    size_t pi_at = 0;
+    F w_of[R::TWO_ADICITY + 1];          // a domain generator costs an exponentiation: once per size, not per proof
+    bool have_w[R::TWO_ADICITY + 1] = {false};
+    for (size_t i = 0; i < k; ++i) {
+        const zkt_verify_inputs& in = ins[i];
+        const int lg = bp.log_n[i];
+        if (!have_w[lg]) {
+            w_of[lg] = root_of_unity<R>(lg);
+            have_w[lg] = true;
+        }
+        desc[i].n = in.n;
+        desc[i].n_pi = in.n_pi;
+        desc[i].pi_off = pi_at;
+        desc[i].reserved = 0;
+        desc[i].w = w_of[lg];
+        desc[i].rho[0] = bp.rho[2 * i];
+        desc[i].rho[1] = bp.rho[2 * i + 1];
+        if (in.n_pi) {
+            memcpy(td.at(lay.roots) + pi_at * 32, in.pi_roots, in.n_pi * 32);
+            memcpy(td.at(lay.vals) + pi_at * 32, in.pub_inputs, in.n_pi * 32);
+        }
+        pi_at += in.n_pi;
+        states[i] = TranscriptState();
+        if (!trs[i]->impl->export_state(states[i])) {
+            *refused = true;
+            return bp.refuse(ZKT_ERR_INVALID_ARGUMENT, i, "a transcript that zkt_transcript_new did not make");
+        }
+    }
+    memcpy(td.at(lay.ev), bp.ev.data(), k * 12 * sizeof(F));
+    if (forced_mont) memcpy(td.at(lay.forced), forced_mont, k * 7 * 32);
+    bp.points_offset = o_out;
+    bp.stage1_end = lay.end;             // zkt_verify_batch_locate's own region starts behind this stage's
+    int rc = grow(c, c->verify_scratch, lay.end);
+    if (rc) return rc;
+    char* const base = (char*)c->verify_scratch.p;
+    bp.cm.resize(npts);
+    td.point_status.resize(npts);
+    const size_t down_end = dbg ? lay.before : lay.dbg;
+    // every step records its error and falls through to the one synchronise: an upload may still be reading td.host
+    auto copy = [&](void* dst, const void* src, size_t bytes, hipMemcpyKind kind, const char* what) {
+        if (rc) return;
+        const hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, c->stream);
+        if (e != hipSuccess) rc = hip_fail(c, e, what);
+    };
+    {
+        ProfScope prof(c, "verify_decompress");
+        copy(base, bp.comp.data(), npts * nb, hipMemcpyHostToDevice, "verify batch: commitments upload");
+        if (!rc) rc = g1_decompress_enqueue(c, base, npts, base + o_out, base + o_st);
+    }
+    {
+        ProfScope prof(c, "verify_terms");
+        copy(base + lay.desc, td.at(lay.desc), lay.status - lay.desc, hipMemcpyHostToDevice, "verify terms: upload");
+        if (!rc) rc = verify_terms_enqueue(c, base, lay, base + o_out, k, forced_mont != nullptr, dbg);
+        copy(td.at(lay.states), base + lay.states, down_end - lay.states, hipMemcpyDeviceToHost, "verify terms: download");
+    }
+    copy(bp.cm.data(), base + o_out, npts * 2 * nb, hipMemcpyDeviceToHost, "verify batch: points download");
+    copy(td.point_status.data(), base + o_st, npts, hipMemcpyDeviceToHost, "verify batch: statuses download");
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    if (!rc && e != hipSuccess) rc = hip_fail(c, e, "verify terms");
+    return rc;
+}
+
+// the first commitment the decompression refused: its index, or npts
+static size_t first_refused_point(const std::vector<uint8_t>& status) {
+    for (size_t p = 0; p < status.size(); ++p)
+        if (status[p] > ZKT_G1_IDENTITY) return p;
+    return status.size();
+}
+
 // ---- zkt_verify_batch_dev: the batch above with its two per-proof costs on the device ------------------------------
 // Stage 1: the 13 k compressed commitments go up in one copy and through ONE k_g1_decompress launch (g1decomp.hip); the
 //          other bytes of a proof (length, Option::None, evaluations) are checked here.
 // Stage 2: Verifier::terms per proof, on the host: transcript, r0, the scalars of both openings -- no group arithmetic.
+//          (zkt_ctx_set_verify_terms(ctx, 1): in one kernel behind stage 1's, with the per-proof sums of stage 4 --
+//          stages12_dev above; stage 3 then runs first, since the kernel takes each proof's rho.)
 // Stage 3: rho_0 = 1, rho_j = low 128 bits of Keccak-256(seed || j); the seed is hashed from everything that determines the
 //          pairs (L_j, W_j), which this route never forms (verify_batch_t hashes the pairs: other coefficients, the same
 //          soundness argument).
@@ -838,39 +959,64 @@ static int batch_fold_dev(zkt_ctx* c, const char* who, const zkt_verify_inputs* 
     auto fail = [&](int rc, size_t i, const std::string& what) {
         return set_err(c, rc, std::string(who) + ": proof " + std::to_string(i) + ": " + what);
     };
+    auto refused_commitment = [&](size_t p, uint8_t st) {
+        static const char* const WHY[6] = {"", "", "x is not below the modulus", "both flag bits set", "not on the curve",
+                                           "outside the prime-order subgroup"};
+        return fail(ZKT_ERR_INVALID_ARGUMENT, p / 13,
+                    std::string("commitment ") + std::to_string(p % 13) + " (" + CM_NAME[p % 13] + ") refused: " +
+                        (st < 6 ? WHY[st] : "unknown status"));
+    };
     // ---- stage 1 ----
     int rc = batch_bytes<C>(ins, trs, k, bp);
     if (rc) return fail(rc, bp.err_proof, bp.err_what);
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t o_out = up(npts * nb), o_st = o_out + up(npts * 2 * nb);
-    bp.points_offset = o_out;
-    bp.stage1_end = o_st + up(npts);
-    if ((rc = grow(c, c->verify_scratch, bp.stage1_end))) return rc;
-    char* const base = (char*)c->verify_scratch.p;
-    bp.cm.resize(npts);
-    std::vector<uint8_t> status(npts);
-    {
-        ProfScope prof(c, "verify_decompress");
-        ZKT_HIP(c, hipMemcpyAsync(base, bp.comp.data(), npts * nb, hipMemcpyHostToDevice, c->stream));
-        if ((rc = g1_decompress_enqueue(c, base, npts, base + o_out, base + o_st))) {
-            (void)hipStreamSynchronize(c->stream);
-            return rc;
+    if (c->verify_terms_mode == 1) {
+        // ---- stage 3 first (the kernel takes each proof's rho), stages 1 and 2 in one pass over the stream ----
+        batch_coefficients<C>(ins, k, h, beta_h, bp);
+        TermsDev td;
+        bool refused = false;
+        if ((rc = stages12_dev<C>(c, ins, trs, k, bp, nullptr, false, td, &refused)))
+            return refused ? fail(rc, bp.err_proof, bp.err_what) : rc;
+        // refusals in the serial loop's order: the first refused commitment, then the lowest proof the term stage refused
+        const size_t p = first_refused_point(td.point_status);
+        if (p < npts) return refused_commitment(p, td.point_status[p]);
+        const int32_t* tstat = (const int32_t*)td.at(td.lay.status);
+        for (size_t i = 0; i < k; ++i)
+            if (tstat[i])
+                return fail(tstat[i], i, tstat[i] == ZKT_ERR_EQUAL_CHALLENGES ? "two challenges are equal" : "a Lagrange denominator is zero");
+        // every proof went through: the handles take the states the host route would have left
+        const TranscriptState* states = (const TranscriptState*)td.at(td.lay.states);
+        for (size_t i = 0; i < k; ++i)
+            if (!trs[i]->impl->import_state(states[i])) return fail(ZKT_ERR_INVALID_ARGUMENT, i, "the transcript refused its state");
+        bp.acc.resize(V::SRC_COUNT * k);
+        memcpy((void*)bp.acc.data(), td.at(td.lay.acc), bp.acc.size() * sizeof(F));
+        bp.other.resize(11 * k);
+        for (size_t i = 0; i < k; ++i) other_bases<C>(ins[i], &bp.other[11 * i]);
+    } else {
+        auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+        const size_t o_out = up(npts * nb), o_st = o_out + up(npts * 2 * nb);
+        bp.points_offset = o_out;
+        bp.stage1_end = o_st + up(npts);
+        if ((rc = grow(c, c->verify_scratch, bp.stage1_end))) return rc;
+        char* const base = (char*)c->verify_scratch.p;
+        bp.cm.resize(npts);
+        std::vector<uint8_t> status(npts);
+        {
+            ProfScope prof(c, "verify_decompress");
+            ZKT_HIP(c, hipMemcpyAsync(base, bp.comp.data(), npts * nb, hipMemcpyHostToDevice, c->stream));
+            if ((rc = g1_decompress_enqueue(c, base, npts, base + o_out, base + o_st))) {
+                (void)hipStreamSynchronize(c->stream);
+                return rc;
+            }
+            ZKT_HIP(c, hipMemcpyAsync(bp.cm.data(), base + o_out, npts * 2 * nb, hipMemcpyDeviceToHost, c->stream));
+            ZKT_HIP(c, hipMemcpyAsync(status.data(), base + o_st, npts, hipMemcpyDeviceToHost, c->stream));
         }
-        ZKT_HIP(c, hipMemcpyAsync(bp.cm.data(), base + o_out, npts * 2 * nb, hipMemcpyDeviceToHost, c->stream));
-        ZKT_HIP(c, hipMemcpyAsync(status.data(), base + o_st, npts, hipMemcpyDeviceToHost, c->stream));
+        ZKT_HIP(c, hipStreamSynchronize(c->stream));
+        for (size_t p = 0; p < npts; ++p)
+            if (status[p] > ZKT_G1_IDENTITY) return refused_commitment(p, status[p]);
+        // ---- stage 3 (before the transcripts are consumed), stage 2 and the per-proof sums of stage 4 ----
+        batch_coefficients<C>(ins, k, h, beta_h, bp);
+        if ((rc = batch_terms<C>(ins, trs, k, bp))) return fail(rc, bp.err_proof, bp.err_what);
     }
-    ZKT_HIP(c, hipStreamSynchronize(c->stream));
-    for (size_t p = 0; p < npts; ++p)
-        if (status[p] > ZKT_G1_IDENTITY) {
-            static const char* const WHY[6] = {"", "", "x is not below the modulus", "both flag bits set", "not on the curve",
-                                               "outside the prime-order subgroup"};
-            return fail(ZKT_ERR_INVALID_ARGUMENT, p / 13,
-                        std::string("commitment ") + std::to_string(p % 13) + " (" + CM_NAME[p % 13] + ") refused: " +
-                            (status[p] < 6 ? WHY[status[p]] : "unknown status"));
-        }
-    // ---- stage 3 (before the transcripts are consumed), stage 2 and the per-proof sums of stage 4 ----
-    batch_coefficients<C>(ins, k, h, beta_h, bp);
-    if ((rc = batch_terms<C>(ins, trs, k, bp))) return fail(rc, bp.err_proof, bp.err_what);
     // ---- stage 4 across proofs ----
     const size_t m = 2 * k;
     std::vector<Affine<Q>> a_bases, b_bases(m);
@@ -921,6 +1067,231 @@ static int verify_batch_prepare_dev_t(zkt_ctx* c, const zkt_verify_inputs* ins, 
     int rc = batch_fold_dev<C>(c, "verify_batch_dev", ins, trs, k, h, beta_h, bp, out_ab, out_inf);
     if (rc) return rc;
     if (out_rho) memcpy(out_rho, bp.rho_c.data(), 2 * k * 32);
+    return ZKT_OK;
+}
+
+// ---- zkt_debug_verify_terms / zkt_debug_verify_terms_host: the term stage alone, by any of its three routes ----------
+// A transcript that hands `inner`'s calls on and replaces its answers by forced[0 .. 7) (Montgomery) in the order they are
+// asked for; it is still fed and asked, so its state moves as usual (tests/forced_challenges.py does the same to the prover)
+template <class R>
+struct ForcedTranscript : HostTranscript {
+    HostTranscript& inner;
+    const Fe<R>* forced;
+    Fe<R> drawn[7];
+    int n_drawn = 0;
+    ForcedTranscript(HostTranscript& in, const Fe<R>* f) : inner(in), forced(f) {}
+    void append_u64(const char* label, uint64_t v) override { inner.append_u64(label, v); }
+    void append_scalars(const char* label, const uint8_t* le, size_t count, size_t fr_bytes, bool single) override {
+        inner.append_scalars(label, le, count, fr_bytes, single);
+    }
+    void append_commitment(const char* label, const uint8_t* x, const uint8_t* y, size_t fq_bytes, bool inf) override {
+        inner.append_commitment(label, x, y, fq_bytes, inf);
+    }
+    void challenge_scalar(const char* label, size_t fr_bits, uint8_t out_le[32]) override {
+        inner.challenge_scalar(label, fr_bits, out_le);
+        if (n_drawn >= 7) return;
+        if (forced) {
+            const Fe<R> v = fe_from_mont<R>(forced[n_drawn]);
+            memcpy(out_le, v.v, 32);
+        }
+        Fe<R> v;
+        memcpy(v.v, out_le, 32);
+        drawn[n_drawn++] = fe_to_mont<R>(v);
+    }
+};
+
+// c == nullptr: no device (routes 0 and 1, the host's own decompression); route 2 needs a context
+template <class C>
+static int debug_terms_t(zkt_ctx* c, const zkt_verify_inputs* ins, zkt_transcript* const* trs, size_t k, const uint64_t* rho_c4,
+                         const uint64_t* forced_mont, int route, uint64_t* out_ch, uint64_t* out_r0, uint64_t* out_acc,
+                         int* out_status) {
+    using V = Verifier<C>;
+    using Q = typename C::Fq;
+    using R = typename C::Fr;
+    using F = Fe<R>;
+    const size_t nb = Q::N * 4, npts = 13 * k;
+    auto err = [&](int rc, const std::string& what) { return c ? set_err(c, rc, "debug_verify_terms: " + what) : rc; };
+    BatchPrep<C> bp;
+    int rc = batch_bytes<C>(ins, trs, k, bp);
+    if (rc) return err(rc, "proof " + std::to_string(bp.err_proof) + ": " + bp.err_what);
+    bp.rho.resize(2 * k);
+    for (size_t j = 0; j < 2 * k; ++j) {
+        F r = fe_zero<R>();
+        r.v[0] = 1;
+        if (rho_c4) memcpy(r.v, rho_c4 + 4 * j, 32);
+        bp.rho[j] = fe_to_mont<R>(r);
+    }
+    memset(out_ch, 0, k * 7 * 32);
+    memset(out_r0, 0, k * 32);
+    memset(out_acc, 0, k * V::SRC_COUNT * 32);
+    if (route == 2) {
+        TermsDev td;
+        bool refused = false;
+        if ((rc = stages12_dev<C>(c, ins, trs, k, bp, forced_mont, true, td, &refused)))
+            return refused ? err(rc, "proof " + std::to_string(bp.err_proof) + ": " + bp.err_what) : rc;
+        if (first_refused_point(td.point_status) < npts) return err(ZKT_ERR_INVALID_ARGUMENT, "a commitment was refused");
+        const TranscriptState* states = (const TranscriptState*)td.at(td.lay.states);
+        const int32_t* tstat = (const int32_t*)td.at(td.lay.status);
+        for (size_t i = 0; i < k; ++i) {
+            if (!trs[i]->impl->import_state(states[i])) return err(ZKT_ERR_INVALID_ARGUMENT, "the transcript refused its state");
+            out_status[i] = tstat[i];
+            memcpy(out_ch + 28 * i, td.at(td.lay.dbg) + i * 8 * 32, 7 * 32);
+            memcpy(out_r0 + 4 * i, td.at(td.lay.dbg) + (i * 8 + 7) * 32, 32);
+        }
+        memcpy(out_acc, td.at(td.lay.acc), k * V::SRC_COUNT * 32);
+        return ZKT_OK;
+    }
+    // ---- the commitments: through the device's decompression where there is a device ----
+    bp.cm.resize(npts);
+    if (c) {
+        auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+        const size_t o_out = up(npts * nb), o_st = o_out + up(npts * 2 * nb);
+        if ((rc = grow(c, c->verify_scratch, o_st + up(npts)))) return rc;
+        char* const base = (char*)c->verify_scratch.p;
+        std::vector<uint8_t> status(npts);
+        hipError_t e = hipMemcpyAsync(base, bp.comp.data(), npts * nb, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) rc = g1_decompress_enqueue(c, base, npts, base + o_out, base + o_st);
+        if (e == hipSuccess && !rc) e = hipMemcpyAsync(bp.cm.data(), base + o_out, npts * 2 * nb, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && !rc) e = hipMemcpyAsync(status.data(), base + o_st, npts, hipMemcpyDeviceToHost, c->stream);
+        const hipError_t es = hipStreamSynchronize(c->stream);
+        if (rc) return rc;
+        if (e != hipSuccess || es != hipSuccess) return hip_fail(c, e != hipSuccess ? e : es, "debug_verify_terms: decompression");
+        if (first_refused_point(status) < npts) return err(ZKT_ERR_INVALID_ARGUMENT, "a commitment was refused");
+    } else {
+        for (size_t p = 0; p < npts; ++p) {
+            bool inf = false;
+            if (!decompress<C>(bp.comp.data() + p * nb, &bp.cm[p], &inf)) return ZKT_ERR_INVALID_ARGUMENT;
+        }
+    }
+    const F* forced = (const F*)forced_mont;
+    auto t = std::make_unique<typename V::Terms>();
+    for (size_t i = 0; i < k; ++i) {
+        F* acc = (F*)(out_acc + 4 * V::SRC_COUNT * i);
+        if (route == 0) {
+            // the existing host code: Verifier::terms, then the sums of batch_terms
+            ForcedTranscript<R> ft(*trs[i]->impl, forced ? forced + 7 * i : nullptr);
+            out_status[i] = V::terms(ins[i], bp.log_n[i], &bp.cm[13 * i], &bp.ev[12 * i], ft, *t);
+            memcpy(out_ch + 28 * i, ft.drawn, (size_t)ft.n_drawn * 32);
+            if (out_status[i]) continue;
+            for (int s = 0; s < V::SRC_COUNT; ++s) acc[s] = fe_zero<R>();
+            for (int o = 0; o < 2; ++o)
+                for (int q = 0; q < t->n[o]; ++q)
+                    acc[t->src[o][q]] = fe_add<R>(acc[t->src[o][q]], fe_mul<R>(bp.rho[2 * i + o], t->sc[o][q]));
+            // r0 is not among the terms' outputs; the scalar on g of the first opening is -(r0 + sum_i eta^(i+1) v_i)
+            const F* ev = &bp.ev[12 * i];
+            const F vs[8] = {ev[EV_A], ev[EV_B], ev[EV_C], ev[EV_S1], ev[EV_S2], ev[EV_QL], ev[EV_T], ev[EV_H2]};
+            const F eta = ft.drawn[6];
+            F r0 = fe_neg<R>(t->sc[0][13 + 8]), ch = eta;
+            for (int q = 0; q < 8; ++q) {
+                r0 = fe_sub<R>(r0, fe_mul<R>(ch, vs[q]));
+                ch = fe_mul<R>(ch, eta);
+            }
+            memcpy(out_r0 + 4 * i, r0.v, 32);
+        } else {
+            // the shared code of verify_terms.hpp on the host: a stride of one in place of the kernel's LDS
+            TranscriptState st;
+            if (!trs[i]->impl->export_state(st)) return err(ZKT_ERR_INVALID_ARGUMENT, "a transcript that zkt_transcript_new did not make");
+            uint64_t words[VT_LANE_WORDS] = {0};
+            VtTr tr;
+            tr.s = VtSponge{words, words + VT_ST_WORDS, words + VT_ST_WORDS + VT_MSG_WORDS, 1};
+            vt_load_state(tr, &st);
+            std::vector<F> roots(ins[i].n_pi), vals(ins[i].n_pi), before(ins[i].n_pi);
+            if (ins[i].n_pi) {
+                memcpy((void*)roots.data(), ins[i].pi_roots, ins[i].n_pi * 32);
+                memcpy((void*)vals.data(), ins[i].pub_inputs, ins[i].n_pi * 32);
+            }
+            F dbg[8];
+            VtProof<C> p;
+            p.n = ins[i].n;
+            p.n_pi = ins[i].n_pi;
+            p.w = root_of_unity<R>(bp.log_n[i]);
+            p.rho[0] = bp.rho[2 * i];
+            p.rho[1] = bp.rho[2 * i + 1];
+            p.cm = &bp.cm[13 * i];
+            p.ev = &bp.ev[12 * i];
+            p.roots = roots.data();
+            p.vals = vals.data();
+            p.forced = forced ? forced + 7 * i : nullptr;
+            p.before = before.data();
+            p.acc = acc;
+            p.dbg = dbg;
+            out_status[i] = vt_terms<C>(tr, p);
+            vt_store_state(tr, &st);
+            if (!trs[i]->impl->import_state(st)) return err(ZKT_ERR_INVALID_ARGUMENT, "the transcript refused its state");
+            memcpy(out_ch + 28 * i, dbg, 7 * 32);
+            memcpy(out_r0 + 4 * i, dbg[7].v, 32);
+        }
+    }
+    return ZKT_OK;
+}
+
+extern "C" int zkt_debug_verify_terms(zkt_ctx* c, const zkt_verify_inputs* ins, zkt_transcript* const* transcripts, size_t count,
+                                      const uint64_t* rho_canonical4, const uint64_t* forced_mont, int route,
+                                      uint64_t* out_challenges, uint64_t* out_r0, uint64_t* out_acc, int* out_status) {
+    if (!c) return ZKT_ERR_INVALID_ARGUMENT;
+    if (!ins || !transcripts || count == 0 || count > ZKT_VERIFY_BATCH_DEV_MAX || !out_challenges || !out_r0 || !out_acc || !out_status)
+        return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "debug_verify_terms: null pointer or bad count");
+    if (route != 0 && route != 2) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "debug_verify_terms: route 0 (host) or 2 (kernel)");
+    (void)hipSetDevice(c->device);
+    if (c->curve == ZKT_CURVE_BN254)
+        return debug_terms_t<Bn254Curve>(c, ins, transcripts, count, rho_canonical4, forced_mont, route, out_challenges, out_r0,
+                                         out_acc, out_status);
+    return debug_terms_t<Bls381Curve>(c, ins, transcripts, count, rho_canonical4, forced_mont, route, out_challenges, out_r0, out_acc,
+                                      out_status);
+}
+
+extern "C" int zkt_debug_verify_terms_host(int curve_id, const zkt_verify_inputs* ins, zkt_transcript* const* transcripts,
+                                           size_t count, const uint64_t* rho_canonical4, const uint64_t* forced_mont, int route,
+                                           uint64_t* out_challenges, uint64_t* out_r0, uint64_t* out_acc, int* out_status) {
+    if (!ins || !transcripts || count == 0 || count > ZKT_VERIFY_BATCH_DEV_MAX || !out_challenges || !out_r0 || !out_acc ||
+        !out_status || (route != 0 && route != 1))
+        return ZKT_ERR_INVALID_ARGUMENT;
+    if (curve_id == ZKT_CURVE_BN254)
+        return debug_terms_t<Bn254Curve>(nullptr, ins, transcripts, count, rho_canonical4, forced_mont, route, out_challenges,
+                                         out_r0, out_acc, out_status);
+    if (curve_id == ZKT_CURVE_BLS12_381)
+        return debug_terms_t<Bls381Curve>(nullptr, ins, transcripts, count, rho_canonical4, forced_mont, route, out_challenges,
+                                          out_r0, out_acc, out_status);
+    return ZKT_ERR_INVALID_ARGUMENT;
+}
+
+// One transcript call through the code of verify_terms.hpp, on the host: the handle's state out, the call, the state in again
+extern "C" int zkt_debug_verify_terms_transcript(zkt_transcript* t, int op, const char* label, const uint8_t* data, size_t len,
+                                                 uint8_t out32[32]) {
+    if (!t || !label || op < 0 || op > 2) return ZKT_ERR_INVALID_ARGUMENT;
+    TranscriptState st;
+    if (!t->impl->export_state(st)) return ZKT_ERR_INVALID_ARGUMENT;
+    uint64_t words[VT_LANE_WORDS] = {0};
+    VtTr tr;
+    tr.s = VtSponge{words, words + VT_ST_WORDS, words + VT_ST_WORDS + VT_MSG_WORDS, 1};
+    vt_load_state(tr, &st);
+    if (op == 2) {
+        if (!out32 || len < 16 || len > 264) return ZKT_ERR_INVALID_ARGUMENT;
+        uint32_t w[8];
+        vt_tr_challenge(tr, label, (uint32_t)len, w);
+        memcpy(out32, w, 32);
+    } else {
+        if (!data || len > (op == 1 ? 96u : 8u * VT_MSG_WORDS) || (op == 1 && (len & 1))) return ZKT_ERR_INVALID_ARGUMENT;
+        if (tr.kind != 0 && len > 68) return ZKT_ERR_INVALID_ARGUMENT;   // one Keccak-256 block: 65 + len + padding <= 136
+        memcpy(words + VT_ST_WORDS, data, len);
+        if (op == 1) {
+            vt_tr_commit_msg(tr, label, (uint32_t)(len / 2));             // the infinity byte behind x || y stays zero
+        } else if (tr.kind == 0) {
+            vt_merlin_header(tr, label, (uint32_t)len);
+            vt_begin_op(tr, VT_FLAG_A);
+            vt_absorb_msg(tr, (uint32_t)len);
+        } else {
+            vt_eth_append(tr, 0, (uint32_t)len);
+        }
+    }
+    vt_store_state(tr, &st);
+    return t->impl->import_state(st) ? ZKT_OK : ZKT_ERR_INVALID_ARGUMENT;
+}
+
+extern "C" int zkt_ctx_set_verify_terms(zkt_ctx* c, int mode) {
+    if (!c) return ZKT_ERR_INVALID_ARGUMENT;
+    if (mode != 0 && mode != 1) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "mode: 0 on the host, 1 on the device");
+    c->verify_terms_mode = mode;
     return ZKT_OK;
 }
 
