@@ -579,6 +579,84 @@ typedef struct {
 } zkt_witness_report;
 int zkt_circuit_check_witness(zkt_ctx* ctx, const zkt_prove_inputs* in, int flags, zkt_witness_report* out);
 
+/* ---- Witness completion from the circuit's free variables: the solving half of the check above ----------------------
+ * The caller uploads the values of the free variables (for a circuit written against the reference's composer: exactly its
+ * direct assign_variable calls); the device fills in every variable that a gate defines and returns the public inputs the
+ * witness implies.  Nothing is assumed about the circuit beyond the rule below, which is part of this interface.
+ *
+ * THE RULE.  Row i asserts q_m a b + q_l a + q_r b + q_o c + q_c + PI_i = 0 (composer.rs:170-199), a, b, c the values of
+ * w_l[i], w_r[i], w_o[i].  The rows are walked in ascending order.  A variable is "unseen" at row i if it stands on no wire of
+ * a row before i.  ZKT_VARIABLE_ZERO and rows >= n_rows define nothing.
+ *  - A public-input row (i among pi_pos) defines nothing.  Its public input is an output:
+ *        PI_i = -(q_m a b + q_l a + q_r b + q_o c + q_c)                       (set_variable_public, mod.rs:216-240).
+ *  - Rule O.  Otherwise, if q_o[i] != 0 and v = w_o[i] is a real variable, unseen, and different from w_l[i] and w_r[i], the
+ *    row defines   v = -(q_m a b + q_l a + q_r b + q_c) / q_o.   This covers add, sub, mul, square and linear_transform
+ *    (arithmetic.rs:15-104, :138-200), the three rows of conditional_select (mod.rs:318-373), bits_le (mod.rs:175-213) and
+ *    the lookup copy (mod.rs:140-160).
+ *  - Rule R.  Otherwise, if v = w_r[i] is a real variable, unseen, and different from w_l[i] and w_o[i], and w_l[i] and
+ *    w_o[i] are each ZKT_VARIABLE_ZERO or already seen, the row defines   v = -(q_l a + q_o c + q_c) / (q_m a + q_r).
+ *    This is the div_gate (arithmetic.rs:104-130).  A zero denominator is a property of the witness, not an error of the
+ *    call: v is written as 0 and the row is reported (zkt_witness_complete_status).
+ *  - Everything else is free: every other variable first seen on some wire is the caller's to supply.  A boolean row
+ *    (x, x, x) (boolean.rs:26-34) defines nothing, by the "different from" clauses.  A variable on no wire is never touched.
+ *  - There is no left-wire rule: no gate of the reference needs one.
+ * The level of a defined variable is 1 + the largest level of the two other wires of its row; free variables and
+ * ZKT_VARIABLE_ZERO have level 0.  Lookup-table membership is not looked at (that is zkt_circuit_check_witness's job).
+ *
+ * Schedule and launches (csrc/witness_plan.hpp, csrc/witness_plan.hip): the defining rows sorted by level; a level with
+ * many rows is one launch with a thread per (witness, row), a run of narrower levels is one launch of one 256-thread
+ * workgroup per witness that walks the levels behind a workgroup barrier; more than 64 such launches fall back to a single
+ * narrow one.  Inside a launch a value written is read only by the workgroup that wrote it: no grid barrier, no flags, no
+ * atomics on values.  A closing launch computes the public inputs.  Measured on an MI355X (docs/EXPERIMENTS.md, "witness
+ * completion from the free variables"): the BN254 2^20 withdrawal (depth 33 853) in 78.9 ms at batch 1, 85.2 ms at batch 64;
+ * the time follows the depth (2.3 us a level), hardly the batch.  Scope "witness_complete" of zkt_profile_get.
+ * Everything in canonical Montgomery words, as the prover requires them. */
+#define ZKT_WITNESS_BATCH_MAX 256                  /* most witnesses one completion takes */
+typedef struct zkt_witness_plan zkt_witness_plan;
+typedef struct {
+    uint64_t n_free;                /* variables the caller supplies */
+    uint64_t n_out;                 /* defined by rule O */
+    uint64_t n_right;               /* defined by rule R */
+    uint64_t n_unused;              /* on no wire */
+    uint32_t depth;                 /* the largest level */
+    uint32_t max_level_rows;        /* rows of the widest level */
+    uint32_t launches;              /* launches that fill the map under the current split (the closing one not counted) */
+    uint32_t reserved;
+    uint64_t device_bytes;          /* 32 B a defined variable + 160 B a distinct coefficient tuple + 4 B a level + 192 B a
+                                     * public input + 16 B x ZKT_WITNESS_BATCH_MAX of status, each rounded up to 256 B */
+} zkt_witness_plan_report;
+typedef struct {
+    uint64_t n_unsolvable;          /* rule-R rows whose denominator was 0 */
+    uint64_t first_unsolvable;      /* the smallest such row, ZKT_CHECK_NONE when there is none */
+} zkt_witness_status;
+/* Plans the circuit loaded in `ctx` (its selectors: the evaluations are made from the key's coefficients as
+ * zkt_circuit_check_witness makes them) under the wiring w_l / w_r / w_o (n_rows indices each, host pointers, or device
+ * pointers with wiring_on_device != 0: what zkt_prove_inputs carries) and the ascending public-input positions pi_pos.
+ * The plan copies all it needs and owns its device memory: a later zkt_circuit_load does not affect it, and any context of
+ * the same curve and device may complete with it -- a fork, a context with a communicator (the call is local, no
+ * collective).  Synchronises.  ZKT_ERR_NOT_LOADED without a circuit; ZKT_ERR_INVALID_ARGUMENT for n_rows > n, an index that
+ * is neither < n_vars nor ZKT_VARIABLE_ZERO, a position >= n, unsorted or repeated positions, NULL wiring with n_rows > 0. */
+int zkt_witness_plan_create(zkt_ctx* ctx, const uint32_t* w_l, const uint32_t* w_r, const uint32_t* w_o, size_t n_rows,
+                            size_t n_vars, int wiring_on_device, const size_t* pi_pos, size_t n_pi, zkt_witness_plan** out);
+/* Waits for ctx's stream (NULL: no wait), then frees the plan and its device memory. */
+void zkt_witness_plan_free(zkt_ctx* ctx, zkt_witness_plan* plan);
+int zkt_witness_plan_info(const zkt_witness_plan* plan, zkt_witness_plan_report* info);
+/* Per variable: 0 on no wire, 1 free, 2 defined by rule O, 3 defined by rule R.  n_vars bytes. */
+int zkt_witness_plan_kinds(const zkt_witness_plan* plan, uint8_t* out_kind);
+/* Completes `batch` witnesses in DEVICE memory: witness w is d_variables + w * stride scalars, stride >= n_vars; only the
+ * defined variables are written, free ones, those on no wire and the padding up to stride stay as they are.  d_out_pi
+ * (optional, DEVICE): batch x n_pi scalars in position order.  1 <= batch <= ZKT_WITNESS_BATCH_MAX.  Enqueue only: no
+ * allocation, no synchronisation, on the context's stream, so zkt_prove with wires_on_device follows without a wait. */
+int zkt_witness_complete_enqueue(zkt_ctx* ctx, const zkt_witness_plan* plan, void* d_variables, size_t stride, size_t batch,
+                             void* d_out_pi);
+/* Synchronises and returns, per witness of the completions enqueued since the last such call, the rule-R rows with a zero
+ * denominator; clears the block.  Completions on several contexts share the plan's one block. */
+int zkt_witness_complete_status(zkt_ctx* ctx, const zkt_witness_plan* plan, size_t batch, zkt_witness_status* out);
+/* The host-pointer form: uploads batch x stride scalars, completes, downloads them (and out_pi, out_status when not NULL),
+ * synchronises. */
+int zkt_witness_complete(zkt_ctx* ctx, const zkt_witness_plan* plan, uint64_t* variables, size_t stride, size_t batch,
+                         uint64_t* out_pi, zkt_witness_status* out_status);
+
 /* ---- Witness synthesis for Poseidon-heavy circuits as batched field kernels ----------------------
  * (1) The permutation of plonk-hashing/src/hasher/poseidon/spec.rs (rounds :18-111, schedule :267-316, input layout
  * :239-265: state[0] = domain_tag, the inputs follow, output = state[1]) for `batch` independent hashes, one thread per
@@ -1186,6 +1264,18 @@ int zkt_debug_wire_elimination(int curve, const uint64_t* const* selectors, cons
                                size_t n_rows, size_t n_vars, const size_t* pi_pos, size_t n_pi, int K, uint8_t* out_kind,
                                uint32_t* out_free, size_t* out_n_free, uint32_t* out_term_v, uint32_t* out_term_f,
                                uint64_t* out_term_coef, size_t* out_n_terms, uint64_t* out_kappa);
+/* The host planner behind zkt_witness_plan_create, alone (csrc/witness_plan.hpp); needs no device and no context.
+ * selectors: q_m q_l q_r q_o q_c, n_rows x 4 Montgomery words each; wires: w_l w_r w_o, n_rows indices each (an index
+ * >= n_vars is read as ZKT_VARIABLE_ZERO); pi_pos ascending and distinct (positions >= n_rows are ignored).  Outputs,
+ * n_vars entries each: out_kind (0 on no wire, 1 free, 2 rule O, 3 rule R), out_def_row (the defining row, 0xFFFFFFFF when
+ * none), out_level. */
+int zkt_debug_witness_plan_host(int curve_id, const uint64_t* const* selectors, const uint32_t* const* wires, size_t n_rows,
+                                size_t n_vars, const size_t* pi_pos, size_t n_pi, uint8_t* out_kind, uint32_t* out_def_row,
+                                uint32_t* out_level);
+/* Overrides the threshold between the two completion kernels for this plan: a level with at least wide_min_rows rows is a
+ * launch of its own, the runs of narrower levels between such are one narrow launch each; a split of more than 64 launches
+ * is one narrow launch altogether.  0 restores the policy.  zkt_witness_plan_info's `launches` follows. */
+int zkt_debug_witness_plan_split(zkt_witness_plan* plan, uint32_t wide_min_rows);
 /* kzg10's witness polynomial alone (row a12): out[0 .. len - 1) = (p(X) - p(z)) / (X - z) for the len <= n + 8 coefficients
  * p, as the prover computes it (scaled suffix sums).  Host pointers, Montgomery words. */
 int zkt_debug_open_witness(zkt_ctx* ctx, const uint64_t* coeffs, size_t len, const uint64_t* z4, uint64_t* out);

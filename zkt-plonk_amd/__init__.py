@@ -11,6 +11,8 @@ Host-side mirror of the reference's two generic seams:
                          ``merkle_path`` ~ ``merkle_proof`` (plonk-hashing/src/merkle/binary.rs:8-30), a path per launch lane group
 * ``MerkleTree``       ~ ``MerkleTree<F, G, H, HEIGHT>`` (gadgets/src/merkle_tree.rs:39-111): the note tree kept and appended on the
                          device, its paths written straight into the variable map
+* ``WitnessPlan``      ~ the witness completed on the device from the circuit's free variables (the composer's direct
+                         ``assign_variable`` calls), with the public inputs it implies
 * ``parallel``         ~ one proof or many across the GPUs of a node (communicators, SRS slices)
 
 These are thin ctypes mirrors for the tests and ``bench.py``; the product is the C-ABI (include/zkt_plonk.h).
@@ -26,7 +28,8 @@ from .domain import GpuDomain  # noqa: F401
 from .prover import GpuProver, GpuKZG10, seed_transcript, PK_ORDER, NUM_BLINDERS  # noqa: F401
 from .poseidon import PoseidonGadget  # noqa: F401
 from .merkle import MerkleTree  # noqa: F401
+from .witness import WitnessPlan  # noqa: F401
 
-__all__ = ["Context", "ZktError", "Transcript", "GpuDomain", "GpuProver", "GpuKZG10", "PoseidonGadget", "MerkleTree", "seed_transcript", "PK_ORDER",
+__all__ = ["Context", "ZktError", "Transcript", "GpuDomain", "GpuProver", "GpuKZG10", "PoseidonGadget", "MerkleTree", "WitnessPlan", "seed_transcript", "PK_ORDER",
            "NUM_BLINDERS", "lib", "lib_path", "CURVE_BN254", "CURVE_BLS12_381", "curve_id", "declared_symbols",
            "WitnessCheck", "WitnessReport", "CHECK_WIRING", "CHECK_NONE", "SrsCheck", "SrsReport"]

@@ -109,6 +109,7 @@ def lib():
         L.zkt_debug_xyzz_op.argtypes = [vp, ctypes.c_int, u32p, ctypes.c_size_t, u32p]
         _bind_optional(L)
         _bind_prover(L)
+        _bind_witness(L)
         _lib = L
     return _lib
 
@@ -648,6 +649,62 @@ def _bind_prover(L):
     L.zkt_circuit_check_witness.argtypes = [vp, ctypes.POINTER(ProveInputs), ctypes.c_int, ctypes.POINTER(WitnessReport)]
 
 
+class WitnessPlanReport(ctypes.Structure):
+    """zkt_witness_plan_report"""
+    _fields_ = [("n_free", ctypes.c_uint64), ("n_out", ctypes.c_uint64), ("n_right", ctypes.c_uint64), ("n_unused", ctypes.c_uint64),
+                ("depth", ctypes.c_uint32), ("max_level_rows", ctypes.c_uint32), ("launches", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("device_bytes", ctypes.c_uint64)]
+
+
+class WitnessStatus(ctypes.Structure):
+    """zkt_witness_status"""
+    _fields_ = [("n_unsolvable", ctypes.c_uint64), ("first_unsolvable", ctypes.c_uint64)]
+
+
+WITNESS_BATCH_MAX = 256           # ZKT_WITNESS_BATCH_MAX
+
+
+def _bind_witness(L):
+    """zkt_witness_plan_* / zkt_witness_complete*: a missing symbol is an error here, not a fallback."""
+    vp, u64p_, u8p = ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint8)
+    u32p, szp, sz = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t
+    L.zkt_witness_plan_create.argtypes = [vp, vp, vp, vp, sz, sz, ctypes.c_int, szp, sz, ctypes.POINTER(vp)]
+    L.zkt_witness_plan_free.argtypes = [vp, vp]
+    L.zkt_witness_plan_free.restype = None
+    L.zkt_witness_plan_info.argtypes = [vp, ctypes.POINTER(WitnessPlanReport)]
+    L.zkt_witness_plan_kinds.argtypes = [vp, u8p]
+    L.zkt_witness_complete_enqueue.argtypes = [vp, vp, vp, sz, sz, vp]
+    L.zkt_witness_complete_status.argtypes = [vp, vp, sz, ctypes.POINTER(WitnessStatus)]
+    L.zkt_witness_complete.argtypes = [vp, vp, u64p_, sz, sz, u64p_, ctypes.POINTER(WitnessStatus)]
+    L.zkt_debug_witness_plan_split.argtypes = [vp, ctypes.c_uint32]
+    L.zkt_debug_witness_plan_host.argtypes = [ctypes.c_int, ctypes.POINTER(u64p_), ctypes.POINTER(u32p), sz, sz, szp, sz, u8p, u32p,
+                                              u32p]
+
+
+def debug_witness_plan_host(curve, selectors, w_l, w_r, w_o, n_vars: int, pi_pos=()):
+    """zkt_debug_witness_plan_host: the host planner of the witness completion alone (no device).  selectors: q_m q_l q_r q_o
+    q_c as (n_rows, 4) Montgomery words; w_*: n_rows uint32 indices (0xFFFFFFFF = Variable::Zero); pi_pos ascending.
+    -> (kind (n_vars,) uint8: 0 on no wire, 1 free, 2 rule O, 3 rule R; def_row (n_vars,) uint32, 0xFFFFFFFF when none;
+    level (n_vars,) uint32)."""
+    L = lib()
+    sel = [np.ascontiguousarray(q, dtype=np.uint64).reshape(-1, 4) for q in selectors]
+    w = [np.ascontiguousarray(x, dtype=np.uint32).reshape(-1) for x in (w_l, w_r, w_o)]
+    n_rows = len(w[0])
+    assert len(sel) == 5 and all(q.shape[0] == n_rows for q in sel) and all(len(x) == n_rows for x in w)
+    pi = (ctypes.c_size_t * max(len(pi_pos), 1))(*[int(x) for x in pi_pos])
+    P64, P32 = ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)
+    sp = (P64 * 5)(*[q.ctypes.data_as(P64) for q in sel])
+    wp = (P32 * 3)(*[x.ctypes.data_as(P32) for x in w])
+    kind = np.zeros(max(n_vars, 1), dtype=np.uint8)
+    def_row, level = np.zeros(max(n_vars, 1), dtype=np.uint32), np.zeros(max(n_vars, 1), dtype=np.uint32)
+    rc = L.zkt_debug_witness_plan_host(curve_id(curve), sp, wp, n_rows, n_vars, pi, len(pi_pos),
+                                       kind.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), def_row.ctypes.data_as(P32),
+                                       level.ctypes.data_as(P32))
+    if rc:
+        raise ZktError(rc, "zkt_debug_witness_plan_host")
+    return kind[:n_vars], def_row[:n_vars], level[:n_vars]
+
+
 def g1_sum_host(curve, points) -> tuple:
     """Host sum of affine G1 points ((count, 2*fq_limbs) Montgomery limbs, (0,0) = identity) -> (xy limbs, is_infinity).
     The combine step of an index-range-sharded MSM; needs no GPU context."""
@@ -1170,6 +1227,72 @@ class Context:
         rc = L.zkt_debug_merkle_tree_split(ctypes.c_void_p(tree), wide_min_parents)
         if rc:
             raise ZktError(rc, "zkt_debug_merkle_tree_split: null tree or negative threshold")
+
+    # -- witness completion from the free variables (csrc/witness_plan.hip) ---------------------------------
+    def witness_plan_create(self, w_l, w_r, w_o, n_vars: int, pi_pos=(), n_rows: int = None) -> int:
+        """zkt_witness_plan_create over the loaded circuit: w_* are uint32 arrays (host) or device pointers (ints, with
+        n_rows given); pi_pos ascending -> opaque plan handle."""
+        vp = ctypes.c_void_p
+        on_device = isinstance(w_l, int)
+        if on_device:
+            ptrs, keep = [vp(x) if x else None for x in (w_l, w_r, w_o)], ()
+            assert n_rows is not None
+        else:
+            keep = [np.ascontiguousarray(x, dtype=np.uint32).reshape(-1) for x in (w_l, w_r, w_o)]
+            n_rows = len(keep[0]) if n_rows is None else n_rows
+            ptrs = [vp(x.ctypes.data) if x.size else None for x in keep]
+        pos = (ctypes.c_size_t * max(1, len(pi_pos)))(*[int(x) for x in pi_pos])
+        plan = vp()
+        self.check(self._L.zkt_witness_plan_create(self._h, ptrs[0], ptrs[1], ptrs[2], n_rows, n_vars, int(on_device), pos,
+                                                   len(pi_pos), ctypes.byref(plan)))
+        return plan.value
+
+    def witness_plan_free(self, plan: int):
+        self._L.zkt_witness_plan_free(self._h, ctypes.c_void_p(plan))
+
+    def witness_plan_info(self, plan: int) -> dict:
+        """zkt_witness_plan_info -> {n_free, n_out, n_right, n_unused, depth, max_level_rows, launches, device_bytes}"""
+        r = WitnessPlanReport()
+        rc = self._L.zkt_witness_plan_info(ctypes.c_void_p(plan), ctypes.byref(r))
+        if rc:
+            raise ZktError(rc, "zkt_witness_plan_info: null plan")
+        return {k: int(getattr(r, k)) for k, _ in WitnessPlanReport._fields_ if k != "reserved"}
+
+    def witness_plan_kinds(self, plan: int, n_vars: int) -> np.ndarray:
+        out = np.zeros(max(n_vars, 1), dtype=np.uint8)
+        rc = self._L.zkt_witness_plan_kinds(ctypes.c_void_p(plan), out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)))
+        if rc:
+            raise ZktError(rc, "zkt_witness_plan_kinds: null plan")
+        return out[:n_vars]
+
+    def debug_witness_plan_split(self, plan: int, wide_min_rows: int):
+        """zkt_debug_witness_plan_split: 0 = the policy."""
+        rc = self._L.zkt_debug_witness_plan_split(ctypes.c_void_p(plan), wide_min_rows)
+        if rc:
+            raise ZktError(rc, "zkt_debug_witness_plan_split: null plan")
+
+    def witness_complete_enqueue(self, plan: int, d_variables: int, stride: int, batch: int = 1, d_out_pi: int = 0):
+        """zkt_witness_complete_enqueue: enqueue only."""
+        vp = ctypes.c_void_p
+        self.check(self._L.zkt_witness_complete_enqueue(self._h, vp(plan), vp(d_variables) if d_variables else None, stride, batch,
+                                                    vp(d_out_pi) if d_out_pi else None))
+
+    def witness_complete_status(self, plan: int, batch: int = 1):
+        """zkt_witness_complete_status -> [(unsolvable rows, the smallest such row or None)] per witness; synchronises, clears."""
+        out = (WitnessStatus * max(batch, 1))()
+        self.check(self._L.zkt_witness_complete_status(self._h, ctypes.c_void_p(plan), batch, out))
+        return [(int(s.n_unsolvable), None if s.first_unsolvable == CHECK_NONE else int(s.first_unsolvable)) for s in out[:batch]]
+
+    def witness_complete(self, plan: int, variables, n_pi: int, stride: int = None):
+        """zkt_witness_complete on a host map of (batch, stride, 4) or (stride, 4) Montgomery words -> (the completed maps
+        (batch, stride, 4), public inputs (batch, n_pi, 4), status as witness_complete_status gives it)."""
+        v = np.array(variables, dtype=np.uint64, order="C")
+        v = v.reshape((1,) + v.shape) if v.ndim == 2 else v
+        batch, stride = v.shape[0], (v.shape[1] if stride is None else stride)
+        pi = np.zeros((batch, max(n_pi, 1), 4), dtype=np.uint64)
+        st = (WitnessStatus * batch)()
+        self.check(self._L.zkt_witness_complete(self._h, ctypes.c_void_p(plan), u64p(v) if v.size else None, stride, batch, u64p(pi), st))
+        return v, pi[:, :n_pi], [(int(s.n_unsolvable), None if s.first_unsolvable == CHECK_NONE else int(s.first_unsolvable)) for s in st]
 
     # -- device memory ------------------------------------------------------------------------
     def alloc(self, nbytes: int) -> int:

@@ -2152,6 +2152,20 @@ int zkt_circuit_check_witness(zkt_ctx* c, const zkt_prove_inputs* in, int flags,
     return witness_check(c, keys, *in, flags, out);
 }
 
+// The plan of a witness completion over the loaded circuit's selectors (witness_plan.hip).  Reads the loaded keys, writes
+// nothing of the circuit state; the plan keeps no pointer into it.
+int zkt_witness_plan_create(zkt_ctx* c, const uint32_t* w_l, const uint32_t* w_r, const uint32_t* w_o, size_t n_rows, size_t n_vars,
+                            int wiring_on_device, const size_t* pi_pos, size_t n_pi, zkt_witness_plan** out) {
+    if (!c) return ZKT_ERR_INVALID_ARGUMENT;
+    if (!out) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
+    if (!c->circuit) return set_err(c, ZKT_ERR_NOT_LOADED, "no circuit loaded (zkt_circuit_load)");
+    const CircuitState& S = *c->circuit;
+    WitnessPlanKeys keys{};
+    keys.log_n = S.log_n;
+    for (int k = 0; k < 5; ++k) keys.pk[k] = S.pk[PK_QM + k];   // PK_QM .. PK_QC
+    return witness_plan_create(c, keys, w_l, w_r, w_o, n_rows, n_vars, wiring_on_device, pi_pos, n_pi, out);
+}
+
 // Test hook: the fused quotient pass on its own (quotient_poly.rs:98-224) over the loaded circuit's key cosets and
 // caller-supplied witness cosets, so that the kernel is compared point by point on inputs that satisfy nothing.
 int zkt_debug_quotient(zkt_ctx* c, const uint64_t* challenges, const uint64_t* const* wit, const uint64_t* pi_pos,
