@@ -1046,12 +1046,12 @@ int zkt_verify_batch_dev(zkt_ctx* ctx, const zkt_verify_inputs* ins, zkt_transcr
  * as far as they were drawn, the rest zero), out_r0 and out_acc (24 sums by source; zero for a refused proof), 4
  * Montgomery words each, and leave every handle where the route left it, a refused proof's included.  They return ZKT_OK
  * when they ran: a per-proof refusal is a result.  Malformed bytes or a refused commitment -> the error of the real call.
- * zkt_debug_verify_terms: on a context, the commitments through the device's decompression; route 0 = the host code
- * (Verifier::terms and the sums of the batch verifier), route 2 = the kernel.  Synchronises the stream.
+ * zkt_debug_verify_terms: on a context, the commitments through the device's decompression; route 0 = the host route
+ * (the replay through the handle's own calls, as mode 0 runs it), route 2 = the kernel.  Synchronises the stream.
  * zkt_debug_verify_terms_host: no context and no device, the host verifier's own decompression; route 0 as above,
- * route 1 = the code of csrc/verify_terms.hpp run on the host.
- * zkt_debug_verify_terms_transcript: ONE transcript call through that code, on the host, on a handle of
- * zkt_transcript_new (state out, the call, state in), so that its STROBE-128 and Keccak-256 can be held to known answers
+ * route 1 = the replay on the transcript's exported state directly, as the kernel runs it, on the host.
+ * zkt_debug_verify_terms_transcript: ONE transcript call on the exported state directly, on the host, on a handle of
+ * zkt_transcript_new (state out, the call, state in), so that STROBE-128 and Keccak-256 can be held to known answers
  * and to the handle's own calls.  op 0: a message -- Merlin append_message(label, data[0 .. len)), len <= 104; Ethereum one
  * item, data little-endian, hashed big-endian, len <= 68.  op 1: a commitment that is not the identity, data = x || y
  * little-endian, len = both.  op 2: a challenge of len = fr_bits bits (Merlin: (len + 7) / 8 - 1 bytes) -> out32,

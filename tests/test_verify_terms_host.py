@@ -1,6 +1,6 @@
-"""CPU: the batch verifier's term stage as the kernel computes it (csrc/verify_terms.hpp run on the host,
-zkt_debug_verify_terms_host route 1) against the existing host code (route 0: Verifier::terms and the sums of the batch
-verifier, which the verifier tests hold to the oracle): statuses, the seven challenges, r0 and the 24 sums, integer for
+"""CPU: the batch verifier's term stage as the kernel computes it (csrc/verify_terms.hpp on the core's transcript state,
+zkt_debug_verify_terms_host route 1) against the host route (route 0: the same replay through the handle's own calls, which
+the verifier tests hold to the oracle and tests/test_verify_terms_pinned.py to what it returned before the two shared code): statuses, the seven challenges, r0 and the 24 sums, integer for
 integer, over the table of tests/verify_terms_cases.py on both curves, and where every transcript handle is left.  The
 STROBE-128 and Keccak-256 of the shared file against the known answers of tests/test_transcript_host.py and against the
 handles' own calls on random traffic."""

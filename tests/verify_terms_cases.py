@@ -8,6 +8,9 @@ evaluations, random public inputs and roots, ten small multiples of g as the ver
 with forced = None or the seven integers (beta, gamma, delta, epsilon, alpha, xi, eta) that replace the transcript's
 answers.  ROWS(cv) are the unforced rows, FORCED(cv) the forced ones, two_refusals(cv) the batch with two refused proofs."""
 import functools
+import hashlib
+import json
+import os
 import random
 from collections import namedtuple
 
@@ -207,3 +210,27 @@ def probes(its):
 def same(a, b):
     """two results of debug_verify_terms* are equal, integer for integer"""
     return all(np.array_equal(x, y) for x, y in zip(a, b))
+
+
+# ---- the results pinned in tests/golden/verify_terms_pinned.json (tests/golden/make_golden_verify_terms.py) ----------
+PINNED = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "verify_terms_pinned.json")
+
+
+def pinned_batches(cv):
+    """(name, rows, rho) of every pinned batch, with the coefficients the other tests give it"""
+    rows, forced = list(ROWS(cv)), list(FORCED(cv)[0])
+    return (("rows", rows, rho_array(cv, len(rows))), ("forced", forced, rho_array(cv, len(forced), seed=6)),
+            ("two_refusals", list(two_refusals(cv)[0]), None), ("two_natural_refusals", list(two_natural_refusals(cv)), None))
+
+
+def digests(result, left):
+    """per proof the SHA-256 over its status, seven challenges, r0, 24 sums and the handle's probe after the call"""
+    ch, r0, acc, status = result
+    words = lambda a: np.ascontiguousarray(a, dtype="<u8").tobytes()  # noqa: E731
+    return [hashlib.sha256(int(status[i]).to_bytes(4, "little", signed=True) + words(ch[i]) + words(r0[i]) + words(acc[i]) +
+                           left[i].to_bytes(32, "little")).hexdigest() for i in range(len(left))]
+
+
+@functools.lru_cache(maxsize=None)
+def pinned():
+    return json.load(open(PINNED))

@@ -19,7 +19,7 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=" + ARCH, "-Wall", "-Wno-
 
 
 def _sources():
-    return sorted(f for f in os.listdir(CSRC) if f.endswith(".hip") or f.endswith(".cpp"))
+    return sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
 
 
 def _headers_mtime():
@@ -37,8 +37,6 @@ def _compile(src, hdr_m, force, extra, obj_dir=None):
     if not force and os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(sp), hdr_m):
         return obj, False
     cmd = ["hipcc"] + FLAGS + extra + ["-c", sp, "-o", obj]
-    if src.endswith(".cpp"):
-        cmd = ["hipcc", "-O3", "-std=c++17", "-fPIC", "-Wall", "-x", "c++", "-c", sp, "-o", obj]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError("hipcc failed for %s:\n%s\n%s" % (src, r.stdout, r.stderr))
@@ -95,7 +93,7 @@ def build_experiments(force: bool = False, extra_flags=None) -> str:
 # ---- host-side sanitizer build ------------------------------------------------------------------------------------
 # Every source compiled for the HOST only (--cuda-host-only: kernels become stubs that cannot launch) with
 # AddressSanitizer + UndefinedBehaviorSanitizer.  The entry points that never touch a device -- transcripts
-# (transcript.cpp), host inversion and field / curve arithmetic (hostinv.hpp, fp.hpp, fx.hpp, ec.hpp through
+# (transcript.hip, transcript_core.hpp), host inversion and field / curve arithmetic (hostinv.hpp, fp.hpp, fx.hpp, ec.hpp through
 # zkt_host_field_op / zkt_g1_sum_host), the communicator plumbing -- then run under the CPU tests
 # (tests/test_host_sanitize.py).  GPU-side sanitizers are not available on this pool.
 ASAN_OBJ = os.path.join(HERE, "_obj_asan")
@@ -115,8 +113,7 @@ def _compile_asan(src, hdr_m, force):
     sp = os.path.join(CSRC, src)
     if not force and os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(sp), hdr_m):
         return obj, False
-    lang = ["-x", "hip", "--cuda-host-only", "-I/opt/rocm/include"] if src.endswith(".hip") else ["-x", "c++"]
-    r = subprocess.run([CLANG] + lang + ASAN_FLAGS + ["-c", sp, "-o", obj], capture_output=True, text=True)
+    r = subprocess.run([CLANG, "-x", "hip", "--cuda-host-only", "-I/opt/rocm/include"] + ASAN_FLAGS + ["-c", sp, "-o", obj], capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError("sanitizer build failed for %s:\n%s\n%s" % (src, r.stdout, r.stderr))
     return obj, True

@@ -112,7 +112,7 @@ inline Fe<P> fe_inv_host(const Fe<P>& a) {
 
 // a domain size (or any 64-bit count) as a field element
 template <class P>
-inline Fe<P> fe_from_u64(uint64_t x) {
+ZKT_HD Fe<P> fe_from_u64(uint64_t x) {
     Fe<P> a = fe_zero<P>();
     a.v[0] = (uint32_t)x;
     a.v[1] = (uint32_t)(x >> 32);

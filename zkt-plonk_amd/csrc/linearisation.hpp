@@ -1,20 +1,33 @@
-// Host arithmetic of the verifier's identity at xi (proof.rs:163-282, linearization_poly.rs:19-121, util.rs:185-195):
+// Arithmetic of the verifier's identity at xi (proof.rs:163-282, linearization_poly.rs:19-121, util.rs:185-195):
 // zh(xi), L_1(xi), the thirteen scalars of the linearisation and compute_r0.  The prover puts the scalars against its
-// polynomials (round 5) and, on the quotient's classes route, checks r(xi) against r0; the verifier puts them against
-// its commitments and folds r0 into the first opening.  One implementation, so the two cannot drift apart.
+// polynomials (round 5) and, on the quotient's classes route, checks r(xi) against r0; the verifier -- on the host and in
+// the kernel of verify_terms.hip -- puts them against its commitments and folds r0 into the first opening.  One
+// implementation, so they cannot drift apart; what differs is the inversion, which the caller names: the host's
+// fe_inv_host, the kernels' fe_inv_call (an inverse is one value, whoever computes it).
 #pragma once
 #include "ctx.hpp"
 #include "hostinv.hpp"
-#include <cstring>
-#include <vector>
 
 namespace zkt {
 
-// the twelve evaluations, in ProofEvaluations order (the proof's wire order)
+// the twelve evaluations, in ProofEvaluations order (the proof's wire order), and their transcript labels
 enum { EV_A = 0, EV_B, EV_C, EV_S1, EV_S2, EV_Z1N, EV_QL, EV_T, EV_TN, EV_Z2N, EV_H1N, EV_H2, EV_COUNT };
-static const char* const EV_LABEL[EV_COUNT] = {"a_eval", "b_eval", "c_eval", "sigma1_eval", "sigma2_eval", "z1_next_eval",
-                                               "q_lookup_eval", "t_eval", "t_next_eval", "z2_next_eval", "h1_next_eval", "h2_eval"};
-// (the device replay of the verifier keeps the same labels in the same order: verify_terms.hpp vt_ev_label)
+ZKT_HD const char* ev_label(int k) {
+    switch (k) {
+        case EV_A: return "a_eval";
+        case EV_B: return "b_eval";
+        case EV_C: return "c_eval";
+        case EV_S1: return "sigma1_eval";
+        case EV_S2: return "sigma2_eval";
+        case EV_Z1N: return "z1_next_eval";
+        case EV_QL: return "q_lookup_eval";
+        case EV_T: return "t_eval";
+        case EV_TN: return "t_next_eval";
+        case EV_Z2N: return "z2_next_eval";
+        case EV_H1N: return "h1_next_eval";
+        default: return "h2_eval";
+    }
+}
 // the thirteen terms of the linearisation, in the order of commitment.rs:32-45
 enum { LIN_QM = 0, LIN_QL, LIN_QR, LIN_QO, LIN_QC, LIN_Z1, LIN_S3, LIN_Z2, LIN_H1, LIN_QTABLE, LIN_QLO, LIN_QMID, LIN_QHI, LIN_COUNT };
 
@@ -24,8 +37,13 @@ template <class R> struct XiPoint {
     Fe<R> a2, a3, a4, a5, eopd;   // powers of alpha, epsilon (1 + delta)
 };
 
+// fe_inv (fp.hpp) as one function that device code calls, not a copy at every use
+template <class R>
+__host__ __device__ __attribute__((noinline)) Fe<R> fe_inv_call(const Fe<R>& a) { return fe_inv<R>(a); }
+
 // false: n (xi - 1) = 0, L_1(xi) has no denominator and is left alone (the other members are set)
-template <class R> static bool xi_point(const Challenges<R>& ch, uint64_t n, XiPoint<R>& at) {
+template <class R, Fe<R> (*INV)(const Fe<R>&)>
+ZKT_HD bool xi_point(const Challenges<R>& ch, uint64_t n, XiPoint<R>& at) {
     const Fe<R> one = fe_one<R>();
     at.zh = fe_sub<R>(fe_pow_u64<R>(ch.xi, n), one);
     at.nn = fe_from_u64<R>(n);
@@ -34,7 +52,7 @@ template <class R> static bool xi_point(const Challenges<R>& ch, uint64_t n, XiP
     at.eopd = fe_mul<R>(ch.epsilon, fe_add<R>(ch.delta, one));
     const Fe<R> l1den = fe_mul<R>(at.nn, fe_sub<R>(ch.xi, one));
     if (fe_is_zero<R>(l1den)) return false;
-    at.l1 = fe_mul<R>(at.zh, fe_inv_host<R>(l1den));
+    at.l1 = fe_mul<R>(at.zh, INV(l1den));
     return true;
 }
 
@@ -67,32 +85,37 @@ template <class R> ZKT_HD void linearisation_scalars(const Challenges<R>& ch, co
     sc[LIN_QHI] = fe_mul<R>(nzh, fe_sqr<R>(xn2));
 }
 
-// compute_r0 (proof.rs:163-217) over k public inputs `vals` at the domain points `roots` (Montgomery form, sizeof(Fe<R>) bytes each):
+// compute_r0 (proof.rs:163-217) over k public inputs `vals` at the domain points `roots` (Montgomery form):
 // L_j(xi) = zh root_j / (n (xi - root_j)), all denominators inverted at once; a root equal to xi has L_j = 1 (and zh = 0
-// silences the others).  Returns whether any denominator was zero: the verifier refuses such a proof, the prover goes on.
-template <class R> static bool compute_r0(const Challenges<R>& ch, const XiPoint<R>& at, const Fe<R>* ev, const void* roots, const void* vals,
-                       size_t k, Fe<R>* out) {
+// silences the others).  No allocation: before[] (k elements, the caller's) keeps the running products of the non-zero
+// denominators, and a denominator is formed again on the way back.  Returns whether any denominator was zero: the
+// verifier refuses such a proof, the prover goes on.
+template <class R, Fe<R> (*INV)(const Fe<R>&)>
+ZKT_HD bool compute_r0(const Challenges<R>& ch, const XiPoint<R>& at, const Fe<R>* ev, const Fe<R>* roots, const Fe<R>* vals,
+                       uint64_t k, Fe<R>* before, Fe<R>* out) {
     typedef Fe<R> F;
     F r0 = fe_zero<R>();
     bool zero_den = false;
-    auto load = [](const void* p, size_t i) { F v; memcpy(v.v, (const char*)p + sizeof(F) * i, sizeof(F)); return v; };
-    std::vector<F> den(k), before(k);   // before[i]: product of the non-zero den[j], j < i
     F run_prod = fe_one<R>();
-    for (size_t i = 0; i < k; ++i) {
-        den[i] = fe_mul<R>(at.nn, fe_sub<R>(ch.xi, load(roots, i)));
+#pragma nounroll
+    for (uint64_t i = 0; i < k; ++i) {
+        const F den = fe_mul<R>(at.nn, fe_sub<R>(ch.xi, roots[i]));
         before[i] = run_prod;
-        if (!fe_is_zero<R>(den[i])) run_prod = fe_mul<R>(run_prod, den[i]);
+        if (!fe_is_zero<R>(den)) run_prod = fe_mul<R>(run_prod, den);
     }
-    F inv_all = k ? fe_inv_host<R>(run_prod) : run_prod;
-    for (size_t i = k; i-- > 0;) {
-        if (fe_is_zero<R>(den[i])) {
+    F inv_all = k ? INV(run_prod) : run_prod;
+#pragma nounroll
+    for (uint64_t i = k; i-- > 0;) {
+        const F root = roots[i], val = vals[i];
+        const F den = fe_mul<R>(at.nn, fe_sub<R>(ch.xi, root));
+        if (fe_is_zero<R>(den)) {
             zero_den = true;
-            r0 = fe_sub<R>(r0, load(vals, i));
+            r0 = fe_sub<R>(r0, val);
             continue;
         }
         const F di = fe_mul<R>(inv_all, before[i]);
-        inv_all = fe_mul<R>(inv_all, den[i]);
-        r0 = fe_sub<R>(r0, fe_mul<R>(fe_mul<R>(fe_mul<R>(at.zh, load(roots, i)), di), load(vals, i)));
+        inv_all = fe_mul<R>(inv_all, den);
+        r0 = fe_sub<R>(r0, fe_mul<R>(fe_mul<R>(fe_mul<R>(at.zh, root), di), val));
     }
     const F &beta = ch.beta, &gamma = ch.gamma, &delta = ch.delta;
     F p2 = fe_mul<R>(ch.alpha, ev[EV_Z1N]);

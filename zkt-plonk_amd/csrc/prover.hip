@@ -1290,10 +1290,11 @@ struct Prover {
     // Classes route, check side: r(xi) against compute_r0 (proof.rs:163-217) made from the prover's own values.  A public
     // input's root equal to xi has L_j = 1 there and the proof goes on.
     int check_identity(const zkt_prove_inputs& in) {
-        std::vector<F> root(in.n_pi);
+        std::vector<F> root(in.n_pi), vals(in.n_pi), before(in.n_pi);
         for (size_t i = 0; i < in.n_pi; ++i) root[i] = fe_pow_u64<R>(w, (uint64_t)in.pi_pos[i]);
+        if (in.n_pi) memcpy((void*)vals.data(), in.pi_vals, in.n_pi * sizeof(F));
         F r0;
-        (void)compute_r0<R>(ch, at, ev, root.data(), in.pi_vals, in.n_pi, &r0);
+        (void)compute_r0<R, fe_inv_host<R>>(ch, at, ev, root.data(), vals.data(), in.n_pi, before.data(), &r0);
         ZKT_HIP(c, hipEventSynchronize(S.ev_win));
         F r_xi = ((const F*)S.pinned)[16];
         if (fused5) {   // the first opening's combination at xi, less eta^k times a b c sigma1 sigma2 q_lookup t h2 at xi
@@ -1374,8 +1375,8 @@ struct Prover {
         prof_round.emplace(c, "round5");
         if ((rc = evaluations())) return rc;
         // zh(xi) = xi^n - 1 ; L_1(xi) = zh * 1 / (n * (xi - 1))   (util.rs:185-195)
-        if (!xi_point<R>(ch, (uint64_t)S.n, at)) return set_err(c, ZKT_ERR_ZERO_DENOMINATOR, "xi = 1");
-        for (int k = 0; k < EV_COUNT; ++k) tr_scalar(EV_LABEL[k], ev[k]);
+        if (!xi_point<R, fe_inv_host<R>>(ch, (uint64_t)S.n, at)) return set_err(c, ZKT_ERR_ZERO_DENOMINATOR, "xi = 1");
+        for (int k = 0; k < EV_COUNT; ++k) tr_scalar(ev_label(k), ev[k]);
         ch.eta = tr_challenge("eta");
         if ((rc = openings())) return rc;
         wait_end();
@@ -1688,7 +1689,7 @@ static int debug_grand_products_t(zkt_ctx* c, const uint64_t* ch, const uint64_t
     const size_t n = S.n;
     void* dst[7] = {S.ev[0], S.ev[1], S.ev[2], S.ev[4], S.ev[3], S.ev[5], S.ev[6]};   // a b c f t h1 h2
     for (int k = 0; k < 7; ++k) ZKT_HIP(c, hipMemcpyAsync(dst[k], v[k], n * 32, hipMemcpyHostToDevice, c->stream));
-    MerlinHostTranscript tr("zkt_debug_grand_products");   // no challenge is drawn: they are the caller's
+    BuiltinTranscript tr(0, "zkt_debug_grand_products");   // no challenge is drawn: they are the caller's
     Prover<C> p(c, S, tr);
     p.ch.beta = H::from_words(ch); p.ch.gamma = H::from_words(ch + 4); p.ch.delta = H::from_words(ch + 8);
     p.ch.epsilon = H::from_words(ch + 12);
@@ -1708,7 +1709,7 @@ static int debug_combine_split_t(zkt_ctx* c, const uint64_t* table, size_t table
                                  uint64_t* h1_out, uint64_t* h2_out) {
     CircuitState& S = *c->circuit;
     const size_t n = S.n;
-    MerlinHostTranscript tr("zkt_debug_combine_split");   // combine_split draws no challenge
+    BuiltinTranscript tr(0, "zkt_debug_combine_split");   // combine_split draws no challenge
     Prover<C> p(c, S, tr);
     ZKT_HIP(c, hipMemsetAsync(S.status, 0, 4, c->stream));
     ZKT_HIP(c, hipMemcpyAsync(S.ev[4], f, n * 32, hipMemcpyHostToDevice, c->stream));
@@ -1822,17 +1823,11 @@ static int circuit_check_epk_t(zkt_ctx* c, const char* path, int* vec_out, size_
 extern "C" {
 
 zkt_transcript* zkt_transcript_new(int kind, const char* label) {
+    if (kind != ZKT_TRANSCRIPT_MERLIN && kind != ZKT_TRANSCRIPT_ETHEREUM) return nullptr;
     zkt_transcript* t = new zkt_transcript();
-    if (kind == ZKT_TRANSCRIPT_MERLIN) {
-        auto* m = new MerlinHostTranscript(label ? label : "");
-        t->merlin = &m->t;
-        t->impl.reset(m);
-    } else if (kind == ZKT_TRANSCRIPT_ETHEREUM) {
-        t->impl.reset(new EthereumHostTranscript());
-    } else {
-        delete t;
-        return nullptr;
-    }
+    auto* b = new BuiltinTranscript(kind == ZKT_TRANSCRIPT_MERLIN ? 0 : 1, label ? label : "");
+    t->impl.reset(b);
+    if (kind == ZKT_TRANSCRIPT_MERLIN) t->merlin = b;
     return t;
 }
 void zkt_transcript_free(zkt_transcript* t) { delete t; }
@@ -1858,14 +1853,10 @@ void zkt_transcript_challenge_scalar(zkt_transcript* t, const char* label, int f
     t->impl->challenge_scalar(label, (size_t)fr_bits, out_le32);
 }
 int zkt_transcript_challenge_bytes(zkt_transcript* t, const char* label, uint8_t* out, size_t len) {
-    if (!t->merlin) return ZKT_ERR_INVALID_ARGUMENT;
-    t->merlin->challenge_bytes(label, out, len);
-    return ZKT_OK;
+    return t->merlin && t->merlin->challenge_bytes(label, out, len) ? ZKT_OK : ZKT_ERR_INVALID_ARGUMENT;
 }
 int zkt_transcript_append_message(zkt_transcript* t, const char* label, const uint8_t* msg, size_t len) {
-    if (!t->merlin) return ZKT_ERR_INVALID_ARGUMENT;
-    t->merlin->append_message(label, msg, len);
-    return ZKT_OK;
+    return t->merlin && t->merlin->append_message(label, msg, len) ? ZKT_OK : ZKT_ERR_INVALID_ARGUMENT;
 }
 
 int zkt_circuit_load(zkt_ctx* c, int log_n, const uint64_t* const* pk_polys, const size_t* pk_lens) {
@@ -2316,7 +2307,7 @@ extern "C++" template <class C>
 static int debug_commit_wires_t(zkt_ctx* c, const zkt_prove_inputs& in, int route, uint64_t* out_xy, int* out_inf, int* out_route) {
     using Q = typename C::Fq;
     CircuitState& S = *c->circuit;
-    MerlinHostTranscript tr("zkt_debug_commit_wires_dev");
+    BuiltinTranscript tr(0, "zkt_debug_commit_wires_dev");
     Prover<C> p(c, S, tr);
     S.wire_dense_only = route == 0;
     S.wire_elim_force = route == 2 ? 1 : 0;

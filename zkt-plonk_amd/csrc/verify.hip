@@ -229,6 +229,86 @@ static hostec::HX<typename C::Fq> msm_wnaf(const hostec::HX<typename C::Fq>* pts
     return acc;
 }
 
+// the ten verifier-key points and g of one proof: sources SRC_VK .. SRC_G
+template <class C>
+static void verifier_key_points(const zkt_verify_inputs& in, Affine<typename C::Fq>* out11) {
+    using Q = typename C::Fq;
+    const size_t nb = Q::N * 4;
+    const int L64 = Q::N / 2;
+    for (int k = 0; k < 10; ++k) {
+        if (in.vk_is_infinity && in.vk_is_infinity[k]) {
+            out11[k].x = fe_zero<Q>();
+            out11[k].y = fe_zero<Q>();
+        } else {
+            memcpy(out11[k].x.v, in.vk_commitments + (size_t)k * 2 * L64, nb);
+            memcpy(out11[k].y.v, in.vk_commitments + (size_t)k * 2 * L64 + L64, nb);
+        }
+    }
+    memcpy(out11[10].x.v, in.g, nb);
+    memcpy(out11[10].y.v, in.g + L64, nb);
+}
+
+// verifier_replay's transcript over a HostTranscript: a built-in one through its virtual calls, or a caller's callbacks
+template <class C>
+struct VtHostTr {
+    using R = typename C::Fr;
+    using Q = typename C::Fq;
+    HostTranscript& tr;
+    void scalars(const char* label, const Fe<R>* mont, uint64_t count, bool single) {
+        std::vector<uint8_t> b(count * 32);
+        for (uint64_t i = 0; i < count; ++i) {
+            const Fe<R> c = fe_from_mont<R>(mont[i]);
+            memcpy(b.data() + 32 * i, c.v, 32);
+        }
+        tr.append_scalars(label, b.data(), count, 32, single);
+    }
+    void commit(const char* label, const Affine<Q>* p) {
+        uint8_t x[64] = {0}, y[64] = {0};
+        const bool inf = aff_is_inf<Q>(*p);
+        if (!inf) {
+            const Fe<Q> cx = fe_from_mont<Q>(p->x), cy = fe_from_mont<Q>(p->y);
+            memcpy(x, cx.v, Q::N * 4);
+            memcpy(y, cy.v, Q::N * 4);
+        }
+        tr.append_commitment(label, x, y, Q::N * 4, inf);
+    }
+    Fe<R> challenge(const char* label) {
+        uint8_t b[32];
+        tr.challenge_scalar(label, R::BITS, b);
+        Fe<R> c;
+        memcpy(c.v, b, 32);
+        return fe_to_mont<R>(c);
+    }
+    static Fe<R> inv(const Fe<R>& a) { return fe_inv_host<R>(a); }
+};
+
+// One proof's data for verifier_replay from the caller's inputs.  The public inputs and their roots are copied (an Fe is
+// 16-byte aligned, the caller's words need not be); rho = (1, 1), nothing forced, no sums and no trace until a caller sets them.
+template <class C>
+struct HostProof {
+    using R = typename C::Fr;
+    std::vector<Fe<R>> pi;              // roots, values and compute_r0's scratch: n_pi each
+    VtProof<C> p;
+    HostProof(const zkt_verify_inputs& in, int log_n, const Affine<typename C::Fq>* cm, const Fe<R>* ev) : pi(3 * in.n_pi) {
+        if (in.n_pi) {
+            memcpy((void*)pi.data(), in.pi_roots, in.n_pi * 32);
+            memcpy((void*)(pi.data() + in.n_pi), in.pub_inputs, in.n_pi * 32);
+        }
+        p.n = in.n;
+        p.n_pi = in.n_pi;
+        p.w = root_of_unity<R>(log_n);
+        p.rho[0] = p.rho[1] = fe_one<R>();
+        p.cm = cm;
+        p.ev = ev;
+        p.roots = pi.data();
+        p.vals = pi.data() + in.n_pi;
+        p.before = pi.data() + 2 * in.n_pi;
+        p.forced = nullptr;
+        p.acc = nullptr;
+        p.dbg = nullptr;
+    }
+};
+
 template <class C>
 struct Verifier {
     using R = typename C::Fr;
@@ -250,43 +330,19 @@ struct Verifier {
         }
         return acc;
     }
-    static void to_le(const F& mont, uint8_t out[32]) {
-        const F c = fe_from_mont<R>(mont);
-        memcpy(out, c.v, 32);
-    }
-    static F from_le(const uint8_t in[32]) {
-        F c;
-        memcpy(c.v, in, 32);
-        return fe_to_mont<R>(c);
-    }
-    static void tr_commit(HostTranscript& tr, const char* label, const Affine<Q>& p) {
-        uint8_t x[64] = {0}, y[64] = {0};
-        const bool inf = aff_is_inf<Q>(p);
-        if (!inf) {
-            const Fe<Q> cx = fe_from_mont<Q>(p.x), cy = fe_from_mont<Q>(p.y);
-            memcpy(x, cx.v, Q::N * 4);
-            memcpy(y, cy.v, Q::N * 4);
-        }
-        tr.append_commitment(label, x, y, Q::N * 4, inf);
-    }
-    static F challenge(HostTranscript& tr, const char* label) {
-        uint8_t b[32];
-        tr.challenge_scalar(label, R::BITS, b);
-        return from_le(b);
-    }
-
-    // Where a term's point comes from: the proof's 13 commitments in wire order, the ten verifier-key commitments, g.
-    // Z1, Z2, T, H1, g and the verifier-key points occur in both openings; a consumer that adds the two lists up (the
-    // batch verifier on the device) is left with at most SRC_COUNT bases per proof.
-    enum { SRC_CM = 0, SRC_VK = 13, SRC_G = 23, SRC_COUNT = 24 };
     static constexpr int MAX_TERMS = 13 + 8 + 2;
-    // Step 2's result: opening o is L_o = sum_k sc[o][k] * base[src[o][k]], checked against W_o = base[wit[o]]
+    // Step 2's result, a sink of verifier_replay: opening o is L_o = sum_k sc[o][k] * base[src[o][k]], checked against
+    // W_o = base[SRC_CM + CM_AW + o]
     struct Terms {
         Affine<Q> base[SRC_COUNT];
-        int n[2];
+        int n[2] = {0, 0};
         int src[2][MAX_TERMS];
         F sc[2][MAX_TERMS];
-        int wit[2];
+        void term(int o, int s, const F& v) {
+            src[o][n[o]] = s;
+            sc[o][n[o]] = v;
+            ++n[o];
+        }
     };
 
     static int shape(const zkt_verify_inputs& in, int* out_log_n) {
@@ -321,100 +377,6 @@ struct Verifier {
         return ZKT_OK;
     }
 
-    // Step 2: the transcript, r0 and the scalars of both openings; no group arithmetic
-    static int terms(const zkt_verify_inputs& in, int log_n, const Affine<Q>* cm, const F* ev, HostTranscript& tr, Terms& out) {
-        const size_t nb = Q::N * 4;
-        const int L64 = Q::N / 2;
-        enum { A, B, Cc, T, H1, H2, Z1, Z2, QLO, QMID, QHI, AW, SAW };
-        Affine<Q> vk[10];
-        for (int k = 0; k < 10; ++k) {
-            if (in.vk_is_infinity && in.vk_is_infinity[k]) {
-                vk[k].x = fe_zero<Q>();
-                vk[k].y = fe_zero<Q>();
-            } else {
-                memcpy(vk[k].x.v, in.vk_commitments + (size_t)k * 2 * L64, nb);
-                memcpy(vk[k].y.v, in.vk_commitments + (size_t)k * 2 * L64 + L64, nb);
-            }
-        }
-        enum { QM, QL, QR, QO, QC, S1, S2, S3, QLOOKUP, QTABLE };
-        // ---- transcript (proof.rs:308-360) ----
-        {
-            std::vector<uint8_t> b(in.n_pi * 32);
-            for (size_t i = 0; i < in.n_pi; ++i) {
-                F v;
-                memcpy(v.v, in.pub_inputs + 4 * i, 32);
-                to_le(v, b.data() + 32 * i);
-            }
-            tr.append_scalars("pi", b.data(), in.n_pi, 32, false);
-        }
-        tr_commit(tr, "a_commit", cm[A]); tr_commit(tr, "b_commit", cm[B]); tr_commit(tr, "c_commit", cm[Cc]);
-        tr_commit(tr, "t_commit", cm[T]); tr_commit(tr, "h1_commit", cm[H1]); tr_commit(tr, "h2_commit", cm[H2]);
-        const F beta = challenge(tr, "beta"), gamma = challenge(tr, "gamma"), delta = challenge(tr, "delta"),
-                epsilon = challenge(tr, "epsilon");
-        if (fe_eq<R>(beta, gamma) || fe_eq<R>(beta, delta) || fe_eq<R>(beta, epsilon) || fe_eq<R>(gamma, delta) ||
-            fe_eq<R>(gamma, epsilon) || fe_eq<R>(delta, epsilon))
-            return ZKT_ERR_EQUAL_CHALLENGES;
-        tr_commit(tr, "z1_commit", cm[Z1]); tr_commit(tr, "z2_commit", cm[Z2]);
-        const F alpha = challenge(tr, "alpha");
-        tr_commit(tr, "q_lo_commit", cm[QLO]); tr_commit(tr, "q_mid_commit", cm[QMID]); tr_commit(tr, "q_hi_commit", cm[QHI]);
-        const F xi = challenge(tr, "xi");
-        // ---- scalars (linearisation.hpp: proof.rs:362-378, compute_r0 163-217, util.rs:185-195) ----
-        const Challenges<R> ch{beta, gamma, delta, epsilon, alpha, xi, fe_zero<R>()};
-        XiPoint<R> at;
-        if (!xi_point<R>(ch, in.n, at)) return ZKT_ERR_ZERO_DENOMINATOR;
-        F r0;
-        if (compute_r0<R>(ch, at, ev, in.pi_roots, in.pub_inputs, in.n_pi, &r0)) return ZKT_ERR_ZERO_DENOMINATOR;
-        // ---- linearisation commitment (proof.rs:220-282; the 13-point MSM of commitment.rs:32-45) ----
-        F sc[LIN_COUNT];
-        linearisation_scalars<R>(ch, at, ev, sc);
-        const int pt[13] = {SRC_VK + QM, SRC_VK + QL, SRC_VK + QR, SRC_VK + QO, SRC_VK + QC, SRC_CM + Z1, SRC_VK + S3, SRC_CM + Z2,
-                            SRC_CM + H1, SRC_VK + QTABLE, SRC_CM + QLO, SRC_CM + QMID, SRC_CM + QHI};
-        for (int k = 0; k < EV_COUNT; ++k) {
-            uint8_t b[32];
-            to_le(ev[k], b);
-            tr.append_scalars(EV_LABEL[k], b, 1, 32, true);
-        }
-        const F eta = challenge(tr, "eta");
-        // ---- the two openings (proof.rs:420-500) ----
-        // L = sum_i eta^i C_i - (sum_i eta^i v_i) g + z W as ONE list of terms; the linearisation commitment (C_0 of the
-        // first opening, coefficient eta^0 = 1) enters through its own 13 terms
-        Affine<Q> g;
-        memcpy(g.x.v, in.g, nb);
-        memcpy(g.y.v, in.g + L64, nb);
-        const F w = root_of_unity<R>(log_n);
-        for (int k = 0; k < 13; ++k) out.base[SRC_CM + k] = cm[k];
-        for (int k = 0; k < 10; ++k) out.base[SRC_VK + k] = vk[k];
-        out.base[SRC_G] = g;
-        auto push = [&](int o, int src, const F& s) {
-            out.src[o][out.n[o]] = src;
-            out.sc[o][out.n[o]] = s;
-            ++out.n[o];
-        };
-        auto fold = [&](int o, const int* commits, const F* values, int k, F ch, F comb_v, const F& z, int wit) {
-            for (int i = 0; i < k; ++i) {
-                push(o, commits[i], ch);
-                comb_v = fe_add<R>(comb_v, fe_mul<R>(ch, values[i]));
-                ch = fe_mul<R>(ch, eta);
-            }
-            push(o, SRC_G, fe_neg<R>(comb_v));
-            push(o, wit, z);
-            out.wit[o] = wit;
-        };
-        out.n[0] = out.n[1] = 0;
-        {
-            for (int k = 0; k < 13; ++k) push(0, pt[k], sc[k]);
-            const int cs[8] = {SRC_CM + A, SRC_CM + B, SRC_CM + Cc, SRC_VK + S1, SRC_VK + S2, SRC_VK + QLOOKUP, SRC_CM + T, SRC_CM + H2};
-            const F vs[8] = {ev[EV_A], ev[EV_B], ev[EV_C], ev[EV_S1], ev[EV_S2], ev[EV_QL], ev[EV_T], ev[EV_H2]};
-            fold(0, cs, vs, 8, eta, r0, xi, SRC_CM + AW);
-        }
-        {
-            const int cs[4] = {SRC_CM + Z1, SRC_CM + Z2, SRC_CM + T, SRC_CM + H1};
-            const F vs[4] = {ev[EV_Z1N], ev[EV_Z2N], ev[EV_TN], ev[EV_H1N]};
-            fold(1, cs, vs, 4, fe_one<R>(), fe_zero<R>(), fe_mul<R>(xi, w), SRC_CM + SAW);
-        }
-        return ZKT_OK;
-    }
-
     // Steps 1 to 3 for one proof: the pairs (L, W) of both openings
     static int run(const zkt_verify_inputs& in, HostTranscript& tr, uint64_t* out_pairs, int* out_inf) {
         const size_t nb = Q::N * 4;
@@ -425,8 +387,13 @@ struct Verifier {
         Affine<Q> cm[13];
         F ev[12];
         if ((rc = parse(in, cm, ev, false))) return rc;
+        // Step 2: the transcript, r0 and the scalars of both openings; no group arithmetic
         auto t = std::make_unique<Terms>();
-        if ((rc = terms(in, log_n, cm, ev, tr, *t))) return rc;
+        HostProof<C> hp(in, log_n, cm, ev);
+        VtHostTr<C> htr{tr};
+        if ((rc = verifier_replay<C>(htr, hp.p, *t))) return rc;
+        for (int k = 0; k < 13; ++k) t->base[SRC_CM + k] = cm[k];
+        verifier_key_points<C>(in, &t->base[SRC_VK]);
         // Step 3: each list as ONE short multi-scalar multiplication
         for (int o = 0; o < 2; ++o) {
             std::vector<HX> pts;
@@ -437,7 +404,7 @@ struct Verifier {
             }
             const HX L = msm_wnaf<C>(pts.data(), scs.data(), (int)pts.size());
             const Affine<Q> la = xyzz_to_affine_host<Q>(hostec::hx_to<Q>(L));
-            const Affine<Q>& wit = t->base[t->wit[o]];
+            const Affine<Q>& wit = t->base[SRC_CM + CM_AW + o];
             uint64_t* o_ = out_pairs + (size_t)o * 4 * L64;
             memcpy(o_, la.x.v, nb);
             memcpy(o_ + L64, la.y.v, nb);
@@ -699,7 +666,7 @@ struct BatchPrep {
         return rc;
     }
     const Affine<Q>& base(size_t i, int s) const {
-        return s < Verifier<C>::SRC_VK ? cm[13 * i + s] : other[11 * i + (s - Verifier<C>::SRC_VK)];
+        return s < SRC_VK ? cm[13 * i + s] : other[11 * i + (s - SRC_VK)];
     }
 };
 
@@ -790,47 +757,70 @@ static void batch_coefficients(const zkt_verify_inputs* ins, size_t k, const uin
     }
 }
 
-// Stage 2 and the per-proof half of stage 4: Verifier::terms, then both openings' scalars times their rho added up by source
+// Stage 2 and the per-proof half of stage 4: the replay through each handle's own calls, both openings' scalars times their
+// rho added up by source
 template <class C>
 static int batch_terms(const zkt_verify_inputs* ins, zkt_transcript* const* trs, size_t k, BatchPrep<C>& bp) {
-    using V = Verifier<C>;
-    using R = typename C::Fr;
-    bp.acc.resize(V::SRC_COUNT * k);
+    bp.acc.resize(SRC_COUNT * k);
     bp.other.resize(11 * k);
-    auto t = std::make_unique<typename V::Terms>();
     for (size_t i = 0; i < k; ++i) {
-        if (int rc = V::terms(ins[i], bp.log_n[i], &bp.cm[13 * i], &bp.ev[12 * i], *trs[i]->impl, *t))
+        HostProof<C> hp(ins[i], bp.log_n[i], &bp.cm[13 * i], &bp.ev[12 * i]);
+        hp.p.rho[0] = bp.rho[2 * i];
+        hp.p.rho[1] = bp.rho[2 * i + 1];
+        hp.p.acc = &bp.acc[SRC_COUNT * i];
+        if (int rc = vt_terms<C>(VtHostTr<C>{*trs[i]->impl}, hp.p))
             return bp.refuse(rc, i, rc == ZKT_ERR_EQUAL_CHALLENGES ? "two challenges are equal" : "a Lagrange denominator is zero");
-        Fe<R>* acc = &bp.acc[V::SRC_COUNT * i];
-        for (int s = 0; s < V::SRC_COUNT; ++s) acc[s] = fe_zero<R>();
-        for (int o = 0; o < 2; ++o) {
-            for (int q = 0; q < t->n[o]; ++q)
-                acc[t->src[o][q]] = fe_add<R>(acc[t->src[o][q]], fe_mul<R>(bp.rho[2 * i + o], t->sc[o][q]));
-            if (t->wit[o] != V::SRC_CM + VL_WITNESS0 + o) return bp.refuse(ZKT_ERR_INVALID_ARGUMENT, i, "unexpected witness source");
-        }
-        for (int s = V::SRC_VK; s < V::SRC_COUNT; ++s) bp.other[11 * i + (s - V::SRC_VK)] = t->base[s];
+        verifier_key_points<C>(ins[i], &bp.other[11 * i]);
     }
     return ZKT_OK;
 }
 
 // ---- stage 2 and the per-proof sums of stage 4 on the device (zkt_ctx_set_verify_terms(ctx, 1); verify_terms.hpp) ----
-// the ten verifier-key points and g of one proof, as Verifier::terms reads them: sources SRC_VK .. SRC_G
-template <class C>
-static void other_bases(const zkt_verify_inputs& in, Affine<typename C::Fq>* out11) {
-    using Q = typename C::Fq;
-    const size_t nb = Q::N * 4;
-    const int L64 = Q::N / 2;
-    for (int k = 0; k < 10; ++k) {
-        if (in.vk_is_infinity && in.vk_is_infinity[k]) {
-            out11[k].x = fe_zero<Q>();
-            out11[k].y = fe_zero<Q>();
-        } else {
-            memcpy(out11[k].x.v, in.vk_commitments + (size_t)k * 2 * L64, nb);
-            memcpy(out11[k].y.v, in.vk_commitments + (size_t)k * 2 * L64 + L64, nb);
-        }
+// hipMemcpyAsync on the context's stream unless an earlier step failed: every step records its error in rc and falls
+// through to the ONE synchronise of its caller, since an upload may still be reading host memory
+static void copy_step(zkt_ctx* c, int& rc, void* dst, const void* src, size_t bytes, hipMemcpyKind kind, const char* what) {
+    if (rc) return;
+    const hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, c->stream);
+    if (e != hipSuccess) rc = hip_fail(c, e, what);
+}
+
+// where stage 1 keeps its data in verify_scratch: the compressed commitments at 0, the points, a status byte per point
+struct DecompLayout {
+    size_t out, status, end;
+};
+static DecompLayout decomp_layout(size_t npts, size_t nb) {
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    DecompLayout l;
+    l.out = up(npts * nb);
+    l.status = l.out + up(npts * 2 * nb);
+    l.end = l.status + up(npts);
+    return l;
+}
+
+// Stage 1's staging: verify_scratch grown to `bytes` (>= the layout's end), the 13 k compressed commitments up, ONE
+// k_g1_decompress launch, behind() -- what else reads the points on the device, enqueued on the same stream: (base) ->
+// code -- then the points into bp.cm and the statuses down, and the stream synchronised ONCE.
+template <class C, class Behind>
+static int decompress_stage(zkt_ctx* c, BatchPrep<C>& bp, size_t k, size_t bytes, std::vector<uint8_t>& status, Behind behind) {
+    const size_t nb = C::Fq::N * 4, npts = 13 * k;
+    const DecompLayout l = decomp_layout(npts, nb);
+    bp.points_offset = l.out;
+    int rc = grow(c, c->verify_scratch, bytes);
+    if (rc) return rc;
+    char* const base = (char*)c->verify_scratch.p;
+    bp.cm.resize(npts);
+    status.resize(npts);
+    {
+        ProfScope prof(c, "verify_decompress");
+        copy_step(c, rc, base, bp.comp.data(), npts * nb, hipMemcpyHostToDevice, "verify batch: commitments upload");
+        if (!rc) rc = g1_decompress_enqueue(c, base, npts, base + l.out, base + l.status);
     }
-    memcpy(out11[10].x.v, in.g, nb);
-    memcpy(out11[10].y.v, in.g + L64, nb);
+    if (!rc) rc = behind(base);
+    copy_step(c, rc, bp.cm.data(), base + l.out, npts * 2 * nb, hipMemcpyDeviceToHost, "verify batch: points download");
+    copy_step(c, rc, status.data(), base + l.status, npts, hipMemcpyDeviceToHost, "verify batch: statuses download");
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    if (!rc && e != hipSuccess) rc = hip_fail(c, e, "verify batch: decompression");
+    return rc;
 }
 
 // What stages 1 and 2 on the device bring down: the status of every commitment and the image of the kernel's region
@@ -851,13 +841,11 @@ static int stages12_dev(zkt_ctx* c, const zkt_verify_inputs* ins, zkt_transcript
     using Q = typename C::Fq;
     using R = typename C::Fr;
     using F = Fe<R>;
-    const size_t nb = Q::N * 4, npts = 13 * k;
     *refused = false;
     size_t total_pi = 0;
     for (size_t i = 0; i < k; ++i) total_pi += ins[i].n_pi;
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t o_out = up(npts * nb), o_st = o_out + up(npts * 2 * nb);
-    const VtLayout lay = vt_layout(o_st + up(npts), k, total_pi, forced_mont != nullptr, dbg);
+    const DecompLayout dl = decomp_layout(13 * k, Q::N * 4);
+    const VtLayout lay = vt_layout(dl.end, k, total_pi, forced_mont != nullptr, dbg);
     td.lay = lay;
     td.host.assign(lay.end - lay.desc, 0);
     auto* desc = (VtDesc<R>*)td.at(lay.desc);
@@ -892,36 +880,16 @@ static int stages12_dev(zkt_ctx* c, const zkt_verify_inputs* ins, zkt_transcript
     }
     memcpy(td.at(lay.ev), bp.ev.data(), k * 12 * sizeof(F));
     if (forced_mont) memcpy(td.at(lay.forced), forced_mont, k * 7 * 32);
-    bp.points_offset = o_out;
     bp.stage1_end = lay.end;             // zkt_verify_batch_locate's own region starts behind this stage's
-    int rc = grow(c, c->verify_scratch, lay.end);
-    if (rc) return rc;
-    char* const base = (char*)c->verify_scratch.p;
-    bp.cm.resize(npts);
-    td.point_status.resize(npts);
     const size_t down_end = dbg ? lay.before : lay.dbg;
-    // every step records its error and falls through to the one synchronise: an upload may still be reading td.host
-    auto copy = [&](void* dst, const void* src, size_t bytes, hipMemcpyKind kind, const char* what) {
-        if (rc) return;
-        const hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, c->stream);
-        if (e != hipSuccess) rc = hip_fail(c, e, what);
-    };
-    {
-        ProfScope prof(c, "verify_decompress");
-        copy(base, bp.comp.data(), npts * nb, hipMemcpyHostToDevice, "verify batch: commitments upload");
-        if (!rc) rc = g1_decompress_enqueue(c, base, npts, base + o_out, base + o_st);
-    }
-    {
+    return decompress_stage<C>(c, bp, k, lay.end, td.point_status, [&](char* base) {
         ProfScope prof(c, "verify_terms");
-        copy(base + lay.desc, td.at(lay.desc), lay.status - lay.desc, hipMemcpyHostToDevice, "verify terms: upload");
-        if (!rc) rc = verify_terms_enqueue(c, base, lay, base + o_out, k, forced_mont != nullptr, dbg);
-        copy(td.at(lay.states), base + lay.states, down_end - lay.states, hipMemcpyDeviceToHost, "verify terms: download");
-    }
-    copy(bp.cm.data(), base + o_out, npts * 2 * nb, hipMemcpyDeviceToHost, "verify batch: points download");
-    copy(td.point_status.data(), base + o_st, npts, hipMemcpyDeviceToHost, "verify batch: statuses download");
-    const hipError_t e = hipStreamSynchronize(c->stream);
-    if (!rc && e != hipSuccess) rc = hip_fail(c, e, "verify terms");
-    return rc;
+        int rc = ZKT_OK;
+        copy_step(c, rc, base + lay.desc, td.at(lay.desc), lay.status - lay.desc, hipMemcpyHostToDevice, "verify terms: upload");
+        if (!rc) rc = verify_terms_enqueue(c, base, lay, base + dl.out, k, forced_mont != nullptr, dbg);
+        copy_step(c, rc, td.at(lay.states), base + lay.states, down_end - lay.states, hipMemcpyDeviceToHost, "verify terms: download");
+        return rc;
+    });
 }
 
 // the first commitment the decompression refused: its index, or npts
@@ -934,7 +902,8 @@ static size_t first_refused_point(const std::vector<uint8_t>& status) {
 // ---- zkt_verify_batch_dev: the batch above with its two per-proof costs on the device ------------------------------
 // Stage 1: the 13 k compressed commitments go up in one copy and through ONE k_g1_decompress launch (g1decomp.hip); the
 //          other bytes of a proof (length, Option::None, evaluations) are checked here.
-// Stage 2: Verifier::terms per proof, on the host: transcript, r0, the scalars of both openings -- no group arithmetic.
+// Stage 2: verifier_replay per proof, on the host through the handle's calls: transcript, r0, the scalars of both openings
+//          -- no group arithmetic.
 //          (zkt_ctx_set_verify_terms(ctx, 1): in one kernel behind stage 1's, with the per-proof sums of stage 4 --
 //          stages12_dev above; stage 3 then runs first, since the kernel takes each proof's rho.)
 // Stage 3: rho_0 = 1, rho_j = low 128 bits of Keccak-256(seed || j); the seed is hashed from everything that determines the
@@ -949,7 +918,6 @@ static size_t first_refused_point(const std::vector<uint8_t>& status) {
 template <class C>
 static int batch_fold_dev(zkt_ctx* c, const char* who, const zkt_verify_inputs* ins, zkt_transcript* const* trs, size_t k,
                           const uint64_t* h, const uint64_t* beta_h, BatchPrep<C>& bp, uint64_t* out_ab, int* out_inf) {
-    using V = Verifier<C>;
     using Q = typename C::Fq;
     using R = typename C::Fr;
     using F = Fe<R>;
@@ -987,30 +955,14 @@ static int batch_fold_dev(zkt_ctx* c, const char* who, const zkt_verify_inputs* 
         const TranscriptState* states = (const TranscriptState*)td.at(td.lay.states);
         for (size_t i = 0; i < k; ++i)
             if (!trs[i]->impl->import_state(states[i])) return fail(ZKT_ERR_INVALID_ARGUMENT, i, "the transcript refused its state");
-        bp.acc.resize(V::SRC_COUNT * k);
+        bp.acc.resize(SRC_COUNT * k);
         memcpy((void*)bp.acc.data(), td.at(td.lay.acc), bp.acc.size() * sizeof(F));
         bp.other.resize(11 * k);
-        for (size_t i = 0; i < k; ++i) other_bases<C>(ins[i], &bp.other[11 * i]);
+        for (size_t i = 0; i < k; ++i) verifier_key_points<C>(ins[i], &bp.other[11 * i]);
     } else {
-        auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-        const size_t o_out = up(npts * nb), o_st = o_out + up(npts * 2 * nb);
-        bp.points_offset = o_out;
-        bp.stage1_end = o_st + up(npts);
-        if ((rc = grow(c, c->verify_scratch, bp.stage1_end))) return rc;
-        char* const base = (char*)c->verify_scratch.p;
-        bp.cm.resize(npts);
-        std::vector<uint8_t> status(npts);
-        {
-            ProfScope prof(c, "verify_decompress");
-            ZKT_HIP(c, hipMemcpyAsync(base, bp.comp.data(), npts * nb, hipMemcpyHostToDevice, c->stream));
-            if ((rc = g1_decompress_enqueue(c, base, npts, base + o_out, base + o_st))) {
-                (void)hipStreamSynchronize(c->stream);
-                return rc;
-            }
-            ZKT_HIP(c, hipMemcpyAsync(bp.cm.data(), base + o_out, npts * 2 * nb, hipMemcpyDeviceToHost, c->stream));
-            ZKT_HIP(c, hipMemcpyAsync(status.data(), base + o_st, npts, hipMemcpyDeviceToHost, c->stream));
-        }
-        ZKT_HIP(c, hipStreamSynchronize(c->stream));
+        bp.stage1_end = decomp_layout(npts, nb).end;
+        std::vector<uint8_t> status;
+        if ((rc = decompress_stage<C>(c, bp, k, bp.stage1_end, status, [](char*) { return (int)ZKT_OK; }))) return rc;
         for (size_t p = 0; p < npts; ++p)
             if (status[p] > ZKT_G1_IDENTITY) return refused_commitment(p, status[p]);
         // ---- stage 3 (before the transcripts are consumed), stage 2 and the per-proof sums of stage 4 ----
@@ -1022,14 +974,14 @@ static int batch_fold_dev(zkt_ctx* c, const char* who, const zkt_verify_inputs* 
     std::vector<Affine<Q>> a_bases, b_bases(m);
     std::vector<F> a_acc;                              // Montgomery sums, one per entry of a_bases
     std::map<std::string, size_t> shared;              // verifier-key points and g, by content
-    a_bases.reserve(V::SRC_COUNT * (k < 64 ? k : 64) + 13 * k);
+    a_bases.reserve(SRC_COUNT * (k < 64 ? k : 64) + 13 * k);
     for (size_t i = 0; i < k; ++i) {
         for (int o = 0; o < 2; ++o) b_bases[2 * i + o] = bp.cm[13 * i + VL_WITNESS0 + o];
-        for (int s = 0; s < V::SRC_COUNT; ++s) {
+        for (int s = 0; s < SRC_COUNT; ++s) {
             const Affine<Q>& pt = bp.base(i, s);
-            const F& sc = bp.acc[V::SRC_COUNT * i + s];
+            const F& sc = bp.acc[SRC_COUNT * i + s];
             if (aff_is_inf<Q>(pt)) continue;
-            if (s >= V::SRC_VK) {
+            if (s >= SRC_VK) {
                 auto ins_ = shared.emplace(std::string((const char*)&pt, sizeof(pt)), a_bases.size());
                 if (!ins_.second) {
                     a_acc[ins_.first->second] = fe_add<R>(a_acc[ins_.first->second], sc);
@@ -1071,32 +1023,20 @@ static int verify_batch_prepare_dev_t(zkt_ctx* c, const zkt_verify_inputs* ins, 
 }
 
 // ---- zkt_debug_verify_terms / zkt_debug_verify_terms_host: the term stage alone, by any of its three routes ----------
-// A transcript that hands `inner`'s calls on and replaces its answers by forced[0 .. 7) (Montgomery) in the order they are
-// asked for; it is still fed and asked, so its state moves as usual (tests/forced_challenges.py does the same to the prover)
-template <class R>
-struct ForcedTranscript : HostTranscript {
-    HostTranscript& inner;
-    const Fe<R>* forced;
-    Fe<R> drawn[7];
-    int n_drawn = 0;
-    ForcedTranscript(HostTranscript& in, const Fe<R>* f) : inner(in), forced(f) {}
-    void append_u64(const char* label, uint64_t v) override { inner.append_u64(label, v); }
-    void append_scalars(const char* label, const uint8_t* le, size_t count, size_t fr_bytes, bool single) override {
-        inner.append_scalars(label, le, count, fr_bytes, single);
+// A built-in handle's state in a core transcript of its own (a stride of one in place of the kernel's LDS), and back
+struct CoreCopy {
+    TranscriptState st;
+    uint64_t words[VT_LANE_WORDS] = {0};
+    VtTr tr;
+    bool load(HostTranscript& h) {
+        if (!h.export_state(st)) return false;
+        tr.s = VtSponge{words, words + VT_ST_WORDS, words + VT_ST_WORDS + VT_MSG_WORDS, 1};
+        vt_load_state(tr, &st);
+        return true;
     }
-    void append_commitment(const char* label, const uint8_t* x, const uint8_t* y, size_t fq_bytes, bool inf) override {
-        inner.append_commitment(label, x, y, fq_bytes, inf);
-    }
-    void challenge_scalar(const char* label, size_t fr_bits, uint8_t out_le[32]) override {
-        inner.challenge_scalar(label, fr_bits, out_le);
-        if (n_drawn >= 7) return;
-        if (forced) {
-            const Fe<R> v = fe_from_mont<R>(forced[n_drawn]);
-            memcpy(out_le, v.v, 32);
-        }
-        Fe<R> v;
-        memcpy(v.v, out_le, 32);
-        drawn[n_drawn++] = fe_to_mont<R>(v);
+    bool store(HostTranscript& h) {
+        vt_store_state(tr, &st);
+        return h.import_state(st);
     }
 };
 
@@ -1105,7 +1045,6 @@ template <class C>
 static int debug_terms_t(zkt_ctx* c, const zkt_verify_inputs* ins, zkt_transcript* const* trs, size_t k, const uint64_t* rho_c4,
                          const uint64_t* forced_mont, int route, uint64_t* out_ch, uint64_t* out_r0, uint64_t* out_acc,
                          int* out_status) {
-    using V = Verifier<C>;
     using Q = typename C::Fq;
     using R = typename C::Fr;
     using F = Fe<R>;
@@ -1123,7 +1062,7 @@ static int debug_terms_t(zkt_ctx* c, const zkt_verify_inputs* ins, zkt_transcrip
     }
     memset(out_ch, 0, k * 7 * 32);
     memset(out_r0, 0, k * 32);
-    memset(out_acc, 0, k * V::SRC_COUNT * 32);
+    memset(out_acc, 0, k * SRC_COUNT * 32);
     if (route == 2) {
         TermsDev td;
         bool refused = false;
@@ -1138,89 +1077,41 @@ static int debug_terms_t(zkt_ctx* c, const zkt_verify_inputs* ins, zkt_transcrip
             memcpy(out_ch + 28 * i, td.at(td.lay.dbg) + i * 8 * 32, 7 * 32);
             memcpy(out_r0 + 4 * i, td.at(td.lay.dbg) + (i * 8 + 7) * 32, 32);
         }
-        memcpy(out_acc, td.at(td.lay.acc), k * V::SRC_COUNT * 32);
+        memcpy(out_acc, td.at(td.lay.acc), k * SRC_COUNT * 32);
         return ZKT_OK;
     }
     // ---- the commitments: through the device's decompression where there is a device ----
-    bp.cm.resize(npts);
     if (c) {
-        auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-        const size_t o_out = up(npts * nb), o_st = o_out + up(npts * 2 * nb);
-        if ((rc = grow(c, c->verify_scratch, o_st + up(npts)))) return rc;
-        char* const base = (char*)c->verify_scratch.p;
-        std::vector<uint8_t> status(npts);
-        hipError_t e = hipMemcpyAsync(base, bp.comp.data(), npts * nb, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) rc = g1_decompress_enqueue(c, base, npts, base + o_out, base + o_st);
-        if (e == hipSuccess && !rc) e = hipMemcpyAsync(bp.cm.data(), base + o_out, npts * 2 * nb, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && !rc) e = hipMemcpyAsync(status.data(), base + o_st, npts, hipMemcpyDeviceToHost, c->stream);
-        const hipError_t es = hipStreamSynchronize(c->stream);
-        if (rc) return rc;
-        if (e != hipSuccess || es != hipSuccess) return hip_fail(c, e != hipSuccess ? e : es, "debug_verify_terms: decompression");
+        std::vector<uint8_t> status;
+        if ((rc = decompress_stage<C>(c, bp, k, decomp_layout(npts, nb).end, status, [](char*) { return (int)ZKT_OK; }))) return rc;
         if (first_refused_point(status) < npts) return err(ZKT_ERR_INVALID_ARGUMENT, "a commitment was refused");
     } else {
+        bp.cm.resize(npts);
         for (size_t p = 0; p < npts; ++p) {
             bool inf = false;
             if (!decompress<C>(bp.comp.data() + p * nb, &bp.cm[p], &inf)) return ZKT_ERR_INVALID_ARGUMENT;
         }
     }
-    const F* forced = (const F*)forced_mont;
-    auto t = std::make_unique<typename V::Terms>();
+    // ---- route 0: through the handle's virtual calls, as the batch verifier's host route and a caller's callbacks go;
+    // ---- route 1: on the core's state directly, as the kernel goes
     for (size_t i = 0; i < k; ++i) {
-        F* acc = (F*)(out_acc + 4 * V::SRC_COUNT * i);
+        HostProof<C> hp(ins[i], bp.log_n[i], &bp.cm[13 * i], &bp.ev[12 * i]);
+        F dbg[8];
+        hp.p.rho[0] = bp.rho[2 * i];
+        hp.p.rho[1] = bp.rho[2 * i + 1];
+        hp.p.forced = forced_mont ? (const F*)forced_mont + 7 * i : nullptr;
+        hp.p.acc = (F*)(out_acc + 4 * SRC_COUNT * i);
+        hp.p.dbg = dbg;
         if (route == 0) {
-            // the existing host code: Verifier::terms, then the sums of batch_terms
-            ForcedTranscript<R> ft(*trs[i]->impl, forced ? forced + 7 * i : nullptr);
-            out_status[i] = V::terms(ins[i], bp.log_n[i], &bp.cm[13 * i], &bp.ev[12 * i], ft, *t);
-            memcpy(out_ch + 28 * i, ft.drawn, (size_t)ft.n_drawn * 32);
-            if (out_status[i]) continue;
-            for (int s = 0; s < V::SRC_COUNT; ++s) acc[s] = fe_zero<R>();
-            for (int o = 0; o < 2; ++o)
-                for (int q = 0; q < t->n[o]; ++q)
-                    acc[t->src[o][q]] = fe_add<R>(acc[t->src[o][q]], fe_mul<R>(bp.rho[2 * i + o], t->sc[o][q]));
-            // r0 is not among the terms' outputs; the scalar on g of the first opening is -(r0 + sum_i eta^(i+1) v_i)
-            const F* ev = &bp.ev[12 * i];
-            const F vs[8] = {ev[EV_A], ev[EV_B], ev[EV_C], ev[EV_S1], ev[EV_S2], ev[EV_QL], ev[EV_T], ev[EV_H2]};
-            const F eta = ft.drawn[6];
-            F r0 = fe_neg<R>(t->sc[0][13 + 8]), ch = eta;
-            for (int q = 0; q < 8; ++q) {
-                r0 = fe_sub<R>(r0, fe_mul<R>(ch, vs[q]));
-                ch = fe_mul<R>(ch, eta);
-            }
-            memcpy(out_r0 + 4 * i, r0.v, 32);
+            out_status[i] = vt_terms<C>(VtHostTr<C>{*trs[i]->impl}, hp.p);
         } else {
-            // the shared code of verify_terms.hpp on the host: a stride of one in place of the kernel's LDS
-            TranscriptState st;
-            if (!trs[i]->impl->export_state(st)) return err(ZKT_ERR_INVALID_ARGUMENT, "a transcript that zkt_transcript_new did not make");
-            uint64_t words[VT_LANE_WORDS] = {0};
-            VtTr tr;
-            tr.s = VtSponge{words, words + VT_ST_WORDS, words + VT_ST_WORDS + VT_MSG_WORDS, 1};
-            vt_load_state(tr, &st);
-            std::vector<F> roots(ins[i].n_pi), vals(ins[i].n_pi), before(ins[i].n_pi);
-            if (ins[i].n_pi) {
-                memcpy((void*)roots.data(), ins[i].pi_roots, ins[i].n_pi * 32);
-                memcpy((void*)vals.data(), ins[i].pub_inputs, ins[i].n_pi * 32);
-            }
-            F dbg[8];
-            VtProof<C> p;
-            p.n = ins[i].n;
-            p.n_pi = ins[i].n_pi;
-            p.w = root_of_unity<R>(bp.log_n[i]);
-            p.rho[0] = bp.rho[2 * i];
-            p.rho[1] = bp.rho[2 * i + 1];
-            p.cm = &bp.cm[13 * i];
-            p.ev = &bp.ev[12 * i];
-            p.roots = roots.data();
-            p.vals = vals.data();
-            p.forced = forced ? forced + 7 * i : nullptr;
-            p.before = before.data();
-            p.acc = acc;
-            p.dbg = dbg;
-            out_status[i] = vt_terms<C>(tr, p);
-            vt_store_state(tr, &st);
-            if (!trs[i]->impl->import_state(st)) return err(ZKT_ERR_INVALID_ARGUMENT, "the transcript refused its state");
-            memcpy(out_ch + 28 * i, dbg, 7 * 32);
-            memcpy(out_r0 + 4 * i, dbg[7].v, 32);
+            CoreCopy cc;
+            if (!cc.load(*trs[i]->impl)) return err(ZKT_ERR_INVALID_ARGUMENT, "a transcript that zkt_transcript_new did not make");
+            out_status[i] = vt_terms<C>(VtCoreTr<C>{cc.tr}, hp.p);
+            if (!cc.store(*trs[i]->impl)) return err(ZKT_ERR_INVALID_ARGUMENT, "the transcript refused its state");
         }
+        memcpy(out_ch + 28 * i, dbg, 7 * 32);
+        memcpy(out_r0 + 4 * i, dbg[7].v, 32);
     }
     return ZKT_OK;
 }
@@ -1255,16 +1146,13 @@ extern "C" int zkt_debug_verify_terms_host(int curve_id, const zkt_verify_inputs
     return ZKT_ERR_INVALID_ARGUMENT;
 }
 
-// One transcript call through the code of verify_terms.hpp, on the host: the handle's state out, the call, the state in again
+// One transcript call on the core's state directly (transcript_core.hpp): the handle's state out, the call, the state in again
 extern "C" int zkt_debug_verify_terms_transcript(zkt_transcript* t, int op, const char* label, const uint8_t* data, size_t len,
                                                  uint8_t out32[32]) {
     if (!t || !label || op < 0 || op > 2) return ZKT_ERR_INVALID_ARGUMENT;
-    TranscriptState st;
-    if (!t->impl->export_state(st)) return ZKT_ERR_INVALID_ARGUMENT;
-    uint64_t words[VT_LANE_WORDS] = {0};
-    VtTr tr;
-    tr.s = VtSponge{words, words + VT_ST_WORDS, words + VT_ST_WORDS + VT_MSG_WORDS, 1};
-    vt_load_state(tr, &st);
+    CoreCopy cc;
+    if (!cc.load(*t->impl)) return ZKT_ERR_INVALID_ARGUMENT;
+    VtTr& tr = cc.tr;
     if (op == 2) {
         if (!out32 || len < 16 || len > 264) return ZKT_ERR_INVALID_ARGUMENT;
         uint32_t w[8];
@@ -1273,7 +1161,7 @@ extern "C" int zkt_debug_verify_terms_transcript(zkt_transcript* t, int op, cons
     } else {
         if (!data || len > (op == 1 ? 96u : 8u * VT_MSG_WORDS) || (op == 1 && (len & 1))) return ZKT_ERR_INVALID_ARGUMENT;
         if (tr.kind != 0 && len > 68) return ZKT_ERR_INVALID_ARGUMENT;   // one Keccak-256 block: 65 + len + padding <= 136
-        memcpy(words + VT_ST_WORDS, data, len);
+        memcpy(cc.words + VT_ST_WORDS, data, len);
         if (op == 1) {
             vt_tr_commit_msg(tr, label, (uint32_t)(len / 2));             // the infinity byte behind x || y stays zero
         } else if (tr.kind == 0) {
@@ -1284,8 +1172,7 @@ extern "C" int zkt_debug_verify_terms_transcript(zkt_transcript* t, int op, cons
             vt_eth_append(tr, 0, (uint32_t)len);
         }
     }
-    vt_store_state(tr, &st);
-    return t->impl->import_state(st) ? ZKT_OK : ZKT_ERR_INVALID_ARGUMENT;
+    return cc.store(*t->impl) ? ZKT_OK : ZKT_ERR_INVALID_ARGUMENT;
 }
 
 extern "C" int zkt_ctx_set_verify_terms(zkt_ctx* c, int mode) {
@@ -1380,11 +1267,8 @@ static int locate_tree_dev(zkt_ctx* c, const BatchPrep<C>& bp, size_t k, LocateT
     if (rc) return rc;
     char* const base = (char*)c->verify_scratch.p;
     const std::vector<uint64_t> sc = leaf_scalars<C>(bp);
-    // every step records its error and falls through to the one synchronise below: an upload may still be reading sc
     auto copy = [&](void* dst, const void* src, size_t bytes, hipMemcpyKind kind, const char* what) {
-        if (rc) return;
-        const hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, c->stream);
-        if (e != hipSuccess) rc = hip_fail(c, e, what);
+        copy_step(c, rc, dst, src, bytes, kind, what);   // an upload may still be reading sc: one synchronise below
     };
     {
         ProfScope prof(c, "verify_leaves");
@@ -1409,7 +1293,6 @@ static int locate_tree_dev(zkt_ctx* c, const BatchPrep<C>& bp, size_t k, LocateT
 template <class C>
 static void locate_tree_host(const BatchPrep<C>& bp, size_t k, LocateTree<C>& tree) {
     using Q = typename C::Fq;
-    using V = Verifier<C>;
     tree.shape(k);
     const std::vector<uint64_t> sc = leaf_scalars<C>(bp);
     auto words = [](const uint64_t* w, uint32_t (&out)[8]) { memcpy(out, w, 32); };
@@ -1417,7 +1300,7 @@ static void locate_tree_host(const BatchPrep<C>& bp, size_t k, LocateTree<C>& tr
         XyzzX<Q> prod[VL_TERMS];
         uint32_t kw[8];
         for (int s = 0; s < VL_SOURCES; ++s) {
-            words(&sc[4 * (V::SRC_COUNT * i + s)], kw);
+            words(&sc[4 * (SRC_COUNT * i + s)], kw);
             prod[s] = vl_mul<Q>(bp.base(i, s), kw);
         }
         for (int o = 0; o < 2; ++o) {

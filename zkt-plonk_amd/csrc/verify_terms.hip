@@ -1,14 +1,15 @@
-// The batch verifier's transcripts and scalar stage on the device (arithmetic, transcript and layout: verify_terms.hpp).
-//   k_verify_terms   one lane per proof: the Fiat-Shamir replay of Verifier::terms from the proof's exported transcript
-//                    state, xi_point, compute_r0, the linearisation scalars, both fold lists and the 24 sums by source.
+// The batch verifier's transcripts and scalar stage on the device (the replay and the layout: verify_terms.hpp; the
+// transcripts: transcript_core.hpp; the arithmetic: linearisation.hpp -- each the code the host runs too).
+//   k_verify_terms   one lane per proof: verifier_replay from the proof's exported transcript state into the 24 sums by
+//                    source -- the Fiat-Shamir replay, xi_point, compute_r0, the linearisation scalars, both fold lists.
 // 64-thread workgroups, so a batch of a few thousand proofs spreads over every CU.  Each lane owns VT_LANE_WORDS 64-bit
 // words of LDS laid out [word][lane] (23.0 KB per workgroup): the sponge, the message buffer and the Ethereum states are
 // addressed by byte there and never sit in a register array.  Lanes diverge -- positions differ with n_pi, so they
 // permute at different times -- which this stage can afford.  Nothing is indexed by proof data beyond the per-proof
 // offsets the host wrote; every lane checks its index against the count it was given.
 //
-// Resources (gfx950, docs/EXPERIMENTS.md "the batch verifier's transcripts and scalar stage on the device"): 256 VGPRs,
-// 6896 bytes of scratch per lane for the call frames of the non-inlined field and transcript functions, no spills.
+// Resources (gfx950, docs/EXPERIMENTS.md "one verifier replay and one transcript core"): 256 VGPRs, 6896 bytes of scratch
+// per lane for the call frames of the non-inlined field and transcript functions, no spills.
 #include "verify_terms.hpp"
 
 namespace zkt {
@@ -48,7 +49,7 @@ __global__ __launch_bounds__(VT_THREADS) void k_verify_terms(const VtDesc<typena
     p.before = before + d.pi_off;
     p.acc = acc + (size_t)i * 24;
     p.dbg = dbg ? dbg + (size_t)i * 8 : nullptr;
-    status[i] = vt_terms<C>(t, p);
+    status[i] = vt_terms<C>(VtCoreTr<C>{t}, p);
     vt_store_state(t, &states[i]);
 }
 
