@@ -107,6 +107,7 @@ int zkt_ctx_synchronize(zkt_ctx* ctx);
  * domain table they read).
  * "check_witness": every launch of zkt_circuit_check_witness (selector transforms, the sigma launches when the wiring
  * is checked, the gate, residual and comparison kernels), not its uploads.
+ * "check_witness_batch": the same launches of zkt_circuit_check_witness_batch, once for the whole batch.
  * "merkle_append": the copy of the leaves into layer 0 and every level launch of one zkt_merkle_tree_append(_dev);
  * "merkle_paths": the table upload and the gather launch of zkt_merkle_tree_paths / _paths_to_variables_dev.
  * A scope that covers a batch counts its units in `calls` (the three commitments of a round grouped and accumulated as one
@@ -579,9 +580,36 @@ typedef struct {
 } zkt_witness_report;
 int zkt_circuit_check_witness(zkt_ctx* ctx, const zkt_prove_inputs* in, int flags, zkt_witness_report* out);
 
+/* The same check over a batch of variable maps that share one wiring -- what one zkt_witness_complete_enqueue leaves in
+ * HBM.  A completion satisfies every defining row by construction; whether a witness is good is decided by the rows that
+ * define nothing (equal_constrain, boolean rows, public rows, the lookup), and this call judges all of them for the whole
+ * batch: one set of selector transforms and one synchronisation, where a loop of the single call makes `batch` of each.
+ * out[w] equals, field for field (counts, first rows, residual, checked, satisfied), what zkt_circuit_check_witness reports
+ * for witness w alone, given w's map, its public inputs, its table and the same flags.  Errors and refusals are those of
+ * the single call, applied to the whole batch (a repeated value in any table, an index outside the map, ...); in addition
+ * ZKT_ERR_INVALID_ARGUMENT for batch = 0, batch > ZKT_WITNESS_BATCH_MAX, stride < n_vars, n_tables not 0, 1 or batch, and
+ * a NULL d_pi_vals with n_pi > 0.  On an error no report is written.  ZKT_CHECK_WIRING concerns the shared wiring: it is
+ * checked once and its three fields are copied into every report.
+ * Kernels (csrc/check.hip): a thread loads its row's selectors, wire indices and public-input slot once and walks a tile of
+ * witnesses (the batch is the launch's second dimension); one status block per witness, filled with sums and minima
+ * (vector atomics), so no result depends on an order.  Enqueues on the context's stream behind whatever is there -- a
+ * completion in particular, without a wait in between -- and synchronises once, at the end.  Works on a fork and under a
+ * communicator (local, no collective); leaves an announced proof (zkt_prove_set_next) untouched, as the single call does.
+ * The name carries no _dev suffix although the maps are device pointers: the call synchronises and returns host reports. */
+typedef struct {
+    const void* d_variables;        /* DEVICE: witness w = d_variables + w * stride scalars, as the completion leaves them */
+    size_t stride, batch, n_vars;   /* 1 <= batch <= ZKT_WITNESS_BATCH_MAX, stride >= n_vars */
+    const uint32_t *w_l, *w_r, *w_o; size_t n_rows; int wiring_on_device;   /* one wiring for the whole batch */
+    const size_t* pi_pos; size_t n_pi;
+    const void* d_pi_vals;          /* DEVICE: batch x n_pi, in the order of pi_pos: what zkt_witness_complete_enqueue writes */
+    const uint64_t* const* tables; const size_t* table_lens; size_t n_tables;   /* HOST; 0, 1 (shared) or batch (one each) */
+} zkt_witness_batch;
+int zkt_circuit_check_witness_batch(zkt_ctx* ctx, const zkt_witness_batch* in, int flags, zkt_witness_report* out /* batch */);
+
 /* ---- Witness completion from the circuit's free variables: the solving half of the check above ----------------------
- * The caller uploads the values of the free variables (for a circuit written against the reference's composer: exactly its
- * direct assign_variable calls); the device fills in every variable that a gate defines and returns the public inputs the
+ * The caller uploads the values of the free variables (for a circuit written against the reference's composer: its direct
+ * assign_variable calls, less the two that should_be_zero_with_output makes when the plan is created with
+ * ZKT_WITNESS_RULE_IS_ZERO); the device fills in every variable that a gate defines and returns the public inputs the
  * witness implies.  Nothing is assumed about the circuit beyond the rule below, which is part of this interface.
  *
  * THE RULE.  Row i asserts q_m a b + q_l a + q_r b + q_o c + q_c + PI_i = 0 (composer.rs:170-199), a, b, c the values of
@@ -589,6 +617,18 @@ int zkt_circuit_check_witness(zkt_ctx* ctx, const zkt_prove_inputs* in, int flag
  * a row before i.  ZKT_VARIABLE_ZERO and rows >= n_rows define nothing.
  *  - A public-input row (i among pi_pos) defines nothing.  Its public input is an output:
  *        PI_i = -(q_m a b + q_l a + q_r b + q_o c + q_c)                       (set_variable_public, mod.rs:216-240).
+ *  - Rule Z (the is-zero pair), only for a plan made with ZKT_WITNESS_RULE_IS_ZERO (zkt_witness_plan_create_ex), tried at
+ *    row i before rule O.  It fires when neither row i nor row i + 1 is a public-input row, i + 1 < n_rows; row i has wires
+ *    (x, y, z) with q_m != 0, q_o != 0, q_l = q_r = 0 (q_c arbitrary); y and z are real variables, unseen at row i, distinct
+ *    from each other and from x; x is any real variable or ZKT_VARIABLE_ZERO; and row i + 1 has wires
+ *    (x, z, ZKT_VARIABLE_ZERO) with q_m != 0 and q_l = q_r = q_o = q_c = 0 (it asserts x z = 0).  Row i then defines both:
+ *        x = 0:   y = 0,  z = -q_c / q_o;          x != 0:   z = 0,  y = -q_c / (q_m x).
+ *    With the reference's selectors (q_m = 1, q_o = 1, q_c = -1) this is should_be_zero_with_output and should_eq_with_output
+ *    (mod.rs:243-289): y = x^-1 or 0 (inverse().unwrap_or_default()), z = (x == 0).  The two equations admit no other z, and
+ *    another y only at x = 0, where the reference's own choice, 0, is taken: the rule is never unsolvable.  Row i + 1 defines
+ *    nothing; level(y) = level(z) = 1 + level(x).  If any clause fails, the rows fall through to rules O and R as without the
+ *    bit.  The rule is opt-in because a mul_gate on a first-seen right operand followed by a row asserting x out = 0 has the
+ *    same shape: without the bit that right operand is the caller's to supply, with it the device chooses it.
  *  - Rule O.  Otherwise, if q_o[i] != 0 and v = w_o[i] is a real variable, unseen, and different from w_l[i] and w_r[i], the
  *    row defines   v = -(q_m a b + q_l a + q_r b + q_c) / q_o.   This covers add, sub, mul, square and linear_transform
  *    (arithmetic.rs:15-104, :138-200), the three rows of conditional_select (mod.rs:318-373), bits_le (mod.rs:175-213) and
@@ -621,8 +661,8 @@ typedef struct {
     uint32_t depth;                 /* the largest level */
     uint32_t max_level_rows;        /* rows of the widest level */
     uint32_t launches;              /* launches that fill the map under the current split (the closing one not counted) */
-    uint32_t reserved;
-    uint64_t device_bytes;          /* 32 B a defined variable + 160 B a distinct coefficient tuple + 4 B a level + 192 B a
+    uint32_t reserved;              /* the number of rule-Z pairs (two variables each); 0 for every plan made without the bit */
+    uint64_t device_bytes;          /* 32 B a scheduled row + 160 B a distinct coefficient tuple + 4 B a level + 192 B a
                                      * public input + 16 B x ZKT_WITNESS_BATCH_MAX of status, each rounded up to 256 B */
 } zkt_witness_plan_report;
 typedef struct {
@@ -638,10 +678,17 @@ typedef struct {
  * is neither < n_vars nor ZKT_VARIABLE_ZERO, a position >= n, unsorted or repeated positions, NULL wiring with n_rows > 0. */
 int zkt_witness_plan_create(zkt_ctx* ctx, const uint32_t* w_l, const uint32_t* w_r, const uint32_t* w_o, size_t n_rows,
                             size_t n_vars, int wiring_on_device, const size_t* pi_pos, size_t n_pi, zkt_witness_plan** out);
+/* The same with a choice of rules: rules = 0 is zkt_witness_plan_create, bit for bit; ZKT_WITNESS_RULE_IS_ZERO adds rule Z
+ * above.  Unknown bits: ZKT_ERR_INVALID_ARGUMENT. */
+enum { ZKT_WITNESS_RULE_IS_ZERO = 1 };   /* rules */
+int zkt_witness_plan_create_ex(zkt_ctx* ctx, const uint32_t* w_l, const uint32_t* w_r, const uint32_t* w_o, size_t n_rows,
+                               size_t n_vars, int wiring_on_device, const size_t* pi_pos, size_t n_pi, uint32_t rules,
+                               zkt_witness_plan** out);
 /* Waits for ctx's stream (NULL: no wait), then frees the plan and its device memory. */
 void zkt_witness_plan_free(zkt_ctx* ctx, zkt_witness_plan* plan);
 int zkt_witness_plan_info(const zkt_witness_plan* plan, zkt_witness_plan_report* info);
-/* Per variable: 0 on no wire, 1 free, 2 defined by rule O, 3 defined by rule R.  n_vars bytes. */
+/* Per variable: 0 on no wire, 1 free, 2 defined by rule O, 3 defined by rule R, 4 rule Z's inverse y, 5 rule Z's flag z.
+ * n_vars bytes. */
 int zkt_witness_plan_kinds(const zkt_witness_plan* plan, uint8_t* out_kind);
 /* Completes `batch` witnesses in DEVICE memory: witness w is d_variables + w * stride scalars, stride >= n_vars; only the
  * defined variables are written, free ones, those on no wire and the padding up to stride stay as they are.  d_out_pi
@@ -1272,6 +1319,11 @@ int zkt_debug_wire_elimination(int curve, const uint64_t* const* selectors, cons
 int zkt_debug_witness_plan_host(int curve_id, const uint64_t* const* selectors, const uint32_t* const* wires, size_t n_rows,
                                 size_t n_vars, const size_t* pi_pos, size_t n_pi, uint8_t* out_kind, uint32_t* out_def_row,
                                 uint32_t* out_level);
+/* The same under a choice of rules (ZKT_WITNESS_RULE_IS_ZERO or 0; 0 is the call above): out_kind also holds 4 and 5, and
+ * both variables of a rule-Z pair carry the pair's first row in out_def_row. */
+int zkt_debug_witness_plan_host_ex(int curve_id, const uint64_t* const* selectors, const uint32_t* const* wires, size_t n_rows,
+                                   size_t n_vars, const size_t* pi_pos, size_t n_pi, uint32_t rules, uint8_t* out_kind,
+                                   uint32_t* out_def_row, uint32_t* out_level);
 /* Overrides the threshold between the two completion kernels for this plan: a level with at least wide_min_rows rows is a
  * launch of its own, the runs of narrower levels between such are one narrow launch each; a split of more than 64 launches
  * is one narrow launch altogether.  0 restores the policy.  zkt_witness_plan_info's `launches` follows. */

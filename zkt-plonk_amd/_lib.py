@@ -662,6 +662,16 @@ class WitnessStatus(ctypes.Structure):
 
 
 WITNESS_BATCH_MAX = 256           # ZKT_WITNESS_BATCH_MAX
+WITNESS_RULE_IS_ZERO = 1          # ZKT_WITNESS_RULE_IS_ZERO
+
+
+class WitnessBatch(ctypes.Structure):
+    """zkt_witness_batch"""
+    _fields_ = [("d_variables", ctypes.c_void_p), ("stride", ctypes.c_size_t), ("batch", ctypes.c_size_t), ("n_vars", ctypes.c_size_t),
+                ("w_l", ctypes.c_void_p), ("w_r", ctypes.c_void_p), ("w_o", ctypes.c_void_p), ("n_rows", ctypes.c_size_t),
+                ("wiring_on_device", ctypes.c_int), ("pi_pos", ctypes.POINTER(ctypes.c_size_t)), ("n_pi", ctypes.c_size_t),
+                ("d_pi_vals", ctypes.c_void_p), ("tables", ctypes.POINTER(ctypes.POINTER(ctypes.c_uint64))),
+                ("table_lens", ctypes.POINTER(ctypes.c_size_t)), ("n_tables", ctypes.c_size_t)]
 
 
 def _bind_witness(L):
@@ -679,13 +689,18 @@ def _bind_witness(L):
     L.zkt_debug_witness_plan_split.argtypes = [vp, ctypes.c_uint32]
     L.zkt_debug_witness_plan_host.argtypes = [ctypes.c_int, ctypes.POINTER(u64p_), ctypes.POINTER(u32p), sz, sz, szp, sz, u8p, u32p,
                                               u32p]
+    L.zkt_witness_plan_create_ex.argtypes = [vp, vp, vp, vp, sz, sz, ctypes.c_int, szp, sz, ctypes.c_uint32, ctypes.POINTER(vp)]
+    L.zkt_circuit_check_witness_batch.argtypes = [vp, ctypes.POINTER(WitnessBatch), ctypes.c_int, ctypes.POINTER(WitnessReport)]
+    L.zkt_debug_witness_plan_host_ex.argtypes = [ctypes.c_int, ctypes.POINTER(u64p_), ctypes.POINTER(u32p), sz, sz, szp, sz, ctypes.c_uint32,
+                                                 u8p, u32p, u32p]
 
 
-def debug_witness_plan_host(curve, selectors, w_l, w_r, w_o, n_vars: int, pi_pos=()):
+def debug_witness_plan_host(curve, selectors, w_l, w_r, w_o, n_vars: int, pi_pos=(), rules: int = 0):
     """zkt_debug_witness_plan_host: the host planner of the witness completion alone (no device).  selectors: q_m q_l q_r q_o
     q_c as (n_rows, 4) Montgomery words; w_*: n_rows uint32 indices (0xFFFFFFFF = Variable::Zero); pi_pos ascending.
-    -> (kind (n_vars,) uint8: 0 on no wire, 1 free, 2 rule O, 3 rule R; def_row (n_vars,) uint32, 0xFFFFFFFF when none;
-    level (n_vars,) uint32)."""
+    rules: WITNESS_RULE_IS_ZERO or 0 (non-zero goes through zkt_debug_witness_plan_host_ex).
+    -> (kind (n_vars,) uint8: 0 on no wire, 1 free, 2 rule O, 3 rule R, 4 / 5 rule Z's y / z; def_row (n_vars,) uint32,
+    0xFFFFFFFF when none; level (n_vars,) uint32)."""
     L = lib()
     sel = [np.ascontiguousarray(q, dtype=np.uint64).reshape(-1, 4) for q in selectors]
     w = [np.ascontiguousarray(x, dtype=np.uint32).reshape(-1) for x in (w_l, w_r, w_o)]
@@ -697,9 +712,11 @@ def debug_witness_plan_host(curve, selectors, w_l, w_r, w_o, n_vars: int, pi_pos
     wp = (P32 * 3)(*[x.ctypes.data_as(P32) for x in w])
     kind = np.zeros(max(n_vars, 1), dtype=np.uint8)
     def_row, level = np.zeros(max(n_vars, 1), dtype=np.uint32), np.zeros(max(n_vars, 1), dtype=np.uint32)
-    rc = L.zkt_debug_witness_plan_host(curve_id(curve), sp, wp, n_rows, n_vars, pi, len(pi_pos),
-                                       kind.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), def_row.ctypes.data_as(P32),
-                                       level.ctypes.data_as(P32))
+    outs = (kind.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), def_row.ctypes.data_as(P32), level.ctypes.data_as(P32))
+    if rules:
+        rc = L.zkt_debug_witness_plan_host_ex(curve_id(curve), sp, wp, n_rows, n_vars, pi, len(pi_pos), int(rules), *outs)
+    else:
+        rc = L.zkt_debug_witness_plan_host(curve_id(curve), sp, wp, n_rows, n_vars, pi, len(pi_pos), *outs)
     if rc:
         raise ZktError(rc, "zkt_debug_witness_plan_host")
     return kind[:n_vars], def_row[:n_vars], level[:n_vars]
@@ -1229,9 +1246,10 @@ class Context:
             raise ZktError(rc, "zkt_debug_merkle_tree_split: null tree or negative threshold")
 
     # -- witness completion from the free variables (csrc/witness_plan.hip) ---------------------------------
-    def witness_plan_create(self, w_l, w_r, w_o, n_vars: int, pi_pos=(), n_rows: int = None) -> int:
+    def witness_plan_create(self, w_l, w_r, w_o, n_vars: int, pi_pos=(), n_rows: int = None, rules: int = 0) -> int:
         """zkt_witness_plan_create over the loaded circuit: w_* are uint32 arrays (host) or device pointers (ints, with
-        n_rows given); pi_pos ascending -> opaque plan handle."""
+        n_rows given); pi_pos ascending -> opaque plan handle.  rules != 0 (WITNESS_RULE_IS_ZERO) goes through
+        zkt_witness_plan_create_ex."""
         vp = ctypes.c_void_p
         on_device = isinstance(w_l, int)
         if on_device:
@@ -1243,20 +1261,25 @@ class Context:
             ptrs = [vp(x.ctypes.data) if x.size else None for x in keep]
         pos = (ctypes.c_size_t * max(1, len(pi_pos)))(*[int(x) for x in pi_pos])
         plan = vp()
-        self.check(self._L.zkt_witness_plan_create(self._h, ptrs[0], ptrs[1], ptrs[2], n_rows, n_vars, int(on_device), pos,
-                                                   len(pi_pos), ctypes.byref(plan)))
+        if rules:
+            self.check(self._L.zkt_witness_plan_create_ex(self._h, ptrs[0], ptrs[1], ptrs[2], n_rows, n_vars, int(on_device), pos,
+                                                          len(pi_pos), int(rules), ctypes.byref(plan)))
+        else:
+            self.check(self._L.zkt_witness_plan_create(self._h, ptrs[0], ptrs[1], ptrs[2], n_rows, n_vars, int(on_device), pos,
+                                                       len(pi_pos), ctypes.byref(plan)))
         return plan.value
 
     def witness_plan_free(self, plan: int):
         self._L.zkt_witness_plan_free(self._h, ctypes.c_void_p(plan))
 
     def witness_plan_info(self, plan: int) -> dict:
-        """zkt_witness_plan_info -> {n_free, n_out, n_right, n_unused, depth, max_level_rows, launches, device_bytes}"""
+        """zkt_witness_plan_info -> {n_free, n_out, n_right, n_unused, depth, max_level_rows, launches, n_pairs, device_bytes};
+        n_pairs is the struct's `reserved` word, the number of rule-Z pairs (0 for a plan made without the bit)."""
         r = WitnessPlanReport()
         rc = self._L.zkt_witness_plan_info(ctypes.c_void_p(plan), ctypes.byref(r))
         if rc:
             raise ZktError(rc, "zkt_witness_plan_info: null plan")
-        return {k: int(getattr(r, k)) for k, _ in WitnessPlanReport._fields_ if k != "reserved"}
+        return {("n_pairs" if k == "reserved" else k): int(getattr(r, k)) for k, _ in WitnessPlanReport._fields_}
 
     def witness_plan_kinds(self, plan: int, n_vars: int) -> np.ndarray:
         out = np.zeros(max(n_vars, 1), dtype=np.uint8)
@@ -1746,6 +1769,36 @@ class Context:
         rep = WitnessReport()
         self.check(self._L.zkt_circuit_check_witness(self._h, ctypes.byref(prep.struct), int(flags), ctypes.byref(rep)))
         return WitnessCheck(rep)
+
+    def witness_batch(self, d_variables: int, stride: int, batch: int, n_vars: int, w_l, w_r, w_o, pi_pos=(), d_pi_vals: int = 0,
+                      tables=(), n_rows: int = None) -> "PreparedInputs":
+        """A zkt_witness_batch with the arrays it points into: `batch` maps in HBM at d_variables, `stride` scalars apart, one
+        wiring (uint32 arrays, or device pointers as ints with n_rows given), d_pi_vals (batch, n_pi) in HBM in the order of
+        pi_pos, `tables` a list of 0, 1 or `batch` host tables of (len, 4) Montgomery words."""
+        vp = ctypes.c_void_p
+        on_device = isinstance(w_l, int)
+        if on_device:
+            ptrs, keep = [x or None for x in (w_l, w_r, w_o)], []
+            assert n_rows is not None
+        else:
+            keep = [np.ascontiguousarray(x, dtype=np.uint32).reshape(-1) for x in (w_l, w_r, w_o)]
+            n_rows = len(keep[0]) if n_rows is None else n_rows
+            ptrs = [x.ctypes.data if x.size else None for x in keep]
+        pos = (ctypes.c_size_t * max(1, len(pi_pos)))(*[int(x) for x in pi_pos])
+        tabs = [np.ascontiguousarray(t, dtype=np.uint64).reshape(-1, 4) for t in tables]
+        P64 = ctypes.POINTER(ctypes.c_uint64)
+        tp = (P64 * max(1, len(tabs)))(*[u64p(t) if t.size else P64() for t in tabs])
+        tl = (ctypes.c_size_t * max(1, len(tabs)))(*[t.shape[0] for t in tabs])
+        st = WitnessBatch(d_variables or None, stride, batch, n_vars, ptrs[0], ptrs[1], ptrs[2], n_rows, int(on_device), pos, len(pi_pos),
+                          d_pi_vals or None, tp, tl, len(tabs))
+        return PreparedInputs(st, (keep, pos, tabs, tp, tl))
+
+    def check_witness_batch(self, wb: "PreparedInputs", flags: int = 0):
+        """zkt_circuit_check_witness_batch on a witness_batch(...) -> [WitnessCheck] per witness, each what check_witness
+        reports for that witness alone.  Enqueues behind the work on the context's stream, synchronises once."""
+        reps = (WitnessReport * max(1, int(wb.struct.batch)))()
+        self.check(self._L.zkt_circuit_check_witness_batch(self._h, ctypes.byref(wb.struct), int(flags), reps))
+        return [WitnessCheck(r) for r in reps[:wb.struct.batch]]
 
     def prove_dev(self, d_a: int, d_b: int, d_c: int, n_rows: int, table, pi_pos, pi_vals, blinders, transcript) -> bytes:
         """Same as prove() with the three wire vectors already resident in HBM (device pointers)."""

@@ -24,6 +24,26 @@
 // one 64-bit atomicMin and one atomicAdd per rule per workgroup into the status block.  These are minima and sums: no
 // result depends on the order of the atomics or on which workgroup runs first.  The status block is written with ordinary
 // vector stores and vector atomics only.
+//
+// The batch (zkt_circuit_check_witness_batch): `batch` variable maps under one wiring, as a completion leaves them.
+//   selector evaluations    once per call, as above
+//   k_check_gates_batch     grid (rows, tiles of CKB_TILE witnesses).  A thread loads, once per row, the five selectors,
+//                           q_lookup, the three wire indices (checked against n_vars there) and the row's public-input slot,
+//                           then walks its tile: per witness three gathers, the gate equation, and the binary search in
+//                           that witness's own sorted table (all tables are sorted on the host and uploaded end to end,
+//                           with an (offset, length) pair per witness).  Then the reduction above, per witness of the tile,
+//                           into that witness's own CK_WORDS block: one atomicAdd and one atomicMin per rule per witness
+//                           per workgroup, sums and minima, vector atomics only
+//   k_check_residual_batch  a thread per witness
+//   k_check_sigma           the shared wiring once, into witness 0's block; the host copies it into every report
+// CKB_TILE = 8.  In registers: a count and a minimum per rule per witness, 4 x CKB_TILE = 32 VGPRs, beside the 40 + 4 that
+// the row's five selectors, three indices and slot occupy across the tile (q_lookup is kept as one bit and read again by the
+// few rows that look up) and what one gate evaluation and the compiler's overlapping of the tile's gathers need: 166 by the
+// compiler's count, the last size at which three waves a SIMD fit (512 / 3 = 170); 16 would add 32 more and cost the third.
+// In bytes: a row's shared part is 6 x 32 + 3 x 4 = 204 B, read once per tile instead of once per witness, while the three
+// gathered values, 96 B a witness, cannot be shared.  A tile of T reads 204 / T + 96 B a witness and row: 300 at T = 1,
+// 121.5 at T = 8, 108.8 at T = 16, 96 at best.  T = 8 is within 27 % of the floor; doubling it again gains 10 % of the
+// traffic for a fifth more registers.
 #include "poly.hpp"
 
 #include <algorithm>
@@ -37,6 +57,7 @@ constexpr int CK_THREADS = 256;
 constexpr int CK_ROWS_PER_THREAD = 4;     // what the grid is sized for; above CK_MAX_BLOCKS workgroups the loop turns more often
 constexpr unsigned CK_MAX_BLOCKS = 2048;
 constexpr uint32_t CK_NONE32 = 0xFFFFFFFFu;
+constexpr int CKB_TILE = 8;               // witnesses a thread of k_check_gates_batch walks per row (head comment)
 // status block, 64-bit words
 enum { CK_N_ARITH = 0, CK_FIRST_ARITH, CK_N_LOOKUP, CK_FIRST_LOOKUP, CK_N_WIRING, CK_FIRST_WIRING, CK_BAD_INDEX, CK_PAD, CK_RESIDUAL,
        CK_WORDS = CK_RESIDUAL + 4 };
@@ -379,6 +400,298 @@ static int witness_check_t(zkt_ctx* c, const WitnessCheckKeys& K, const zkt_prov
 int witness_check(zkt_ctx* c, const WitnessCheckKeys& keys, const zkt_prove_inputs& in, int flags, zkt_witness_report* out) {
     return c->curve == ZKT_CURVE_BN254 ? witness_check_t<Bn254Fr>(c, keys, in, flags, out)
                                        : witness_check_t<Bls381Fr>(c, keys, in, flags, out);
+}
+
+// ---- zkt_circuit_check_witness_batch: the same rules over `batch` variable maps under one wiring ----------------------
+// (the head comment, "The batch", describes the kernels and the choice of CKB_TILE)
+struct CheckBatchArgs {
+    const void *q_m, *q_l, *q_r, *q_o, *q_c, *q_lookup;   // n evaluations each
+    const void* variables;                                // witness w = variables + w * stride
+    unsigned long long stride;
+    uint32_t batch;
+    const uint32_t *w_l, *w_r, *w_o;
+    uint32_t n, n_rows, n_vars;
+    const uint32_t* pi_pos;                               // ascending
+    const uint32_t* pi_slot;                              // the caller's index of each sorted position
+    const void* pi_vals;                                  // batch x n_pi, the caller's order
+    uint32_t n_pi;
+    const void* tables;                                   // every witness's sorted table, concatenated
+    const unsigned long long* tab;                        // per witness: offset into `tables`, length
+    unsigned long long* status;                           // CK_WORDS per witness
+};
+
+// what a row holds for every witness alike
+template <class P>
+struct CkbRow {
+    Fe<P> q[5];
+    bool looks;         // q_lookup != 0; the value itself is read again where a witness needs it: such rows are few
+    uint32_t w[3];      // CK_NONE32: the wire is zero (Variable::Zero, a padded row, an index outside the map)
+    uint32_t slot;      // its public input's index within a witness's n_pi values, CK_NONE32 when it has none
+};
+
+template <class P>
+ZKT_D void ckb_row_load(const CheckBatchArgs& q, uint32_t i, CkbRow<P>& r) {
+    const Fe<P>* const sel[5] = {(const Fe<P>*)q.q_m, (const Fe<P>*)q.q_l, (const Fe<P>*)q.q_r, (const Fe<P>*)q.q_o, (const Fe<P>*)q.q_c};
+#pragma unroll
+    for (int k = 0; k < 5; ++k) r.q[k] = fe_load<P>(sel[k] + i);
+    r.looks = !fe_is_zero<P>(fe_load<P>((const Fe<P>*)q.q_lookup + i));
+    const uint32_t* const idx[3] = {q.w_l, q.w_r, q.w_o};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        uint32_t v = CK_NONE32;
+        if (i < q.n_rows) {
+            v = idx[k][i];
+            if (v != ZKT_VARIABLE_ZERO && v >= q.n_vars) {   // reported as ZKT_ERR_INVALID_ARGUMENT; read as Variable::Zero
+                atomicOr(q.status + CK_BAD_INDEX, 1ull);
+                v = CK_NONE32;
+            }
+        }
+        r.w[k] = v;
+    }
+    uint32_t lo = 0, hi = q.n_pi;                   // the first position >= i
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (q.pi_pos[mid] < i) lo = mid + 1;
+        else hi = mid;
+    }
+    r.slot = lo < q.n_pi && q.pi_pos[lo] == i ? q.pi_slot[lo] : CK_NONE32;
+}
+
+// the gate equation of row r on witness w and the wire value the lookup reads; canonical
+template <class P>
+ZKT_D Fe<P> ckb_gate(const CheckBatchArgs& q, const CkbRow<P>& r, uint32_t w, Fe<P>& c) {
+    const Fe<P>* const x = (const Fe<P>*)q.variables + (unsigned long long)w * q.stride;
+    const Fe<P> a = r.w[0] == CK_NONE32 ? fe_zero<P>() : fe_load<P>(x + r.w[0]);
+    const Fe<P> b = r.w[1] == CK_NONE32 ? fe_zero<P>() : fe_load<P>(x + r.w[1]);
+    c = r.w[2] == CK_NONE32 ? fe_zero<P>() : fe_load<P>(x + r.w[2]);
+    Fe<P> t = fe_add<P>(fe_mul<P>(r.q[0], b), r.q[1]);
+    t = fe_mul<P>(t, a);
+    t = fe_add<P>(t, fe_mul<P>(r.q[2], b));
+    t = fe_add<P>(t, fe_mul<P>(r.q[3], c));
+    t = fe_add<P>(t, r.q[4]);
+    if (r.slot != CK_NONE32) t = fe_add<P>(t, fe_load<P>((const Fe<P>*)q.pi_vals + (unsigned long long)w * q.n_pi + r.slot));
+    return t;
+}
+
+template <class P>
+__global__ __launch_bounds__(CK_THREADS) void k_check_gates_batch(CheckBatchArgs q) {
+    __shared__ uint32_t sh_cnt[CK_THREADS / 64], sh_min[CK_THREADS / 64];
+    uint32_t n_arith[CKB_TILE], first_arith[CKB_TILE], n_lookup[CKB_TILE], first_lookup[CKB_TILE];
+#pragma unroll
+    for (int t = 0; t < CKB_TILE; ++t) {
+        n_arith[t] = n_lookup[t] = 0;
+        first_arith[t] = first_lookup[t] = CK_NONE32;
+    }
+    const uint32_t w0 = blockIdx.y * CKB_TILE;      // this workgroup's witnesses: w0 .. w0 + CKB_TILE, below batch
+    const uint32_t stride = gridDim.x * CK_THREADS;
+#pragma unroll 1
+    for (uint32_t i = blockIdx.x * CK_THREADS + threadIdx.x; i < q.n; i += stride) {   // n <= 2^25: no wrap
+        CkbRow<P> r;
+        ckb_row_load<P>(q, i, r);
+#pragma unroll
+        for (int t = 0; t < CKB_TILE; ++t) {
+            const uint32_t w = w0 + t;
+            if (w >= q.batch) continue;
+            Fe<P> c;
+            if (!fe_is_zero<P>(ckb_gate<P>(q, r, w, c))) {
+                ++n_arith[t];
+                first_arith[t] = i < first_arith[t] ? i : first_arith[t];
+            }
+            if (!r.looks) continue;
+            const Fe<P> f = fe_mul<P>(fe_load<P>((const Fe<P>*)q.q_lookup + i), c);
+            if (fe_is_zero<P>(f)) continue;
+            const Fe<P>* const tab = (const Fe<P>*)q.tables + q.tab[2 * w];
+            const uint32_t len = (uint32_t)q.tab[2 * w + 1];
+            uint32_t lo = 0, hi = len;
+            while (lo < hi) {
+                const uint32_t mid = lo + (hi - lo) / 2;
+                if (ck_cmp<P>(fe_load<P>(tab + mid), f) < 0) lo = mid + 1;
+                else hi = mid;
+            }
+            if (lo >= len || ck_cmp<P>(fe_load<P>(tab + lo), f) != 0) {
+                ++n_lookup[t];
+                first_lookup[t] = i < first_lookup[t] ? i : first_lookup[t];
+            }
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < CKB_TILE; ++t) {
+        if (w0 + t >= q.batch) break;               // uniform over the workgroup
+        unsigned long long* const st = q.status + (size_t)(w0 + t) * CK_WORDS;
+        ck_block_reduce(n_arith[t], first_arith[t], st + CK_N_ARITH, st + CK_FIRST_ARITH, sh_cnt, sh_min);
+        ck_block_reduce(n_lookup[t], first_lookup[t], st + CK_N_LOOKUP, st + CK_FIRST_LOOKUP, sh_cnt, sh_min);
+    }
+}
+
+// after k_check_gates_batch on the same stream, a thread per witness: the equation's value at its first failing row
+template <class P>
+__global__ __launch_bounds__(64) void k_check_residual_batch(CheckBatchArgs q) {
+    const uint32_t w = blockIdx.x * 64 + threadIdx.x;
+    if (w >= q.batch) return;
+    unsigned long long* const st = q.status + (size_t)w * CK_WORDS;
+    const unsigned long long first = st[CK_FIRST_ARITH];
+    if (first >= q.n) return;                       // none: the residual words stay 0
+    CkbRow<P> r;
+    ckb_row_load<P>(q, (uint32_t)first, r);
+    Fe<P> c;
+    const Fe<P> t = ckb_gate<P>(q, r, w, c);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) st[CK_RESIDUAL + k] = (unsigned long long)t.v[2 * k] | ((unsigned long long)t.v[2 * k + 1] << 32);
+}
+
+template <class P>
+static int witness_check_batch_t(zkt_ctx* c, const WitnessCheckKeys& K, const zkt_witness_batch& in, int flags, zkt_witness_report* out) {
+    using F = Fe<P>;
+    const int log_n = K.log_n;
+    const size_t n = (size_t)1 << log_n;
+    const bool wiring = (flags & ZKT_CHECK_WIRING) != 0;
+    const bool on_device = in.wiring_on_device != 0;
+    const size_t rows = in.n_rows, n_pi = in.n_pi, batch = in.batch;
+
+    // ---- host side: every table sorted by the kernel's order and laid end to end, the public-input positions by row ----
+    std::vector<F> sorted;
+    std::vector<unsigned long long> tab(2 * batch, 0);
+    for (size_t k = 0; k < in.n_tables; ++k) {
+        const size_t tl = in.table_lens[k], at0 = sorted.size();
+        const F* t = reinterpret_cast<const F*>(in.tables[k]);
+        std::vector<uint32_t> order(tl);
+        std::iota(order.begin(), order.end(), 0u);
+        std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return ck_cmp<P>(t[x], t[y]) < 0; });
+        for (size_t i = 0; i < tl; ++i) sorted.push_back(t[order[i]]);
+        for (size_t i = 1; i < tl; ++i)
+            if (ck_cmp<P>(sorted[at0 + i - 1], sorted[at0 + i]) == 0)
+                return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "lookup table holds a repeated value");
+        for (size_t w = in.n_tables == 1 ? 0 : k; w < (in.n_tables == 1 ? batch : k + 1); ++w) {
+            tab[2 * w] = at0;
+            tab[2 * w + 1] = tl;
+        }
+    }
+    std::vector<uint32_t> pos(n_pi), slot(n_pi);
+    if (n_pi) {
+        std::iota(slot.begin(), slot.end(), 0u);
+        std::stable_sort(slot.begin(), slot.end(), [&](uint32_t x, uint32_t y) { return in.pi_pos[x] < in.pi_pos[y]; });
+        for (size_t i = 0; i < n_pi; ++i) pos[i] = (uint32_t)in.pi_pos[slot[i]];
+    }
+
+    // ---- the call's scratch, one block carved on 256-byte boundaries ----
+    size_t at = 0;
+    auto take = [&](size_t bytes) {
+        const size_t here = at;
+        at += (bytes + 255) / 256 * 256;
+        return here;
+    };
+    const size_t status_bytes = batch * CK_WORDS * 8;
+    const size_t o_status = take(status_bytes);
+    size_t o_sel[5];
+    for (size_t& o : o_sel) o = take(n * 32);
+    const size_t o_pos = take(n_pi * 4), o_slot = take(n_pi * 4), o_table = take(sorted.size() * 32), o_tab = take(tab.size() * 8);
+    size_t o_idx[3] = {};
+    if (!on_device)
+        for (size_t& o : o_idx) o = take(rows * 4);
+    size_t o_made[3] = {}, o_sigma = 0;
+    if (wiring) {
+        for (size_t& o : o_made) o = take(n * 32);
+        o_sigma = take(sigma_scratch_bytes(log_n, rows));
+    }
+    int rc = grow(c, c->check_scratch, at);
+    if (rc) return rc;
+    char* const base = (char*)c->check_scratch.p;
+    unsigned long long* const d_status = (unsigned long long*)(base + o_status);
+
+    std::vector<unsigned long long> h_status(batch * CK_WORDS, 0);
+    struct Drain {   // an early return must not leave copies from this frame's host staging in flight
+        zkt_ctx* c;
+        bool done = false;
+        ~Drain() {
+            if (!done) (void)hipStreamSynchronize(c->stream);
+        }
+    } drain{c};
+    for (size_t w = 0; w < batch; ++w) {
+        unsigned long long* const st = h_status.data() + w * CK_WORDS;
+        st[CK_FIRST_ARITH] = st[CK_FIRST_LOOKUP] = st[CK_FIRST_WIRING] = ~0ull;
+    }
+    ZKT_HIP(c, hipMemcpyAsync(d_status, h_status.data(), status_bytes, hipMemcpyHostToDevice, c->stream));
+    if (n_pi) {
+        ZKT_HIP(c, hipMemcpyAsync(base + o_pos, pos.data(), n_pi * 4, hipMemcpyHostToDevice, c->stream));
+        ZKT_HIP(c, hipMemcpyAsync(base + o_slot, slot.data(), n_pi * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    if (!sorted.empty()) ZKT_HIP(c, hipMemcpyAsync(base + o_table, sorted.data(), sorted.size() * 32, hipMemcpyHostToDevice, c->stream));
+    ZKT_HIP(c, hipMemcpyAsync(base + o_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c->stream));
+
+    CheckBatchArgs q{};
+    q.variables = in.d_variables;
+    q.stride = in.stride;
+    q.batch = (uint32_t)batch;
+    q.w_l = in.w_l; q.w_r = in.w_r; q.w_o = in.w_o;
+    if (!on_device) {   // a host wiring travels inside the call
+        const uint32_t* src[3] = {in.w_l, in.w_r, in.w_o};
+        const uint32_t** dst[3] = {&q.w_l, &q.w_r, &q.w_o};
+        for (int k = 0; k < 3; ++k) {
+            if (rows) ZKT_HIP(c, hipMemcpyAsync(base + o_idx[k], src[k], rows * 4, hipMemcpyHostToDevice, c->stream));
+            *dst[k] = (const uint32_t*)(base + o_idx[k]);
+        }
+    }
+    q.q_m = base + o_sel[0]; q.q_l = base + o_sel[1]; q.q_r = base + o_sel[2]; q.q_o = base + o_sel[3]; q.q_c = base + o_sel[4];
+    q.q_lookup = K.q_lookup_ev;
+    q.n = (uint32_t)n; q.n_rows = (uint32_t)rows; q.n_vars = (uint32_t)in.n_vars;
+    q.pi_pos = (const uint32_t*)(base + o_pos); q.pi_slot = (const uint32_t*)(base + o_slot); q.pi_vals = in.d_pi_vals;
+    q.n_pi = (uint32_t)n_pi;
+    q.tables = base + o_table;
+    q.tab = (const unsigned long long*)(base + o_tab);
+    q.status = d_status;
+
+    {
+        ProfScope prof(c, "check_witness_batch");
+        void* outs[5];
+        for (int k = 0; k < 5; ++k) outs[k] = base + o_sel[k];
+        if ((rc = selector_evals_enqueue(c, log_n, K.pk, outs))) return rc;
+        const unsigned tiles = (unsigned)((batch + CKB_TILE - 1) / CKB_TILE);
+        hipLaunchKernelGGL(k_check_gates_batch<P>, dim3(ck_blocks(n), tiles), dim3(CK_THREADS), 0, c->stream, q);
+        hipLaunchKernelGGL(k_check_residual_batch<P>, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, c->stream, q);
+        ZKT_HIP(c, hipGetLastError());
+        if (wiring) {   // the shared wiring, once, into witness 0's block
+            void* made[3] = {base + o_made[0], base + o_made[1], base + o_made[2]};
+            if ((rc = sigma_enqueue(c, log_n, q.w_l, q.w_r, q.w_o, rows, in.n_vars, made, base + o_sigma,
+                                    (uint32_t*)(d_status + CK_BAD_INDEX))))
+                return rc;
+            hipLaunchKernelGGL(k_check_sigma<P>, dim3(ck_blocks(n)), dim3(CK_THREADS), 0, c->stream, (const F*)made[0], (const F*)made[1],
+                               (const F*)made[2], (const F*)K.sigma_ev[0], (const F*)K.sigma_ev[1], (const F*)K.sigma_ev[2], (uint32_t)n,
+                               d_status);
+            ZKT_HIP(c, hipGetLastError());
+        }
+    }
+    ZKT_HIP(c, hipMemcpyAsync(h_status.data(), d_status, status_bytes, hipMemcpyDeviceToHost, c->stream));
+    ZKT_HIP(c, hipStreamSynchronize(c->stream));
+    drain.done = true;
+    if (h_status[CK_BAD_INDEX])
+        return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "wire index outside the variable map: every entry must be < n_vars or ZKT_VARIABLE_ZERO");
+
+    for (size_t w = 0; w < batch; ++w) {
+        const unsigned long long* const st = h_status.data() + w * CK_WORDS;
+        zkt_witness_report r;
+        memset(&r, 0, sizeof(r));   // padding too: equal results are equal bytes
+        r.checked = 3 | (wiring ? 4 : 0);
+        r.n_arithmetic = st[CK_N_ARITH];
+        r.first_arithmetic = st[CK_FIRST_ARITH];
+        for (int k = 0; k < 4; ++k) r.residual[k] = st[CK_RESIDUAL + k];
+        r.n_lookup = st[CK_N_LOOKUP];
+        r.first_lookup = st[CK_FIRST_LOOKUP];
+        r.n_wiring = h_status[CK_N_WIRING];          // the wiring is the batch's: witness 0's block holds it
+        r.first_wiring_row = ZKT_CHECK_NONE;
+        r.first_wiring_column = -1;
+        if (h_status[CK_FIRST_WIRING] != ~0ull) {
+            r.first_wiring_row = h_status[CK_FIRST_WIRING] / 3;
+            r.first_wiring_column = (int)(h_status[CK_FIRST_WIRING] % 3);
+        }
+        r.satisfied = !r.n_arithmetic && !r.n_lookup && !r.n_wiring;
+        memcpy(out + w, &r, sizeof(r));
+    }
+    return ZKT_OK;
+}
+
+int witness_check_batch(zkt_ctx* c, const WitnessCheckKeys& keys, const zkt_witness_batch& in, int flags, zkt_witness_report* out) {
+    return c->curve == ZKT_CURVE_BN254 ? witness_check_batch_t<Bn254Fr>(c, keys, in, flags, out)
+                                       : witness_check_batch_t<Bls381Fr>(c, keys, in, flags, out);
 }
 
 }  // namespace zkt

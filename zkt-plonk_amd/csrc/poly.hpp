@@ -178,13 +178,17 @@ struct WitnessCheckKeys {
 int selector_evals_enqueue(zkt_ctx* c, int log_n, const void* const* pk, void* const* outs);
 int witness_check(zkt_ctx* c, const WitnessCheckKeys& keys, const zkt_prove_inputs& in, int flags, zkt_witness_report* out);
 // witness_plan.hip: zkt_witness_plan_create on the loaded circuit's selectors (pk as in WitnessCheckKeys).  Validates its
-// arguments, synchronises, *out is written only on ZKT_OK.
+// arguments (rules: ZKT_WITNESS_RULE_* bits), synchronises, *out is written only on ZKT_OK.
 struct WitnessPlanKeys {
     int log_n;
     const void* pk[5];
 };
 int witness_plan_create(zkt_ctx* c, const WitnessPlanKeys& keys, const uint32_t* w_l, const uint32_t* w_r, const uint32_t* w_o,
-                        size_t n_rows, size_t n_vars, int wiring_on_device, const size_t* pi_pos, size_t n_pi, zkt_witness_plan** out);
+                        size_t n_rows, size_t n_vars, int wiring_on_device, const size_t* pi_pos, size_t n_pi, uint32_t rules,
+                        zkt_witness_plan** out);
+// check.hip: zkt_circuit_check_witness_batch on the loaded circuit's keys; `in` and `flags` validated by the caller except for
+// what needs the data.  out[0 .. batch) is written only on ZKT_OK.
+int witness_check_batch(zkt_ctx* c, const WitnessCheckKeys& keys, const zkt_witness_batch& in, int flags, zkt_witness_report* out);
 // table generation
 int gen_powers(zkt_ctx* c, void* out, size_t n, const uint32_t base[8], const uint32_t scale[8]);
 // Plookup sorted halves h1/h2 (lookup/multiset.rs:103-146)

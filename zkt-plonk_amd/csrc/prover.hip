@@ -2145,8 +2145,8 @@ int zkt_circuit_check_witness(zkt_ctx* c, const zkt_prove_inputs* in, int flags,
 
 // The plan of a witness completion over the loaded circuit's selectors (witness_plan.hip).  Reads the loaded keys, writes
 // nothing of the circuit state; the plan keeps no pointer into it.
-int zkt_witness_plan_create(zkt_ctx* c, const uint32_t* w_l, const uint32_t* w_r, const uint32_t* w_o, size_t n_rows, size_t n_vars,
-                            int wiring_on_device, const size_t* pi_pos, size_t n_pi, zkt_witness_plan** out) {
+int zkt_witness_plan_create_ex(zkt_ctx* c, const uint32_t* w_l, const uint32_t* w_r, const uint32_t* w_o, size_t n_rows, size_t n_vars,
+                               int wiring_on_device, const size_t* pi_pos, size_t n_pi, uint32_t rules, zkt_witness_plan** out) {
     if (!c) return ZKT_ERR_INVALID_ARGUMENT;
     if (!out) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
     if (!c->circuit) return set_err(c, ZKT_ERR_NOT_LOADED, "no circuit loaded (zkt_circuit_load)");
@@ -2154,7 +2154,48 @@ int zkt_witness_plan_create(zkt_ctx* c, const uint32_t* w_l, const uint32_t* w_r
     WitnessPlanKeys keys{};
     keys.log_n = S.log_n;
     for (int k = 0; k < 5; ++k) keys.pk[k] = S.pk[PK_QM + k];   // PK_QM .. PK_QC
-    return witness_plan_create(c, keys, w_l, w_r, w_o, n_rows, n_vars, wiring_on_device, pi_pos, n_pi, out);
+    return witness_plan_create(c, keys, w_l, w_r, w_o, n_rows, n_vars, wiring_on_device, pi_pos, n_pi, rules, out);
+}
+
+int zkt_witness_plan_create(zkt_ctx* c, const uint32_t* w_l, const uint32_t* w_r, const uint32_t* w_o, size_t n_rows, size_t n_vars,
+                            int wiring_on_device, const size_t* pi_pos, size_t n_pi, zkt_witness_plan** out) {
+    return zkt_witness_plan_create_ex(c, w_l, w_r, w_o, n_rows, n_vars, wiring_on_device, pi_pos, n_pi, 0, out);
+}
+
+// The single check's rules over a batch of completed maps under one wiring (check.hip).  Reads the loaded keys, writes
+// nothing of the circuit state, as zkt_circuit_check_witness.
+int zkt_circuit_check_witness_batch(zkt_ctx* c, const zkt_witness_batch* in, int flags, zkt_witness_report* out) {
+    if (!c) return ZKT_ERR_INVALID_ARGUMENT;
+    if (!in || !out) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
+    if (!c->circuit) return set_err(c, ZKT_ERR_NOT_LOADED, "no circuit loaded (zkt_circuit_load)");
+    if (flags & ~ZKT_CHECK_WIRING) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "unknown flag bits");
+    const CircuitState& S = *c->circuit;
+    const size_t n = S.n;
+    if (in->batch < 1 || in->batch > ZKT_WITNESS_BATCH_MAX) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "1 <= batch <= ZKT_WITNESS_BATCH_MAX");
+    if (in->stride < in->n_vars) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "stride below n_vars");
+    if (in->n_tables != 0 && in->n_tables != 1 && in->n_tables != in->batch)
+        return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "n_tables must be 0, 1 or batch");
+    if (in->n_tables && (!in->tables || !in->table_lens)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null lookup tables");
+    if (in->n_rows > n) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "more rows than the circuit bound");
+    for (size_t t = 0; t < in->n_tables; ++t) {
+        if (in->table_lens[t] >= n) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "max table size is equal or larger than n");
+        if (in->table_lens[t] && !in->tables[t]) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null lookup table");
+    }
+    if (in->n_pi && (!in->pi_pos || !in->d_pi_vals)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null public inputs");
+    for (size_t i = 0; i < in->n_pi; ++i)
+        if (in->pi_pos[i] >= n) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "public input position out of range");
+    if (in->n_rows && (!in->w_l || !in->w_r || !in->w_o)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null wire index vector");
+    if (in->n_vars && !in->d_variables) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null variable map");
+    if (in->n_vars > 0xFFFFFFFEull) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "too many variables");
+    if ((flags & ZKT_CHECK_WIRING) && S.log_n > 25)
+        return set_err(c, ZKT_ERR_INVALID_DOMAIN_SIZE, "InvalidEvalDomainSize: the wiring's positions are 32-bit (log_n <= 25)");
+    (void)hipSetDevice(c->device);
+    WitnessCheckKeys keys{};
+    keys.log_n = S.log_n;
+    for (int k = 0; k < 5; ++k) keys.pk[k] = S.pk[PK_QM + k];   // PK_QM .. PK_QC
+    keys.q_lookup_ev = S.q_lookup_ev;
+    for (int k = 0; k < 3; ++k) keys.sigma_ev[k] = S.sigma_ev[k];
+    return witness_check_batch(c, keys, *in, flags, out);
 }
 
 // Test hook: the fused quotient pass on its own (quotient_poly.rs:98-224) over the loaded circuit's key cosets and

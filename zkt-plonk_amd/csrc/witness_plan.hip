@@ -11,7 +11,8 @@
 //
 // Arithmetic: canonical Montgomery words from end to end (fe_add / fe_sub / fe_neg of fp.hpp, fe_mul through fx.hpp), as the
 // prover requires its witness.  Rule R inverts with fe_inv, the Fermat ladder the kernels use; a circuit has a handful of
-// such rows, and the threads of their level wait for them.
+// such rows, and the threads of their level wait for them.  Rule Z (a pair's record) decides x = 0 on the canonical words,
+// inverts with the same ladder when x != 0, and stores its two values with plain vector stores; it writes no status.
 // Status block: per witness two 64-bit words, the number of rule-R rows with a zero denominator (atomicAdd) and
 // 2^32 - their smallest row (atomicMax, 0 = none, so that clearing is a memset): a sum and a maximum, independent of the
 // order of the atomics; vector atomics only.  Such rows are rare, so every thread that meets one reports it itself.
@@ -62,6 +63,23 @@ ZKT_D void wp_const(Fe<P>& acc, uint32_t flag, const Fe<P>* t) {
     else if (flag == WP_GEN) acc = fe_add<P>(acc, fe_load<P>(t));
 }
 
+// rule Z's record: x = 0: y = 0, z = t_o; else z = 0, y = t_m / x.  Not inlined, as wp_inv: a circuit has few such records,
+// and the registers of k_wp_narrow stay those of rules O and R.  The record's words travel by value: a reference would pin the
+// caller's copy of every record, rule O's too, to scratch
+template <class P>
+__device__ __attribute__((noinline)) void wp_pair(uint32_t in0, uint32_t out, uint32_t out2, uint32_t flags, const Fe<P>* t, Fe<P>* x) {
+    const uint32_t fm = wp_flag(flags, WP_M), fo = wp_flag(flags, WP_O);
+    Fe<P> a = fe_zero<P>(), y = fe_zero<P>(), z = fe_zero<P>();
+    if (wp_flag(flags, WP_L) != WP_ZERO) a = fe_load<P>(x + in0);
+    if (fe_is_zero<P>(a)) {     // canonical words: zero is all-zero words
+        wp_const<P>(z, fo, t + WP_O);
+    } else if (fm != WP_ZERO) {
+        wp_term<P>(y, fm, t + WP_M, wp_inv<P>(a));
+    }
+    fe_store<P>(x + out, y);
+    fe_store<P>(x + out2, z);
+}
+
 // one scheduled row of witness `wit` (x = its map): every index was checked against n_vars when the plan was made
 template <class P>
 ZKT_D void wp_row(const WpArgs<P>& q, uint32_t k, Fe<P>* x, uint32_t wit) {
@@ -70,7 +88,7 @@ ZKT_D void wp_row(const WpArgs<P>& q, uint32_t k, Fe<P>* x, uint32_t wit) {
     const uint32_t fm = wp_flag(r.flags, WP_M), fl = wp_flag(r.flags, WP_L), fr = wp_flag(r.flags, WP_R), fo = wp_flag(r.flags, WP_O),
                    fc = wp_flag(r.flags, WP_C);
     Fe<P> v = fe_zero<P>();
-    if (!(r.flags & WP_RULE_R)) {   // v = t_m a b + t_l a + t_r b + t_c
+    if (!(r.flags & (WP_RULE_R | WP_RULE_Z))) {   // v = t_m a b + t_l a + t_r b + t_c (one test in front of rule O, as ever)
         Fe<P> a = fe_zero<P>(), b = fe_zero<P>();
         if (fm != WP_ZERO || fl != WP_ZERO) a = fe_load<P>(x + r.in0);
         if (fm != WP_ZERO || fr != WP_ZERO) b = fe_load<P>(x + r.in1);
@@ -78,6 +96,9 @@ ZKT_D void wp_row(const WpArgs<P>& q, uint32_t k, Fe<P>* x, uint32_t wit) {
         if (fm != WP_ZERO) wp_term<P>(v, fm, t + WP_M, fe_mul<P>(a, b));
         wp_term<P>(v, fl, t + WP_L, a);
         wp_term<P>(v, fr, t + WP_R, b);
+    } else if (r.flags & WP_RULE_Z) {
+        wp_pair<P>(r.in0, r.out, r.out2, r.flags, t, x);
+        return;
     } else {                        // v = (t_l a + t_o c + t_c) / (t_m a + t_r)
         Fe<P> a = fe_zero<P>(), c = fe_zero<P>(), den = fe_zero<P>();
         if (fm != WP_ZERO || fl != WP_ZERO) a = fe_load<P>(x + r.in0);
@@ -142,7 +163,7 @@ struct zkt_witness_plan {
     std::vector<uint8_t> kind;
     std::vector<uint32_t> level_start;
     uint32_t depth = 0, max_level_rows = 0;
-    uint64_t n_free = 0, n_out = 0, n_right = 0, n_unused = 0, device_bytes = 0;
+    uint64_t n_free = 0, n_out = 0, n_right = 0, n_unused = 0, n_pairs = 0, device_bytes = 0;
     std::vector<zkt::WpLaunch> launches;
     zkt::DevSet mem;                       // everything the plan holds on the device: freed with the plan
     void *d_rows = nullptr, *d_tuples = nullptr, *d_level_start = nullptr, *d_public = nullptr, *d_status = nullptr;
@@ -155,7 +176,7 @@ static size_t wp_round(size_t bytes) { return (std::max<size_t>(bytes, 1) + 255)
 
 template <class P>
 static int plan_create_t(zkt_ctx* c, const WitnessPlanKeys& K, const uint32_t* const* w, size_t n_rows, size_t n_vars,
-                         const size_t* pi_pos, size_t n_pi, zkt_witness_plan* pl) {
+                         const size_t* pi_pos, size_t n_pi, uint32_t rules, zkt_witness_plan* pl) {
     using F = Fe<P>;
     static_assert(sizeof(F) == 32 && sizeof(WpTuple<P>) == 160 && sizeof(WpPublic<P>) == 192, "layouts of witness_plan.hpp");
     const size_t n = (size_t)1 << K.log_n;
@@ -178,7 +199,7 @@ static int plan_create_t(zkt_ctx* c, const WitnessPlanKeys& K, const uint32_t* c
     for (int k = 0; k < 5; ++k) selp[k] = sel[k].data();
 
     WitnessPlan<P> W;
-    witness_plan_make<P>(selp, w, n_rows, n_vars, pi_pos, n_pi, W);
+    witness_plan_make<P>(selp, w, n_rows, n_vars, pi_pos, n_pi, W, rules);
     std::vector<WpPublic<P>> pub(n_pi);
     for (size_t j = 0; j < n_pi; ++j) {
         const size_t i = pi_pos[j];
@@ -195,6 +216,7 @@ static int plan_create_t(zkt_ctx* c, const WitnessPlanKeys& K, const uint32_t* c
     pl->depth = W.depth;
     pl->max_level_rows = W.max_level_rows;
     pl->n_free = W.n_free; pl->n_out = W.n_out; pl->n_right = W.n_right; pl->n_unused = W.n_unused;
+    pl->n_pairs = W.n_pairs;
     pl->launches = witness_plan_split(pl->level_start, pl->depth, WP_WIDE_MIN_ROWS);
 
     struct Part {
@@ -218,8 +240,10 @@ static int plan_create_t(zkt_ctx* c, const WitnessPlanKeys& K, const uint32_t* c
 }
 
 int witness_plan_create(zkt_ctx* c, const WitnessPlanKeys& K, const uint32_t* w_l, const uint32_t* w_r, const uint32_t* w_o,
-                        size_t n_rows, size_t n_vars, int wiring_on_device, const size_t* pi_pos, size_t n_pi, zkt_witness_plan** out) {
+                        size_t n_rows, size_t n_vars, int wiring_on_device, const size_t* pi_pos, size_t n_pi, uint32_t rules,
+                        zkt_witness_plan** out) {
     const size_t n = (size_t)1 << K.log_n;
+    if (rules & ~(uint32_t)ZKT_WITNESS_RULE_IS_ZERO) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "unknown rule bits");
     if (n_rows > n) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "more rows than the circuit bound");
     if (n_rows && (!w_l || !w_r || !w_o)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null wire index vector");
     if (n_pi && !pi_pos) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null public-input positions");
@@ -245,8 +269,8 @@ int witness_plan_create(zkt_ctx* c, const WitnessPlanKeys& K, const uint32_t* w_
             if (w[k][i] != ZKT_VARIABLE_ZERO && w[k][i] >= n_vars)
                 return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "wire index outside the variable map: every entry must be < n_vars or ZKT_VARIABLE_ZERO");
     zkt_witness_plan* pl = new zkt_witness_plan(c->device);
-    const int rc = c->curve == ZKT_CURVE_BN254 ? plan_create_t<Bn254Fr>(c, K, w, n_rows, n_vars, pi_pos, n_pi, pl)
-                                                : plan_create_t<Bls381Fr>(c, K, w, n_rows, n_vars, pi_pos, n_pi, pl);
+    const int rc = c->curve == ZKT_CURVE_BN254 ? plan_create_t<Bn254Fr>(c, K, w, n_rows, n_vars, pi_pos, n_pi, rules, pl)
+                                                : plan_create_t<Bls381Fr>(c, K, w, n_rows, n_vars, pi_pos, n_pi, rules, pl);
     if (rc) {
         (void)hipStreamSynchronize(c->stream);
         delete pl;
@@ -298,11 +322,11 @@ static int complete_check(zkt_ctx* c, const zkt_witness_plan* pl, const void* va
 // zkt_debug_witness_plan_host: the host planner alone, on caller-supplied selectors and wiring (no device, no context)
 template <class R>
 static int debug_plan_host_t(const uint64_t* const* selectors, const uint32_t* const* w, size_t n_rows, size_t n_vars, const size_t* pi_pos,
-                             size_t n_pi, uint8_t* out_kind, uint32_t* out_def_row, uint32_t* out_level) {
+                             size_t n_pi, uint32_t rules, uint8_t* out_kind, uint32_t* out_def_row, uint32_t* out_level) {
     const Fe<R>* sel[5];
     for (int k = 0; k < 5; ++k) sel[k] = reinterpret_cast<const Fe<R>*>(selectors[k]);
     WitnessPlan<R> W;
-    witness_plan_make<R>(sel, w, n_rows, n_vars, pi_pos, n_pi, W);
+    witness_plan_make<R>(sel, w, n_rows, n_vars, pi_pos, n_pi, W, rules);
     if (n_vars) {
         memcpy(out_kind, W.kind.data(), n_vars);
         memcpy(out_def_row, W.def_row.data(), n_vars * 4);
@@ -333,6 +357,7 @@ int zkt_witness_plan_info(const zkt_witness_plan* pl, zkt_witness_plan_report* i
     info->depth = pl->depth;
     info->max_level_rows = pl->max_level_rows;
     info->launches = (uint32_t)pl->launches.size();
+    info->reserved = (uint32_t)pl->n_pairs;
     info->device_bytes = pl->device_bytes;
     return ZKT_OK;
 }
@@ -396,8 +421,10 @@ int zkt_witness_complete(zkt_ctx* c, const zkt_witness_plan* pl, uint64_t* varia
     return rc;
 }
 
-int zkt_debug_witness_plan_host(int curve, const uint64_t* const* selectors, const uint32_t* const* wires, size_t n_rows, size_t n_vars,
-                                const size_t* pi_pos, size_t n_pi, uint8_t* out_kind, uint32_t* out_def_row, uint32_t* out_level) {
+int zkt_debug_witness_plan_host_ex(int curve, const uint64_t* const* selectors, const uint32_t* const* wires, size_t n_rows, size_t n_vars,
+                                   const size_t* pi_pos, size_t n_pi, uint32_t rules, uint8_t* out_kind, uint32_t* out_def_row,
+                                   uint32_t* out_level) {
+    if (rules & ~(uint32_t)ZKT_WITNESS_RULE_IS_ZERO) return ZKT_ERR_INVALID_ARGUMENT;
     if (!selectors || !wires || (n_vars && (!out_kind || !out_def_row || !out_level)) || (n_pi && !pi_pos)) return ZKT_ERR_INVALID_ARGUMENT;
     if (n_vars > 0xFFFFFFFEull) return ZKT_ERR_INVALID_ARGUMENT;
     for (int k = 0; k < 5; ++k)
@@ -406,10 +433,15 @@ int zkt_debug_witness_plan_host(int curve, const uint64_t* const* selectors, con
         if (n_rows && !wires[k]) return ZKT_ERR_INVALID_ARGUMENT;
     for (size_t j = 1; j < n_pi; ++j)
         if (pi_pos[j] <= pi_pos[j - 1]) return ZKT_ERR_INVALID_ARGUMENT;
-    if (curve == ZKT_CURVE_BN254) return debug_plan_host_t<Bn254Fr>(selectors, wires, n_rows, n_vars, pi_pos, n_pi, out_kind, out_def_row, out_level);
+    if (curve == ZKT_CURVE_BN254) return debug_plan_host_t<Bn254Fr>(selectors, wires, n_rows, n_vars, pi_pos, n_pi, rules, out_kind, out_def_row, out_level);
     if (curve == ZKT_CURVE_BLS12_381)
-        return debug_plan_host_t<Bls381Fr>(selectors, wires, n_rows, n_vars, pi_pos, n_pi, out_kind, out_def_row, out_level);
+        return debug_plan_host_t<Bls381Fr>(selectors, wires, n_rows, n_vars, pi_pos, n_pi, rules, out_kind, out_def_row, out_level);
     return ZKT_ERR_INVALID_ARGUMENT;
+}
+
+int zkt_debug_witness_plan_host(int curve, const uint64_t* const* selectors, const uint32_t* const* wires, size_t n_rows, size_t n_vars,
+                                const size_t* pi_pos, size_t n_pi, uint8_t* out_kind, uint32_t* out_def_row, uint32_t* out_level) {
+    return zkt_debug_witness_plan_host_ex(curve, selectors, wires, n_rows, n_vars, pi_pos, n_pi, 0, out_kind, out_def_row, out_level);
 }
 
 }  // extern "C"
