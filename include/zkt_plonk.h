@@ -1200,6 +1200,71 @@ int zkt_circuit_check_epk_file(zkt_ctx* ctx, const char* epk_path, int* first_mi
 int zkt_srs_load_file(zkt_ctx* ctx, const char* ck_path, size_t max_powers);
 int zkt_circuit_load_file(zkt_ctx* ctx, const char* pk_path, int log_n);
 
+/* ---- the keys that setup makes, and the files of the reference CLI's `Compile` ------------------------------------
+ * proof_system::setup (setup.rs:42-166) returns a ProverKey, a VerifierKey and an ExtendedProverKey; `Compile`
+ * (bin/src/main.rs:105-111) writes them with the CommitterKey to --ck / --pk / --vk / --epk.  zkt_circuit_setup /
+ * zkt_circuit_setup_wiring return the VerifierKey's commitments and keep the rest in HBM; the entries below bring all
+ * of it out, whichever way the circuit was loaded (zkt_circuit_load, _load_file, _setup, _setup_wiring).  All of them
+ * synchronise and write to host memory or files; after any of them the next zkt_prove gives the bytes it would have
+ * given.  The file layouts are those of the readers above: restated from ark-serialize / ark-poly-commit 0.3 and
+ * pinned to the writer in oracle/keyfile.py and to those readers, not to a file the reference made ("parity
+ * unpinned").
+ *
+ * zkt_circuit_export -- the ProverKey (setup.rs:72-101, keys/mod.rs:29-41): the ten polynomials in zkt_circuit_load
+ * order as coefficients in Montgomery limbs.  lens10[k] is the length DensePolynomial::from_coefficients_vec leaves
+ * (trailing zeros stripped, the zero polynomial 0), taken on the device, whatever lengths the load was given.
+ * out_polys = NULL or an entry NULL: no download for it (lengths only); an entry holds n elements.  Read-only on the
+ * keys and free of the work buffers: allowed on forks, on sharded contexts (the polynomials are replicated) and while a
+ * next proof is announced.
+ * zkt_circuit_commitments -- the VerifierKey's commitments (setup.rs:104-121 PC::commit, keys/mod.rs:196-210) of the
+ * loaded circuit under the loaded SRS, in the format of zkt_circuit_setup's outputs ((0, 0) and the flag for the
+ * identity): what a context started from a --pk file needs to seed its transcript.  The same commit stage as
+ * zkt_circuit_setup, over the trimmed lengths: the SRS must be as long as the longest polynomial
+ * (ZKT_ERR_TOO_MANY_COEFFICIENTS otherwise).
+ * zkt_circuit_export_epk -- the ExtendedProverKey (keys/mod.rs:78-174): vector `which` (0 .. 16, arkworks' order, see
+ * zkt_keyfile_extended_prover_key; -1: lengths only) in Montgomery limbs into out_mont (cap elements; too few ->
+ * ZKT_ERR_INVALID_ARGUMENT) and the seventeen lengths.  The derivation is the one zkt_circuit_check_epk_file compares
+ * a file with.
+ * zkt_circuit_check_vk_file -- a --vk file (bin/src/main.rs:111) against the loaded circuit under the loaded SRS:
+ * *first_mismatch = -1 identical, 0 .. 9 the first differing commitment, 10 another n.
+ * The last three (and the file writers below that need them) use the per-proof work buffers: unsharded contexts only,
+ * refused while a next proof is announced (zkt_prove_set_next); forks are fine. */
+int zkt_circuit_export(zkt_ctx* ctx, uint64_t* const* out_polys, size_t* lens10);
+int zkt_circuit_commitments(zkt_ctx* ctx, uint64_t* out_commitments, int* out_is_infinity);
+int zkt_circuit_export_epk(zkt_ctx* ctx, int which, uint64_t* out_mont, size_t cap, size_t* lens17);
+int zkt_circuit_check_vk_file(zkt_ctx* ctx, const char* vk_path, int* first_mismatch);
+/* Host-only writers of the three small files, from Montgomery limbs.  Each writes a temporary sibling of `path` and
+ * renames it: a failed call leaves neither a truncated key file nor the temporary one.  A limb vector that is not
+ * below its modulus -> ZKT_ERR_INVALID_ARGUMENT (our readers refuse such values, so every file written can be read
+ * back); so is a file that cannot be written.  zkt_keyfile_last_error: the calling thread's last writer failure, a
+ * text that names the path ("" after a success).
+ * --ck (bin/src/main.rs:105; plonk.rs:79-85 PC::trim): powers_of_g = the count >= 1 points, an empty powers_of_gamma_g,
+ * shifted_powers_of_g / shifted_powers_of_gamma_g / enforced_degree_bounds = None, max_degree = count - 1.  An all-zero
+ * (x, y) is the identity, as the reader returns it, written as GroupAffine::zero() = (0, 1) with the infinity flag.
+ * --pk (bin/src/main.rs:107; keys/mod.rs:29-41): ten LabeledPolynomial labelled as in setup.rs:92-101, degree_bound and
+ * hiding_bound None; lens10[k] coefficients each, written as given (zkt_circuit_export's are trimmed).
+ * --vk (bin/src/main.rs:111; keys/mod.rs:180-210): n, pi_roots (n_pi > 0 needs them), the ten commitments;
+ * is_infinity10 may be NULL when (0, 0) alone marks the identity. */
+const char* zkt_keyfile_last_error(void);
+int zkt_keyfile_write_committer_key(const char* path, int curve_id, const uint64_t* g1_xy_mont, size_t count);
+int zkt_keyfile_write_prover_key(const char* path, int curve_id, const uint64_t* const* polys, const size_t* lens10);
+int zkt_keyfile_write_verifier_key(const char* path, int curve_id, uint64_t n, const uint64_t* pi_roots_mont, size_t n_pi,
+                                   const uint64_t* commitments_xy_mont, const int* is_infinity10);
+/* Files straight from the device; errors name the path in zkt_last_error.
+ * zkt_srs_save_file -- --ck (bin/src/main.rs:105): the first `count` loaded powers (0: all), downloaded a block at a
+ * time.  Unsharded contexts only.
+ * zkt_circuit_write_epk_file -- --epk (bin/src/main.rs:108-109): the seventeen vectors streamed through two pinned
+ * chunks (the next chunk's copy and the next vector's transform run while the current chunk is written); host memory
+ * is the two chunks, where the file of an n = 2^20 circuit holds 1.9 GB.
+ * zkt_circuit_save_files -- --pk / --vk / --epk (bin/src/main.rs:107-111) of the loaded circuit; a NULL path is
+ * skipped.  The vk's pi_roots are w^pos (keys/mod.rs:186-188), w = zkt_domain_group_gen(log_n), for the n_pi
+ * public-input positions: ascending, distinct and below n, otherwise ZKT_ERR_INVALID_ARGUMENT and nothing is written.
+ * A --pk alone needs neither an SRS nor an unsharded context. */
+int zkt_srs_save_file(zkt_ctx* ctx, const char* ck_path, size_t count);
+int zkt_circuit_write_epk_file(zkt_ctx* ctx, const char* epk_path);
+int zkt_circuit_save_files(zkt_ctx* ctx, const char* pk_path, const char* vk_path, const char* epk_path, const size_t* pi_pos,
+                           size_t n_pi);
+
 /* ---- debug / test support ------------------------------------------------------------------ */
 /* Dumps the compiled-in parameter tables (modulus, -p^-1 mod 2^32, R, R^2) as u32 words for
  * which = 0 (Fr) or 1 (Fq) of the context's curve; returns the limb count. */

@@ -363,6 +363,60 @@ def keyfile_verifier_key(path: str, curve):
     return n.value, roots[:k.value], commits, np.array([bool(x) for x in inf])
 
 
+def keyfile_last_error() -> str:
+    """zkt_keyfile_last_error: this thread's last writer failure (the text names the path), "" after a success."""
+    L = lib()
+    L.zkt_keyfile_last_error.restype = ctypes.c_char_p
+    return L.zkt_keyfile_last_error().decode()
+
+
+def _writer_check(rc: int, what: str):
+    if rc:
+        raise ZktError(rc, keyfile_last_error() or what)
+
+
+def keyfile_write_committer_key(path: str, curve, powers):
+    """zkt_keyfile_write_committer_key: (count, 2*fq_limbs) Montgomery limbs -> the --ck file; an all-zero point is the
+    identity (host only)."""
+    L = lib()
+    cid = curve_id(curve)
+    words = 8 if cid == CURVE_BN254 else 12
+    pts = np.ascontiguousarray(powers, dtype=np.uint64).reshape(-1, words)
+    L.zkt_keyfile_write_committer_key.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t]
+    _writer_check(L.zkt_keyfile_write_committer_key(path.encode(), cid, u64p(pts) if pts.size else None, pts.shape[0]),
+                  "zkt_keyfile_write_committer_key(%s)" % path)
+
+
+def keyfile_write_prover_key(path: str, curve, polys):
+    """zkt_keyfile_write_prover_key: ten (len_k, 4) coefficient arrays in zkt_circuit_load order -> the --pk file (host only)."""
+    L = lib()
+    cid = curve_id(curve)
+    P64 = ctypes.POINTER(ctypes.c_uint64)
+    arrs = [np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 4) for a in polys]
+    assert len(arrs) == 10
+    ptrs = (P64 * 10)(*[u64p(a) if a.size else P64() for a in arrs])
+    lens = (ctypes.c_size_t * 10)(*[a.shape[0] for a in arrs])
+    L.zkt_keyfile_write_prover_key.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(P64), ctypes.POINTER(ctypes.c_size_t)]
+    _writer_check(L.zkt_keyfile_write_prover_key(path.encode(), cid, ptrs, lens), "zkt_keyfile_write_prover_key(%s)" % path)
+
+
+def keyfile_write_verifier_key(path: str, curve, n: int, pi_roots, commitments, is_infinity=None, n_pi: int = None):
+    """zkt_keyfile_write_verifier_key: n, pi_roots (k, 4), commitments (10, 2*fq_limbs), is_infinity (10,) or None -> the
+    --vk file (host only).  n_pi overrides the number of roots announced (pi_roots None: a NULL pointer)."""
+    L = lib()
+    cid = curve_id(curve)
+    words = 8 if cid == CURVE_BN254 else 12
+    P64 = ctypes.POINTER(ctypes.c_uint64)
+    roots = None if pi_roots is None else np.ascontiguousarray(pi_roots, dtype=np.uint64).reshape(-1, 4)
+    k = (0 if roots is None else roots.shape[0]) if n_pi is None else n_pi
+    com = np.ascontiguousarray(commitments, dtype=np.uint64).reshape(10, words)
+    inf = None if is_infinity is None else (ctypes.c_int * 10)(*[int(bool(x)) for x in is_infinity])
+    L.zkt_keyfile_write_verifier_key.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_uint64, P64, ctypes.c_size_t, P64,
+                                                 ctypes.POINTER(ctypes.c_int)]
+    _writer_check(L.zkt_keyfile_write_verifier_key(path.encode(), cid, n, u64p(roots) if roots is not None and roots.size else None, k,
+                                                   u64p(com), inf), "zkt_keyfile_write_verifier_key(%s)" % path)
+
+
 class VerifyInputs(ctypes.Structure):
     _fields_ = [("n", ctypes.c_uint64), ("vk_commitments", ctypes.POINTER(ctypes.c_uint64)),
                 ("vk_is_infinity", ctypes.POINTER(ctypes.c_int)), ("pi_roots", ctypes.POINTER(ctypes.c_uint64)),
@@ -1927,6 +1981,74 @@ class Context:
         if vec.value < 0:
             return None
         return vec.value, (-1 if at.value == ctypes.c_size_t(-1).value else at.value)
+
+    # -- the keys that setup makes, and the files of the reference CLI's `Compile` -----------------------
+    def circuit_export(self, lengths_only: bool = False):
+        """zkt_circuit_export: the ten ProverKey polynomials of the loaded circuit as (len_k, 4) Montgomery arrays in
+        zkt_circuit_load order, trimmed as DensePolynomial::from_coefficients_vec leaves them; lengths_only: the ten
+        lengths, nothing downloaded."""
+        P64 = ctypes.POINTER(ctypes.c_uint64)
+        self._L.zkt_circuit_export.argtypes = [ctypes.c_void_p, ctypes.POINTER(P64), ctypes.POINTER(ctypes.c_size_t)]
+        lens = (ctypes.c_size_t * 10)()
+        if lengths_only:
+            self.check(self._L.zkt_circuit_export(self._h, None, lens))
+            return list(lens)
+        if self.circuit_log_n is None:
+            raise ValueError("circuit_export: load the circuit through this Context (entry buffers hold n elements)")
+        arrs = [np.zeros((1 << self.circuit_log_n, 4), dtype=np.uint64) for _ in range(10)]
+        ptrs = (P64 * 10)(*[u64p(a) for a in arrs])
+        self.check(self._L.zkt_circuit_export(self._h, ptrs, lens))
+        return [a[:lens[k]].copy() for k, a in enumerate(arrs)]
+
+    def circuit_commitments(self):
+        """zkt_circuit_commitments -> (commitments (10, 2*fq_limbs) Montgomery limbs, is_infinity (10,) bool): the
+        VerifierKey commitments of the loaded circuit under the loaded SRS, as circuit_setup returns them."""
+        self._L.zkt_circuit_commitments.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int)]
+        out = np.zeros((10, 2 * self.fq_limbs), dtype=np.uint64)
+        inf = (ctypes.c_int * 10)()
+        self.check(self._L.zkt_circuit_commitments(self._h, u64p(out), inf))
+        return out, np.array([bool(x) for x in inf])
+
+    def circuit_export_epk(self, which: int = -1, cap: int = None):
+        """zkt_circuit_export_epk -> (the seventeen lengths, vector `which` as (len, 4) Montgomery limbs or None for -1);
+        cap: the element count announced for the buffer (default: the vector's length)."""
+        P64 = ctypes.POINTER(ctypes.c_uint64)
+        self._L.zkt_circuit_export_epk.argtypes = [ctypes.c_void_p, ctypes.c_int, P64, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+        lens = (ctypes.c_size_t * 17)()
+        self.check(self._L.zkt_circuit_export_epk(self._h, -1, None, 0, lens))
+        if which < 0:
+            return list(lens), None
+        out = np.zeros((max(lens[which], 1), 4), dtype=np.uint64)
+        self.check(self._L.zkt_circuit_export_epk(self._h, which, u64p(out), lens[which] if cap is None else cap, lens))
+        return list(lens), out[:lens[which]]
+
+    def check_vk_file(self, path: str):
+        """zkt_circuit_check_vk_file: None when the --vk file's n and ten commitments are the loaded circuit's under the
+        loaded SRS, else the first differing commitment (0 .. 9) or 10 for n."""
+        self._L.zkt_circuit_check_vk_file.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]
+        at = ctypes.c_int(0)
+        self.check(self._L.zkt_circuit_check_vk_file(self._h, path.encode(), ctypes.byref(at)))
+        return None if at.value < 0 else at.value
+
+    def srs_save_file(self, ck_path: str, count: int = 0):
+        """zkt_srs_save_file: the first `count` loaded powers (0: all) as the reference CLI's --ck file."""
+        self._L.zkt_srs_save_file.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
+        self.check(self._L.zkt_srs_save_file(self._h, ck_path.encode(), count))
+
+    def write_epk_file(self, epk_path: str):
+        """zkt_circuit_write_epk_file: the loaded circuit's ExtendedProverKey streamed into the --epk file."""
+        self._L.zkt_circuit_write_epk_file.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
+        self.check(self._L.zkt_circuit_write_epk_file(self._h, epk_path.encode()))
+
+    def circuit_save_files(self, pk_path: str = None, vk_path: str = None, epk_path: str = None, pi_pos=()):
+        """zkt_circuit_save_files: the --pk / --vk / --epk files of the loaded circuit (None: skipped); pi_pos: the
+        public-input positions behind the vk's pi_roots, ascending."""
+        pos = [int(x) for x in pi_pos]
+        arr = (ctypes.c_size_t * max(len(pos), 1))(*pos)
+        enc = lambda p: None if p is None else p.encode()
+        self._L.zkt_circuit_save_files.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
+                                                   ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t]
+        self.check(self._L.zkt_circuit_save_files(self._h, enc(pk_path), enc(vk_path), enc(epk_path), arr, len(pos)))
 
     def debug_eval_lincomb(self, polys, points, scalars, out_len: int):
         """zkt_debug_eval_lincomb: polys: list of (len_j, 4) arrays, points / scalars (k, 4); returns (evals (k, 4), lincomb

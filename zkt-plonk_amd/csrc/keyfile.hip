@@ -6,6 +6,8 @@
 //   * plonk-core's ExtendedProverKey<F> (bin/src/main.rs:34-35,108-109 --epk; keys/mod.rs:148-174): never NEEDED -- the
 //     extended key is derived on the device by zkt_circuit_load -- but read, vector by vector, so that a file the reference
 //     wrote can be checked against that derivation (zkt_circuit_check_epk_file, prover.hip)
+// and the writers of the same four files (byte layout: keyfile_write.hpp; zkt_keyfile_write_*, zkt_srs_save_file here, the
+// circuit's files in prover.hip).
 // Host-only code.  The byte layouts follow ark-serialize 0.3 / ark-poly-commit 0.3 (third-party crates absent from
 // /root/reference; restated from their published derive rules, no reference-held file exists to pin them against:
 // "parity unpinned", the round trip is tested against the writer of the test-side restatement):
@@ -19,6 +21,7 @@
 #include "ctx.hpp"
 #include "ec.hpp"
 #include "keyfile.hpp"
+#include "keyfile_write.hpp"
 #include "msm.hpp"
 
 #include <algorithm>
@@ -256,11 +259,71 @@ static int epk_vector_t(EpkReader& rd, int which, uint64_t* out, size_t cap, siz
     return rd.at_end() ? ZKT_OK : ZKT_ERR_INVALID_ARGUMENT;   // trailing bytes: not an ExtendedProverKey
 }
 
+// ---- writers (keyfile_write.hpp holds the byte layout; it knows nothing of HIP, so its moduli are checked here) --------
+template <class P>
+static constexpr bool kw_modulus_is(const uint32_t (&m)[12]) {
+    for (int i = 0; i < P::N; ++i)
+        if (m[i] != P::mod(i)) return false;
+    return true;
+}
+static bool kw_moduli_checked() {
+    return kw::field(ZKT_CURVE_BN254, false).n32 == Bn254Fr::N && kw_modulus_is<Bn254Fr>(kw::field(ZKT_CURVE_BN254, false).mod) &&
+           kw::field(ZKT_CURVE_BN254, true).n32 == Bn254Fq::N && kw_modulus_is<Bn254Fq>(kw::field(ZKT_CURVE_BN254, true).mod) &&
+           kw::field(ZKT_CURVE_BLS12_381, false).n32 == Bls381Fr::N && kw_modulus_is<Bls381Fr>(kw::field(ZKT_CURVE_BLS12_381, false).mod) &&
+           kw::field(ZKT_CURVE_BLS12_381, true).n32 == Bls381Fq::N && kw_modulus_is<Bls381Fq>(kw::field(ZKT_CURVE_BLS12_381, true).mod);
+}
+
+static thread_local std::string keyfile_err;
+// the writers' result: the message (which names the path) kept for zkt_keyfile_last_error, and for `c` when there is one
+int keyfile_write_done(zkt_ctx* c, kw::File& w) {
+    static const bool moduli_ok = kw_moduli_checked();
+    if (!moduli_ok) w.reject("keyfile_write.hpp holds another modulus than fp.hpp");
+    if (w.commit()) {
+        keyfile_err.clear();
+        return ZKT_OK;
+    }
+    keyfile_err = w.error();
+    return set_err(c, ZKT_ERR_INVALID_ARGUMENT, keyfile_err);   // as the readers answer a file they cannot read
+}
+static int keyfile_refuse(const char* why) {
+    keyfile_err = why;
+    return ZKT_ERR_INVALID_ARGUMENT;
+}
+
 }  // namespace zkt
 
 using namespace zkt;
 
 extern "C" {
+
+const char* zkt_keyfile_last_error(void) { return keyfile_err.c_str(); }
+
+int zkt_keyfile_write_committer_key(const char* path, int curve_id, const uint64_t* g1_xy_mont, size_t count) {
+    if (!path || !g1_xy_mont || count == 0 || (curve_id != ZKT_CURVE_BN254 && curve_id != ZKT_CURVE_BLS12_381))
+        return keyfile_refuse("zkt_keyfile_write_committer_key: a path, a curve and at least one power");
+    kw::File w(path);
+    kw::write_committer_key(w, curve_id, g1_xy_mont, count);
+    return keyfile_write_done(nullptr, w);
+}
+
+int zkt_keyfile_write_prover_key(const char* path, int curve_id, const uint64_t* const* polys, const size_t* lens10) {
+    if (!path || !polys || !lens10 || (curve_id != ZKT_CURVE_BN254 && curve_id != ZKT_CURVE_BLS12_381))
+        return keyfile_refuse("zkt_keyfile_write_prover_key: null pointer or unknown curve");
+    for (int k = 0; k < 10; ++k)
+        if (lens10[k] && !polys[k]) return keyfile_refuse("zkt_keyfile_write_prover_key: a polynomial with a length and no coefficients");
+    kw::File w(path);
+    kw::write_prover_key(w, curve_id, polys, lens10);
+    return keyfile_write_done(nullptr, w);
+}
+
+int zkt_keyfile_write_verifier_key(const char* path, int curve_id, uint64_t n, const uint64_t* pi_roots_mont, size_t n_pi,
+                                   const uint64_t* commitments_xy_mont, const int* is_infinity10) {
+    if (!path || !commitments_xy_mont || (n_pi && !pi_roots_mont) || (curve_id != ZKT_CURVE_BN254 && curve_id != ZKT_CURVE_BLS12_381))
+        return keyfile_refuse("zkt_keyfile_write_verifier_key: null pointer or unknown curve");
+    kw::File w(path);
+    kw::write_verifier_key(w, curve_id, n, pi_roots_mont, n_pi, commitments_xy_mont, is_infinity10);
+    return keyfile_write_done(nullptr, w);
+}
 
 int zkt_keyfile_committer_key(const char* path, int curve_id, size_t max_powers, uint64_t* out_xy_mont, size_t* n_powers) {
     if (!path || !n_powers || (curve_id != ZKT_CURVE_BN254 && curve_id != ZKT_CURVE_BLS12_381)) return ZKT_ERR_INVALID_ARGUMENT;
@@ -314,6 +377,27 @@ int zkt_srs_load_file(zkt_ctx* c, const char* ck_path, size_t max_powers) {
         return set_err(c, rc, std::string("malformed point in ") + ck_path);
     (void)hipSetDevice(c->device);
     return srs_load(c, pts.data(), count, false, 0, 0);
+}
+
+// the loaded powers in the --ck format, a block at a time: the host never holds the whole key
+int zkt_srs_save_file(zkt_ctx* c, const char* ck_path, size_t count) {
+    if (!c || !ck_path) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
+    if (!c->msm) return set_err(c, ZKT_ERR_NOT_LOADED, "no SRS loaded (zkt_srs_load)");
+    if (c->sharded()) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "a sharded context holds a slice of the key: save it from an unsharded one");
+    if (count == 0) count = c->msm->count;
+    if (count == 0 || count > c->msm->count) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "more powers asked for than are loaded");
+    const kw::Field& fq = kw::field(c->curve, true);
+    const size_t words = (size_t)fq.n32, step = (size_t)1 << 14;
+    std::vector<uint64_t> pts(std::min(step, count) * words);
+    kw::File w(ck_path);
+    kw::committer_key_head(w, count);
+    for (size_t i = 0; i < count && w.ok(); i += step) {
+        const size_t cnt = std::min(step, count - i);
+        if (int rc = zkt_srs_download(c, i, cnt, pts.data())) return rc;
+        for (size_t j = 0; j < cnt && w.ok(); ++j) w.g1(fq, pts.data() + j * words, false);
+    }
+    kw::committer_key_tail(w, count);
+    return keyfile_write_done(c, w);
 }
 
 int zkt_circuit_load_file(zkt_ctx* c, const char* pk_path, int log_n) {

@@ -5,7 +5,14 @@
 #include <cstdint>
 #include <cstdio>
 
+struct zkt_ctx;
+
 namespace zkt {
+
+namespace kw { class File; }   // keyfile_write.hpp
+// ends a written key file: the rename into place, or the error (its text names the path) for zkt_keyfile_last_error and
+// for `c` when there is one
+int keyfile_write_done(zkt_ctx* c, kw::File& w);
 
 // arith { q_m_coset q_l_coset q_r_coset q_o_coset q_c_coset } (keys/arithmetic.rs:51-62), lookup { q_lookup q_lookup_coset
 // q_table_coset } (keys/lookup.rs:70-77), perm { sigma1 sigma1_coset sigma2 sigma2_coset sigma3 sigma3_coset x_coset }

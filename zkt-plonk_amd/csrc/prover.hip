@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include "ec.hpp"
 #include "keyfile.hpp"
+#include "keyfile_write.hpp"
 #include "linearisation.hpp"
 #include "msm.hpp"
 #include "poly.hpp"
@@ -1591,35 +1592,33 @@ static int circuit_load_t(zkt_ctx* c, int log_n, const uint64_t* const* polys, c
     return ZKT_OK;
 }
 
-// setup.rs:42-166 on the device: polynomials from the evaluation vectors, ExtendedProverKey, the ten commitments
-template <class C>
-static int circuit_setup_t(zkt_ctx* c, int log_n, const uint64_t* const* evals, const size_t* lens, unsigned evals_dev_mask,
-                           uint64_t* out_commitments, int* out_is_inf) {
-    using Q = typename C::Fq;
-    int rc = circuit_load_t<C>(c, log_n, evals, lens, true, evals_dev_mask);
-    if (rc) return rc;
-    CircuitState& S = *c->circuit;
-    // setup.rs:104-121: PC::commit of the ten labelled polynomials, ProverKey order; batches of the MSM's slot count
-    const int L = Q::N / 2;
+// setup.rs:104-121: PC::commit of the ten labelled polynomials of the loaded circuit, ProverKey order, in batches of the
+// MSM's slot count: the one commit stage of zkt_circuit_setup (lens[k] = n) and of zkt_circuit_commitments / _check_vk_file
+// (the trimmed lengths; the zero polynomial commits to the identity without an MSM).  Identity = (0, 0) and the flag.
+static int circuit_commit_keys(zkt_ctx* c, CircuitState& S, const size_t* lens, uint64_t* out_commitments, int* out_is_inf) {
+    const int L = c->curve == ZKT_CURVE_BN254 ? 4 : 6;
+    int rc;
     size_t off = 0, cnt = 0, total = 0;
     msm_slice(c, &off, &cnt, &total);
-    if (c->sharded() && S.n > total)
-        return set_err(c, ZKT_ERR_TOO_MANY_COEFFICIENTS, "TooManyCoefficients: polynomial longer than the committer key");
+    for (int k = 0; k < PK_COUNT; ++k)
+        if (lens[k] > S.n || (c->sharded() && lens[k] > total))
+            return set_err(c, ZKT_ERR_TOO_MANY_COEFFICIENTS, "TooManyCoefficients: polynomial longer than the committer key");
     for (int k0 = 0; k0 < PK_COUNT; k0 += 5) {
         const int kk = std::min(5, PK_COUNT - k0);
         uint64_t xy[5 * 12] = {};
         if (!c->sharded()) {
             for (int k = 0; k < kk; ++k)
-                if ((rc = msm_begin(c, S.pk[k0 + k], S.n, 0, 1, k))) return rc;
+                if (lens[k0 + k] && (rc = msm_begin(c, S.pk[k0 + k], lens[k0 + k], 0, 1, k))) return rc;
             for (int k = 0; k < kk; ++k)
-                if ((rc = msm_end(c, k, xy + 12 * k))) return rc;
+                if (lens[k0 + k] && (rc = msm_end(c, k, xy + 12 * k))) return rc;
         } else {   // this rank's slice of the coefficients; one all-gather per batch
             int slots[5];
             bool have[5];
             for (int k = 0; k < kk; ++k) {
+                const size_t len = lens[k0 + k];
                 slots[k] = k;
-                have[k] = S.n > off;
-                if (have[k] && (rc = msm_begin(c, (const char*)S.pk[k0 + k] + off * 32, std::min(S.n, off + cnt) - off, 0, 1, k)))
+                have[k] = len > off;
+                if (have[k] && (rc = msm_begin(c, (const char*)S.pk[k0 + k] + off * 32, std::min(len, off + cnt) - off, 0, 1, k)))
                     return rc;
             }
             if ((rc = msm_end_sharded(c, slots, have, kk, xy))) return rc;
@@ -1631,6 +1630,38 @@ static int circuit_setup_t(zkt_ctx* c, int log_n, const uint64_t* const* evals, 
             for (int i = 0; i < 2 * L; ++i) out_commitments[(size_t)(k0 + k) * 2 * L + i] = xy[12 * k + i];
         }
     }
+    return ZKT_OK;
+}
+
+// setup.rs:42-166 on the device: polynomials from the evaluation vectors, ExtendedProverKey, the ten commitments
+template <class C>
+static int circuit_setup_t(zkt_ctx* c, int log_n, const uint64_t* const* evals, const size_t* lens, unsigned evals_dev_mask,
+                           uint64_t* out_commitments, int* out_is_inf) {
+    int rc = circuit_load_t<C>(c, log_n, evals, lens, true, evals_dev_mask);
+    if (rc) return rc;
+    CircuitState& S = *c->circuit;
+    size_t full[PK_COUNT];
+    for (auto& l : full) l = S.n;   // the polynomials as the inverse transforms left them, untrimmed
+    return circuit_commit_keys(c, S, full, out_commitments, out_is_inf);
+}
+
+// The ten ProverKey polynomials' lengths as DensePolynomial::from_coefficients_vec leaves them (trailing zeros stripped, the
+// zero polynomial 0), taken on the device, whatever lengths the load was given.  Reads the keys and a word vector of its
+// own: no work buffer, so it may run beside an announced proof's early rounds, on a fork and on a sharded context.
+static int circuit_key_lens(zkt_ctx* c, const CircuitState& S, size_t* lens10) {
+    DevSet tmp(c->device);
+    void* d = nullptr;
+    int rc = tmp.alloc(c, &d, PK_COUNT * 4);
+    if (rc) return rc;
+    uint32_t h[PK_COUNT] = {};
+    ZKT_HIP(c, hipMemsetAsync(d, 0, PK_COUNT * 4, c->stream));
+    for (int k = 0; k < PK_COUNT && !rc; ++k) rc = poly_trim_len(c, S.pk[k], S.n, (uint32_t*)d + k);
+    if (!rc && hipMemcpyAsync(h, d, PK_COUNT * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+        rc = set_err(c, ZKT_ERR_HIP, "downloading the key lengths failed");
+    const hipError_t e = hipStreamSynchronize(c->stream);   // before `tmp` goes, whatever happened
+    if (rc) return rc;
+    ZKT_HIP(c, e);
+    for (int k = 0; k < PK_COUNT; ++k) lens10[k] = h[k];
     return ZKT_OK;
 }
 
@@ -1725,9 +1756,63 @@ static int debug_combine_split_t(zkt_ctx* c, const uint64_t* table, size_t table
     return ZKT_OK;
 }
 
+// ---- the ExtendedProverKey's vectors, one at a time (keys/mod.rs:78-146 as zkt_circuit_load runs it) ----------------------
+// The derivation zkt_circuit_check_epk_file compares a file with and zkt_circuit_export_epk / _write_epk_file hand out: every
+// vector is recomputed in arkworks' own form (the resident cosets partly live in the quotient kernel's radix).
+static bool epk_is_evals(int k) { return k == EPK_QLOOKUP || k == EPK_S1 || k == EPK_S2 || k == EPK_S3; }
+// zh_coset takes four values: g^n w4^(i mod 4) - 1 (keys/mod.rs:115-117); it never exists as a vector on the device
+template <class R>
+static void epk_zh4(int log_n, Fe<R> out[4]) {
+    const size_t n = (size_t)1 << log_n;
+    const Fe<R> one = fe_one<R>(), g = fe_from_u32<R>(R::GENERATOR), w4n = root_of_unity<R>(log_n + 2);
+    const Fe<R> w4 = fe_pow_u64<R>(w4n, (uint64_t)n);
+    Fe<R> cur = fe_pow_u64<R>(g, (uint64_t)n);
+    for (int j = 0; j < 4; ++j) {
+        out[j] = fe_sub<R>(cur, one);
+        cur = fe_mul<R>(cur, w4);
+    }
+}
+// Vector k (not zh_coset) on the device: *out is a resident table or `plain` (4n elements, written here; S.ev[0] as well
+// for l_1_coset), Montgomery form; with `canon` (4n elements) the canonical values, written there.
+template <class C>
+static int epk_vector_dev(zkt_ctx* c, CircuitState& S, int k, void* plain, void* canon, const void** out) {
+    using R = typename C::Fr;
+    using F = Fe<R>;
+    static const int pk_of[EPK_VECTORS] = {PK_QM, PK_QL, PK_QR, PK_QO, PK_QC, -1, PK_QLOOKUP, PK_QTABLE, -1, PK_S1, -1, PK_S2, -1, PK_S3,
+                                           -1, -1, -1};
+    const size_t n = S.n;
+    const int log_n = S.log_n;
+    const size_t expect = epk_is_evals(k) ? n : 4 * n;
+    int rc;
+    const void* src = plain;
+    if (pk_of[k] >= 0) {
+        if ((rc = ntt_run(c, log_n + 2, 0, 1, S.pk[pk_of[k]], n, plain))) return rc;
+    } else if (k == EPK_QLOOKUP) {
+        src = S.q_lookup_ev;
+    } else if (epk_is_evals(k)) {
+        src = S.sigma_ev[k == EPK_S1 ? 0 : k == EPK_S2 ? 1 : 2];
+    } else if (k == EPK_X_C) {
+        src = S.coset[CS_X];
+    } else {              // l_1_coset = coset_fft(ifft(1, 0, ..., 0)) (keys/mod.rs:119-120)
+        const F one = fe_one<R>();
+        const F ninv = fe_inv_host<R>(fe_from_u64<R>(n));
+        if ((rc = gen_powers(c, S.ev[0], n, one.v, ninv.v))) return rc;
+        if ((rc = ntt_run(c, log_n + 2, 0, 1, S.ev[0], n, plain))) return rc;
+    }
+    *out = src;
+    if (!canon) return ZKT_OK;
+    LinCombArgs lc{};     // times the word 1 = R^-1 as a Montgomery operand: the canonical value
+    lc.poly[0] = src;
+    lc.len[0] = expect;
+    lc.scalar[0][0] = 1;
+    lc.nterms = 1;
+    if ((rc = poly_lincomb(c, lc, canon, expect))) return rc;
+    *out = canon;
+    return ZKT_OK;
+}
+
 // A file the reference CLI wrote with --epk (bin/src/main.rs:108-109: ExtendedProverKey<F>, keys/mod.rs:148-174) against the
-// extended key this circuit's ProverKey gives on the device (keys/mod.rs:78-146 as zkt_circuit_load runs it): every vector is
-// recomputed in arkworks' own form (the resident cosets partly live in the quotient kernel's radix), turned canonical,
+// extended key this circuit's ProverKey gives on the device: every vector is derived (epk_vector_dev), turned canonical,
 // brought to the host and compared with the file's bytes as they stream by.
 template <class C>
 static int circuit_check_epk_t(zkt_ctx* c, const char* path, int* vec_out, size_t* at_out) {
@@ -1735,7 +1820,6 @@ static int circuit_check_epk_t(zkt_ctx* c, const char* path, int* vec_out, size_
     using F = Fe<R>;
     CircuitState& S = *c->circuit;
     const size_t n = S.n, m = 4 * n;
-    const int log_n = S.log_n;
     *vec_out = -1;
     *at_out = 0;
     EpkReader rd;
@@ -1746,19 +1830,12 @@ static int circuit_check_epk_t(zkt_ctx* c, const char* path, int* vec_out, size_
     if (!rd.open(path)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, std::string("cannot open ") + path);
     void* plain = S.qev;          // 4n work buffers, free between proofs
     void* canon = S.wcos[W_A];
-    const F one = fe_one<R>();
-    uint8_t zh4[4][32];           // zh_coset takes four values: g^n w4^(i mod 4) - 1 (keys/mod.rs:115-117)
+    uint8_t zh4[4][32];
     {
-        const F g = fe_from_u32<R>(R::GENERATOR), w4n = root_of_unity<R>(log_n + 2);
-        const F w4 = fe_pow_u64<R>(w4n, (uint64_t)n);
-        F cur = fe_pow_u64<R>(g, (uint64_t)n);
-        for (int j = 0; j < 4; ++j) {
-            HostF<R>::to_le_bytes(fe_sub<R>(cur, one), zh4[j]);
-            cur = fe_mul<R>(cur, w4);
-        }
+        F zh[4];
+        epk_zh4<R>(S.log_n, zh);
+        for (int j = 0; j < 4; ++j) HostF<R>::to_le_bytes(zh[j], zh4[j]);
     }
-    static const int pk_of[EPK_VECTORS] = {PK_QM, PK_QL, PK_QR, PK_QO, PK_QC, -1, PK_QLOOKUP, PK_QTABLE, -1, PK_S1, -1, PK_S2, -1, PK_S3,
-                                           -1, -1, -1};
     std::vector<uint8_t> want, got;
     const size_t step = (size_t)1 << 16;
     got.resize(step * 32);
@@ -1766,36 +1843,17 @@ static int circuit_check_epk_t(zkt_ctx* c, const char* path, int* vec_out, size_
     for (int k = 0; k < EPK_VECTORS; ++k) {
         uint64_t len = 0;
         if (!rd.next(&len)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, std::string("not an ExtendedProverKey file: ") + path);
-        const bool evals = k == EPK_QLOOKUP || k == EPK_S1 || k == EPK_S2 || k == EPK_S3;
-        const size_t expect = evals ? n : m;
+        const size_t expect = epk_is_evals(k) ? n : m;
         if (len != expect) {      // another circuit size: no element to point at
             *vec_out = k;
             *at_out = (size_t)-1;
             return ZKT_OK;
         }
         if (k != EPK_ZH_C) {
-            const void* src = plain;
-            if (pk_of[k] >= 0) {
-                if ((rc = ntt_run(c, log_n + 2, 0, 1, S.pk[pk_of[k]], n, plain))) return rc;
-            } else if (k == EPK_QLOOKUP) {
-                src = S.q_lookup_ev;
-            } else if (evals) {
-                src = S.sigma_ev[k == EPK_S1 ? 0 : k == EPK_S2 ? 1 : 2];
-            } else if (k == EPK_X_C) {
-                src = S.coset[CS_X];
-            } else {              // l_1_coset = coset_fft(ifft(1, 0, ..., 0)) (keys/mod.rs:119-120)
-                const F ninv = fe_inv_host<R>(fe_from_u64<R>(n));
-                if ((rc = gen_powers(c, S.ev[0], n, one.v, ninv.v))) return rc;
-                if ((rc = ntt_run(c, log_n + 2, 0, 1, S.ev[0], n, plain))) return rc;
-            }
-            LinCombArgs lc{};     // times the word 1 = R^-1 as a Montgomery operand: the canonical value
-            lc.poly[0] = src;
-            lc.len[0] = expect;
-            lc.scalar[0][0] = 1;
-            lc.nterms = 1;
-            if ((rc = poly_lincomb(c, lc, canon, expect))) return rc;
+            const void* src = nullptr;
+            if ((rc = epk_vector_dev<C>(c, S, k, plain, canon, &src))) return rc;
             want.resize(expect * 32);
-            ZKT_HIP(c, hipMemcpyAsync(want.data(), canon, expect * 32, hipMemcpyDeviceToHost, c->stream));
+            ZKT_HIP(c, hipMemcpyAsync(want.data(), src, expect * 32, hipMemcpyDeviceToHost, c->stream));
             ZKT_HIP(c, hipStreamSynchronize(c->stream));
         }
         for (size_t i = 0; i < expect; i += step) {
@@ -1818,6 +1876,107 @@ static int circuit_check_epk_t(zkt_ctx* c, const char* path, int* vec_out, size_
     }
     if (!rd.at_end()) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, std::string("bytes after the seventeenth vector of ") + path);
     return ZKT_OK;
+}
+
+// zkt_circuit_export_epk: vector `which` in Montgomery limbs, straight from the derivation above
+template <class C>
+static int circuit_export_epk_t(zkt_ctx* c, int which, uint64_t* out, size_t cap, size_t* lens17) {
+    using R = typename C::Fr;
+    CircuitState& S = *c->circuit;
+    for (int k = 0; k < EPK_VECTORS; ++k) lens17[k] = epk_is_evals(k) ? S.n : 4 * S.n;
+    if (which < 0) return ZKT_OK;
+    const size_t len = lens17[which];
+    if (!out || cap < len) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "zkt_circuit_export_epk: the buffer is shorter than the vector");
+    if (which == EPK_ZH_C) {
+        Fe<R> zh[4];
+        epk_zh4<R>(S.log_n, zh);
+        for (size_t i = 0; i < len; ++i) memcpy(out + 4 * i, zh[i & 3].v, 32);
+        return ZKT_OK;
+    }
+    const void* src = nullptr;
+    if (int rc = epk_vector_dev<C>(c, S, which, S.qev, nullptr, &src)) return rc;
+    ZKT_HIP(c, hipMemcpyAsync(out, src, len * 32, hipMemcpyDeviceToHost, c->stream));
+    ZKT_HIP(c, hipStreamSynchronize(c->stream));
+    return ZKT_OK;
+}
+
+// zkt_circuit_write_epk_file (bin/src/main.rs:108-109 --epk): the seventeen vectors, canonical, streamed into `w`.  Vector
+// k drains from one of two 4n device buffers through two pinned chunks -- the copy of chunk i + 1 is in flight on the copy
+// stream while chunk i is written -- and vector k + 1 is derived into the other buffer on the main stream meanwhile.  The
+// host holds the two chunks and never a whole vector.
+constexpr size_t EPK_WRITE_CHUNK = (size_t)1 << 16;   // elements: 2 MiB, the step the check reads the file in
+template <class C>
+static int circuit_write_epk_t(zkt_ctx* c, kw::File& w) {
+    using R = typename C::Fr;
+    CircuitState& S = *c->circuit;
+    const size_t n = S.n, step = EPK_WRITE_CHUNK;
+    DevSet tmp(c->device);            // the call's own: the staging chunks and the events of the drain
+    // whatever ends this call, nothing may still read or write the chunks or the work buffers when `tmp` goes
+    struct Drain {
+        zkt_ctx* c;
+        hipStream_t copy;
+        ~Drain() {
+            (void)hipStreamSynchronize(copy);
+            (void)hipStreamSynchronize(c->stream);
+        }
+    } drain{c, S.copy_stream};
+    void* pin[2] = {};
+    hipEvent_t copied[2] = {}, derived[2] = {};
+    int rc;
+    for (int j = 0; j < 2; ++j) {
+        if ((rc = tmp.pinned(c, &pin[j], std::min(step, 4 * n) * 32))) return rc;
+        if ((rc = tmp.event(c, &copied[j]))) return rc;
+        if ((rc = tmp.event(c, &derived[j]))) return rc;
+    }
+    void* canon[2] = {S.wcos[W_A], S.wcos[W_B]};   // 4n each, free between proofs
+    const void* src[2] = {};
+    auto derive = [&](int k) -> int {   // enqueue vector k on the main stream (zh_coset needs no device work)
+        if (k >= EPK_VECTORS || k == EPK_ZH_C) return ZKT_OK;
+        // canon[k & 1] held vector k - 2, whose last chunk the host has waited for; `plain` is read on the main stream only
+        if (int r = epk_vector_dev<C>(c, S, k, S.qev, canon[k & 1], &src[k & 1])) return r;
+        ZKT_HIP(c, hipEventRecord(derived[k & 1], c->stream));
+        return ZKT_OK;
+    };
+    if ((rc = derive(0))) return rc;
+    for (int k = 0; k < EPK_VECTORS && w.ok(); ++k) {
+        const size_t len = epk_is_evals(k) ? n : 4 * n;
+        const size_t chunks = (len + step - 1) / step;
+        w.u64(len);
+        if (k == EPK_ZH_C) {      // the four values, over and over (a chunk is a multiple of four elements)
+            if ((rc = derive(k + 1))) return rc;
+            Fe<R> zh[4];
+            epk_zh4<R>(S.log_n, zh);
+            const size_t fill = std::min(step, len);
+            for (size_t i = 0; i < fill; ++i) HostF<R>::to_le_bytes(zh[i & 3], (uint8_t*)pin[0] + 32 * i);
+            for (size_t i = 0; i < len; i += step) w.bytes(pin[0], std::min(step, len - i) * 32);
+            continue;
+        }
+        ZKT_HIP(c, hipStreamWaitEvent(S.copy_stream, derived[k & 1], 0));
+        auto issue = [&](size_t i) -> int {
+            const size_t at = i * step, cnt = std::min(step, len - at);
+            ZKT_HIP(c, hipMemcpyAsync(pin[i & 1], (const char*)src[k & 1] + at * 32, cnt * 32, hipMemcpyDeviceToHost, S.copy_stream));
+            ZKT_HIP(c, hipEventRecord(copied[i & 1], S.copy_stream));
+            return ZKT_OK;
+        };
+        if ((rc = issue(0))) return rc;
+        if ((rc = derive(k + 1))) return rc;   // the next vector's transform runs while this one drains
+        for (size_t i = 0; i < chunks; ++i) {
+            if (i + 1 < chunks && (rc = issue(i + 1))) return rc;   // chunk i - 1, in the same half, is written
+            ZKT_HIP(c, hipEventSynchronize(copied[i & 1]));
+            w.bytes(pin[i & 1], std::min(step, len - i * step) * 32);
+        }
+    }
+    return ZKT_OK;
+}
+
+// the VerifierKey's pi_roots (keys/mod.rs:186-188): w^pos
+template <class R>
+static void pi_roots_t(int log_n, const size_t* pi_pos, size_t n_pi, uint64_t* out) {
+    const Fe<R> w = root_of_unity<R>(log_n);   // zkt_domain_group_gen
+    for (size_t i = 0; i < n_pi; ++i) {
+        const Fe<R> r = fe_pow_u64<R>(w, (uint64_t)pi_pos[i]);
+        memcpy(out + 4 * i, r.v, 32);
+    }
 }
 
 extern "C" {
@@ -2282,6 +2441,130 @@ int zkt_circuit_check_epk_file(zkt_ctx* c, const char* epk_path, int* first_mism
     c->circuit->prefetch_stage = 0;   // the work buffers are shared with an announced proof's early rounds
     if (c->curve == ZKT_CURVE_BN254) return circuit_check_epk_t<Bn254Curve>(c, epk_path, first_mismatch_vector, mismatch_at);
     return circuit_check_epk_t<Bls381Curve>(c, epk_path, first_mismatch_vector, mismatch_at);
+}
+
+// ---- the keys that setup makes, handed back (setup.rs:42-166 returns ProverKey, VerifierKey, ExtendedProverKey) -------------
+int zkt_circuit_export(zkt_ctx* c, uint64_t* const* out_polys, size_t* lens10) {
+    if (!c || !lens10) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
+    if (!c->circuit) return set_err(c, ZKT_ERR_NOT_LOADED, "no circuit loaded (zkt_circuit_load)");
+    (void)hipSetDevice(c->device);
+    const CircuitState& S = *c->circuit;   // read-only on the keys: forks, sharded contexts (the polynomials are replicated)
+    if (int rc = circuit_key_lens(c, S, lens10)) return rc;
+    if (!out_polys) return ZKT_OK;
+    for (int k = 0; k < PK_COUNT; ++k)
+        if (out_polys[k] && lens10[k])
+            ZKT_HIP(c, hipMemcpyAsync(out_polys[k], S.pk[k], lens10[k] * 32, hipMemcpyDeviceToHost, c->stream));
+    ZKT_HIP(c, hipStreamSynchronize(c->stream));
+    return ZKT_OK;
+}
+
+// what the entries below share: they use the per-proof work buffers (or the MSM's slots)
+static int circuit_work_entry(zkt_ctx* c, const char* who) {
+    if (!c->circuit) return set_err(c, ZKT_ERR_NOT_LOADED, "no circuit loaded (zkt_circuit_load)");
+    if (c->sharded() || c->circuit->G != 1)
+        return set_err(c, ZKT_ERR_INVALID_ARGUMENT, std::string(who) + ": a sharded context holds one class of every coset and a slice of the key; use an unsharded one");
+    if (c->circuit->has_next) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, std::string(who) + ": a next proof is announced");
+    (void)hipSetDevice(c->device);
+    c->circuit->prefetch_stage = 0;   // the work buffers are shared with an announced proof's early rounds
+    return ZKT_OK;
+}
+
+static int circuit_commitments(zkt_ctx* c, uint64_t* out_commitments, int* out_is_infinity) {
+    if (!c->msm) return set_err(c, ZKT_ERR_NOT_LOADED, "no SRS loaded (zkt_srs_load)");
+    CircuitState& S = *c->circuit;
+    size_t lens[PK_COUNT];
+    if (int rc = circuit_key_lens(c, S, lens)) return rc;
+    return circuit_commit_keys(c, S, lens, out_commitments, out_is_infinity);
+}
+
+int zkt_circuit_commitments(zkt_ctx* c, uint64_t* out_commitments, int* out_is_infinity) {
+    if (!c || !out_commitments) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
+    if (int rc = circuit_work_entry(c, "zkt_circuit_commitments")) return rc;
+    return circuit_commitments(c, out_commitments, out_is_infinity);
+}
+
+int zkt_circuit_export_epk(zkt_ctx* c, int which, uint64_t* out_mont, size_t cap, size_t* lens17) {
+    if (!c || !lens17) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
+    if (which < -1 || which >= EPK_VECTORS) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "which: -1 (lengths) or 0 .. 16");
+    if (int rc = circuit_work_entry(c, "zkt_circuit_export_epk")) return rc;
+    if (c->curve == ZKT_CURVE_BN254) return circuit_export_epk_t<Bn254Curve>(c, which, out_mont, cap, lens17);
+    return circuit_export_epk_t<Bls381Curve>(c, which, out_mont, cap, lens17);
+}
+
+int zkt_circuit_check_vk_file(zkt_ctx* c, const char* vk_path, int* first_mismatch) {
+    if (!c || !vk_path || !first_mismatch) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
+    if (int rc = circuit_work_entry(c, "zkt_circuit_check_vk_file")) return rc;
+    uint64_t n = 0, theirs[10 * 12] = {}, ours[10 * 12] = {};
+    size_t n_pi = 0;
+    int their_inf[10] = {}, our_inf[10] = {};
+    if (int rc = zkt_keyfile_verifier_key(vk_path, c->curve, &n, nullptr, 0, &n_pi, theirs, their_inf))
+        return set_err(c, rc, std::string("cannot read a VerifierKey from ") + vk_path);
+    *first_mismatch = -1;
+    if (n != c->circuit->n) {
+        *first_mismatch = 10;
+        return ZKT_OK;
+    }
+    if (int rc = circuit_commitments(c, ours, our_inf)) return rc;
+    const size_t words = c->curve == ZKT_CURVE_BN254 ? 8 : 12;
+    for (int k = 9; k >= 0; --k)
+        if (their_inf[k] != our_inf[k] || memcmp(theirs + k * words, ours + k * words, words * 8) != 0) *first_mismatch = k;
+    return ZKT_OK;
+}
+
+static int circuit_write_epk(zkt_ctx* c, const char* epk_path) {
+    kw::File w(epk_path);
+    const int rc = c->curve == ZKT_CURVE_BN254 ? circuit_write_epk_t<Bn254Curve>(c, w) : circuit_write_epk_t<Bls381Curve>(c, w);
+    if (rc) return rc;   // (the temporary file goes with `w`)
+    return keyfile_write_done(c, w);
+}
+
+int zkt_circuit_write_epk_file(zkt_ctx* c, const char* epk_path) {
+    if (!c || !epk_path) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
+    if (int rc = circuit_work_entry(c, "zkt_circuit_write_epk_file")) return rc;
+    return circuit_write_epk(c, epk_path);
+}
+
+// bin/src/main.rs:105-111: the files `Compile` writes beside --ck (zkt_srs_save_file)
+int zkt_circuit_save_files(zkt_ctx* c, const char* pk_path, const char* vk_path, const char* epk_path, const size_t* pi_pos,
+                           size_t n_pi) {
+    if (!c || (n_pi && !pi_pos)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
+    if (!c->circuit) return set_err(c, ZKT_ERR_NOT_LOADED, "no circuit loaded (zkt_circuit_load)");
+    const size_t n = c->circuit->n;
+    for (size_t i = 0; i < n_pi; ++i)
+        if (pi_pos[i] >= n || (i && pi_pos[i] <= pi_pos[i - 1]))
+            return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "public-input positions must be ascending, distinct and below n");
+    if (vk_path && !c->msm) return set_err(c, ZKT_ERR_NOT_LOADED, "no SRS loaded (zkt_srs_load)");
+    if (vk_path || epk_path) {
+        if (int rc = circuit_work_entry(c, "zkt_circuit_save_files")) return rc;
+    }
+    (void)hipSetDevice(c->device);
+    if (pk_path) {   // --pk: ProverKey (keys/mod.rs:29-41)
+        size_t lens[PK_COUNT];
+        if (int rc = zkt_circuit_export(c, nullptr, lens)) return rc;
+        std::vector<std::vector<uint64_t>> polys(PK_COUNT);
+        uint64_t* ptrs[PK_COUNT];
+        for (int k = 0; k < PK_COUNT; ++k) {
+            polys[k].resize(lens[k] * 4 + 4);
+            ptrs[k] = polys[k].data();
+        }
+        if (int rc = zkt_circuit_export(c, ptrs, lens)) return rc;
+        kw::File w(pk_path);
+        kw::write_prover_key(w, c->curve, ptrs, lens);
+        if (int rc = keyfile_write_done(c, w)) return rc;
+    }
+    if (vk_path) {   // --vk: VerifierKey (keys/mod.rs:180-210), pi_roots = w^pos
+        uint64_t commits[10 * 12] = {};
+        int inf[10] = {};
+        if (int rc = circuit_commitments(c, commits, inf)) return rc;
+        std::vector<uint64_t> roots(4 * n_pi + 4);
+        if (c->curve == ZKT_CURVE_BN254) pi_roots_t<Bn254Fr>(c->circuit->log_n, pi_pos, n_pi, roots.data());
+        else pi_roots_t<Bls381Fr>(c->circuit->log_n, pi_pos, n_pi, roots.data());
+        kw::File w(vk_path);
+        kw::write_verifier_key(w, c->curve, (uint64_t)n, roots.data(), n_pi, commits, inf);
+        if (int rc = keyfile_write_done(c, w)) return rc;
+    }
+    if (epk_path) return circuit_write_epk(c, epk_path);
+    return ZKT_OK;
 }
 
 // Row a13's two kernels alone (linearization_poly.rs:55-121): k <= 12 polynomials of the prover's lengths, each evaluated at its
