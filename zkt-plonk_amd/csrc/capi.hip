@@ -363,6 +363,37 @@ int zkt_ctx_set_stream(zkt_ctx* c, void* hip_stream) {
     return ZKT_OK;
 }
 
+// ---- switches read by the prover as it enqueues a proof -----------------------------------------------
+// commitments of evaluation vectors (lagrange.hip)
+int zkt_ctx_set_lagrange(zkt_ctx* c, int on) {
+    if (!c) return ZKT_ERR_INVALID_ARGUMENT;
+    c->lagrange_off = !on;
+    ++c->msm_epoch;   // early work of an announced proof was issued under the other setting
+    return ZKT_OK;
+}
+
+int zkt_ctx_set_wire_elimination(zkt_ctx* c, int mode) {
+    if (!c) return ZKT_ERR_INVALID_ARGUMENT;
+    if (mode < 0 || mode > 2) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "mode: 0 off, 1 automatic, 2 whenever a table can be built");
+    c->wire_elim_mode = mode;
+    ++c->msm_epoch;   // early work of an announced proof was issued under the other setting
+    return ZKT_OK;
+}
+
+int zkt_ctx_set_quotient_route(zkt_ctx* c, int mode) {
+    if (!c) return ZKT_ERR_INVALID_ARGUMENT;
+    if (mode < 0 || mode > 2) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "mode: 0 automatic, 1 three classes, 2 the whole coset");
+    c->quotient_route = mode;   // the next proof compares its route with what was transformed ahead of time (choose_route)
+    return ZKT_OK;
+}
+
+int zkt_ctx_set_fused_passes(zkt_ctx* c, int mode) {
+    if (!c) return ZKT_ERR_INVALID_ARGUMENT;
+    if (mode < 0 || mode > 2) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "mode: 0 automatic, 1 fused, 2 one launch per step");
+    c->fused_passes = mode;   // read by every round as it is enqueued; early work of an announced proof stays valid (same values)
+    return ZKT_OK;
+}
+
 int zkt_profile_enable(zkt_ctx* c, int on) {
     if (!c) return ZKT_ERR_INVALID_ARGUMENT;
     prof_resolve(c);

@@ -19,7 +19,7 @@ namespace zkt {
 struct MsmState;      // msm.hip
 struct MsmBasesState; // msm.hip (zkt_msm_g1_bases)
 struct KzgState;      // kzg.hip (zkt_kzg_commit_batch / zkt_kzg_open)
-struct CircuitState;  // prover.hip
+struct CircuitState;  // circuit.hpp
 
 // Everything one owner takes from the runtime and gives back together: device memory, pinned memory, streams, events.
 // A state's work set, a function's temporaries and the context's own allocations are each one of these, so nothing is
@@ -199,7 +199,7 @@ int ntt_class_code(int log_big, int cls);
 int ntt_force_split(zkt_ctx* c, int npass, const int* log_r);
 int ntt_run_class(zkt_ctx* c, int log_n, int log_big, int cls, const void* d_in, size_t in_len, void* d_out, void* d_fold);
 
-// prover.hip
+// circuit.hip (the state and what else its units share: circuit.hpp)
 void circuit_release(zkt_ctx* c);
 // a circuit state of its own over the parent's read-only tables (zkt_ctx_fork)
 int circuit_fork(zkt_ctx* child, const zkt_ctx* parent);

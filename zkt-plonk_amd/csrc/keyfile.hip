@@ -5,9 +5,9 @@
 //   * plonk-core's VerifierKey     (bin/src/main.rs:111 --vk; keys/mod.rs:180-210)       -> zkt_transcript_seed
 //   * plonk-core's ExtendedProverKey<F> (bin/src/main.rs:34-35,108-109 --epk; keys/mod.rs:148-174): never NEEDED -- the
 //     extended key is derived on the device by zkt_circuit_load -- but read, vector by vector, so that a file the reference
-//     wrote can be checked against that derivation (zkt_circuit_check_epk_file, prover.hip)
+//     wrote can be checked against that derivation (zkt_circuit_check_epk_file, circuit_keys.hip)
 // and the writers of the same four files (byte layout: keyfile_write.hpp; zkt_keyfile_write_*, zkt_srs_save_file here, the
-// circuit's files in prover.hip).
+// circuit's files in circuit_keys.hip).
 // Host-only code.  The byte layouts follow ark-serialize 0.3 / ark-poly-commit 0.3 (third-party crates absent from
 // /root/reference; restated from their published derive rules, no reference-held file exists to pin them against:
 // "parity unpinned", the round trip is tested against the writer of the test-side restatement):

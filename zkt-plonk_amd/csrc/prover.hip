@@ -2,18 +2,14 @@
 // plonk-core/src/proof_system/prove.rs:59-470.  Witness vectors are uploaded once; every
 // polynomial stays in HBM between rounds; only commitments (affine points), the 12 evaluations and
 // two scalars (the grand-product denominators) cross PCIe, for the host-side Fiat-Shamir transcript.
-#include "ctx.hpp"
-#include "hostinv.hpp"
+// The circuit's state and life cycle are circuit.hpp / circuit.hip; this unit holds Prover<C>, the entries that prove and
+// the test hooks that run single rounds of it.
+#include "circuit.hpp"
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
-#include "ec.hpp"
-#include "keyfile.hpp"
-#include "keyfile_write.hpp"
 #include "linearisation.hpp"
 #include "msm.hpp"
-#include "poly.hpp"
-#include "quotient_classes.hpp"
 #include "transcript.hpp"
 
 #include <algorithm>
@@ -24,139 +20,6 @@
 #include <vector>
 
 namespace zkt {
-
-enum { PK_QM = 0, PK_QL, PK_QR, PK_QO, PK_QC, PK_S1, PK_S2, PK_S3, PK_QLOOKUP, PK_QTABLE, PK_COUNT };
-// coset vectors kept on the device (keys/mod.rs:153-174; x and l_1 are stored, zh is 4 scalars)
-enum { CS_QM = 0, CS_QL, CS_QR, CS_QO, CS_QC, CS_QLOOKUP, CS_QTABLE, CS_S1, CS_S2, CS_S3, CS_X, CS_L1, CS_COUNT };
-enum { W_A = 0, W_B, W_C, W_PI, W_Z1, W_Z2, W_T, W_H1, W_H2, W_COUNT };  // witness cosets of quotient_poly.rs:52-96
-
-// The keys (ProverKey polynomials, ExtendedProverKey cosets, sigma / q_lookup evaluations, domain roots): read-only for a
-// prover, so a fork reads its source's (circuit_fork)
-struct CircuitKeys {
-    std::shared_ptr<DevShared> keys_mem;   // owns every array below
-    void* pk[PK_COUNT] = {};
-    size_t pk_len[PK_COUNT] = {};
-    void* coset[CS_COUNT] = {};
-    void* sigma_ev[3] = {};
-    void* q_lookup_ev = nullptr;
-    void* roots = nullptr;
-    uint32_t zh_inv[4][8] = {};
-};
-// The tables of the quotient on classes 0, 1, 2 of the 4n coset (quotient_classes.hpp): ccoset[] are coset[] as [3][n]
-// class arrays, key_win the windows of sigma1..3 and q_lookup.  Built on first use (ensure_class_tables), keys as well:
-// contexts forked afterwards read them.
-struct ClassTables {
-    std::shared_ptr<DevShared> class_mem;   // owns ccoset[]
-    void* ccoset[CS_COUNT] = {};
-    bool ccoset_ready = false;
-    uint32_t key_win[4][QCW][8] = {};
-    uint32_t qc_gamma[4][8] = {}, qc_vinv[9][8] = {}, qc_g3[3][8] = {};
-};
-
-struct CircuitState : CircuitKeys, ClassTables {
-    // owns everything circuit_alloc_work makes: the per-proof buffers, pinned staging, streams and events below
-    DevSet work;
-    explicit CircuitState(int device) : work(device) {}
-    int log_n = 0;
-    size_t n = 0;
-    // A proof sharded over G GPUs (zkt_ctx_set_comm): this GPU owns the 4n-coset points of global index cls modulo G,
-    // m = 4n / G of them; coset[] and wcos[] hold that class only.  G = 1: the whole coset, as the reference has it.
-    int G = 1, cls = 0, log_m = 0;
-    size_t m = 0;
-    void* wnext[4] = {};       // G = 8: z1, z2, t, h1 on the class (cls + 4) mod 8, where "omega-next" lives
-    void* fold = nullptr;      // m elements: a polynomial folded modulo X^m - shift^m before its class transform
-    void* qgather = nullptr;   // 4n elements: every rank's quotient evaluations, class-major (the all-gather's target)
-    bool have[16] = {};        // commitment slot -> this rank's SRS slice takes part (an MSM was started)
-    // per-proof work buffers
-    void* ev[8] = {};       // a, b, c, t, f, h1, h2, pi   (n each)
-    void* sc[4] = {};       // scan scratch: num, den, PN, SD (n each)
-    void* scan_tmp = nullptr;
-    void* poly[13] = {};    // a b c t h1 h2 z1 z2 pi q_lo q_mid q_hi work   (n + 8 each)
-    void* wcos[W_COUNT] = {};
-    void* qev = nullptr;    // 4n
-    // scalars of a commitment taken in the Lagrange basis (read by the MSM's level-1 kernels only): n + 16 each; one per
-    // commitment that may wait in the queue of a round (t, h1, h2; z2), the last also stages zkt_commit_evals_dev's blinders
-    void* lag_scalars = nullptr;
-    void* lag_scalars_q[3] = {};
-    void* small = nullptr;  // blinders (19), eval partials, eval results
-    uint32_t* status = nullptr;  // [0] error bits, [1] len scratch ... [4..7] quotient lens, [8..] poly lens
-    uint32_t* lk_u32 = nullptr;  // lookup: perm, base counts, starts of the even half, of the odd half, hit counts
-    uint32_t lk_nkeys = 0;       // keys of the resident lookup tables (0 = none)
-    std::vector<uint32_t> lk_host_keys, lk_host_sorted, lk_host_counts, lk_host_order;   // host staging (8 words per key)
-    // zkt_prove_set_next: rounds 1 and 2 of the NEXT proof depend on no challenge; they are issued behind the last
-    // commitments of the current proof, so the GPU never drains between two proofs
-    // Round 1 of the next proof goes behind the quotient commitments of round 4, round 2 behind the opening commitments
-    // of round 5.  Round 1 overwrites what round 5 of the current proof still reads (the wire polynomials) and both
-    // use the status words, so those exist twice; `*_alt` is the set the early work writes.
-    bool has_next = false, prefetch_same_table = false;
-    int prefetch_stage = 0;        // 0 nothing, 1 round 1 issued, 2 rounds 1 and 2 issued (only then it is usable)
-    uint64_t prefetch_epoch = 0;   // zkt_ctx::msm_epoch right after the early work was issued
-    zkt_prove_inputs next_in{}, prefetch_in{};
-    void* poly_alt[3] = {};
-    uint32_t* status_alt = nullptr;
-    void* lk_keys = nullptr;     // insertion-order keys then sorted keys
-    size_t lk_cap = 0;
-    void* pinned = nullptr;
-    hipStream_t comm_stream = nullptr;   // sharded proof, asynchronous communicator: the quotient exchange's pieces travel here
-    hipEvent_t ev_piece[ZKT_QUOTIENT_CHUNKS] = {}, ev_gathered = nullptr;
-    // Round 5: the second opening's polynomial work (a linear combination and a division: memory-bound) runs on this stream
-    // beside the first opening's commitment (integer-ALU bound), in buffers of its own
-    hipStream_t aux_stream = nullptr;
-    hipEvent_t ev_aux_go = nullptr, ev_aux_done = nullptr;
-    void* aux_scan_tmp = nullptr;
-    void* aux_pw = nullptr;
-    hipStream_t copy_stream = nullptr;   // host witness uploads travel beside the main stream's work (cold path)
-    hipEvent_t ev_copy[4] = {};          // a, b, c uploaded; [3]: main stream reached the upload point
-    void* pinned_pi = nullptr;      // host staging of pi_tab
-    uint32_t* pi_tab = nullptr;     // device: QUOTIENT_PI_DIRECT_MAX entries of {rotation, 9 limbs}
-    void* eval_pw = nullptr;        // round 5: EVAL_MAX x 257 powers of the evaluation points, or (fused passes) the opening tables of xi and xi w
-    // The table polynomial depends on the lookup table only: while consecutive proofs pass the same table its
-    // evaluations, coefficients, 4n-coset and commitment are reused (one MSM and two transforms less).
-    std::vector<uint64_t> cached_table;
-    bool t_cached = false, t_coset_valid = false;
-    uint64_t t_srs_generation = 0;   // zkt_ctx::srs_generation the cached commitment was made under
-    uint64_t t_commit_xy[12] = {};
-    // wire base tables (lagrange.hip): the wires of the round 1 last enqueued that were committed over them; their digest
-    // and trimmed lengths are compared when that round is collected (collect_wires)
-    bool wire_route[3] = {};
-    bool wire_dense_only = false;   // zkt_debug_commit_wires_dev route 0
-    int wire_elim_force = -1;       // zkt_debug_commit_wires_dev: 0 = per-variable tables only (route 1), 1 = over free variables (route 2)
-    // The quotient on classes 0, 1, 2 of the 4n coset (single GPU, zkt_ctx_set_quotient_route; ClassTables above): wcos[]
-    // then hold [3][n] as well.
-    bool use_classes = false;       // the route of the proof in flight: layout of wcos[] and of the resident t coset
-    void* heads = nullptr;          // 3 x NTT_MAX_BATCH x NTT_HEAD folded head coefficients of the batch being transformed
-    void* d_win = nullptr;          // QC_WIN_POLYS windows (a b c z1 z2 t), gathered in round 3 ...
-    void* pinned_win = nullptr;     // ... and copied here behind them
-    hipEvent_t ev_win = nullptr;
-    uint32_t last_u[6][8] = {};     // zkt_debug_quotient_top
-    bool last_u_valid = false;
-};
-
-// ---- host field helpers ------------------------------------------------------------------------------
-template <class P>
-struct HostF {
-    using F = Fe<P>;
-    static F from_words(const uint64_t* w) {
-        F r;
-        memcpy(r.v, w, 32);
-        return r;
-    }
-    static void to_le_bytes(const F& mont, uint8_t out[32]) {
-        F c = fe_from_mont<P>(mont);
-        memcpy(out, c.v, 32);
-    }
-    static F from_le_bytes(const uint8_t in[32]) {
-        F c;
-        memcpy(c.v, in, 32);
-        return fe_to_mont<P>(c);
-    }
-};
-
-template <class Q>
-static void fq_to_le(const Fe<Q>& mont, uint8_t* out) {
-    Fe<Q> c = fe_from_mont<Q>(mont);
-    memcpy(out, c.v, Q::N * 4);
-}
 
 // ark-serialize 0.3 compressed short-Weierstrass point (proof wire format, proof.rs:98-155):
 // x little-endian, bit 7 of the last byte = y > -y, bit 6 = infinity.
@@ -180,38 +43,6 @@ static void serialize_point(const Affine<Q>& p, std::vector<uint8_t>& out) {
         if (greater) b[nb - 1] |= 0x80;
     }
     out.insert(out.end(), b.begin(), b.end());
-}
-
-// Public inputs the quotient kernel evaluates itself (poly.hpp): rows of {rotation, nine 29-bit limbs of the value}; the
-// rotation 4 pos / G is in entries of a class of a coset split G ways (1: the whole coset)
-template <class R>
-static void pi_rows(const uint64_t* pi_pos, const uint64_t* pi_vals, size_t n_pi, size_t G, uint32_t* tab) {
-    for (size_t i = 0; i < n_pi; ++i) {
-        tab[10 * i] = (uint32_t)(4 * pi_pos[i] / G);
-        const Fx<R> v = fx_unpack<R>(HostF<R>::from_words(pi_vals + 4 * i));
-        for (int w = 0; w < 9; ++w) tab[10 * i + 1 + w] = v.l[w];
-    }
-}
-
-// The quotient kernel's arguments (quotient_poly.rs:52-224).  _vectors: the twelve coset tables and the nine witness cosets,
-// each `off` bytes into its vector (the classes route's [3][n] arrays); quotient_args: the whole-coset keys, the witness,
-// the challenges (8 Montgomery words each) and zh_inv.  Output, size and public inputs are the caller's.
-static void quotient_vectors(QuotientArgs& q, void* const cs[CS_COUNT], void* const w[W_COUNT], size_t off) {
-    auto at = [&](void* const* v, int k) { return (const void*)((const char*)v[k] + off); };
-    q.q_m = at(cs, CS_QM); q.q_l = at(cs, CS_QL); q.q_r = at(cs, CS_QR); q.q_o = at(cs, CS_QO); q.q_c = at(cs, CS_QC);
-    q.q_lookup = at(cs, CS_QLOOKUP); q.q_table = at(cs, CS_QTABLE); q.x = at(cs, CS_X); q.l1 = at(cs, CS_L1);
-    q.sigma1 = at(cs, CS_S1); q.sigma2 = at(cs, CS_S2); q.sigma3 = at(cs, CS_S3);
-    q.a = at(w, W_A); q.b = at(w, W_B); q.c = at(w, W_C); q.pi = at(w, W_PI);
-    q.z1 = at(w, W_Z1); q.z2 = at(w, W_Z2); q.t = at(w, W_T); q.h1 = at(w, W_H1); q.h2 = at(w, W_H2);
-}
-static QuotientArgs quotient_args(const CircuitState& S, void* const w[W_COUNT], const void* alpha, const void* beta,
-                                  const void* gamma, const void* delta, const void* epsilon) {
-    QuotientArgs q{};
-    quotient_vectors(q, S.coset, w, 0);
-    memcpy(q.alpha, alpha, 32); memcpy(q.beta, beta, 32); memcpy(q.gamma, gamma, 32);
-    memcpy(q.delta, delta, 32); memcpy(q.epsilon, epsilon, 32);
-    memcpy(q.zh_inv, S.zh_inv, sizeof(q.zh_inv));
-    return q;
 }
 
 constexpr int WIRE_ELIM_MIN_LOG_N = 17;   // zkt_ctx_set_wire_elimination mode 1: circuits from this size on
@@ -1405,268 +1236,6 @@ static int run_prover(zkt_ctx* c, const zkt_prove_inputs& in, HostTranscript& tr
     return rc;
 }
 
-// ---- circuit (ProverKey + ExtendedProverKey) ------------------------------------------------------
-// the work set, the keys and the class tables go together (the tables unless a fork still reads them)
-void circuit_release(zkt_ctx* c) {
-    if (!c->circuit) return;
-    (void)hipStreamSynchronize(c->stream);
-    wire_bases_drop(c);   // the wiring is the circuit's
-    c->circuit.reset();
-}
-bool circuit_tables_have_readers(const zkt_ctx* c) {
-    return c->circuit && (dev_shared_has_readers(c->circuit->keys_mem) || dev_shared_has_readers(c->circuit->class_mem));
-}
-
-// Everything a context needs PER PROOF (work buffers, staging, streams, events) for the circuit shape in S (log_n, G, cls
-// set): what a forked context allocates for itself while the keys stay its parent's.
-static int circuit_alloc_work(zkt_ctx* c, CircuitState& S) {
-    const size_t n = S.n, m = S.m;
-    int rc;
-    auto alloc = [&](void** p, size_t elems) { return S.work.alloc(c, p, elems * 32); };
-    if ((rc = alloc(&S.qev, 4 * n))) return rc;
-    if (S.G > 1) {
-        if ((rc = alloc(&S.fold, m))) return rc;
-        if ((rc = alloc(&S.qgather, 4 * n))) return rc;
-        if (S.G == 8) for (auto& p : S.wnext) if ((rc = alloc(&p, m))) return rc;
-    }
-    for (auto& p : S.ev) if ((rc = alloc(&p, n + 8))) return rc;
-    for (auto& p : S.sc) if ((rc = alloc(&p, n + 8))) return rc;
-    if ((rc = alloc(&S.scan_tmp, 2 * ((n + 8) / 1024 + 4096)))) return rc;
-    for (auto& p : S.poly) if ((rc = alloc(&p, n + 8))) return rc;
-    for (int k = 0; k < W_COUNT; ++k)   // the z1 slot doubles as 2n elements of scan scratch in round 3
-        if ((rc = alloc(&S.wcos[k], k == W_Z1 ? std::max(std::max(m, 2 * n), 3 * (n + 8)) : m))) return rc;   // (round 5's second opening borrows 3 (n + 8))
-    const size_t eval_blocks = (n + 8 + 2047) / 2048 + 1;
-    if ((rc = alloc(&S.small, 64 + 16 * eval_blocks))) return rc;
-    if ((rc = alloc(&S.lag_scalars, n + 16))) return rc;   // n + 8 scalars, then the blinders of zkt_commit_evals_dev
-    for (auto& q : S.lag_scalars_q) if ((rc = alloc(&q, n + 16))) return rc;
-    if (S.G == 1) {   // quotient on classes
-        if ((rc = alloc(&S.heads, 3 * NTT_MAX_BATCH * NTT_HEAD))) return rc;
-        if ((rc = alloc(&S.d_win, QC_WIN_POLYS * QC_WIN))) return rc;
-        if ((rc = S.work.pinned(c, &S.pinned_win, QC_WIN_POLYS * QC_WIN * 32))) return rc;
-        if ((rc = S.work.event(c, &S.ev_win))) return rc;
-    }
-    if ((rc = S.work.alloc(c, (void**)&S.status, 64 * 4))) return rc;
-    if ((rc = S.work.alloc(c, (void**)&S.status_alt, 64 * 4))) return rc;
-    for (auto& p : S.poly_alt) if ((rc = alloc(&p, n + 8))) return rc;
-    S.lk_cap = n + 2;
-    if ((rc = S.work.alloc(c, (void**)&S.lk_u32, 5 * S.lk_cap * 4 + 16))) return rc;
-    if ((rc = alloc(&S.lk_keys, 2 * S.lk_cap))) return rc;
-    if ((rc = S.work.pinned(c, &S.pinned, 64 * 32))) return rc;
-    if ((rc = S.work.stream(c, &S.copy_stream))) return rc;
-    if (S.G > 1) {
-        if ((rc = S.work.stream(c, &S.comm_stream))) return rc;
-        for (auto& e : S.ev_piece) if ((rc = S.work.event(c, &e))) return rc;
-        if ((rc = S.work.event(c, &S.ev_gathered))) return rc;
-    }
-    for (auto& e : S.ev_copy) if ((rc = S.work.event(c, &e))) return rc;
-    if ((rc = S.work.pinned(c, &S.pinned_pi, QUOTIENT_PI_DIRECT_MAX * 40))) return rc;
-    if ((rc = S.work.alloc(c, (void**)&S.pi_tab, QUOTIENT_PI_DIRECT_MAX * 40))) return rc;
-    if ((rc = alloc(&S.eval_pw, std::max((size_t)EVAL_MAX * (257 + eval_blocks), 2 * open_witness_powers(n + 8))))) return rc;
-    if (S.G == 1) {
-        if ((rc = alloc(&S.aux_scan_tmp, 2 * ((n + 8) / 1024 + 4096)))) return rc;
-        if ((rc = alloc(&S.aux_pw, open_witness_powers(n + 8)))) return rc;
-        if ((rc = S.work.stream(c, &S.aux_stream))) return rc;
-        if ((rc = S.work.event(c, &S.ev_aux_go))) return rc;
-        if ((rc = S.work.event(c, &S.ev_aux_done))) return rc;
-    }
-    return ZKT_OK;
-}
-
-// zkt_ctx_fork: the parent's keys and, where they exist, its class tables; this context's own work set
-int circuit_fork(zkt_ctx* child, const zkt_ctx* parent) {
-    circuit_release(child);
-    if (!parent->circuit) return ZKT_OK;
-    const CircuitState& P0 = *parent->circuit;
-    auto st = std::make_shared<CircuitState>(child->device);
-    CircuitState& S = *st;
-    S.log_n = P0.log_n; S.n = P0.n; S.G = P0.G; S.cls = P0.cls; S.log_m = P0.log_m; S.m = P0.m;
-    static_cast<CircuitKeys&>(S) = P0;
-    S.keys_mem = dev_shared_reader(P0.keys_mem);
-    if (P0.ccoset_ready) {
-        static_cast<ClassTables&>(S) = P0;
-        S.class_mem = dev_shared_reader(P0.class_mem);
-    }
-    if (int rc = circuit_alloc_work(child, S)) return rc;
-    child->circuit = st;
-    return ZKT_OK;
-}
-
-template <class C>
-static int circuit_load_t(zkt_ctx* c, int log_n, const uint64_t* const* polys, const size_t* lens, bool from_evals = false,
-                          unsigned evals_dev_mask = 0) {   // bit k: evaluation vector k is a device pointer
-    using R = typename C::Fr;
-    using F = Fe<R>;
-    if (log_n < 3 || log_n + 2 > R::TWO_ADICITY || log_n + 2 > 27)
-        return set_err(c, ZKT_ERR_INVALID_DOMAIN_SIZE, "InvalidEvalDomainSize: 4n domain unsupported");
-    if (int rf = refuse_if_forked(c, "loading a circuit")) return rf;
-    circuit_release(c);
-    auto st = std::make_shared<CircuitState>(c->device);
-    // a refused load lets `st` go: what it enqueued on the stream reads the half-built state, so the stream drains first
-    struct Drain {
-        zkt_ctx* c;
-        ~Drain() { if (!c->circuit) (void)hipStreamSynchronize(c->stream); }
-    } drain{c};
-    CircuitState& S = *st;
-    S.log_n = log_n;
-    const size_t n = (size_t)1 << log_n;
-    S.n = n;
-    // sharded proof: this GPU keeps (and later transforms) only its class of the 4n coset
-    S.G = c->sharded() ? c->comm.vt.world : 1;
-    S.cls = c->sharded() ? c->comm.vt.rank : 0;
-    S.log_m = log_n + 2 - (S.G == 8 ? 3 : S.G == 4 ? 2 : S.G == 2 ? 1 : 0);
-    S.m = (size_t)1 << S.log_m;
-    const size_t m = S.m;
-    int rc;
-    S.keys_mem = std::make_shared<DevShared>(c->device);
-    auto alloc = [&](void** p, size_t elems) { return S.keys_mem->alloc(c, p, elems * 32); };
-    if ((rc = circuit_alloc_work(c, S))) return rc;   // (the quotient vector doubles as staging below)
-    for (int k = 0; k < PK_COUNT; ++k) {
-        if (lens[k] > n) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "prover-key polynomial longer than n");
-        if ((rc = alloc(&S.pk[k], n))) return rc;
-        if (from_evals) {
-            // setup.rs:72-90: poly_from_evals of the padded selector / sigma / table-mask evaluations
-            const void* src = polys[k];
-            const bool on_device = (evals_dev_mask >> k) & 1u;
-            if (!on_device) {
-                ZKT_HIP(c, hipMemsetAsync(S.qev, 0, n * 32, c->stream));   // the quotient vector doubles as staging
-                if (lens[k]) ZKT_HIP(c, hipMemcpyAsync(S.qev, polys[k], lens[k] * 32, hipMemcpyHostToDevice, c->stream));
-                src = S.qev;
-            }
-            if ((rc = ntt_run(c, log_n, 1, 0, src, on_device ? lens[k] : n, S.pk[k]))) return rc;
-            S.pk_len[k] = n;
-        } else {
-            ZKT_HIP(c, hipMemsetAsync(S.pk[k], 0, n * 32, c->stream));
-            if (lens[k]) ZKT_HIP(c, hipMemcpyAsync(S.pk[k], polys[k], lens[k] * 32, hipMemcpyHostToDevice, c->stream));
-            S.pk_len[k] = lens[k];
-        }
-    }
-    for (int k = 0; k < CS_COUNT; ++k) if ((rc = alloc(&S.coset[k], m))) return rc;
-    for (int k = 0; k < 3; ++k) if ((rc = alloc(&S.sigma_ev[k], n))) return rc;
-    if ((rc = alloc(&S.q_lookup_ev, n))) return rc;
-    if ((rc = alloc(&S.roots, n))) return rc;
-
-    // extend_prover_key (keys/mod.rs:78-146) on the device
-    const int pk_of_cs[10] = {PK_QM, PK_QL, PK_QR, PK_QO, PK_QC, PK_QLOOKUP, PK_QTABLE, PK_S1, PK_S2, PK_S3};
-    auto key_coset = [&](const void* poly, size_t len, void* out) {   // keys/mod.rs:98-120 coset_fft, this GPU's class
-        return S.G == 1 ? ntt_run(c, log_n + 2, 0, 1, poly, len, out)
-                        : ntt_run_class(c, S.log_m, log_n + 2, S.cls, poly, len, out, S.fold);
-    };
-    for (int k = 0; k < 10; ++k)
-        if ((rc = key_coset(S.pk[pk_of_cs[k]], n, S.coset[k]))) return rc;
-    // sigma / q_lookup evaluations on the n domain (prove.rs:91-94)
-    if ((rc = ntt_run(c, log_n, 0, 0, S.pk[PK_S1], n, S.sigma_ev[0]))) return rc;
-    if ((rc = ntt_run(c, log_n, 0, 0, S.pk[PK_S2], n, S.sigma_ev[1]))) return rc;
-    if ((rc = ntt_run(c, log_n, 0, 0, S.pk[PK_S3], n, S.sigma_ev[2]))) return rc;
-    if ((rc = ntt_run(c, log_n, 0, 0, S.pk[PK_QLOOKUP], n, S.q_lookup_ev))) return rc;
-    const F one = fe_one<R>();
-    const F w = root_of_unity<R>(log_n), w4n = root_of_unity<R>(log_n + 2);
-    const F g = fe_from_u32<R>(R::GENERATOR);
-    if ((rc = gen_powers(c, S.roots, n, w.v, one.v))) return rc;                 // domain.elements()
-    {   // x_coset = g * w4n^t (keys/mod.rs:110-113), t = cls + G i on this GPU
-        const F step = fe_pow_u64<R>(w4n, (uint64_t)S.G), first = fe_mul<R>(g, fe_pow_u64<R>(w4n, (uint64_t)S.cls));
-        if ((rc = gen_powers(c, S.coset[CS_X], m, step.v, first.v))) return rc;
-    }
-    {   // l_1_coset = coset_fft(L_1), L_1 = ifft(1, 0, ..., 0) = (1/n, ..., 1/n)  (keys/mod.rs:119-120)
-        const F ninv = fe_inv_host<R>(fe_from_u64<R>(n));
-        if ((rc = gen_powers(c, S.ev[0], n, one.v, ninv.v))) return rc;
-        if ((rc = key_coset(S.ev[0], n, S.coset[CS_L1]))) return rc;
-    }
-    // the tables that only ever multiply go to the quotient kernel's own Montgomery radix (poly.hpp)
-    if ((rc = to_hat_form(c, S.coset[CS_QM], m, 1))) return rc;
-    for (int k : {CS_QL, CS_QR, CS_QO, CS_QLOOKUP, CS_QTABLE, CS_L1})
-        if ((rc = to_hat_form(c, S.coset[k], m, 0))) return rc;
-    {   // zh_coset takes four values: (g * w4n^i)^n - 1 = g^n * w4^(i mod 4) - 1   (keys/mod.rs:115-117)
-        const F gn = fe_pow_u64<R>(g, (uint64_t)n);
-        const F w4 = fe_pow_u64<R>(w4n, (uint64_t)n);
-        F cur = gn;
-        for (int j = 0; j < 4; ++j) {
-            F zh = fe_sub<R>(cur, one);
-            if (fe_is_zero<R>(zh)) return set_err(c, ZKT_ERR_ZERO_DENOMINATOR, "vanishing polynomial is zero on the coset");
-            F inv = fe_inv_host<R>(zh);
-            memcpy(S.zh_inv[j], inv.v, 32);
-            cur = fe_mul<R>(cur, w4);
-        }
-    }
-    ZKT_HIP(c, hipStreamSynchronize(c->stream));
-    c->circuit = st;
-    return ZKT_OK;
-}
-
-// setup.rs:104-121: PC::commit of the ten labelled polynomials of the loaded circuit, ProverKey order, in batches of the
-// MSM's slot count: the one commit stage of zkt_circuit_setup (lens[k] = n) and of zkt_circuit_commitments / _check_vk_file
-// (the trimmed lengths; the zero polynomial commits to the identity without an MSM).  Identity = (0, 0) and the flag.
-static int circuit_commit_keys(zkt_ctx* c, CircuitState& S, const size_t* lens, uint64_t* out_commitments, int* out_is_inf) {
-    const int L = c->curve == ZKT_CURVE_BN254 ? 4 : 6;
-    int rc;
-    size_t off = 0, cnt = 0, total = 0;
-    msm_slice(c, &off, &cnt, &total);
-    for (int k = 0; k < PK_COUNT; ++k)
-        if (lens[k] > S.n || (c->sharded() && lens[k] > total))
-            return set_err(c, ZKT_ERR_TOO_MANY_COEFFICIENTS, "TooManyCoefficients: polynomial longer than the committer key");
-    for (int k0 = 0; k0 < PK_COUNT; k0 += 5) {
-        const int kk = std::min(5, PK_COUNT - k0);
-        uint64_t xy[5 * 12] = {};
-        if (!c->sharded()) {
-            for (int k = 0; k < kk; ++k)
-                if (lens[k0 + k] && (rc = msm_begin(c, S.pk[k0 + k], lens[k0 + k], 0, 1, k))) return rc;
-            for (int k = 0; k < kk; ++k)
-                if (lens[k0 + k] && (rc = msm_end(c, k, xy + 12 * k))) return rc;
-        } else {   // this rank's slice of the coefficients; one all-gather per batch
-            int slots[5];
-            bool have[5];
-            for (int k = 0; k < kk; ++k) {
-                const size_t len = lens[k0 + k];
-                slots[k] = k;
-                have[k] = len > off;
-                if (have[k] && (rc = msm_begin(c, (const char*)S.pk[k0 + k] + off * 32, std::min(len, off + cnt) - off, 0, 1, k)))
-                    return rc;
-            }
-            if ((rc = msm_end_sharded(c, slots, have, kk, xy))) return rc;
-        }
-        for (int k = 0; k < kk; ++k) {
-            bool inf = true;   // the identity comes back as (0, 0)
-            for (int i = 0; i < 2 * L; ++i) inf = inf && xy[12 * k + i] == 0;
-            if (out_is_inf) out_is_inf[k0 + k] = inf ? 1 : 0;
-            for (int i = 0; i < 2 * L; ++i) out_commitments[(size_t)(k0 + k) * 2 * L + i] = xy[12 * k + i];
-        }
-    }
-    return ZKT_OK;
-}
-
-// setup.rs:42-166 on the device: polynomials from the evaluation vectors, ExtendedProverKey, the ten commitments
-template <class C>
-static int circuit_setup_t(zkt_ctx* c, int log_n, const uint64_t* const* evals, const size_t* lens, unsigned evals_dev_mask,
-                           uint64_t* out_commitments, int* out_is_inf) {
-    int rc = circuit_load_t<C>(c, log_n, evals, lens, true, evals_dev_mask);
-    if (rc) return rc;
-    CircuitState& S = *c->circuit;
-    size_t full[PK_COUNT];
-    for (auto& l : full) l = S.n;   // the polynomials as the inverse transforms left them, untrimmed
-    return circuit_commit_keys(c, S, full, out_commitments, out_is_inf);
-}
-
-// The ten ProverKey polynomials' lengths as DensePolynomial::from_coefficients_vec leaves them (trailing zeros stripped, the
-// zero polynomial 0), taken on the device, whatever lengths the load was given.  Reads the keys and a word vector of its
-// own: no work buffer, so it may run beside an announced proof's early rounds, on a fork and on a sharded context.
-static int circuit_key_lens(zkt_ctx* c, const CircuitState& S, size_t* lens10) {
-    DevSet tmp(c->device);
-    void* d = nullptr;
-    int rc = tmp.alloc(c, &d, PK_COUNT * 4);
-    if (rc) return rc;
-    uint32_t h[PK_COUNT] = {};
-    ZKT_HIP(c, hipMemsetAsync(d, 0, PK_COUNT * 4, c->stream));
-    for (int k = 0; k < PK_COUNT && !rc; ++k) rc = poly_trim_len(c, S.pk[k], S.n, (uint32_t*)d + k);
-    if (!rc && hipMemcpyAsync(h, d, PK_COUNT * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
-        rc = set_err(c, ZKT_ERR_HIP, "downloading the key lengths failed");
-    const hipError_t e = hipStreamSynchronize(c->stream);   // before `tmp` goes, whatever happened
-    if (rc) return rc;
-    ZKT_HIP(c, e);
-    for (int k = 0; k < PK_COUNT; ++k) lens10[k] = h[k];
-    return ZKT_OK;
-}
-
-struct VtableTranscript;  // capi glue below
-
 }  // namespace zkt
 
 using namespace zkt;
@@ -1756,300 +1325,17 @@ static int debug_combine_split_t(zkt_ctx* c, const uint64_t* table, size_t table
     return ZKT_OK;
 }
 
-// ---- the ExtendedProverKey's vectors, one at a time (keys/mod.rs:78-146 as zkt_circuit_load runs it) ----------------------
-// The derivation zkt_circuit_check_epk_file compares a file with and zkt_circuit_export_epk / _write_epk_file hand out: every
-// vector is recomputed in arkworks' own form (the resident cosets partly live in the quotient kernel's radix).
-static bool epk_is_evals(int k) { return k == EPK_QLOOKUP || k == EPK_S1 || k == EPK_S2 || k == EPK_S3; }
-// zh_coset takes four values: g^n w4^(i mod 4) - 1 (keys/mod.rs:115-117); it never exists as a vector on the device
-template <class R>
-static void epk_zh4(int log_n, Fe<R> out[4]) {
-    const size_t n = (size_t)1 << log_n;
-    const Fe<R> one = fe_one<R>(), g = fe_from_u32<R>(R::GENERATOR), w4n = root_of_unity<R>(log_n + 2);
-    const Fe<R> w4 = fe_pow_u64<R>(w4n, (uint64_t)n);
-    Fe<R> cur = fe_pow_u64<R>(g, (uint64_t)n);
-    for (int j = 0; j < 4; ++j) {
-        out[j] = fe_sub<R>(cur, one);
-        cur = fe_mul<R>(cur, w4);
-    }
-}
-// Vector k (not zh_coset) on the device: *out is a resident table or `plain` (4n elements, written here; S.ev[0] as well
-// for l_1_coset), Montgomery form; with `canon` (4n elements) the canonical values, written there.
-template <class C>
-static int epk_vector_dev(zkt_ctx* c, CircuitState& S, int k, void* plain, void* canon, const void** out) {
-    using R = typename C::Fr;
-    using F = Fe<R>;
-    static const int pk_of[EPK_VECTORS] = {PK_QM, PK_QL, PK_QR, PK_QO, PK_QC, -1, PK_QLOOKUP, PK_QTABLE, -1, PK_S1, -1, PK_S2, -1, PK_S3,
-                                           -1, -1, -1};
-    const size_t n = S.n;
-    const int log_n = S.log_n;
-    const size_t expect = epk_is_evals(k) ? n : 4 * n;
-    int rc;
-    const void* src = plain;
-    if (pk_of[k] >= 0) {
-        if ((rc = ntt_run(c, log_n + 2, 0, 1, S.pk[pk_of[k]], n, plain))) return rc;
-    } else if (k == EPK_QLOOKUP) {
-        src = S.q_lookup_ev;
-    } else if (epk_is_evals(k)) {
-        src = S.sigma_ev[k == EPK_S1 ? 0 : k == EPK_S2 ? 1 : 2];
-    } else if (k == EPK_X_C) {
-        src = S.coset[CS_X];
-    } else {              // l_1_coset = coset_fft(ifft(1, 0, ..., 0)) (keys/mod.rs:119-120)
-        const F one = fe_one<R>();
-        const F ninv = fe_inv_host<R>(fe_from_u64<R>(n));
-        if ((rc = gen_powers(c, S.ev[0], n, one.v, ninv.v))) return rc;
-        if ((rc = ntt_run(c, log_n + 2, 0, 1, S.ev[0], n, plain))) return rc;
-    }
-    *out = src;
-    if (!canon) return ZKT_OK;
-    LinCombArgs lc{};     // times the word 1 = R^-1 as a Montgomery operand: the canonical value
-    lc.poly[0] = src;
-    lc.len[0] = expect;
-    lc.scalar[0][0] = 1;
-    lc.nterms = 1;
-    if ((rc = poly_lincomb(c, lc, canon, expect))) return rc;
-    *out = canon;
-    return ZKT_OK;
-}
-
-// A file the reference CLI wrote with --epk (bin/src/main.rs:108-109: ExtendedProverKey<F>, keys/mod.rs:148-174) against the
-// extended key this circuit's ProverKey gives on the device: every vector is derived (epk_vector_dev), turned canonical,
-// brought to the host and compared with the file's bytes as they stream by.
-template <class C>
-static int circuit_check_epk_t(zkt_ctx* c, const char* path, int* vec_out, size_t* at_out) {
-    using R = typename C::Fr;
-    using F = Fe<R>;
-    CircuitState& S = *c->circuit;
-    const size_t n = S.n, m = 4 * n;
-    *vec_out = -1;
-    *at_out = 0;
-    EpkReader rd;
-    struct Closer {
-        EpkReader& r;
-        ~Closer() { r.close(); }
-    } closer{rd};
-    if (!rd.open(path)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, std::string("cannot open ") + path);
-    void* plain = S.qev;          // 4n work buffers, free between proofs
-    void* canon = S.wcos[W_A];
-    uint8_t zh4[4][32];
-    {
-        F zh[4];
-        epk_zh4<R>(S.log_n, zh);
-        for (int j = 0; j < 4; ++j) HostF<R>::to_le_bytes(zh[j], zh4[j]);
-    }
-    std::vector<uint8_t> want, got;
-    const size_t step = (size_t)1 << 16;
-    got.resize(step * 32);
-    int rc;
-    for (int k = 0; k < EPK_VECTORS; ++k) {
-        uint64_t len = 0;
-        if (!rd.next(&len)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, std::string("not an ExtendedProverKey file: ") + path);
-        const size_t expect = epk_is_evals(k) ? n : m;
-        if (len != expect) {      // another circuit size: no element to point at
-            *vec_out = k;
-            *at_out = (size_t)-1;
-            return ZKT_OK;
-        }
-        if (k != EPK_ZH_C) {
-            const void* src = nullptr;
-            if ((rc = epk_vector_dev<C>(c, S, k, plain, canon, &src))) return rc;
-            want.resize(expect * 32);
-            ZKT_HIP(c, hipMemcpyAsync(want.data(), src, expect * 32, hipMemcpyDeviceToHost, c->stream));
-            ZKT_HIP(c, hipStreamSynchronize(c->stream));
-        }
-        for (size_t i = 0; i < expect; i += step) {
-            const size_t cnt = std::min(step, expect - i);
-            if (!rd.read(got.data(), cnt)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, std::string("short read from ") + path);
-            bool same = true;
-            if (k != EPK_ZH_C) {
-                same = memcmp(want.data() + i * 32, got.data(), cnt * 32) == 0;
-            } else {
-                for (size_t j = 0; j < cnt && same; ++j) same = memcmp(zh4[(i + j) & 3], got.data() + j * 32, 32) == 0;
-            }
-            if (!same) {
-                size_t j = 0;
-                while (memcmp(k != EPK_ZH_C ? want.data() + (i + j) * 32 : zh4[(i + j) & 3], got.data() + j * 32, 32) == 0) ++j;
-                *vec_out = k;
-                *at_out = i + j;
-                return ZKT_OK;
-            }
-        }
-    }
-    if (!rd.at_end()) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, std::string("bytes after the seventeenth vector of ") + path);
-    return ZKT_OK;
-}
-
-// zkt_circuit_export_epk: vector `which` in Montgomery limbs, straight from the derivation above
-template <class C>
-static int circuit_export_epk_t(zkt_ctx* c, int which, uint64_t* out, size_t cap, size_t* lens17) {
-    using R = typename C::Fr;
-    CircuitState& S = *c->circuit;
-    for (int k = 0; k < EPK_VECTORS; ++k) lens17[k] = epk_is_evals(k) ? S.n : 4 * S.n;
-    if (which < 0) return ZKT_OK;
-    const size_t len = lens17[which];
-    if (!out || cap < len) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "zkt_circuit_export_epk: the buffer is shorter than the vector");
-    if (which == EPK_ZH_C) {
-        Fe<R> zh[4];
-        epk_zh4<R>(S.log_n, zh);
-        for (size_t i = 0; i < len; ++i) memcpy(out + 4 * i, zh[i & 3].v, 32);
-        return ZKT_OK;
-    }
-    const void* src = nullptr;
-    if (int rc = epk_vector_dev<C>(c, S, which, S.qev, nullptr, &src)) return rc;
-    ZKT_HIP(c, hipMemcpyAsync(out, src, len * 32, hipMemcpyDeviceToHost, c->stream));
-    ZKT_HIP(c, hipStreamSynchronize(c->stream));
-    return ZKT_OK;
-}
-
-// zkt_circuit_write_epk_file (bin/src/main.rs:108-109 --epk): the seventeen vectors, canonical, streamed into `w`.  Vector
-// k drains from one of two 4n device buffers through two pinned chunks -- the copy of chunk i + 1 is in flight on the copy
-// stream while chunk i is written -- and vector k + 1 is derived into the other buffer on the main stream meanwhile.  The
-// host holds the two chunks and never a whole vector.
-constexpr size_t EPK_WRITE_CHUNK = (size_t)1 << 16;   // elements: 2 MiB, the step the check reads the file in
-template <class C>
-static int circuit_write_epk_t(zkt_ctx* c, kw::File& w) {
-    using R = typename C::Fr;
-    CircuitState& S = *c->circuit;
-    const size_t n = S.n, step = EPK_WRITE_CHUNK;
-    DevSet tmp(c->device);            // the call's own: the staging chunks and the events of the drain
-    // whatever ends this call, nothing may still read or write the chunks or the work buffers when `tmp` goes
-    struct Drain {
-        zkt_ctx* c;
-        hipStream_t copy;
-        ~Drain() {
-            (void)hipStreamSynchronize(copy);
-            (void)hipStreamSynchronize(c->stream);
-        }
-    } drain{c, S.copy_stream};
-    void* pin[2] = {};
-    hipEvent_t copied[2] = {}, derived[2] = {};
-    int rc;
-    for (int j = 0; j < 2; ++j) {
-        if ((rc = tmp.pinned(c, &pin[j], std::min(step, 4 * n) * 32))) return rc;
-        if ((rc = tmp.event(c, &copied[j]))) return rc;
-        if ((rc = tmp.event(c, &derived[j]))) return rc;
-    }
-    void* canon[2] = {S.wcos[W_A], S.wcos[W_B]};   // 4n each, free between proofs
-    const void* src[2] = {};
-    auto derive = [&](int k) -> int {   // enqueue vector k on the main stream (zh_coset needs no device work)
-        if (k >= EPK_VECTORS || k == EPK_ZH_C) return ZKT_OK;
-        // canon[k & 1] held vector k - 2, whose last chunk the host has waited for; `plain` is read on the main stream only
-        if (int r = epk_vector_dev<C>(c, S, k, S.qev, canon[k & 1], &src[k & 1])) return r;
-        ZKT_HIP(c, hipEventRecord(derived[k & 1], c->stream));
-        return ZKT_OK;
-    };
-    if ((rc = derive(0))) return rc;
-    for (int k = 0; k < EPK_VECTORS && w.ok(); ++k) {
-        const size_t len = epk_is_evals(k) ? n : 4 * n;
-        const size_t chunks = (len + step - 1) / step;
-        w.u64(len);
-        if (k == EPK_ZH_C) {      // the four values, over and over (a chunk is a multiple of four elements)
-            if ((rc = derive(k + 1))) return rc;
-            Fe<R> zh[4];
-            epk_zh4<R>(S.log_n, zh);
-            const size_t fill = std::min(step, len);
-            for (size_t i = 0; i < fill; ++i) HostF<R>::to_le_bytes(zh[i & 3], (uint8_t*)pin[0] + 32 * i);
-            for (size_t i = 0; i < len; i += step) w.bytes(pin[0], std::min(step, len - i) * 32);
-            continue;
-        }
-        ZKT_HIP(c, hipStreamWaitEvent(S.copy_stream, derived[k & 1], 0));
-        auto issue = [&](size_t i) -> int {
-            const size_t at = i * step, cnt = std::min(step, len - at);
-            ZKT_HIP(c, hipMemcpyAsync(pin[i & 1], (const char*)src[k & 1] + at * 32, cnt * 32, hipMemcpyDeviceToHost, S.copy_stream));
-            ZKT_HIP(c, hipEventRecord(copied[i & 1], S.copy_stream));
-            return ZKT_OK;
-        };
-        if ((rc = issue(0))) return rc;
-        if ((rc = derive(k + 1))) return rc;   // the next vector's transform runs while this one drains
-        for (size_t i = 0; i < chunks; ++i) {
-            if (i + 1 < chunks && (rc = issue(i + 1))) return rc;   // chunk i - 1, in the same half, is written
-            ZKT_HIP(c, hipEventSynchronize(copied[i & 1]));
-            w.bytes(pin[i & 1], std::min(step, len - i * step) * 32);
-        }
-    }
-    return ZKT_OK;
-}
-
-// the VerifierKey's pi_roots (keys/mod.rs:186-188): w^pos
-template <class R>
-static void pi_roots_t(int log_n, const size_t* pi_pos, size_t n_pi, uint64_t* out) {
-    const Fe<R> w = root_of_unity<R>(log_n);   // zkt_domain_group_gen
-    for (size_t i = 0; i < n_pi; ++i) {
-        const Fe<R> r = fe_pow_u64<R>(w, (uint64_t)pi_pos[i]);
-        memcpy(out + 4 * i, r.v, 32);
-    }
-}
-
 extern "C" {
 
-zkt_transcript* zkt_transcript_new(int kind, const char* label) {
-    if (kind != ZKT_TRANSCRIPT_MERLIN && kind != ZKT_TRANSCRIPT_ETHEREUM) return nullptr;
-    zkt_transcript* t = new zkt_transcript();
-    auto* b = new BuiltinTranscript(kind == ZKT_TRANSCRIPT_MERLIN ? 0 : 1, label ? label : "");
-    t->impl.reset(b);
-    if (kind == ZKT_TRANSCRIPT_MERLIN) t->merlin = b;
-    return t;
-}
-void zkt_transcript_free(zkt_transcript* t) { delete t; }
-void zkt_transcript_append_u64(zkt_transcript* t, const char* label, uint64_t v) { t->impl->append_u64(label, v); }
-void zkt_transcript_append_scalars(zkt_transcript* t, const char* label, const uint8_t* le32, size_t count, int single) {
-    t->impl->append_scalars(label, le32, count, 32, single != 0);
-}
-void zkt_transcript_append_commitment(zkt_transcript* t, const char* label, const uint8_t* x_le, const uint8_t* y_le,
-                                      size_t fq_bytes, int is_infinity) {
-    t->impl->append_commitment(label, x_le, y_le, fq_bytes, is_infinity != 0);
-}
-void zkt_transcript_seed(zkt_transcript* t, uint64_t circuit_size, const uint8_t* xy_le, const uint8_t* is_infinity,
-                         size_t fq_bytes) {
-    static const char* labels[10] = {"q_m_commit", "q_l_commit", "q_r_commit", "q_o_commit", "q_c_commit",
-                                     "sigma1_commit", "sigma2_commit", "sigma3_commit", "q_lookup_commit", "q_table_commit"};
-    t->impl->append_u64("circuit_size", circuit_size);
-    for (int k = 0; k < 10; ++k) {
-        const uint8_t* x = xy_le + (size_t)k * 2 * fq_bytes;
-        t->impl->append_commitment(labels[k], x, x + fq_bytes, fq_bytes, is_infinity && is_infinity[k]);
-    }
-}
-void zkt_transcript_challenge_scalar(zkt_transcript* t, const char* label, int fr_bits, uint8_t out_le32[32]) {
-    t->impl->challenge_scalar(label, (size_t)fr_bits, out_le32);
-}
-int zkt_transcript_challenge_bytes(zkt_transcript* t, const char* label, uint8_t* out, size_t len) {
-    return t->merlin && t->merlin->challenge_bytes(label, out, len) ? ZKT_OK : ZKT_ERR_INVALID_ARGUMENT;
-}
-int zkt_transcript_append_message(zkt_transcript* t, const char* label, const uint8_t* msg, size_t len) {
-    return t->merlin && t->merlin->append_message(label, msg, len) ? ZKT_OK : ZKT_ERR_INVALID_ARGUMENT;
-}
-
-int zkt_circuit_load(zkt_ctx* c, int log_n, const uint64_t* const* pk_polys, const size_t* pk_lens) {
-    if (!c || !pk_polys || !pk_lens) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
-    (void)hipSetDevice(c->device);
-    if (c->curve == ZKT_CURVE_BN254) return circuit_load_t<Bn254Curve>(c, log_n, pk_polys, pk_lens);
-    return circuit_load_t<Bls381Curve>(c, log_n, pk_polys, pk_lens);
-}
-
-// With a communicator attached every rank must hold exactly its zkt_shard_range of the key: a rank that loaded the
-// whole key (or somebody else's slice) would make the combined commitments a multiple of the right ones.
-static int check_sharded_key(zkt_ctx* c) {
-    if (!c->sharded()) return ZKT_OK;
-    size_t off = 0, cnt = 0, total = 0, lo = 0, hi = 0;
-    zkt::msm_slice(c, &off, &cnt, &total);
-    (void)zkt_shard_range(total, c->comm.vt.rank, c->comm.vt.world, &lo, &hi);
-    if (off != lo || off + cnt != hi)
-        return set_err(c, ZKT_ERR_INVALID_ARGUMENT,
-                       "sharded proof: this rank must load powers zkt_shard_range(total, rank, world) with zkt_srs_load_slice");
-    if (c->circuit && c->circuit->G != c->comm.vt.world)
-        return set_err(c, ZKT_ERR_NOT_LOADED, "the circuit was loaded for another communicator");
-    return ZKT_OK;
-}
-
 static int prove_impl(zkt_ctx* c, const zkt_prove_inputs* in, HostTranscript& tr, uint8_t* out, size_t cap, size_t* len) {
-    if (!c->circuit) return set_err(c, ZKT_ERR_NOT_LOADED, "no circuit loaded (zkt_circuit_load)");
-    if (!c->msm) return set_err(c, ZKT_ERR_NOT_LOADED, "no SRS loaded (zkt_srs_load)");
+    if (int rc0 = circuit_entry(c, ENTRY_SRS)) return rc0;
     if (int rc0 = check_sharded_key(c)) return rc0;
     (void)hipSetDevice(c->device);
     // the Lagrange-basis table of this domain (lagrange.hip): built on the first proof after a key or circuit change
     if (!c->lagrange_off)
         if (int rc1 = lagrange_ensure(c, c->circuit->log_n)) return rc1;
     std::vector<uint8_t> proof;
-    const int rc = c->curve == ZKT_CURVE_BN254 ? run_prover<Bn254Curve>(c, *in, tr, proof) : run_prover<Bls381Curve>(c, *in, tr, proof);
+    const int rc = by_curve(c->curve, [&](auto C) { return run_prover<decltype(C)>(c, *in, tr, proof); });
     if (rc) {
         // a failed proof withdraws the announcement of its successor: the next call must not issue early work from
         // pointers the caller may have released meanwhile, nor pick up half-issued early rounds
@@ -2063,566 +1349,26 @@ static int prove_impl(zkt_ctx* c, const zkt_prove_inputs* in, HostTranscript& tr
     return ZKT_OK;
 }
 
-// ---- commitments of evaluation vectors (lagrange.hip) --------------------------------------------------
-int zkt_ctx_set_lagrange(zkt_ctx* c, int on) {
-    if (!c) return ZKT_ERR_INVALID_ARGUMENT;
-    c->lagrange_off = !on;
-    ++c->msm_epoch;   // early work of an announced proof was issued under the other setting
-    return ZKT_OK;
-}
-
-int zkt_ctx_set_wire_elimination(zkt_ctx* c, int mode) {
-    if (!c) return ZKT_ERR_INVALID_ARGUMENT;
-    if (mode < 0 || mode > 2) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "mode: 0 off, 1 automatic, 2 whenever a table can be built");
-    c->wire_elim_mode = mode;
-    ++c->msm_epoch;   // early work of an announced proof was issued under the other setting
-    return ZKT_OK;
-}
-
-int zkt_ctx_set_quotient_route(zkt_ctx* c, int mode) {
-    if (!c) return ZKT_ERR_INVALID_ARGUMENT;
-    if (mode < 0 || mode > 2) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "mode: 0 automatic, 1 three classes, 2 the whole coset");
-    c->quotient_route = mode;   // the next proof compares its route with what was transformed ahead of time (choose_route)
-    return ZKT_OK;
-}
-
-int zkt_ctx_set_fused_passes(zkt_ctx* c, int mode) {
-    if (!c) return ZKT_ERR_INVALID_ARGUMENT;
-    if (mode < 0 || mode > 2) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "mode: 0 automatic, 1 fused, 2 one launch per step");
-    c->fused_passes = mode;   // read by every round as it is enqueued; early work of an announced proof stays valid (same values)
-    return ZKT_OK;
-}
-
-int zkt_debug_quotient_top(zkt_ctx* c, uint64_t* out_u, int* out_on_classes) {
-    if (!c || !out_u) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
-    if (!c->circuit) return set_err(c, ZKT_ERR_NOT_LOADED, "no circuit loaded (zkt_circuit_load)");
-    const CircuitState& S = *c->circuit;
-    if (out_on_classes) *out_on_classes = S.use_classes ? 1 : 0;
-    memcpy(out_u, S.last_u, sizeof(S.last_u));   // zero until a proof has taken the route
-    return ZKT_OK;
-}
-
-int zkt_debug_quotient_coeffs(zkt_ctx* c, uint64_t* out, size_t count) {
-    if (!c || !out) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
-    if (!c->circuit) return set_err(c, ZKT_ERR_NOT_LOADED, "no circuit loaded (zkt_circuit_load)");
-    const CircuitState& S = *c->circuit;
-    if (count > 4 * S.n) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "the quotient vector holds 4n elements");
-    (void)hipSetDevice(c->device);
-    ZKT_HIP(c, hipStreamSynchronize(c->stream));
-    ZKT_HIP(c, hipMemcpy(out, S.qev, count * 32, hipMemcpyDeviceToHost));
-    return ZKT_OK;
-}
-
-extern "C++" template <class R>
-static void debug_quotient_classes_host_t(int log_n, const uint64_t* windows, const uint64_t* challenges, uint64_t* out_u,
-                                          uint64_t* out_consts) {
-    typedef Fe<R> F;
-    const QuotientClassConsts<R> q = quotient_class_consts<R>(log_n);
-    for (int k = 0; k < 4; ++k) memcpy(out_consts + 4 * k, q.gamma[k].v, 32);
-    for (int k = 0; k < 9; ++k) memcpy(out_consts + 4 * (4 + k), q.vinv[k].v, 32);
-    for (int k = 0; k < 3; ++k) memcpy(out_consts + 4 * (13 + k), q.g3[k].v, 32);
-    const uint32_t* w = (const uint32_t*)windows;
-    QuotientWindows W{};
-    const uint32_t** slot[10] = {&W.a, &W.b, &W.c, &W.z1, &W.z2, &W.t, &W.sigma1, &W.sigma2, &W.sigma3, &W.q_lookup};
-    for (int k = 0; k < 10; ++k) *slot[k] = w + (size_t)k * QCW * 8;
-    F alpha, beta, delta, u[6];
-    memcpy(alpha.v, challenges, 32);
-    memcpy(beta.v, challenges + 4, 32);
-    memcpy(delta.v, challenges + 8, 32);
-    quotient_top_coefficients<R>(log_n, W, alpha, beta, delta, u);
-    for (int e = 0; e < 6; ++e) memcpy(out_u + 4 * e, u[e].v, 32);
-}
-
-int zkt_debug_quotient_classes_host(int curve, int log_n, const uint64_t* windows, const uint64_t* challenges, uint64_t* out_u,
-                                    uint64_t* out_consts) {
-    if (!windows || !challenges || !out_u || !out_consts) return ZKT_ERR_INVALID_ARGUMENT;
-    if (curve == ZKT_CURVE_BN254) {
-        if (log_n < 3 || log_n + 2 > Bn254Fr::TWO_ADICITY) return ZKT_ERR_INVALID_DOMAIN_SIZE;
-        debug_quotient_classes_host_t<Bn254Fr>(log_n, windows, challenges, out_u, out_consts);
-    } else if (curve == ZKT_CURVE_BLS12_381) {
-        if (log_n < 3 || log_n + 2 > Bls381Fr::TWO_ADICITY) return ZKT_ERR_INVALID_DOMAIN_SIZE;
-        debug_quotient_classes_host_t<Bls381Fr>(log_n, windows, challenges, out_u, out_consts);
-    } else {
-        return ZKT_ERR_INVALID_ARGUMENT;
-    }
-    return ZKT_OK;
-}
-
-int zkt_lagrange_info(zkt_ctx* c, int* log_n, size_t* bases) {
-    if (!c) return ZKT_ERR_INVALID_ARGUMENT;
-    const bool ready = c->circuit && lagrange_ready(c, c->circuit->log_n) && !c->lagrange_off;
-    if (log_n) *log_n = ready ? c->circuit->log_n : -1;
-    if (bases) *bases = ready ? lagrange_bases(c) : 0;
-    return ZKT_OK;
-}
-
-int zkt_commit_evals_dev(zkt_ctx* c, const void* d_evals, const uint64_t* blinders, int k, int path, uint64_t* out_xy,
-                         int* out_is_infinity) {
-    if (!c || !d_evals || !out_xy || (k > 0 && !blinders)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
-    if (k < 0 || k > 3) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "0 .. 3 blinders");
-    if (!c->circuit) return set_err(c, ZKT_ERR_NOT_LOADED, "no circuit loaded (the domain comes from it)");
-    if (!c->msm) return set_err(c, ZKT_ERR_NOT_LOADED, "no SRS loaded (zkt_srs_load)");
-    if (c->sharded()) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "not available on a sharded key");
-    (void)hipSetDevice(c->device);
-    CircuitState& S = *c->circuit;
-    const size_t n = S.n;
-    int rc;
-    if (path == 1) {
-        if ((rc = lagrange_ensure(c, S.log_n))) return rc;
-        if (!lagrange_ready(c, S.log_n)) return set_err(c, ZKT_ERR_NOT_LOADED, "the key is too short for the Lagrange-basis table");
-    } else if (path != 0) {
-        return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "path: 0 coefficients, 1 Lagrange basis");
-    }
-    c->circuit->prefetch_stage = 0;   // the work buffer below belongs to round 5 of an announced proof as well
-    uint32_t* d_len = S.status + 8 + 12;
-    void* d_bl = (char*)S.lag_scalars + (n + 8) * 32;
-    void* poly = S.poly[12];
-    ZKT_HIP(c, hipMemsetAsync(d_len, 0, 4, c->stream));
-    if (k) ZKT_HIP(c, hipMemcpyAsync(d_bl, blinders, (size_t)k * 32, hipMemcpyHostToDevice, c->stream));
-    // poly_from_evals + add_blinders_to_poly (util.rs:63-86, prove.rs:472-483)
-    if ((rc = ntt_run(c, S.log_n, 1, 0, d_evals, n, poly))) return rc;
-    if (c->fused(4)) {
-        const TrimBlindSpec tb{poly, d_bl, d_len, k};
-        if ((rc = poly_trim_blind(c, &tb, 1, n, 8))) return rc;
-    } else {
-        if ((rc = poly_trim_len(c, poly, n, d_len, (char*)poly + n * 32, 8))) return rc;
-        if (k && (rc = poly_add_blinders(c, poly, d_len, d_bl, k, n + 8))) return rc;
-    }
-    if (path == 0) return msm_g1_dev(c, poly, n + (size_t)k, 0, 1, out_xy, out_is_infinity);
-    if ((rc = lagrange_scalars(c, d_evals, n, d_len, d_bl, k, S.roots, S.lag_scalars))) return rc;
-    if ((rc = msm_begin(c, S.lag_scalars, n + (size_t)k, 0, 1, 0, 1))) return rc;
-    uint64_t xy[12] = {};
-    if ((rc = msm_end(c, 0, xy))) return rc;
-    const size_t words = c->curve == ZKT_CURVE_BN254 ? 8 : 12;
-    memcpy(out_xy, xy, words * 8);
-    if (out_is_infinity) {
-        bool any = false;
-        for (size_t i = 0; i < words; ++i) any = any || xy[i] != 0;
-        *out_is_infinity = any ? 0 : 1;
-    }
-    return ZKT_OK;
-}
-
-int zkt_circuit_setup(zkt_ctx* c, int log_n, const uint64_t* const* evals, const size_t* eval_lens, int evals_on_device,
-                      uint64_t* out_commitments, int* out_is_infinity) {
-    if (!c || !evals || !eval_lens || !out_commitments) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
-    if (!c->msm) return set_err(c, ZKT_ERR_NOT_LOADED, "no SRS loaded (zkt_srs_load)");
-    (void)hipSetDevice(c->device);
-    if (log_n < 3 || log_n > 26) return set_err(c, ZKT_ERR_INVALID_DOMAIN_SIZE, "circuit bound out of range");
-    if (int rc0 = check_sharded_key(c)) return rc0;
-    const unsigned mask = evals_on_device ? (1u << PK_COUNT) - 1u : 0u;
-    if (c->curve == ZKT_CURVE_BN254)
-        return circuit_setup_t<Bn254Curve>(c, log_n, evals, eval_lens, mask, out_commitments, out_is_infinity);
-    return circuit_setup_t<Bls381Curve>(c, log_n, evals, eval_lens, mask, out_commitments, out_is_infinity);
-}
-
-int zkt_circuit_setup_wiring(zkt_ctx* c, int log_n, const uint64_t* const* evals, const size_t* eval_lens, int evals_on_device,
-                             const uint32_t* w_l, const uint32_t* w_r, const uint32_t* w_o, size_t n_rows, size_t n_vars,
-                             int wiring_on_device, uint64_t* out_commitments, int* out_is_infinity) {
-    if (!c || !evals || !eval_lens || !out_commitments) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
-    if (!c->msm) return set_err(c, ZKT_ERR_NOT_LOADED, "no SRS loaded (zkt_srs_load)");
-    (void)hipSetDevice(c->device);
-    const int max_log_n = (c->curve == ZKT_CURVE_BN254 ? Bn254Fr::TWO_ADICITY : Bls381Fr::TWO_ADICITY) - 2;
-    if (log_n < 3 || log_n > 25 || log_n > max_log_n)   // what zkt_circuit_load accepts (the 4n domain), 32-bit wire positions
-        return set_err(c, ZKT_ERR_INVALID_DOMAIN_SIZE, "circuit bound out of range");
-    if (int rc0 = check_sharded_key(c)) return rc0;
-    if (int rf = refuse_if_forked(c, "loading a circuit")) return rf;
-    // from here on as a failing zkt_circuit_setup: the previous circuit is gone
-    circuit_release(c);
-    const size_t n = (size_t)1 << log_n;
-    if (n_rows > n) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "more wiring rows than the domain size");
-    for (int k = PK_S1; k <= PK_S3; ++k)
-        if (evals[k] || eval_lens[k])
-            return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "zkt_circuit_setup_wiring makes sigma1..3 itself: entries 5, 6, 7 must be NULL / 0");
-    if (n_rows && (!w_l || !w_r || !w_o)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null wiring pointer");
-    // the call's own buffers: the three sigma vectors and, for host wiring, the uploaded indices
-    DevSet tmp(c->device);
-    void* held[6] = {};
-    int rc = ZKT_OK;
-    for (int k = 0; k < 3 && !rc; ++k) rc = tmp.alloc(c, &held[k], n * 32);
-    const uint32_t* w[3] = {w_l, w_r, w_o};
-    if (!wiring_on_device && n_rows) {
-        for (int k = 0; k < 3 && !rc; ++k) {
-            rc = tmp.alloc(c, &held[3 + k], n_rows * 4);
-            if (!rc && hipMemcpyAsync(held[3 + k], w[k], n_rows * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess)
-                rc = set_err(c, ZKT_ERR_HIP, "uploading the wiring failed");
-            w[k] = (const uint32_t*)held[3 + k];
-        }
-    }
-    if (!rc) rc = sigma_build(c, log_n, w[0], w[1], w[2], n_rows, n_vars, held);
-    if (!rc) {
-        const uint64_t* ev[PK_COUNT];
-        size_t lens[PK_COUNT];
-        for (int k = 0; k < PK_COUNT; ++k) { ev[k] = evals[k]; lens[k] = eval_lens[k]; }
-        unsigned mask = evals_on_device ? (1u << PK_COUNT) - 1u : 0u;
-        for (int k = 0; k < 3; ++k) {
-            ev[PK_S1 + k] = (const uint64_t*)held[k];
-            lens[PK_S1 + k] = n;
-            mask |= 1u << (PK_S1 + k);
-        }
-        rc = c->curve == ZKT_CURVE_BN254 ? circuit_setup_t<Bn254Curve>(c, log_n, ev, lens, mask, out_commitments, out_is_infinity)
-                                         : circuit_setup_t<Bls381Curve>(c, log_n, ev, lens, mask, out_commitments, out_is_infinity);
-    }
-    (void)hipStreamSynchronize(c->stream);   // before `tmp` goes
-    return rc;
-}
-
-// helper.rs:13-75 check_gate over every row (check.hip).  Reads the loaded keys, writes nothing of the circuit state: the
-// work buffers, the resident lookup keys and an announced proof's early rounds stay as they are.
-int zkt_circuit_check_witness(zkt_ctx* c, const zkt_prove_inputs* in, int flags, zkt_witness_report* out) {
-    if (!c) return ZKT_ERR_INVALID_ARGUMENT;
-    if (!in || !out) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
-    if (!c->circuit) return set_err(c, ZKT_ERR_NOT_LOADED, "no circuit loaded (zkt_circuit_load)");
-    if (flags & ~ZKT_CHECK_WIRING) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "unknown flag bits");
-    const CircuitState& S = *c->circuit;
-    const size_t n = S.n;
-    if (in->n_rows > n) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "more rows than the circuit bound");
-    if (in->table_len >= n) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "max table size is equal or larger than n");
-    if (in->table_len && !in->table) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null lookup table");
-    if (in->n_pi && (!in->pi_pos || !in->pi_vals)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null public inputs");
-    for (size_t i = 0; i < in->n_pi; ++i)
-        if (in->pi_pos[i] >= n) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "public input position out of range");
-    if (in->a_evals) {
-        if (flags & ZKT_CHECK_WIRING)
-            return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "ZKT_CHECK_WIRING needs the witness as variables + w_l / w_r / w_o: evaluation vectors carry no wiring");
-        if (in->n_rows && (!in->b_evals || !in->c_evals)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null wire vector");
-    } else {
-        if (in->n_rows && (!in->w_l || !in->w_r || !in->w_o)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null wire index vector");
-        if (in->n_vars && !in->variables) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null variable map");
-        if (in->n_vars > 0xFFFFFFFEull) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "too many variables");
-        if ((flags & ZKT_CHECK_WIRING) && S.log_n > 25)
-            return set_err(c, ZKT_ERR_INVALID_DOMAIN_SIZE, "InvalidEvalDomainSize: the wiring's positions are 32-bit (log_n <= 25)");
-    }
-    (void)hipSetDevice(c->device);
-    WitnessCheckKeys keys{};
-    keys.log_n = S.log_n;
-    for (int k = 0; k < 5; ++k) keys.pk[k] = S.pk[PK_QM + k];   // PK_QM .. PK_QC
-    keys.q_lookup_ev = S.q_lookup_ev;
-    for (int k = 0; k < 3; ++k) keys.sigma_ev[k] = S.sigma_ev[k];
-    return witness_check(c, keys, *in, flags, out);
-}
-
-// The plan of a witness completion over the loaded circuit's selectors (witness_plan.hip).  Reads the loaded keys, writes
-// nothing of the circuit state; the plan keeps no pointer into it.
-int zkt_witness_plan_create_ex(zkt_ctx* c, const uint32_t* w_l, const uint32_t* w_r, const uint32_t* w_o, size_t n_rows, size_t n_vars,
-                               int wiring_on_device, const size_t* pi_pos, size_t n_pi, uint32_t rules, zkt_witness_plan** out) {
-    if (!c) return ZKT_ERR_INVALID_ARGUMENT;
-    if (!out) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
-    if (!c->circuit) return set_err(c, ZKT_ERR_NOT_LOADED, "no circuit loaded (zkt_circuit_load)");
-    const CircuitState& S = *c->circuit;
-    WitnessPlanKeys keys{};
-    keys.log_n = S.log_n;
-    for (int k = 0; k < 5; ++k) keys.pk[k] = S.pk[PK_QM + k];   // PK_QM .. PK_QC
-    return witness_plan_create(c, keys, w_l, w_r, w_o, n_rows, n_vars, wiring_on_device, pi_pos, n_pi, rules, out);
-}
-
-int zkt_witness_plan_create(zkt_ctx* c, const uint32_t* w_l, const uint32_t* w_r, const uint32_t* w_o, size_t n_rows, size_t n_vars,
-                            int wiring_on_device, const size_t* pi_pos, size_t n_pi, zkt_witness_plan** out) {
-    return zkt_witness_plan_create_ex(c, w_l, w_r, w_o, n_rows, n_vars, wiring_on_device, pi_pos, n_pi, 0, out);
-}
-
-// The single check's rules over a batch of completed maps under one wiring (check.hip).  Reads the loaded keys, writes
-// nothing of the circuit state, as zkt_circuit_check_witness.
-int zkt_circuit_check_witness_batch(zkt_ctx* c, const zkt_witness_batch* in, int flags, zkt_witness_report* out) {
-    if (!c) return ZKT_ERR_INVALID_ARGUMENT;
-    if (!in || !out) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
-    if (!c->circuit) return set_err(c, ZKT_ERR_NOT_LOADED, "no circuit loaded (zkt_circuit_load)");
-    if (flags & ~ZKT_CHECK_WIRING) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "unknown flag bits");
-    const CircuitState& S = *c->circuit;
-    const size_t n = S.n;
-    if (in->batch < 1 || in->batch > ZKT_WITNESS_BATCH_MAX) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "1 <= batch <= ZKT_WITNESS_BATCH_MAX");
-    if (in->stride < in->n_vars) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "stride below n_vars");
-    if (in->n_tables != 0 && in->n_tables != 1 && in->n_tables != in->batch)
-        return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "n_tables must be 0, 1 or batch");
-    if (in->n_tables && (!in->tables || !in->table_lens)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null lookup tables");
-    if (in->n_rows > n) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "more rows than the circuit bound");
-    for (size_t t = 0; t < in->n_tables; ++t) {
-        if (in->table_lens[t] >= n) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "max table size is equal or larger than n");
-        if (in->table_lens[t] && !in->tables[t]) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null lookup table");
-    }
-    if (in->n_pi && (!in->pi_pos || !in->d_pi_vals)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null public inputs");
-    for (size_t i = 0; i < in->n_pi; ++i)
-        if (in->pi_pos[i] >= n) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "public input position out of range");
-    if (in->n_rows && (!in->w_l || !in->w_r || !in->w_o)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null wire index vector");
-    if (in->n_vars && !in->d_variables) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null variable map");
-    if (in->n_vars > 0xFFFFFFFEull) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "too many variables");
-    if ((flags & ZKT_CHECK_WIRING) && S.log_n > 25)
-        return set_err(c, ZKT_ERR_INVALID_DOMAIN_SIZE, "InvalidEvalDomainSize: the wiring's positions are 32-bit (log_n <= 25)");
-    (void)hipSetDevice(c->device);
-    WitnessCheckKeys keys{};
-    keys.log_n = S.log_n;
-    for (int k = 0; k < 5; ++k) keys.pk[k] = S.pk[PK_QM + k];   // PK_QM .. PK_QC
-    keys.q_lookup_ev = S.q_lookup_ev;
-    for (int k = 0; k < 3; ++k) keys.sigma_ev[k] = S.sigma_ev[k];
-    return witness_check_batch(c, keys, *in, flags, out);
-}
-
-// Test hook: the fused quotient pass on its own (quotient_poly.rs:98-224) over the loaded circuit's key cosets and
-// caller-supplied witness cosets, so that the kernel is compared point by point on inputs that satisfy nothing.
-int zkt_debug_quotient(zkt_ctx* c, const uint64_t* challenges, const uint64_t* const* wit, const uint64_t* pi_pos,
-                       const uint64_t* pi_vals, size_t n_pi, uint64_t* out) {
-    if (!c || !challenges || !wit || !out || (n_pi && (!pi_pos || !pi_vals)))
-        return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
-    if (!c->circuit) return set_err(c, ZKT_ERR_NOT_LOADED, "no circuit loaded (zkt_circuit_load)");
-    CircuitState& S = *c->circuit;
-    if (S.G != 1) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "zkt_debug_quotient: whole-coset circuits only");
-    if (n_pi > (size_t)QUOTIENT_PI_DIRECT_MAX) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "too many direct public inputs");
-    for (size_t i = 0; i < n_pi; ++i)
-        if (pi_pos[i] >= S.n) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "public input position out of range");
-    (void)hipSetDevice(c->device);
-    const size_t bytes = 4 * S.n * 32;
-    DevSet tmp(c->device);
-    void* d[W_COUNT] = {};
-    void* d_out = nullptr;
-    uint32_t* d_tab = nullptr;
-    int rc = ZKT_OK;
-    for (int k = 0; k < W_COUNT && !rc; ++k) {
-        if (k == W_PI && n_pi) continue;
-        if (!wit[k]) rc = set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null witness coset");
-        else if (!(rc = tmp.alloc(c, &d[k], bytes)) && hipMemcpy(d[k], wit[k], bytes, hipMemcpyHostToDevice) != hipSuccess)
-            rc = set_err(c, ZKT_ERR_HIP, "copy of a witness coset failed");
-    }
-    if (!rc) rc = tmp.alloc(c, &d_out, bytes);
-    if (!rc && n_pi) {
-        std::vector<uint32_t> tab(10 * n_pi);
-        if (c->curve == ZKT_CURVE_BN254) pi_rows<Bn254Curve::Fr>(pi_pos, pi_vals, n_pi, 1, tab.data());
-        else pi_rows<Bls381Curve::Fr>(pi_pos, pi_vals, n_pi, 1, tab.data());
-        if (!(rc = tmp.alloc(c, (void**)&d_tab, tab.size() * 4)) &&
-            hipMemcpy(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-            rc = set_err(c, ZKT_ERR_HIP, "copy of the public-input rows failed");
-    }
-    if (!rc) {
-        QuotientArgs q = quotient_args(S, d, challenges, challenges + 4, challenges + 8, challenges + 12, challenges + 16);
-        q.out = d_out;
-        q.n4 = 4 * S.n;
-        q.pi_tab = n_pi ? d_tab : nullptr;
-        q.n_pi_direct = (uint32_t)n_pi;
-        rc = quotient_pointwise(c, q);
-        if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = set_err(c, ZKT_ERR_HIP, "quotient kernel failed");
-        if (!rc && hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = set_err(c, ZKT_ERR_HIP, "copy back failed");
-    }
-    return rc;
-}
-
 int zkt_debug_grand_products(zkt_ctx* c, const uint64_t* challenges, const uint64_t* const* vectors, uint64_t* out_z1,
                              uint64_t* out_z2) {
     if (!c || !challenges || !vectors || !out_z1 || !out_z2) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
     for (int k = 0; k < 7; ++k)
         if (!vectors[k]) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null vector");
-    if (!c->circuit) return set_err(c, ZKT_ERR_NOT_LOADED, "no circuit loaded (zkt_circuit_load)");
-    (void)hipSetDevice(c->device);
-    c->circuit->prefetch_stage = 0;   // the work buffers are shared with an announced proof's early rounds
+    if (int rc = circuit_entry(c, ENTRY_DEVICE | ENTRY_WITHDRAW)) return rc;
     // the caller's t replaces the evaluations of the cached table polynomial: the next proof rebuilds it
     c->circuit->t_cached = false;
-    if (c->curve == ZKT_CURVE_BN254) return debug_grand_products_t<Bn254Curve>(c, challenges, vectors, out_z1, out_z2);
-    return debug_grand_products_t<Bls381Curve>(c, challenges, vectors, out_z1, out_z2);
+    return by_curve(c->curve, [&](auto C) { return debug_grand_products_t<decltype(C)>(c, challenges, vectors, out_z1, out_z2); });
 }
 
 int zkt_debug_combine_split(zkt_ctx* c, const uint64_t* table, size_t table_len, const uint64_t* f, int fresh,
                             uint64_t* h1_out, uint64_t* h2_out) {
     if (!c || !f || !h1_out || !h2_out || (table_len && !table)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
-    if (!c->circuit) return set_err(c, ZKT_ERR_NOT_LOADED, "no circuit loaded (zkt_circuit_load)");
+    if (int rc = circuit_entry(c, ENTRY_NO_NEXT | ENTRY_DEVICE | ENTRY_WITHDRAW, "zkt_debug_combine_split")) return rc;
     CircuitState& S = *c->circuit;
-    if (S.has_next) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "zkt_debug_combine_split: a next proof is announced");
     if (table_len >= S.n) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "max table size is equal or larger than n");
-    (void)hipSetDevice(c->device);
-    S.prefetch_stage = 0;   // the work buffers are shared with an announced proof's early rounds
     // the keys this call leaves resident need not be those of the cached table polynomial: the next proof rebuilds both
     S.t_cached = false;
-    if (c->curve == ZKT_CURVE_BN254) return debug_combine_split_t<Bn254Curve>(c, table, table_len, f, fresh != 0, h1_out, h2_out);
-    return debug_combine_split_t<Bls381Curve>(c, table, table_len, f, fresh != 0, h1_out, h2_out);
-}
-
-int zkt_circuit_check_epk_file(zkt_ctx* c, const char* epk_path, int* first_mismatch_vector, size_t* mismatch_at) {
-    if (!c || !epk_path || !first_mismatch_vector || !mismatch_at) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
-    if (!c->circuit) return set_err(c, ZKT_ERR_NOT_LOADED, "no circuit loaded (zkt_circuit_load)");
-    if (c->circuit->G != 1) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "a sharded context holds one class of every coset: check the file on an unsharded one");
-    (void)hipSetDevice(c->device);
-    c->circuit->prefetch_stage = 0;   // the work buffers are shared with an announced proof's early rounds
-    if (c->curve == ZKT_CURVE_BN254) return circuit_check_epk_t<Bn254Curve>(c, epk_path, first_mismatch_vector, mismatch_at);
-    return circuit_check_epk_t<Bls381Curve>(c, epk_path, first_mismatch_vector, mismatch_at);
-}
-
-// ---- the keys that setup makes, handed back (setup.rs:42-166 returns ProverKey, VerifierKey, ExtendedProverKey) -------------
-int zkt_circuit_export(zkt_ctx* c, uint64_t* const* out_polys, size_t* lens10) {
-    if (!c || !lens10) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
-    if (!c->circuit) return set_err(c, ZKT_ERR_NOT_LOADED, "no circuit loaded (zkt_circuit_load)");
-    (void)hipSetDevice(c->device);
-    const CircuitState& S = *c->circuit;   // read-only on the keys: forks, sharded contexts (the polynomials are replicated)
-    if (int rc = circuit_key_lens(c, S, lens10)) return rc;
-    if (!out_polys) return ZKT_OK;
-    for (int k = 0; k < PK_COUNT; ++k)
-        if (out_polys[k] && lens10[k])
-            ZKT_HIP(c, hipMemcpyAsync(out_polys[k], S.pk[k], lens10[k] * 32, hipMemcpyDeviceToHost, c->stream));
-    ZKT_HIP(c, hipStreamSynchronize(c->stream));
-    return ZKT_OK;
-}
-
-// what the entries below share: they use the per-proof work buffers (or the MSM's slots)
-static int circuit_work_entry(zkt_ctx* c, const char* who) {
-    if (!c->circuit) return set_err(c, ZKT_ERR_NOT_LOADED, "no circuit loaded (zkt_circuit_load)");
-    if (c->sharded() || c->circuit->G != 1)
-        return set_err(c, ZKT_ERR_INVALID_ARGUMENT, std::string(who) + ": a sharded context holds one class of every coset and a slice of the key; use an unsharded one");
-    if (c->circuit->has_next) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, std::string(who) + ": a next proof is announced");
-    (void)hipSetDevice(c->device);
-    c->circuit->prefetch_stage = 0;   // the work buffers are shared with an announced proof's early rounds
-    return ZKT_OK;
-}
-
-static int circuit_commitments(zkt_ctx* c, uint64_t* out_commitments, int* out_is_infinity) {
-    if (!c->msm) return set_err(c, ZKT_ERR_NOT_LOADED, "no SRS loaded (zkt_srs_load)");
-    CircuitState& S = *c->circuit;
-    size_t lens[PK_COUNT];
-    if (int rc = circuit_key_lens(c, S, lens)) return rc;
-    return circuit_commit_keys(c, S, lens, out_commitments, out_is_infinity);
-}
-
-int zkt_circuit_commitments(zkt_ctx* c, uint64_t* out_commitments, int* out_is_infinity) {
-    if (!c || !out_commitments) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
-    if (int rc = circuit_work_entry(c, "zkt_circuit_commitments")) return rc;
-    return circuit_commitments(c, out_commitments, out_is_infinity);
-}
-
-int zkt_circuit_export_epk(zkt_ctx* c, int which, uint64_t* out_mont, size_t cap, size_t* lens17) {
-    if (!c || !lens17) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
-    if (which < -1 || which >= EPK_VECTORS) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "which: -1 (lengths) or 0 .. 16");
-    if (int rc = circuit_work_entry(c, "zkt_circuit_export_epk")) return rc;
-    if (c->curve == ZKT_CURVE_BN254) return circuit_export_epk_t<Bn254Curve>(c, which, out_mont, cap, lens17);
-    return circuit_export_epk_t<Bls381Curve>(c, which, out_mont, cap, lens17);
-}
-
-int zkt_circuit_check_vk_file(zkt_ctx* c, const char* vk_path, int* first_mismatch) {
-    if (!c || !vk_path || !first_mismatch) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
-    if (int rc = circuit_work_entry(c, "zkt_circuit_check_vk_file")) return rc;
-    uint64_t n = 0, theirs[10 * 12] = {}, ours[10 * 12] = {};
-    size_t n_pi = 0;
-    int their_inf[10] = {}, our_inf[10] = {};
-    if (int rc = zkt_keyfile_verifier_key(vk_path, c->curve, &n, nullptr, 0, &n_pi, theirs, their_inf))
-        return set_err(c, rc, std::string("cannot read a VerifierKey from ") + vk_path);
-    *first_mismatch = -1;
-    if (n != c->circuit->n) {
-        *first_mismatch = 10;
-        return ZKT_OK;
-    }
-    if (int rc = circuit_commitments(c, ours, our_inf)) return rc;
-    const size_t words = c->curve == ZKT_CURVE_BN254 ? 8 : 12;
-    for (int k = 9; k >= 0; --k)
-        if (their_inf[k] != our_inf[k] || memcmp(theirs + k * words, ours + k * words, words * 8) != 0) *first_mismatch = k;
-    return ZKT_OK;
-}
-
-static int circuit_write_epk(zkt_ctx* c, const char* epk_path) {
-    kw::File w(epk_path);
-    const int rc = c->curve == ZKT_CURVE_BN254 ? circuit_write_epk_t<Bn254Curve>(c, w) : circuit_write_epk_t<Bls381Curve>(c, w);
-    if (rc) return rc;   // (the temporary file goes with `w`)
-    return keyfile_write_done(c, w);
-}
-
-int zkt_circuit_write_epk_file(zkt_ctx* c, const char* epk_path) {
-    if (!c || !epk_path) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
-    if (int rc = circuit_work_entry(c, "zkt_circuit_write_epk_file")) return rc;
-    return circuit_write_epk(c, epk_path);
-}
-
-// bin/src/main.rs:105-111: the files `Compile` writes beside --ck (zkt_srs_save_file)
-int zkt_circuit_save_files(zkt_ctx* c, const char* pk_path, const char* vk_path, const char* epk_path, const size_t* pi_pos,
-                           size_t n_pi) {
-    if (!c || (n_pi && !pi_pos)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
-    if (!c->circuit) return set_err(c, ZKT_ERR_NOT_LOADED, "no circuit loaded (zkt_circuit_load)");
-    const size_t n = c->circuit->n;
-    for (size_t i = 0; i < n_pi; ++i)
-        if (pi_pos[i] >= n || (i && pi_pos[i] <= pi_pos[i - 1]))
-            return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "public-input positions must be ascending, distinct and below n");
-    if (vk_path && !c->msm) return set_err(c, ZKT_ERR_NOT_LOADED, "no SRS loaded (zkt_srs_load)");
-    if (vk_path || epk_path) {
-        if (int rc = circuit_work_entry(c, "zkt_circuit_save_files")) return rc;
-    }
-    (void)hipSetDevice(c->device);
-    if (pk_path) {   // --pk: ProverKey (keys/mod.rs:29-41)
-        size_t lens[PK_COUNT];
-        if (int rc = zkt_circuit_export(c, nullptr, lens)) return rc;
-        std::vector<std::vector<uint64_t>> polys(PK_COUNT);
-        uint64_t* ptrs[PK_COUNT];
-        for (int k = 0; k < PK_COUNT; ++k) {
-            polys[k].resize(lens[k] * 4 + 4);
-            ptrs[k] = polys[k].data();
-        }
-        if (int rc = zkt_circuit_export(c, ptrs, lens)) return rc;
-        kw::File w(pk_path);
-        kw::write_prover_key(w, c->curve, ptrs, lens);
-        if (int rc = keyfile_write_done(c, w)) return rc;
-    }
-    if (vk_path) {   // --vk: VerifierKey (keys/mod.rs:180-210), pi_roots = w^pos
-        uint64_t commits[10 * 12] = {};
-        int inf[10] = {};
-        if (int rc = circuit_commitments(c, commits, inf)) return rc;
-        std::vector<uint64_t> roots(4 * n_pi + 4);
-        if (c->curve == ZKT_CURVE_BN254) pi_roots_t<Bn254Fr>(c->circuit->log_n, pi_pos, n_pi, roots.data());
-        else pi_roots_t<Bls381Fr>(c->circuit->log_n, pi_pos, n_pi, roots.data());
-        kw::File w(vk_path);
-        kw::write_verifier_key(w, c->curve, (uint64_t)n, roots.data(), n_pi, commits, inf);
-        if (int rc = keyfile_write_done(c, w)) return rc;
-    }
-    if (epk_path) return circuit_write_epk(c, epk_path);
-    return ZKT_OK;
-}
-
-// Row a13's two kernels alone (linearization_poly.rs:55-121): k <= 12 polynomials of the prover's lengths, each evaluated at its
-// own point (poly_eval_many), and their linear combination sum_j scalars[j] polys[j] (poly_lincomb)
-int zkt_debug_eval_lincomb(zkt_ctx* c, const uint64_t* const* polys, const size_t* lens, int k, const uint64_t* points,
-                           const uint64_t* scalars, uint64_t* out_evals, uint64_t* out_lincomb, size_t out_len) {
-    if (!c || !polys || !lens || !points || !scalars || !out_evals || !out_lincomb) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
-    if (!c->circuit) return set_err(c, ZKT_ERR_NOT_LOADED, "no circuit loaded (zkt_circuit_load)");
-    CircuitState& S = *c->circuit;
-    const size_t cap = S.n + 8;
-    if (k < 1 || k > 12 || out_len < 1 || out_len > cap) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "1 .. 12 polynomials, out_len <= n + 8");
-    for (int j = 0; j < k; ++j)
-        if (!polys[j] || lens[j] < 1 || lens[j] > cap) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "1 .. n + 8 coefficients each");
-    (void)hipSetDevice(c->device);
-    S.prefetch_stage = 0;   // the work buffers are shared with an announced proof's early rounds
-    EvalArgs ea{};
-    LinCombArgs lc{};
-    ea.count = k;
-    lc.nterms = k;
-    for (int j = 0; j < k; ++j) {
-        ZKT_HIP(c, hipMemcpyAsync(S.poly[j], polys[j], lens[j] * 32, hipMemcpyHostToDevice, c->stream));
-        ea.poly[j] = lc.poly[j] = S.poly[j];
-        ea.len[j] = lc.len[j] = lens[j];
-        memcpy(ea.point[j], points + 4 * j, 32);
-        memcpy(lc.scalar[j], scalars + 4 * j, 32);
-    }
-    void* d_partials = (char*)S.small + 64 * 32;
-    void* d_results = (char*)S.small + 32 * 32;
-    int rc = poly_eval_many(c, ea, d_partials, d_results, S.eval_pw);
-    if (rc) return rc;
-    if ((rc = poly_lincomb(c, lc, S.sc[0], out_len))) return rc;
-    ZKT_HIP(c, hipMemcpyAsync(out_evals, d_results, (size_t)k * 32, hipMemcpyDeviceToHost, c->stream));
-    ZKT_HIP(c, hipMemcpyAsync(out_lincomb, S.sc[0], out_len * 32, hipMemcpyDeviceToHost, c->stream));
-    ZKT_HIP(c, hipStreamSynchronize(c->stream));
-    return ZKT_OK;
-}
-
-// kzg10::compute_witness_polynomial alone (row a12: the division of prove.rs:381-451's aggregated polynomial by X - z)
-int zkt_debug_open_witness(zkt_ctx* c, const uint64_t* coeffs, size_t len, const uint64_t* z4, uint64_t* out) {
-    if (!c || !coeffs || !z4 || !out) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
-    if (!c->circuit) return set_err(c, ZKT_ERR_NOT_LOADED, "no circuit loaded (zkt_circuit_load)");
-    CircuitState& S = *c->circuit;
-    if (len < 2 || len > S.n + 8) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "2 .. n + 8 coefficients");
-    (void)hipSetDevice(c->device);
-    c->circuit->prefetch_stage = 0;
-    uint32_t z[8], zi[8];
-    memcpy(z, z4, 32);
-    bool zero = true;
-    for (int i = 0; i < 8; ++i) zero = zero && z[i] == 0;
-    if (zero) return set_err(c, ZKT_ERR_ZERO_DENOMINATOR, "evaluation point is zero");
-    if (c->curve == ZKT_CURVE_BN254) memcpy(zi, fe_inv_host<Bn254Fr>(HostF<Bn254Fr>::from_words(z4)).v, 32);
-    else memcpy(zi, fe_inv_host<Bls381Fr>(HostF<Bls381Fr>::from_words(z4)).v, 32);
-    ZKT_HIP(c, hipMemcpyAsync(S.sc[0], coeffs, len * 32, hipMemcpyHostToDevice, c->stream));
-    int rc = open_witness(c, S.sc[0], len, z, zi, S.sc[1], S.sc[2], S.scan_tmp, S.sc[3], S.eval_pw);
-    if (rc) return rc;
-    ZKT_HIP(c, hipMemcpyAsync(out, S.sc[3], (len - 1) * 32, hipMemcpyDeviceToHost, c->stream));
-    ZKT_HIP(c, hipStreamSynchronize(c->stream));
-    return ZKT_OK;
+    return by_curve(c->curve, [&](auto C) { return debug_combine_split_t<decltype(C)>(c, table, table_len, f, fresh != 0, h1_out, h2_out); });
 }
 
 // Test hook: round 1 of the prover (gather, transforms, the three wire commitments, their collection) on a variable map
@@ -2673,13 +1419,9 @@ int zkt_debug_commit_wires_pi_dev(zkt_ctx* c, const void* d_variables, size_t n_
     if (!c || !d_variables || !blinders || !out_xy || (n_pi && !pi_pos)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
     if (route < 0 || route > 2)
         return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "route: 0 coefficients, 1 wire base tables, 2 tables over free variables");
-    if (!c->circuit) return set_err(c, ZKT_ERR_NOT_LOADED, "no circuit loaded (the domain comes from it)");
-    if (!c->msm) return set_err(c, ZKT_ERR_NOT_LOADED, "no SRS loaded (zkt_srs_load)");
-    if (c->sharded()) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "not available on a sharded key");
+    if (int rc0 = circuit_entry(c, ENTRY_DOMAIN | ENTRY_SRS | ENTRY_WHOLE_KEY | ENTRY_NO_NEXT | ENTRY_DEVICE | ENTRY_WITHDRAW, "zkt_debug_commit_wires_dev"))
+        return rc0;
     CircuitState& S = *c->circuit;
-    if (S.has_next) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "zkt_debug_commit_wires_dev: a next proof is announced");
-    (void)hipSetDevice(c->device);
-    S.prefetch_stage = 0;   // the work buffers are shared with an announced proof's early rounds
     if (route >= 1 && !c->lagrange_off)
         if (int rc1 = lagrange_ensure(c, S.log_n)) return rc1;
     uint64_t bl[19 * 4] = {};
@@ -2693,13 +1435,12 @@ int zkt_debug_commit_wires_pi_dev(zkt_ctx* c, const void* d_variables, size_t n_
     in.blinders = bl;
     in.pi_pos = pi_pos;
     in.n_pi = n_pi;
-    if (c->curve == ZKT_CURVE_BN254) return debug_commit_wires_t<Bn254Curve>(c, in, route, out_xy, out_is_infinity, out_route);
-    return debug_commit_wires_t<Bls381Curve>(c, in, route, out_xy, out_is_infinity, out_route);
+    return by_curve(c->curve, [&](auto C) { return debug_commit_wires_t<decltype(C)>(c, in, route, out_xy, out_is_infinity, out_route); });
 }
 
 int zkt_prove_set_next(zkt_ctx* c, const zkt_prove_inputs* next) {
     if (!c) return ZKT_ERR_INVALID_ARGUMENT;
-    if (!c->circuit) return set_err(c, ZKT_ERR_NOT_LOADED, "no circuit loaded (zkt_circuit_load)");
+    if (int rc = circuit_entry(c, 0)) return rc;
     c->circuit->has_next = next != nullptr;
     if (next) c->circuit->next_in = *next;
     return ZKT_OK;
@@ -2714,12 +1455,10 @@ int zkt_prove(zkt_ctx* c, const zkt_prove_inputs* in, zkt_transcript* tr, uint8_
 int zkt_prove_with(zkt_ctx* c, const zkt_prove_inputs* in, const zkt_transcript_vtable* vt, uint8_t* proof_out,
                    size_t proof_cap, size_t* proof_len) {
     if (!c || !in || !vt || !proof_out) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
-    if (c->curve == ZKT_CURVE_BN254) {
-        VtableAdapter<Bn254Curve> a(vt);
+    return by_curve(c->curve, [&](auto C) {
+        VtableAdapter<decltype(C)> a(vt);
         return prove_impl(c, in, a, proof_out, proof_cap, proof_len);
-    }
-    VtableAdapter<Bls381Curve> a(vt);
-    return prove_impl(c, in, a, proof_out, proof_cap, proof_len);
+    });
 }
 
 }  // extern "C"

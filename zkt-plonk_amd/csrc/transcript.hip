@@ -1,6 +1,8 @@
 // Host-side transcripts: Keccak-256 over whole messages and the built-in Merlin / Ethereum transcript, both on
-// transcript_core.hpp at a stride of one.  See transcript.hpp for the reference files they mirror.
+// transcript_core.hpp at a stride of one, and the zkt_transcript_* C API over them.  See transcript.hpp for the reference
+// files they mirror.
 #include "transcript.hpp"
+#include "../../include/zkt_plonk.h"
 
 #include <cstring>
 
@@ -107,3 +109,47 @@ bool BuiltinTranscript::import_state(const TranscriptState& in) {
 }
 
 }  // namespace zkt
+
+// ---- the zkt_transcript_* C API over the built-in transcripts ------------------------------------------------------------
+using namespace zkt;
+
+extern "C" {
+
+zkt_transcript* zkt_transcript_new(int kind, const char* label) {
+    if (kind != ZKT_TRANSCRIPT_MERLIN && kind != ZKT_TRANSCRIPT_ETHEREUM) return nullptr;
+    zkt_transcript* t = new zkt_transcript();
+    auto* b = new BuiltinTranscript(kind == ZKT_TRANSCRIPT_MERLIN ? 0 : 1, label ? label : "");
+    t->impl.reset(b);
+    if (kind == ZKT_TRANSCRIPT_MERLIN) t->merlin = b;
+    return t;
+}
+void zkt_transcript_free(zkt_transcript* t) { delete t; }
+void zkt_transcript_append_u64(zkt_transcript* t, const char* label, uint64_t v) { t->impl->append_u64(label, v); }
+void zkt_transcript_append_scalars(zkt_transcript* t, const char* label, const uint8_t* le32, size_t count, int single) {
+    t->impl->append_scalars(label, le32, count, 32, single != 0);
+}
+void zkt_transcript_append_commitment(zkt_transcript* t, const char* label, const uint8_t* x_le, const uint8_t* y_le,
+                                      size_t fq_bytes, int is_infinity) {
+    t->impl->append_commitment(label, x_le, y_le, fq_bytes, is_infinity != 0);
+}
+void zkt_transcript_seed(zkt_transcript* t, uint64_t circuit_size, const uint8_t* xy_le, const uint8_t* is_infinity,
+                         size_t fq_bytes) {
+    static const char* labels[10] = {"q_m_commit", "q_l_commit", "q_r_commit", "q_o_commit", "q_c_commit",
+                                     "sigma1_commit", "sigma2_commit", "sigma3_commit", "q_lookup_commit", "q_table_commit"};
+    t->impl->append_u64("circuit_size", circuit_size);
+    for (int k = 0; k < 10; ++k) {
+        const uint8_t* x = xy_le + (size_t)k * 2 * fq_bytes;
+        t->impl->append_commitment(labels[k], x, x + fq_bytes, fq_bytes, is_infinity && is_infinity[k]);
+    }
+}
+void zkt_transcript_challenge_scalar(zkt_transcript* t, const char* label, int fr_bits, uint8_t out_le32[32]) {
+    t->impl->challenge_scalar(label, (size_t)fr_bits, out_le32);
+}
+int zkt_transcript_challenge_bytes(zkt_transcript* t, const char* label, uint8_t* out, size_t len) {
+    return t->merlin && t->merlin->challenge_bytes(label, out, len) ? ZKT_OK : ZKT_ERR_INVALID_ARGUMENT;
+}
+int zkt_transcript_append_message(zkt_transcript* t, const char* label, const uint8_t* msg, size_t len) {
+    return t->merlin && t->merlin->append_message(label, msg, len) ? ZKT_OK : ZKT_ERR_INVALID_ARGUMENT;
+}
+
+}  // extern "C"
