@@ -110,6 +110,8 @@ int zkt_ctx_synchronize(zkt_ctx* ctx);
  * "check_witness_batch": the same launches of zkt_circuit_check_witness_batch, once for the whole batch.
  * "merkle_append": the copy of the leaves into layer 0 and every level launch of one zkt_merkle_tree_append(_dev);
  * "merkle_paths": the table upload and the gather launch of zkt_merkle_tree_paths / _paths_to_variables_dev.
+ * "withdraw_layout": the two row launches of zkt_withdraw_create / zkt_withdraw_rows / zkt_withdraw_setup;
+ * "withdraw_witness": everything zkt_withdraw_witness enqueues, from the staged requests' copy to the closing kernel.
  * A scope that covers a batch counts its units in `calls` (the three commitments of a round grouped and accumulated as one
  * batch of launches: 3); "<name>#launches" returns the number of recorded scopes instead.
  * on = 0: off; 1: every scope; 2: only "msm_accumulate" and "host_wait" -- the level for timing the dominant kernel
@@ -876,6 +878,105 @@ int zkt_merkle_tree_paths(zkt_ctx* ctx, zkt_merkle_tree* tree, const uint64_t* i
 int zkt_merkle_tree_paths_to_variables_dev(zkt_ctx* ctx, zkt_merkle_tree* tree, const uint64_t* indices, size_t k,
                                            void* d_variables, size_t n_vars, const uint32_t* bit_var0,
                                            const uint32_t* sibling_var0);
+
+/* (5) The withdraw circuit as a component: WithdrawCircuit<F, u64, G, H, INPUTS, HEIGHT>::synthesize
+ * (circuits/src/withdraw.rs:57-150) -- its rows, its setup (the CLI's Compile, bin/src/main.rs:90-112) and the witness of
+ * a batch of withdrawals (ProveWithdraw, bin/src/main.rs:190-300), all made on the device.
+ * zkt_withdraw_create plans the circuit on the host from (Poseidon parameters, INPUTS, HEIGHT): variable numbering and row
+ * order are the reference composer's allocation order.  4 <= width <= 8 (width 3 cannot hash a leaf: three inputs make it
+ * FullBuffer), 1 <= inputs <= 32, 1 <= height <= 64, else ZKT_ERR_INVALID_ARGUMENT.  The plan is one gadget template per
+ * arity (the rows of one PoseidonRef::hash relative to its first variable, selectors from the round constants, the MDS
+ * entries and the domain tag), the list of hash calls, the glue rows (per note 7 H + 4, 130 + INPUTS global ones) and the
+ * INPUTS + 4 public-input positions.  On the device one kernel stamps the hash rows (a thread per hash call and template
+ * row) and one scatters the glue rows.  The handle keeps in HBM the wiring (3 x n_gates x 4 B), the templates, the index
+ * vectors of the witness launches and the staging of the requests; the selector vectors are scratch of the calls that
+ * need them.  It loads and owns a zkt_poseidon of its own: zkt_withdraw_poseidon returns it BORROWED, so that a
+ * zkt_merkle_tree can be bound to the same tables.  Create synchronises. */
+typedef struct zkt_withdraw zkt_withdraw;
+typedef struct {
+    int inputs, height, width;
+    int log_n_min;                     /* the smallest log_n with n_gates <= 2^log_n */
+    size_t n_gates;                    /* inputs ((3 + height) P + 7 height + 4) + 2 P + 130 + inputs, P = vars_per_hash */
+    size_t n_vars;
+    size_t n_hashes;                   /* inputs (3 + height) + 2 */
+    size_t vars_per_hash;
+    size_t n_pi;                       /* inputs + 4 */
+    size_t device_bytes;               /* what the handle holds in HBM (0 from zkt_debug_withdraw_layout_host) */
+} zkt_withdraw_info;
+int zkt_withdraw_create(zkt_ctx* ctx, const zkt_poseidon_params* params, int inputs, int height, zkt_withdraw** out);
+void zkt_withdraw_free(zkt_ctx* ctx, zkt_withdraw* w);
+const zkt_poseidon* zkt_withdraw_poseidon(const zkt_withdraw* w);
+int zkt_withdraw_get_info(const zkt_withdraw* w, zkt_withdraw_info* out);
+/* The n_pi public-input rows, ascending: root, nullifiers, withdraw_amount, new_identifier, new_leaf -- the CLI's order
+ * (bin/src/main.rs:266-271). */
+int zkt_withdraw_pi_pos(const zkt_withdraw* w, size_t* out);
+/* Regenerates the rows on the device and downloads them to HOST memory, n_gates entries each: out_selectors6 = q_m, q_l,
+ * q_r, q_o, q_c, q_lookup (Montgomery words), out_wires3 = w_l, w_r, w_o (ZKT_VARIABLE_ZERO = Variable::Zero).  Either
+ * of the two may be NULL.  Synchronises the stream. */
+int zkt_withdraw_rows(zkt_ctx* ctx, const zkt_withdraw* w, uint64_t* const* out_selectors6, uint32_t* const* out_wires3);
+/* The same rows expanded by the planner on the HOST, with no context and no device: for tests.  info, the row outputs,
+ * out_pi_pos (n_pi) and out_hash_calls (n_hashes x 5 words: first variable, arity, three input variables with
+ * ZKT_VARIABLE_ZERO beyond the arity) are each optional: call once for info, then with buffers of those sizes. */
+int zkt_debug_withdraw_layout_host(int curve_id, const zkt_poseidon_params* params, int inputs, int height, zkt_withdraw_info* info,
+                                   uint64_t* const* out_selectors6, uint32_t* const* out_wires3, size_t* out_pi_pos,
+                                   uint32_t* out_hash_calls);
+/* proof_system::setup of the circuit: the six selector vectors and the q_table mask (0 for the first table_size rows, 1
+ * after, as zkt_circuit_setup documents it) are made on the device and go, with the resident wiring, through
+ * zkt_circuit_setup_wiring with evals_on_device and wiring_on_device set; results and refusals are that call's, plus
+ * ZKT_ERR_INVALID_ARGUMENT for log_n < log_n_min and table_size >= n.  Afterwards the circuit is loaded and the key-file
+ * writers (zkt_circuit_save_files ..) work as after any setup.  Scratch (~200 MB of selectors at n = 2^20) is the call's
+ * own.  Synchronises the stream. */
+int zkt_withdraw_setup(zkt_ctx* ctx, const zkt_withdraw* w, int log_n, size_t table_size, uint64_t* out_commitments,
+                       int* out_is_infinity);
+/* One withdrawal as the CLI assembles it (bin/src/main.rs:198-271).  HOST pointers, scalars in Montgomery words. */
+typedef struct {
+    const uint64_t* secrets;           /* inputs scalars */
+    const uint64_t* identifiers;       /* inputs scalars */
+    const uint64_t* amounts;           /* inputs words */
+    const uint64_t* leaf_indices;      /* inputs words, each below 2^height */
+    const uint64_t* siblings;          /* inputs x height scalars, level 0 first; NULL: taken from `tree` */
+    const uint64_t* root;              /* one scalar; NULL: the tree's root (costs a synchronisation: zkt_merkle_tree_root) */
+    const uint64_t* new_secret;
+    const uint64_t* new_identifier;
+    uint64_t withdraw_amount;
+} zkt_withdraw_request;
+typedef struct {
+    uint32_t bad_paths;                /* bit k: note k's path does not end in the root variable */
+} zkt_withdraw_status;
+/* The whole variable map and the public inputs of `batch` withdrawals (1 <= batch <= ZKT_WITNESS_BATCH_MAX), made on the
+ * device.  d_variables is DEVICE memory: request b's map is the n_vars scalars at d_variables + b * stride (stride >=
+ * n_vars, the layout zkt_circuit_check_witness_batch reads; padding beyond n_vars is never written); batch x stride must
+ * fit the 32-bit variable indices of the gadget kernels.  Refused on the host before anything is enqueued: a sum of
+ * amounts that overflows u64, withdraw_amount above the sum (withdraw.rs:59), a leaf index >= 2^height, siblings == NULL
+ * without a tree or with a tree of another height (ZKT_ERR_INVALID_ARGUMENT); a secret equal to 0
+ * (ZKT_ERR_ZERO_DENOMINATOR: the reference panics on 1 / secret, main.rs:257).  A tree must be bound to
+ * zkt_withdraw_poseidon(w).
+ * Launches, all on the context's stream, their number independent of the batch, no allocation: the staged requests' copy;
+ * (1) a kernel that writes every variable that is neither a hash trace nor a select (amounts, identifiers, root, secrets,
+ * 1 / secret, position bits, siblings, lookup copies, the 64 bits of amount_out and their 63 recombination sums, the
+ * running sums, new_secret, new_identifier) -- with a tree the siblings come from
+ * zkt_merkle_tree_paths_to_variables_dev instead (one call per ZKT_MERKLE_TREE_PATHS_MAX paths: two beyond 4096); (2) zkt_poseidon_gadget_witness_dev for the arity-1 hashes
+ * (commitments, nullifiers, the new commitment); (3) the same for the arity-3 hashes (leaves, the new leaf); (4)
+ * zkt_poseidon_merkle_path_witness_dev for the batch x inputs paths; (5) a kernel that gathers the public inputs and
+ * compares every path's root with the root variable.  The launches' index vectors for every batch slot are made by one
+ * more small kernel when (stride, batch) differ from the previous call's, and kept.
+ * The requests are staged in pinned memory the handle owns: a second call waits for the first one's copy to have left
+ * that buffer, nothing else; the requests' arrays are free on return.
+ * out_pi (optional): batch x n_pi scalars in position order = the CLI's order.  out_status (optional): per request.  When
+ * either is non-NULL the call synchronises; with both NULL it only enqueues (no synchronisation), and zkt_prove with
+ * wires_on_device can follow without a wait.  A wrong sibling is a property of the witness, not an error: the map is
+ * written, the bit is reported and zkt_circuit_check_witness names the equal_constrain row. */
+int zkt_withdraw_witness(zkt_ctx* ctx, zkt_withdraw* w, const zkt_withdraw_request* reqs, size_t batch, zkt_merkle_tree* tree,
+                         void* d_variables, size_t stride, uint64_t* out_pi, zkt_withdraw_status* out_status);
+/* Fills zkt_prove_inputs for request b of such a map: the device wiring and n_rows, n_vars, wires_on_device = 1, the
+ * given public inputs; a_evals .. c_evals are set NULL; table, table_len and blinders are left for the caller. */
+int zkt_withdraw_prove_inputs(const zkt_withdraw* w, const void* d_variables, size_t stride, size_t b, const size_t* pi_pos,
+                              const uint64_t* pi_vals, zkt_prove_inputs* out);
+/* Deposit (bin/src/main.rs:160-163): leaf = H(identifier, amount, H(secret)) for m deposits, DEVICE pointers (m scalars,
+ * m scalars, m words, m scalars out), two launches of the hash-batch kernel; the output feeds zkt_merkle_tree_append_dev
+ * without the host.  The 3 m scalars of scratch are the call's own, so it synchronises the stream before it returns. */
+int zkt_note_leaves(zkt_ctx* ctx, const zkt_poseidon* poseidon, const void* d_secrets, const void* d_identifiers,
+                    const void* d_amounts_u64, size_t m, void* d_out_leaves);
 
 /* ---- Verifier (proof_system/proof.rs:285-503): zkt_verify_prepare = everything but the pairings,
  * ---- zkt_pairing_product_is_one = the pairings, zkt_verify = both ------------------------------------------------

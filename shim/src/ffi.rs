@@ -187,6 +187,24 @@ extern "C" {
     pub fn zkt_dev_alloc(ctx: *mut ZktCtx, bytes: usize, dptr: *mut *mut c_void) -> c_int;
     pub fn zkt_dev_free(ctx: *mut ZktCtx, dptr: *mut c_void) -> c_int;
     pub fn zkt_dev_upload(ctx: *mut ZktCtx, dptr: *mut c_void, host: *const c_void, bytes: usize) -> c_int;
+    // the withdraw circuit as a component (include/zkt_plonk.h "(5) The withdraw circuit")
+    pub fn zkt_withdraw_create(ctx: *mut ZktCtx, params: *const ZktPoseidonParams, inputs: c_int, height: c_int, out: *mut *mut c_void) -> c_int;
+    pub fn zkt_withdraw_free(ctx: *mut ZktCtx, w: *mut c_void);
+    pub fn zkt_withdraw_poseidon(w: *const c_void) -> *const c_void;
+    pub fn zkt_withdraw_get_info(w: *const c_void, out: *mut ZktWithdrawInfo) -> c_int;
+    pub fn zkt_withdraw_pi_pos(w: *const c_void, out: *mut usize) -> c_int;
+    pub fn zkt_withdraw_rows(ctx: *mut ZktCtx, w: *const c_void, out_selectors6: *const *mut u64, out_wires3: *const *mut u32) -> c_int;
+    pub fn zkt_debug_withdraw_layout_host(curve_id: c_int, params: *const ZktPoseidonParams, inputs: c_int, height: c_int,
+                                          info: *mut ZktWithdrawInfo, out_selectors6: *const *mut u64, out_wires3: *const *mut u32,
+                                          out_pi_pos: *mut usize, out_hash_calls: *mut u32) -> c_int;
+    pub fn zkt_withdraw_setup(ctx: *mut ZktCtx, w: *const c_void, log_n: c_int, table_size: usize, out_commitments: *mut u64,
+                              out_is_infinity: *mut c_int) -> c_int;
+    pub fn zkt_withdraw_witness(ctx: *mut ZktCtx, w: *mut c_void, reqs: *const ZktWithdrawRequest, batch: usize, tree: *mut c_void,
+                                d_variables: *mut c_void, stride: usize, out_pi: *mut u64, out_status: *mut ZktWithdrawStatus) -> c_int;
+    pub fn zkt_withdraw_prove_inputs(w: *const c_void, d_variables: *const c_void, stride: usize, b: usize, pi_pos: *const usize,
+                                     pi_vals: *const u64, out: *mut ZktProveInputs) -> c_int;
+    pub fn zkt_note_leaves(ctx: *mut ZktCtx, poseidon: *const c_void, d_secrets: *const c_void, d_identifiers: *const c_void,
+                           d_amounts_u64: *const c_void, m: usize, d_out_leaves: *mut c_void) -> c_int;
 }
 
 /// include/zkt_comm_rccl.h: the optional RCCL transport (libzkt_comm_rccl.so), INTEGRATION.md section 3c
@@ -250,4 +268,36 @@ pub struct ZktPoseidonParams {
     pub round_constants: *const u64,
     pub mds: *const u64,
     pub domain_tag: *const u64,
+}
+
+#[repr(C)]
+pub struct ZktWithdrawInfo {
+    pub inputs: c_int,
+    pub height: c_int,
+    pub width: c_int,
+    pub log_n_min: c_int,
+    pub n_gates: usize,
+    pub n_vars: usize,
+    pub n_hashes: usize,
+    pub vars_per_hash: usize,
+    pub n_pi: usize,
+    pub device_bytes: usize,
+}
+
+#[repr(C)]
+pub struct ZktWithdrawRequest {
+    pub secrets: *const u64,
+    pub identifiers: *const u64,
+    pub amounts: *const u64,
+    pub leaf_indices: *const u64,
+    pub siblings: *const u64,
+    pub root: *const u64,
+    pub new_secret: *const u64,
+    pub new_identifier: *const u64,
+    pub withdraw_amount: u64,
+}
+
+#[repr(C)]
+pub struct ZktWithdrawStatus {
+    pub bad_paths: u32,
 }

@@ -13,6 +13,8 @@ Host-side mirror of the reference's two generic seams:
                          device, its paths written straight into the variable map
 * ``WitnessPlan``      ~ the witness completed on the device from the circuit's free variables (the composer's direct
                          ``assign_variable`` calls), with the public inputs it implies
+* ``WithdrawCircuit``  ~ ``WithdrawCircuit<F, u64, G, H, INPUTS, HEIGHT>`` (circuits/src/withdraw.rs:57-150): its rows, its setup and
+                         the witness of a batch of withdrawals, made on the device
 * ``parallel``         ~ one proof or many across the GPUs of a node (communicators, SRS slices)
 
 These are thin ctypes mirrors for the tests and ``bench.py``; the product is the C-ABI (include/zkt_plonk.h).
@@ -29,7 +31,8 @@ from .prover import GpuProver, GpuKZG10, seed_transcript, PK_ORDER, NUM_BLINDERS
 from .poseidon import PoseidonGadget  # noqa: F401
 from .merkle import MerkleTree  # noqa: F401
 from .witness import WitnessPlan  # noqa: F401
+from .withdraw import WithdrawCircuit  # noqa: F401
 
-__all__ = ["Context", "ZktError", "Transcript", "GpuDomain", "GpuProver", "GpuKZG10", "PoseidonGadget", "MerkleTree", "WitnessPlan", "seed_transcript", "PK_ORDER",
+__all__ = ["Context", "ZktError", "Transcript", "GpuDomain", "GpuProver", "GpuKZG10", "PoseidonGadget", "MerkleTree", "WitnessPlan", "WithdrawCircuit", "seed_transcript", "PK_ORDER",
            "NUM_BLINDERS", "lib", "lib_path", "CURVE_BN254", "CURVE_BLS12_381", "curve_id", "declared_symbols",
            "WitnessCheck", "WitnessReport", "CHECK_WIRING", "CHECK_NONE", "SrsCheck", "SrsReport"]

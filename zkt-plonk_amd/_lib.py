@@ -627,6 +627,75 @@ class ProveInputs(ctypes.Structure):
                 ("w_o", ctypes.POINTER(ctypes.c_uint32))]
 
 
+class PoseidonParamsStruct(ctypes.Structure):
+    """zkt_poseidon_params"""
+    _fields_ = [("width", ctypes.c_int), ("half_full_rounds", ctypes.c_int), ("partial_rounds", ctypes.c_int),
+                ("round_constants", ctypes.POINTER(ctypes.c_uint64)), ("mds", ctypes.POINTER(ctypes.c_uint64)),
+                ("domain_tag", ctypes.POINTER(ctypes.c_uint64))]
+
+
+def poseidon_params_struct(width, half_full, partial, round_constants, mds, domain_tag):
+    """-> (zkt_poseidon_params, the arrays it points into); all constants as Montgomery words."""
+    rc = np.ascontiguousarray(round_constants, dtype=np.uint64).reshape(-1, 4)
+    m = np.ascontiguousarray(mds, dtype=np.uint64).reshape(-1, 4)
+    tag = np.ascontiguousarray(domain_tag, dtype=np.uint64).reshape(4)
+    assert rc.shape[0] == (2 * half_full + partial) * width and m.shape[0] == width * width
+    return PoseidonParamsStruct(width, half_full, partial, u64p(rc), u64p(m), u64p(tag)), (rc, m, tag)
+
+
+class WithdrawInfo(ctypes.Structure):
+    """zkt_withdraw_info"""
+    _fields_ = [("inputs", ctypes.c_int), ("height", ctypes.c_int), ("width", ctypes.c_int), ("log_n_min", ctypes.c_int),
+                ("n_gates", ctypes.c_size_t), ("n_vars", ctypes.c_size_t), ("n_hashes", ctypes.c_size_t),
+                ("vars_per_hash", ctypes.c_size_t), ("n_pi", ctypes.c_size_t), ("device_bytes", ctypes.c_size_t)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class WithdrawRequest(ctypes.Structure):
+    """zkt_withdraw_request"""
+    _fields_ = [(k, ctypes.POINTER(ctypes.c_uint64)) for k in ("secrets", "identifiers", "amounts", "leaf_indices", "siblings", "root",
+                                                               "new_secret", "new_identifier")] + [("withdraw_amount", ctypes.c_uint64)]
+
+
+def _withdraw_row_buffers(n_gates, rows, wires):
+    P64, P32 = ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)
+    sel = [np.zeros((n_gates, 4), dtype=np.uint64) for _ in range(6)] if rows else None
+    w = [np.zeros(n_gates, dtype=np.uint32) for _ in range(3)] if wires else None
+    sp = (P64 * 6)(*[u64p(a) for a in sel]) if rows else None
+    wp = (P32 * 3)(*[a.ctypes.data_as(P32) for a in w]) if wires else None
+    return sel, w, sp, wp
+
+
+def debug_withdraw_layout_host(curve, params, inputs: int, height: int, rows: bool = True):
+    """zkt_debug_withdraw_layout_host: the withdraw circuit's rows as the host planner expands them (no device).  params:
+    (width, half_full, partial, round_constants, mds, domain_tag) in Montgomery words.  -> dict with the info fields and, with
+    rows, `selectors` (six (n_gates, 4) arrays: q_m, q_l, q_r, q_o, q_c, q_lookup), `wires` (three uint32 arrays), `pi_pos` and
+    `hash_calls` ((n_hashes, 5): first variable, arity, three input variables)."""
+    L = lib()
+    P64, P32 = ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)
+    L.zkt_debug_withdraw_layout_host.argtypes = [ctypes.c_int, ctypes.POINTER(PoseidonParamsStruct), ctypes.c_int, ctypes.c_int,
+                                                 ctypes.POINTER(WithdrawInfo), ctypes.POINTER(P64), ctypes.POINTER(P32),
+                                                 ctypes.POINTER(ctypes.c_size_t), P32]
+    prm, keep = poseidon_params_struct(*params)
+    info = WithdrawInfo()
+    rc = L.zkt_debug_withdraw_layout_host(curve_id(curve), ctypes.byref(prm), inputs, height, ctypes.byref(info), None, None, None, None)
+    if rc:
+        raise ZktError(rc, "zkt_debug_withdraw_layout_host")
+    out = info.as_dict()
+    if rows:
+        sel, w, sp, wp = _withdraw_row_buffers(out["n_gates"], True, True)
+        pos = (ctypes.c_size_t * out["n_pi"])()
+        calls = np.zeros((out["n_hashes"], 5), dtype=np.uint32)
+        rc = L.zkt_debug_withdraw_layout_host(curve_id(curve), ctypes.byref(prm), inputs, height, None, sp, wp, pos,
+                                              calls.ctypes.data_as(P32))
+        if rc:
+            raise ZktError(rc, "zkt_debug_withdraw_layout_host")
+        out.update(selectors=sel, wires=w, pi_pos=[int(x) for x in pos], hash_calls=calls)
+    return out
+
+
 class WitnessReport(ctypes.Structure):
     """zkt_witness_report"""
     _fields_ = [("satisfied", ctypes.c_int), ("checked", ctypes.c_int),
@@ -1298,6 +1367,114 @@ class Context:
         rc = L.zkt_debug_merkle_tree_split(ctypes.c_void_p(tree), wide_min_parents)
         if rc:
             raise ZktError(rc, "zkt_debug_merkle_tree_split: null tree or negative threshold")
+
+    # -- the withdraw circuit as a component (csrc/withdraw.hip) ----------------------------------------------
+    def withdraw_create(self, params, inputs: int, height: int) -> int:
+        """zkt_withdraw_create: params = (width, half_full, partial, round_constants, mds, domain_tag) -> opaque handle."""
+        L, vp = self._L, ctypes.c_void_p
+        L.zkt_withdraw_create.argtypes = [vp, ctypes.POINTER(PoseidonParamsStruct), ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp)]
+        prm, keep = poseidon_params_struct(*params)
+        w = vp()
+        self.check(L.zkt_withdraw_create(self._h, ctypes.byref(prm), inputs, height, ctypes.byref(w)))
+        return w.value
+
+    def withdraw_free(self, w: int):
+        L = self._L
+        L.zkt_withdraw_free.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        L.zkt_withdraw_free.restype = None
+        L.zkt_withdraw_free(self._h, ctypes.c_void_p(w))
+
+    def withdraw_poseidon(self, w: int) -> int:
+        """zkt_withdraw_poseidon: the handle's own zkt_poseidon, borrowed (bind a MerkleTree to it)."""
+        L = self._L
+        L.zkt_withdraw_poseidon.argtypes = [ctypes.c_void_p]
+        L.zkt_withdraw_poseidon.restype = ctypes.c_void_p
+        return L.zkt_withdraw_poseidon(ctypes.c_void_p(w))
+
+    def withdraw_get_info(self, w: int) -> dict:
+        L = self._L
+        L.zkt_withdraw_get_info.argtypes = [ctypes.c_void_p, ctypes.POINTER(WithdrawInfo)]
+        info = WithdrawInfo()
+        rc = L.zkt_withdraw_get_info(ctypes.c_void_p(w), ctypes.byref(info))
+        if rc:
+            raise ZktError(rc, "zkt_withdraw_get_info: null handle")
+        return info.as_dict()
+
+    def withdraw_pi_pos(self, w: int):
+        L = self._L
+        L.zkt_withdraw_pi_pos.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_size_t)]
+        pos = (ctypes.c_size_t * self.withdraw_get_info(w)["n_pi"])()
+        rc = L.zkt_withdraw_pi_pos(ctypes.c_void_p(w), pos)
+        if rc:
+            raise ZktError(rc, "zkt_withdraw_pi_pos: null handle")
+        return [int(x) for x in pos]
+
+    def withdraw_rows(self, w: int, selectors: bool = True, wires: bool = True):
+        """zkt_withdraw_rows: the rows regenerated on the device -> (six (n_gates, 4) selector arrays or None, three uint32
+        wire arrays or None)."""
+        L, vp = self._L, ctypes.c_void_p
+        P64, P32 = ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)
+        L.zkt_withdraw_rows.argtypes = [vp, vp, ctypes.POINTER(P64), ctypes.POINTER(P32)]
+        sel, wr, sp, wp = _withdraw_row_buffers(self.withdraw_get_info(w)["n_gates"], selectors, wires)
+        self.check(L.zkt_withdraw_rows(self._h, vp(w), sp, wp))
+        return sel, wr
+
+    def withdraw_setup(self, w: int, log_n: int, table_size: int):
+        """zkt_withdraw_setup -> (commitments, is_infinity) as circuit_setup; leaves the circuit loaded."""
+        L, vp = self._L, ctypes.c_void_p
+        L.zkt_withdraw_setup.argtypes = [vp, vp, ctypes.c_int, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int)]
+        out = np.zeros((10, 2 * self.fq_limbs), dtype=np.uint64)
+        inf = (ctypes.c_int * 10)()
+        self.check(L.zkt_withdraw_setup(self._h, vp(w), log_n, table_size, u64p(out), inf))
+        self.circuit_log_n = log_n
+        return out, np.array([bool(x) for x in inf])
+
+    def withdraw_witness(self, w: int, requests, d_variables: int, stride: int, tree: int = 0, want_pi: bool = True,
+                         want_status: bool = True):
+        """zkt_withdraw_witness.  requests: dicts with secrets, identifiers (inputs x 4 Montgomery words), amounts,
+        leaf_indices (inputs words), siblings ((inputs, height, 4) or None), root ((4,) or None), new_secret, new_identifier
+        ((4,)), withdraw_amount.  -> (public inputs (batch, n_pi, 4) or None, [bad_paths] or None); with neither wanted the
+        call only enqueues."""
+        L, vp = self._L, ctypes.c_void_p
+        L.zkt_withdraw_witness.argtypes = [vp, vp, ctypes.POINTER(WithdrawRequest), ctypes.c_size_t, vp, vp, ctypes.c_size_t,
+                                           ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
+        keep, reqs = [], (WithdrawRequest * max(1, len(requests)))()
+        null = ctypes.POINTER(ctypes.c_uint64)()
+        for r, q in zip(reqs, requests):
+            for k in ("secrets", "identifiers", "amounts", "leaf_indices", "siblings", "root", "new_secret", "new_identifier"):
+                if q.get(k) is None:
+                    setattr(r, k, null)
+                else:
+                    a = np.ascontiguousarray(q[k], dtype=np.uint64).reshape(-1)
+                    keep.append(a)
+                    setattr(r, k, u64p(a))
+            r.withdraw_amount = int(q["withdraw_amount"])
+        n_pi = self.withdraw_get_info(w)["n_pi"]
+        pi = np.zeros((len(requests), n_pi, 4), dtype=np.uint64) if want_pi else None
+        st = (ctypes.c_uint32 * max(1, len(requests)))() if want_status else None
+        self.check(L.zkt_withdraw_witness(self._h, vp(w), reqs, len(requests), vp(tree) if tree else None, vp(d_variables) if d_variables else None,
+                                          stride, u64p(pi) if want_pi else None, st))
+        return pi, ([int(x) for x in st[:len(requests)]] if want_status else None)
+
+    def withdraw_prepare(self, w: int, d_variables: int, stride: int, b: int, table, pi_vals, blinders) -> "PreparedInputs":
+        """zkt_withdraw_prove_inputs for request b of a map made by withdraw_witness, with the caller's table, public-input
+        values (in position order) and blinders."""
+        L, vp = self._L, ctypes.c_void_p
+        L.zkt_withdraw_prove_inputs.argtypes = [vp, vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t),
+                                                ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ProveInputs)]
+        null = ctypes.POINTER(ctypes.c_uint64)()
+        prep = self._prepare((null, null, null), 0, table, self.withdraw_pi_pos(w), pi_vals, blinders, True)
+        rc = L.zkt_withdraw_prove_inputs(vp(w), vp(d_variables), stride, b, prep.struct.pi_pos, prep.struct.pi_vals, ctypes.byref(prep.struct))
+        if rc:
+            raise ZktError(rc, "zkt_withdraw_prove_inputs: null pointer or stride below n_vars")
+        return prep
+
+    def note_leaves(self, poseidon_handle: int, d_secrets: int, d_identifiers: int, d_amounts: int, m: int, d_out_leaves: int):
+        """zkt_note_leaves: leaf = H(identifier, amount, H(secret)) for m deposits, device pointers; synchronises."""
+        L, vp = self._L, ctypes.c_void_p
+        L.zkt_note_leaves.argtypes = [vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
+        self.check(L.zkt_note_leaves(self._h, vp(poseidon_handle), vp(d_secrets) if d_secrets else None, vp(d_identifiers) if d_identifiers else None,
+                                     vp(d_amounts) if d_amounts else None, m, vp(d_out_leaves) if d_out_leaves else None))
 
     # -- witness completion from the free variables (csrc/witness_plan.hip) ---------------------------------
     def witness_plan_create(self, w_l, w_r, w_o, n_vars: int, pi_pos=(), n_rows: int = None, rules: int = 0) -> int:
