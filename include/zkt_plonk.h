@@ -830,9 +830,8 @@ int zkt_poseidon_merkle_path_validate(zkt_ctx* ctx, const zkt_poseidon* params, 
  * call enqueues on the stream of the context it is given -- use one context per tree, or order the streams yourself.  Any
  * context will do: forked, with a communicator (the tree is local, no collective is made), with or without SRS or circuit
  * -- the tree touches none of their memory.  Everything in Montgomery words.
- * Out of scope: reading or writing the reference's serialised MerkleTreeStore file (zkt_merkle_tree_layer of layer 0 and an
- * append of what it returned is the persistence path); deleting or updating leaves (the reference has neither); a tree
- * sharded over ranks. */
+ * The reference's serialised MerkleTreeStore file is written and read by zkt_merkle_tree_save_file / _load_file ("(4b) The
+ * store files" below).  Out of scope: deleting or updating leaves (the reference has neither); a tree sharded over ranks. */
 #define ZKT_MERKLE_TREE_MAX ((size_t)1 << 24)      /* most leaves a tree holds */
 #define ZKT_MERKLE_TREE_PATHS_MAX 4096             /* most paths one zkt_merkle_tree_paths* call takes */
 typedef struct zkt_merkle_tree zkt_merkle_tree;
@@ -879,6 +878,57 @@ int zkt_merkle_tree_paths_to_variables_dev(zkt_ctx* ctx, zkt_merkle_tree* tree, 
                                            void* d_variables, size_t n_vars, const uint32_t* bit_var0,
                                            const uint32_t* sibling_var0);
 
+/* (4b) The store files: the two files the reference CLI keeps its state in, --merkle-tree (MerkleTreeStore,
+ * gadgets/src/merkle_tree.rs:8-13) and --notes (Notes, gadgets/src/note.rs), read by ProveWithdraw, Deposit, InitStore and
+ * ListNotes.  Both are serialize_unchecked output (bin/src/parser.rs); the byte layouts (csrc/storefile.hpp) are DERIVED from
+ * ark-serialize 0.3's rules, as the key files' are: usize and u64 are 8 bytes little endian, a scalar is 32 canonical
+ * little-endian bytes on both curves, a Vec or BTreeMap is a u64 length and then its items (a map's in ascending key order).
+ * The reference holds no such file, so no reference-made file has ever been compared ("parity unpinned").
+ *   MerkleTreeStore: u64 E; E entries (u64 layer, u64 idx, scalar) in ascending (layer, idx) order; the scalar root; u64
+ *                    next_index.  MerkleTreeStore::default() is 48 bytes.  After add_leaf of `count` leaves the map holds, for
+ *                    every layer L in [0, HEIGHT), exactly the indices 0 .. ceil(count / 2^L) - 1 (merkle_tree.rs:92-95): what
+ *                    zkt_merkle_tree_layer returns.  HEIGHT is not in the file; it is max layer + 1.
+ *   Notes:           u64 count; per note u64 leaf_index, scalar identifier, u64 amount, scalar secret (80 bytes).
+ * With the key files (zkt_keyfile_*, zkt_srs_*_file, zkt_circuit_*_file) these are all the files of a reference data directory
+ * but one: the --cvk file is NOT read or written.  Its type comes from ark-poly-commit, whose source is not in the reference
+ * tree, so its layout cannot be derived here.
+ *
+ * zkt_merkle_tree_save_file: the tree as a MerkleTreeStore file.  Synchronises; the layers come out in bounded chunks through
+ * pinned staging, into a temporary sibling of `path` that is renamed into place (a failed call leaves neither).  An empty
+ * tree writes the 48-byte default store.  Errors: ZKT_ERR_INVALID_ARGUMENT with the path in the message (also kept for
+ * zkt_keyfile_last_error). */
+int zkt_merkle_tree_save_file(zkt_ctx* ctx, zkt_merkle_tree* tree, const char* path);
+/* What zkt_merkle_tree_load_file found.  entries: the file's E.  mismatches: stored nodes of the file (the root not among
+ * them) that differ from the rebuilt tree's; first_layer / first_idx: the smallest such (layer, idx), -1 / 0 when there is
+ * none; root_matches: 1 when the file's root is the rebuilt one. */
+typedef struct {
+    uint64_t entries, mismatches;
+    int first_layer;
+    uint64_t first_idx;
+    int root_matches;
+} zkt_tree_file_report;
+/* Reads a MerkleTreeStore file into a new tree of (height, capacity) bound to `poseidon` (as zkt_merkle_tree_create; *out is
+ * the caller's to free) and checks the file against it, the way zkt_srs_check treats a committer key.  The file is parsed on
+ * the host, in chunks; ZKT_ERR_INVALID_ARGUMENT, with a message naming the path and the byte offset, for: a file that is
+ * truncated or has trailing bytes (its size is not 48 + 48 E); a scalar not below the modulus; keys that are not ascending;
+ * keys that are not exactly the dense set of next_index leaves under `height` (a key outside it, or too few entries);
+ * next_index > capacity.  Nothing is created then.  Otherwise layer 0 is uploaded and appended through
+ * zkt_merkle_tree_append_dev, so the tree kept is self-consistent whatever the file says above layer 0, and EVERY stored node
+ * of every layer and the root are compared with the rebuilt ones on the device: one launch over all the file's nodes (they go
+ * up in the same bounded chunks; the file is never whole in host memory), a lane per node.  A mismatch is a finding, not an
+ * error: ZKT_OK with the rebuilt tree, and the caller decides.  report may be NULL.  Scratch (48 B per entry and 32 B per
+ * leaf) is the call's own and freed before it returns.  Synchronises. */
+int zkt_merkle_tree_load_file(zkt_ctx* ctx, const zkt_poseidon* poseidon, int height, size_t capacity, const char* path,
+                              zkt_merkle_tree** out, zkt_tree_file_report* report);
+/* The --notes file.  Host-only, no context; errors are ZKT_ERR_INVALID_ARGUMENT with the text (path, offset) in
+ * zkt_keyfile_last_error.  Scalars are Montgomery words.  Read is two-call: with any output NULL only *count is written;
+ * with all four, `cap` notes fit (a file with more -> ZKT_ERR_INVALID_ARGUMENT).  Truncated files, trailing bytes and scalars
+ * not below the modulus are refused.  Write goes through a temporary sibling, as the key-file writers do. */
+int zkt_notes_read_file(const char* path, int curve_id, size_t cap, uint64_t* out_leaf_indices, uint64_t* out_identifiers_mont,
+                        uint64_t* out_amounts, uint64_t* out_secrets_mont, size_t* count);
+int zkt_notes_write_file(const char* path, int curve_id, const uint64_t* leaf_indices, const uint64_t* identifiers_mont,
+                         const uint64_t* amounts, const uint64_t* secrets_mont, size_t count);
+
 /* (5) The withdraw circuit as a component: WithdrawCircuit<F, u64, G, H, INPUTS, HEIGHT>::synthesize
  * (circuits/src/withdraw.rs:57-150) -- its rows, its setup (the CLI's Compile, bin/src/main.rs:90-112) and the witness of
  * a batch of withdrawals (ProveWithdraw, bin/src/main.rs:190-300), all made on the device.
@@ -901,7 +951,8 @@ typedef struct {
     size_t n_hashes;                   /* inputs (3 + height) + 2 */
     size_t vars_per_hash;
     size_t n_pi;                       /* inputs + 4 */
-    size_t device_bytes;               /* what the handle holds in HBM (0 from zkt_debug_withdraw_layout_host) */
+    size_t device_bytes;               /* what the handle holds in HBM (0 from zkt_debug_withdraw_layout_host); 128 KiB of it
+                                          (ZKT_WITHDRAW_PROVE_MAX scalars) is the staging of zkt_withdraw_prove's new leaves */
 } zkt_withdraw_info;
 int zkt_withdraw_create(zkt_ctx* ctx, const zkt_poseidon_params* params, int inputs, int height, zkt_withdraw** out);
 void zkt_withdraw_free(zkt_ctx* ctx, zkt_withdraw* w);
@@ -977,6 +1028,57 @@ int zkt_withdraw_prove_inputs(const zkt_withdraw* w, const void* d_variables, si
  * without the host.  The 3 m scalars of scratch are the call's own, so it synchronises the stream before it returns. */
 int zkt_note_leaves(zkt_ctx* ctx, const zkt_poseidon* poseidon, const void* d_secrets, const void* d_identifiers,
                     const void* d_amounts_u64, size_t m, void* d_out_leaves);
+
+/* ProveWithdraw (bin/src/main.rs:190-319) for a batch of requests in ONE call: the identifiers set deduplicated into the
+ * lookup table, the witness (zkt_withdraw_witness), one proof per request under a transcript seeded from the loaded circuit's
+ * own commitments and n (zkt_prove), the CLI's check of each proof (zkt_verify, main.rs:298) and the new leaves added to the
+ * tree (main.rs:302-304).  Needs what zkt_prove needs: an SRS and the withdraw circuit loaded (zkt_withdraw_setup, or
+ * zkt_circuit_load / _load_file of its ProverKey). */
+#define ZKT_WITHDRAW_PROVE_MAX 4096                /* most requests one zkt_withdraw_prove takes */
+typedef struct {
+    int transcript_kind; const char* label;          /* T::new("ZKT Plonk"), plonk.rs:107 */
+    const uint64_t* identifiers_set; size_t set_len; /* Montgomery; a repeated value is dropped, the first kept
+                                                        (IndexSet::from_iter, lookup/table.rs:64-72); > table_size refused */
+    const uint64_t* blinders;                        /* batch x 19, the order zkt_prove documents */
+    int verify;                                      /* != 0: zkt_verify each proof (main.rs:298); needs the next three */
+    const uint64_t* g_xy_mont; const uint64_t* h_g2_mont; const uint64_t* beta_h_g2_mont;
+    int append;                                      /* != 0: add the new leaves to `tree` (main.rs:302-304) */
+    void* d_variables; size_t stride; size_t slots;  /* caller's workspace: `slots` maps, as zkt_withdraw_witness reads it */
+} zkt_withdraw_prove_args;
+typedef struct { int code; uint32_t bad_paths; int verified; uint64_t new_leaf_index; } zkt_withdraw_result;
+/* proofs: batch x proof_stride bytes (proof_stride >= 802 on BN254, 1010 on BLS12-381), request b's proof at b x proof_stride;
+ * out_pi (optional): batch x n_pi scalars, the CLI-order public inputs; results: batch entries.
+ * Snapshot.  The whole batch is proved against the tree as it is at the call: one root, like the withdrawals of one block
+ *   (nothing is appended before the last proof).  The CLI's one-at-a-time behaviour is batch = 1.  Paths and roots come from
+ *   `tree` or from reqs[b].siblings / .root, exactly as in zkt_withdraw_witness.
+ * Chunking.  1 <= slots <= ZKT_WITNESS_BATCH_MAX maps of `stride` scalars at d_variables.  The batch is worked in chunks of
+ *   `slots` requests: one zkt_withdraw_witness per chunk, whose public inputs and bad_paths come to the host (one
+ *   synchronisation a chunk), then the chunk's proofs, each announced to its predecessor with zkt_prove_set_next.  The chain
+ *   does not cross a chunk boundary (the next chunk's maps do not exist yet).  Proof bytes depend neither on that nor on
+ *   `slots`.  An announcement the caller made before the call is withdrawn.
+ * Table.  The deduplicated set is every proof's lookup table.  More values than the table size are refused
+ *   (ZKT_ERR_INVALID_ARGUMENT, "table size exceeds max size", lookup/table.rs:57): the size zkt_withdraw_setup was given when
+ *   it set the loaded circuit up (kept with the circuit), n - 1 (zkt_prove's own bound) under a circuit loaded another way.
+ * Per-request results.  Whatever zkt_withdraw_witness would refuse on the host -- for any request of the batch -- fails the
+ *   whole call before anything is enqueued, as do a null pointer, batch outside 1 .. ZKT_WITHDRAW_PROVE_MAX, slots or stride
+ *   out of range, a proof_stride too short, an unknown transcript kind and, with append != 0, a missing tree or one without
+ *   room for `batch` more leaves.  After that: a request whose bad_paths != 0 is not proved (code = ZKT_ERR_INVALID_ARGUMENT,
+ *   its proof bytes zeroed); a request zkt_prove refuses keeps that code (ZKT_ERR_NOT_IN_TABLE for an identifier outside the
+ *   set, ZKT_ERR_EQUAL_CHALLENGES, ZKT_ERR_ZERO_DENOMINATOR, ZKT_ERR_QUOTIENT_TOO_SHORT; proof bytes zeroed); the batch goes
+ *   on in both cases, and the successor of a refused proof is proved like any other (its early rounds are simply issued
+ *   again).  Any other failure of zkt_prove ends the call with that code.  verified: 1 when verify != 0 and zkt_verify
+ *   accepted the proof under out_pi, else 0.  The return value is ZKT_OK unless the call as a whole failed.
+ * Append.  After the last proof the new leaves of the requests that were proved -- with verify != 0: proved and verified --
+ *   are appended in request order through ONE zkt_merkle_tree_append_dev.  They never visit the host: a small kernel gathers
+ *   them chunk by chunk from the maps' new-leaf variable into staging the handle owns.  new_leaf_index is the leaf's index
+ *   for those requests and UINT64_MAX for all others.  Nothing is appended when there is none.
+ * The call allocates no device memory (the first call under a circuit that zkt_withdraw_setup did not make, or after the SRS
+ * was loaded again, makes the circuit's commitments once, zkt_circuit_commitments, and keeps them with the circuit),
+ * synchronises once more at its end, and leaves the context
+ * ready for the next proof on every path: no announcement pending. */
+int zkt_withdraw_prove(zkt_ctx* ctx, zkt_withdraw* w, const zkt_withdraw_request* reqs, size_t batch, zkt_merkle_tree* tree,
+                       const zkt_withdraw_prove_args* args, uint8_t* proofs, size_t proof_stride, uint64_t* out_pi,
+                       zkt_withdraw_result* results);
 
 /* ---- Verifier (proof_system/proof.rs:285-503): zkt_verify_prepare = everything but the pairings,
  * ---- zkt_pairing_product_is_one = the pairings, zkt_verify = both ------------------------------------------------
@@ -1412,6 +1514,9 @@ int zkt_debug_live_allocations(uint64_t* count, uint64_t* bytes);
  * level in LDS, a wider one is a launch of its own whatever is asked), 0 restores the policy.  Tests use it to run both
  * kernels on every level of small trees.  A negative value gives ZKT_ERR_INVALID_ARGUMENT. */
 int zkt_debug_merkle_tree_split(zkt_merkle_tree* tree, int wide_min_parents);
+/* How many nodes one staging chunk of zkt_merkle_tree_save_file / _load_file holds, on this context: 0 restores the default
+ * (2^16).  Tests shrink it so that a small file crosses several chunks.  Null context -> ZKT_ERR_INVALID_ARGUMENT. */
+int zkt_debug_store_chunk(zkt_ctx* ctx, size_t nodes);
 /* Self-check of the host pairing's shortcuts against their plain definitions (Frobenius maps = powers by p, sparse
  * and cyclotomic products = dense ones, the final exponentiation leaves an element of order r).  0 = all good. */
 int zkt_debug_pairing_selftest(int curve_id);

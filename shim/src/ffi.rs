@@ -183,6 +183,16 @@ extern "C" {
                                                   d_variables: *mut c_void, n_vars: usize, bit_var0: *const u32,
                                                   sibling_var0: *const u32) -> c_int;
     pub fn zkt_debug_merkle_tree_split(tree: *mut c_void, wide_min_parents: c_int) -> c_int;
+    // the reference CLI's store files (--merkle-tree, --notes): include/zkt_plonk.h "(4b) The store files"
+    pub fn zkt_merkle_tree_save_file(ctx: *mut ZktCtx, tree: *mut c_void, path: *const c_char) -> c_int;
+    pub fn zkt_merkle_tree_load_file(ctx: *mut ZktCtx, poseidon: *const c_void, height: c_int, capacity: usize, path: *const c_char,
+                                     out: *mut *mut c_void, report: *mut ZktTreeFileReport) -> c_int;
+    pub fn zkt_notes_read_file(path: *const c_char, curve_id: c_int, cap: usize, out_leaf_indices: *mut u64,
+                               out_identifiers_mont: *mut u64, out_amounts: *mut u64, out_secrets_mont: *mut u64,
+                               count: *mut usize) -> c_int;
+    pub fn zkt_notes_write_file(path: *const c_char, curve_id: c_int, leaf_indices: *const u64, identifiers_mont: *const u64,
+                                amounts: *const u64, secrets_mont: *const u64, count: usize) -> c_int;
+    pub fn zkt_debug_store_chunk(ctx: *mut ZktCtx, nodes: usize) -> c_int;
     pub fn zkt_debug_live_allocations(count: *mut u64, bytes: *mut u64) -> c_int;
     pub fn zkt_dev_alloc(ctx: *mut ZktCtx, bytes: usize, dptr: *mut *mut c_void) -> c_int;
     pub fn zkt_dev_free(ctx: *mut ZktCtx, dptr: *mut c_void) -> c_int;
@@ -205,6 +215,10 @@ extern "C" {
                                      pi_vals: *const u64, out: *mut ZktProveInputs) -> c_int;
     pub fn zkt_note_leaves(ctx: *mut ZktCtx, poseidon: *const c_void, d_secrets: *const c_void, d_identifiers: *const c_void,
                            d_amounts_u64: *const c_void, m: usize, d_out_leaves: *mut c_void) -> c_int;
+    // ProveWithdraw in one call: witness, proofs, their check and the append of the new leaves
+    pub fn zkt_withdraw_prove(ctx: *mut ZktCtx, w: *mut c_void, reqs: *const ZktWithdrawRequest, batch: usize, tree: *mut c_void,
+                              args: *const ZktWithdrawProveArgs, proofs: *mut u8, proof_stride: usize, out_pi: *mut u64,
+                              results: *mut ZktWithdrawResult) -> c_int;
 }
 
 /// include/zkt_comm_rccl.h: the optional RCCL transport (libzkt_comm_rccl.so), INTEGRATION.md section 3c
@@ -300,4 +314,41 @@ pub struct ZktWithdrawRequest {
 #[repr(C)]
 pub struct ZktWithdrawStatus {
     pub bad_paths: u32,
+}
+
+/// zkt_withdraw_prove_args
+#[repr(C)]
+pub struct ZktWithdrawProveArgs {
+    pub transcript_kind: c_int,
+    pub label: *const c_char,
+    pub identifiers_set: *const u64,
+    pub set_len: usize,
+    pub blinders: *const u64,
+    pub verify: c_int,
+    pub g_xy_mont: *const u64,
+    pub h_g2_mont: *const u64,
+    pub beta_h_g2_mont: *const u64,
+    pub append: c_int,
+    pub d_variables: *mut c_void,
+    pub stride: usize,
+    pub slots: usize,
+}
+
+/// zkt_withdraw_result
+#[repr(C)]
+pub struct ZktWithdrawResult {
+    pub code: c_int,
+    pub bad_paths: u32,
+    pub verified: c_int,
+    pub new_leaf_index: u64,
+}
+
+/// zkt_tree_file_report: how a MerkleTreeStore file compares with the tree rebuilt from its leaves
+#[repr(C)]
+pub struct ZktTreeFileReport {
+    pub entries: u64,
+    pub mismatches: u64,
+    pub first_layer: c_int,
+    pub first_idx: u64,
+    pub root_matches: c_int,
 }

@@ -375,6 +375,43 @@ def _writer_check(rc: int, what: str):
         raise ZktError(rc, keyfile_last_error() or what)
 
 
+def notes_write_file(path: str, curve, leaf_indices, identifiers, amounts, secrets):
+    """zkt_notes_write_file: the reference CLI's --notes file from leaf indices, identifiers (k, 4), amounts and secrets (k, 4),
+    scalars in Montgomery words (host only)."""
+    L = lib()
+    P64 = ctypes.POINTER(ctypes.c_uint64)
+    li = np.ascontiguousarray(leaf_indices, dtype=np.uint64).reshape(-1)
+    am = np.ascontiguousarray(amounts, dtype=np.uint64).reshape(-1)
+    idn = np.ascontiguousarray(identifiers, dtype=np.uint64).reshape(-1, 4)
+    sec = np.ascontiguousarray(secrets, dtype=np.uint64).reshape(-1, 4)
+    k = li.shape[0]
+    assert am.shape[0] == k and idn.shape[0] == k and sec.shape[0] == k
+    L.zkt_notes_write_file.argtypes = [ctypes.c_char_p, ctypes.c_int, P64, P64, P64, P64, ctypes.c_size_t]
+    p = lambda a: u64p(a) if a.size else None
+    _writer_check(L.zkt_notes_write_file(path.encode(), curve_id(curve), p(li), p(idn), p(am), p(sec), k), "zkt_notes_write_file(%s)" % path)
+
+
+def notes_read_file(path: str, curve):
+    """zkt_notes_read_file, both calls -> (leaf_indices (k,), identifiers (k, 4), amounts (k,), secrets (k, 4))."""
+    L = lib()
+    P64 = ctypes.POINTER(ctypes.c_uint64)
+    L.zkt_notes_read_file.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_size_t, P64, P64, P64, P64, ctypes.POINTER(ctypes.c_size_t)]
+    k = ctypes.c_size_t(0)
+    _writer_check(L.zkt_notes_read_file(path.encode(), curve_id(curve), 0, None, None, None, None, ctypes.byref(k)), "zkt_notes_read_file(%s)" % path)
+    n = max(k.value, 1)
+    li, am = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+    idn, sec = np.zeros((n, 4), dtype=np.uint64), np.zeros((n, 4), dtype=np.uint64)
+    _writer_check(L.zkt_notes_read_file(path.encode(), curve_id(curve), n, u64p(li), u64p(idn), u64p(am), u64p(sec), ctypes.byref(k)),
+                  "zkt_notes_read_file(%s)" % path)
+    return li[:k.value], idn[:k.value], am[:k.value], sec[:k.value]
+
+
+class TreeFileReport(ctypes.Structure):
+    """zkt_tree_file_report"""
+    _fields_ = [("entries", ctypes.c_uint64), ("mismatches", ctypes.c_uint64), ("first_layer", ctypes.c_int), ("first_idx", ctypes.c_uint64),
+                ("root_matches", ctypes.c_int)]
+
+
 def keyfile_write_committer_key(path: str, curve, powers):
     """zkt_keyfile_write_committer_key: (count, 2*fq_limbs) Montgomery limbs -> the --ck file; an all-zero point is the
     identity (host only)."""
@@ -657,6 +694,39 @@ class WithdrawRequest(ctypes.Structure):
     """zkt_withdraw_request"""
     _fields_ = [(k, ctypes.POINTER(ctypes.c_uint64)) for k in ("secrets", "identifiers", "amounts", "leaf_indices", "siblings", "root",
                                                                "new_secret", "new_identifier")] + [("withdraw_amount", ctypes.c_uint64)]
+
+
+class WithdrawProveArgs(ctypes.Structure):
+    """zkt_withdraw_prove_args"""
+    _fields_ = [("transcript_kind", ctypes.c_int), ("label", ctypes.c_char_p),
+                ("identifiers_set", ctypes.POINTER(ctypes.c_uint64)), ("set_len", ctypes.c_size_t),
+                ("blinders", ctypes.POINTER(ctypes.c_uint64)),
+                ("verify", ctypes.c_int),
+                ("g_xy_mont", ctypes.POINTER(ctypes.c_uint64)), ("h_g2_mont", ctypes.POINTER(ctypes.c_uint64)),
+                ("beta_h_g2_mont", ctypes.POINTER(ctypes.c_uint64)),
+                ("append", ctypes.c_int),
+                ("d_variables", ctypes.c_void_p), ("stride", ctypes.c_size_t), ("slots", ctypes.c_size_t)]
+
+
+class WithdrawResult(ctypes.Structure):
+    """zkt_withdraw_result"""
+    _fields_ = [("code", ctypes.c_int), ("bad_paths", ctypes.c_uint32), ("verified", ctypes.c_int), ("new_leaf_index", ctypes.c_uint64)]
+
+
+def _withdraw_requests(requests):
+    """zkt_withdraw_request[] from request dictionaries -> (the array, the numpy arrays it points into)."""
+    keep, reqs = [], (WithdrawRequest * max(1, len(requests)))()
+    null = ctypes.POINTER(ctypes.c_uint64)()
+    for r, q in zip(reqs, requests):
+        for k in ("secrets", "identifiers", "amounts", "leaf_indices", "siblings", "root", "new_secret", "new_identifier"):
+            if q.get(k) is None:
+                setattr(r, k, null)
+            else:
+                a = np.ascontiguousarray(q[k], dtype=np.uint64).reshape(-1)
+                keep.append(a)
+                setattr(r, k, u64p(a))
+        r.withdraw_amount = int(q["withdraw_amount"])
+    return reqs, keep
 
 
 def _withdraw_row_buffers(n_gates, rows, wires):
@@ -1294,6 +1364,29 @@ class Context:
         L.zkt_merkle_tree_free.restype = None
         L.zkt_merkle_tree_free(self._h, ctypes.c_void_p(tree))
 
+    def merkle_tree_save_file(self, tree: int, path: str):
+        """zkt_merkle_tree_save_file: the tree as the reference CLI's --merkle-tree file."""
+        L, vp = self._L, ctypes.c_void_p
+        L.zkt_merkle_tree_save_file.argtypes = [vp, vp, ctypes.c_char_p]
+        self.check(L.zkt_merkle_tree_save_file(self._h, vp(tree), path.encode()))
+
+    def merkle_tree_load_file(self, poseidon: int, height: int, capacity: int, path: str):
+        """zkt_merkle_tree_load_file -> (tree handle, report dict): the tree rebuilt from the file's leaves, and how the file's
+        other nodes and root compare with it."""
+        L, vp = self._L, ctypes.c_void_p
+        L.zkt_merkle_tree_load_file.argtypes = [vp, vp, ctypes.c_int, ctypes.c_size_t, ctypes.c_char_p, ctypes.POINTER(vp),
+                                                ctypes.POINTER(TreeFileReport)]
+        out, rep = vp(0), TreeFileReport()
+        self.check(L.zkt_merkle_tree_load_file(self._h, vp(poseidon), height, capacity, path.encode(), ctypes.byref(out), ctypes.byref(rep)))
+        return out.value, {"entries": rep.entries, "mismatches": rep.mismatches, "first_layer": rep.first_layer, "first_idx": rep.first_idx,
+                           "root_matches": bool(rep.root_matches)}
+
+    def debug_store_chunk(self, nodes: int):
+        """zkt_debug_store_chunk: nodes per staging chunk of the tree-file calls on this context (0 = the default)."""
+        L = self._L
+        L.zkt_debug_store_chunk.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
+        self.check(L.zkt_debug_store_chunk(self._h, nodes))
+
     def merkle_tree_append_dev(self, tree: int, d_leaves: int, m: int) -> int:
         """zkt_merkle_tree_append_dev: add_leaf for m device scalars, enqueue only -> index of the first."""
         L, vp = self._L, ctypes.c_void_p
@@ -1468,6 +1561,36 @@ class Context:
         if rc:
             raise ZktError(rc, "zkt_withdraw_prove_inputs: null pointer or stride below n_vars")
         return prep
+
+    def withdraw_prove(self, w: int, requests, d_variables: int, stride: int, slots: int, identifiers_set, blinders, tree: int = 0,
+                       transcript_kind: str = "merlin", label: str = "ZKT Plonk", verify_key=None, append: bool = False):
+        """zkt_withdraw_prove: ProveWithdraw for every request in one call.  requests as withdraw_witness takes them;
+        identifiers_set (k, 4) and blinders (batch, 19, 4) Montgomery words; verify_key = (g, h, beta_h) to have each proof
+        checked; `slots` maps of `stride` scalars at d_variables.  -> ([proof bytes], public inputs (batch, n_pi, 4),
+        [{code, bad_paths, verified, new_leaf_index}]); a proof that was not made is b""."""
+        L, vp = self._L, ctypes.c_void_p
+        P64 = ctypes.POINTER(ctypes.c_uint64)
+        batch = len(requests)
+        reqs, keep = _withdraw_requests(requests)
+        ids = np.ascontiguousarray(identifiers_set, dtype=np.uint64).reshape(-1, 4)
+        bl = np.ascontiguousarray(blinders, dtype=np.uint64).reshape(-1)
+        assert bl.size == batch * 19 * 4
+        vk = [np.ascontiguousarray(x, dtype=np.uint64).reshape(-1) for x in verify_key] if verify_key is not None else None
+        args = WithdrawProveArgs(0 if transcript_kind == "merlin" else 1 if transcript_kind == "ethereum" else int(transcript_kind), label.encode(),
+                                 u64p(ids) if ids.size else P64(), ids.shape[0], u64p(bl) if bl.size else P64(), int(vk is not None),
+                                 u64p(vk[0]) if vk else P64(), u64p(vk[1]) if vk else P64(), u64p(vk[2]) if vk else P64(), int(bool(append)),
+                                 d_variables or None, stride, slots)
+        n_pi = self.withdraw_get_info(w)["n_pi"]
+        plen = 802 if self.curve == CURVE_BN254 else 1010
+        proofs = np.zeros((max(batch, 1), plen), dtype=np.uint8)
+        pi = np.zeros((batch, n_pi, 4), dtype=np.uint64)
+        res = (WithdrawResult * max(batch, 1))()
+        L.zkt_withdraw_prove.argtypes = [vp, vp, ctypes.POINTER(WithdrawRequest), ctypes.c_size_t, vp, ctypes.POINTER(WithdrawProveArgs),
+                                         ctypes.POINTER(ctypes.c_uint8), ctypes.c_size_t, P64, ctypes.POINTER(WithdrawResult)]
+        self.check(L.zkt_withdraw_prove(self._h, vp(w), reqs, batch, vp(tree) if tree else None, ctypes.byref(args),
+                                        proofs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), plen, u64p(pi) if pi.size else P64(), res))
+        out = [dict(code=r.code, bad_paths=r.bad_paths, verified=bool(r.verified), new_leaf_index=r.new_leaf_index) for r in res[:batch]]
+        return [proofs[b].tobytes() if out[b]["code"] == 0 else b"" for b in range(batch)], pi, out
 
     def note_leaves(self, poseidon_handle: int, d_secrets: int, d_identifiers: int, d_amounts: int, m: int, d_out_leaves: int):
         """zkt_note_leaves: leaf = H(identifier, amount, H(secret)) for m deposits, device pointers; synchronises."""

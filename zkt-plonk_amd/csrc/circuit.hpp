@@ -114,6 +114,14 @@ struct CircuitState : CircuitKeys, ClassTables {
     void* d_win = nullptr;          // QC_WIN_POLYS windows (a b c z1 z2 t), gathered in round 3 ...
     void* pinned_win = nullptr;     // ... and copied here behind them
     hipEvent_t ev_win = nullptr;
+    // zkt_withdraw_prove: the VerifierKey's commitments of this circuit under the SRS of generation vk_srs_generation, as every
+    // transcript is seeded from them (kept by zkt_withdraw_setup, else made by the first zkt_withdraw_prove under this circuit),
+    // and the table size zkt_withdraw_setup masked q_table for (0: unknown, the circuit was loaded another way)
+    bool vk_cached = false;
+    uint64_t vk_srs_generation = 0;
+    uint64_t vk_commits[10 * 12] = {};
+    int vk_inf[10] = {};
+    size_t vk_table_size = 0;
     uint32_t last_u[6][8] = {};     // zkt_debug_quotient_top
     bool last_u_valid = false;
 };

@@ -96,6 +96,7 @@ struct zkt_ctx {
     std::shared_ptr<zkt::MsmBasesState> msmb;   // zkt_msm_g1_bases scratch (separate from the prover's MSM state)
     std::shared_ptr<zkt::KzgState> kzg;         // KZG seam scratch: copy stream, open buffers (never forked)
     size_t srs_check_chunk = 0;                 // zkt_debug_srs_check_chunk: points per chunk of zkt_srs_check, 0 = ZKT_MSM_BASES_MAX
+    size_t store_chunk = 0;                     // zkt_debug_store_chunk: nodes per staging chunk of the tree-file entries, 0 = the default
     uint64_t msm_epoch = 0;   // bumped by every MSM enqueue and SRS (re)load: work issued ahead of time is tied to it
     uint64_t srs_generation = 0;   // bumped by every SRS (re)load: cached commitments are tied to the key they were made under
     bool is_fork = false;     // made by zkt_ctx_fork: no forced NTT split, no communicator

@@ -285,6 +285,11 @@ int keyfile_write_done(zkt_ctx* c, kw::File& w) {
     keyfile_err = w.error();
     return set_err(c, ZKT_ERR_INVALID_ARGUMENT, keyfile_err);   // as the readers answer a file they cannot read
 }
+int keyfile_refused(zkt_ctx* c, const std::string& why) {
+    keyfile_err = why;
+    return c ? set_err(c, ZKT_ERR_INVALID_ARGUMENT, why) : ZKT_ERR_INVALID_ARGUMENT;
+}
+void keyfile_clear_error() { keyfile_err.clear(); }
 static int keyfile_refuse(const char* why) {
     keyfile_err = why;
     return ZKT_ERR_INVALID_ARGUMENT;

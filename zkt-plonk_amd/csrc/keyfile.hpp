@@ -4,6 +4,7 @@
 #pragma once
 #include <cstdint>
 #include <cstdio>
+#include <string>
 
 struct zkt_ctx;
 
@@ -13,6 +14,10 @@ namespace kw { class File; }   // keyfile_write.hpp
 // ends a written key file: the rename into place, or the error (its text names the path) for zkt_keyfile_last_error and
 // for `c` when there is one
 int keyfile_write_done(zkt_ctx* c, kw::File& w);
+// a file that a reader refuses: `why` (it names the path) kept in the same two places; ZKT_ERR_INVALID_ARGUMENT
+int keyfile_refused(zkt_ctx* c, const std::string& why);
+// a reader's success: the thread's last error is empty again, as after a writer's
+void keyfile_clear_error();
 
 // arith { q_m_coset q_l_coset q_r_coset q_o_coset q_c_coset } (keys/arithmetic.rs:51-62), lookup { q_lookup q_lookup_coset
 // q_table_coset } (keys/lookup.rs:70-77), perm { sigma1 sigma1_coset sigma2 sigma2_coset sigma3 sigma3_coset x_coset }

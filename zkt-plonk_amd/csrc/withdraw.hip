@@ -2,12 +2,17 @@
 // from (Poseidon parameters, INPUTS, HEIGHT), its setup, and the whole variable map and public inputs of a batch of
 // withdrawals made on the device from the notes themselves.  The planner is host code (withdraw_layout.hpp); the hash
 // traces, the Merkle paths and the note tree are the existing entry points of poseidon.hip, called as any caller would.
+#include "circuit.hpp"
 #include "ctx.hpp"
 #include "hostinv.hpp"
+#include "merkle_tree.hpp"
 #include "withdraw_layout.hpp"
 
 #include <algorithm>
+#include <array>
 #include <cstring>
+#include <map>
+#include <memory>
 #include <vector>
 
 namespace zkt {
@@ -241,6 +246,22 @@ __global__ __launch_bounds__(256) void k_note_leaf_inputs(const Fe<P>* ident, co
     fe_store<P>(out + 3 * t + 2, fe_load<P>(commitment + t));
 }
 
+// The new leaves of the requests a chunk of zkt_withdraw_prove takes into the tree: slot b of the chunk's maps is taken when
+// bit b of `mask` is set (256 slots: ZKT_WITNESS_BATCH_MAX), and lands behind the taken slots below it.
+struct WdSlotMask {
+    uint64_t w[4];
+};
+template <class P>
+__global__ __launch_bounds__(256) void k_withdraw_new_leaves(const Fe<P>* vars, uint64_t stride, uint32_t leaf_var, WdSlotMask mask, uint32_t slots,
+                                                              Fe<P>* out) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= slots || !((mask.w[b >> 6] >> (b & 63)) & 1)) return;
+    uint32_t at = 0;
+    for (uint32_t k = 0; k < (b >> 6); ++k) at += __popcll(mask.w[k]);
+    at += __popcll(mask.w[b >> 6] & (((uint64_t)1 << (b & 63)) - 1));
+    fe_store<P>(out + at, fe_load<P>(vars + (size_t)b * stride + leaf_var));
+}
+
 }  // namespace zkt
 
 // the opaque handle of include/zkt_plonk.h
@@ -270,6 +291,7 @@ struct zkt_withdraw {
     bool stage_busy = false;
     void* d_pi = nullptr;                // batch x n_pi
     uint32_t* d_status = nullptr;        // batch
+    void* d_new_leaves = nullptr;        // zkt_withdraw_prove: the leaves of one call's append, ZKT_WITHDRAW_PROVE_MAX scalars
 };
 
 namespace zkt {
@@ -425,6 +447,7 @@ static int wd_create_t(zkt_ctx* c, const zkt_poseidon_params* p, zkt_withdraw* w
     if ((rc = w->set.event(c, &w->staged))) return rc;
     if ((rc = alloc(&w->d_pi, B * s.n_pi * 32))) return rc;
     if ((rc = alloc((void**)&w->d_status, B * 4))) return rc;
+    if ((rc = alloc(&w->d_new_leaves, (size_t)ZKT_WITHDRAW_PROVE_MAX * 32))) return rc;
     {
         ProfScope ps(c, "withdraw_layout");
         if ((rc = wd_rows_enqueue_t<P>(c, w, nullptr, w->d_w))) return rc;
@@ -440,15 +463,14 @@ static int wd_check(zkt_ctx* c, const zkt_withdraw* w) {
     return ZKT_OK;
 }
 
+// Everything zkt_withdraw_witness can refuse on the host, for `batch` requests, before anything is enqueued.  amount_out:
+// batch words, the sums less the withdrawn amounts (may be null).
 template <class P>
-static int wd_witness_t(zkt_ctx* c, zkt_withdraw* w, const zkt_withdraw_request* reqs, size_t batch, zkt_merkle_tree* tree, void* d_variables,
-                        size_t stride, uint64_t* out_pi, zkt_withdraw_status* out_status) {
+static int wd_validate_t(zkt_ctx* c, const zkt_withdraw* w, const zkt_withdraw_request* reqs, size_t batch, zkt_merkle_tree* tree,
+                         uint64_t* amount_out, bool& any_sib, bool& any_tree, bool& tree_root) {
     const wd::Shape& s = w->plan.s;
     const size_t I = (size_t)s.inputs, H = (size_t)s.height;
-    const size_t FA = wd_stage_fe(s), UA = wd_stage_u(s), SA = wd_stage_sib(s);
-    // ---- everything that can be refused, before anything is enqueued ----
-    bool any_sib = false, any_tree = false, tree_root = false;
-    std::vector<uint64_t> amount_out(batch);
+    any_sib = any_tree = tree_root = false;
     for (size_t b = 0; b < batch; ++b) {
         const zkt_withdraw_request& r = reqs[b];
         if (!r.secrets || !r.identifiers || !r.amounts || !r.leaf_indices || !r.new_secret || !r.new_identifier)
@@ -460,7 +482,7 @@ static int wd_witness_t(zkt_ctx* c, zkt_withdraw* w, const zkt_withdraw_request*
             if (H < 64 && (r.leaf_indices[k] >> H)) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "withdraw: a leaf index is not below 2^height");
         }
         if (r.withdraw_amount > sum) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "withdraw: invalid withdraw amount (withdraw.rs:59)");
-        amount_out[b] = sum - r.withdraw_amount;
+        if (amount_out) amount_out[b] = sum - r.withdraw_amount;
         for (size_t k = 0; k < I; ++k) {
             Fe<P> x;
             memcpy((void*)&x, r.secrets + 4 * k, 32);
@@ -475,6 +497,19 @@ static int wd_witness_t(zkt_ctx* c, zkt_withdraw* w, const zkt_withdraw_request*
         if (zkt_merkle_tree_info(tree, &th, nullptr, nullptr) || th != s.height)
             return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "withdraw: the tree has another height");
     }
+    return ZKT_OK;
+}
+
+template <class P>
+static int wd_witness_t(zkt_ctx* c, zkt_withdraw* w, const zkt_withdraw_request* reqs, size_t batch, zkt_merkle_tree* tree, void* d_variables,
+                        size_t stride, uint64_t* out_pi, zkt_withdraw_status* out_status) {
+    const wd::Shape& s = w->plan.s;
+    const size_t I = (size_t)s.inputs, H = (size_t)s.height;
+    const size_t FA = wd_stage_fe(s), UA = wd_stage_u(s), SA = wd_stage_sib(s);
+    // ---- everything that can be refused, before anything is enqueued ----
+    bool any_sib = false, any_tree = false, tree_root = false;
+    std::vector<uint64_t> amount_out(batch);
+    if (int rc = wd_validate_t<P>(c, w, reqs, batch, tree, amount_out.data(), any_sib, any_tree, tree_root)) return rc;
     Fe<P> troot = fe_zero<P>();
     if (tree_root)
         if (int rc = zkt_merkle_tree_root(c, tree, (uint64_t*)&troot)) return rc;
@@ -607,6 +642,36 @@ static int note_leaves_t(zkt_ctx* c, const zkt_poseidon* pos, const void* d_secr
                        (const uint64_t*)d_amounts, (const Fe<P>*)d_out, (Fe<P>*)d_tmp, (uint64_t)m);
     ZKT_HIP(c, hipGetLastError());
     return zkt_poseidon_hash_batch_dev(c, pos, d_tmp, m, 3, d_out, nullptr);
+}
+
+// ---- ProveWithdraw in one call ---------------------------------------------------------------------------------------------
+// the codes with which zkt_prove refuses ONE proof (its witness or its challenges), as opposed to a failure of the call
+static bool wd_is_proof_refusal(int rc) {
+    return rc == ZKT_ERR_NOT_IN_TABLE || rc == ZKT_ERR_EQUAL_CHALLENGES || rc == ZKT_ERR_ZERO_DENOMINATOR || rc == ZKT_ERR_QUOTIENT_TOO_SHORT;
+}
+
+// the loaded circuit's commitments as the transcripts are seeded from them: canonical little-endian bytes and flags
+template <class C>
+static void wd_seed_bytes(const CircuitState* S, uint8_t* xy_le, uint8_t* inf) {
+    using Q = typename C::Fq;
+    for (int k = 0; k < 10; ++k) {
+        Fe<Q> x, y;
+        memcpy(x.v, S->vk_commits + (size_t)k * Q::N, Q::N * 4);
+        memcpy(y.v, S->vk_commits + (size_t)k * Q::N + Q::N / 2, Q::N * 4);
+        fq_to_le<Q>(x, xy_le + (size_t)k * 2 * Q::N * 4);
+        fq_to_le<Q>(y, xy_le + ((size_t)k * 2 + 1) * Q::N * 4);
+        inf[k] = S->vk_inf[k] ? 1 : 0;
+    }
+}
+
+// VerifierKey::pi_roots: w^pos for the circuit's public-input rows
+template <class R>
+static void wd_pi_roots(int log_n, const std::vector<size_t>& pi_pos, uint64_t* out) {
+    const Fe<R> w = root_of_unity<R>(log_n);
+    for (size_t i = 0; i < pi_pos.size(); ++i) {
+        const Fe<R> r = fe_pow_u64<R>(w, (uint64_t)pi_pos[i]);
+        memcpy(out + 4 * i, r.v, 32);
+    }
 }
 
 }  // namespace zkt
@@ -743,6 +808,17 @@ int zkt_withdraw_setup(zkt_ctx* c, const zkt_withdraw* w, int log_n, size_t tabl
     };
     const int rc = run();
     (void)hipStreamSynchronize(c->stream);   // before `tmp` goes
+    if (!rc) {   // what zkt_withdraw_prove seeds its transcripts from, and the table size q_table was masked for: kept with the circuit
+        CircuitState* S = c->circuit.get();
+        const size_t words = c->curve == ZKT_CURVE_BN254 ? 8 : 12;
+        memcpy(S->vk_commits, out_commitments, 10 * words * 8);
+        for (int k = 0; k < 10; ++k)   // the identity comes back as (0, 0) with its flag; the flags are optional for the caller
+            S->vk_inf[k] = out_is_infinity ? out_is_infinity[k]
+                                           : std::all_of(out_commitments + k * words, out_commitments + (k + 1) * words, [](uint64_t x) { return x == 0; });
+        S->vk_srs_generation = c->srs_generation;
+        S->vk_table_size = table_size;
+        S->vk_cached = true;
+    }
     return rc;
 }
 
@@ -772,6 +848,172 @@ int zkt_withdraw_prove_inputs(const zkt_withdraw* w, const void* d_variables, si
     out->w_l = w->d_w[0];
     out->w_r = w->d_w[1];
     out->w_o = w->d_w[2];
+    return ZKT_OK;
+}
+
+int zkt_withdraw_prove(zkt_ctx* c, zkt_withdraw* w, const zkt_withdraw_request* reqs, size_t batch, zkt_merkle_tree* tree,
+                       const zkt_withdraw_prove_args* a, uint8_t* proofs, size_t proof_stride, uint64_t* out_pi, zkt_withdraw_result* results) {
+    if (int rc = wd_check(c, w)) return rc;
+    if (!reqs || !a || !proofs || !results || !a->d_variables || !a->blinders || (a->set_len && !a->identifiers_set))
+        return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "null pointer");
+    if (a->verify && (!a->g_xy_mont || !a->h_g2_mont || !a->beta_h_g2_mont))
+        return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "withdraw prove: verify needs g, h and beta h");
+    const wd::Shape& s = w->plan.s;
+    const size_t n_pi = s.n_pi, proof_len = c->curve == ZKT_CURVE_BN254 ? 802 : 1010;
+    if (batch < 1 || batch > ZKT_WITHDRAW_PROVE_MAX) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "withdraw prove: 1 <= batch <= ZKT_WITHDRAW_PROVE_MAX");
+    if (a->slots < 1 || a->slots > ZKT_WITNESS_BATCH_MAX) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "withdraw prove: 1 <= slots <= ZKT_WITNESS_BATCH_MAX");
+    if (a->stride < s.n_vars) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "withdraw: stride below n_vars");
+    if (a->stride > 0xFFFFFFFEull / a->slots) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "withdraw: slots x stride must fit 32-bit variable indices");
+    if (proof_stride < proof_len) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "withdraw prove: proof_stride below the proof's length");
+    if (a->transcript_kind != ZKT_TRANSCRIPT_MERLIN && a->transcript_kind != ZKT_TRANSCRIPT_ETHEREUM)
+        return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "withdraw prove: unknown transcript kind");
+    if (tree && tree->curve != c->curve) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "withdraw prove: the tree belongs to another curve");
+    if (int rc = circuit_entry(c, ENTRY_SRS | ENTRY_DEVICE)) return rc;
+    (void)zkt_prove_set_next(c, nullptr);   // the chain below is the only one
+    const std::shared_ptr<CircuitState> circuit = c->circuit;
+    const uint64_t n = circuit->n;
+    CircuitState* S = circuit.get();
+
+    // the identifiers set as a LookupTable: the first of equal values stays
+    std::vector<uint64_t> table;
+    {
+        std::map<std::array<uint64_t, 4>, bool> seen;
+        for (size_t i = 0; i < a->set_len; ++i) {
+            std::array<uint64_t, 4> v;
+            memcpy(v.data(), a->identifiers_set + 4 * i, 32);
+            if (seen.emplace(v, true).second) table.insert(table.end(), v.begin(), v.end());
+        }
+    }
+    const size_t table_len = table.size() / 4, table_max = S->vk_table_size ? S->vk_table_size : (size_t)n - 1;
+    if (table_len > table_max) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "withdraw prove: table size exceeds max size (lookup/table.rs:57)");
+    {
+        bool any_sib, any_tree, tree_root;
+        const int rc = c->curve == ZKT_CURVE_BN254 ? wd_validate_t<Bn254Fr>(c, w, reqs, batch, tree, nullptr, any_sib, any_tree, tree_root)
+                                                   : wd_validate_t<Bls381Fr>(c, w, reqs, batch, tree, nullptr, any_sib, any_tree, tree_root);
+        if (rc) return rc;
+    }
+    if (a->append) {
+        int th = 0;
+        uint64_t count = 0, capacity = 0;
+        if (!tree || zkt_merkle_tree_info(tree, &th, &count, &capacity) || th != s.height)
+            return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "withdraw prove: append needs a tree of the circuit's height");
+        if (batch > capacity - count) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "withdraw prove: the tree has no room for `batch` more leaves");
+    }
+    // the commitments of a circuit that zkt_withdraw_setup did not make, or under another SRS than it had: once
+    if (!S->vk_cached || S->vk_srs_generation != c->srs_generation) {
+        S->vk_cached = false;
+        if (int rc = zkt_circuit_commitments(c, S->vk_commits, S->vk_inf)) return rc;
+        S->vk_srs_generation = c->srs_generation;
+        S->vk_cached = true;
+    }
+    const size_t fq_bytes = c->curve == ZKT_CURVE_BN254 ? 32 : 48;
+    uint8_t seed_xy[10 * 2 * 48], seed_inf[10];
+    if (c->curve == ZKT_CURVE_BN254) wd_seed_bytes<Bn254Curve>(S, seed_xy, seed_inf);
+    else wd_seed_bytes<Bls381Curve>(S, seed_xy, seed_inf);
+    auto transcript = [&]() {
+        zkt_transcript* t = zkt_transcript_new(a->transcript_kind, a->label);
+        if (t) zkt_transcript_seed(t, n, seed_xy, seed_inf, fq_bytes);
+        return t;
+    };
+    std::vector<uint64_t> pi_roots(a->verify ? 4 * n_pi : 0), pi_own(out_pi ? 0 : batch * n_pi * 4);
+    if (a->verify) {
+        if (c->curve == ZKT_CURVE_BN254) wd_pi_roots<Bn254Fr>(circuit->log_n, w->plan.pi_pos, pi_roots.data());
+        else wd_pi_roots<Bls381Fr>(circuit->log_n, w->plan.pi_pos, pi_roots.data());
+    }
+    uint64_t* pi = out_pi ? out_pi : pi_own.data();
+    for (size_t b = 0; b < batch; ++b) results[b] = zkt_withdraw_result{ZKT_OK, 0, 0, UINT64_MAX};
+    const uint32_t leaf_var = s.new_leaf_base() + s.hash_off;
+
+    std::vector<size_t> taken;   // the requests whose leaves wait in d_new_leaves, in order
+    auto run = [&]() -> int {
+        std::vector<zkt_prove_inputs> ins(a->slots);
+        std::vector<uint32_t> status(a->slots);
+        for (size_t base = 0; base < batch; base += a->slots) {
+            const size_t cnt = std::min(a->slots, batch - base);
+            if (int rc = zkt_withdraw_witness(c, w, reqs + base, cnt, tree, a->d_variables, a->stride, pi + base * n_pi * 4,
+                                              (zkt_withdraw_status*)status.data()))
+                return rc;
+            std::vector<size_t> good;
+            for (size_t b = 0; b < cnt; ++b) {
+                zkt_withdraw_result& r = results[base + b];
+                memset(proofs + (base + b) * proof_stride, 0, proof_len);
+                r.bad_paths = status[b];
+                if (status[b]) {
+                    r.code = ZKT_ERR_INVALID_ARGUMENT;
+                    continue;
+                }
+                zkt_withdraw_prove_inputs(w, a->d_variables, a->stride, b, w->plan.pi_pos.data(), pi + (base + b) * n_pi * 4, &ins[b]);
+                ins[b].table = table.data();
+                ins[b].table_len = table_len;
+                ins[b].blinders = a->blinders + (base + b) * 19 * 4;
+                good.push_back(b);
+            }
+            WdSlotMask mask{};
+            size_t n_taken = 0;
+            for (size_t k = 0; k < good.size(); ++k) {
+                const size_t b = good[k];
+                zkt_withdraw_result& r = results[base + b];
+                uint8_t* proof = proofs + (base + b) * proof_stride;
+                if (int rc = zkt_prove_set_next(c, k + 1 < good.size() ? &ins[good[k + 1]] : nullptr)) return rc;
+                zkt_transcript* t = transcript();
+                if (!t) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "withdraw prove: the transcript could not be made");
+                size_t len = 0;
+                const int rc = zkt_prove(c, &ins[b], t, proof, proof_len, &len);
+                zkt_transcript_free(t);
+                if (rc) {
+                    if (!wd_is_proof_refusal(rc)) return rc;
+                    memset(proof, 0, proof_len);
+                    r.code = rc;
+                    continue;
+                }
+                if (a->verify) {
+                    zkt_verify_inputs v{};
+                    v.n = n;
+                    v.vk_commitments = S->vk_commits;
+                    v.vk_is_infinity = S->vk_inf;
+                    v.pi_roots = pi_roots.data();
+                    v.pub_inputs = ins[b].pi_vals;
+                    v.n_pi = n_pi;
+                    v.proof = proof;
+                    v.proof_len = len;
+                    v.g = a->g_xy_mont;
+                    int accepted = 0;
+                    zkt_transcript* tv = transcript();
+                    if (!tv) return set_err(c, ZKT_ERR_INVALID_ARGUMENT, "withdraw prove: the transcript could not be made");
+                    const int vrc = zkt_verify(c->curve, &v, tv, a->h_g2_mont, a->beta_h_g2_mont, &accepted);
+                    zkt_transcript_free(tv);
+                    r.verified = !vrc && accepted ? 1 : 0;
+                    if (!r.verified) continue;
+                }
+                if (a->append) {
+                    mask.w[b >> 6] |= (uint64_t)1 << (b & 63);
+                    taken.push_back(base + b);
+                    ++n_taken;
+                }
+            }
+            if (n_taken) {   // this chunk's leaves leave the maps before the next chunk's witness overwrites them
+                void* out = (char*)w->d_new_leaves + (taken.size() - n_taken) * 32;
+                if (c->curve == ZKT_CURVE_BN254)
+                    hipLaunchKernelGGL((k_withdraw_new_leaves<Bn254Fr>), dim3(1), dim3(256), 0, c->stream, (const Fe<Bn254Fr>*)a->d_variables,
+                                       (uint64_t)a->stride, leaf_var, mask, (uint32_t)cnt, (Fe<Bn254Fr>*)out);
+                else
+                    hipLaunchKernelGGL((k_withdraw_new_leaves<Bls381Fr>), dim3(1), dim3(256), 0, c->stream, (const Fe<Bls381Fr>*)a->d_variables,
+                                       (uint64_t)a->stride, leaf_var, mask, (uint32_t)cnt, (Fe<Bls381Fr>*)out);
+                ZKT_HIP(c, hipGetLastError());
+            }
+        }
+        if (!taken.empty()) {
+            uint64_t first = 0;
+            if (int rc = zkt_merkle_tree_append_dev(c, tree, w->d_new_leaves, taken.size(), &first)) return rc;
+            for (size_t k = 0; k < taken.size(); ++k) results[taken[k]].new_leaf_index = first + k;
+        }
+        return ZKT_OK;
+    };
+    const int rc = run();
+    (void)zkt_prove_set_next(c, nullptr);
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    if (rc) return rc;
+    ZKT_HIP(c, e);
     return ZKT_OK;
 }
 

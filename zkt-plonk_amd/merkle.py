@@ -22,6 +22,19 @@ class MerkleTree:
         self.ctx, self.height, self.capacity = ctx, height, capacity
         self._t = ctx.merkle_tree_create(poseidon_handle, height, capacity)
 
+    @classmethod
+    def load_file(cls, ctx: Context, poseidon_handle: int, height: int, capacity: int, path: str):
+        """zkt_merkle_tree_load_file: a reference --merkle-tree file -> (the tree rebuilt from its leaves, the report on how
+        the file's other nodes and root compare with it: entries, mismatches, first_layer, first_idx, root_matches)."""
+        t = cls.__new__(cls)
+        t.ctx, t.height, t.capacity = ctx, height, capacity
+        t._t, report = ctx.merkle_tree_load_file(poseidon_handle, height, capacity, path)
+        return t, report
+
+    def save_file(self, path: str):
+        """zkt_merkle_tree_save_file: the tree as the reference CLI's --merkle-tree file (MerkleTreeStore)."""
+        self.ctx.merkle_tree_save_file(self._t, path)
+
     def close(self):
         if self._t:
             self.ctx.merkle_tree_free(self._t)

@@ -54,6 +54,14 @@ class WithdrawCircuit:
         return self.ctx.withdraw_witness(self._w, requests, d_variables, self.n_vars if stride is None else stride,
                                          tree.handle if tree is not None else 0, want_pi, want_status)
 
+    def prove(self, requests: Sequence[dict], d_variables: int, slots: int, identifiers_set, blinders, stride: Optional[int] = None, tree=None,
+              transcript_kind: str = "merlin", label: str = "ZKT Plonk", verify_key=None, append: bool = False):
+        """zkt_withdraw_prove, the CLI's ProveWithdraw for every request in one call: witness, proof, the CLI's own check of
+        the proof (verify_key = (g, h, beta_h)) and the new leaves appended to `tree` -> ([proof bytes], public inputs
+        (batch, n_pi, 4), [{code, bad_paths, verified, new_leaf_index}]).  d_variables: `slots` maps, `stride` scalars apart."""
+        return self.ctx.withdraw_prove(self._w, requests, d_variables, self.n_vars if stride is None else stride, slots, identifiers_set,
+                                       blinders, tree.handle if tree is not None else 0, transcript_kind, label, verify_key, append)
+
     def prepare(self, d_variables: int, stride: int, b: int, table, pi_vals, blinders):
         """zkt_prove_inputs of request b over the device wiring, for Context.prove_prepared / check_witness."""
         return self.ctx.withdraw_prepare(self._w, d_variables, stride, b, table, np.asarray(pi_vals, dtype=np.uint64), blinders)
